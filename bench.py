@@ -7,8 +7,12 @@ deblock -> SAO -> border padding; key pictures: intra mode pre-selection + wavef
 HBM.  Each rank (one per GPU) encodes --streams (default 3) independent GOP shards, each on its own HIP stream: GOPs are
 independent units (frames/GOPs shard, no data-path collective) and the search kernels are latency bound, so the
 kernels of different shards overlap (+53 % pictures/s over one stream on a whole -iper 128 GOP: the intra wavefront of a key
-picture keeps only 34 of 256 CUs busy and runs underneath the other shards' P pictures).  Weak scaling; value = pictures of all ranks / max-over-ranks time.  Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, HIP-event timed) and
-`cpu_baseline` (the CPU oracle port on a bounded sample).
+picture keeps only 34 of 256 CUs busy and runs underneath the other shards' P pictures).  Weak scaling; value = pictures of all ranks / max-over-ranks time.  Prints ONE JSON line on rank 0.
+
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline needs: it sets up, warms up, times exactly N steps (one step = one picture through the encoder's
+C API), writes the outputs of the last timed step if `--dump-outputs DIR` is given, and prints the line.  `--full` adds everything else: the IPPP variant beside the
+headline, window B (four whole rounds of GOPs), the device-resident leg with `roofline` (dominant kernel, HIP-event timed) and stage times, and `cpu_baseline` (the
+reference's CLI encoder, else the CPU oracle port, on a bounded sample).
 """
 from __future__ import annotations
 
@@ -90,6 +94,10 @@ def main():
     ap.add_argument("--job-frames", type=int, default=1024, help="--scaling strong: pictures of the fixed job")
     ap.add_argument("--out", default=None, help="--scaling strong: rank 0 writes the gathered Annex-B stream here")
     ap.add_argument("--host-threads", type=int, default=0, help="slice-writer threads of the encoded leg per rank (0 = min(32, host cores / ranks))")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the IPPP variant, window B, the device-resident leg with roofline and "
+                    "stage times, the CPU baseline (a plain run times the --steps pictures of the headline and nothing else)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write what the timed path computed in its last step as DIR/<name>.npy "
+                    "(float32 / float64, at most 64 MB in all); the inputs are the same from run to run for the same arguments")
     args = ap.parse_args()
     # round 5: the headline is the GOP the reference itself codes for `-preset slow -rc 0 -qp 27 -iper 128` = hierarchical-B 8; IPPP (`-bframes 0`) runs beside it
     args.both_gops = args.hier_b < 0 and not args.bframes and args.refs <= 1 and not args.b_spread and args.scaling == "weak"
@@ -147,7 +155,7 @@ def main():
         import copy
         shared_clip = None if args.scaling == "strong" else make_clip(W, H, args.clip_frames, seed=7 + rank, abc=(67, 91, 33), pan=(8, 5))
         encoded = encoded_leg(args, torch, dist, rank, world, dev_index, backend, sync_all, shared_clip)
-        if args.both_gops:
+        if args.both_gops and args.full:
             a2 = copy.copy(args); a2.hier_b = 0; a2.bframes = 0
             e2 = encoded_leg(a2, torch, dist, rank, world, dev_index, backend, sync_all, shared_clip)
             encoded["ippp"] = {"value": round(e2["fps"], 2), "unit": "frames/s", "psnr_y": round(float(e2["psnr_y"]), 3), "bytes_per_picture": int(e2["bytes_per_picture"]),
@@ -169,8 +177,10 @@ def main():
                                                 "work (flush + synchronize on both sides), so it includes starting from and draining to an empty pipeline"}
             except Exception as ex:                               # the opt-in leg must never cost the default line
                 encoded["two_lanes"] = {"error": repr(ex)[:200]}
-        if args.leg == "encoded":
+        if args.leg == "encoded" or not args.full:                 # a plain run: the headline is the encoded leg, nothing else is measured
             if rank == 0:
+                if args.dump_outputs:
+                    write_dumps(args.dump_outputs, encoded["dump"])
                 print(json.dumps(encoded_line(args, encoded, world, None, None)), flush=True)
             if dist is not None:
                 dist.barrier(); dist.destroy_process_group()
@@ -349,6 +359,15 @@ def main():
         dt = time.perf_counter() - t0
         ks.marker(2)
         total_pictures = world * args.steps * nstreams
+    if args.dump_outputs and rank == 0:                  # the last timed step's reconstructed pictures (before the untimed passes below move the shards on)
+        dump = {}
+        for i, sh in enumerate([sh0] if args.b_spread else shards):
+            pic = bout if args.b_spread else sh.state["last"][1]
+            torch.cuda.synchronize()
+            rec = sh.ks.host(sh.fr.store_i420(pic), np.uint8)
+            torch.cuda.synchronize()
+            dump[f"recon_i420_shard{i}"] = rec if i == 0 else rec[:W * H:97]    # shard 0 whole, the others a fixed sample of their luma (64 MB in all)
+        write_dumps(args.dump_outputs, dump)
     if dist is not None:
         tt = torch.tensor([dt], dtype=torch.float64, device=ks.device if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -367,134 +386,136 @@ def main():
         mse = sse / (npic * W * H)
         psnr_y = 99.0 if mse == 0 else 10.0 * np.log10(255.0 ** 2 / mse)
 
-        # ---- per-stage HIP-event timing IN SITU: events recorded on the kernels' own stream between the stages of
-        #      ks265_encode_picture while the real pipeline runs -> roofline of the dominant kernel
-        P = float(W * H)
-        fr.set_profiling(True)
+        roofline, key_ms = None, {}
+        if args.full:                                   # everything below up to the line is --full only
+            # ---- per-stage HIP-event timing IN SITU: events recorded on the kernels' own stream between the stages of
+            #      ks265_encode_picture while the real pipeline runs -> roofline of the dominant kernel
+            P = float(W * H)
+            fr.set_profiling(True)
 
-        probe_out = fr.new_pic()
+            probe_out = fr.new_pic()
 
-        def stage_pass(all_shards):
-            acc, nacc = {}, 0
-            for _ in range(24):
-                (step if all_shards else sh0.step)()
-                if state["kind"] == "Pm":              # multi-reference run: time the stages on an extra single-reference picture (same kernels per launch)
-                    fr.encode_picture(src_of(state["last"][0]), state["ref0"], False, probe_out)
-                elif state["kind"] != "P":             # stage events are recorded by ks265_encode_picture (I / P pictures)
-                    continue
-                ms = fr.stage_ms()
-                ms["me_int_kernel"] = fr.me_int_ms()      # the SAD kernel alone (HIP events around its launch on the frame's stream): stage me_integer also holds pre-search + propagation
-                for k, v in ms.items():
-                    acc[k] = acc.get(k, 0.0) + v
-                nacc += 1
-            torch.cuda.synchronize()
-            return {k: v / nacc for k, v in acc.items()}
-
-        torch.cuda.synchronize()
-        stage_alone = stage_pass(False)                 # shard 0 alone on the GPU: the kernels' own durations (= a --streams 1 run)
-        stage_run = stage_pass(True) if nstreams > 1 else stage_alone   # event-to-event intervals on shard 0's stream while the other shards run
-        # one key picture on its own (not part of the schedule): intra mode pre-selection + wavefront reconstruction + loop filters
-        fr.set_qp(qp, lambda_q4(qp))
-        kout = fr.new_pic()
-        torch.cuda.synchronize()
-        fr.encode_picture(srcs[0], kout, True, kout)
-        torch.cuda.synchronize()
-        key_ms = {k: round(v, 3) for k, v in fr.stage_ms().items() if v > 0}
-        fr.set_profiling(False)
-        me_int_kernel_ms = stage_alone.pop("me_int_kernel"); stage_run.pop("me_int_kernel", None)
-        # round 6: the roofline's kernel ON THE GOP OF `value`.  With the default command `value` is the hierarchical-B 8 GOP; there me_int_kernel is launched once
-        # per P picture and twice per B picture (list 1's search runs beside list 0's on the frame's side stream), so a launch takes longer than alone in an IPPP chain.
-        # A device-resident pyramid of 8 on a frame object of its own (one stream), HIP events around the MAIN chain's launch of every picture (ks265_frame_me_int_ms)
-        hier_me_ms = None
-        if getattr(args, "ref_hier_b", 0) == 8 and not args.hier_b:
-            R0 = max(1, min(4, args.ref0))
-            frh = KsFrame(ks, W, H, qp, lambda_q4(qp), bframes=7, refs=R0, **hot_tools(args, me_method))
-            frh.set_profiling(True)
-            NH = 8 * R0 + 1
-            hd = [frh.new_pic() for _ in range(NH)]
-            hs = gop.hier_order(8, args.iper)
-            acc_p, acc_b, n_p, n_b = 0.0, 0.0, 0, 0
-            hist = []
-            for i in range(1 + 8 * 6):
-                d, kind, r0, r1, layer = next(hs)
-                q = qp + host_qp_offset(kind, layer=layer, hier=True)
-                frh.set_qp(q, lambda_q4(q, inter=kind != "I"))
-                frh.set_picture_tools(*((0, 0, 0, 1 if os.environ.get("KS265_LEAN_B") == "2" and me_method == 2 else -1) if kind == "B" and layer == 3 and not os.environ.get("KS265_LEAN_B") == "0" else (0, -1, 0, -1) if kind == "B" and layer == 2 and os.environ.get("KS265_LEAN_B") not in ("0", "3") else (-1, -1, -1, -1)))      # the host's lean B pictures
-                out = hd[d % NH]
-                if kind == "B":
-                    frh.encode_picture_b(src_of(d), hd[r0 % NH], hd[r1 % NH], out)
-                elif kind == "P" and R0 > 1 and len(hist) > 1 and hist[0] == r0:      # -ref0: the anchor searches the last ref0 anchors (one me_int_kernel launch per picture searched; the events time the last one)
-                    frh.encode_picture_mref(src_of(d), [hd[p % NH] for p in hist[:R0]], out)
-                else:
-                    frh.encode_picture(src_of(d), hd[r0 % NH] if r0 is not None else out, kind == "I", out)
-                if kind == "I":
-                    hist = [d]
-                elif kind == "P":
-                    hist = [d] + hist[:3]
+            def stage_pass(all_shards):
+                acc, nacc = {}, 0
+                for _ in range(24):
+                    (step if all_shards else sh0.step)()
+                    if state["kind"] == "Pm":              # multi-reference run: time the stages on an extra single-reference picture (same kernels per launch)
+                        fr.encode_picture(src_of(state["last"][0]), state["ref0"], False, probe_out)
+                    elif state["kind"] != "P":             # stage events are recorded by ks265_encode_picture (I / P pictures)
+                        continue
+                    ms = fr.stage_ms()
+                    ms["me_int_kernel"] = fr.me_int_ms()      # the SAD kernel alone (HIP events around its launch on the frame's stream): stage me_integer also holds pre-search + propagation
+                    for k, v in ms.items():
+                        acc[k] = acc.get(k, 0.0) + v
+                    nacc += 1
                 torch.cuda.synchronize()
-                if i > 8 and kind != "I":                       # (the first mini-GOP warms the frame object up)
-                    v = frh.me_int_ms()
-                    if v > 0:
-                        if kind == "B": acc_b += v; n_b += 1
-                        else: acc_p += v; n_p += 1
-            frh.set_profiling(False); frh.close()
-            if n_p and n_b:
-                tp, tb = acc_p / n_p, acc_b / n_b
-                hier_me_ms = {"p_picture": round(tp, 4), "b_picture_list0": round(tb, 4), "per_launch": round((R0 * tp + 14 * tb) / (R0 + 14), 4),
-                              "launches_per_mini_gop": R0 + 14, "what": f"me_int_kernel by HIP events in a device-resident pyramid of 8 on one stream: {R0} launches per anchor (-ref0 {R0}: one per picture searched), 2 per B picture (the two lists' searches side by side: the event pair times list 0's launch while list 1's runs on the side stream)"}
-        stage_ms = stage_alone
-        dom_stage = max(stage_ms, key=stage_ms.get)
-        # the roofline figure is the SAD kernel's (north_star; VERDICT r3: the kernel alone, not the stage): algorithmic bytes / its own launch duration
-        dom = "me_integer"
-        algo_bytes = ALGO_BYTES_P[dom] * P
-        if not me_int_kernel_ms or me_int_kernel_ms <= 0:      # ks265_frame_me_int_ms had no valid event pair: fall back to the stage's interval, which contains the kernel
-            me_int_kernel_ms = stage_ms["me_integer"]
-        achieved = algo_bytes / (me_int_kernel_ms * 1e-3) / 1e9
-        # counters under profiles/ are inputs measured by a rocprofv3 --pmc run of an EARLIER invocation: they count only if they were taken on this very kernel source
-        from ks265codec_amd.build import source_sha
-        my_sha, stale = source_sha(), []
-        traffic = None
-        tfile = os.path.join(ROOT, "profiles", "hbm_traffic.json")      # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (tools/hbm_traffic.py)
-        if os.path.exists(tfile):
-            tall = json.load(open(tfile)).get(f"{W}x{H}", {})
-            if tall.get("_stamp", {}).get("kernel_src_sha") != my_sha:
-                stale.append("hbm_traffic.json")
-            elif tall.get(dom):
-                traffic = tall[dom]["bytes_per_launch"]
-        # second figure per stage: the VALU-issue fraction = wave-level VALU instructions per launch (SQ_INSTS_VALU of a rocprofv3 --pmc pass,
-        # profiles/sq_counters.json by tools/sq_issue.py) / 1.23e12 per second / the stage's duration - the kernels of this path are bound by latency and issue, not bytes
-        valu = {}
-        sfile = os.path.join(ROOT, "profiles", "sq_counters.json")
-        if os.path.exists(sfile):
-            sq = json.load(open(sfile)).get(f"{W}x{H}", {})
-            if sq.get("_stamp", {}).get("kernel_src_sha") != my_sha:
-                stale.append("sq_counters.json"); sq = {}
-            for k, v in stage_ms.items():
-                n = sum(sq.get(kk, {}).get("insts_valu_per_launch", 0) for kk in ((k, "merge_pass") if k == "cu_decide" else (k,)))
-                if n and v > 0:
-                    valu[k] = round(n / 1.23e12 / (v * 1e-3), 4)
-        ippp_fig = {"achieved": round(achieved, 2), "frac": round(achieved / HBM_PEAK_GBS, 5), "avg_launch_ms": round(me_int_kernel_ms, 4), "gop": "IPPP (device-resident leg)"}
-        if hier_me_ms:                                            # the headline's GOP: this is the figure of `roofline`; the IPPP one stays beside it
-            me_int_kernel_ms = hier_me_ms["per_launch"]
+                return {k: v / nacc for k, v in acc.items()}
+
+            torch.cuda.synchronize()
+            stage_alone = stage_pass(False)                 # shard 0 alone on the GPU: the kernels' own durations (= a --streams 1 run)
+            stage_run = stage_pass(True) if nstreams > 1 else stage_alone   # event-to-event intervals on shard 0's stream while the other shards run
+            # one key picture on its own (not part of the schedule): intra mode pre-selection + wavefront reconstruction + loop filters
+            fr.set_qp(qp, lambda_q4(qp))
+            kout = fr.new_pic()
+            torch.cuda.synchronize()
+            fr.encode_picture(srcs[0], kout, True, kout)
+            torch.cuda.synchronize()
+            key_ms = {k: round(v, 3) for k, v in fr.stage_ms().items() if v > 0}
+            fr.set_profiling(False)
+            me_int_kernel_ms = stage_alone.pop("me_int_kernel"); stage_run.pop("me_int_kernel", None)
+            # round 6: the roofline's kernel ON THE GOP OF `value`.  With the default command `value` is the hierarchical-B 8 GOP; there me_int_kernel is launched once
+            # per P picture and twice per B picture (list 1's search runs beside list 0's on the frame's side stream), so a launch takes longer than alone in an IPPP chain.
+            # A device-resident pyramid of 8 on a frame object of its own (one stream), HIP events around the MAIN chain's launch of every picture (ks265_frame_me_int_ms)
+            hier_me_ms = None
+            if getattr(args, "ref_hier_b", 0) == 8 and not args.hier_b:
+                R0 = max(1, min(4, args.ref0))
+                frh = KsFrame(ks, W, H, qp, lambda_q4(qp), bframes=7, refs=R0, **hot_tools(args, me_method))
+                frh.set_profiling(True)
+                NH = 8 * R0 + 1
+                hd = [frh.new_pic() for _ in range(NH)]
+                hs = gop.hier_order(8, args.iper)
+                acc_p, acc_b, n_p, n_b = 0.0, 0.0, 0, 0
+                hist = []
+                for i in range(1 + 8 * 6):
+                    d, kind, r0, r1, layer = next(hs)
+                    q = qp + host_qp_offset(kind, layer=layer, hier=True)
+                    frh.set_qp(q, lambda_q4(q, inter=kind != "I"))
+                    frh.set_picture_tools(*((0, 0, 0, 1 if os.environ.get("KS265_LEAN_B") == "2" and me_method == 2 else -1) if kind == "B" and layer == 3 and not os.environ.get("KS265_LEAN_B") == "0" else (0, -1, 0, -1) if kind == "B" and layer == 2 and os.environ.get("KS265_LEAN_B") not in ("0", "3") else (-1, -1, -1, -1)))      # the host's lean B pictures
+                    out = hd[d % NH]
+                    if kind == "B":
+                        frh.encode_picture_b(src_of(d), hd[r0 % NH], hd[r1 % NH], out)
+                    elif kind == "P" and R0 > 1 and len(hist) > 1 and hist[0] == r0:      # -ref0: the anchor searches the last ref0 anchors (one me_int_kernel launch per picture searched; the events time the last one)
+                        frh.encode_picture_mref(src_of(d), [hd[p % NH] for p in hist[:R0]], out)
+                    else:
+                        frh.encode_picture(src_of(d), hd[r0 % NH] if r0 is not None else out, kind == "I", out)
+                    if kind == "I":
+                        hist = [d]
+                    elif kind == "P":
+                        hist = [d] + hist[:3]
+                    torch.cuda.synchronize()
+                    if i > 8 and kind != "I":                       # (the first mini-GOP warms the frame object up)
+                        v = frh.me_int_ms()
+                        if v > 0:
+                            if kind == "B": acc_b += v; n_b += 1
+                            else: acc_p += v; n_p += 1
+                frh.set_profiling(False); frh.close()
+                if n_p and n_b:
+                    tp, tb = acc_p / n_p, acc_b / n_b
+                    hier_me_ms = {"p_picture": round(tp, 4), "b_picture_list0": round(tb, 4), "per_launch": round((R0 * tp + 14 * tb) / (R0 + 14), 4),
+                                  "launches_per_mini_gop": R0 + 14, "what": f"me_int_kernel by HIP events in a device-resident pyramid of 8 on one stream: {R0} launches per anchor (-ref0 {R0}: one per picture searched), 2 per B picture (the two lists' searches side by side: the event pair times list 0's launch while list 1's runs on the side stream)"}
+            stage_ms = stage_alone
+            dom_stage = max(stage_ms, key=stage_ms.get)
+            # the roofline figure is the SAD kernel's (north_star; VERDICT r3: the kernel alone, not the stage): algorithmic bytes / its own launch duration
+            dom = "me_integer"
+            algo_bytes = ALGO_BYTES_P[dom] * P
+            if not me_int_kernel_ms or me_int_kernel_ms <= 0:      # ks265_frame_me_int_ms had no valid event pair: fall back to the stage's interval, which contains the kernel
+                me_int_kernel_ms = stage_ms["me_integer"]
             achieved = algo_bytes / (me_int_kernel_ms * 1e-3) / 1e9
-        roofline = {"bound": "hbm", "kernel": "me_int_kernel", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "gop": "hierarchical-B 8 (the GOP of value)" if hier_me_ms else "the device-resident leg's",
-                    "in_the_gop_of_value": hier_me_ms, "roofline_ippp": ippp_fig if hier_me_ms else None,
-                    "counters_stale": stale or None, "kernel_src_sha": my_sha,
-                    "algorithmic_bytes_per_launch": int(algo_bytes), "avg_launch_ms": round(me_int_kernel_ms, 4), "longest_stage": dom_stage,
-                    "stages_ms": {k: round(v, 4) for k, v in stage_ms.items()},
-                    "streams_in_run": nstreams,
-                    "stage_intervals_ms_in_run": {k: round(v, 4) for k, v in stage_run.items()},
-                    "note": "avg_launch_ms / stages_ms / frac: HIP events around each stage with ONE shard on the GPU = the kernel's own duration; it agrees with the rocprofv3 kernel trace of `bench.py --streams 1` (profiles/). With the run's --streams shards in flight the kernels of different shards overlap: stage_intervals_ms_in_run are event-to-event intervals on one shard's stream under that load (queueing behind the other shards' kernels included), the kernel durations of that condition are in the rocprofv3 trace of the default command (profiles/).",
-                    "stages_frac": {k: round(ALGO_BYTES_P[k] * P / (v * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) for k, v in stage_ms.items()},
-                    "valu_issue_frac": (round(valu["me_integer"] * stage_ms["me_integer"] / ippp_fig["avg_launch_ms"], 4) if valu.get("me_integer") else None), "stages_valu_issue_frac": valu or None,
-                    "bound_note": "no stage of a P picture is limited by HBM bytes: each is a dependency chain per CTU (search state machines, the intra CUs' wavefront) or issue-bound "
-                                  "arithmetic on L2-resident samples; valu_issue_frac = VALU wave-instructions / 1.23e12 per s / duration says how busy the vector ALUs are"}
+            # counters under profiles/ are inputs measured by a rocprofv3 --pmc run of an EARLIER invocation: they count only if they were taken on this very kernel source
+            from ks265codec_amd.build import source_sha
+            my_sha, stale = source_sha(), []
+            traffic = None
+            tfile = os.path.join(ROOT, "profiles", "hbm_traffic.json")      # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (tools/hbm_traffic.py)
+            if os.path.exists(tfile):
+                tall = json.load(open(tfile)).get(f"{W}x{H}", {})
+                if tall.get("_stamp", {}).get("kernel_src_sha") != my_sha:
+                    stale.append("hbm_traffic.json")
+                elif tall.get(dom):
+                    traffic = tall[dom]["bytes_per_launch"]
+            # second figure per stage: the VALU-issue fraction = wave-level VALU instructions per launch (SQ_INSTS_VALU of a rocprofv3 --pmc pass,
+            # profiles/sq_counters.json by tools/sq_issue.py) / 1.23e12 per second / the stage's duration - the kernels of this path are bound by latency and issue, not bytes
+            valu = {}
+            sfile = os.path.join(ROOT, "profiles", "sq_counters.json")
+            if os.path.exists(sfile):
+                sq = json.load(open(sfile)).get(f"{W}x{H}", {})
+                if sq.get("_stamp", {}).get("kernel_src_sha") != my_sha:
+                    stale.append("sq_counters.json"); sq = {}
+                for k, v in stage_ms.items():
+                    n = sum(sq.get(kk, {}).get("insts_valu_per_launch", 0) for kk in ((k, "merge_pass") if k == "cu_decide" else (k,)))
+                    if n and v > 0:
+                        valu[k] = round(n / 1.23e12 / (v * 1e-3), 4)
+            ippp_fig = {"achieved": round(achieved, 2), "frac": round(achieved / HBM_PEAK_GBS, 5), "avg_launch_ms": round(me_int_kernel_ms, 4), "gop": "IPPP (device-resident leg)"}
+            if hier_me_ms:                                            # the headline's GOP: this is the figure of `roofline`; the IPPP one stays beside it
+                me_int_kernel_ms = hier_me_ms["per_launch"]
+                achieved = algo_bytes / (me_int_kernel_ms * 1e-3) / 1e9
+            roofline = {"bound": "hbm", "kernel": "me_int_kernel", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "gop": "hierarchical-B 8 (the GOP of value)" if hier_me_ms else "the device-resident leg's",
+                        "in_the_gop_of_value": hier_me_ms, "roofline_ippp": ippp_fig if hier_me_ms else None,
+                        "counters_stale": stale or None, "kernel_src_sha": my_sha,
+                        "algorithmic_bytes_per_launch": int(algo_bytes), "avg_launch_ms": round(me_int_kernel_ms, 4), "longest_stage": dom_stage,
+                        "stages_ms": {k: round(v, 4) for k, v in stage_ms.items()},
+                        "streams_in_run": nstreams,
+                        "stage_intervals_ms_in_run": {k: round(v, 4) for k, v in stage_run.items()},
+                        "note": "avg_launch_ms / stages_ms / frac: HIP events around each stage with ONE shard on the GPU = the kernel's own duration; it agrees with the rocprofv3 kernel trace of `bench.py --streams 1` (profiles/). With the run's --streams shards in flight the kernels of different shards overlap: stage_intervals_ms_in_run are event-to-event intervals on one shard's stream under that load (queueing behind the other shards' kernels included), the kernel durations of that condition are in the rocprofv3 trace of the default command (profiles/).",
+                        "stages_frac": {k: round(ALGO_BYTES_P[k] * P / (v * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) for k, v in stage_ms.items()},
+                        "valu_issue_frac": (round(valu["me_integer"] * stage_ms["me_integer"] / ippp_fig["avg_launch_ms"], 4) if valu.get("me_integer") else None), "stages_valu_issue_frac": valu or None,
+                        "bound_note": "no stage of a P picture is limited by HBM bytes: each is a dependency chain per CTU (search state machines, the intra CUs' wavefront) or issue-bound "
+                                      "arithmetic on L2-resident samples; valu_issue_frac = VALU wave-instructions / 1.23e12 per s / duration says how busy the vector ALUs are"}
 
         # ---- CPU baseline on this box's host cores: the reference's own CLI encoder when it is staged (oracle/_ref/appencoder or $KS265_REF_ENCODER,
         #      SURVEY.md §8d-iii), else the oracle port; a bounded sample of the same workload either way
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and not args.no_cpu_baseline and args.full:
             cpu = reference_leg(args, clip, order) or port_leg(args, clip, order, me_method)
 
         bf_desc = f"{args.hier_b - 1} (hierarchical GOP {args.hier_b}, B-ref)" if args.hier_b else str(args.bframes)
@@ -507,7 +528,7 @@ def main():
                                    f"-rc 0 -qp {qp} (the encoder host's ladders = the reference's: I = Q; IPPP P = Q + 1 + 0 / 2 / 1 / 2 over four pictures; pyramid anchors Q + 1, B layers + 2 / + 4 / + 4; plain B = Q + 2) -iper {args.iper}, -bframes {bf_desc}, -ref {max(1, args.refs)} -ref0 {max(1, args.ref0) if args.hier_b else max(1, args.refs)} ({'the anchors of the pyramid search the last ref0 anchors of their GOP, B pictures one picture per list' if args.hier_b else 'one reference picture per list' if args.refs <= 1 else 'every P picture searches that many list-0 pictures'}), -me {me_method} ({args.me.upper()}{', interMeHex below ' + str(args.me_hex_thr) + ' SAD/sample as at -preset slow' if me_method == 2 and args.me_hex_thr else ''}) range 64, -subme 1 as the reference runs it at -preset slow (fast candidate sets judged by SAD + rate; DESIGN.md 5e), sao on, df on",
                        "pictures_per_step": nstreams, "streams_per_gpu": nstreams,
                        "key_picture_ms": {"intra_decide": key_ms.get("intra_candidates"), "intra_reconstruct": key_ms.get("intra_pass"), "total": round(sum(key_ms.values()), 3),
-                                          "note": f"one intra picture per -iper {args.iper} pictures; it is in the timed region whenever the schedule puts one there"},
+                                          "note": f"one intra picture per -iper {args.iper} pictures; it is in the timed region whenever the schedule puts one there"} if key_ms else None,
                        "sharding": "anchor chain rotating over the ranks + RCCL broadcast of every reconstructed anchor from its owner, B pictures spread over the ranks not coding an anchor" if args.b_spread else f"{nstreams} GOP shard(s) in flight per GPU on separate HIP streams, no data-path collective"},
             "roofline": roofline, "cpu_baseline": cpu,
         }
@@ -520,6 +541,24 @@ def main():
     for sh in shards:
         sh.fr.close()
     ks.close()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_dumps(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy, float64 where it came as float64, else float32; an array that would take the files past 64 MB in all is
+    cut to a fixed sample (evenly spaced elements), so that two runs with the same arguments write the same files"""
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_LIMIT_BYTES
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a).reshape(-1)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        n = min(a.size, max(0, left - 4096) // a.itemsize)          # (room for the .npy header)
+        if n < a.size:
+            a = a[np.linspace(0, a.size - 1, n).astype(np.int64)] if n else a[:0]
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        left -= a.nbytes + 4096
 
 
 def host_cores():
@@ -656,7 +695,7 @@ def encoded_leg(args, torch, dist, rank, world, dev_index, backend, sync_all, sh
     yuv.iWidth, yuv.iHeight = W, H
     yuv.iStride[0], yuv.iStride[1], yuv.iStride[2] = W, W // 2, W // 2
     pic.yuv = C.pointer(yuv)
-    state = {"t": 0, "bytes": 0, "nals": 0, "pics": 0, "keep": None}
+    state = {"t": 0, "bytes": 0, "nals": 0, "pics": 0, "keep": None, "window": None, "dump": {} if args.dump_outputs and rank == 0 else None}
     lib.ks265_enc_lanes.restype = C.c_int
     lanes = lib.ks265_enc_lanes(h)
 
@@ -667,6 +706,8 @@ def encoded_leg(args, torch, dist, rank, world, dev_index, backend, sync_all, sh
             state["pics"] += nal[i].naltype < 32                 # VCL NAL units = coded pictures (one slice each)
             if state["keep"] is not None:
                 state["keep"].append(C.string_at(nal[i].pPayload, nal[i].iSize))
+            if state["dump"] is not None and state["window"] and state["window"][0] <= nal[i].pts < state["window"][1]:
+                state["dump"].setdefault(nal[i].pts, []).append((nal[i].naltype, C.string_at(nal[i].pPayload, nal[i].iSize)))     # --dump-outputs: the timed pictures' NAL units
 
     def feed(n):
         for _ in range(n):
@@ -732,51 +773,53 @@ def encoded_leg(args, torch, dist, rank, world, dev_index, backend, sync_all, sh
         sync_all()
         dt = time.perf_counter() - t0
     else:
-        # Weak mode: STEADY-STATE throughput of the asynchronous encoder (output lags input by the SDK's contract).  Untimed: the W warm-up pictures and
-        # as many more as it takes to fill the pipeline and to stand just behind a key picture (the ring of pictures in flight is then full and every
-        # EncodeFrame call returns only when a picture has left the encoder: back-pressure = one picture in, one picture out).  Timed window A: exactly
-        # K pictures (no key picture among them when K < iper).  Timed window B (unless A spans four GOPs itself): exactly FOUR whole GOPs of -iper
-        # pictures each = iper - 1 P/B pictures + ONE key picture (one GOP when -iper > 256).  `value` is the whole-GOP rate (the key picture's share included); A is reported beside it.
+        # Weak mode: exactly --steps pictures are timed (window A); `value` = pictures / seconds of that window.  One lane: STEADY STATE of the asynchronous encoder (output
+        # lags input by the SDK's contract).  Untimed: the W warm-up pictures and as many more as it takes to fill the pipeline and to stand just behind a key picture (the
+        # ring of pictures in flight is then full and every EncodeFrame call returns only when a picture has left the encoder: back-pressure = one picture in, one picture
+        # out); the window is bracketed by barrier + device synchronize.  --full adds window B (unless A spans four GOPs itself): exactly FOUR whole GOPs of -iper pictures
+        # each = iper - 1 P/B pictures + ONE key picture (one GOP when -iper > 256), reported beside `value`.
         iper = args.iper if args.iper > 0 else 1 << 30
         if lanes > 1:
             # GOP lanes: `lanes` closed GOPs are coded at once and handed out in GOP order; every lane buffers a whole GOP of input beyond the one it is coding, and
             # while the caller sits in a device synchronize the lanes go on coding from those buffers - "pictures in" or "pictures out" between two synchronizes
             # is then not the number of pictures the GPU coded between them.  So each window is a closed piece of work: the encoder is EMPTY on both sides
             # (flush + barrier + device synchronize), the pictures fed in between are exactly the pictures coded in between.  Untimed: the warm-up and two whole
-            # rounds of `lanes` GOPs (graphs captured, buffers touched).  Window A = --steps pictures.  Window B = four whole rounds (4 x `lanes` GOPs, as many key
-            # pictures) = `value`; it includes starting from and draining to an empty pipeline, which a long-running encoder pays once (about 5 % of the window).
+            # rounds of `lanes` GOPs (graphs captured, buffers touched).  Window A = --steps pictures; it includes starting from and draining to an empty pipeline, which a
+            # long-running encoder pays once (about 5 % of four whole rounds: --steps of a few rounds or more measure what such an encoder does).  --full: window B = four
+            # whole rounds (4 x `lanes` GOPs, as many key pictures).
             rnd = lanes * iper
             feed(-(-(args.warmup + 2 * rnd) // rnd) * rnd)
             flush(); sync_all()
+            state["window"] = (state["t"], state["t"] + args.steps)
             t0 = time.perf_counter()
             feed(args.steps); flush()
             sync_all()
-            dt_a = time.perf_counter() - t0
-            win = {"A": {"pictures": args.steps, "seconds": round(dt_a, 5), "clock": "fed, coded and flushed between two synchronizes"}}
-            sync_all()
-            o0, t0 = state["pics"], time.perf_counter()
-            feed(4 * rnd)
-            t_in = time.perf_counter() - t0
-            flush()
-            sync_all()
             dt = time.perf_counter() - t0
-            npic = 4 * rnd
-            assert state["pics"] - o0 == npic, (state["pics"] - o0, npic)
-            win["B"] = {"pictures": npic, "seconds": round(dt, 5), "key_pictures": 4 * lanes, "clock": "fed, coded and flushed between two synchronizes", "gop_lanes": lanes,
-                        "seconds_feeding": round(t_in, 5)}
+            win = {"A": {"pictures": args.steps, "seconds": round(dt, 5), "clock": "fed, coded and flushed between two synchronizes"}}
+            if args.full:
+                sync_all()
+                o0, t0 = state["pics"], time.perf_counter()
+                feed(4 * rnd)
+                t_in = time.perf_counter() - t0
+                flush()
+                sync_all()
+                dt_b = time.perf_counter() - t0
+                assert state["pics"] - o0 == 4 * rnd, (state["pics"] - o0, 4 * rnd)
+                win["B"] = {"pictures": 4 * rnd, "seconds": round(dt_b, 5), "key_pictures": 4 * lanes, "clock": "fed, coded and flushed between two synchronizes", "gop_lanes": lanes,
+                            "seconds_feeding": round(t_in, 5)}
         else:
             fill = args.warmup + 132
             if iper < 1 << 20:
                 fill = -(-fill // iper) * iper + 1                # first picture of window A = the one right after a key picture
             feed(fill)
             sync_all()
+            state["window"] = (state["t"], state["t"] + args.steps)
             t0 = time.perf_counter()
             feed(args.steps)
             sync_all()                                            # barrier + device synchronize on both sides (all ranks)
-            dt_a = time.perf_counter() - t0
-            dt, npic = dt_a, args.steps
-            win = {"A": {"pictures": args.steps, "seconds": round(dt_a, 5), "key_pictures": (fill + args.steps - 1) // iper - (fill - 1) // iper}}
-            if args.steps < 4 * iper and iper < 1 << 20:               # (A itself is the value only when it spans four GOPs or more)
+            dt = time.perf_counter() - t0
+            win = {"A": {"pictures": args.steps, "seconds": round(dt, 5), "key_pictures": (fill + args.steps - 1) // iper - (fill - 1) // iper}}
+            if args.full and args.steps < 4 * iper and iper < 1 << 20:     # (A itself spans four GOPs or more otherwise)
                 pos = fill + args.steps
                 feed(-pos % iper + 1 if pos % iper != 1 else 0)   # untimed: up to the picture right after the next key picture
                 ngop = 4 if iper <= 256 else 1                     # round 4: four whole GOPs, not one - 0.14 s windows moved by 12 % when one key picture was not hidden under its predecessor GOP
@@ -784,17 +827,19 @@ def encoded_leg(args, torch, dist, rank, world, dev_index, backend, sync_all, sh
                 t0 = time.perf_counter()
                 feed(ngop * iper)
                 sync_all()
-                dt = time.perf_counter() - t0
-                npic = ngop * iper
-                win["B"] = {"pictures": npic, "seconds": round(dt, 5), "key_pictures": ngop}
+                win["B"] = {"pictures": ngop * iper, "seconds": round(time.perf_counter() - t0, 5), "key_pictures": ngop}
         flush()
     st = Stats()
     lib.ks265_enc_get_stats(h, C.byref(st))
     lib.QY265EncoderClose(h)
-    if dist is not None:
-        tt = torch.tensor([dt], dtype=torch.float64, device=torch.device("cuda", dev_index) if backend == "nccl" else "cpu")
+    def max_over_ranks(x):
+        if dist is None:
+            return x
+        tt = torch.tensor([x], dtype=torch.float64, device=torch.device("cuda", dev_index) if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        dt = float(tt.item())
+        return float(tt.item())
+
+    dt = max_over_ranks(dt)
     mse = st.sse[0] / max(1, st.frames) / (W * H)
     if strong:
         import hashlib
@@ -802,12 +847,20 @@ def encoded_leg(args, torch, dist, rank, world, dev_index, backend, sync_all, sh
                 "md5": hashlib.md5(blob).hexdigest() if rank == 0 else None, "gop_lanes": lanes,
                 "psnr_y": 99.0 if mse == 0 else 10.0 * np.log10(255.0 ** 2 / mse), "slice_write_ms_per_picture": st.host_write_ms / max(1, st.frames), "preset": preset.decode(),
                 "gop": f"hierarchical-B {args.hier_b}" if args.hier_b else (f"P + {gop_b} B" if gop_b else "IPPP")}
-    if dist is not None:
-        ta = torch.tensor([win["A"]["seconds"]], dtype=torch.float64, device=torch.device("cuda", dev_index) if backend == "nccl" else "cpu")
-        dist.all_reduce(ta, op=dist.ReduceOp.MAX)
-        win["A"]["seconds"] = round(float(ta.item()), 5)
-    win["A"]["fps_all_ranks"] = round(world * win["A"]["pictures"] / win["A"]["seconds"], 2)
-    return {"fps": world * npic / dt, "dt": dt * args.steps / npic, "windows": win, "gop_lanes": lanes, "host_threads": threads, "host_cores": cores, "bytes_per_picture": st.bytes / max(1, st.frames),
+    for w in win.values():
+        w["seconds"] = round(max_over_ranks(w["seconds"]), 5)
+        w["fps_all_ranks"] = round(world * w["pictures"] / w["seconds"], 2)
+    dump = None
+    if state["dump"] is not None:                              # what the caller received for the timed pictures (flushed: all of them are out)
+        pics = [state["dump"].get(p, []) for p in range(*state["window"])]
+        last = pics[-1]
+        stream = np.frombuffer(b"".join(b for pic in pics for _, b in pic), np.uint8)
+        dump = {"last_step_nal_bytes": np.frombuffer(b"".join(b for _, b in last), np.uint8),
+                "last_step_nal_types": np.array([t for t, _ in last], np.float32),
+                "timed_picture_bytes": np.array([sum(len(b) for _, b in pic) for pic in pics], np.float64),
+                "timed_stream_bytes": stream if stream.size <= 8 << 20 else stream[np.linspace(0, stream.size - 1, 8 << 20).astype(np.int64)],     # a fixed sample past 8 M bytes
+                "sse_yuv_whole_run": np.array(list(st.sse), np.float64)}
+    return {"fps": world * args.steps / dt, "dt": dt, "windows": win, "dump": dump, "gop_lanes": lanes, "host_threads": threads, "host_cores": cores, "bytes_per_picture": st.bytes / max(1, st.frames),
             "psnr_y": 99.0 if mse == 0 else 10.0 * np.log10(255.0 ** 2 / mse), "slice_write_ms_per_picture": st.host_write_ms / max(1, st.frames), "preset": preset.decode(),
             "caller_ms_per_picture": {"input_copy": round(st.in_copy_ms / max(1, st.frames), 3), "enqueue": round((st.submit_ms - st.submit_wait_ms) / max(1, st.frames), 3), "enqueue_waiting_for_ring_space": round(st.submit_wait_ms / max(1, st.frames), 3), "output": round(st.output_ms / max(1, st.frames), 3),
                                       "latency_enqueue_to_records_on_host": round(st.lat_gpu_ms / max(1, st.frames), 2), "latency_enqueue_to_writer_pickup": round(st.lat_queue_ms / max(1, st.frames), 2),
@@ -834,12 +887,12 @@ def encoded_line(args, enc, world, hot, cpu):
                                f"{enc['host_threads']} host threads -> Annex-B NAL units out; -rc 0 -qp {args.qp} (I = Q; IPPP: P = Q + 1 + the reference's cascade 2 / 1 / 2 / 0 over four pictures; pyramid: anchors Q + 1, B layers + 2 / + 4 / + 4 as in the reference) -iper {args.iper}, {enc['gop']}, "
                                f"-ref {max(1, args.refs)} -ref0 3 (the preset's: an anchor of a pyramid GOP searches the last three anchors of its GOP); the stream decodes with the reference's appdecoder to the encoder's reconstruction (tests/test_stream.py)",
                    "timed": None if strong else (("the asynchronous encoder with %d GOP lanes (closed GOPs coded concurrently on the one GPU, output in stream order).  A lane buffers a whole GOP "
-                             "of input and goes on coding while the caller sits in a synchronize, so each window is a closed piece of work: flush + barrier + device synchronize on both sides; "
-                             "A = --steps pictures, B = four whole rounds of lanes x iper pictures (one key picture per GOP) fed, coded and flushed in between.  value = pictures / seconds of B "
-                             "(starting from and draining to an empty pipeline included); ms_per_step = 1000 / value per GPU" % enc["gop_lanes"]) if enc.get("gop_lanes", 1) > 1 else
+                             "of input and goes on coding while the caller sits in a synchronize, so the window is a closed piece of work: flush + barrier + device synchronize on both sides; "
+                             "A = exactly --steps pictures fed, coded and flushed in between (starting from and draining to an empty pipeline included).  value = pictures / seconds of A; "
+                             "ms_per_step = 1000 / value per GPU; with --full, B = four whole rounds of lanes x iper pictures (one key picture per GOP) is reported beside it" % enc["gop_lanes"]) if enc.get("gop_lanes", 1) > 1 else
                              "steady state of the asynchronous encoder (pipeline full before and after, back-pressure: one picture in = one picture out), barrier + "
-                             "device synchronize on both sides of each window.  A = exactly --steps pictures; B = four whole GOPs of -iper pictures incl. their key pictures "
-                             "(run unless A spans four GOPs itself).  value = pictures / seconds of B (of A in that case); ms_per_step = 1000 / value per GPU"),
+                             "device synchronize on both sides of the window.  A = exactly --steps pictures.  value = pictures / seconds of A; ms_per_step = 1000 / value per GPU; "
+                             "with --full, B = four whole GOPs of -iper pictures incl. their key pictures is reported beside it (unless A spans four GOPs itself)"),
                    "gop_lanes": enc.get("gop_lanes", 1),
                    "windows": enc.get("windows"),
                    "pictures_per_step": 1, "host_threads_per_gpu": enc["host_threads"], "host_cores": enc["host_cores"],

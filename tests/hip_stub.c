@@ -11,6 +11,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <time.h>
 
 struct ks265_ctx { int capturing; struct Op *ops; int nops; };
 typedef struct Op { int kind; ks265_frame *f; const void *a; ks265_pic p0, p1, p2, p3; int i0; void *dst; } Op;
@@ -152,8 +153,17 @@ static void do_load(ks265_frame *f, const uint8_t *i420, ks265_pic dst)
     }
 }
 static int stub_fast(void) { static int fast = -1; if (fast < 0) fast = getenv("KS265_STUB_FAST") ? 1 : 0; return fast; }
+/* KS265_STUB_ENCODE_US = n: every picture costs the "device" n microseconds of the thread that runs it, so that a test can rely on the lanes being slower than the
+ * caller (a stand-in that codes everything at once finishes a GOP before the caller has fed the next one on a busy machine) */
+static void stub_encode_delay(void)
+{
+    static long us = -1;
+    if (us < 0) us = getenv("KS265_STUB_ENCODE_US") ? atol(getenv("KS265_STUB_ENCODE_US")) : 0;
+    if (us > 0) { struct timespec ts = {us / 1000000, (us % 1000000) * 1000}; nanosleep(&ts, NULL); }
+}
 static void do_encode(ks265_frame *f, int kind /*0 key, 1 P, 2 B*/, ks265_pic src, ks265_pic r0, ks265_pic r1, ks265_pic out, int state_at_capture)
 {
+    stub_encode_delay();
     const int w8 = f->cfg.width / 8, h8 = f->cfg.height / 8;
     const uint64_t hs = pic_id(f, src), h0 = kind ? pic_id(f, r0) : 0, h1 = kind == 2 ? pic_id(f, r1) : 0;
     /* of the frame state only "a previous P picture exists" may show in the result (the PU ping-pong buffer is an implementation detail: two lanes are at different

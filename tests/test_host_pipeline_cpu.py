@@ -40,7 +40,9 @@ def run(stub_lib, n, iper, bframes, W=128, H=72, out=None, timeout=120, **env):
 @pytest.mark.parametrize("bframes", [0, -1, 3])
 def test_lanes_hand_out_the_one_lane_stream(stub_lib, tmp_path, bframes):
     """IPPP, hierarchical B (8), P + 3 B: the scheduler closes every GOP in front of the next key picture, so GOPs can be coded on different lanes"""
-    res = {L: run(stub_lib, 150, 32, bframes, out=tmp_path / f"l{L}.265", KS265_GOP_LANES=L) for L in (1, 2, 3)}
+    # (2 ms per picture in the stand-in: a lane codes a GOP in 64 ms, long after the caller has fed the next one - without it a busy machine can let the first lane
+    #  finish before the caller runs ahead, and nothing is held back)
+    res = {L: run(stub_lib, 150, 32, bframes, out=tmp_path / f"l{L}.265", KS265_GOP_LANES=L, KS265_STUB_ENCODE_US=2000) for L in (1, 2, 3)}
     for L, r in res.items():
         assert r["lanes"] == L and r["vcl"] == 150 and r["idr"] == 5 and sorted(r["pts"]) == list(range(150)), (L, r["vcl"], r["idr"])
         assert (r["pts"] == list(range(150))) == (bframes == 0)

@@ -6,8 +6,8 @@ export TMPDIR=/tmp
 cp ks265codec_amd/libks265hip.so /tmp/base.so
 for v in base ws212 ws220 ws228; do
   if [ $v = base ]; then cp /tmp/base.so ks265codec_amd/libks265hip.so; else cp scratch/variants/libks265hip_$v.so ks265codec_amd/libks265hip.so; fi
-  timeout 150 python bench.py --leg hot --streams 1 --steps 40 --no-cpu-baseline 2>/dev/null | tail -1 > $O/line_$v.json
-  (cd /tmp && timeout 200 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS --output-format csv -d $O/pmc_$v -o p -- python $R/bench.py --leg hot --steps 6 --warmup 2 --streams 1 --no-cpu-baseline > /dev/null 2>&1)
+  timeout 150 python bench.py --full --leg hot --streams 1 --steps 40 --no-cpu-baseline 2>/dev/null | tail -1 > $O/line_$v.json
+  (cd /tmp && timeout 200 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS --output-format csv -d $O/pmc_$v -o p -- python $R/bench.py --full --leg hot --steps 6 --warmup 2 --streams 1 --no-cpu-baseline > /dev/null 2>&1)
   python tools/sq_summary.py $(ls $O/pmc_$v/*counter_collection.csv | head -1) 2>/dev/null | grep -E "^kernel|me_int_kernel|me_subpel" > $O/sq_$v.txt
   rm -rf $O/pmc_$v
   python - $v <<PY
