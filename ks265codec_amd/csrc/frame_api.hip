@@ -70,7 +70,7 @@ int ks265_frame_create(ks265_ctx *ctx, const ks265_frame_cfg *cfg, ks265_frame *
     if (!r) r = dev_alloc(ctx, (void **)&f->deb[2], (size_t)g.bytes_c, true);
     if (!r) r = dev_alloc(ctx, (void **)&f->sse, 3 * sizeof(unsigned long long), true);
     if (!r) r = dev_alloc(ctx, (void **)&f->sse_acc, 4 * sizeof(unsigned long long), true);
-    if (!r) r = dev_alloc(ctx, (void **)&f->progress, sizeof(int) * (size_t)g.ctu_rows * g.ctu_cols, true);   /* intra wavefront flags: per CTU row (key pictures), per CTU (cfg.intra_inter) */
+    if (!r) r = dev_alloc(ctx, (void **)&f->progress, sizeof(int) * ((size_t)g.ctu_rows * g.ctu_cols + 1), true);   /* intra wavefront: a z-count per CTU + the key pictures' CTU ticket */
     if (!r) r = dev_alloc(ctx, (void **)&f->mats, sizeof(short) * 2 * 1600, true);      /* 2 x MAT_SHORTS (recon_dev.h) */
     if (!r) r = ks265_frame_build_matrices(f);
     if (r) { ks265_frame_destroy(f); return r; }

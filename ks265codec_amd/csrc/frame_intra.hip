@@ -2,15 +2,16 @@
 //   ks265_intra_decide       all 35 luma modes of every 8x8 / 16x16 / 32x32 block predicted from SOURCE neighbours
 //                            (decideBestLumaModeBySadFast enc@0x499170 lineage: pre-selection on source pixels is embarrassingly
 //                            parallel), cost = SATD + lambda * mode bits, CU quadtree bottom-up.  One workgroup per CTU.
-//   ks265_intra_reconstruct  the sequential part: CTUs as a wavefront = the reference's WPP order (CCtuEncWpp::waitForTopRightCtu
-//                            enc@0x46f4a0) (one workgroup per CTU row, two CTUs behind the row above,
-//                            progress counters in HBM), CUs in z-order, neighbours from the RECONSTRUCTED picture with the
+//   ks265_intra_reconstruct  the sequential part: a wavefront at CU granularity - worker work-groups take CTUs in wavefront order from a
+//                            ticket, code a CTU's CUs in z-order, and before each CU wait only for the blocks of the neighbour CTUs
+//                            it reads (a z-count per CTU in HBM, intra_deps.h); neighbours from the RECONSTRUCTED picture with the
 //                            normative availability / substitution / smoothing rules, then the reconstruct() chain per TU.
 // Prediction arithmetic = g_IntraPredFunction enc@0x7070a0 / IntraPredFilterRef_c enc@0x424110 (intra_dev.h, pinned).
 #include "frame_common.h"
 #include <cstddef>
 #include "intra_dev.h"
 #include "recon_dev.h"
+#include "intra_deps.h"
 
 using namespace ks265;
 
@@ -67,6 +68,14 @@ __device__ __forceinline__ int intra_ref_sample(const uint8_t *plane, int stride
 }
 
 // ------------------------------------------------------------------ reconstruction (wavefront)
+// samples other work-groups of the launch read: stored write-through (global_store_dword sc1) and loaded from L2 (global_load_dword sc1), four
+// aligned bytes at a time (explicitly global pointers: a FLAT access would count against lgkmcnt)
+typedef __attribute__((address_space(1))) unsigned ks_gu32;
+typedef __attribute__((address_space(1))) int ks_gi32;
+__device__ __forceinline__ void st_wt(uint8_t *p, unsigned v) { __hip_atomic_store((ks_gu32 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ unsigned ld_wt(const uint8_t *p) { return __hip_atomic_load((const ks_gu32 *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int z_x(int z) { return (z & 1) | ((z >> 1) & 2) | ((z >> 2) & 4); }
+__device__ __forceinline__ int z_y(int z) { return ((z >> 1) & 1) | ((z >> 2) & 2) | ((z >> 3) & 4); }
 #ifdef KS_INTRA_CLOCK
 // experiment build (-DKS_INTRA_CLOCK; tools/intra_clock.py reads the sums): where the time of the intra chain goes - cycles of wave 0 per phase over all work-groups.
 // Measured in round 6 at 2160p (profiles/r06_intra_clock.txt): a CU is 25 - 30 dependent LDS round trips, not arithmetic - 8x8: 11.9 K cycles (TU pipeline 8.5 K: sign-data
@@ -314,7 +323,7 @@ __device__ __forceinline__ void tu_pipeline(IntraLds &L, const TuRole &r, const 
         unsigned o = 0;
 #pragma unroll
         for (int i = 0; i < 4; ++i) o |= (unsigned)clip8((int)((pv >> (8 * i)) & 255) + (live ? (acc[i] + 2048) >> 12 : 0)) << (8 * i);
-        *(unsigned *)((cp == 0 ? c.R0 : (cp == 1 ? c.R1 : c.R2)) + (long)(py + r.qy) * stride + px + r.qx) = o;
+        st_wt((cp == 0 ? c.R0 : (cp == 1 ? c.R1 : c.R2)) + (long)(py + r.qy) * stride + px + r.qx, o);   // write-through: other work-groups read it
         if (cp == 0) *(unsigned *)&L.WY[(1 + c.ly * 8 + r.qy) * 136 + 4 + c.lx * 8 + r.qx] = o;
         else *(unsigned *)&L.WC[cp - 1][(1 + c.ly * 4 + r.qy) * 72 + 4 + c.lx * 4 + r.qx] = o;
     }
@@ -325,38 +334,75 @@ __device__ __forceinline__ void tu_pipeline(IntraLds &L, const TuRole &r, const 
 // PMODE = false: an intra picture (every CU).  PMODE = true (cfg.intra_inter): the intra CUs (pred_mode 2) of a P / B picture AFTER reconstruct_kernel has written every
 // inter CU - a CTU without intra CUs is passed over at once, the others load their own reconstructed samples into the window first (inter neighbours count like intra
 // ones: constrained_intra_pred_flag = 0), quantise with the slice's rounding offset and prune coefficient groups like the inter TUs (cfg.rdo).
+//
+// The wavefront is CU-granular.  progress[k] = the z-count of CTU k (intra_deps.h): how many of its 8x8 blocks, in z-order, are final and visible.  Before a CU,
+// lanes 0 .. 3 of the wave that codes it wait for the z-counts its samples in other CTUs need (ks_intra_need: left, top-left, top, top-right), then that wave
+// loads exactly those samples into the window (wave 0 luma, wave 1 chroma).  After a CU that touches the CTU's right column or bottom row - the only blocks other
+// CTUs read - and after the CTU's last CU the z-count is published.
+// Hand-off (MI355X_MICROARCH.md, Valid forms: one lane of each storing work-group signals for all its stores; sc1 stores, sc1 loads, no fences): every
+// reconstructed sample is stored write-through (st_wt: global_store_dword sc1), every storing wave drains its stores (s_waitcnt vmcnt(0)), a work-group barrier,
+// then ONE lane stores the z-count (global_store_dword sc1).  The consumer polls it with sc1 loads, and the polling wave itself then loads the samples with sc1
+// dword loads (ld_wt) - no acquire, no release, no __threadfence.
+// Key pictures: a fixed number of worker work-groups take CTUs from a ticket (a returning atomic on progress[nctu], zeroed with the flags) in wavefront order
+// (ks_ctu_of_ticket: diagonals cx + 2 cy).  A CTU only waits for CTUs on earlier diagonals = smaller tickets, which were taken by work-groups already running:
+// progress never rests on dispatch order or residency.  PMODE: one work-group per CTU in raster order (most of them leave at once; a ticket per work-group would put some 2000 same-address atomics in front
+// of the few that code): a CTU waits only for smaller raster indices, i.e. for work-groups dispatched before it, as it always did, and the bounded spin turns a
+// wait that never ends into KS_DEVERR_WAVEFRONT_TIMEOUT instead of a hang.
+#ifndef KS_INTRA_WORKERS                                              // (-D...: measurement builds only)
+#define KS_INTRA_WORKERS 128                                         // key pictures: worker work-groups (profiles/r07_intra_workers.txt)
+#endif
+
+// The samples of other CTUs that the CU at block (lx, ly) of CTU (cx, cy), n8 x n8 blocks, reads.  First the wait: lanes 0 .. 3 poll one neighbour each
+// (ks_intra_need; dep_mask: the neighbours that may still change).  Bounded: the CTUs waited for hold smaller tickets, so they are being coded and this never
+// spins long; if it ever does (a lost launch), give up after ~1 s instead of hanging the GPU and SAY SO: the error word makes ks265_synchronize return
+// KS265_FAIL (the picture is invalid and must be re-encoded).
+__device__ __forceinline__ void intra_wait(const KsGeom &g, const int *progress, unsigned *err_word, int spin_limit, int dep_mask, int lane, int cx, int cy, int lx, int ly, int n8)
+{
+    if (lane < 4 && ((dep_mask >> lane) & 1)) {
+        int nk;
+        const int need = ks_intra_need(lane, g.ctu_cols, g.w8, g.h8, cx, cy, lx, ly, n8, &nk);
+        int spins = 0;
+        if (need > 0)
+            while (__hip_atomic_load((const ks_gi32 *)progress + nk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
+                if (spins++ >= spin_limit) { __hip_atomic_fetch_or(err_word, KS_DEVERR_WAVEFRONT_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
+                __builtin_amdgcn_s_sleep(8);
+            }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");          // (no instruction: keeps the loads behind the poll)
+}
+
+// ... then the loads into the window, by the wave that polled (half 0: luma, half 1: both chroma planes): the row above from x0 - 4 (the corner's dword)
+// to x0 + 2 n - 1 when the CU touches the CTU's top, the column left from the corner (from y0 when that lies in the row above) to the end of the
+// below-left part when it touches the CTU's left side; the dwords of x = -4 .. -1 go to window columns 0 .. 3
+__device__ __forceinline__ void intra_border_loads(IntraLds &L, const KsGeom &g, const uint8_t *R0, const uint8_t *R1, const uint8_t *R2, int half, int lane, int cx, int cy,
+                                                   int lx, int ly, int n8)
+{
+    const int sh = half, W = g.W >> sh, H = g.H >> sh, CW = 64 >> sh, n = (8 * n8) >> sh, pitch = half ? 72 : 136, part = half ? lane >> 5 : 0, l = half ? lane & 31 : lane;
+    const uint8_t *R = half ? (part ? R2 : R1) : R0;
+    const long stride = half ? g.sc : g.sy;
+    unsigned char *Wn = half ? L.WC[part] : L.WY;
+    const int x0 = cx * CW + ((lx * 8) >> sh), y0 = cy * CW + ((ly * 8) >> sh);
+    if (ly == 0 && cy > 0) {
+        const int x = x0 - 4 + 4 * l;
+        if (l <= n / 2 && x >= 0 && x < W) *(unsigned *)&Wn[4 + x - cx * CW] = ld_wt(R + (long)(y0 - 1) * stride + x);
+    }
+    if (lx == 0 && cx > 0) {
+        const int y = (ly ? y0 - 1 : y0) + l, ye = min(min(y0 + 2 * n, cy * CW + CW), H);
+        if (y < ye) *(unsigned *)&Wn[(1 + y - cy * CW) * pitch] = ld_wt(R + (long)y * stride + x0 - 4);
+    }
+}
+
+
 template <bool PMODE>
 __global__ __launch_bounds__(256) void intra_recon_kernel(KsGeom g, int qp, const uint8_t *src_y, const uint8_t *src_u, const uint8_t *src_v, ks265_cu8 *cu8,
                                                           int16_t *lvl_y, int16_t *lvl_u, int16_t *lvl_v, uint8_t *rec_y, uint8_t *rec_u, uint8_t *rec_v,
                                                           int *progress, unsigned *err_word, int spin_limit, int sdh_on, long long rdo_lam2k, const int8_t *qp_map)
 {
     __shared__ __attribute__((aligned(16))) IntraLds L;
-    // PMODE: one work-group per CTU in raster order (a CTU's neighbours have smaller indices, so the work-groups it may wait for were dispatched before it);
-    // an intra picture: one work-group per CTU ROW walking its CTUs (every CTU has work, the row is the natural unit)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, cy = PMODE ? (int)blockIdx.x / g.ctu_cols : (int)blockIdx.x;
-    const int cx_first = PMODE ? (int)blockIdx.x % g.ctu_cols : 0, cx_end = PMODE ? cx_first + 1 : g.ctu_cols;
-    __shared__ int s_need;                                           // PMODE: which of the four neighbour CTUs (bit 0 left, 1 top-left, 2 top, 3 top-right) this CTU's intra CUs read
-    if (PMODE) {                                                     // most CTUs of a P / B picture hold no intra CU: leave before any set-up
-        __shared__ int s_any;
-        if (tid < 64) {
-            const int bx = cx_first * 8 + (tid & 7), by = cy * 8 + (tid >> 3);
-            bool intra = false;
-            if (bx < g.w8 && by < g.h8) { const ks265_cu8 q = cu8[(long)by * g.w8 + bx]; intra = q.pred_mode == 2; }
-            const unsigned long long any = __ballot(intra);              // bit = 8x8 block, raster
-            if (tid == 0) {
-                s_any = any != 0ull;
-                // an intra CU reads a neighbour CTU's samples only across the border it touches: left column -> the left CTU (incl. its below-left samples), block (0, 0) -> the
-                // top-left one, top row -> the top one, top row from x = 32 on -> the top-right one (x0 + 2 n > 64 needs x0 >= 32).  The others need not be waited for: round 4,
-                // the wavefront of a 2160p P picture is cut where intra CUs lie inside their CTUs
-                s_need = ((any & 0x0101010101010101ull) ? 1 : 0) | ((any & 1ull) ? 2 : 0) | ((any & 0xFFull) ? 4 : 0) | ((any & 0xF0ull) ? 8 : 0);
-            }
-        }
-        __syncthreads();
-        if (!s_any) {
-            if (tid == 0) __hip_atomic_store(progress + blockIdx.x, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            return;
-        }
-    }
+    __shared__ unsigned long long s_starts;                          // the CTU's CUs to code: bit z = a CU starts at the 8x8 block of z-order index z
+    __shared__ int s_ctu, s_dep;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nctu = g.ctu_cols * g.ctu_rows;
+    ks_gi32 *const prog = (ks_gi32 *)progress;                       // (global: the flags are vector sc1 accesses, never FLAT)
     ICLK_DECL;
     build_matrices(L.Mf, L.Mt, tid, 256);                            // (cheaper than fetching the frame's copy: no memory latency)
     TuCtx c;
@@ -364,36 +410,69 @@ __global__ __launch_bounds__(256) void intra_recon_kernel(KsGeom g, int qp, cons
     c.rdo_lam2k = PMODE ? rdo_lam2k : 0; c.qoff = PMODE ? 85 : 171;
     c.g = &g; c.lvl_y = lvl_y; c.lvl_u = lvl_u; c.lvl_v = lvl_v;
     // quantiser constants of the two QPs, fetched once per CTU (a table load inside the CU loop would sit behind every outstanding store); with a QP per CTU
-    // (qp_map: cu_qp_delta, quantisation group = CTU) a key picture's work-group sets them again at every CTU of its row
+    // (qp_map: cu_qp_delta, quantisation group = CTU) they differ from CTU to CTU
     auto set_qp = [&](int q) {
         const int qc = chroma_qp(q);
         c.qsc[0] = kQuantScales[q % 6]; c.qsc[1] = kQuantScales[qc % 6];
         c.qdq[0] = kInvQuantScales[q % 6] << (q / 6); c.qdq[1] = kInvQuantScales[qc % 6] << (qc / 6);
         c.qp6[0] = q / 6; c.qp6[1] = qc / 6;
     };
-    set_qp(qp_map ? qp_map[cy * g.ctu_cols + cx_first] : qp);
     // (component pointers are picked with selects, not from an array: a dynamically indexed pointer array loses the global address
     //  space, its stores become FLAT stores, and FLAT stores count against lgkmcnt - every LDS barrier would wait for HBM)
     const uint8_t *const S0 = ks_org_y(g, src_y), *const S1 = ks_org_c(g, src_u), *const S2 = ks_org_c(g, src_v);
     c.R0 = ks_org_y(g, rec_y); c.R1 = ks_org_c(g, rec_u); c.R2 = ks_org_c(g, rec_v);
-    for (int cx = cx_first; cx < cx_end; ++cx) {
-        __syncthreads();                                             // nobody still walks the previous CTU's map
-        if (!PMODE && qp_map && cx > cx_first) set_qp(qp_map[cy * g.ctu_cols + cx]);
+    for (;;) {
+        __syncthreads();                                             // nobody still works on the previous CTU
+        if (tid == 0) {
+            if (PMODE) s_ctu = (int)blockIdx.x;
+            else {                                                   // key pictures: the next CTU in wavefront order
+                const int t = atomicAdd(progress + nctu, 1);
+                s_ctu = t < nctu ? ks_ctu_of_ticket(t, g.ctu_cols, g.ctu_rows) : nctu;
+            }
+        }
+        __syncthreads();
+        const int ctu = s_ctu;
+        if (ctu >= nctu) break;
+        const int cy = ctu / g.ctu_cols, cx = ctu - cy * g.ctu_cols;
         if (tid < 64) {
-            const int bx = cx * 8 + (tid & 7), by = cy * 8 + (tid >> 3);
+            // lane = z-order index of an 8x8 block: the CU map, and the CUs to code as a ballot in z-order
+            const int lx = z_x(lane), ly = z_y(lane), bx = cx * 8 + lx, by = cy * 8 + ly;
             ks265_cu8 cu;
             cu.mvx = 0; cu.mvy = 0; cu.mv1x = 0; cu.mv1y = 0; cu.log2_cu = 0; cu.cbf = 0; cu.pred_mode = 0; cu.inter_dir = 0;
             if (bx < g.w8 && by < g.h8) cu = cu8[(long)by * g.w8 + bx];
-            L.cu[tid] = cu;
-            L.cbf[tid] = PMODE && cu.pred_mode != 2 ? cu.cbf : 0;        // the inter CUs keep what reconstruct_kernel found
-            if (!PMODE) {
-                // the previous CTU's last column becomes this CTU's left neighbour column
-                L.WY[(1 + tid) * 136 + 3] = L.WY[(1 + tid) * 136 + 4 + 63];
-                L.WC[tid >> 5][(1 + (tid & 31)) * 72 + 3] = L.WC[tid >> 5][(1 + (tid & 31)) * 72 + 4 + 31];
+            L.cu[ly * 8 + lx] = cu;
+            L.cbf[ly * 8 + lx] = PMODE && cu.pred_mode != 2 ? cu.cbf : 0;        // the inter CUs keep what reconstruct_kernel found
+            const int n8 = cu.log2_cu ? 1 << ((cu.log2_cu & 15) - 3) : 1;
+            const unsigned long long st = __ballot(cu.log2_cu != 0 && (!PMODE || cu.pred_mode == 2) && !(lx & (n8 - 1)) && !(ly & (n8 - 1)));
+            if (lane == 0) s_starts = st;
+            if (PMODE) {
+                // a neighbour CTU is waited for only if it holds an intra CU along the shared border (its right column / bottom-right block / bottom row / left half
+                // of its bottom row): what reconstruct_kernel wrote there is final otherwise
+                bool dep = false;
+                if (lane < 4 && st) {
+                    const int nx = lane == 0 ? cx - 1 : cx - 2 + lane, ny = lane == 0 ? cy : cy - 1;
+                    if (nx >= 0 && nx < g.ctu_cols && ny >= 0)
+                        for (int k = 0; k < (lane == 1 ? 1 : lane == 3 ? 4 : 8); ++k) {
+                            const int kx = nx * 8 + (lane == 0 || lane == 1 ? 7 : k), ky = ny * 8 + (lane == 0 ? k : 7);
+                            if (kx < g.w8 && ky < g.h8 && cu8[(long)ky * g.w8 + kx].pred_mode == 2) dep = true;
+                        }
+                }
+                const unsigned long long d = __ballot(dep);
+                if (lane == 0) {
+                    s_dep = (int)d;
+                    // most CTUs of a P / B picture hold no intra CU: done at once; the others are final up to their first intra CU
+                    const int z0 = st ? __builtin_ctzll(st) : 64;
+                    if (z0) __hip_atomic_store(prog + ctu, z0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
             }
         }
-        auto load_own = [&]() {
-            // source samples of the CTU: 64 rows x 64 bytes luma (16-byte pieces), 2 x 32 x 32 chroma; rows below the picture are padding, never used
+        __syncthreads();
+        const unsigned long long starts = ((unsigned long long)__builtin_amdgcn_readfirstlane((int)(s_starts >> 32)) << 32) |
+                                          (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)s_starts);
+        if (PMODE && !starts) break;
+        const int dep_mask = PMODE ? __builtin_amdgcn_readfirstlane(s_dep) : 15;
+        set_qp(qp_map ? qp_map[ctu] : qp);
+        {   // source samples of the CTU: 64 rows x 64 bytes luma (16-byte pieces), 2 x 32 x 32 chroma; rows below the picture are padding, never used
             const int r = tid >> 2, cc16 = (tid & 3) * 16;
             *(uint4 *)&L.SY[r * 64 + cc16] = *(const uint4 *)(S0 + (long)(cy * 64 + r) * g.sy + cx * 64 + cc16);
             const int cc = tid >> 7, t = tid & 127, rc = t >> 2, c8 = (t & 3) * 8;
@@ -408,80 +487,28 @@ __global__ __launch_bounds__(256) void intra_recon_kernel(KsGeom g, int qp, cons
                 unsigned *dc = (unsigned *)&L.WC[cc][(1 + rc) * 72 + 4 + c8];
                 dc[0] = wc.x; dc[1] = wc.y;
             }
-        };
-        ICLK(0);                                                     // [0] set-up: matrices, map load
-        if (PMODE) load_own();                                       // nothing of this depends on the neighbours: under way before the wait
-        if (PMODE) {
-            // the neighbour CTUs whose samples this CTU's intra CUs read (of left, top-left, top, top-right: s_need) must be through - with or without intra CUs of
-            // their own (those without flagged themselves at once)
-            if (tid < 4 && ((s_need >> tid) & 1)) {
-                const int nx = tid == 0 ? cx - 1 : cx - 2 + tid, ny = tid == 0 ? cy : cy - 1;
-                // ... and only if that CTU holds an intra CU along the shared border (its right column / bottom-right block / bottom row / left half of its bottom row): what
-                // reconstruct_kernel wrote there is final otherwise
-                bool dep = false;
-                if (nx >= 0 && nx < g.ctu_cols && ny >= 0)
-                    for (int k = 0; k < (tid == 1 ? 1 : tid == 3 ? 4 : 8); ++k) {
-                        const int bx = nx * 8 + (tid == 0 || tid == 1 ? 7 : k), by = ny * 8 + (tid == 0 ? k : 7);
-                        if (bx < g.w8 && by < g.h8 && cu8[(long)by * g.w8 + bx].pred_mode == 2) dep = true;
-                    }
-                if (dep) {
-                    int spins = 0;
-                    while (__hip_atomic_load(progress + ny * g.ctu_cols + nx, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-                        if (spins++ >= spin_limit) { __hip_atomic_fetch_or(err_word, KS_DEVERR_WAVEFRONT_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
-                        __builtin_amdgcn_s_sleep(8);
-                    }
-                }
-            }
-        } else if (cy > 0 && tid == 0) {
-            // wavefront: the row above must be two CTUs ahead (top-right neighbours)
-            const int need = min(cx + 2, g.ctu_cols);
-            // bounded: rows are normally dispatched in order, so the row above is resident and this never spins long; if it ever does
-            // (a lost launch, a row that is not resident under heavy multi-stream load), give up after ~1 s instead of hanging the GPU
-            // and SAY SO: the error word makes ks265_synchronize return KS265_FAIL (the picture is invalid and must be re-encoded)
-            int spins = 0;
-            while (__hip_atomic_load(progress + cy - 1, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < need) {
-                if (spins++ >= spin_limit) { __hip_atomic_fetch_or(err_word, KS_DEVERR_WAVEFRONT_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
-                __builtin_amdgcn_s_sleep(8);
-            }
         }
         __syncthreads();
-        ICLK(1);                                                     // [1] waiting for the neighbour CTUs
-        if (!PMODE) load_own();
-        if (PMODE && cx > 0) {                                       // the left neighbour column: another work-group's stores (L2-coherent loads)
-            if (tid < 64) L.WY[(1 + tid) * 136 + 3] = __hip_atomic_load(c.R0 + (long)(cy * 64 + tid) * g.sy + cx * 64 - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else if (tid < 128) {
-                const int k = tid - 64, pc = k >> 5, rr = k & 31;
-                L.WC[pc][(1 + rr) * 72 + 3] = __hip_atomic_load((pc ? c.R2 : c.R1) + (long)(cy * 32 + rr) * g.sc + cx * 32 - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        if (cy > 0) {                                                // the row above: finished by another workgroup -> L2-coherent loads
-            if (tid < 129) {
-                const int x = cx * 64 - 1 + tid;
-                if (x >= 0 && x < g.W) L.WY[3 + tid] = __hip_atomic_load(c.R0 + (long)(cy * 64 - 1) * g.sy + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            if (tid < 130) {
-                const int cc = tid / 65, k = tid % 65, x = cx * 32 - 1 + k;
-                if (x >= 0 && x < g.W / 2) L.WC[cc][3 + k] = __hip_atomic_load((cc ? c.R2 : c.R1) + (long)(cy * 32 - 1) * g.sc + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        __syncthreads();
-        ICLK(2);                                                     // [2] window loads
+        ICLK(0);                                                     // [0] set-up: ticket, map, the CTU's own samples
+#define BORDERS() do { intra_wait(g, progress, err_word, spin_limit, dep_mask, lane, cx, cy, lx, ly, n8); ICLK(1);                   /* [1] waiting for z-counts */ \
+                       intra_border_loads(L, g, c.R0, c.R1, c.R2, wave, lane, cx, cy, lx, ly, n8); ICLK(2); } while (0)   /* [2] window loads (issued) */
+        unsigned long long todo = starts;
 #pragma unroll 1
-        for (int z = 0; z < 64; ++z) {                              // 8x8 blocks of the CTU in z-order; a CU is coded at its first block
-            const int lx = (z & 1) | ((z >> 1) & 2) | ((z >> 2) & 4), ly = ((z >> 1) & 1) | ((z >> 2) & 2) | ((z >> 3) & 4);
+        while (todo) {                                               // the CUs of the CTU in z-order
+            const int z = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const int znext = todo ? __builtin_ctzll(todo) : 64;      // the z-count once this CU is through
+            const int lx = z_x(z), ly = z_y(z);
             const ks265_cu8 cu = L.cu[ly * 8 + lx];
-            if (cu.log2_cu == 0) continue;                          // outside the picture
-            if (PMODE && cu.pred_mode != 2) continue;               // an inter CU: reconstructed already
-            const int n8 = 1 << ((cu.log2_cu & 15) - 3);
-            if ((lx & (n8 - 1)) || (ly & (n8 - 1))) continue;
-            const int n = 8 * n8, log2 = cu.log2_cu & 15;
+            const int log2 = cu.log2_cu & 15, n8 = 1 << (log2 - 3), n = 8 * n8;
             c.mode = cu.mvx; c.lx = lx; c.ly = ly; c.x0 = cx * 64 + lx * 8; c.y0 = cy * 64 + ly * 8;
             c.filt = intra_filter_flag(c.mode, n);
-            ICLK(3);                                                 // [3] walking the z loop (skipped blocks included)
+            ICLK(3);                                                 // [3] walking the CU list
             ICLK_CNT(16 + (n == 32 ? 2 : n == 16 ? 1 : 0));          // [16..18] CUs of 8 / 16 / 32
             if (n == 32) {
                 // ---- 32x32: the luma TU needs all four waves (256 quads) -> work-group barriers; chroma as a second phase
-                lds_barrier();                                       // waves 0 / 1 may still be inside a small CU
+                if (wave < 2) { BORDERS(); }
+                lds_barrier();                                       // waves 0 / 1 may still be inside a small CU; the window is complete
                 const unsigned mask = intra_unit_mask(g, c.x0, c.y0, n, lane);
                 if (tid < 3) { L.nz[tid] = 0; L.lastcg[tid] = 0; }
                 if (tid < 129) L.raw[0][66 - 64 + tid] = (unsigned char)intra_ref_sample<false>(&L.WY[136 + 4], 136, mask, lx * 8, ly * 8, 32, 8, tid);
@@ -510,7 +537,8 @@ __global__ __launch_bounds__(256) void intra_recon_kernel(KsGeom g, int qp, cons
                 lds_barrier();
             } else if (wave < 2) {
                 // ---- 8x8 / 16x16: wave 0 codes the luma TU, wave 1 both chroma TUs, each on its own (no work-group barrier: a wave's
-                //      gathers only read what the same wave reconstructed, or what was there before the CTU started)
+                //      gathers only read what the same wave reconstructed or loaded, or what was there before the CTU started)
+                BORDERS();
                 const unsigned mask = intra_unit_mask(g, c.x0, c.y0, n, lane);
                 TuRole r;
                 if (wave == 0) {
@@ -562,30 +590,39 @@ __global__ __launch_bounds__(256) void intra_recon_kernel(KsGeom g, int qp, cons
                     if (lane < n8 * n8 && (L.nz[1] | L.nz[2])) atomicOr(&L.cbf[(ly + lane / n8) * 8 + lx + lane % n8], (L.nz[1] ? 2 : 0) | (L.nz[2] ? 4 : 0));
                 }
             }
+            if (PMODE || znext == 64 || lx + n8 == 8 || ly + n8 == 8) {
+                // publish the z-count: every storing wave's sc1 stores are through, then one lane signals for the work-group (PMODE after every intra CU: the inter
+                // CUs up to the next intra CU are final already)
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+                if (tid == 0) __hip_atomic_store(prog + ctu, znext, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                ICLK(10);                                            // [10] publishing
+            }
         }
         lds_barrier();
         if (tid < 64) {
             const int bx = cx * 8 + (tid & 7), by = cy * 8 + (tid >> 3);
             if (bx < g.w8 && by < g.h8) cu8[(long)by * g.w8 + bx].cbf = (uint8_t)L.cbf[tid];
         }
-        __threadfence();                                             // this CTU's samples are in L2 before the row below is released
-        __syncthreads();
-        ICLK(11);                                                    // [11] cbf write-back, fence
+        ICLK(11);                                                    // [11] cbf write-back
         ICLK_CNT(19);                                                // [19] CTUs coded
 #ifdef KS_INTRA_CLOCK
         if (tid == 0) for (int i = 0; i < 24; ++i) if (ick_a[i]) { atomicAdd(&g_iclk[PMODE ? 1 : 0][i], ick_a[i]); ick_a[i] = 0; }
         if (tid == 0) for (int i = 0; i < 9; ++i) if (g_tclk_acc[i]) { atomicAdd(&g_iclk[PMODE ? 1 : 0][20 + i], g_tclk_acc[i]); g_tclk_acc[i] = 0; }
 #endif
-        if (tid == 0) __hip_atomic_store(progress + (PMODE ? (int)blockIdx.x : cy), PMODE ? 1 : cx + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        if (PMODE) break;
     }
+#undef BORDERS
 }
 
 extern "C" int ks265_intra_reconstruct(ks265_frame *f, ks265_pic src, ks265_cu8 *cu8, int16_t *lvl_y, int16_t *lvl_u, int16_t *lvl_v, ks265_pic recon)
 {
     KS_FRAME_CHECK(f);
     if (!src.y || !cu8 || !lvl_y || !lvl_u || !lvl_v || !recon.y) return KS265_POINTER;
-    if (hipMemsetAsync(f->progress, 0, sizeof(int) * (size_t)f->g.ctu_rows, f->ctx->stream) != hipSuccess) return ks265_hip(f->ctx, hipGetLastError());
-    hipLaunchKernelGGL(intra_recon_kernel<false>, dim3(f->g.ctu_rows), dim3(256), 0, f->ctx->stream, f->g, f->cfg.qp, src.y, src.u, src.v, cu8, lvl_y, lvl_u, lvl_v,
+    const int nctu = f->g.ctu_cols * f->g.ctu_rows;
+    // the z-counts and the ticket behind them
+    if (hipMemsetAsync(f->progress, 0, sizeof(int) * (size_t)(nctu + 1), f->ctx->stream) != hipSuccess) return ks265_hip(f->ctx, hipGetLastError());
+    hipLaunchKernelGGL(intra_recon_kernel<false>, dim3(min(nctu, KS_INTRA_WORKERS)), dim3(256), 0, f->ctx->stream, f->g, f->cfg.qp, src.y, src.u, src.v, cu8, lvl_y, lvl_u, lvl_v,
                        recon.y, recon.u, recon.v, f->progress, f->ctx->err_dev, f->ctx->wavefront_spin_limit, f->cfg.sdh, 0ll, f->qp_map);
     return ks265_check_launch(f->ctx);
 }

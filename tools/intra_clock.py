@@ -12,7 +12,7 @@ W, H = 3840, 2160
 clip = make_clip(W, H, 17, seed=7, abc=(67, 91, 33), pan=(8, 5))
 ks = KsContext(0)
 lib = load_library()
-names = ["setup", "wait-nbr", "window", "z-walk", "cu32", "mask", "gather", "smooth/dc", "tu8", "tu16", "z-end", "fence", "", "", "", "", "n8", "n16", "n32", "ctus"]
+names = ["setup", "wait-nbr", "border-ld", "cu-walk", "cu32", "mask", "gather", "smooth/dc", "tu8", "tu16", "publish", "cbf-out", "", "", "", "", "n8", "n16", "n32", "ctus"]   # wait-nbr: the CU-granular waits on neighbour z-counts
 def dump(tag):
     buf = (C.c_ulonglong * 64)()
     assert lib.ks265_debug_clock_read(buf, 1) == 0
