@@ -27,7 +27,9 @@
  *     candidates) - measured on configs[0]: 5.5 % more bytes at equal PSNR-Y than the build's rule, which is why the presets do not select it;
  *   - transskip, tuIntra, vpp_*, 2-pass, long-term references, VBV / CVQ: accepted, ignored;
  *   - input pictures: the caller's planes are pinned in place and uploaded from where they lie inside QY265EncoderEncodeFrame; the caller may reuse its buffers when the call returns
- *     (the SDK requires them to stay valid until the frame is done).
+ *     (the SDK requires them to stay valid until the frame is done);
+ *   - pictures in device memory (not in the SDK): ks265_enc_encode_device_frame takes I420, NV12 or RGB(A) planes on the GPU and converts them there, in the caller's stream
+ *     order (ks265_dev_picture below) - no host copy, no upload, no pinning.
  */
 #ifndef KS265_ENC_H
 #define KS265_ENC_H
@@ -119,6 +121,34 @@ int ks265_enc_set_default(const char *name, int value);
  * buffer and no free input slot is left, the encoder copies that picture into the acquired buffer (its last resort; anything the caller had written there is lost).  Acquire,
  * fill and hand in the same buffer, one picture at a time.  With the lookahead every input slot also has a twin in device memory (picture size each; logged at open). */
 int ks265_enc_acquire_input(void *pEncoder, QY265YUV *yuv);
+/* extension: pictures in device memory.  ks265_enc_enable_device_input (between Open and the first picture; QY_NOTSUPPORTED after it, for a handle whose GOP lanes span several
+ * GPUs, and with the KS265_GRAPH experiment) gives every input slot a twin in device memory; from then on ks265_enc_encode_device_frame takes pictures whose planes lie on `device`
+ * (the handle's GPU: else QY_NOTSUPPORTED), as QY265EncoderEncodeFrame takes host pictures - the same key requests, GOP lanes, delayed frames, zero latency and output; both
+ * kinds of picture may be mixed.  Each plane must lie inside one device allocation of the HIP runtime on that device, [plane, plane + pitch (rows - 1) + row bytes): else
+ * QY_POINTER, and nothing is enqueued (host, managed and other devices' memory, short buffers, pitches below the row).  Width a multiple of 8 as for the encoder.
+ *   KS265_IN_I420  plane[0..2] = Y, U, V with their own pitches;  KS265_IN_NV12  plane[0] = Y, plane[1] = interleaved UV (height / 2 rows);
+ *   KS265_IN_RGB   plane[0..2] = the R, G, B samples of pixel (0, 0), pixel_step bytes apart horizontally, pitch[0] bytes between rows: RGB24 (step 3), RGBA (step 4,
+ *                  base + 0 / 1 / 2), BGRA (step 4, base + 2 / 1 / 0), planar (step 1); converted with the BT.709 (default) or BT.601 matrix, limited (default) or full range,
+ *                  in exact integer arithmetic (the stream signals no colour description: the application knows what it asked for).
+ * CONTRACT: the encoder reads the planes in the order of `stream` (a hipStream_t; NULL = the null stream): its work waits for everything the caller enqueued there before the
+ * call, and everything the caller enqueues there after the call waits until the encoder has read the picture.  So the caller may overwrite the buffer with further work on that
+ * same stream as soon as the call returns - no host synchronisation.  Work on OTHER streams must order itself against `stream`.  The call does not block on the GPU. */
+#define KS265_IN_I420 0
+#define KS265_IN_NV12 1
+#define KS265_IN_RGB 2
+#define KS265_MATRIX_BT709 0
+#define KS265_MATRIX_BT601 1
+typedef struct ks265_dev_picture {
+    int format;                                /* KS265_IN_I420 / _NV12 / _RGB */
+    int device;                                /* HIP ordinal the planes live on */
+    const void *plane[3]; int pitch[3];        /* bytes; RGB: channel pointers R, G, B and pitch[0] */
+    int pixel_step;                            /* RGB only */
+    int matrix, full_range;                    /* RGB only: KS265_MATRIX_BT709 (0, default) / _BT601; 0 = limited range */
+    void *stream;                              /* hipStream_t the planes were produced on; NULL = the null stream */
+    long long pts;
+} ks265_dev_picture;
+int ks265_enc_enable_device_input(void *pEncoder);
+int ks265_enc_encode_device_frame(void *pEncoder, QY265Nal **pNals, int *iNalCount, const ks265_dev_picture *pic, QY265Picture *pOutpic);
 /* extension: write the reconstruction (I420, display order) to `path` - the reference CLI's `-o`; call between Open and the first picture */
 int ks265_enc_set_recon_file(void *pEncoder, const char *path);
 

@@ -84,6 +84,34 @@ int ks265_event_query(ks265_ctx *, void *ev, int *done);          /* *done = 1 w
  * copy-in / compute / copy-out streams of a pipelined host hand pictures over without blocking a host thread */
 int ks265_stream_wait_event(ks265_ctx *, void *ev);
 int ks265_event_destroy(ks265_ctx *, void *ev);
+/* ordering against a stream the library does not own (a hipStream_t of the application, passed as void *; NULL = the device's null stream), for hosts without HIP headers:
+ * ks265_wait_external - everything enqueued on the context's stream after the call waits for the work enqueued on `hip_stream` so far (an event of the context's own is
+ * recorded there; one thread at a time per context); ks265_external_wait_event - everything enqueued on `hip_stream` after the call waits for `ev` (ks265_event_record) */
+int ks265_wait_external(ks265_ctx *, void *hip_stream);
+int ks265_external_wait_event(ks265_ctx *, void *hip_stream, void *ev);
+/* Pictures that are in device memory already (a decoder's NV12 output, a tensor of a model, a rendered frame) converted into the packed I420 layout of the encoder's input
+ * (Y width x height, then U and V width / 2 x height / 2, stride = width) by one kernel on the context's stream (input_convert.hip).  Sources:
+ *   KS265_IN_I420  plane[0..2] = Y, U, V, each with its own pitch in bytes (>= the row's bytes): a repack
+ *   KS265_IN_NV12  plane[0] = Y, plane[1] = interleaved UV (height / 2 rows of width bytes): a deinterleave
+ *   KS265_IN_RGB   plane[0..2] = the R, G and B samples of pixel (0, 0); pixel_step = bytes between horizontally adjacent samples, pitch[0] = bytes between rows, for all three:
+ *                  packed RGB24 (step 3), RGBA (step 4, base + 0 / 1 / 2), BGRA (step 4, base + 2 / 1 / 0), planar CHW (step 1, three plane pointers).  Exact integer
+ *                  arithmetic, BT.709 or BT.601, limited or full range, chroma by a (1, 2, 1) x (1, 1) filter at HEVC's default siting (tests/yuv_convert_ref.py is the specification)
+ * width a multiple of 8, height even.  ks265_input_validate enqueues nothing: KS265_POINTER unless the whole extent of every plane - [p, p + pitch (rows - 1) + row bytes) -
+ * lies inside ONE device allocation on the context's device (host, managed and other devices' memory, short buffers, pitches below the row are refused); KS265_NOTSUPPORTED for a
+ * format / size / matrix outside the list.  ks265_input_convert validates the source and the destination (width x height x 3 / 2 bytes of device memory, 16-byte aligned) the
+ * same way before it launches anything. */
+#define KS265_IN_I420 0
+#define KS265_IN_NV12 1
+#define KS265_IN_RGB 2
+#define KS265_MATRIX_BT709 0
+#define KS265_MATRIX_BT601 1
+typedef struct {
+    int32_t format, width, height;
+    const void *plane[3]; int32_t pitch[3];
+    int32_t pixel_step, matrix, full_range;    /* KS265_IN_RGB only */
+} ks265_in_desc;
+int ks265_input_validate(ks265_ctx *, const ks265_in_desc *src);
+int ks265_input_convert(ks265_ctx *, const ks265_in_desc *src, uint8_t *dev_i420);
 /* Launch sequences as graphs: between ks265_capture_begin and ks265_capture_end everything enqueued on this context's stream by THIS thread (kernel launches,
  * async memsets of the stage functions) is recorded instead of run (hipStreamBeginCapture, relaxed mode: other threads may go on using the runtime);
  * ks265_capture_end returns an executable graph, ks265_graph_launch enqueues all of it with one runtime call.  A host whose pictures repeat the same

@@ -26,7 +26,7 @@ int ks265_create_prio(ks265_ctx **out, int device, int high_priority)
         if (hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, phi) != hipSuccess) { delete c; return KS265_FAIL; }
     } else if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return KS265_FAIL; }
     c->own_stream = true;
-    if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) { ks265_destroy(c); return KS265_FAIL; }
+    if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess || hipEventCreateWithFlags(&c->ev_ext, hipEventDisableTiming) != hipSuccess) { ks265_destroy(c); return KS265_FAIL; }
     if (hipHostMalloc((void **)&c->err_host, sizeof(unsigned), hipHostMallocMapped) != hipSuccess ||
         hipHostGetDevicePointer((void **)&c->err_dev, c->err_host, 0) != hipSuccess) { ks265_destroy(c); return KS265_FAIL; }
     *c->err_host = 0;
@@ -41,6 +41,7 @@ void ks265_destroy(ks265_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
+    if (c->ev_ext) (void)hipEventDestroy(c->ev_ext);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     if (c->err_host) (void)hipHostFree(c->err_host);
     delete c;

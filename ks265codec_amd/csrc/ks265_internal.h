@@ -11,6 +11,7 @@ struct ks265_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t ev_ext = nullptr;                 // ks265_wait_external: recorded on the application's stream, waited for by this one
     std::string last_error;
     // device-side error word: pinned, device-mapped host memory that kernels OR error bits into (KS_DEVERR_*); ks265_synchronize
     // reads and clears it after the stream has drained and turns a set bit into KS265_FAIL

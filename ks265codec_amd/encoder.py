@@ -1,0 +1,167 @@
+"""Encoder for torch users: pictures that are GPU tensors already go into the encoder without leaving the device (include/ks265_enc.h ks265_enc_encode_device_frame).
+
+    enc = Encoder(3840, 2160, preset="slow", qp=27, iper=128)
+    for frame in frames:                          # uint8 CUDA/HIP tensors: (H, W, 3 / 4) RGB(A) / BGR(A), (3, H, W) planar RGB, (H * 3 / 2, W) I420 / NV12
+        out += enc.encode(frame, format="rgba")
+    out += enc.flush()
+    enc.close()
+
+The encoder reads each tensor in the order of torch's current stream and makes that stream wait until it has: the caller may overwrite the tensor with further work on the
+same stream as soon as encode() returns, with no host synchronisation.  Parameters are QY265ConfigParse names (qp, crf, rc, iper, bframes, lookahead, latency, ...)."""
+from __future__ import annotations
+
+import ctypes as C
+
+from . import stream as _stream
+
+IN_I420, IN_NV12, IN_RGB = 0, 1, 2
+MATRIX_BT709, MATRIX_BT601 = 0, 1
+QY_OK, QY_FAIL, QY_OUTOFMEMORY, QY_POINTER, QY_NOTSUPPORTED = 0, -0x7FFFFFFF, -0x7FFFFFFE, -0x7FFFFFFD, -0x7FFFFFFC
+# format name -> (code, byte offsets of R, G, B inside a pixel of an HWC tensor)
+_FORMATS = {"i420": (IN_I420, None), "nv12": (IN_NV12, None), "rgb": (IN_RGB, (0, 1, 2)), "bgr": (IN_RGB, (2, 1, 0)),
+            "rgba": (IN_RGB, (0, 1, 2)), "bgra": (IN_RGB, (2, 1, 0)), "rgb_planar": (IN_RGB, None)}
+_CONFIG_BYTES = 4096                                           # more than sizeof(QY265EncConfig): the library writes only its own layout
+
+
+class Nal(C.Structure):
+    _fields_ = [("naltype", C.c_int), ("tid", C.c_int), ("iSize", C.c_int), ("pts", C.c_longlong), ("pPayload", C.POINTER(C.c_ubyte))]
+
+
+class Picture(C.Structure):
+    _fields_ = [("iSliceType", C.c_int), ("poc", C.c_int), ("pts", C.c_longlong), ("dts", C.c_longlong), ("yuv", C.c_void_p)]
+
+
+class DevPicture(C.Structure):
+    """ks265_dev_picture of include/ks265_enc.h"""
+    _fields_ = [("format", C.c_int), ("device", C.c_int), ("plane", C.c_void_p * 3), ("pitch", C.c_int * 3), ("pixel_step", C.c_int),
+                ("matrix", C.c_int), ("full_range", C.c_int), ("stream", C.c_void_p), ("pts", C.c_longlong)]
+
+
+class EncoderError(RuntimeError):
+    def __init__(self, what: str, rc: int):
+        super().__init__(f"{what}: 0x{rc & 0xFFFFFFFF:08X}")
+        self.rc = rc
+
+
+_lib = None
+
+
+def library() -> C.CDLL:
+    global _lib
+    if _lib is None:
+        _lib = C.CDLL(_stream.build())
+        _lib.QY265EncoderOpen.restype = C.c_void_p
+        _lib.QY265EncoderOpen.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        for n in ("QY265EncoderClose", "ks265_enc_enable_device_input", "QY265EncoderDelayedFrames"):
+            getattr(_lib, n).argtypes = [C.c_void_p]
+        _lib.QY265EncoderEncodeFrame.argtypes = [C.c_void_p, C.POINTER(C.POINTER(Nal)), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int]
+        _lib.ks265_enc_encode_device_frame.argtypes = [C.c_void_p, C.POINTER(C.POINTER(Nal)), C.POINTER(C.c_int), C.POINTER(DevPicture), C.c_void_p]
+    return _lib
+
+
+def describe(t, format: str, matrix: int = MATRIX_BT709, full_range: bool = False) -> DevPicture:
+    """the ks265_dev_picture of a uint8 GPU tensor (no copy: its storage, its strides); ValueError for a layout the encoder cannot read in place"""
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.device.type != "cuda":
+        raise ValueError("a uint8 tensor on the GPU")
+    if format not in _FORMATS:
+        raise ValueError(f"format: one of {sorted(_FORMATS)}")
+    code, offs = _FORMATS[format]
+    p = DevPicture()
+    p.format, p.device = code, t.device.index if t.device.index is not None else torch.cuda.current_device()
+    p.matrix, p.full_range = matrix, int(bool(full_range))
+    base, es = t.data_ptr(), t.element_size()
+    if code == IN_RGB and format == "rgb_planar":
+        if t.dim() != 3 or t.shape[0] != 3 or t.stride(2) != 1 or t.stride(1) < t.shape[2]:
+            raise ValueError("rgb_planar: a (3, H, W) tensor with unit column stride")
+        for k in range(3):
+            p.plane[k] = base + k * t.stride(0) * es
+        p.pitch[0], p.pixel_step = t.stride(1), 1
+    elif code == IN_RGB:
+        n = 4 if format.endswith("a") else 3
+        if t.dim() != 3 or t.shape[2] != n or t.stride(2) != 1 or t.stride(1) < n:
+            raise ValueError(f"{format}: an (H, W, {n}) tensor with contiguous pixels")
+        for k in range(3):
+            p.plane[k] = base + offs[k]
+        p.pitch[0], p.pixel_step = t.stride(0), t.stride(1)
+    else:                                                       # (H * 3 / 2, W): Y rows, then the chroma rows
+        if t.dim() != 2 or t.shape[0] % 3 or t.stride(1) != 1:
+            raise ValueError(f"{format}: an (H * 3 / 2, W) tensor with unit column stride")
+        H, W, rs = t.shape[0] * 2 // 3, t.shape[1], t.stride(0)
+        p.plane[0], p.pitch[0] = base, rs
+        if code == IN_NV12:
+            p.plane[1], p.pitch[1] = base + H * rs, rs
+        else:                                                   # I420 in a 2-D tensor: each chroma row of the tensor holds two rows of U (then of V) of W / 2
+            if rs != W:
+                raise ValueError("i420: a (H * 3 / 2, W) tensor must be contiguous (its chroma rows hold two plane rows each); pass a padded picture as nv12 or through the C API")
+            p.plane[1], p.plane[2] = base + H * W, base + H * W + H * W // 4
+            p.pitch[1] = p.pitch[2] = W // 2
+    p.stream = torch.cuda.current_stream(t.device).cuda_stream
+    return p
+
+
+class Encoder:
+    """one encoder handle with device input enabled; encode() returns the bytes of the NAL units that call produced (the encoder's output lags its input)"""
+
+    def __init__(self, width: int, height: int, preset: str = "slow", **params):
+        self.lib, self.width, self.height = library(), width, height
+        self._cfg = (C.c_uint8 * _CONFIG_BYTES)()
+        if self.lib.QY265ConfigDefaultPreset(self._cfg, preset.encode(), None, str(params.pop("latency", "default")).encode()) != 0:
+            raise ValueError(f"preset {preset!r}")
+        for k, v in (("wdt", width), ("hgt", height), *params.items()):
+            rc = self.lib.QY265ConfigParse(self._cfg, str(k).encode(), str(v).encode())
+            if rc != 0:
+                raise ValueError(f"parameter {k}={v!r}: {'unknown name' if rc == -1 else 'bad value'}")
+        err = C.c_int(0)
+        self.h = self.lib.QY265EncoderOpen(self._cfg, C.byref(err))
+        if not self.h:
+            raise EncoderError("QY265EncoderOpen", err.value)
+        rc = self.lib.ks265_enc_enable_device_input(self.h)
+        if rc != QY_OK:
+            self.lib.QY265EncoderClose(self.h)
+            self.h = None
+            raise EncoderError("ks265_enc_enable_device_input", rc)
+        self._nal, self._nn, self._out, self._pts = C.POINTER(Nal)(), C.c_int(0), Picture(), 0
+
+    def _take(self) -> bytes:
+        return b"".join(C.string_at(self._nal[i].pPayload, self._nal[i].iSize) for i in range(self._nn.value) if self._nal[i].iSize > 0)
+
+    def encode(self, tensor, format: str = "rgba", matrix: int = MATRIX_BT709, full_range: bool = False) -> bytes:
+        if self.h is None:
+            raise RuntimeError("encoder closed")
+        pic = describe(tensor, format, matrix, full_range)
+        shape = (tensor.shape[0], tensor.shape[1]) if format not in ("i420", "nv12", "rgb_planar") else (tensor.shape[1], tensor.shape[2]) if format == "rgb_planar" \
+            else (tensor.shape[0] * 2 // 3, tensor.shape[1])
+        if shape != (self.height, self.width):
+            raise ValueError(f"picture {shape[1]}x{shape[0]}, encoder {self.width}x{self.height}")
+        pic.pts, self._pts = self._pts, self._pts + 1
+        rc = self.lib.ks265_enc_encode_device_frame(self.h, C.byref(self._nal), C.byref(self._nn), C.byref(pic), C.addressof(self._out))
+        if rc != QY_OK:
+            raise EncoderError("ks265_enc_encode_device_frame", rc)
+        return self._take()
+
+    def flush(self) -> bytes:
+        out = bytearray()
+        while self.h is not None and self.lib.QY265EncoderDelayedFrames(self.h):
+            rc = self.lib.QY265EncoderEncodeFrame(self.h, C.byref(self._nal), C.byref(self._nn), None, C.addressof(self._out), 0)
+            if rc != QY_OK:
+                raise EncoderError("QY265EncoderEncodeFrame (flush)", rc)
+            out += self._take()
+        return bytes(out)
+
+    def close(self) -> None:
+        if self.h is not None:
+            self.lib.QY265EncoderClose(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

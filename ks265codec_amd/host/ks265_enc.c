@@ -24,6 +24,12 @@
 #include <string.h>
 #include <time.h>
 #include <unistd.h>
+/* device input (ks265_enc_encode_device_frame) reaches these entry points of libks265hip.so as weak symbols: a device library without them - the CPU tests' stand-in - leaves
+ * them NULL, and the device input is QY_NOTSUPPORTED */
+#pragma weak ks265_input_validate
+#pragma weak ks265_input_convert
+#pragma weak ks265_wait_external
+#pragma weak ks265_external_wait_event
 
 const char strLibQy265Version[] = "ks265enc 0.2 (MI355X pixel path + host CABAC; API of libqycodec V2.6.1.3)";
 
@@ -307,6 +313,7 @@ typedef struct Enc {
      * the encoder's own (KS265_INPUT_COPY=1: the copying path; pictures under 1 MB always copy).  The upload is waited for before QY265EncoderEncodeFrame returns - the SDK's own callers
      * refill ONE buffer for every picture (encoderwrapper.c:367-379) - unless KS265_INPUT_HOLD=1 (the caller keeps every buffer until its picture has come out, qy265enc.h:153-156) */
     int direct_in, hold_in; ks265_ctx *ctx_upl; struct Input *pending_up;
+    int dev_id, dev_in_on;                                /* the lane's GPU; ks265_enc_enable_device_input: every input slot has a twin, pictures may come from device memory */
     ks265_ctx *ctx_up;                                    /* with the lookahead: = ctx_la, the stream the caller's thread feeds with uploads (the moment a picture is handed in) and with the analysis; else NULL */
     uint8_t *stg[NPIPE]; size_t cmp_off[8];               /* staging blocks of the (compact) records on the device and their layout */
     void *ev_staged[NPIPE], *ev_drained[NPIPE];
@@ -1464,6 +1471,7 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
     if (e->base_qp > 51) e->base_qp = 51;
     e->iper = cfg->iIntraPeriod;
     e->coded_upto = -1; e->gop_end = e->gop_end_seen = -1;
+    e->dev_id = device;
     long ncpu = sysconf(_SC_NPROCESSORS_ONLN);
     e->nthreads = cfg->threads > 0 ? cfg->threads : (int)(ncpu > 0 ? ncpu : 4);
     if (e->nthreads > 64) e->nthreads = 64;
@@ -1957,7 +1965,6 @@ static int la_take(Enc *e, Input *slot)
     return r;
 }
 
-/* one picture into the lane: copy to a pinned slot, hand it to the scheduler thread.  key: it starts a closed GOP regardless of the period */
 /* ---- the application's picture buffers, pinned in place once and remembered (process-wide: hipHostRegister refuses memory that is registered already) --------------------------- */
 #define REG_MAX 160
 static struct { pthread_mutex_t mu; struct { uint8_t *base; size_t n; unsigned long stamp; } ent[REG_MAX]; int n; unsigned long clock; uint8_t *bad[32]; int nbad; int handles; } g_reg = {.mu = PTHREAD_MUTEX_INITIALIZER};
@@ -1991,10 +1998,21 @@ static void reg_handle(ks265_ctx *c, int open)
     pthread_mutex_unlock(&g_reg.mu);
 }
 
-static int lane_put(Enc *e, QY265Picture *in, int key)
+/* the conversion's view of a device picture of the lane's size */
+static void dev_desc(const Enc *e, const ks265_dev_picture *p, ks265_in_desc *d)
 {
-    if (!in->yuv || !in->yuv->pData[0] || !in->yuv->pData[1] || !in->yuv->pData[2]) return QY_POINTER;
-    if (in->yuv->iWidth != e->W || in->yuv->iHeight != e->H) return QY_NOTSUPPORTED;
+    memset(d, 0, sizeof *d);
+    d->format = p->format; d->width = e->W; d->height = e->H;
+    for (int k = 0; k < 3; ++k) { d->plane[k] = p->plane[k]; d->pitch[k] = p->pitch[k]; }
+    d->pixel_step = p->pixel_step; d->matrix = p->matrix; d->full_range = p->full_range;
+}
+
+/* one picture into the lane - a host picture (yuv: copied to a pinned slot or uploaded from where it lies) or a device picture (dp, validated by the caller: converted into the
+ * slot's twin on ctx_up in the order of the caller's stream) - and on to the scheduler thread.  key: it starts a closed GOP regardless of the period */
+static int lane_put(Enc *e, const QY265YUV *yuv, const ks265_dev_picture *dp, long long pts, int key)
+{
+    if (!dp && (!yuv || !yuv->pData[0] || !yuv->pData[1] || !yuv->pData[2])) return QY_POINTER;
+    if (!dp && (yuv->iWidth != e->W || yuv->iHeight != e->H)) return QY_NOTSUPPORTED;
     Input *slot = NULL;
     const double tc0 = now_ms();
     pthread_mutex_lock(&e->mu);
@@ -2005,7 +2023,7 @@ static int lane_put(Enc *e, QY265Picture *in, int key)
     while (!e->multi && !e->quit && !e->sched_err && e->next_disp - (e->coded_upto + 1) > 16 + (e->ct_on ? e->ct_depth + e->gop_b + 1 : 0) && e->njobs <= e->ring - 12) pthread_cond_wait(&e->cv_sched_done, &e->mu);
     e->la_t_bp += now_ms() - tc0;   /* a scheduler that failed makes no more progress */
     int own = 0;                                                       /* the caller wrote the picture into a slot it had acquired (ks265_enc_acquire_input): nothing to copy */
-    for (int i = 0; i < e->nin && !slot; ++i) if (e->in[i].used == 4 && e->in[i].i420 == in->yuv->pData[0]) { slot = &e->in[i]; own = 1; }
+    for (int i = 0; i < e->nin && !slot && !dp; ++i) if (e->in[i].used == 4 && e->in[i].i420 == yuv->pData[0]) { slot = &e->in[i]; own = 1; }
     for (int i = 0; i < e->nin && !slot; ++i) if (!e->in[i].used) slot = &e->in[i];
     for (int i = 0; i < e->nin && !slot; ++i) if (e->in[i].used == 4) slot = &e->in[i];   /* last resort: a buffer the caller acquired and did not use for this picture - copy into it
                                                                                             * (the caller's pointer to it is dead from here on, as after any EncodeFrame call) */
@@ -2014,9 +2032,18 @@ static int lane_put(Enc *e, QY265Picture *in, int key)
     if (!slot) return QY_FAIL;                                         /* one lane: cannot happen (more input slots than pictures in flight + one mini-GOP); lanes: the caller checked lane_has_slot */
     uint8_t *u = slot->i420 + (size_t)e->W * e->H, *v = u + (size_t)e->W * e->H / 4;
     int direct = 0;
-    if (e->direct_in && !own && slot->dev && in->yuv->iStride[0] == e->W && in->yuv->iStride[1] == e->W / 2 && in->yuv->iStride[2] == e->W / 2) {
+    if (dp) {                                                          /* the caller's stream -> ctx_up: conversion into the twin -> ev_up -> the caller's stream waits for it */
+        ks265_in_desc d;
+        dev_desc(e, dp, &d);
+        int ru = ks265_wait_external(e->ctx_up, dp->stream);
+        if (!ru) ru = ks265_input_convert(e->ctx_up, &d, slot->dev);
+        if (!ru) ru = ks265_event_record(e->ctx_up, slot->ev_up);
+        if (!ru) ru = ks265_external_wait_event(e->ctx_up, dp->stream, slot->ev_up);
+        if (ru) { pthread_mutex_lock(&e->mu); slot->used = 0; e->sched_err = hip_rc(ru); pthread_mutex_unlock(&e->mu); return hip_rc(ru); }
+        direct = 1;
+    } else if (e->direct_in && !own && slot->dev && yuv->iStride[0] == e->W && yuv->iStride[1] == e->W / 2 && yuv->iStride[2] == e->W / 2) {
         const size_t ny = (size_t)e->W * e->H, nc = ny / 4;
-        uint8_t *p0 = in->yuv->pData[0], *p1 = in->yuv->pData[1], *p2 = in->yuv->pData[2];
+        uint8_t *p0 = yuv->pData[0], *p1 = yuv->pData[1], *p2 = yuv->pData[2];
         const int whole = p1 == p0 + ny && p2 == p1 + nc, evict = !e->hold_in;      /* (hold: an old registration may still be read by a DMA in flight - then the table only grows) */
         int ru = KS265_OK;
         if (whole ? reg_get(e->ctx_up, p0, ny + 2 * nc, evict) : (reg_get(e->ctx_up, p0, ny, evict) && reg_get(e->ctx_up, p1, nc, evict) && reg_get(e->ctx_up, p2, nc, evict))) {
@@ -2034,17 +2061,17 @@ static int lane_put(Enc *e, QY265Picture *in, int key)
             direct = 1;
         }
     }
-    if (direct) { /* on its way from the caller's own memory */ }
+    if (direct) { /* on its way from the caller's own memory (host: DMA; device: the conversion) */ }
     else if (own) { /* in place */ }
-    else if (in->yuv->iStride[0] == e->W && in->yuv->iStride[1] == e->W / 2 && in->yuv->iStride[2] == e->W / 2) {    /* packed planes: three block copies */
-        copy_shared(e->pool, slot->i420, in->yuv->pData[0], (size_t)e->W * e->H);
-        copy_shared(e->pool, u, in->yuv->pData[1], (size_t)e->W * e->H / 4);
-        copy_shared(e->pool, v, in->yuv->pData[2], (size_t)e->W * e->H / 4);
+    else if (yuv->iStride[0] == e->W && yuv->iStride[1] == e->W / 2 && yuv->iStride[2] == e->W / 2) {    /* packed planes: three block copies */
+        copy_shared(e->pool, slot->i420, yuv->pData[0], (size_t)e->W * e->H);
+        copy_shared(e->pool, u, yuv->pData[1], (size_t)e->W * e->H / 4);
+        copy_shared(e->pool, v, yuv->pData[2], (size_t)e->W * e->H / 4);
     } else {
-        for (int y = 0; y < e->H; ++y) memcpy(slot->i420 + (size_t)y * e->W, in->yuv->pData[0] + (size_t)y * in->yuv->iStride[0], (size_t)e->W);
+        for (int y = 0; y < e->H; ++y) memcpy(slot->i420 + (size_t)y * e->W, yuv->pData[0] + (size_t)y * yuv->iStride[0], (size_t)e->W);
         for (int y = 0; y < e->H / 2; ++y) {
-            memcpy(u + (size_t)y * (e->W / 2), in->yuv->pData[1] + (size_t)y * in->yuv->iStride[1], (size_t)e->W / 2);
-            memcpy(v + (size_t)y * (e->W / 2), in->yuv->pData[2] + (size_t)y * in->yuv->iStride[2], (size_t)e->W / 2);
+            memcpy(u + (size_t)y * (e->W / 2), yuv->pData[1] + (size_t)y * yuv->iStride[1], (size_t)e->W / 2);
+            memcpy(v + (size_t)y * (e->W / 2), yuv->pData[2] + (size_t)y * yuv->iStride[2], (size_t)e->W / 2);
         }
     }
     if (slot->dev && !direct) {   /* on its way to the device at once, on the lookahead's stream (nothing there waits for the pipeline) */
@@ -2055,7 +2082,7 @@ static int lane_put(Enc *e, QY265Picture *in, int key)
     /* the picture's own fields travel with it from now; with the lookahead it becomes visible to the scheduler when its results are there (la_drain) */
     pthread_mutex_lock(&e->mu);
     slot->mini4 = 0;
-    slot->disp = e->in_disp++; slot->pts = in->pts; slot->key = key || e->force_key; slot->base_qp = e->base_qp; slot->iper = e->iper; slot->kbps = e->cfg.bitrateInkbps;
+    slot->disp = e->in_disp++; slot->pts = pts; slot->key = key || e->force_key; slot->base_qp = e->base_qp; slot->iper = e->iper; slot->kbps = e->cfg.bitrateInkbps;
     e->force_key = 0;
     if (!e->la_on) { slot->used = 1; e->next_disp = e->in_disp; pthread_cond_signal(&e->cv_sched); }   /* the scheduler thread takes it from here */
     pthread_mutex_unlock(&e->mu);
@@ -2088,12 +2115,12 @@ static int lane_flush_begin(Enc *e, int wait)
     return all;
 }
 
-static int lane_encode_frame(Enc *e, QY265Nal **pNals, int *iNalCount, QY265Picture *in, QY265Picture *out)
+static int lane_encode_frame(Enc *e, QY265Nal **pNals, int *iNalCount, QY265Picture *in, const ks265_dev_picture *dp, QY265Picture *out)
 {
     *pNals = e->nals; *iNalCount = 0;
     int r = QY_OK;
-    if (in) {
-        r = lane_put(e, in, 0);
+    if (in || dp) {
+        r = in ? lane_put(e, in->yuv, NULL, in->pts, 0) : lane_put(e, NULL, dp, dp->pts, 0);
         if (r) return r;
         /* finished pictures (copied to the output buffer); when the ring of in-flight pictures is nearly full, wait for the oldest ones -
          * only as many as needed, the writers keep running */
@@ -2458,16 +2485,14 @@ int QY265EncoderDelayedFrames(void *h)
     return n;
 }
 
-int QY265EncoderEncodeFrame(void *h, QY265Nal **pNals, int *iNalCount, QY265Picture *in, QY265Picture *out, int bForceLogo)
+/* one call of the API: a host picture (in), a device picture (dp) or, neither, the flush */
+static int top_encode(Top *t, QY265Nal **pNals, int *iNalCount, QY265Picture *in, const ks265_dev_picture *dp, QY265Picture *out)
 {
-    (void)bForceLogo;
-    Top *t = (Top *)h;
-    if (!t || !pNals || !iNalCount) return QY_POINTER;
-    if (t->nlanes == 1) return lane_encode_frame(t->lane[0], pNals, iNalCount, in, out);
+    if (t->nlanes == 1) return lane_encode_frame(t->lane[0], pNals, iNalCount, in, dp, out);
     *pNals = NULL; *iNalCount = 0;
     t->on = 0; t->opos = 0;
     int r = QY_OK;
-    if (in) {
+    if (in || dp) {
         int first = 0;
         if (t->chunk_left <= 0 || t->key_request) {                     /* a new GOP: the next lane */
             if (t->ch_n) top_close_chunk(t, t->chunk_left > 0);
@@ -2483,12 +2508,12 @@ int QY265EncoderEncodeFrame(void *h, QY265Nal **pNals, int *iNalCount, QY265Pict
         }
         Enc *e = t->lane[t->cur_lane];
         const double t0 = now_ms();
-        while (!lane_has_slot(e, in->yuv ? in->yuv->pData[0] : NULL)) {                                     /* this lane is as far ahead as its buffers allow: finish older GOPs first */
+        while (!lane_has_slot(e, in && in->yuv ? in->yuv->pData[0] : NULL)) {                                     /* this lane is as far ahead as its buffers allow: finish older GOPs first */
             r = top_collect(t, 1, out);
             if (r) return r;
         }
         t->output_ms += now_ms() - t0;
-        r = lane_put(e, in, first);
+        r = in ? lane_put(e, in->yuv, NULL, in->pts, first) : lane_put(e, NULL, dp, dp->pts, first);
         if (r) return r;
         ++t->ch[(t->ch_head + t->ch_n - 1) % MAX_CHUNKS].count; ++t->n_in; --t->chunk_left;
         const double t1 = now_ms();
@@ -2518,6 +2543,14 @@ int QY265EncoderEncodeFrame(void *h, QY265Nal **pNals, int *iNalCount, QY265Pict
     return r;
 }
 
+int QY265EncoderEncodeFrame(void *h, QY265Nal **pNals, int *iNalCount, QY265Picture *in, QY265Picture *out, int bForceLogo)
+{
+    (void)bForceLogo;
+    Top *t = (Top *)h;
+    if (!t || !pNals || !iNalCount) return QY_POINTER;
+    return top_encode(t, pNals, iNalCount, in, NULL, out);
+}
+
 int ks265_enc_get_stats(void *h, ks265_enc_stats *out)
 {
     Top *t = (Top *)h;
@@ -2544,6 +2577,54 @@ int ks265_enc_acquire_input(void *h, QY265YUV *yuv)
     /* the lane the NEXT picture goes to (QY265EncoderEncodeFrame: a new GOP starts on the next lane) */
     const int lane = t->nlanes == 1 ? 0 : (t->chunk_left <= 0 || t->key_request) ? (t->cur_lane + 1) % t->nlanes : t->cur_lane;
     return lane_acquire(t->lane[lane], yuv);
+}
+
+/* every input slot of the lane gets a device twin (and the event behind its filling) if it has none yet, and the lane a stream for filling them: the lookahead's when there is one
+ * (its analysis reads the twin right after), else the pixel path's - no stream more (a stream more is a hardware queue shared with somebody, lane_open) */
+static int lane_enable_device_input(Enc *e)
+{
+    if (e->dev_in_on) return QY_OK;
+    if (!e->ctx_up) { e->ctx_up = e->ctx_la ? e->ctx_la : e->ctx; reg_handle(e->ctx, 1); }     /* (lane_close lets go of the registrations of every lane with a ctx_up) */
+    const size_t fsz = (size_t)e->W * e->H * 3 / 2;
+    int r = KS265_OK;
+    for (int i = 0; i < e->nin && !r; ++i) {
+        if (!e->in[i].dev) r = ks265_dev_malloc(e->ctx, (void **)&e->in[i].dev, fsz);
+        if (!r && !e->in[i].ev_up) r = ks265_event_create(e->ctx_up, &e->in[i].ev_up);
+    }
+    if (r) return hip_rc(r);
+    e->dev_in_on = 1;
+    return QY_OK;
+}
+
+int ks265_enc_enable_device_input(void *h)
+{
+    Top *t = (Top *)h;
+    if (!t) return QY_POINTER;
+    if (!ks265_input_validate || !ks265_input_convert || !ks265_wait_external || !ks265_external_wait_event) return QY_NOTSUPPORTED;   /* a device library without the conversion */
+    for (int i = 0; i < t->nlanes; ++i) {
+        const Enc *e = t->lane[i];
+        if (e->in_disp || e->dev_id != t->lane[0]->dev_id || e->use_graph) return QY_NOTSUPPORTED;   /* after the first picture; lanes on several GPUs; the graph experiment (captures on the pixel path's stream) */
+    }
+    for (int i = 0; i < t->nlanes; ++i) { const int r = lane_enable_device_input(t->lane[i]); if (r) return r; }
+    return QY_OK;
+}
+
+int ks265_enc_encode_device_frame(void *h, QY265Nal **pNals, int *iNalCount, const ks265_dev_picture *pic, QY265Picture *out)
+{
+    Top *t = (Top *)h;
+    if (!t || !pNals || !iNalCount || !pic) return QY_POINTER;
+    *iNalCount = 0;
+    Enc *e0 = t->lane[0];
+    if (!e0->dev_in_on || !ks265_input_validate) return QY_NOTSUPPORTED;
+    if (pic->device != e0->dev_id) return QY_NOTSUPPORTED;
+    /* the whole picture is checked before anything of it is enqueued or counted: a refused picture leaves the handle as it was */
+    const double t0 = now_ms();
+    ks265_in_desc d;
+    dev_desc(e0, pic, &d);
+    const int rv = ks265_input_validate(e0->ctx, &d);
+    e0->st.in_copy_ms += now_ms() - t0;
+    if (rv) return hip_rc(rv);
+    return top_encode(t, pNals, iNalCount, NULL, pic, out);
 }
 
 int ks265_enc_set_recon_file(void *h, const char *path)
