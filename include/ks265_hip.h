@@ -460,8 +460,9 @@ int ks265_cu_decide_part_b(ks265_frame *f, ks265_pic src, ks265_pic ref0, ks265_
 int ks265_merge_pass(ks265_frame *f, ks265_pic src, ks265_pic ref0, ks265_pic ref1, const ks265_pu *dev_pu, const ks265_pu_b *dev_pub,
                      const ks265_cu8 *dev_cu_in, ks265_cu8 *dev_cu_out);
 /* Stage D2 (cfg.skip_rd; run by ks265_encode_picture[_b|_mref|_b_mref] itself, exported for stage tests): after ks265_reconstruct* - dev_cu8 with its coded-block flags, the
- * level planes and the reconstruction are updated in place for the nodes that become one CU without residual; ref1 = null picture for P pictures; a multi-reference picture's
- * context (ks265_encode_picture_mref / _b_mref) supplies the pictures of every candidate.  Intra CUs are not touched (and keep a node from being looked at). */
+ * level planes and the reconstruction are updated in place for the nodes that become one CU without residual; ref1 = null picture for P pictures.  This call takes one picture
+ * per list; ks265_encode_picture_mref / _b_mref hand the pass their lists, and every candidate takes its pictures from its record.  Intra CUs are not touched (and keep a node
+ * from being looked at). */
 int ks265_skip_pass(ks265_frame *f, ks265_pic src, ks265_pic ref0, ks265_pic ref1, ks265_cu8 *dev_cu8, int16_t *dev_lvl_y, int16_t *dev_lvl_u, int16_t *dev_lvl_v, ks265_pic recon);
 /* Stage C: CU quadtree decision from the PU costs (the bottom-up compare of processTree enc@0x4722a0) */
 int ks265_cu_decide(ks265_frame *f, const ks265_pu *dev_pu, ks265_cu8 *dev_cu8);

@@ -153,6 +153,74 @@ static int records_fence(ks265_frame *f)
     f->rec_fence = nullptr;
     return ks265_hip(f->ctx, hipStreamWaitEvent(f->ctx->stream, (hipEvent_t)ev, 0));
 }
+}  // extern "C": the sequencer's helpers take their chains and stage marks as callables
+
+/* The searches of one picture as two independent chains (pre-search, integer search, propagation, sub-pel refinement: ~ 0.4 ms each at 2160p, each kernel with a long tail
+ * of half-empty CUs - an anchor with three pictures takes two chains' time instead of three).  Where the frame can fork, side_chain is enqueued on the side stream with its own
+ * workspace and runs beside main_chain; both have finished, for the context's stream, when this returns.  Otherwise main_chain, then side_chain, on the one stream.  A chain
+ * is a callable that enqueues on the stream the context holds at the moment.  (A picture being captured as a graph stays on the one stream: the fork's host-side workspace
+ * swaps are not part of a graph.)  caller_can: the term of the condition that only one caller has */
+template <typename Side, typename Main>
+static int search_forked(ks265_frame *f, ks265_pic src, bool caller_can, Side side_chain, Main main_chain)
+{
+    int r;
+    if (!(caller_can && f->b_parallel && !f->ctx->capturing && f->side && f->cfg.pre_search && (!f->cfg.propagate || f->pu_s2))) {
+        if ((r = main_chain())) return r;
+        return side_chain();
+    }
+    if ((r = ks265_presearch_source(f, src))) return r;                        /* the source pyramid both use, once, before the fork */
+    if ((r = ks265_hip(f->ctx, hipEventRecord(f->ev_fork, f->ctx->stream)))) return r;
+    if ((r = ks265_hip(f->ctx, hipStreamWaitEvent(f->side, f->ev_fork, 0)))) return r;
+    hipStream_t mainst = f->ctx->stream;
+    auto swap_ws = [&]() {
+        for (int i = 0; i < 10; ++i) { uint8_t *t = f->pyr[i]; f->pyr[i] = f->pyr2[i]; f->pyr2[i] = t; }
+        ks265_pu *t = f->pu_s; f->pu_s = f->pu_s2; f->pu_s2 = t;
+        if (f->me_work) { const bool side = f->me_work == f->me_work_all[0]; f->me_work = f->me_work_all[side]; f->me_order = f->me_order_all[side]; }
+    };
+    f->src_pyr_ready = true;
+    f->ctx->stream = f->side; swap_ws();
+    r = side_chain();
+    /* the join is recorded and waited for whatever happened after the fork: what the side stream has been handed keeps reading src / refs and writing this frame's
+     * workspace, and the host recycles those on its error path */
+    const int rj = ks265_hip(f->ctx, hipEventRecord(f->ev_join, f->side));
+    f->ctx->stream = mainst; swap_ws();
+    if (!r) r = main_chain();
+    f->src_pyr_ready = false;
+    const int rw = rj ? ks265_hip(f->ctx, hipStreamSynchronize(f->side)) : ks265_hip(f->ctx, hipStreamWaitEvent(f->ctx->stream, f->ev_join, 0));
+    return r ? r : rw;
+}
+
+/* The back end of every picture.  mark(n) closes stage n - 1 of the in-situ timing (ks265_encode_picture; the other entry points record no stage events: no_mark).
+ * in_place: the picture is coded without SAO and reconstructed and deblocked where it is handed over - no SAO launch, no copy */
+static void no_mark(int) {}
+template <typename Mark>
+static int loop_filters(ks265_frame *f, ks265_pic src, bool in_place, ks265_pic recon_out, Mark mark)
+{
+    int r;
+    const ks265_pic deb = in_place ? recon_out : ks_deb_pic(f);
+    mark(6);
+    if (f->cfg.deblock && (r = ks265_deblock(f, f->cu8, deb))) return r;
+    mark(7);
+    if ((r = in_place ? ks265_sao_off(f, f->sao, recon_out) : ks265_sao(f, src, deb, f->sao, recon_out))) return r;
+    mark(8);
+    return KS265_OK;
+}
+/* an inter picture from its CU map on: reconstruction, skip pass (stage D2: on the coded distortion), the intra CUs' pass, the loop filters.  What differs between the
+ * kinds of picture is decided by the caller: skip / ii = whether those passes run */
+template <typename Mark>
+static int inter_back_end(ks265_frame *f, ks265_pic src, const KsPicLists &lists, bool skip, bool ii, bool in_place, ks265_pic recon_out, Mark mark)
+{
+    int r;
+    const ks265_pic deb = in_place ? recon_out : ks_deb_pic(f);
+    if ((r = ks_reconstruct(f, src, lists, f->cu8, f->lvl[0], f->lvl[1], f->lvl[2], deb))) return r;
+    if (skip && (r = ks_skip_pass(f, src, lists, f->cu8, f->lvl[0], f->lvl[1], f->lvl[2], deb))) return r;
+    mark(5);
+    if (ii && (r = ks265_intra_inter_reconstruct(f, src, f->cu8, f->lvl[0], f->lvl[1], f->lvl[2], deb))) return r;
+    return loop_filters(f, src, in_place, recon_out, mark);
+}
+
+extern "C" {
+
 int ks265_encode_picture(ks265_frame *f, ks265_pic src, ks265_pic ref, int is_key, ks265_pic recon_out)
 {
     KS_FRAME_CHECK(f);
@@ -167,7 +235,6 @@ int ks265_encode_picture(ks265_frame *f, ks265_pic src, ks265_pic ref, int is_ke
         f->ev_valid[stage_done] = true;
         evi = stage_done + 1;
     };
-    ks265_pic deb = ks_deb_pic(f);
     if (is_key) {
         /* intra picture: mode pre-selection + CU tree on the source, then the wavefront reconstruction */
         mark(2);
@@ -175,36 +242,28 @@ int ks265_encode_picture(ks265_frame *f, ks265_pic src, ks265_pic ref, int is_ke
         if ((r = ks265_intra_decide(f, src, f->cu8))) return r;
         mark(3);
         mark(5);
-        if ((r = ks265_intra_reconstruct(f, src, f->cu8, f->lvl[0], f->lvl[1], f->lvl[2], deb))) return r;
+        if ((r = ks265_intra_reconstruct(f, src, f->cu8, f->lvl[0], f->lvl[1], f->lvl[2], ks_deb_pic(f)))) return r;
         f->have_prev = false;
-    } else {
-        if (!ref.y) return KS265_POINTER;
-        mark(0);
-        if ((r = me_search(f, src, ref, f->have_prev ? f->pu[f->cur_pu ^ 1] : nullptr, pu))) return r;
-        mark(1);
-        if (f->cfg.subme && (r = ks265_me_subpel(f, src, ref, pu))) return r;
-        mark(2);
-        const bool ii = f->cfg.intra_inter != 0;              /* intra CUs may compete: their candidates first */
-        if (ii && (r = ks265_intra_candidates(f, src, pu, f->icost))) return r;
-        mark(3);
-        if ((r = records_fence(f))) return r;
-        const bool part = f->cfg.part != 0;                    /* -part 1: the halves of every 64 / 32 / 16 CU priced first, the CU decision then picks among 2Nx2N / 2NxN / Nx2N / split */
-        if (f->cfg.merge) {                                    /* stage C2: the CU decision goes to the spare map, the merge pass writes the final one */
-            if ((r = part ? ks265_cu_decide_part(f, src, ref, pu, ii ? f->icost : nullptr, f->cu8_tmp) : ks265_cu_decide_ii(f, pu, ii ? f->icost : nullptr, f->cu8_tmp))) return r;
-            if ((r = ks265_merge_pass(f, src, ref, ks265_pic{nullptr, nullptr, nullptr}, pu, nullptr, f->cu8_tmp, f->cu8))) return r;
-        } else if ((r = part ? ks265_cu_decide_part(f, src, ref, pu, ii ? f->icost : nullptr, f->cu8) : ks265_cu_decide_ii(f, pu, ii ? f->icost : nullptr, f->cu8))) return r;
-        mark(4);
-        if ((r = ks265_reconstruct(f, src, ref, f->cu8, f->lvl[0], f->lvl[1], f->lvl[2], deb))) return r;
-        if (f->cfg.skip_rd >= 2 && (r = ks265_skip_pass(f, src, ref, ks265_pic{nullptr, nullptr, nullptr}, f->cu8, f->lvl[0], f->lvl[1], f->lvl[2], deb))) return r;   /* stage D2: on the coded distortion (1: B pictures only) */
-        mark(5);
-        if (ii && (r = ks265_intra_inter_reconstruct(f, src, f->cu8, f->lvl[0], f->lvl[1], f->lvl[2], deb))) return r;
+        return loop_filters(f, src, false, recon_out, mark);
     }
-    mark(6);
-    if (f->cfg.deblock && (r = ks265_deblock(f, f->cu8, deb))) return r;
-    mark(7);
-    if ((r = ks265_sao(f, src, deb, f->sao, recon_out))) return r;
-    mark(8);
-    if (!is_key) { f->cur_pu ^= 1; f->have_prev = true; }
+    if (!ref.y) return KS265_POINTER;
+    const KsPicLists lists = ks_pic_lists(ref, ks265_pic{nullptr, nullptr, nullptr});
+    mark(0);
+    if ((r = me_search(f, src, ref, f->have_prev ? f->pu[f->cur_pu ^ 1] : nullptr, pu))) return r;
+    mark(1);
+    if (f->cfg.subme && (r = ks265_me_subpel(f, src, ref, pu))) return r;
+    mark(2);
+    const bool ii = f->cfg.intra_inter != 0;              /* intra CUs may compete: their candidates first */
+    if (ii && (r = ks265_intra_candidates(f, src, pu, f->icost))) return r;
+    mark(3);
+    if ((r = records_fence(f))) return r;
+    const bool part = f->cfg.part != 0;                    /* -part 1: the halves of every 64 / 32 / 16 CU priced first, the CU decision then picks among 2Nx2N / 2NxN / Nx2N / split */
+    ks265_cu8 *cud = f->cfg.merge ? f->cu8_tmp : f->cu8;   /* stage C2: the CU decision goes to the spare map, the merge pass writes the final one */
+    if ((r = part ? ks265_cu_decide_part(f, src, ref, pu, ii ? f->icost : nullptr, cud) : ks265_cu_decide_ii(f, pu, ii ? f->icost : nullptr, cud))) return r;
+    if (f->cfg.merge && (r = ks_merge_pass(f, src, lists, pu, nullptr, f->cu8_tmp, f->cu8))) return r;
+    mark(4);
+    if ((r = inter_back_end(f, src, lists, f->cfg.skip_rd >= 2 /* (1: B pictures only) */, ii, false, recon_out, mark))) return r;
+    f->cur_pu ^= 1; f->have_prev = true;
     return KS265_OK;
 }
 
@@ -226,32 +285,11 @@ int ks265_encode_picture_mref(ks265_frame *f, ks265_pic src, const ks265_pic *re
         if (!rr && f->cfg.subme) rr = ks265_me_subpel(f, src, refs[i], pu);
         return rr;
     };
-    const bool par = f->b_parallel && !f->ctx->capturing && f->side && f->pyr2[0] && f->cfg.pre_search && (!f->cfg.propagate || f->pu_s2);
-    if (par) {
-        /* round 6: the chains of the farther pictures on the side stream beside the nearest picture's (the B pictures' two lists do the same, encode_b_lists): chains of
-         * latency-bound kernels that leave most of the device idle - an anchor with three pictures takes two chains' time instead of three */
-        if ((r = ks265_presearch_source(f, src))) return r;
-        if ((r = ks265_hip(f->ctx, hipEventRecord(f->ev_fork, f->ctx->stream)))) return r;
-        if ((r = ks265_hip(f->ctx, hipStreamWaitEvent(f->side, f->ev_fork, 0)))) return r;
-        hipStream_t mainst = f->ctx->stream;
-        auto swap_ws = [&]() {
-            for (int i = 0; i < 10; ++i) { uint8_t *t = f->pyr[i]; f->pyr[i] = f->pyr2[i]; f->pyr2[i] = t; }
-            ks265_pu *t = f->pu_s; f->pu_s = f->pu_s2; f->pu_s2 = t;
-            if (f->me_work) { const bool side = f->me_work == f->me_work_all[0]; f->me_work = f->me_work_all[side]; f->me_order = f->me_order_all[side]; }
-        };
-        f->src_pyr_ready = true;
-        f->ctx->stream = f->side; swap_ws();
-        r = 0;
-        for (int i = 1; i < nref && !r; ++i) r = chain(i);
-        const int rj = ks265_hip(f->ctx, hipEventRecord(f->ev_join, f->side));      /* (joined whatever happened after the fork: see encode_b_lists) */
-        f->ctx->stream = mainst; swap_ws();
-        if (!r) r = chain(0);
-        f->src_pyr_ready = false;
-        const int rw = rj ? ks265_hip(f->ctx, hipStreamSynchronize(f->side)) : ks265_hip(f->ctx, hipStreamWaitEvent(f->ctx->stream, f->ev_join, 0));
-        if (r) return r;
-        if (rw) return rw;
-    } else
-        for (int i = 0; i < nref; ++i) if ((r = chain(i))) return r;
+    /* round 6: the chains of the farther pictures beside the nearest picture's.  Unlike a B picture, this path forks only once the side workspace exists (f->pyr2[0]: the first
+     * pre-search of the frame object allocates it) */
+    r = search_forked(f, src, f->pyr2[0] != nullptr,
+                      [&] { int rr = 0; for (int i = 1; i < nref && !rr; ++i) rr = chain(i); return rr; }, [&] { return chain(0); });
+    if (r) return r;
     if ((r = ks265_ref_decide(f, nref, pus, f->pub))) return r;
     /* round 6 (-ref0: the anchors of the pyramid GOPs search several past anchors): the two-list records go through the stages a one-reference P picture has - intra candidates
      * against them (cfg.intra_inter), the CU tree, the merge pass on the records' pictures (cfg.merge), the intra CUs' pass; -part 1 stays with one reference picture */
@@ -260,20 +298,10 @@ int ks265_encode_picture_mref(ks265_frame *f, ks265_pic src, const ks265_pic *re
     if ((r = records_fence(f))) return r;
     const bool mg = f->cfg.merge && f->cu8_tmp;
     if ((r = ks265_cu_decide_b_ii(f, f->pub, ii ? f->icost : nullptr, mg ? f->cu8_tmp : f->cu8))) return r;
-    /* the merge pass and the skip pass take a candidate's picture from its record (the multi-reference form); list 1 does not exist: mr_pslice makes the zero candidate uni-directional */
-    auto mr_scope = [&](auto &&body) -> int {
-        struct MrScope { ks265_frame *f; ~MrScope() { f->mrefb = false; f->mr_pslice = false; } } scope{f};
-        f->mrefb = true; f->mr_pslice = true; f->mr_n[0] = nref; f->mr_n[1] = 1;
-        for (int i = 0; i < 4; ++i) { f->mr_pic[0][i] = refs[i < nref ? i : nref - 1]; f->mr_pic[1][i] = refs[0]; }
-        return body();
-    };
-    if (mg && (r = mr_scope([&] { return ks265_merge_pass(f, src, refs[0], refs[0], nullptr, f->pub, f->cu8_tmp, f->cu8); }))) return r;
-    ks265_pic deb = ks_deb_pic(f);
-    if ((r = ks265_reconstruct_mref(f, src, nref, refs, f->cu8, f->lvl[0], f->lvl[1], f->lvl[2], deb))) return r;
-    if (f->cfg.skip_rd >= 2 && f->cu8_tmp && (r = mr_scope([&] { return ks265_skip_pass(f, src, refs[0], ks265_pic{nullptr, nullptr, nullptr}, f->cu8, f->lvl[0], f->lvl[1], f->lvl[2], deb); }))) return r;
-    if (ii && (r = ks265_intra_inter_reconstruct(f, src, f->cu8, f->lvl[0], f->lvl[1], f->lvl[2], deb))) return r;
-    if (f->cfg.deblock && (r = ks265_deblock(f, f->cu8, deb))) return r;
-    if ((r = ks265_sao(f, src, deb, f->sao, recon_out))) return r;
+    /* from here on a block's picture comes from its record; list 1 does not exist (pslice): in the records it is the nearest picture */
+    const KsPicLists lists = ks_pic_lists(refs, nref, refs, 1, true, true);
+    if (mg && (r = ks_merge_pass(f, src, lists, nullptr, f->pub, f->cu8_tmp, f->cu8))) return r;
+    if ((r = inter_back_end(f, src, lists, f->cfg.skip_rd >= 2 && f->cu8_tmp, ii, false, recon_out, no_mark))) return r;
     f->cur_pu ^= 1; f->have_prev = true;                          /* the nearest picture's vectors seed the next picture */
     return KS265_OK;
 }
@@ -306,11 +334,11 @@ int ks265_encode_picture_b_mref(ks265_frame *f, ks265_pic src, const ks265_pic *
 }
 static int encode_b_lists(ks265_frame *f, ks265_pic src, const ks265_pic *refs0, int n0, const ks265_pic *refs1, int n1, ks265_pic recon_out)
 {
-    const ks265_pic ref0 = refs0[0], ref1 = refs1[0];
-    const bool mr = n0 > 1 || n1 > 1;
+    const bool mr = n0 > 1 || n1 > 1;                         /* several pictures per list: from the bi-predictive decision on every stage takes a block's pictures from its record */
+    const KsPicLists lists = ks_pic_lists(refs0, n0, refs1, n1, mr, false);
     int r;
     ks265_pu *pu0 = f->pu[f->cur_pu];                         /* scratch: the next P picture overwrites it */
-    /* one list's chain on the stream the context holds at the moment: every picture of the list searched and refined, then (several pictures) the per-PU choice */
+    /* one list's chain: every picture of the list searched and refined, then (several pictures) the per-PU choice */
     auto chain = [&](int l) -> int {
         const ks265_pic *refs = l ? refs1 : refs0; const int n = l ? n1 : n0;
         const ks265_pu *pus[4];
@@ -324,58 +352,17 @@ static int encode_b_lists(ks265_frame *f, ks265_pic src, const ks265_pic *refs0,
         if (!rr && mr) rr = ks265_ref_pick(f, n, pus, l ? f->pu1 : pu0, f->ridx[l]);
         return rr;
     };
-    const bool par = f->b_parallel && !f->ctx->capturing && f->side && f->cfg.pre_search && (!f->cfg.propagate || f->pu_s2);   /* (a picture being captured as a graph stays on the one stream: the fork's host-side workspace swaps are not part of a graph) */
-    if (par) {
-        /* the two searches are independent chains (pre-search, integer search, propagation, sub-pel refinement: ~ 0.4 ms each at 2160p, each kernel with a long tail of
-         * half-empty CUs): list 1's is enqueued on the side stream with its own workspace and runs beside list 0's; the join is in front of the bi-predictive decision */
-        if ((r = ks265_presearch_source(f, src))) return r;                        /* the source pyramid both use, once, before the fork */
-        if ((r = ks265_hip(f->ctx, hipEventRecord(f->ev_fork, f->ctx->stream)))) return r;
-        if ((r = ks265_hip(f->ctx, hipStreamWaitEvent(f->side, f->ev_fork, 0)))) return r;
-        hipStream_t mainst = f->ctx->stream;
-        auto swap_ws = [&]() {
-            for (int i = 0; i < 10; ++i) { uint8_t *t = f->pyr[i]; f->pyr[i] = f->pyr2[i]; f->pyr2[i] = t; }
-            ks265_pu *t = f->pu_s; f->pu_s = f->pu_s2; f->pu_s2 = t;
-            if (f->me_work) { const bool side = f->me_work == f->me_work_all[0]; f->me_work = f->me_work_all[side]; f->me_order = f->me_order_all[side]; }
-        };
-        f->src_pyr_ready = true;
-        f->ctx->stream = f->side; swap_ws();
-        r = chain(1);
-        /* the join is recorded and waited for whatever happened after the fork: what the side stream has been handed keeps reading src / refs and writing this frame's
-         * workspace, and the host recycles those on its error path */
-        const int rj = ks265_hip(f->ctx, hipEventRecord(f->ev_join, f->side));
-        f->ctx->stream = mainst; swap_ws();
-        if (!r) r = chain(0);
-        f->src_pyr_ready = false;
-        const int rw = rj ? ks265_hip(f->ctx, hipStreamSynchronize(f->side)) : ks265_hip(f->ctx, hipStreamWaitEvent(f->ctx->stream, f->ev_join, 0));
-        if (r) return r;
-        if (rw) return rw;
-    } else {
-    if ((r = chain(0))) return r;
-    if ((r = chain(1))) return r;
-    }
-    /* several pictures per list: from here to the reconstruction every stage takes a block's pictures from its record */
-    struct MrScope { ks265_frame *f; ~MrScope() { f->mrefb = false; } } scope{f};
-    if (mr) {
-        f->mrefb = true; f->mr_n[0] = n0; f->mr_n[1] = n1;
-        for (int i = 0; i < 4; ++i) { f->mr_pic[0][i] = refs0[i < n0 ? i : n0 - 1]; f->mr_pic[1][i] = refs1[i < n1 ? i : n1 - 1]; }
-    }
-    if ((r = ks265_bi_decide(f, src, ref0, ref1, pu0, f->pu1, f->pub))) return r;
+    if ((r = search_forked(f, src, true, [&] { return chain(1); }, [&] { return chain(0); }))) return r;   /* list 1's beside list 0's; the join is in front of the bi-predictive decision */
+    if ((r = ks_bi_decide(f, src, lists, pu0, f->pu1, f->pub))) return r;
     const bool ii = f->cfg.intra_inter != 0;
     if (ii && (r = ks265_intra_candidates(f, src, f->pub, f->icost))) return r;
     if ((r = records_fence(f))) return r;
     const bool part = f->cfg.part != 0;                        /* -part 1: the halves of every 64 / 32 / 16 CU priced with the motions of the CU and of its quarters (round 5: B pictures too) */
     ks265_cu8 *cud = f->cfg.merge ? f->cu8_tmp : f->cu8;
-    if ((r = part ? ks265_cu_decide_part_b(f, src, ref0, ref1, pu0, f->pu1, f->pub, ii ? f->icost : nullptr, cud) : ks265_cu_decide_b_ii(f, f->pub, ii ? f->icost : nullptr, cud))) return r;
-    if (f->cfg.bi_refine == 2 && (r = ks265_bi_refine_chosen(f, src, ref0, ref1, pu0, f->pu1, f->pub, cud))) return r;   /* the joint refinement, for the CUs the decision chose (round 5) */
-    if (f->cfg.merge && (r = ks265_merge_pass(f, src, ref0, ref1, nullptr, f->pub, f->cu8_tmp, f->cu8))) return r;
-    const bool no_sao = f->cfg.sao == 0;                       /* without SAO the picture is reconstructed and deblocked where it is handed over: no SAO launch, no copy */
-    ks265_pic deb = no_sao ? recon_out : ks_deb_pic(f);
-    if ((r = ks265_reconstruct_b(f, src, ref0, ref1, f->cu8, f->lvl[0], f->lvl[1], f->lvl[2], deb))) return r;
-    if (f->cfg.skip_rd && (r = ks265_skip_pass(f, src, ref0, ref1, f->cu8, f->lvl[0], f->lvl[1], f->lvl[2], deb))) return r;
-    if (ii && (r = ks265_intra_inter_reconstruct(f, src, f->cu8, f->lvl[0], f->lvl[1], f->lvl[2], deb))) return r;
-    if (f->cfg.deblock && (r = ks265_deblock(f, f->cu8, deb))) return r;
-    if (no_sao) return ks265_sao_off(f, f->sao, recon_out);
-    return ks265_sao(f, src, deb, f->sao, recon_out);
+    if ((r = part ? ks_cu_decide_part_b(f, src, lists, pu0, f->pu1, f->pub, ii ? f->icost : nullptr, cud) : ks265_cu_decide_b_ii(f, f->pub, ii ? f->icost : nullptr, cud))) return r;
+    if (f->cfg.bi_refine == 2 && (r = ks_bi_refine_chosen(f, src, lists, pu0, f->pu1, f->pub, cud))) return r;   /* the joint refinement, for the CUs the decision chose (round 5) */
+    if (f->cfg.merge && (r = ks_merge_pass(f, src, lists, nullptr, f->pub, f->cu8_tmp, f->cu8))) return r;
+    return inter_back_end(f, src, lists, f->cfg.skip_rd != 0, ii, f->cfg.sao == 0, recon_out, no_mark);
 }
 
 /* forget the temporal predictors (the next P picture starts like the first one after a key picture): for hosts that code key pictures on another frame object */

@@ -68,8 +68,6 @@ struct ks265_frame {
     unsigned *me_work = nullptr, *me_work_all[2] = {nullptr, nullptr};
     int *me_order = nullptr, *me_order_all[2] = {nullptr, nullptr};
     int me_order_off = 0;               // KS265_ME_ORDER_OFF: experiments
-    // multi-reference B picture being coded (ks265_encode_picture_b_mref sets it for the duration of the picture: ks265_bi_decide, ks265_merge_pass, ks265_cu_decide_part_b and
-    // ks265_reconstruct_b then take every block's pictures from its record); host-side copies of the lists + the per-PU index arrays and the extra list-1 PU records
     // cfg.rdoq (round 6; -rdoq 1 = the SDK's rdoq field, qy265enc.h:129): the luma transform blocks of inter CUs go through the reference's rdoQuant (rdoq_ops.hip) - front half of
     // ks265_reconstruct* (coefficients + levels rounded at 1 / 2 to planes), rdoq_prep_kernel (the blocks listed, packed, their significance masks and last positions), rdoq_kernel,
     // rdoq_unpack_kernel, back half (dequantisation, inverse transform, reconstruction).  Workspace allocated by ks265_frame_set_rdoq; tables + lambdas from the host per picture
@@ -81,12 +79,8 @@ struct ks265_frame {
     uint16_t *rq_sigmask = nullptr;
     unsigned long long *rq_hidden = nullptr;
     bool rq_ready = false;
-    bool mrefb = false;
-    bool mr_pslice = false;             // round 6: the context is a multi-reference P picture's (ks265_encode_picture_mref: two-list records, one list in the slice - the merge pass's zero candidate is uni-directional)
-    int mr_n[2] = {1, 1};
-    ks265_pic mr_pic[2][4] = {};
-    uint8_t *ridx[2] = {nullptr, nullptr};
-    ks265_pu *pu1_x[3] = {nullptr, nullptr, nullptr};
+    uint8_t *ridx[2] = {nullptr, nullptr};              // multi-reference B pictures: per list the index of every PU's picture (ks265_ref_pick) ...
+    ks265_pu *pu1_x[3] = {nullptr, nullptr, nullptr};   // ... and the records of list 1's pictures 1 .. refs - 1
     bool src_pyr_ready = false;         // ks265_presearch: the source picture's pyramid is in place (skip its pyr_down launch)
     int b_parallel = 1;                 // 0: the two searches one after the other on the context's stream (graph capture, experiments: KS265_B_SERIAL)
     // optional in-situ stage timing (HIP events on the context's stream, between the stages of ks265_encode_picture)
@@ -97,6 +91,22 @@ struct ks265_frame {
 };
 
 static inline ks265_pic ks_deb_pic(ks265_frame *f) { return ks265_pic{f->deb[0], f->deb[1], f->deb[2]}; }
+
+// The pictures a picture predicts from.  The sequencer (frame_api.hip) builds the value once per picture and hands it to every stage that reads reference pictures; the
+// exported stage functions build the one-picture-per-list value from their ref0 / ref1 arguments.  Nothing of it is kept on the frame object.
+struct KsPicLists {
+    int n[2];                 // pictures per list
+    ks265_pic pic[2][4];      // entries past n repeat the list's last picture
+    bool multi;               // a block's pictures come from its record (inter_dir = direction | idx0 << 4 | idx1 << 6): the multi-reference kernels
+    bool pslice;              // two-list records, one list in the slice (multi-reference P picture): no list-1 prediction, the merge pass's zero candidate is uni-directional
+};
+static inline KsPicLists ks_pic_lists(const ks265_pic *refs0, int n0, const ks265_pic *refs1, int n1, bool multi, bool pslice)
+{
+    KsPicLists L{{n0, n1}, {}, multi, pslice};
+    for (int i = 0; i < 4; ++i) { L.pic[0][i] = refs0[i < n0 ? i : n0 - 1]; L.pic[1][i] = refs1[i < n1 ? i : n1 - 1]; }
+    return L;
+}
+static inline KsPicLists ks_pic_lists(ks265_pic ref0, ks265_pic ref1) { return ks_pic_lists(&ref0, 1, &ref1, 1, false, false); }   // one picture per list (ref1 = null picture: P)
 
 __device__ __forceinline__ const uint8_t *ks_org_y(const KsGeom &g, const uint8_t *p) { return p + g.org_y; }
 __device__ __forceinline__ uint8_t *ks_org_y(const KsGeom &g, uint8_t *p) { return p + g.org_y; }
@@ -134,6 +144,13 @@ __device__ __forceinline__ void ctu_mv_limits(const KsGeom &g, int range, int cx
 int ks265_frame_build_matrices(ks265_frame *f);      // frame_recon.hip
 int ks265_presearch_source(ks265_frame *f, ks265_pic src);   // frame_presearch.hip
 int ks265_sao_off(ks265_frame *f, ks265_sao_param *sao, ks265_pic dst);   // frame_loop.hip: the tail of a picture coded without SAO, in place
+// the stages that read reference pictures, on explicit lists (the exported ks265_* functions of the same names wrap them; same argument checks)
+int ks_bi_decide(ks265_frame *f, ks265_pic src, const KsPicLists &lists, const ks265_pu *pu0, const ks265_pu *pu1, ks265_pu_b *pub);                                         // frame_me.hip
+int ks_bi_refine_chosen(ks265_frame *f, ks265_pic src, const KsPicLists &lists, const ks265_pu *pu0, const ks265_pu *pu1, ks265_pu_b *pub, ks265_cu8 *cu8);
+int ks_cu_decide_part_b(ks265_frame *f, ks265_pic src, const KsPicLists &lists, const ks265_pu *pu0, const ks265_pu *pu1, const ks265_pu_b *pub, const uint32_t *ibest, ks265_cu8 *cu8);
+int ks_merge_pass(ks265_frame *f, ks265_pic src, const KsPicLists &lists, const ks265_pu *pu, const ks265_pu_b *pub, const ks265_cu8 *cu_in, ks265_cu8 *cu_out);
+int ks_skip_pass(ks265_frame *f, ks265_pic src, const KsPicLists &lists, ks265_cu8 *cu8, int16_t *lvl_y, int16_t *lvl_u, int16_t *lvl_v, ks265_pic recon);                  // frame_skip.hip
+int ks_reconstruct(ks265_frame *f, ks265_pic src, const KsPicLists &lists, ks265_cu8 *cu8, int16_t *lvl_y, int16_t *lvl_u, int16_t *lvl_v, ks265_pic recon);                // frame_recon.hip (no checks: its callers made them)
 
 // every frame-level entry point: the calling thread's current device is the frame's (a host with one encoder lane per GPU drives several devices from several
 // threads; kernel launches go to the CURRENT device's streams only)

@@ -1010,28 +1010,29 @@ __global__ __launch_bounds__(64, 2) void bi_refine_chosen_kernel(KsGeom g, int l
     }
 }
 
-// the lists of the multi-reference B picture being coded as kernel arguments (entries past a list's size repeat its last picture); all zero when none is
-static KsMrefB ks_mrefb(const ks265_frame *f)
+// the lists of a multi-reference picture as kernel arguments; all zero when a block's pictures do not come from its record
+static KsMrefB ks_mref_args(const ks265_frame *f, const KsPicLists &lists)
 {
     KsMrefB m{};
-    if (!f->mrefb) return m;
+    if (!lists.multi) return m;
+    const int n0 = lists.n[0], n1 = lists.n[1];
     for (int i = 0; i < 4; ++i) {
-        m.y0.p[i] = f->mr_pic[0][i < f->mr_n[0] ? i : f->mr_n[0] - 1].y; m.y1.p[i] = f->mr_pic[1][i < f->mr_n[1] ? i : f->mr_n[1] - 1].y;
-        const int b0 = f->mr_n[0] <= 1 ? 0 : (i < f->mr_n[0] - 1 ? i + 1 : f->mr_n[0] - 1), b1 = f->mr_n[1] <= 1 ? 0 : (i < f->mr_n[1] - 1 ? i + 1 : f->mr_n[1] - 1);
+        m.y0.p[i] = lists.pic[0][i].y; m.y1.p[i] = lists.pic[1][i].y;
+        const int b0 = n0 <= 1 ? 0 : (i < n0 - 1 ? i + 1 : n0 - 1), b1 = n1 <= 1 ? 0 : (i < n1 - 1 ? i + 1 : n1 - 1);
         m.bits0[i] = (f->cfg.lambda_q4 * b0) >> 4; m.bits1[i] = (f->cfg.lambda_q4 * b1) >> 4;
     }
     m.idx0 = f->ridx[0]; m.idx1 = f->ridx[1];
     return m;
 }
 
-extern "C" int ks265_bi_decide(ks265_frame *f, ks265_pic src, ks265_pic ref0, ks265_pic ref1, const ks265_pu *pu0, const ks265_pu *pu1,
-                               ks265_pu_b *pub)
+int ks_bi_decide(ks265_frame *f, ks265_pic src, const KsPicLists &lists, const ks265_pu *pu0, const ks265_pu *pu1, ks265_pu_b *pub)
 {
     KS_FRAME_CHECK(f);
+    const ks265_pic ref0 = lists.pic[0][0], ref1 = lists.pic[1][0];
     if (!src.y || !ref0.y || !ref1.y || !pu0 || !pu1 || !pub) return KS265_POINTER;
     const dim3 grid(f->g.ctu_cols * f->g.ctu_rows), block(256);
-    const KsMrefB mr = ks_mrefb(f);
-    if (f->mrefb) {
+    const KsMrefB mr = ks_mref_args(f, lists);
+    if (lists.multi) {
         if (f->cfg.bi_refine == 1) hipLaunchKernelGGL((bi_decide_kernel<true, true>), grid, block, 0, f->ctx->stream, f->g, f->cfg.lambda_q4, src.y, ref0.y, ref1.y, pu0, pu1, pub, mr);
         else hipLaunchKernelGGL((bi_decide_kernel<false, true>), grid, block, 0, f->ctx->stream, f->g, f->cfg.lambda_q4, src.y, ref0.y, ref1.y, pu0, pu1, pub, mr);
     } else {
@@ -1040,17 +1041,25 @@ extern "C" int ks265_bi_decide(ks265_frame *f, ks265_pic src, ks265_pic ref0, ks
     }
     return ks265_check_launch(f->ctx);
 }
+extern "C" int ks265_bi_decide(ks265_frame *f, ks265_pic src, ks265_pic ref0, ks265_pic ref1, const ks265_pu *pu0, const ks265_pu *pu1, ks265_pu_b *pub)
+{
+    return ks_bi_decide(f, src, ks_pic_lists(ref0, ref1), pu0, pu1, pub);
+}
 
-extern "C" int ks265_bi_refine_chosen(ks265_frame *f, ks265_pic src, ks265_pic ref0, ks265_pic ref1, const ks265_pu *pu0, const ks265_pu *pu1,
-                                      ks265_pu_b *pub, ks265_cu8 *cu8)
+int ks_bi_refine_chosen(ks265_frame *f, ks265_pic src, const KsPicLists &lists, const ks265_pu *pu0, const ks265_pu *pu1, ks265_pu_b *pub, ks265_cu8 *cu8)
 {
     KS_FRAME_CHECK(f);
+    const ks265_pic ref0 = lists.pic[0][0], ref1 = lists.pic[1][0];
     if (!src.y || !ref0.y || !ref1.y || !pu0 || !pu1 || !pub || !cu8) return KS265_POINTER;
     const dim3 grid(f->g.ctu_cols * f->g.ctu_rows), block(64);
-    const KsMrefB mr = ks_mrefb(f);
-    if (f->mrefb) hipLaunchKernelGGL((bi_refine_chosen_kernel<true>), grid, block, 0, f->ctx->stream, f->g, f->cfg.lambda_q4, src.y, ref0.y, ref1.y, pu0, pu1, pub, cu8, mr);
+    const KsMrefB mr = ks_mref_args(f, lists);
+    if (lists.multi) hipLaunchKernelGGL((bi_refine_chosen_kernel<true>), grid, block, 0, f->ctx->stream, f->g, f->cfg.lambda_q4, src.y, ref0.y, ref1.y, pu0, pu1, pub, cu8, mr);
     else hipLaunchKernelGGL((bi_refine_chosen_kernel<false>), grid, block, 0, f->ctx->stream, f->g, f->cfg.lambda_q4, src.y, ref0.y, ref1.y, pu0, pu1, pub, cu8, mr);
     return ks265_check_launch(f->ctx);
+}
+extern "C" int ks265_bi_refine_chosen(ks265_frame *f, ks265_pic src, ks265_pic ref0, ks265_pic ref1, const ks265_pu *pu0, const ks265_pu *pu1, ks265_pu_b *pub, ks265_cu8 *cu8)
+{
+    return ks_bi_refine_chosen(f, src, ks_pic_lists(ref0, ref1), pu0, pu1, pub, cu8);
 }
 
 // ------------------------------------------------------------------ cfg.part: the halves of every 64 / 32 / 16 CU of a P picture (-part 1: 2NxN / Nx2N)
@@ -1254,16 +1263,21 @@ __global__ __launch_bounds__(192) void rect_eval_b_kernel(KsGeom g, int lam, con
     }
 }
 
-extern "C" int ks265_cu_decide_part_b(ks265_frame *f, ks265_pic src, ks265_pic ref0, ks265_pic ref1, const ks265_pu *pu0, const ks265_pu *pu1, const ks265_pu_b *pub, const uint32_t *ibest, ks265_cu8 *cu8)
+int ks_cu_decide_part_b(ks265_frame *f, ks265_pic src, const KsPicLists &lists, const ks265_pu *pu0, const ks265_pu *pu1, const ks265_pu_b *pub, const uint32_t *ibest, ks265_cu8 *cu8)
 {
     KS_FRAME_CHECK(f);
+    const ks265_pic ref0 = lists.pic[0][0], ref1 = lists.pic[1][0];
     if (!src.y || !ref0.y || !ref1.y || !pu0 || !pu1 || !pub || !cu8) return KS265_POINTER;
     if (!f->rect) return KS265_NOTSUPPORTED;                                      // the frame object was created without cfg.part
     const int nctu = f->g.ctu_cols * f->g.ctu_rows;
-    if (f->mrefb) hipLaunchKernelGGL(rect_eval_b_kernel<true>, dim3(nctu), dim3(192), 0, f->ctx->stream, f->g, f->cfg.lambda_q4, src.y, ref0.y, ref1.y, pu0, pu1, pub, (KsRect *)f->rect, ks_mrefb(f));
+    if (lists.multi) hipLaunchKernelGGL(rect_eval_b_kernel<true>, dim3(nctu), dim3(192), 0, f->ctx->stream, f->g, f->cfg.lambda_q4, src.y, ref0.y, ref1.y, pu0, pu1, pub, (KsRect *)f->rect, ks_mref_args(f, lists));
     else hipLaunchKernelGGL(rect_eval_b_kernel<false>, dim3(nctu), dim3(192), 0, f->ctx->stream, f->g, f->cfg.lambda_q4, src.y, ref0.y, ref1.y, pu0, pu1, pub, (KsRect *)f->rect, KsMrefB{});
     hipLaunchKernelGGL(cu_decide_kernel<ks265_pu_b>, dim3(nctu), dim3(64), 0, f->ctx->stream, f->g, f->cfg.lambda_q4, pub, cu8, ibest, (const KsRect *)f->rect);
     return ks265_check_launch(f->ctx);
+}
+extern "C" int ks265_cu_decide_part_b(ks265_frame *f, ks265_pic src, ks265_pic ref0, ks265_pic ref1, const ks265_pu *pu0, const ks265_pu *pu1, const ks265_pu_b *pub, const uint32_t *ibest, ks265_cu8 *cu8)
+{
+    return ks_cu_decide_part_b(f, src, ks_pic_lists(ref0, ref1), pu0, pu1, pub, ibest, cu8);
 }
 
 extern "C" int ks265_cu_decide_part(ks265_frame *f, ks265_pic src, ks265_pic ref, const ks265_pu *pu, const uint32_t *ibest, ks265_cu8 *cu8)
@@ -1402,14 +1416,18 @@ __global__ __launch_bounds__(256) void merge_pass_kernel(KsGeom g, int lam, cons
     }
 }
 
-extern "C" int ks265_merge_pass(ks265_frame *f, ks265_pic src, ks265_pic ref0, ks265_pic ref1, const ks265_pu *pu, const ks265_pu_b *pub,
-                                const ks265_cu8 *cu_in, ks265_cu8 *cu_out)
+int ks_merge_pass(ks265_frame *f, ks265_pic src, const KsPicLists &lists, const ks265_pu *pu, const ks265_pu_b *pub, const ks265_cu8 *cu_in, ks265_cu8 *cu_out)
 {
     KS_FRAME_CHECK(f);
+    const ks265_pic ref0 = lists.pic[0][0], ref1 = lists.pic[1][0];
     if (!src.y || !ref0.y || !cu_in || !cu_out || cu_in == cu_out || (!pu && !pub) || (pub && !ref1.y)) return KS265_POINTER;
-    if (f->mrefb && pub) hipLaunchKernelGGL(merge_pass_kernel<true>, dim3(f->g.ctu_cols * f->g.ctu_rows), dim3(256), 0, f->ctx->stream, f->g, f->cfg.lambda_q4, src.y, ref0.y, ref1.y, pu, pub, cu_in, cu_out, ks_mrefb(f), f->mr_pslice ? 1 : 0);
+    if (lists.multi && pub) hipLaunchKernelGGL(merge_pass_kernel<true>, dim3(f->g.ctu_cols * f->g.ctu_rows), dim3(256), 0, f->ctx->stream, f->g, f->cfg.lambda_q4, src.y, ref0.y, ref1.y, pu, pub, cu_in, cu_out, ks_mref_args(f, lists), lists.pslice ? 1 : 0);
     else hipLaunchKernelGGL(merge_pass_kernel<false>, dim3(f->g.ctu_cols * f->g.ctu_rows), dim3(256), 0, f->ctx->stream, f->g, f->cfg.lambda_q4, src.y, ref0.y, ref1.y, pu, pub, cu_in, cu_out, KsMrefB{}, 0);
     return ks265_check_launch(f->ctx);
+}
+extern "C" int ks265_merge_pass(ks265_frame *f, ks265_pic src, ks265_pic ref0, ks265_pic ref1, const ks265_pu *pu, const ks265_pu_b *pub, const ks265_cu8 *cu_in, ks265_cu8 *cu_out)
+{
+    return ks_merge_pass(f, src, ks_pic_lists(ref0, ref1), pu, pub, cu_in, cu_out);
 }
 
 extern "C" int ks265_cu_flat_intra(ks265_frame *f, ks265_cu8 *cu8)

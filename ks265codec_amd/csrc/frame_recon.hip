@@ -501,13 +501,22 @@ static int reconstruct_sequence(ks265_frame *f, ks265_cu8 *cu8, int16_t *lvl_y, 
     return ks265_check_launch(f->ctx);
 }
 
-static int launch_reconstruct(ks265_frame *f, ks265_pic src, ks265_pic ref0, ks265_pic ref1, ks265_cu8 *cu8,
-                              int16_t *lvl_y, int16_t *lvl_u, int16_t *lvl_v, ks265_pic recon)
+// the one launch of the reconstruction.  lists.multi: every CU's pictures from its record (reconstruct_kernel<true>), pictures 1 .. 3 of the lists as KsRefExtra.  A P slice's
+// list 1 is not handed over, nor are list 0's repeats past its n pictures (no record of the picture names them)
+int ks_reconstruct(ks265_frame *f, ks265_pic src, const KsPicLists &lists, ks265_cu8 *cu8, int16_t *lvl_y, int16_t *lvl_u, int16_t *lvl_v, ks265_pic recon)
 {
+    const ks265_pic ref0 = lists.pic[0][0], ref1 = lists.pslice ? ks265_pic{nullptr, nullptr, nullptr} : lists.pic[1][0];
+    KsRefExtra xr{};
+    for (int r = 1; r < 4 && lists.multi; ++r) {
+        const ks265_pic a = lists.pic[0][r], b = lists.pic[1][r];
+        if (!lists.pslice || r < lists.n[0]) { xr.y.r[r - 1] = a.y; xr.u.r[r - 1] = a.u; xr.v.r[r - 1] = a.v; }
+        if (!lists.pslice) { xr.y.s[r - 1] = b.y; xr.u.s[r - 1] = b.u; xr.v.s[r - 1] = b.v; }
+    }
+    const auto kernel = !lists.multi ? reconstruct_kernel<false> : reconstruct_kernel<true>;      // (<false> first: the order the two instances have in the code object)
     dim3 grid(((f->g.W + 31) / 32) * ((f->g.H + 31) / 32));
     return reconstruct_sequence(f, cu8, lvl_y, [&](int rq_mode) {
-    hipLaunchKernelGGL(reconstruct_kernel<false>, grid, dim3(256), 0, f->ctx->stream, f->g, f->cfg.qp, src.y, src.u, src.v, ref0.y, ref0.u, ref0.v, ref1.y,
-                       ref1.u, ref1.v, cu8, lvl_y, lvl_u, lvl_v, recon.y, recon.u, recon.v, f->mats, KsRefExtra{}, f->cfg.sdh, f->cfg.decimate, ks_rdo_lam2k(f), f->qp_map, f->cfg.tu_inter, rq_mode, f->rq_coef);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, f->ctx->stream, f->g, f->cfg.qp, src.y, src.u, src.v, ref0.y, ref0.u, ref0.v, ref1.y,
+                       ref1.u, ref1.v, cu8, lvl_y, lvl_u, lvl_v, recon.y, recon.u, recon.v, f->mats, xr, f->cfg.sdh, f->cfg.decimate, ks_rdo_lam2k(f), f->qp_map, f->cfg.tu_inter, rq_mode, f->rq_coef);
     });
 }
 
@@ -518,17 +527,8 @@ extern "C" int ks265_reconstruct_mref(ks265_frame *f, ks265_pic src, int nref, c
     KS_FRAME_CHECK(f);
     if (!src.y || !refs || !cu8 || !lvl_y || !lvl_u || !lvl_v || !recon.y) return KS265_POINTER;
     if (nref < 1 || nref > 4) return KS265_NOTSUPPORTED;
-    KsRefExtra xr{};
-    for (int r = 1; r < nref; ++r) {
-        if (!refs[r].y) return KS265_POINTER;
-        xr.y.r[r - 1] = refs[r].y; xr.u.r[r - 1] = refs[r].u; xr.v.r[r - 1] = refs[r].v;
-    }
-    dim3 grid(((f->g.W + 31) / 32) * ((f->g.H + 31) / 32));
-    return reconstruct_sequence(f, cu8, lvl_y, [&](int rq_mode) {
-    hipLaunchKernelGGL(reconstruct_kernel<true>, grid, dim3(256), 0, f->ctx->stream, f->g, f->cfg.qp, src.y, src.u, src.v, refs[0].y, refs[0].u, refs[0].v,
-                       (const uint8_t *)nullptr, (const uint8_t *)nullptr, (const uint8_t *)nullptr, cu8, lvl_y, lvl_u, lvl_v, recon.y, recon.u,
-                       recon.v, f->mats, xr, f->cfg.sdh, f->cfg.decimate, ks_rdo_lam2k(f), f->qp_map, f->cfg.tu_inter, rq_mode, f->rq_coef);
-    });
+    for (int r = 1; r < nref; ++r) if (!refs[r].y) return KS265_POINTER;
+    return ks_reconstruct(f, src, ks_pic_lists(refs, nref, refs, 1, true, true), cu8, lvl_y, lvl_u, lvl_v, recon);
 }
 
 extern "C" int ks265_reconstruct(ks265_frame *f, ks265_pic src, ks265_pic ref, ks265_cu8 *cu8, int16_t *lvl_y, int16_t *lvl_u,
@@ -536,7 +536,7 @@ extern "C" int ks265_reconstruct(ks265_frame *f, ks265_pic src, ks265_pic ref, k
 {
     KS_FRAME_CHECK(f);
     if (!src.y || !cu8 || !lvl_y || !lvl_u || !lvl_v || !recon.y) return KS265_POINTER;
-    return launch_reconstruct(f, src, ref, ks265_pic{nullptr, nullptr, nullptr}, cu8, lvl_y, lvl_u, lvl_v, recon);
+    return ks_reconstruct(f, src, ks_pic_lists(ref, ks265_pic{nullptr, nullptr, nullptr}), cu8, lvl_y, lvl_u, lvl_v, recon);
 }
 
 extern "C" int ks265_reconstruct_b(ks265_frame *f, ks265_pic src, ks265_pic ref0, ks265_pic ref1,
@@ -544,18 +544,5 @@ extern "C" int ks265_reconstruct_b(ks265_frame *f, ks265_pic src, ks265_pic ref0
 {
     KS_FRAME_CHECK(f);
     if (!src.y || !ref0.y || !ref1.y || !cu8 || !lvl_y || !lvl_u || !lvl_v || !recon.y) return KS265_POINTER;
-    if (f->mrefb) {                                                   // several pictures per list: every CU's pictures from its record (the lists of ks265_encode_picture_b_mref)
-        KsRefExtra xr{};
-        for (int r = 1; r < 4; ++r) {
-            const ks265_pic a = f->mr_pic[0][r < f->mr_n[0] ? r : f->mr_n[0] - 1], b = f->mr_pic[1][r < f->mr_n[1] ? r : f->mr_n[1] - 1];
-            xr.y.r[r - 1] = a.y; xr.u.r[r - 1] = a.u; xr.v.r[r - 1] = a.v; xr.y.s[r - 1] = b.y; xr.u.s[r - 1] = b.u; xr.v.s[r - 1] = b.v;
-        }
-        const ks265_pic a0 = f->mr_pic[0][0], b0 = f->mr_pic[1][0];
-        dim3 grid(((f->g.W + 31) / 32) * ((f->g.H + 31) / 32));
-        return reconstruct_sequence(f, cu8, lvl_y, [&](int rq_mode) {
-        hipLaunchKernelGGL(reconstruct_kernel<true>, grid, dim3(256), 0, f->ctx->stream, f->g, f->cfg.qp, src.y, src.u, src.v, a0.y, a0.u, a0.v, b0.y, b0.u, b0.v, cu8, lvl_y, lvl_u, lvl_v,
-                           recon.y, recon.u, recon.v, f->mats, xr, f->cfg.sdh, f->cfg.decimate, ks_rdo_lam2k(f), f->qp_map, f->cfg.tu_inter, rq_mode, f->rq_coef);
-        });
-    }
-    return launch_reconstruct(f, src, ref0, ref1, cu8, lvl_y, lvl_u, lvl_v, recon);
+    return ks_reconstruct(f, src, ks_pic_lists(ref0, ref1), cu8, lvl_y, lvl_u, lvl_v, recon);
 }

@@ -386,23 +386,28 @@ __global__ __launch_bounds__(128, KS_SKIP_OCC) void skip_pass_kernel(KsGeom g, l
 }
 
 // dev_cu8: the picture's CU map after ks265_reconstruct* (cbf set); the frame's spare map takes the snapshot the candidates are read from
-extern "C" int ks265_skip_pass(ks265_frame *f, ks265_pic src, ks265_pic ref0, ks265_pic ref1, ks265_cu8 *dev_cu8, int16_t *dev_lvl_y, int16_t *dev_lvl_u, int16_t *dev_lvl_v, ks265_pic recon)
+int ks_skip_pass(ks265_frame *f, ks265_pic src, const KsPicLists &lists, ks265_cu8 *dev_cu8, int16_t *dev_lvl_y, int16_t *dev_lvl_u, int16_t *dev_lvl_v, ks265_pic recon)
 {
     KS_FRAME_CHECK(f);
+    const ks265_pic ref0 = lists.pic[0][0];
     if (!src.y || !src.u || !src.v || !ref0.y || !ref0.u || !ref0.v || !dev_cu8 || !dev_lvl_y || !dev_lvl_u || !dev_lvl_v || !recon.y || !recon.u || !recon.v) return KS265_POINTER;
     if (!f->cu8_tmp) return KS265_NOTSUPPORTED;                          // the frame object was created without cfg.merge / cfg.skip_rd
     if (dev_cu8 == f->cu8_tmp) return KS265_POINTER;
     int r = ks265_hip(f->ctx, hipMemcpyAsync(f->cu8_tmp, dev_cu8, (size_t)f->geom.bytes_cu8, hipMemcpyDeviceToDevice, f->ctx->stream));
     if (r) return r;
-    const bool is_b = ref1.y != nullptr || (f->mrefb && !f->mr_pslice);
+    const bool is_b = !lists.pslice && lists.pic[1][0].y != nullptr;       // the slice has a list 1
     KsSkipRefs R;
     for (int i = 0; i < 4; ++i) {
-        const ks265_pic a = f->mrefb ? f->mr_pic[0][i] : ref0, b = f->mrefb ? f->mr_pic[1][i] : (ref1.y ? ref1 : ref0);
+        const ks265_pic a = lists.pic[0][i], b = lists.pic[1][i].y ? lists.pic[1][i] : a;      // (no list 1: its slots repeat list 0's picture)
         R.y0[i] = a.y; R.u0[i] = a.u; R.v0[i] = a.v; R.y1[i] = b.y; R.u1[i] = b.u; R.v1[i] = b.v;
     }
     const long long lam2 = ((long long)f->cfg.lambda_q4 * f->cfg.lambda_q4 * SP_LAMBDA_Q4) >> 4;
     const int nctu = f->g.ctu_cols * f->g.ctu_rows;
-    if (f->mrefb) hipLaunchKernelGGL(skip_pass_kernel<true>, dim3(nctu), dim3(128), 0, f->ctx->stream, f->g, lam2, is_b ? 1 : 0, src.y, src.u, src.v, R, f->cu8_tmp, dev_cu8, dev_lvl_y, dev_lvl_u, dev_lvl_v, recon.y, recon.u, recon.v);
+    if (lists.multi) hipLaunchKernelGGL(skip_pass_kernel<true>, dim3(nctu), dim3(128), 0, f->ctx->stream, f->g, lam2, is_b ? 1 : 0, src.y, src.u, src.v, R, f->cu8_tmp, dev_cu8, dev_lvl_y, dev_lvl_u, dev_lvl_v, recon.y, recon.u, recon.v);
     else hipLaunchKernelGGL(skip_pass_kernel<false>, dim3(nctu), dim3(128), 0, f->ctx->stream, f->g, lam2, is_b ? 1 : 0, src.y, src.u, src.v, R, f->cu8_tmp, dev_cu8, dev_lvl_y, dev_lvl_u, dev_lvl_v, recon.y, recon.u, recon.v);
     return ks265_check_launch(f->ctx);
+}
+extern "C" int ks265_skip_pass(ks265_frame *f, ks265_pic src, ks265_pic ref0, ks265_pic ref1, ks265_cu8 *dev_cu8, int16_t *dev_lvl_y, int16_t *dev_lvl_u, int16_t *dev_lvl_v, ks265_pic recon)
+{
+    return ks_skip_pass(f, src, ks_pic_lists(ref0, ref1), dev_cu8, dev_lvl_y, dev_lvl_u, dev_lvl_v, recon);
 }
