@@ -25,6 +25,9 @@
  *   - sao: every level > 0, the presets' 3 (veryfast, fast) included, = this build's rule over all four edge classes + band offset; sao 3 set BY NAME (QY265ConfigParse "sao" "3" =
  *     `-sao 3`, stored as 5) = the reference's decision on its -sao 4 path (band offset + the 0 / 90 degree edge classes, its estimation functions, rates and lambda table, no merge
  *     candidates) - measured on configs[0]: 5.5 % more bytes at equal PSNR-Y than the build's rule, which is why the presets do not select it;
+ *   - sao-ref (not in the SDK; QY265ConfigParse "sao-ref" = `-sao-ref`): the reference's decision under a name of its own - "1" = what sao 3 by name selects (stored as 5),
+ *     "2" = the same with the reference's merge candidates (stored as 6): a CTU whose left or upper CTU's final parameters are strictly cheaper on its own statistics takes
+ *     them and codes sao_merge_left_flag / sao_merge_up_flag instead of its parameters; "0" leaves sao as it is.  No preset selects it;
  *   - transskip, tuIntra, vpp_*, 2-pass, long-term references, VBV / CVQ: accepted, ignored;
  *   - input pictures: the caller's planes are pinned in place and uploaded from where they lie inside QY265EncoderEncodeFrame; the caller may reuse its buffers when the call returns
  *     (the SDK requires them to stay valid until the frame is done);

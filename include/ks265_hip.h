@@ -320,7 +320,8 @@ typedef struct {
                                   1 6 3 0 5 4 2 7; strict '<' against the integer cost; fast = only candidates within +-2 quarter samples of the integer position and
                                   diagonals next to the running winner) - restated in oracle/ks265_subme_ref.c, pinned on recorded calls (tests/test_subme.py) */
     int32_t deblock;           /* -df                                                               */
-    int32_t sao;               /* -sao: 0 off, 1 BO + EO0..3 (this build's rule), 2 = the reference's decision: BO + EO0 / EO1 by CEncSao::modeDecisionBoEo01 enc@0x4af300 */
+    int32_t sao;               /* -sao: 0 off, 1 BO + EO0..3 (this build's rule), 2 = the reference's decision: BO + EO0 / EO1 by CEncSao::modeDecisionBoEo01 enc@0x4af300,
+                                * 3 = 2 + its merge candidates (checkMerge enc@0x4ae7f0): a CTU may take the final parameters of its left or upper CTU, flagged in ks265_sao_param.rsv; pictures of up to 136 CTU rows */
     int32_t beta_offset_div2, tc_offset_div2;
     int32_t bframes;           /* > 0: allocate the second-list workspace (planes, PU records) for B pictures (-bframes) */
     int32_t refs;              /* list-0 reference pictures a P picture may search (-ref / -ref0), 0 or 1 = one, at most 4 */
@@ -391,7 +392,11 @@ typedef struct { int16_t mvx, mvy; /* list 0 */ int16_t mv1x, mv1y; /* list 1 */
 /* B pictures: the per-PU winner among L0, L1 and bi-prediction */
 typedef struct { int16_t mvx, mvy, mv1x, mv1y; uint32_t cost; uint32_t inter_dir; } ks265_pu_b;
 /* SAO decision per CTU and component */
+/* rsv of a CTU's LUMA record (index 3 * ctu): rsv[0] = sao_merge_left_flag, rsv[1] = sao_merge_up_flag (0 / 1, never both; only cfg.sao = 3 sets them); the two chroma records keep
+ * rsv = 0.  A merged CTU's three records hold copies of the neighbour's type, band and offsets, so that the apply step and every reader work without following the flags. */
 typedef struct { int8_t type; /* -1 off, 0 BO, 1..4 EO class 0..3 */ int8_t band; int8_t offset[4]; int8_t rsv[2]; } ks265_sao_param;
+#define KS265_SAO_MERGE_LEFT 0      /* indices into ks265_sao_param.rsv of a luma record */
+#define KS265_SAO_MERGE_UP 1
 
 /* a padded YUV 4:2:0 picture in HBM (pointers to the first byte of each allocation) */
 typedef struct { uint8_t *y, *u, *v; } ks265_pic;
@@ -409,7 +414,8 @@ int ks265_frame_set_qp(ks265_frame *f, int qp, int lambda_q4);
 /* round 6 - tools per picture: a host that codes a whole pyramid on one frame object lowers tools for some of its pictures (host/ks265_enc.c: the B pictures nothing predicts
  * from run without intra candidates, without the joint refinement and without SAO - measured on the CPU mirror and on the MI355X: the bytes at equal PSNR-Y stay, a quarter
  * of such a picture's kernel time goes).  Each argument: -1 = the value the frame object was created with, else the value cfg.intra_inter / cfg.bi_refine / cfg.sao take for
- * the pictures coded from now on - 0 or the created value (the workspace is the creation's); me_method: -1 = as created, else 0 .. 2 (interMeDia / interMeHex / interMeUMH: the
+ * the pictures coded from now on - 0 or the created value (the workspace is the creation's; a frame object created with sao = 3 also runs sao = 2, the same decision without
+ * the merge chain); me_method: -1 = as created, else 0 .. 2 (interMeDia / interMeHex / interMeUMH: the
  * search method needs no workspace of its own).  With cfg.sao = 0 a B picture is reconstructed and deblocked straight in
  * recon_out (no SAO launch, no copy); its SAO records are written as "off" and the host passes ks265_slice_in.sao = NULL (slice_sao_luma_flag = slice_sao_chroma_flag = 0). */
 int ks265_frame_set_picture_tools(ks265_frame *f, int intra_inter, int bi_refine, int sao, int me_method);
@@ -526,7 +532,9 @@ int ks265_intra_reconstruct(ks265_frame *, ks265_pic src, ks265_cu8 *dev_cu8, in
  * enc@0x403de0, CtuDeblockFilterHorT enc@0x477200) */
 int ks265_deblock(ks265_frame *f, const ks265_cu8 *dev_cu8, ks265_pic recon);
 /* Stage F: SAO statistics + decision + apply (CEncSao::modeDecisionCtu enc@0x4af690, qy265SaoApplyOffset
- * enc@0x43fc00); dst becomes the next reference picture (borders padded) */
+ * enc@0x43fc00); dst becomes the next reference picture (borders padded).  cfg.sao = 1, 2: one launch, a work-group per CTU.  cfg.sao = 3: three launches - statistics + own
+ * decision per CTU into the frame object's workspace, the merge chain (ONE work-group walks the anti-diagonals cx + cy: a CTU's final record needs those of its left and upper
+ * CTU), the apply per CTU; records with the merge flags in rsv (ks265_sao_param).  Needs a frame object created with sao = 3 (KS265_NOTSUPPORTED otherwise). */
 /* cfg.rdoq (round 6; the SDK's rdoq field, qy265enc.h:129): with tables set, ks265_reconstruct / _b / _mref send the luma transform blocks of inter CUs through the reference's
  * rdoQuant (the operator of ks265_rdoq_batch: levels q / q - 1 / 0, last position, all-zero groups, sign-data hiding by RD cost) between a front half (transform, levels rounded at
  * 1 / 2) and a back half (dequantisation, inverse transform) - in place of dead zone + coefficient-group pruning + sign-data hiding at the seam.  host_tables: [4 sizes][luma,

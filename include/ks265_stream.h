@@ -59,7 +59,9 @@ typedef struct {
     /* records of the HIP stages (HOST copies): CU map (W/8 x H/8), levels (W x H, W/2 x H/2 x 2, TU in place), SAO (3 per CTU) */
     const ks265_cu8 *cu8;
     const int16_t *lvl[3];
-    const ks265_sao_param *sao;            /* NULL = SAO off for this picture                                                        */
+    const ks265_sao_param *sao;            /* NULL = SAO off for this picture.  rsv[0] / rsv[1] of a CTU's luma record = sao_merge_left_flag / sao_merge_up_flag: after a flag
+                                            * of 1 nothing more is coded for the CTB (7.3.8.3).  A flagged CTU must be usable - the neighbour exists, one flag at most, all three
+                                            * records equal the neighbour's - else the slice call returns KS265_NOTSUPPORTED                                       */
     const int8_t *qp_map;                  /* cfg.cu_qp_delta: the QP each CTU's residual was quantised with (raster order); NULL = the slice QP everywhere.
                                             * cu_qp_delta goes out with the first coded residual of a CTU, predicted from the previous CTU of the row (8.6.1)  */
 } ks265_slice_in;

@@ -26,6 +26,7 @@ int ks265_frame_create(ks265_ctx *ctx, const ks265_frame_cfg *cfg, ks265_frame *
     if (cfg->me_method < 0 || cfg->me_method > 2) return KS265_NOTSUPPORTED;   /* 0 = DIA, 1 = HEX, 2 = UMH (-me); EPZS / Cross not built */
     if (cfg->refs > 4 || cfg->propagate < 0 || cfg->propagate > 4) return KS265_NOTSUPPORTED;
     if ((long long)geom.bytes_y >= (1ll << 31)) return KS265_NOTSUPPORTED;         /* stage B addresses a luma plane with 32-bit offsets */
+    if (cfg->sao == 3 && geom.ctu_rows > KS_SAO_CHAIN_ROWS) return KS265_NOTSUPPORTED;   /* the merge chain keeps one record set per CTU row in LDS */
     ks265_frame *f = new ks265_frame();                                            /* every validation above: nothing to undo on those returns */
     f->ctx = ctx; f->cfg = *cfg; f->cfg0 = *cfg; f->geom = geom;
     f->me_order_off = getenv("KS265_ME_ORDER_OFF") ? 1 : 0;
@@ -62,6 +63,7 @@ int ks265_frame_create(ks265_ctx *ctx, const ks265_frame_cfg *cfg, ks265_frame *
     if (!r) r = dev_alloc(ctx, (void **)&f->cu8, (size_t)geom.bytes_cu8, true);
     if (!r && (cfg->merge || cfg->skip_rd)) r = dev_alloc(ctx, (void **)&f->cu8_tmp, (size_t)geom.bytes_cu8, true);      /* the CU decision's map in front of the merge pass; the skip pass's snapshot */
     if (!r) r = dev_alloc(ctx, (void **)&f->sao, (size_t)geom.bytes_sao, true);
+    if (!r && cfg->sao == 3) r = dev_alloc(ctx, (void **)&f->sao_ws, (size_t)geom.ctu_cols * geom.ctu_rows * KS_SAO_WS_WORDS * sizeof(int), true);   /* the merge chain's input */
     if (!r) r = dev_alloc(ctx, (void **)&f->lvl[0], npx * 2, true);
     if (!r) r = dev_alloc(ctx, (void **)&f->lvl[1], npx / 2, true);
     if (!r) r = dev_alloc(ctx, (void **)&f->lvl[2], npx / 2, true);
@@ -90,7 +92,7 @@ void ks265_frame_destroy(ks265_frame *f)
     if (f->ev_join) (void)hipEventDestroy(f->ev_join);
     for (int i = 0; i < 10; ++i)
         if (f->pyr2[i] && f->pyr2[i] != f->pyr[i]) (void)hipFree(f->pyr2[i]);
-    void *ptrs[] = {f->rq_coef, f->rq_pack_lvl, f->rq_pack_coef, f->rq_tus, f->rq_pos, f->rq_ctr, f->rq_out, f->rq_tab, f->rq_lam, f->rq_sigmask, f->rq_hidden, f->ic_work, f->pu1_x[0], f->pu1_x[1], f->pu1_x[2], f->ridx[0], f->ridx[1], f->pu_s2, f->pu1, f->pu_s, f->pub, f->pu[0], f->pu[1], f->cu8, f->sao, f->lvl[0], f->lvl[1], f->lvl[2], f->deb[0], f->deb[1], f->deb[2], f->sse, f->sse_acc, f->cu8_tmp, f->progress, f->mats, f->icost, f->rect, f->pu_x[0], f->pu_x[1], f->pu_x[2]};
+    void *ptrs[] = {f->rq_coef, f->rq_pack_lvl, f->rq_pack_coef, f->rq_tus, f->rq_pos, f->rq_ctr, f->rq_out, f->rq_tab, f->rq_lam, f->rq_sigmask, f->rq_hidden, f->ic_work, f->pu1_x[0], f->pu1_x[1], f->pu1_x[2], f->ridx[0], f->ridx[1], f->pu_s2, f->pu1, f->pu_s, f->pub, f->pu[0], f->pu[1], f->cu8, f->sao, f->sao_ws, f->lvl[0], f->lvl[1], f->lvl[2], f->deb[0], f->deb[1], f->deb[2], f->sse, f->sse_acc, f->cu8_tmp, f->progress, f->mats, f->icost, f->rect, f->pu_x[0], f->pu_x[1], f->pu_x[2]};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (uint8_t *p : f->pyr)
@@ -119,7 +121,7 @@ int ks265_frame_set_picture_tools(ks265_frame *f, int intra_inter, int bi_refine
 {
     KS_FRAME_CHECK(f);
     const int ii = intra_inter < 0 ? f->cfg0.intra_inter : intra_inter, br = bi_refine < 0 ? f->cfg0.bi_refine : bi_refine, so = sao < 0 ? f->cfg0.sao : sao;
-    if ((ii && ii != f->cfg0.intra_inter) || (br && br != f->cfg0.bi_refine) || (so && so != f->cfg0.sao)) return KS265_NOTSUPPORTED;   /* off, or what the workspace was made for */
+    if ((ii && ii != f->cfg0.intra_inter) || (br && br != f->cfg0.bi_refine) || (so && so != f->cfg0.sao && !(so == 2 && f->cfg0.sao == 3))) return KS265_NOTSUPPORTED;   /* off, or what the workspace was made for (sao 3 = sao 2 + the merge chain) */
     if (me_method > 2) return KS265_NOTSUPPORTED;
     f->cfg.intra_inter = ii; f->cfg.bi_refine = br; f->cfg.sao = so; f->cfg.me_method = me_method < 0 ? f->cfg0.me_method : me_method;
     return KS265_OK;

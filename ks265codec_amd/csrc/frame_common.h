@@ -5,6 +5,8 @@
 #define KS_PAD_Y 80
 #define KS_PAD_C 40
 #define KS_COST_INVALID 0xFFFFFFFFu
+#define KS_SAO_WS_WORDS 320            // cfg.sao == 3: words per CTU of ks265_frame::sao_ws
+#define KS_SAO_CHAIN_ROWS 136          // ... and the CTU rows its merge chain keeps a diagonal's records in LDS for (pictures up to 8704 rows of samples)
 #define KS_NSTAGE 8                   // me_integer, me_subpel, intra_candidates, cu_decide (+ merge pass), reconstruct, intra_pass, deblock, sao (+ padding)
 
 // geometry handed to kernels by value
@@ -45,6 +47,7 @@ struct ks265_frame {
     ks265_cu8 *cu8 = nullptr;
     ks265_cu8 *cu8_tmp = nullptr;        // cfg.merge: the CU decision's map, input of the merge pass
     ks265_sao_param *sao = nullptr;
+    int *sao_ws = nullptr;               // cfg.sao == 3: per CTU the statistics, own records and own cost the merge chain reads (KS_SAO_WS_WORDS words, frame_loop.hip)
     int16_t *lvl[3] = {nullptr, nullptr, nullptr};
     uint8_t *deb[3] = {nullptr, nullptr, nullptr};   // reconstructed picture before SAO (padded geometry)
     unsigned long long *sse = nullptr;

@@ -258,6 +258,42 @@ __device__ __forceinline__ int sao_ref_eo(int lam, const int *count, const int *
     return total;
 }
 
+// the candidates of modeDecisionBoEo01 in the reference's order, on the priced bands and edge classes of the three components: sel[3] = the CTU's own records, by / buv = the
+// costs of its luma and chroma choice (what the merge candidates of cfg.sao == 3 are compared with)
+__device__ __forceinline__ void sao_ref_decide(const int (*rb_off)[32], const int (*rb_cost)[32], const int (*re_cost)[2], const int8_t (*re_off)[2][4], int lamY, int lamC,
+                                               ks265_sao_param *sel, int &by, int &buv)
+{
+    ks265_sao_param off;
+    off.type = -1; off.band = 0; off.offset[0] = off.offset[1] = off.offset[2] = off.offset[3] = 0; off.rsv[0] = off.rsv[1] = 0;
+    sel[0] = sel[1] = sel[2] = off;
+    int bandc[3], bcost[3];
+    for (int c = 0; c < 3; ++c) {                                  // the first of the 28 windows of four bands with the smallest cost sum
+        int bc = 0xffff000, bb = 0;
+        for (int k = 0; k < 28; ++k) { const int cc = rb_cost[c][k] + rb_cost[c][k + 1] + rb_cost[c][k + 2] + rb_cost[c][k + 3]; if (cc < bc) { bc = cc; bb = k; } }
+        bandc[c] = bb; bcost[c] = bc;
+    }
+    int best = (lamY + 128) >> 8;
+    for (int cls = 0; cls < 2; ++cls) {
+        const int cost = re_cost[0][cls] + ((4 * lamY + 128) >> 8);
+        if (cost < best) { best = cost; sel[0].type = (int8_t)(1 + cls); sel[0].band = 0; for (int k = 0; k < 4; ++k) sel[0].offset[k] = re_off[0][cls][k]; }
+    }
+    if (bcost[0] + ((7 * lamY + 128) >> 8) < best) { best = bcost[0] + ((7 * lamY + 128) >> 8); sel[0].type = 0; sel[0].band = (int8_t)bandc[0]; for (int k = 0; k < 4; ++k) sel[0].offset[k] = (int8_t)rb_off[0][bandc[0] + k]; }
+    by = best;
+    best = (lamC + 128) >> 8;
+    for (int cls = 0; cls < 2; ++cls) {
+        const int cost = re_cost[1][cls] + re_cost[2][cls] + ((4 * lamC + 128) >> 8);
+        if (cost < best) {
+            best = cost;
+            for (int c = 1; c < 3; ++c) { sel[c].type = (int8_t)(1 + cls); sel[c].band = 0; for (int k = 0; k < 4; ++k) sel[c].offset[k] = re_off[c][cls][k]; }
+        }
+    }
+    if (bcost[1] + bcost[2] + ((12 * lamC + 128) >> 8) < best) {
+        best = bcost[1] + bcost[2] + ((12 * lamC + 128) >> 8);
+        for (int c = 1; c < 3; ++c) { sel[c].type = 0; sel[c].band = (int8_t)bandc[c]; for (int k = 0; k < 4; ++k) sel[c].offset[k] = (int8_t)rb_off[c][bandc[c] + k]; }
+    }
+    buv = best;
+}
+
 // ---- LDS-staged CTU tiles: deblocked samples with a 1-sample halo (row pitch TP, sample (0,0) at [1][4]) + source samples.
 // One thread owns a 4x4 block: 6 rows x 3 dwords of the deblocked tile feed all four EO classes of its 16 samples.
 // Per-thread EO statistics are PACKED: per class one register of four 8-bit counts and two registers of two 16-bit sums
@@ -442,31 +478,8 @@ __global__ __launch_bounds__(256) void sao_ctu_kernel(KsGeom g, int lam, int ena
         else if (tid < 102) { const int c = (tid - 96) >> 1, cls = (tid - 96) & 1; re_cost[c][cls] = sao_ref_eo(c ? lamC : lamY, st[c].cnt[1 + cls], st[c].sum[1 + cls], re_off[c][cls]); }
         __syncthreads();
         if (tid == 0) {
-            ks265_sao_param off;
-            off.type = -1; off.band = 0; off.offset[0] = off.offset[1] = off.offset[2] = off.offset[3] = 0; off.rsv[0] = off.rsv[1] = 0;
-            sel[0] = sel[1] = sel[2] = off;
-            int bandc[3], bcost[3];
-            for (int c = 0; c < 3; ++c) {                                  // the first of the 28 windows of four bands with the smallest cost sum
-                int bc = 0xffff000, bb = 0;
-                for (int k = 0; k < 28; ++k) { const int cc = rb_cost[c][k] + rb_cost[c][k + 1] + rb_cost[c][k + 2] + rb_cost[c][k + 3]; if (cc < bc) { bc = cc; bb = k; } }
-                bandc[c] = bb; bcost[c] = bc;
-            }
-            int best = (lamY + 128) >> 8;
-            for (int cls = 0; cls < 2; ++cls) {
-                const int cost = re_cost[0][cls] + ((4 * lamY + 128) >> 8);
-                if (cost < best) { best = cost; sel[0].type = (int8_t)(1 + cls); sel[0].band = 0; for (int k = 0; k < 4; ++k) sel[0].offset[k] = re_off[0][cls][k]; }
-            }
-            if (bcost[0] + ((7 * lamY + 128) >> 8) < best) { sel[0].type = 0; sel[0].band = (int8_t)bandc[0]; for (int k = 0; k < 4; ++k) sel[0].offset[k] = (int8_t)rb_off[0][bandc[0] + k]; }
-            best = (lamC + 128) >> 8;
-            for (int cls = 0; cls < 2; ++cls) {
-                const int cost = re_cost[1][cls] + re_cost[2][cls] + ((4 * lamC + 128) >> 8);
-                if (cost < best) {
-                    best = cost;
-                    for (int c = 1; c < 3; ++c) { sel[c].type = (int8_t)(1 + cls); sel[c].band = 0; for (int k = 0; k < 4; ++k) sel[c].offset[k] = re_off[c][cls][k]; }
-                }
-            }
-            if (bcost[1] + bcost[2] + ((12 * lamC + 128) >> 8) < best)
-                for (int c = 1; c < 3; ++c) { sel[c].type = 0; sel[c].band = (int8_t)bandc[c]; for (int k = 0; k < 4; ++k) sel[c].offset[k] = (int8_t)rb_off[c][bandc[c] + k]; }
+            int by, buv;
+            sao_ref_decide(rb_off, rb_cost, re_cost, re_off, lamY, lamC, sel, by, buv);
             sao[(long)ctu * 3 + 0] = sel[0]; sao[(long)ctu * 3 + 1] = sel[1]; sao[(long)ctu * 3 + 2] = sel[2];
         }
     } else {
@@ -502,6 +515,168 @@ __global__ __launch_bounds__(256) void sao_ctu_kernel(KsGeom g, int lam, int ena
     if (wave < 2) sao_apply_block<32>(tc[wave], lane & 7, lane >> 3, w / 2, h / 2, x0 / 2, y0 / 2, g.W / 2, g.H / 2, sel[1 + wave], ks_org_c(g, wave ? ov : ou), g.sc);
 }
 
+// ---- cfg.sao == 3: cfg.sao == 2 plus the merge candidates of CEncSao::modeDecisionCtu enc@0x4af690 (checkMerge enc@0x4ae7f0; the oracle's pinned restatement of it with both
+// neighbours, masks 0x13).  After its own choice a CTU prices the FINAL records of its left and upper CTU on its own statistics; strictly cheaper copies them and sets
+// sao_merge_left_flag / sao_merge_up_flag (rsv[0] / rsv[1] of the luma record).  The final record of a CTU depends on those of (cx - 1, cy) and (cx, cy - 1): a chain in coding
+// order, run along the anti-diagonals cx + cy.  Three launches:
+//   sao_merge_stats_kernel  one work-group per CTU: statistics + own decision (the front of sao_ctu_kernel<true>) into the workspace, KS_SAO_WS_WORDS words per CTU:
+//                           [0..312) the statistics in the reference's 312-word layout (bands Y / U / V, edge classes at 96 + 20 component + 5 class; sums 156 words on), [312..318) the own three records, [318] the own cost by + buv,
+//                           [319] (lambda_avg + 128) >> 8, what an upper CTU adds to the own cost and to the upper candidate;
+//   sao_merge_chain_kernel  ONE work-group: wave 0 decides a diagonal, a lane per CTU, from LDS only; the other waves meanwhile stage the next diagonal's words;
+//   sao_merge_apply_kernel  one work-group per CTU: the final records applied out of place.
+// No work-group waits for another one.
+__global__ __launch_bounds__(256) void sao_merge_stats_kernel(KsGeom g, const uint8_t *sy, const uint8_t *su, const uint8_t *sv, const uint8_t *dy, const uint8_t *du,
+                                                              const uint8_t *dv, int *ws, int qp, const int8_t *qp_map)
+{
+    __shared__ int rb_off[3][32], rb_cost[3][32], re_cost[3][2];
+    __shared__ int8_t re_off[3][2][4];
+    __shared__ __attribute__((aligned(16))) SaoTile<64> tl;
+    __shared__ __attribute__((aligned(16))) SaoTile<32> tc[2];
+    __shared__ __attribute__((aligned(16))) SaoAcc acc[3];
+    __shared__ SaoStats st[3];
+    __shared__ __attribute__((aligned(8))) ks265_sao_param sel[3];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ctu = ks_xcd_swizzle(blockIdx.x, g.ctu_cols * g.ctu_rows), cx = ctu % g.ctu_cols, cy = ctu / g.ctu_cols;
+    const int x0 = cx * 64, y0 = cy * 64, w = min(64, g.W - x0), h = min(64, g.H - y0);
+    for (int i = tid; i < (int)(sizeof(acc) / 4); i += 256) ((int *)acc)[i] = 0;
+    sao_load_tile<64>(tl, ks_org_y(g, sy), ks_org_y(g, dy), g.sy, x0, y0, tid, 256);
+    {
+        const int cc = tid >> 7;
+        sao_load_tile<32>(tc[cc], ks_org_c(g, cc ? sv : su), ks_org_c(g, cc ? dv : du), g.sc, x0 / 2, y0 / 2, tid & 127, 128);
+    }
+    __syncthreads();
+    sao_stats_block<64>(tl, tid & 15, tid >> 4, w, h, x0, y0, g.W, g.H, &acc[0], true, lane);
+    sao_stats_block<32>(tc[wave & 1], lane & 7, lane >> 3, w / 2, h / 2, x0 / 2, y0 / 2, g.W / 2, g.H / 2, &acc[1 + (wave & 1)], wave < 2, lane);
+    __syncthreads();
+    sao_acc_to_stats(&acc[0], &st[0], tid, 256);
+    sao_acc_to_stats(&acc[1], &st[1], tid, 256);
+    sao_acc_to_stats(&acc[2], &st[2], tid, 256);
+    __syncthreads();
+    const int q = qp_map ? qp_map[ctu] : qp, lamY = kLambdaSaoQ8[q], lamC = kLambdaSaoQ8[chroma_qp(q)];
+    if (tid < 96) { const int c = tid >> 5, b = tid & 31; sao_ref_band(c ? lamC : lamY, st[c].cnt[0][b], st[c].sum[0][b], rb_off[c][b], rb_cost[c][b]); }
+    else if (tid < 102) { const int c = (tid - 96) >> 1, cls = (tid - 96) & 1; re_cost[c][cls] = sao_ref_eo(c ? lamC : lamY, st[c].cnt[1 + cls], st[c].sum[1 + cls], re_off[c][cls]); }
+    int *out = ws + (long)ctu * KS_SAO_WS_WORDS;
+    for (int i = tid; i < 156; i += 256) {               // counts, then the sums 156 words on: bands of Y, U, V; per component 4 classes x 5 words, classes 0 and 1 x 4 categories used
+        int cn = 0, sm = 0;
+        if (i < 96) { cn = st[i >> 5].cnt[0][i & 31]; sm = st[i >> 5].sum[0][i & 31]; }
+        else {
+            const int j = i - 96, c = j / 20, r = j - 20 * c, cls = r / 5, k = r - 5 * cls;
+            if (cls < 2 && k < 4) { cn = st[c].cnt[1 + cls][k]; sm = st[c].sum[1 + cls][k]; }
+        }
+        out[i] = cn; out[156 + i] = sm;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int by, buv;
+        sao_ref_decide(rb_off, rb_cost, re_cost, re_off, lamY, lamC, sel, by, buv);
+        const int *sw = (const int *)sel;
+        for (int i = 0; i < 6; ++i) out[312 + i] = sw[i];
+        out[318] = (int)((unsigned)by + (unsigned)buv);
+        out[319] = (((lamY + lamC + 1) >> 1) + 128) >> 8;
+    }
+}
+
+// the words of a CTU's workspace that the chain can ask for, compacted for LDS: [0..96) band counts of Y, U, V, [96..120) edge counts [component][class 0, 1][category],
+// [120..240) the sums likewise, [240..248) the own records, own cost and the upper CTU's lambda term
+#define KS_SAO_CHAIN_WORDS 248
+__device__ __forceinline__ int sao_chain_src_word(int w)
+{
+    if (w >= 240) return 312 + (w - 240);
+    const int half = w >= 120, v = w - 120 * half, e = v - 96;
+    return 156 * half + (v < 96 ? v : 96 + 20 * (e >> 3) + 5 * ((e >> 2) & 1) + (e & 3));
+}
+// the distortion change the three records p[] give on the statistics m[] of another CTU (sao_merge_dist of the oracle in this build's record codes; 32-bit wrap-around)
+__device__ __forceinline__ int sao_chain_merge_dist(const int *m, const ks265_sao_param *p)
+{
+    unsigned d = 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const ks265_sao_param r = p[c];
+        if (r.type < 0) continue;
+        const int at = r.type == 0 ? 32 * c + r.band : 96 + 8 * c + 4 * (r.type - 1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { const unsigned o = (unsigned)(int)r.offset[i]; d += ((unsigned)m[at + i] * o - 2u * (unsigned)m[120 + at + i]) * o; }
+    }
+    return (int)d;
+}
+// the diagonal d holds the CTUs (d - cy, cy), cy in [lo, hi]; a step = up to 64 of them from cy0 on
+struct SaoChainStep { int d, cy0, n; };
+__device__ __forceinline__ SaoChainStep sao_chain_step(int d, int cy0, int cols, int rows)
+{
+    const int hi = min(rows - 1, d);
+    SaoChainStep s = {d, cy0, min(64, hi - cy0 + 1)};
+    return s;
+}
+__device__ __forceinline__ SaoChainStep sao_chain_next(SaoChainStep s, int cols, int rows)
+{
+    if (s.cy0 + 64 <= min(rows - 1, s.d)) return sao_chain_step(s.d, s.cy0 + 64, cols, rows);
+    return sao_chain_step(s.d + 1, max(0, s.d + 1 - (cols - 1)), cols, rows);
+}
+__device__ __forceinline__ void sao_chain_stage(int (*dst)[KS_SAO_CHAIN_WORDS], const int *ws, SaoChainStep s, int cols, int lt, int nt)
+{
+    for (int i = lt; i < s.n * KS_SAO_CHAIN_WORDS; i += nt) {
+        const int l = i / KS_SAO_CHAIN_WORDS, w = i - l * KS_SAO_CHAIN_WORDS, cy = s.cy0 + l;
+        dst[l][w] = ws[(long)(cy * cols + s.d - cy) * KS_SAO_WS_WORDS + sao_chain_src_word(w)];
+    }
+}
+__global__ __launch_bounds__(256) void sao_merge_chain_kernel(int cols, int rows, const int *ws, ks265_sao_param *sao)
+{
+    __shared__ int ms[2][64][KS_SAO_CHAIN_WORDS];                                            // the step being decided and the next one
+    __shared__ __attribute__((aligned(8))) ks265_sao_param fin[2][KS_SAO_CHAIN_ROWS][3];     // final records of the diagonal being decided and of the one before, by CTU row
+    const int tid = threadIdx.x, last = cols + rows - 2;
+    SaoChainStep s = sao_chain_step(0, 0, cols, rows);
+    sao_chain_stage(ms[0], ws, s, cols, tid, 256);
+    __syncthreads();
+    for (int b = 0; s.d <= last; b ^= 1) {
+        const SaoChainStep nx = sao_chain_next(s, cols, rows);
+        if (tid >= 64) { if (nx.d <= last) sao_chain_stage(ms[b ^ 1], ws, nx, cols, tid - 64, 192); }
+        else if (tid < s.n) {
+            const int cy = s.cy0 + tid, cx = s.d - cy, *m = ms[b][tid];
+            const ks265_sao_param *prev = &fin[(s.d & 1) ^ 1][0][0];
+            ks265_sao_param r[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) r[c] = ((const ks265_sao_param *)(m + 240))[c];
+            int tot = (int)((unsigned)m[246] + (cy > 0 ? (unsigned)m[247] : 0u)), ml = 0, mu = 0;
+            if (cx > 0) {
+                const int c = sao_chain_merge_dist(m, prev + 3 * cy);
+                if (tot > c) { tot = c; ml = 1; }
+            }
+            if (cy > 0) {
+                const int c = (int)((unsigned)sao_chain_merge_dist(m, prev + 3 * (cy - 1)) + (unsigned)m[247]);
+                if (tot > c) { ml = 0; mu = 1; }
+            }
+            if (ml | mu) {
+                const ks265_sao_param *n = prev + 3 * (cy - mu);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) { r[c] = n[c]; r[c].rsv[0] = r[c].rsv[1] = 0; }
+                r[0].rsv[0] = (int8_t)ml; r[0].rsv[1] = (int8_t)mu;
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { fin[s.d & 1][cy][c] = r[c]; sao[(long)(cy * cols + cx) * 3 + c] = r[c]; }
+        }
+        __syncthreads();
+        s = nx;
+    }
+}
+
+__global__ __launch_bounds__(256) void sao_merge_apply_kernel(KsGeom g, const uint8_t *sy, const uint8_t *su, const uint8_t *sv, const uint8_t *dy, const uint8_t *du,
+                                                              const uint8_t *dv, const ks265_sao_param *sao, uint8_t *oy, uint8_t *ou, uint8_t *ov)
+{
+    __shared__ __attribute__((aligned(16))) SaoTile<64> tl;
+    __shared__ __attribute__((aligned(16))) SaoTile<32> tc[2];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ctu = ks_xcd_swizzle(blockIdx.x, g.ctu_cols * g.ctu_rows), cx = ctu % g.ctu_cols, cy = ctu / g.ctu_cols;
+    const int x0 = cx * 64, y0 = cy * 64, w = min(64, g.W - x0), h = min(64, g.H - y0);
+    sao_load_tile<64>(tl, ks_org_y(g, sy), ks_org_y(g, dy), g.sy, x0, y0, tid, 256);
+    {
+        const int cc = tid >> 7;
+        sao_load_tile<32>(tc[cc], ks_org_c(g, cc ? sv : su), ks_org_c(g, cc ? dv : du), g.sc, x0 / 2, y0 / 2, tid & 127, 128);
+    }
+    __syncthreads();
+    sao_apply_block<64>(tl, tid & 15, tid >> 4, w, h, x0, y0, g.W, g.H, sao[(long)ctu * 3], ks_org_y(g, oy), g.sy);
+    if (wave < 2) sao_apply_block<32>(tc[wave], lane & 7, lane >> 3, w / 2, h / 2, x0 / 2, y0 / 2, g.W / 2, g.H / 2, sao[(long)ctu * 3 + 1 + wave], ks_org_c(g, wave ? ov : ou), g.sc);
+}
+
 // a picture without SAO (cfg.sao = 0 per picture, ks265_frame_set_picture_tools): every record "off" - what sao_ctu_kernel writes with enable = 0
 __global__ void sao_off_kernel(int n, ks265_sao_param *sao)
 {
@@ -527,7 +702,13 @@ extern "C" int ks265_sao(ks265_frame *f, ks265_pic src, ks265_pic deb, ks265_sao
 {
     KS_FRAME_CHECK(f);
     if (!src.y || !deb.y || !sao || !dst.y) return KS265_POINTER;
-    if (f->cfg.sao == 2) hipLaunchKernelGGL(sao_ctu_kernel<true>, dim3(f->g.ctu_cols * f->g.ctu_rows), dim3(256), 0, f->ctx->stream, f->g, f->cfg.lambda_q4, f->cfg.sao, src.y, src.u,
+    if (f->cfg.sao == 3) {
+        if (!f->sao_ws) return KS265_NOTSUPPORTED;
+        const int n = f->g.ctu_cols * f->g.ctu_rows;
+        hipLaunchKernelGGL(sao_merge_stats_kernel, dim3(n), dim3(256), 0, f->ctx->stream, f->g, src.y, src.u, src.v, deb.y, deb.u, deb.v, f->sao_ws, f->cfg.qp, f->qp_map);
+        hipLaunchKernelGGL(sao_merge_chain_kernel, dim3(1), dim3(256), 0, f->ctx->stream, f->g.ctu_cols, f->g.ctu_rows, (const int *)f->sao_ws, sao);
+        hipLaunchKernelGGL(sao_merge_apply_kernel, dim3(n), dim3(256), 0, f->ctx->stream, f->g, src.y, src.u, src.v, deb.y, deb.u, deb.v, (const ks265_sao_param *)sao, dst.y, dst.u, dst.v);
+    } else if (f->cfg.sao == 2) hipLaunchKernelGGL(sao_ctu_kernel<true>, dim3(f->g.ctu_cols * f->g.ctu_rows), dim3(256), 0, f->ctx->stream, f->g, f->cfg.lambda_q4, f->cfg.sao, src.y, src.u,
                                             src.v, deb.y, deb.u, deb.v, sao, dst.y, dst.u, dst.v, f->cfg.qp, f->qp_map);
     else hipLaunchKernelGGL(sao_ctu_kernel<false>, dim3(f->g.ctu_cols * f->g.ctu_rows), dim3(256), 0, f->ctx->stream, f->g, f->cfg.lambda_q4, f->cfg.sao, src.y, src.u,
                             src.v, deb.y, deb.u, deb.v, sao, dst.y, dst.u, dst.v, f->cfg.qp, f->qp_map);

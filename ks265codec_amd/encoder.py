@@ -109,7 +109,7 @@ class Encoder:
         if self.lib.QY265ConfigDefaultPreset(self._cfg, preset.encode(), None, str(params.pop("latency", "default")).encode()) != 0:
             raise ValueError(f"preset {preset!r}")
         for k, v in (("wdt", width), ("hgt", height), *params.items()):
-            rc = self.lib.QY265ConfigParse(self._cfg, str(k).encode(), str(v).encode())
+            rc = self.lib.QY265ConfigParse(self._cfg, str(k).replace("_", "-").encode(), str(v).encode())   # keyword form of the names with a dash: sao_ref=2 -> "sao-ref"
             if rc != 0:
                 raise ValueError(f"parameter {k}={v!r}: {'unknown name' if rc == -1 else 'bad value'}")
         err = C.c_int(0)

@@ -169,6 +169,9 @@ int QY265ConfigParse(QY265EncConfig *c, const char *name, const char *value)
     /* sao (qy265enc.h:143): veryfast and fast resolve to 3, which - like every level > 0 - runs this build's rule; asked for BY NAME, sao 3 is stored as 5 = the reference's own
      * decision restated (ks265_frame_cfg.sao = 2), so that the presets' streams do not pay for it (configs[0] on the MI355X: 5.5 % fewer bytes at equal PSNR-Y with the build's rule) */
     if (!strcmp(name, "sao")) { if (!num_ok || iv < 0 || iv > 4) return QY265_PARAM_BAD_VALUE; c->sao = iv == 3 ? 5 : iv; return 0; }
+    /* sao-ref: the reference's decision under a name of its own - 1 = what sao 3 BY NAME selects (stored 5, ks265_frame_cfg.sao = 2), 2 = the same with its merge candidates
+     * (stored 6, ks265_frame_cfg.sao = 3: sao_merge_left_flag / sao_merge_up_flag are coded), 0 = leave sao as it is */
+    if (!strcmp(name, "sao-ref")) { if (!num_ok || dv != iv || iv < 0 || iv > 2) return QY265_PARAM_BAD_VALUE; if (iv) c->sao = 4 + iv; return 0; }
     INTP("wpp", enWavefront, 0, 1) INTP("fpp", enFrameParallel, 0, 1) INTP("vbv-maxrate", vbv_max_rate, 0, 10000000)
     INTP("aq", iAqMode, 0, 3)                                  /* the reference's hidden -aq (iAqMode, qy265enc.h:145) */
     INTP("vbv-bufsize", vbv_buffer_size, 0, 10000000) INTP("pass", iPass, 0, 2) INTP("tlayer", temporalLayer, 0, 1) INTP("frameskip", enFrameSkip, 0, 1)
@@ -1524,7 +1527,7 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
     /* -sao (qy265enc.h:143: 1 / 2 faster, 3 usual, 4 complex): 3 given BY NAME = the reference's own decision on its -sao 4 path - band offset + the 0 / 90 degree edge classes priced by its pinned
      * estimation functions, rates and lambda table (ks265_frame_cfg.sao = 2: CEncSao::modeDecisionBoEo01 enc@0x4af300 without the merge candidates); every other level > 0 = this build's
      * rule over all four edge classes + band offset (the presets' -sao 4: 2.7 - 4.6 % fewer bytes at equal PSNR-Y than level 3, which buys 0.8 - 1.9 dB of chroma: DESIGN.md) */
-    e->fcfg.sao = cfg->sao == 5 ? 2 : e->use_sao;                       /* (5 = -sao 3 BY NAME, QY265ConfigParse; the presets' 3 is the build's rule) */
+    e->fcfg.sao = cfg->sao == 6 ? 3 : cfg->sao == 5 ? 2 : e->use_sao;   /* (5 = -sao 3 BY NAME or -sao-ref 1, 6 = -sao-ref 2: + the merge candidates, QY265ConfigParse; the presets' 3 is the build's rule) */
     {   /* the sub-pel refinement's knobs follow the preset, as in the reference */
         const int ps = (int)cfg->preset < 0 || (int)cfg->preset > 8 ? QY265PRESET_SLOW : (int)cfg->preset;
         e->fcfg.sub_satd = kPresetSubme[ps].satd; e->fcfg.sub_thr = kPresetSubme[ps].thr; e->fcfg.sub_flat = kPresetSubme[ps].flat;
@@ -1757,8 +1760,9 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
     if (e->nth && !pthread_create(&e->disp, NULL, dispatcher, e)) e->disp_on = 1;
     if (e->disp_on && !pthread_create(&e->sched, NULL, scheduler, e)) e->sched_on = 1;
     if (!e->nth || !e->disp_on || !e->sched_on) { *err = QY_FAIL; lane_close(e, 0); return NULL; }
-    logf_(0, e->log_level, "ks265enc: GPU %d: %dx%d %.2f fps, qp %d, -me %d (hex below %d), subme %d, refs %d, %s, sao %d, key period %d, %d slice writer threads, %s\n", device, e->W, e->H,
-          cfg->frameRate, e->base_qp, e->me_method, e->hex_thr, e->subme, e->refs, e->hier ? (e->gop_b == 3 ? "hierarchical-B GOP 4" : "hierarchical-B GOP 8") : e->gop_b ? "P + non-reference B" : "IPPP", e->use_sao, e->iper,
+    logf_(0, e->log_level, "ks265enc: GPU %d: %dx%d %.2f fps, qp %d, -me %d (hex below %d), subme %d, refs %d, %s, sao %d (%s), key period %d, %d slice writer threads, %s\n", device, e->W, e->H,
+          cfg->frameRate, e->base_qp, e->me_method, e->hex_thr, e->subme, e->refs, e->hier ? (e->gop_b == 3 ? "hierarchical-B GOP 4" : "hierarchical-B GOP 8") : e->gop_b ? "P + non-reference B" : "IPPP", e->use_sao,
+          e->fcfg.sao == 3 ? "the reference's decision with merge candidates" : e->fcfg.sao == 2 ? "the reference's decision" : e->fcfg.sao ? "the build's rule" : "off", e->iper,
           e->nth, ks265_version());
     return e;
 }

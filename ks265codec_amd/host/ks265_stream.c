@@ -463,8 +463,9 @@ static void sao_ctb(Enc *e, int rx, int ry)
     Cabac *c = &e->c;
     const ks265_sao_param *p = e->in->sao + (long)(ry * e->ctb_cols + rx) * 3;
     CAT(c, CAT_SAO);
-    if (rx > 0) cb_bin(c, CX_SAO_MERGE, 0);                          /* sao_merge_left_flag */
-    if (ry > 0) cb_bin(c, CX_SAO_MERGE, 0);                          /* sao_merge_up_flag */
+    /* the luma record's rsv[0] / rsv[1] = merge left / up (ks265_frame_cfg.sao = 3; consistency was checked by sao_merge_ok): after a flag of 1 the CTB codes nothing more */
+    if (rx > 0) { cb_bin(c, CX_SAO_MERGE, p->rsv[0] != 0); if (p->rsv[0]) { CAT(c, CAT_CU); return; } }      /* sao_merge_left_flag */
+    if (ry > 0) { cb_bin(c, CX_SAO_MERGE, p->rsv[1] != 0); if (p->rsv[1]) { CAT(c, CAT_CU); return; } }      /* sao_merge_up_flag */
     for (int ci = 0; ci < 3; ++ci) {
         const ks265_sao_param *q = p + ci;
         if (ci < 2) {                                               /* sao_type_idx_luma / _chroma (shared by Cb and Cr): 0 off, 1 band, 2 edge */
@@ -1040,6 +1041,31 @@ static int check_lists(const ks265_stream_cfg *cfg, const ks265_slice_in *in)
 }
 
 /* argument checks shared by the whole-slice and the row-wise entry points */
+/* a merge flag must be usable: the neighbour exists, one flag at most, and the three records are copies of the neighbour's (the decoder takes the neighbour's parameters,
+ * so anything else would decode to another picture).  Only the luma record carries flags. */
+static int sao_param_same(const ks265_sao_param *a, const ks265_sao_param *b)
+{
+    if (a->type != b->type) return 0;
+    if (a->type < 0) return 1;                                      /* off: band and offsets are not coded */
+    if (a->type == 0 && a->band != b->band) return 0;
+    return !memcmp(a->offset, b->offset, 4);
+}
+static int sao_merge_ok(const ks265_stream_cfg *cfg, const ks265_slice_in *in)
+{
+    const int cols = (cfg->width + 63) >> 6, rows = (cfg->height + 63) >> 6;
+    for (int ry = 0; ry < rows; ++ry)
+        for (int rx = 0; rx < cols; ++rx) {
+            const ks265_sao_param *p = in->sao + (long)(ry * cols + rx) * 3;
+            const int ml = p[0].rsv[0], mu = p[0].rsv[1];
+            if (p[1].rsv[0] | p[1].rsv[1] | p[2].rsv[0] | p[2].rsv[1]) return 0;
+            if (!ml && !mu) continue;
+            if ((ml && mu) || (ml | mu) != 1 || (ml && rx == 0) || (mu && ry == 0)) return 0;
+            const ks265_sao_param *n = ml ? p - 3 : p - 3 * (long)cols;
+            for (int ci = 0; ci < 3; ++ci) if (!sao_param_same(p + ci, n + ci)) return 0;
+        }
+    return 1;
+}
+
 static int slice_args_ok(const ks265_stream_cfg *cfg, const ks265_slice_in *in)
 {
     if (!cfg || !in || !in->cu8 || !in->lvl[0] || !in->lvl[1] || !in->lvl[2]) return KS265_POINTER;
@@ -1048,6 +1074,7 @@ static int slice_args_ok(const ks265_stream_cfg *cfg, const ks265_slice_in *in)
     const int idr = in->nal_type == KS265_NAL_IDR_W_RADL || in->nal_type == KS265_NAL_IDR_N_LP;
     if (idr && (in->slice_type != KS265_SLICE_I || in->poc != 0)) return KS265_NOTSUPPORTED;
     if (!idr && !check_lists(cfg, in)) return KS265_NOTSUPPORTED;
+    if (cfg->sao && in->sao && !sao_merge_ok(cfg, in)) return KS265_NOTSUPPORTED;
     return KS265_OK;
 }
 

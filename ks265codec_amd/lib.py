@@ -22,7 +22,8 @@ CU8 = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("mv1x", "<i2"), ("mv1y", "<i2")
 PU_B = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("mv1x", "<i2"), ("mv1y", "<i2"), ("cost", "<u4"), ("inter_dir", "<u4")])
 RDOQ_TU = np.dtype([("off", "<i4"), ("tab", "<i4"), ("dq", "<i4"), ("last_pos", "<i4"), ("lam", "<i8"), ("lam_sdh", "<i8"), ("log2", "i1"), ("scan_idx", "i1"), ("comp", "i1"), ("per", "i1"),
                     ("tu5", "i1"), ("flag_a4c0", "i1"), ("sdh", "i1"), ("rsv", "i1")])      # ks265_rdoq_tu
-SAO_PARAM = np.dtype([("type", "i1"), ("band", "i1"), ("offset", "i1", 4), ("rsv", "i1", 2)])
+SAO_PARAM = np.dtype([("type", "i1"), ("band", "i1"), ("offset", "i1", 4), ("rsv", "i1", 2)])      # rsv of a CTU's luma record: [SAO_MERGE_LEFT], [SAO_MERGE_UP] (sao=3)
+SAO_MERGE_LEFT, SAO_MERGE_UP = 0, 1
 
 
 class FrameCfg(C.Structure):
@@ -364,7 +365,7 @@ class KsFrame:
         self.ks._chk(self.lib.ks265_frame_set_qp(self.h, C.c_int(qp), C.c_int(lambda_q4)))
 
     def set_picture_tools(self, intra_inter: int = -1, bi_refine: int = -1, sao: int = -1, me_method: int = -1):
-        """tools of the pictures coded from here on (-1 = as created, else 0 or the created value): ks265_frame_set_picture_tools"""
+        """tools of the pictures coded from here on (-1 = as created, else 0 or the created value; a frame made with sao=3 also takes sao=2): ks265_frame_set_picture_tools"""
         self.ks._chk(self.lib.ks265_frame_set_picture_tools(self.h, C.c_int(intra_inter), C.c_int(bi_refine), C.c_int(sao), C.c_int(me_method)))
 
     def set_qp_map(self, dev_map):

@@ -272,7 +272,7 @@ def main():
     ap.add_argument("--pdelta", type=int, default=1)
     ap.add_argument("--cascade", default="")
     ap.add_argument("--lam-scale", type=float, default=1.0)
-    ap.add_argument("--host", action="store_true", help="exactly what the encoder host does: its tool set (intra_inter=1, rdo=4, propagate=1 on top of ENCODER_TOOLS without the decimation), its P / B lambda table, its QP ladder")
+    ap.add_argument("--host", action="store_true", help="exactly what the encoder host does: its tool set (intra_inter=1, rdo=4, propagate=1 on top of ENCODER_TOOLS without the decimation), its P / B lambda table, its QP ladder; SAO modes up to ks265_frame_cfg.sao = 2 only: the pipeline oracle has no merge step (-sao-ref 2 is not mirrored)")
     ap.add_argument("--adaptive", action="store_true", help="--gop hier: the host's slice-type decision of -lookahead N (blocks of 8 pictures as 8 or 4 + 4)")
     ap.add_argument("--pingpong", type=int, default=0, metavar="K", help="the clip of the same-clip tables: K pictures of the generator played forth and back, --frames pictures in all")
     ap.add_argument("--pan", default="", help="pan of the synthetic clip in samples per picture, e.g. 8,5")
