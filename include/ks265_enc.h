@@ -28,6 +28,8 @@
  *   - sao-ref (not in the SDK; QY265ConfigParse "sao-ref" = `-sao-ref`): the reference's decision under a name of its own - "1" = what sao 3 by name selects (stored as 5),
  *     "2" = the same with the reference's merge candidates (stored as 6): a CTU whose left or upper CTU's final parameters are strictly cheaper on its own statistics takes
  *     them and codes sao_merge_left_flag / sao_merge_up_flag instead of its parameters; "0" leaves sao as it is.  No preset selects it;
+ *   - calcSsim (-ssim 1 | 2): the reference's ` ssim:` line behind `bitrate, psnr:` (8x8 windows), computed on the device in the same pass as the SSE; 2 adds one
+ *     `ks265enc: poc N ssim Y U V` line per picture (the reference prints nothing per picture); totals and the last picture's values: ks265_enc_get_quality;
  *   - transskip, tuIntra, vpp_*, 2-pass, long-term references, VBV / CVQ: accepted, ignored;
  *   - input pictures: the caller's planes are pinned in place and uploaded from where they lie inside QY265EncoderEncodeFrame; the caller may reuse its buffers when the call returns
  *     (the SDK requires them to stay valid until the frame is done);
@@ -109,6 +111,12 @@ typedef struct { long frames; long long bytes; double sse[3]; double gpu_ms; dou
                  double submit_wait_ms;                     /* the part of submit_ms the scheduler thread spent WAITING for a free ring slot (not runtime calls) */
 } ks265_enc_stats;
 int ks265_enc_get_stats(void *pEncoder, ks265_enc_stats *out);
+/* not in the SDK: the quality figures of the pictures handed out so far (accounted in output order, so the totals are the same for any number of GOP lanes).
+ * sse: summed squared error per plane (calcPsnr != 0, else 0; = ks265_enc_stats.sse).  ssim: per plane the SUM over the pictures of the picture's SSIM as the reference's
+ * `-ssim` computes it (calcSsim != 0 and a device library that has the pass: have_ssim, else 0) - the ` ssim:` line prints ssim[k] / frames.
+ * last_*: the picture accounted last (its display index in the stream - with GOP lanes in its GOP - and its own SSE and SSIM values; last_poc = -1 before the first). */
+typedef struct { long frames; int have_sse, have_ssim; double sse[3]; double ssim[3]; int last_poc; double last_sse[3]; double last_ssim[3]; } ks265_enc_quality;
+int ks265_enc_get_quality(void *pEncoder, ks265_enc_quality *out);
 /* extension: closed GOPs coded concurrently by this handle ("GOP lanes": KS265_GOP_LANES = 2..4 with enFrameParallel, -rc 0, key period >= 32, any GOP structure;
  * default: 2 for the pyramid GOPs - the SDK's default GOP and -bframes 3 - on one GPU with -rc 0 / -rc 3, where lanes leave the stream as it is (round 5: their B pictures leave the device under-filled, two closed GOPs side by side
  * code 700 pictures/s where one codes 631 at 2160p), 1 otherwise; KS265_GOP_LANES=1 switches it off).  Output stays in stream order and is byte for byte the one-lane stream;

@@ -610,6 +610,12 @@ int ks265_copy_out_compact_dma_async(ks265_ctx *, ks265_frame *f, void *pinned_h
 /* luma SSE between two padded pictures (PSNR-Y of the bench line; CPSNR_I420::calcPSNR enc@0x4c4060) */
 int ks265_sse_picture(ks265_frame *f, ks265_pic a, ks265_pic b, uint64_t *dev_sse3);
 int ks265_sse_picture_on(ks265_ctx *cx, ks265_frame *f, ks265_pic a, ks265_pic b, uint64_t *dev_sse3);
+/* SSIM between two padded pictures as the reference's `-ssim` computes it: 8x8 windows, non-overlapping, from sample (0, 0), windows that do not lie wholly inside
+ * a plane dropped; population variances; C1 = 6.5025, C2 = 58.5225.  dev_ssim3[p] = the sum over plane p's (width / 8) x (height / 8) windows of llrint(ssim x 2^30) - the
+ * plane's SSIM is that over windows x 2^30; integer sums, so the result does not depend on the order the work-groups finish in.  The same launch leaves in dev_sse3 (may be
+ * NULL) what ks265_sse_picture gives, bit for bit: the pictures are read once for both. */
+int ks265_ssim_picture(ks265_frame *f, ks265_pic a, ks265_pic b, uint64_t *dev_sse3, int64_t *dev_ssim3);
+int ks265_ssim_picture_on(ks265_ctx *cx, ks265_frame *f, ks265_pic a, ks265_pic b, uint64_t *dev_sse3, int64_t *dev_ssim3);
 
 #ifdef __cplusplus
 }

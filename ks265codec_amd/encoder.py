@@ -37,6 +37,12 @@ class DevPicture(C.Structure):
                 ("matrix", C.c_int), ("full_range", C.c_int), ("stream", C.c_void_p), ("pts", C.c_longlong)]
 
 
+class Quality(C.Structure):
+    """ks265_enc_quality of include/ks265_enc.h"""
+    _fields_ = [("frames", C.c_long), ("have_sse", C.c_int), ("have_ssim", C.c_int), ("sse", C.c_double * 3), ("ssim", C.c_double * 3), ("last_poc", C.c_int),
+                ("last_sse", C.c_double * 3), ("last_ssim", C.c_double * 3)]
+
+
 class EncoderError(RuntimeError):
     def __init__(self, what: str, rc: int):
         super().__init__(f"{what}: 0x{rc & 0xFFFFFFFF:08X}")
@@ -55,6 +61,7 @@ def library() -> C.CDLL:
         for n in ("QY265EncoderClose", "ks265_enc_enable_device_input", "QY265EncoderDelayedFrames"):
             getattr(_lib, n).argtypes = [C.c_void_p]
         _lib.QY265EncoderEncodeFrame.argtypes = [C.c_void_p, C.POINTER(C.POINTER(Nal)), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int]
+        _lib.ks265_enc_get_quality.argtypes = [C.c_void_p, C.POINTER(Quality)]
         _lib.ks265_enc_encode_device_frame.argtypes = [C.c_void_p, C.POINTER(C.POINTER(Nal)), C.POINTER(C.c_int), C.POINTER(DevPicture), C.c_void_p]
     return _lib
 
@@ -148,6 +155,19 @@ class Encoder:
                 raise EncoderError("QY265EncoderEncodeFrame (flush)", rc)
             out += self._take()
         return bytes(out)
+
+    def quality(self) -> dict:
+        """quality figures of the pictures handed out so far (ks265_enc_get_quality): `frames`; `sse` = summed squared error per plane (psnr=1, else None); `ssim` = per plane the
+        mean over the pictures of the reference's `-ssim` figure (ssim=1, else None); `last` = display index, SSE and SSIM of the picture accounted last"""
+        if self.h is None:
+            raise RuntimeError("encoder closed")
+        q = Quality()
+        rc = self.lib.ks265_enc_get_quality(self.h, C.byref(q))
+        if rc != QY_OK:
+            raise EncoderError("ks265_enc_get_quality", rc)
+        n = max(1, q.frames)
+        return {"frames": q.frames, "sse": list(q.sse) if q.have_sse else None, "ssim": [v / n for v in q.ssim] if q.have_ssim else None,
+                "last": {"poc": q.last_poc, "sse": list(q.last_sse) if q.have_sse else None, "ssim": list(q.last_ssim) if q.have_ssim else None}}
 
     def close(self) -> None:
         if self.h is not None:

@@ -2,7 +2,7 @@
  * plus the tool flags the v2.6.1.3 binary accepts), driving the library API exactly like the SDK's own callers do
  * (encoderwrapper.c:327-427: ConfigDefaultPreset -> set fields -> Open -> EncodeFrame per picture -> flush while DelayedFrames -> Close).
  * Output conventions kept: Annex-B stream to -b, stdout lines `Total Frames: N, test time: X ms, FPS: F` and `bitrate, psnr: kbps Y U V`
- * (the Android demo parses the latter), `H265 encoder passed!!!` at the end. */
+ * (the Android demo parses the latter; with -ssim the reference's ` ssim: kbps Y U V` line follows it), `H265 encoder passed!!!` at the end. */
 #define _GNU_SOURCE
 #include "ks265_enc.h"
 #include <stdio.h>
@@ -55,7 +55,7 @@ static unsigned char *reader_next(Reader *r, int *cur)
 static void usage(void)
 {
     puts("usage: ks265enc -i in.yuv -wdt W -hgt H [-fr FPS] [-preset ultrafast..placebo] [-latency zerolatency|lowdelay|livestreaming|default] [-tune T]\n"
-         "                [-rc 0..5] [-qp Q] [-crf C] [-br KBPS] [-iper N] [-bframes N] [-frms N] [-threads N] [-psnr 0|1|2] [-b out.265] [-o recon.yuv]\n"
+         "                [-rc 0..5] [-qp Q] [-crf C] [-br KBPS] [-iper N] [-bframes N] [-frms N] [-threads N] [-psnr 0|1|2] [-ssim 0|1|2] [-b out.265] [-o recon.yuv]\n"
          "                [-me 0|1|2] [-subme 0|1|2] [-merange R] [-ref N] [-sao 0..4] [-sao-ref 0|1|2 (the reference's SAO decision: 1 = as -sao 3, 2 = with its left / up merge candidates)] [-df 0|1] [-fixqp 0|1] [-md5 0|1] [-scenecut N (with -lookahead: the reference's scene-cut rule at threshold N)] [-cutree 0|1 (-rc 3: the reference's macroblock tree over the lookahead, a QP per CTU; default 1)] [-aq 0|1 -aqs S (adaptive quantisation: a QP per CTU from the reference's block-variance rule)] [-c config_file] [-gpus N] [-v]\n"
          "  I420 8-bit input; width and height multiples of 8.  Needs one MI355X (gfx950): there is no CPU fallback.");
 }

@@ -30,10 +30,15 @@
 #pragma weak ks265_input_convert
 #pragma weak ks265_wait_external
 #pragma weak ks265_external_wait_event
+/* -ssim (calcSsim) reaches the fused SSIM + SSE pass the same way: on a device library without it the encoder works as before, logs once that SSIM is unavailable
+ * and prints no ` ssim:` line */
+#pragma weak ks265_ssim_picture
+#pragma weak ks265_ssim_picture_on
 
 const char strLibQy265Version[] = "ks265enc 0.2 (MI355X pixel path + host CABAC; API of libqycodec V2.6.1.3)";
 
 static QYLogPrintf g_log_cb;
+static unsigned long g_q_seq;                             /* pictures accounted by any lane of any handle: which lane's last picture is THE last one (ks265_enc_get_quality) */
 void QY265SetLogPrintf(QYLogPrintf cb) { g_log_cb = cb; }
 static void logf_(int level, int min_level, const char *fmt, ...)
 {
@@ -209,6 +214,7 @@ typedef struct Job {
     long sub_seq;                                         /* this picture's number in submission order (the dispatcher's sticky device error ends at a key picture submitted after the error was seen) */
     void *wpp; ks265_slice_in sin; int started, nrows, next_row, rows_done;   /* row-wise writing of the slice (ks265_wpp_*) */
     int8_t *qp_map;                                       /* -aq: the QP of every CTU this picture was coded with (pinned; NULL without) */
+    int64_t *ssim;                                        /* -ssim: per plane the sum over its 8x8 windows of llrint(ssim x 2^30) (pinned; NULL without) */
     uint8_t *recon;                                       /* pinned I420 copy of the reconstruction (only with ks265_enc_set_recon_file / -md5) */
     char md5[3][33];
     void *ev;                                             /* recorded after the D2H copies */
@@ -339,6 +345,9 @@ typedef struct Enc {
     int recon_fd, recon_on; uint8_t *dev_recon;           /* reconstruction dump (the CLI's -o) and / or plane MD5s (-md5 1): recon_on = the pictures come back to the host */
     int md5, fixqp, psnr_hdr; int md5_next; char (*md5_ring)[3][33]; unsigned char *md5_have;   /* MD5 lines go out in display order (ring of 256 by display index) */
     ks265_pic src; ks265_pic dpb[MAX_DPB]; int dpb_poc[MAX_DPB]; int ndpb; uint64_t *dev_sse;
+    /* -ssim: the fused pass is there and asked for; its device sums ([0..2] main stream / copy-out stream, [4..6] key pictures' stream, [8..10] anchors' stream); the session's
+     * totals in output order as exact integers (hi x 2^30 + lo: the same for any number of GOP lanes), the picture accounted last and when (q_seq: across lanes) */
+    int ssim_on; int64_t *dev_ssim; long long q_hi[3], q_lo[3]; int q_last_poc; double q_last_sse[3], q_last_ssim[3]; unsigned long q_seq;
     /* key pictures on their own stream and frame object: an intra picture keeps 34 of 256 compute units busy for ~26 ms (2160p); coded as soon as its
      * input arrives - the pixel path is tens of pictures behind the input - it runs underneath the P pictures of the previous GOP instead of between
      * two GOPs.  Its reconstruction goes to one of two DPB slots of its own; the first P picture of the GOP waits for ev_key. */
@@ -829,6 +838,15 @@ static int ct_run(Enc *e, int key, int d, int a, int end)
     return r;
 }
 
+/* source against reconstruction: the SSE (-psnr), or with -ssim the fused pass that reads the two pictures once for both (the SSE sums bit for bit those of the SSE pass;
+ * not wanted without -psnr).  on = NULL: the frame's own stream.  The SSIM sums then go home by a copy of their own on the same stream, in front of the picture's event */
+static int quality_pass(Enc *e, ks265_ctx *on, ks265_frame *fr, ks265_pic src, ks265_pic rec, uint64_t *dsse, int64_t *dssim)
+{
+    if (dssim) return on ? ks265_ssim_picture_on(on, fr, src, rec, e->cfg.calcPsnr ? dsse : NULL, dssim) : ks265_ssim_picture(fr, src, rec, e->cfg.calcPsnr ? dsse : NULL, dssim);
+    if (!e->cfg.calcPsnr) return 0;
+    return on ? ks265_sse_picture_on(on, fr, src, rec, dsse) : ks265_sse_picture(fr, src, rec, dsse);
+}
+
 /* enqueue one picture: GPU work + copies on the stream, then hand it to the writers */
 static int submit(Enc *e, Input *in, int kind, int poc, int qp, const int *l0, int nl0, const int *l1, int nl1, const int *keep_after, int nkeep, int is_ref, int key_headers)
 {
@@ -872,6 +890,7 @@ static int submit(Enc *e, Input *in, int kind, int poc, int qp, const int *l0, i
     if (!r && split) r = ks265_load_i420_on(e->ctx_in, fr, din, srcp);
     if (!r && !direct) r = ks265_event_record(e->ctx_in, e->ev_h2d[k]);
     uint64_t *dsse = on_key ? e->dev_sse_key : on_anc ? e->dev_sse_anc : e->dev_sse;
+    int64_t *dssim = e->ssim_on ? e->dev_ssim + (on_key ? 4 : on_anc ? 8 : 0) : NULL;
     if (!r && !direct) r = ks265_stream_wait_event(cx, e->ev_h2d[k]);
     /* graph path: a P picture with one reference on the main stream, once the first pictures have made every lazy allocation */
     const int graphable = e->use_graph && ((kind == 'P' && nl0 == 1) || (kind == 'B' && nl0 == 1 && nl1 == 1)) && !on_key && !on_anc && !e->recon_on && e->seq >= 8;
@@ -952,7 +971,7 @@ static int submit(Enc *e, Input *in, int kind, int poc, int qp, const int *l0, i
     if (!r && graphable) {
         const ks265_pic refp = e->dpb[dpb_find(e, l0[0])], ref1p = kind == 'B' ? e->dpb[dpb_find(e, l1[0])] : refp;
         const uint64_t key[9] = {(uint64_t)(uintptr_t)refp.y, (uint64_t)(uintptr_t)out.y, (uint64_t)(uintptr_t)e->dev_in[k], (uint64_t)(uintptr_t)e->stg[k],
-                                 (uint64_t)qp, (uint64_t)ks265_frame_p_state(fr), (uint64_t)(e->cfg.calcPsnr != 0), (uint64_t)kind | ((uint64_t)lean << 8), (uint64_t)(uintptr_t)ref1p.y};
+                                 (uint64_t)qp, (uint64_t)ks265_frame_p_state(fr), (uint64_t)(e->cfg.calcPsnr != 0) | (uint64_t)e->ssim_on << 1, (uint64_t)kind | ((uint64_t)lean << 8), (uint64_t)(uintptr_t)ref1p.y};
         void *exec = NULL;
         for (int i = 0; i < e->ngraph && !exec; ++i) if (!memcmp(e->graph[i].key, key, sizeof key)) exec = e->graph[i].exec;
         if (recycled) r = ks265_stream_wait_event(cx, e->ev_drained[k]);       /* the staging block of this rotation slot has been copied out */
@@ -965,7 +984,7 @@ static int submit(Enc *e, Input *in, int kind, int poc, int qp, const int *l0, i
             if (keep_it && ks265_capture_begin(cx)) { keep_it = 0; e->use_graph = 0; }   /* no capture on this runtime: launch by launch from here on */
             if (!r) r = ks265_load_i420(fr, e->dev_in[k], srcp);
             if (!r) r = kind == 'B' ? ks265_encode_picture_b(fr, srcp, refp, ref1p, out) : ks265_encode_picture(fr, srcp, refp, 0, out);
-            if (!r && e->cfg.calcPsnr) r = ks265_sse_picture(fr, srcp, out, dsse);
+            if (!r) r = quality_pass(e, NULL, fr, srcp, out, dsse, dssim);
             if (!r) r = ks265_frame_pack_compact(fr, e->stg[k], e->cfg.calcPsnr ? dsse : NULL);
             if (keep_it) {
                 void *ex = NULL;
@@ -976,11 +995,12 @@ static int submit(Enc *e, Input *in, int kind, int poc, int qp, const int *l0, i
                     r = ks265_frame_p_restore(fr, state0);
                     if (!r) r = ks265_load_i420(fr, e->dev_in[k], srcp);
                     if (!r) r = kind == 'B' ? ks265_encode_picture_b(fr, srcp, refp, ref1p, out) : ks265_encode_picture(fr, srcp, refp, 0, out);
-                    if (!r && e->cfg.calcPsnr) r = ks265_sse_picture(fr, srcp, out, dsse);
+                    if (!r) r = quality_pass(e, NULL, fr, srcp, out, dsse, dssim);
                     if (!r) r = ks265_frame_pack_compact(fr, e->stg[k], e->cfg.calcPsnr ? dsse : NULL);
                 }
             }
         }
+        if (!r && dssim) r = ks265_memcpy_d2h_async(cx, j->ssim, dssim, 24);  /* (not part of the captured picture: every job has its own buffer) */
         if (!r) r = ks265_event_record(cx, e->ev_loaded[k]);                  /* the input buffer is free again (a little later than on the plain path) */
         if (!r) r = ks265_event_record(cx, e->ev_staged[k]);
         e->dpb_poc[slot] = poc;
@@ -998,7 +1018,7 @@ static int submit(Enc *e, Input *in, int kind, int poc, int qp, const int *l0, i
         else r = ks265_encode_picture(fr, srcp, e->dpb[dpb_find(e, l0[0])], 0, out);
     }
     e->dpb_poc[slot] = poc;
-    if (!r && e->cfg.calcPsnr && !split) r = ks265_sse_picture(fr, srcp, out, dsse);
+    if (!r && !split) { r = quality_pass(e, NULL, fr, srcp, out, dsse, dssim); if (!r && dssim) r = ks265_memcpy_d2h_async(cx, j->ssim, dssim, 24); }
     if (!r && e->recon_on) {
         r = ks265_store_i420(fr, out, e->dev_recon);
         if (!r) r = ks265_memcpy_d2h_async(cx, j->recon, e->dev_recon, fsz);
@@ -1007,7 +1027,8 @@ static int submit(Enc *e, Input *in, int kind, int poc, int qp, const int *l0, i
         /* the drain runs on the copy-out stream (in order with the earlier pictures' drains: the staging block of this slot has been copied out before it is written) */
         if (!r) r = ks265_event_record(cx, e->ev_coded[k]);
         if (!r) r = ks265_stream_wait_event(e->ctx_out, e->ev_coded[k]);
-        if (!r && e->cfg.calcPsnr) r = ks265_sse_picture_on(e->ctx_out, fr, srcp, out, dsse);
+        if (!r) r = quality_pass(e, e->ctx_out, fr, srcp, out, dsse, dssim);
+        if (!r && dssim) r = ks265_memcpy_d2h_async(e->ctx_out, j->ssim, dssim, 24);
         if (!r) r = ks265_frame_pack_compact_on(e->ctx_out, fr, e->stg[k], e->cfg.calcPsnr ? dsse : NULL);
         if (!r) r = ks265_event_record(e->ctx_out, e->ev_packed[k]);
         if (!r) r = ks265_event_record(e->ctx_out, e->ev_staged[k]);
@@ -1332,6 +1353,17 @@ static int take_output(Enc *e, int max_in_flight, int max_pics, QY265Nal **pNals
                 logf_(2, e->log_level, "%d\t%c\t%ld\t%.4f\t%.4f\t%.4f\t%d\n", j->disp, j->kind, (long)j->nal_len * 8, ps[0], ps[1], ps[2], j->qp);
             }
         }
+        if (e->ssim_on) {
+            const double nw[3] = {(double)(e->W / 8) * (e->H / 8), (double)(e->W / 16) * (e->H / 16), (double)(e->W / 16) * (e->H / 16)};
+            for (int k = 0; k < 3; ++k) {
+                e->q_hi[k] += j->ssim[k] >> 30; e->q_lo[k] += j->ssim[k] & 0x3fffffff;
+                e->q_last_ssim[k] = nw[k] > 0 ? (double)j->ssim[k] / 1073741824.0 / nw[k] : 0.0;
+            }
+            /* the reference prints nothing per picture with -ssim 2 (and its -psnr 2 table stays as it is: callers parse it): a line in this build's own style */
+            if (e->cfg.calcSsim >= 2) logf_(2, e->log_level, "ks265enc: poc %d ssim %.4f %.4f %.4f\n", j->disp, e->q_last_ssim[0], e->q_last_ssim[1], e->q_last_ssim[2]);
+        }
+        e->q_last_poc = j->disp; e->q_seq = __atomic_add_fetch(&g_q_seq, 1, __ATOMIC_RELAXED);
+        for (int k = 0; k < 3; ++k) e->q_last_sse[k] = e->cfg.calcPsnr ? (double)j->sse[k] : 0.0;
         if (e->md5 && e->md5_ring) {                                    /* `POC n MD5 y,u,v` in display order, like the reference's reconstruction output */
             memcpy(e->md5_ring[j->disp & 255], j->md5, sizeof j->md5); e->md5_have[j->disp & 255] = 1;
             while (e->md5_have[e->md5_next & 255]) {
@@ -1351,6 +1383,16 @@ static int take_output(Enc *e, int max_in_flight, int max_pics, QY265Nal **pNals
     *pNals = e->nals; *n = cnt;
     if (pics) *pics = taken;
     return err;
+}
+
+/* the reference's line behind `bitrate, psnr:` (or alone with -psnr 0), byte for byte its format (tests/golden/ssim_ref.npz): kbit/s, then the mean over the pictures of
+ * every plane's mean over its windows.  hi / lo: the summed fixed-point window sums, hi x 2^30 + lo */
+static double ssim_mean(long long hi, long long lo, double windows, long frames) { return windows > 0 && frames ? ((double)hi + (double)lo / 1073741824.0) / (windows * (double)frames) : 0.0; }
+static void ssim_line(const Enc *e, long frames, long long bytes, const long long hi[3], const long long lo[3])
+{
+    const double nw[3] = {(double)(e->W / 8) * (e->H / 8), (double)(e->W / 16) * (e->H / 16), (double)(e->W / 16) * (e->H / 16)};
+    logf_(2, e->log_level, "\t ssim: %.4f\t%.4f\t%.4f\t%.4f\n", bytes * 8.0 * e->cfg.frameRate / frames / 1000.0, ssim_mean(hi[0], lo[0], nw[0], frames), ssim_mean(hi[1], lo[1], nw[1], frames),
+          ssim_mean(hi[2], lo[2], nw[2], frames));
 }
 
 static void lane_close(Enc *e, int report)
@@ -1376,9 +1418,10 @@ static void lane_close(Enc *e, int report)
             for (int k = 0; k < 3; ++k) ps[k] = e->st.sse[k] > 0 ? 10.0 * log10(255.0 * 255.0 * np[k] * e->st.frames / e->st.sse[k]) : 99.0;
             logf_(2, e->log_level, "bitrate, psnr: %.4f\t%.4f\t%.4f\t%.4f\n", e->st.bytes * 8.0 * e->cfg.frameRate / e->st.frames / 1000.0, ps[0], ps[1], ps[2]);
         }
+        if (report && e->ssim_on && e->st.frames) ssim_line(e, e->st.frames, e->st.bytes, e->q_hi, e->q_lo);
         for (int i = 0; i < MAX_JOBS; ++i) {
             Job *j = &e->jobs[i];
-            ks265_host_free(e->ctx, j->cmp); ks265_host_free(e->ctx, j->recon); ks265_host_free(e->ctx, j->qp_map); ks265_host_free(e->ctx, j->rq_host); free(j->lvlbuf); free(j->dirty);
+            ks265_host_free(e->ctx, j->cmp); ks265_host_free(e->ctx, j->recon); ks265_host_free(e->ctx, j->qp_map); ks265_host_free(e->ctx, j->ssim); ks265_host_free(e->ctx, j->rq_host); free(j->lvlbuf); free(j->dirty);
             if (j->ev) ks265_event_destroy(e->ctx, j->ev);
             free(j->nal);
         }
@@ -1408,7 +1451,7 @@ static void lane_close(Enc *e, int report)
             pic_free(e, &e->srcq[k]);
         }
         for (int i = 0; i < e->ngraph; ++i) ks265_graph_destroy(e->ctx, e->graph[i].exec);
-        ks265_dev_free(e->ctx, e->dev_sse); ks265_dev_free(e->ctx, e->dev_recon);
+        ks265_dev_free(e->ctx, e->dev_sse); ks265_dev_free(e->ctx, e->dev_ssim); ks265_dev_free(e->ctx, e->dev_recon);
         for (int q = 0; q < 2; ++q) { ks265_dev_free(e->ctx, e->aq_off[q]); ks265_dev_free(e->ctx, e->aq_inv[q]); ks265_dev_free(e->ctx, e->aq_scratch[q]); }
         for (int k = 0; k < NPIPE; ++k) ks265_dev_free(e->ctx, e->dev_qmap[k]);
         for (int q = 0; q < 2; ++q) ks265_dev_free(e->ctx, e->dev_qmap_key[q]);
@@ -1572,6 +1615,9 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
         if (!r && e->split) r = pic_alloc(e, &e->srcq[k]);
     }
     if (!r) r = ks265_dev_malloc(e->ctx, (void **)&e->dev_sse, 64);
+    e->ssim_on = cfg->calcSsim != 0 && ks265_ssim_picture && ks265_ssim_picture_on;
+    if (cfg->calcSsim && !e->ssim_on) logf_(2, e->log_level, "ks265enc: SSIM is unavailable: the device library has no ks265_ssim_picture (-ssim is ignored, no ssim line)\n");
+    if (!r && e->ssim_on) r = ks265_dev_malloc(e->ctx, (void **)&e->dev_ssim, 96);
     e->aq_on = cfg->iAqMode != 0 && cfg->fAqStrength > 0;
     /* cuTree: -rc 3 (CRF) with the reference's -cutree 1 (its default), B pictures (with -bframes 0 the reference runs no tree: TEncParam+0x388 = 0, every offset it leaves is zero)
      * and a lookahead (not -lookahead 0, not zero latency): a QP per CTU from the lookahead window */
@@ -1689,6 +1735,7 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
             j->lvl[0] = (int16_t *)j->lvlbuf; j->lvl[1] = (int16_t *)(j->lvlbuf + npx * 2); j->lvl[2] = (int16_t *)(j->lvlbuf + npx * 2 + npx / 2);
         }
         if (!r && e->qmap_on) r = ks265_host_malloc(e->ctx, (void **)&j->qp_map, (size_t)e->geom.ctu_cols * e->geom.ctu_rows);
+        if (!r && e->ssim_on) r = ks265_host_malloc(e->ctx, (void **)&j->ssim, 32);
         if (!r && e->rdoq_on) r = ks265_host_malloc(e->ctx, (void **)&j->rq_host, 1440 * sizeof(int32_t) + 104 * sizeof(int64_t));
         if (!r) r = ks265_event_create(e->ctx, &j->ev);
         j->nal_cap = npx * 2 + 65536;
@@ -2445,12 +2492,15 @@ void QY265EncoderClose(void *h)
         Enc *e0 = t->lane[0];
         ks265_enc_stats st; memset(&st, 0, sizeof st);
         for (int i = 0; i < t->nlanes; ++i) { const ks265_enc_stats *s = &t->lane[i]->st; st.frames += s->frames; st.bytes += s->bytes; for (int k = 0; k < 3; ++k) st.sse[k] += s->sse[k]; }
+        long long hi[3] = {0, 0, 0}, lo[3] = {0, 0, 0};
+        for (int i = 0; i < t->nlanes; ++i) for (int k = 0; k < 3; ++k) { hi[k] += t->lane[i]->q_hi[k]; lo[k] += t->lane[i]->q_lo[k]; }
         if (e0->cfg.calcPsnr && st.frames) {
             const double np[3] = {(double)e0->W * e0->H, (double)e0->W * e0->H / 4, (double)e0->W * e0->H / 4};
             double ps[3];
             for (int k = 0; k < 3; ++k) ps[k] = st.sse[k] > 0 ? 10.0 * log10(255.0 * 255.0 * np[k] * st.frames / st.sse[k]) : 99.0;
             logf_(2, e0->log_level, "bitrate, psnr: %.4f\t%.4f\t%.4f\t%.4f\n", st.bytes * 8.0 * e0->cfg.frameRate / st.frames / 1000.0, ps[0], ps[1], ps[2]);
         }
+        if (e0->ssim_on && st.frames) ssim_line(e0, st.frames, st.bytes, hi, lo);
     }
     for (int i = 0; i < t->nlanes; ++i) lane_close(t->lane[i], t->nlanes == 1);
     pthread_mutex_destroy(&t->wake.mu); pthread_cond_destroy(&t->wake.cv);
@@ -2569,6 +2619,31 @@ int ks265_enc_get_stats(void *h, ks265_enc_stats *out)
         out->submit_wait_ms += s->submit_wait_ms; out->occ_samples += s->occ_samples; out->occ_ring += s->occ_ring; out->occ_gpu += s->occ_gpu; out->occ_ready += s->occ_ready;
     }
     if (t->nlanes > 1) out->output_ms = t->output_ms;
+    return QY_OK;
+}
+
+int ks265_enc_get_quality(void *h, ks265_enc_quality *out)
+{
+    Top *t = (Top *)h;
+    if (!t || !out) return QY_POINTER;
+    memset(out, 0, sizeof *out);
+    const Enc *e0 = t->lane[0], *last = NULL;
+    const double nw[3] = {(double)(e0->W / 8) * (e0->H / 8), (double)(e0->W / 16) * (e0->H / 16), (double)(e0->W / 16) * (e0->H / 16)};
+    long long hi[3] = {0, 0, 0}, lo[3] = {0, 0, 0};
+    out->last_poc = -1;
+    for (int i = 0; i < t->nlanes; ++i) {
+        Enc *e = t->lane[i];
+        pthread_mutex_lock(&e->mu);
+        out->frames += e->st.frames;
+        for (int k = 0; k < 3; ++k) { out->sse[k] += e->st.sse[k]; hi[k] += e->q_hi[k]; lo[k] += e->q_lo[k]; }
+        if (e->st.frames && (!last || e->q_seq > last->q_seq)) {
+            last = e; out->last_poc = e->q_last_poc;
+            for (int k = 0; k < 3; ++k) { out->last_sse[k] = e->q_last_sse[k]; out->last_ssim[k] = e->q_last_ssim[k]; }
+        }
+        pthread_mutex_unlock(&e->mu);
+    }
+    out->have_sse = e0->cfg.calcPsnr != 0; out->have_ssim = e0->ssim_on;
+    for (int k = 0; k < 3; ++k) out->ssim[k] = e0->ssim_on && nw[k] > 0 ? ((double)hi[k] + (double)lo[k] / 1073741824.0) / nw[k] : 0.0;
     return QY_OK;
 }
 

@@ -65,6 +65,7 @@ EXPORTS = [
     "ks265_encode_picture", "ks265_encode_picture_b", "ks265_encode_picture_mref", "ks265_encode_picture_b_mref", "ks265_ref_pick", "ks265_ref_decide", "ks265_reconstruct_mref",
     "ks265_intra_candidates", "ks265_cu_decide_ii", "ks265_cu_decide_b_ii", "ks265_intra_inter_reconstruct", "ks265_frame_set_profiling", "ks265_frame_stage_ms", "ks265_frame_me_int_ms", "ks265_frame_levels", "ks265_frame_pu", "ks265_frame_cu8", "ks265_frame_ibest", "ks265_frame_sao", "ks265_sse_picture",
     "ks265_input_validate", "ks265_input_convert", "ks265_wait_external", "ks265_external_wait_event",
+    "ks265_ssim_picture", "ks265_ssim_picture_on",
 ]
 
 
@@ -505,6 +506,13 @@ class KsFrame:
         out = self.ks.zeros(24)
         self.ks._chk(self.lib.ks265_sse_picture(self.h, a.c(), b.c(), _p(out)))
         return self.ks.host(out, np.uint64)
+
+    def ssim_picture(self, a: DevPic, b: DevPic, with_sse: bool = True):
+        """(sse[3] uint64 or None, ssim[3] int64): per plane the SSE and the sum over the plane's whole 8x8 windows of llrint(ssim * 2^30), from one launch"""
+        sse = self.ks.zeros(24) if with_sse else None
+        out = self.ks.zeros(24)
+        self.ks._chk(self.lib.ks265_ssim_picture(self.h, a.c(), b.c(), _p(sse), _p(out)))
+        return (self.ks.host(sse, np.uint64) if with_sse else None), self.ks.host(out, np.int64)
 
     # internal workspace views (device pointers wrapped as ctypes addresses)
     def ws_ptr(self, name: str, comp: int = 0) -> int:
