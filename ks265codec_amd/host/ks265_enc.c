@@ -296,11 +296,22 @@ static void copy_shared(CopyPool *p, uint8_t *d, const uint8_t *s, size_t n)
 #define LA_RING 9                                                      /* half-size pictures kept for the analysis: the current one and eight back */
 #define LA_QMAX 64                                                     /* pictures that may wait at the input for their analysis (a GOP lane runs a whole GOP ahead of its pixel path) */
 #define LA_FLY 16                                                      /* analyses in flight = result areas */
-typedef struct Input { int used, disp, key, base_qp, iper, mini4, kbps, la_what, la_p, la_buf, up_sync; long long pts; uint8_t *i420; uint8_t *dev; void *ev_up; } Input;   /* up_sync: the twin was filled by a host-synchronous copy (nothing to wait for) */   /* dev / ev_up: the slot's twin on the device, uploaded
-                                                                                                 * when the picture is handed in (round 4), and the event behind that upload */     /* pinned; key: this picture starts a closed GOP whatever the period says (GOP lanes,
-                                                                                                 * QY265EncoderKeyFrameRequest); base_qp: the QP in force when the picture was handed in (QY265EncoderReconfig) -
-                                                                                                 * iper: the key period in force then - all three travel WITH the picture: the scheduler thread
-                                                                                                 * may be several pictures behind the caller */
+/* an input slot.  i420: the pinned host copy of the picture.  key: this picture starts a closed GOP whatever the period says (GOP lanes, QY265EncoderKeyFrameRequest); base_qp: the
+ * QP in force when the picture was handed in (QY265EncoderReconfig) - iper: the key period in force then - all three travel WITH the picture: the scheduler thread may be several
+ * pictures behind the caller.  dev / ev_up: the slot's twin on the device, uploaded when the picture is handed in (round 4), and the event behind that upload; up_sync: the twin
+ * was filled by a host-synchronous copy (nothing to wait for) */
+typedef struct Input { int used, disp, key, base_qp, iper, mini4, kbps, la_what, la_p, la_buf, up_sync; long long pts; uint8_t *i420; uint8_t *dev; void *ev_up; } Input;
+
+/* one pixel path: a stream (context), the frame object that codes on it, its source picture and what its quality pass and -aq write on the device.  PATH_MAIN codes every picture
+ * that has no path of its own (and is the context that owns the lane's allocations and events); PATH_KEY: the key pictures (Enc::key_overlap); PATH_ANC: the anchors of the
+ * pyramid GOPs (Enc::anc_on).  What only one of them has - events, counters, DPB slots, the key pictures' QP maps - stays with its owner in Enc */
+enum { PATH_MAIN, PATH_KEY, PATH_ANC, NPATH };
+typedef struct PixPath {
+    ks265_ctx *ctx; ks265_frame *frame; ks265_pic src;
+    uint64_t *dev_sse;                                    /* 64 bytes: the SSE sums of the path's latest picture */
+    int64_t *dev_ssim;                                    /* -ssim: the three sums of the fused pass, 32 bytes apart inside PATH_MAIN's allocation of 96 (NULL without) */
+    double *aq_off, *aq_scratch; uint16_t *aq_inv;        /* -aq: the key pictures' stream has buffers of its own, the anchors share the main stream's */
+} PixPath;
 
 typedef struct Enc {
     QY265EncConfig cfg;
@@ -310,8 +321,8 @@ typedef struct Enc {
     int lean_b;                                                                         /* B pictures nothing predicts from: no intra candidates, no joint refinement, no SAO (KS265_LEAN_B=0: as the others) */
     int refs0, anc_hist[4], n_anc;                                                      /* -ref0 (qy265enc.h:142, the reference's ActiveRefNumFrm0InGop): how many past anchors an anchor of the pyramid searches; the last anchors' POCs, nearest first */
     int base_qp, iper, nthreads;
-    ks265_ctx *ctx; ks265_frame *frame; ks265_frame_geom geom; ks265_frame_cfg fcfg; ks265_stream_cfg scfg;
-    /* device: three streams - copy-in (ctx_in), the pixel path (ctx), copy-out (ctx_out) - so that the H2D of picture n+1 and the D2H of
+    PixPath path[NPATH]; ks265_frame_geom geom; ks265_frame_cfg fcfg; ks265_stream_cfg scfg;
+    /* device: three streams - copy-in (ctx_in), the pixel path (path[].ctx), copy-out (ctx_out) - so that the H2D of picture n+1 and the D2H of
      * picture n-1 run under the kernels of picture n.  Hand-over by events only (no host thread blocks): input buffers and output staging
      * sets rotate over NPIPE slots. */
 #define NPIPE 3
@@ -331,7 +342,7 @@ typedef struct Enc {
      * a record (ks265_frame_set_records_fence).  Measured at 2160p IPPP: 120 us of a 1.11 ms picture period leave the critical path. */
     /* -aq N (iAqMode != 0): adaptive quantisation = the reference's calcFrameAdaptQuant enc@0x4653c0 on the source picture (ks265_frame_adapt_quant, pinned on recorded
      * calls), one QP per CTU from it (ks265_aq_ctu_map), the pixel path and the writer on that map (ks265_frame_set_qp_map, cu_qp_delta) */
-    int aq_on, aq_nx, aq_ny; double *aq_off[2], *aq_scratch[2]; uint16_t *aq_inv[2]; int8_t *dev_qmap[NPIPE], *dev_qmap_key[2];   /* aq_*[1], dev_qmap_key: the key pictures' stream (its own maps, rotating with nkeys: a key picture runs beside the pictures of its rotation slot) */
+    int aq_on, aq_nx, aq_ny; int8_t *dev_qmap[NPIPE], *dev_qmap_key[2];   /* dev_qmap_key: the key pictures' stream (its own maps, rotating with nkeys: a key picture runs beside the pictures of its rotation slot) */
     int zero_latency;                                     /* -latency zerolatency without B pictures / lookahead / lanes: every EncodeFrame call hands out its own picture */
     int copy_mb;                                          /* KS265_COPYOUT_MB = N: hipMemcpyAsync takes the fixed part + N MB of stored lines per P / B picture (a key picture: everything) and the copy kernel
                                                            * only what lies beyond; default -1 = the copy kernel alone.  On this runtime the D2H hipMemcpyAsync is itself a kernel (__amd_rocclr_copyBuffer,
@@ -344,20 +355,20 @@ typedef struct Enc {
     int use_graph, ngraph; struct { uint64_t key[9]; void *exec; } graph[MAX_GRAPHS];
     int recon_fd, recon_on; uint8_t *dev_recon;           /* reconstruction dump (the CLI's -o) and / or plane MD5s (-md5 1): recon_on = the pictures come back to the host */
     int md5, fixqp, psnr_hdr; int md5_next; char (*md5_ring)[3][33]; unsigned char *md5_have;   /* MD5 lines go out in display order (ring of 256 by display index) */
-    ks265_pic src; ks265_pic dpb[MAX_DPB]; int dpb_poc[MAX_DPB]; int ndpb; uint64_t *dev_sse;
-    /* -ssim: the fused pass is there and asked for; its device sums ([0..2] main stream / copy-out stream, [4..6] key pictures' stream, [8..10] anchors' stream); the session's
+    ks265_pic dpb[MAX_DPB]; int dpb_poc[MAX_DPB]; int ndpb;
+    /* -ssim: the fused pass is there and asked for (its device sums: PixPath::dev_ssim); the session's
      * totals in output order as exact integers (hi x 2^30 + lo: the same for any number of GOP lanes), the picture accounted last and when (q_seq: across lanes) */
-    int ssim_on; int64_t *dev_ssim; long long q_hi[3], q_lo[3]; int q_last_poc; double q_last_sse[3], q_last_ssim[3]; unsigned long q_seq;
-    /* key pictures on their own stream and frame object: an intra picture keeps 34 of 256 compute units busy for ~26 ms (2160p); coded as soon as its
+    int ssim_on; long long q_hi[3], q_lo[3]; int q_last_poc; double q_last_sse[3], q_last_ssim[3]; unsigned long q_seq;
+    /* key pictures on their own stream and frame object (path[PATH_KEY]): an intra picture keeps 34 of 256 compute units busy for ~26 ms (2160p); coded as soon as its
      * input arrives - the pixel path is tens of pictures behind the input - it runs underneath the P pictures of the previous GOP instead of between
      * two GOPs.  Its reconstruction goes to one of two DPB slots of its own; the first P picture of the GOP waits for ev_key. */
     int refs_b;                                           /* reference pictures per list of a pyramid's B pictures (1 .. 4) */
     /* round 5 - the ANCHOR LANE of the pyramid GOPs: a mini-GOP's anchor P picture predicts from the anchor before it and from nothing else, so the chain of anchors is coded on a
-     * stream and frame object of its own (like the key pictures), ahead of the B pictures of the mini-GOPs behind it: its kernels - and the long intra chain pass of a picture
+     * stream and frame object of its own (path[PATH_ANC], like the key pictures), ahead of the B pictures of the mini-GOPs behind it: its kernels - and the long intra chain pass of a picture
      * 4 or 8 away from its reference - run beside the B pictures' instead of in front of them.  Four DPB slots of its own, rotating; a slot is overwritten only after the B
      * pictures that read its previous content have run on the main stream (ev_mg: one mark per mini-GOP, recorded behind its last B picture) */
-    int anc_on, nanch, last_on_anc; ks265_ctx *ctx_anc; ks265_frame *frame_anc; ks265_pic src_anc; uint64_t *dev_sse_anc; void *ev_anc, *ev_mg[8];
-    int key_overlap, nkeys; ks265_ctx *ctx_key; ks265_frame *frame_key; ks265_pic src_key; uint64_t *dev_sse_key; void *ev_key, *ev_firstp[2];
+    int anc_on, nanch, last_on_anc; void *ev_anc, *ev_mg[8];
+    int key_overlap, nkeys; void *ev_key, *ev_firstp[2];
     /* scheduling */
     Input in[MAX_INPUT]; int nin, next_disp, in_disp;          /* next_disp: pictures handed to the scheduler; in_disp: pictures taken in (= next_disp + the lookahead's queue la_q) */
     int gop_start;                                        /* display index of the last key picture */
@@ -415,6 +426,8 @@ typedef struct Enc {
     double rc_sum_budget, rc_bhist[RC_HIST], rc_sum_real, rc_rhist[RC_HIST];   /* the budget and the bits really produced, summed picture by picture like rc_sum_norm */
 } Enc;
 
+static ks265_ctx *main_ctx(const Enc *e) { return e->path[PATH_MAIN].ctx; }
+static ks265_frame *main_frame(const Enc *e) { return e->path[PATH_MAIN].frame; }
 static double now_ms(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec * 1e3 + t.tv_nsec * 1e-6; }
 static void rc_account(Enc *e);
 static void lane_wake_top(Enc *e)
@@ -431,13 +444,13 @@ static int pic_alloc(Enc *e, ks265_pic *p)
     /* KS265_PIC_SPACER = bytes: an unused allocation in front of every picture (where pictures lie against each other in device memory decides what shares a memory channel:
      * round 4) */
     const char *sp = getenv("KS265_PIC_SPACER");
-    if (sp && atol(sp) > 0 && e->nspacer < 64) { void *d = NULL; if (!ks265_dev_malloc(e->ctx, &d, (size_t)atol(sp))) e->spacer[e->nspacer++] = d; }
-    int r = ks265_dev_malloc(e->ctx, (void **)&p->y, (size_t)e->geom.bytes_y);
-    if (!r) r = ks265_dev_malloc(e->ctx, (void **)&p->u, (size_t)e->geom.bytes_c);
-    if (!r) r = ks265_dev_malloc(e->ctx, (void **)&p->v, (size_t)e->geom.bytes_c);
+    if (sp && atol(sp) > 0 && e->nspacer < 64) { void *d = NULL; if (!ks265_dev_malloc(main_ctx(e), &d, (size_t)atol(sp))) e->spacer[e->nspacer++] = d; }
+    int r = ks265_dev_malloc(main_ctx(e), (void **)&p->y, (size_t)e->geom.bytes_y);
+    if (!r) r = ks265_dev_malloc(main_ctx(e), (void **)&p->u, (size_t)e->geom.bytes_c);
+    if (!r) r = ks265_dev_malloc(main_ctx(e), (void **)&p->v, (size_t)e->geom.bytes_c);
     return r;
 }
-static void pic_free(Enc *e, ks265_pic *p) { ks265_dev_free(e->ctx, p->y); ks265_dev_free(e->ctx, p->u); ks265_dev_free(e->ctx, p->v); p->y = p->u = p->v = NULL; }
+static void pic_free(Enc *e, ks265_pic *p) { ks265_dev_free(main_ctx(e), p->y); ks265_dev_free(main_ctx(e), p->u); ks265_dev_free(main_ctx(e), p->v); p->y = p->u = p->v = NULL; }
 
 /* ---- the dispatcher: ONE host thread waits for the pictures' events, in submission order (the copy-out stream finishes them in that order), and
  *      releases them to the writers.  Writers that waited inside the GPU runtime themselves would contend with the calling thread's enqueues. */
@@ -454,8 +467,8 @@ static void *dispatcher(void *arg)
         err = ks265_event_wait(e->ctx_out, j->ev);
         /* the device error word of the streams that code pictures (a wavefront that timed out leaves a picture whose levels do not match its reconstruction): the
          * picture - this one or one enqueued after it - fails instead of going out as if nothing had happened */
-        if (!err) err = ks265_take_device_error(e->ctx);
-        if (!err && e->ctx_key) err = ks265_take_device_error(e->ctx_key);
+        if (!err) err = ks265_take_device_error(main_ctx(e));
+        if (!err && e->path[PATH_KEY].ctx) err = ks265_take_device_error(e->path[PATH_KEY].ctx);
         if (err) logf_(2, e->log_level, "ks265enc: device error at picture %d: %s\n", j->disp, "intra wavefront timeout or device error flag (ks265_take_device_error)");
         j->t_event = now_ms();
         pthread_mutex_lock(&e->mu);
@@ -847,10 +860,21 @@ static int quality_pass(Enc *e, ks265_ctx *on, ks265_frame *fr, ks265_pic src, k
     return on ? ks265_sse_picture_on(on, fr, src, rec, dsse) : ks265_sse_picture(fr, src, rec, dsse);
 }
 
-/* enqueue one picture: GPU work + copies on the stream, then hand it to the writers */
-static int submit(Enc *e, Input *in, int kind, int poc, int qp, const int *l0, int nl0, const int *l1, int nl1, const int *keep_after, int nkeep, int is_ref, int key_headers)
+/* ---- submit(): one picture's GPU work + copies on the streams, then the hand-over to the writers - a sequence of steps (scheduler thread).  What the steps share travels in a
+ *      Sub that submit() owns; nothing of it outlives the call.  Every device-library call of a step is skipped once an earlier one has failed (the lane is lost then: sched_err) */
+typedef struct Sub {
+    Job *j; Input *in;
+    int kind, poc, qp, nl0, nl1, is_ref; const int *l0, *l1;
+    int keep[32], nk;                                     /* POCs that must stay in the DPB: the caller's keep_after + what this picture uses */
+    int k, recycled;                                      /* rotation slot of the input buffer / staging set (seq % NPIPE); it has held a picture before */
+    int path; PixPath *p;                                 /* the pixel path that codes the picture (PATH_*) */
+    int split, direct, graphable, lean;
+    const uint8_t *din; ks265_pic srcp; int slot; ks265_pic out;   /* the packed input on the device, the unpacked source picture, the reconstruction's DPB slot */
+} Sub;
+
+/* wait for a free job slot (the ring is full only if the consumer did not drain it: block on the oldest) */
+static Job *wait_job_slot(Enc *e)
 {
-    /* wait for a free job slot (the ring is full only if the consumer did not drain it: block on the oldest) */
     pthread_mutex_lock(&e->mu);
     const double tw0 = now_ms();
     while (e->njobs == e->ring && !e->quit) {
@@ -858,240 +882,334 @@ static int submit(Enc *e, Input *in, int kind, int poc, int qp, const int *l0, i
         pthread_cond_wait(&e->cv_done, &e->mu);                         /* take_output signals when it has freed ring slots */
     }
     e->st.submit_wait_ms += now_ms() - tw0;
-    if (e->quit) { pthread_mutex_unlock(&e->mu); return QY_FAIL; }       /* drained by take_output() of the calling thread itself: never full here */
-    Job *j = &e->jobs[e->job_tail];
+    Job *j = e->quit ? NULL : &e->jobs[e->job_tail];                    /* drained by take_output() of the calling thread itself: never full here */
     pthread_mutex_unlock(&e->mu);
-    const size_t fsz = (size_t)e->W * e->H * 3 / 2;
-    const int k = (int)(e->seq % NPIPE);
-    const int recycled = e->seq >= NPIPE;
-    /* copy-in stream: the slot's previous picture must have been unpacked before the buffer is overwritten */
-    int r = recycled ? ks265_stream_wait_event(e->ctx_in, e->ev_loaded[k]) : 0;
-    /* pixel path: the main stream / frame object, or the key pictures' own */
-    const int on_key = kind == 'I' && e->key_overlap && (in->iper <= 0 || in->iper >= 32);
-    const int on_anc = kind == 'P' && e->anc_on && e->key_overlap && nl0 == 1;      /* (key_overlap goes off with the reconstruction dump: everything on the main stream then) */
-    const int split = e->split && !on_key && !on_anc;
-    ks265_ctx *cx = on_key ? e->ctx_key : on_anc ? e->ctx_anc : e->ctx;
-    ks265_frame *fr = on_key ? e->frame_key : on_anc ? e->frame_anc : e->frame;
-    ks265_pic srcp = on_key ? e->src_key : on_anc ? e->src_anc : split ? e->srcq[k] : e->src;
-    if (!r && split && recycled) r = ks265_stream_wait_event(e->ctx_in, e->ev_drained[k]);   /* srcq[k]'s last reader (the SSE of three pictures ago) is through */
-    /* with the lookahead the picture is on the device already, or on its way: uploaded into the slot's twin when it was handed in (round 4); else an H2D copy here, on this
-     * stream, behind the waits above.  Graph replay needs fixed addresses: a device-to-device copy into the rotation buffer */
-    const uint8_t *din = e->dev_in[k];
+    return j;
+}
+
+/* pixel path: the main stream / frame object, the key pictures' own or the anchors' own - the ONE place that decides it - and what follows from the choice */
+static void choose_path(Enc *e, Sub *s)
+{
+    const int on_key = s->kind == 'I' && e->key_overlap && (s->in->iper <= 0 || s->in->iper >= 32);
+    const int on_anc = s->kind == 'P' && e->anc_on && e->key_overlap && s->nl0 == 1;      /* (key_overlap goes off with the reconstruction dump: everything on the main stream then) */
+    s->path = on_key ? PATH_KEY : on_anc ? PATH_ANC : PATH_MAIN;
+    s->p = &e->path[s->path];
+    s->k = (int)(e->seq % NPIPE);
+    s->recycled = e->seq >= NPIPE;
+    s->split = e->split && s->path == PATH_MAIN;
+    s->srcp = s->split ? e->srcq[s->k] : s->p->src;
     /* an anchor on its lane whose picture is on the device already waits for the upload itself: a mark on the copy-in stream would sit behind that stream's work for the
      * pictures in front of it - and, HIP streams sharing hardware queues (four by default), behind whatever else runs in that queue: measured, the anchor then starts when
      * the last B picture of the mini-GOP before it has left the device */
-    const int direct = on_anc && in->dev && !e->use_graph;
-    if (direct) { if (!r && !in->up_sync) r = ks265_stream_wait_event(cx, in->ev_up); din = in->dev; }
+    s->direct = s->path == PATH_ANC && s->in->dev && !e->use_graph;
+    /* graph path: a P picture with one reference on the main stream, once the first pictures have made every lazy allocation */
+    s->graphable = e->use_graph && ((s->kind == 'P' && s->nl0 == 1) || (s->kind == 'B' && s->nl0 == 1 && s->nl1 == 1)) && s->path == PATH_MAIN && !e->recon_on && e->seq >= 8;
+}
+
+/* the input picture reaches the device and, unpacked and padded, the path's source picture */
+static int stage_input(Enc *e, Sub *s)
+{
+    const size_t fsz = (size_t)e->W * e->H * 3 / 2;
+    const int k = s->k; Input *in = s->in; ks265_ctx *cx = s->p->ctx;
+    /* copy-in stream: the slot's previous picture must have been unpacked before the buffer is overwritten */
+    int r = s->recycled ? ks265_stream_wait_event(e->ctx_in, e->ev_loaded[k]) : 0;
+    if (!r && s->split && s->recycled) r = ks265_stream_wait_event(e->ctx_in, e->ev_drained[k]);   /* srcq[k]'s last reader (the SSE of three pictures ago) is through */
+    /* with the lookahead the picture is on the device already, or on its way: uploaded into the slot's twin when it was handed in (round 4); else an H2D copy here, on this
+     * stream, behind the waits above.  Graph replay needs fixed addresses: a device-to-device copy into the rotation buffer */
+    s->din = e->dev_in[k];
+    if (s->direct) { if (!r && !in->up_sync) r = ks265_stream_wait_event(cx, in->ev_up); s->din = in->dev; }     /* (see choose_path) */
     else if (in->dev) {
         if (!r && !in->up_sync) r = ks265_stream_wait_event(e->ctx_in, in->ev_up);
         if (!r && e->use_graph) r = ks265_memcpy_d2d_async(e->ctx_in, e->dev_in[k], in->dev, fsz);
-        else din = in->dev;
+        else s->din = in->dev;
     } else if (!r) r = ks265_memcpy_h2d_async(e->ctx_in, e->dev_in[k], in->i420, fsz);
-    if (!r && split) r = ks265_load_i420_on(e->ctx_in, fr, din, srcp);
-    if (!r && !direct) r = ks265_event_record(e->ctx_in, e->ev_h2d[k]);
-    uint64_t *dsse = on_key ? e->dev_sse_key : on_anc ? e->dev_sse_anc : e->dev_sse;
-    int64_t *dssim = e->ssim_on ? e->dev_ssim + (on_key ? 4 : on_anc ? 8 : 0) : NULL;
-    if (!r && !direct) r = ks265_stream_wait_event(cx, e->ev_h2d[k]);
-    /* graph path: a P picture with one reference on the main stream, once the first pictures have made every lazy allocation */
-    const int graphable = e->use_graph && ((kind == 'P' && nl0 == 1) || (kind == 'B' && nl0 == 1 && nl1 == 1)) && !on_key && !on_anc && !e->recon_on && e->seq >= 8;
-    if (!graphable && !split) {
-        if (!r) r = ks265_load_i420(fr, din, srcp);
+    if (!r && s->split) r = ks265_load_i420_on(e->ctx_in, s->p->frame, s->din, s->srcp);
+    if (!r && !s->direct) r = ks265_event_record(e->ctx_in, e->ev_h2d[k]);
+    if (!r && !s->direct) r = ks265_stream_wait_event(cx, e->ev_h2d[k]);
+    if (!s->graphable && !s->split) {
+        if (!r) r = ks265_load_i420(s->p->frame, s->din, s->srcp);
         if (!r) r = ks265_event_record(cx, e->ev_loaded[k]);
     }
-    if (!r) r = ks265_frame_set_qp(fr, qp, kind == 'I' ? kLambdaQ4[qp] : kLambdaInterQ4[qp]);
+    return r;
+}
+
+/* the picture's QP and the tools it runs without */
+static int set_picture_tools(Enc *e, Sub *s)
+{
+    ks265_frame *fr = s->p->frame;
+    int r = ks265_frame_set_qp(fr, s->qp, s->kind == 'I' ? kLambdaQ4[s->qp] : kLambdaInterQ4[s->qp]);
     /* round 6: a B picture nothing predicts from (half the pictures of a pyramid of 8) runs without intra candidates, without the joint refinement of its bi-predictive CUs and
      * without SAO - on the CPU mirror and on the MI355X its bytes at equal PSNR-Y stay (the refinement even costs bytes at QP + 4), a quarter of its kernel time goes */
     /* ... and a B picture others predict from whose own references are at most two pictures away (the second-deepest layer of a pyramid) keeps the refinement but runs without intra
      * candidates and without SAO: neutral at equal PSNR-Y on the mirror's three clips (profiles/r06_lean_b.txt) */
-    const int near = kind == 'B' && is_ref && nl0 > 0 && nl1 > 0 && poc - l0[0] <= 2 && l1[0] - poc <= 2;
-    const int lean = !e->lean_b || kind != 'B' ? 0 : !is_ref ? 2 : near && e->lean_b != 3 ? 1 : 0;          /* (KS265_LEAN_B=3: the non-reference pictures alone) */
-    if (!r) r = lean == 2 ? ks265_frame_set_picture_tools(fr, 0, 0, 0, e->lean_b == 2 && e->me_method == 2 ? 1 : -1) : lean == 1 ? ks265_frame_set_picture_tools(fr, 0, -1, 0, -1) : ks265_frame_set_picture_tools(fr, -1, -1, -1, -1);
-    if (e->rdoq_on && kind == 'I') e->rq_gop_seq = e->rc_sub;
-    if (!r && e->rdoq_on && kind != 'I') {
-        /* -rdoq 1: wait until every picture up to RC_LAG before this one is accounted (as the rate controller does), then the latest tables of this picture's kind among them */
-        int32_t *tb = j->rq_host;
-        pthread_mutex_lock(&e->mu);
-        const long s0 = e->rc_sub, need = s0 - RC_LAG;
-        for (;;) { rc_account(e); if (e->rc_acc_seq >= need || e->quit) break; pthread_cond_wait(&e->cv_done, &e->mu); }
-        int found = 0;
-        for (long q = need - 1; q >= 0 && q > e->rq_gop_seq && q >= need - (RQ_HIST - RC_LAG - 8) && !found; --q)
-            if (e->rq_hist_kind[q % RQ_HIST] == (char)kind) { memcpy(tb, e->rq_hist + (size_t)(q % RQ_HIST) * 1440, 1440 * sizeof(int32_t)); found = 1; }
-        pthread_mutex_unlock(&e->mu);
-        if (!found) r = ks265_rdoq_tables(&e->scfg, NULL, kind == 'P' ? KS265_SLICE_P : KS265_SLICE_B, qp, tb) ? KS265_FAIL : 0;
-        memcpy(tb + 1440, e->rq_lam, sizeof e->rq_lam);
-        if (!r) r = ks265_frame_set_rdoq(fr, tb, (const int64_t *)(tb + 1440), (const int64_t *)(tb + 1440) + 52);
-    }
-    if (!r && e->ct_on) {
+    const int near = s->kind == 'B' && s->is_ref && s->nl0 > 0 && s->nl1 > 0 && s->poc - s->l0[0] <= 2 && s->l1[0] - s->poc <= 2;
+    s->lean = !e->lean_b || s->kind != 'B' ? 0 : !s->is_ref ? 2 : near && e->lean_b != 3 ? 1 : 0;          /* (KS265_LEAN_B=3: the non-reference pictures alone) */
+    if (!r) r = s->lean == 2 ? ks265_frame_set_picture_tools(fr, 0, 0, 0, e->lean_b == 2 && e->me_method == 2 ? 1 : -1) : s->lean == 1 ? ks265_frame_set_picture_tools(fr, 0, -1, 0, -1) : ks265_frame_set_picture_tools(fr, -1, -1, -1, -1);
+    return r;
+}
+
+/* -rdoq 1: wait until every picture up to RC_LAG before this one is accounted (as the rate controller does), then the latest tables of this picture's kind among them */
+static int set_rdoq_tables(Enc *e, Sub *s)
+{
+    if (!e->rdoq_on) return 0;
+    if (s->kind == 'I') { e->rq_gop_seq = e->rc_sub; return 0; }
+    int32_t *tb = s->j->rq_host;
+    pthread_mutex_lock(&e->mu);
+    const long s0 = e->rc_sub, need = s0 - RC_LAG;
+    for (;;) { rc_account(e); if (e->rc_acc_seq >= need || e->quit) break; pthread_cond_wait(&e->cv_done, &e->mu); }
+    int found = 0;
+    for (long q = need - 1; q >= 0 && q > e->rq_gop_seq && q >= need - (RQ_HIST - RC_LAG - 8) && !found; --q)
+        if (e->rq_hist_kind[q % RQ_HIST] == (char)s->kind) { memcpy(tb, e->rq_hist + (size_t)(q % RQ_HIST) * 1440, 1440 * sizeof(int32_t)); found = 1; }
+    pthread_mutex_unlock(&e->mu);
+    int r = 0;
+    if (!found) r = ks265_rdoq_tables(&e->scfg, NULL, s->kind == 'P' ? KS265_SLICE_P : KS265_SLICE_B, s->qp, tb) ? KS265_FAIL : 0;
+    memcpy(tb + 1440, e->rq_lam, sizeof e->rq_lam);
+    if (!r) r = ks265_frame_set_rdoq(s->p->frame, tb, (const int64_t *)(tb + 1440), (const int64_t *)(tb + 1440) + 52);
+    return r;
+}
+
+/* one QP per CTU around this picture's QP (cuTree, else -aq): the map is made, handed to the frame object and copied home for the writer */
+static int set_qp_map(Enc *e, Sub *s)
+{
+    if (!e->ct_on && !e->aq_on) return 0;
+    const int k = s->k; PixPath *p = s->p;
+    ks265_ctx *ca = s->split ? e->ctx_in : p->ctx;
+    /* a key picture on its own stream runs beside the pictures of earlier GOPs - among them the one three submissions back, whose kernels still read dev_qmap[k]
+     * (ADVICE r4): it gets a map of its own; everything that touches that one is on the key pictures' stream, in order */
+    int8_t *qm = s->path == PATH_KEY ? e->dev_qmap_key[e->nkeys & 1] : e->dev_qmap[k];
+    int r = 0;
+    if (e->ct_on) {
         /* cuTree: the picture's block offsets were finished on the lookahead's stream when its mini-GOP was scheduled (ct_run): one QP per CTU around this picture's QP */
-        ks265_ctx *ca = split ? e->ctx_in : cx;
-        struct CtPic *cp = ct_slot(e, in->disp);
-        int8_t *qm = on_key ? e->dev_qmap_key[e->nkeys & 1] : e->dev_qmap[k];
-        if (cp->disp != in->disp) r = KS265_FAIL;
+        struct CtPic *cp = ct_slot(e, s->in->disp);
+        if (cp->disp != s->in->disp) r = KS265_FAIL;
         if (!r) r = ks265_stream_wait_event(ca, e->ct_ev);
-        if (!r) r = ks265_qoff_ctu_map(ca, cp->qoff, e->ct_nx, e->ct_ny, e->ct_lg, e->geom.ctu_cols, e->geom.ctu_rows, qp, e->cfg.qpmin, e->cfg.qpmax ? e->cfg.qpmax : 51, qm);
+        if (!r) r = ks265_qoff_ctu_map(ca, cp->qoff, e->ct_nx, e->ct_ny, e->ct_lg, e->geom.ctu_cols, e->geom.ctu_rows, s->qp, e->cfg.qpmin, e->cfg.qpmax ? e->cfg.qpmax : 51, qm);
         if (!r) r = ks265_event_record(ca, cp->ev_used);
         cp->used = 1;
-        if (!r) r = ks265_frame_set_qp_map(fr, qm);
-        if (!r) r = ks265_memcpy_d2h_async(ca, j->qp_map, qm, (size_t)e->geom.ctu_cols * e->geom.ctu_rows);
-        if (!r && split) { r = ks265_event_record(e->ctx_in, e->ev_h2d[k]); if (!r) r = ks265_stream_wait_event(cx, e->ev_h2d[k]); }
-    } else if (!r && e->aq_on) {
+    } else {
         /* the source picture is on the device: block variances -> offsets (the reference's arithmetic) -> one QP per CTU around this picture's QP.  With the split pipeline
          * this runs on the copy-in stream right behind the unpack (off the pixel path's chain: the mean is a sequential sum, 0.15 ms at 2160p); the map stays in its rotation
          * slot while the picture's kernels and the copy-home run */
-        ks265_ctx *ca = split ? e->ctx_in : cx;
         const size_t oy = (size_t)e->geom.pad_y * e->geom.stride_y + e->geom.pad_y, oc = (size_t)e->geom.pad_c * e->geom.stride_c + e->geom.pad_c;
-        r = ks265_frame_adapt_quant(ca, srcp.y + oy, e->geom.stride_y, srcp.u + oc, srcp.v + oc, e->geom.stride_c, e->aq_nx, e->aq_ny, e->aq_nx * e->aq_ny, e->cfg.fAqStrength,
-                                    e->aq_off[on_key], e->aq_inv[on_key], e->aq_scratch[on_key]);
-        /* a key picture on its own stream runs beside the pictures of earlier GOPs - among them the one three submissions back, whose kernels still read dev_qmap[k]
-         * (ADVICE r4): it gets a map of its own; everything that touches that one is on the key pictures' stream, in order */
-        int8_t *qm = on_key ? e->dev_qmap_key[e->nkeys & 1] : e->dev_qmap[k];
-        if (!r) r = ks265_aq_ctu_map(ca, e->aq_off[on_key], e->aq_nx, e->aq_ny, qp, e->cfg.rc ? e->cfg.qpmin : 0, e->cfg.rc && e->cfg.qpmax ? e->cfg.qpmax : 51, qm);
-        if (!r) r = ks265_frame_set_qp_map(fr, qm);
-        if (!r) r = ks265_memcpy_d2h_async(ca, j->qp_map, qm, (size_t)e->geom.ctu_cols * e->geom.ctu_rows);
-        if (!r && split) { r = ks265_event_record(e->ctx_in, e->ev_h2d[k]); if (!r) r = ks265_stream_wait_event(cx, e->ev_h2d[k]); }   /* (recorded again behind the map: the pixel path waits for this one) */
+        r = ks265_frame_adapt_quant(ca, s->srcp.y + oy, e->geom.stride_y, s->srcp.u + oc, s->srcp.v + oc, e->geom.stride_c, e->aq_nx, e->aq_ny, e->aq_nx * e->aq_ny, e->cfg.fAqStrength,
+                                    p->aq_off, p->aq_inv, p->aq_scratch);
+        if (!r) r = ks265_aq_ctu_map(ca, p->aq_off, e->aq_nx, e->aq_ny, s->qp, e->cfg.rc ? e->cfg.qpmin : 0, e->cfg.rc && e->cfg.qpmax ? e->cfg.qpmax : 51, qm);
     }
-    int keep[32], nk = 0;
-    for (int i = 0; i < nkeep; ++i) keep[nk++] = keep_after[i];
-    for (int i = 0; i < nl0; ++i) keep[nk++] = l0[i];
-    for (int i = 0; i < nl1; ++i) keep[nk++] = l1[i];
-    int slot;
-    if (on_key) {
-        slot = e->ndpb + (e->nkeys & 1);
+    if (!r) r = ks265_frame_set_qp_map(p->frame, qm);
+    if (!r) r = ks265_memcpy_d2h_async(ca, s->j->qp_map, qm, (size_t)e->geom.ctu_cols * e->geom.ctu_rows);
+    if (!r && s->split) { r = ks265_event_record(e->ctx_in, e->ev_h2d[k]); if (!r) r = ks265_stream_wait_event(p->ctx, e->ev_h2d[k]); }   /* (recorded again behind the map: the pixel path waits for this one) */
+    return r;
+}
+
+/* where the reconstruction goes: a free DPB slot, or one of the rotating slots the key pictures and the anchors own - those once their previous readers are through */
+static int choose_recon_slot(Enc *e, Sub *s)
+{
+    ks265_ctx *cx = s->p->ctx;
+    int r = 0;
+    switch (s->path) {
+    case PATH_KEY:
+        s->slot = e->ndpb + (e->nkeys & 1);
         /* everything enqueued on the main stream so far belongs to earlier GOPs: when this mark fires, the readers of the previous key picture are through.
          * The slot written now held the key picture two GOPs back: wait for the mark set when the previous key picture was submitted */
-        if (!r && e->nkeys >= 1) r = ks265_event_record(e->ctx, e->ev_firstp[(e->nkeys - 1) & 1]);
+        if (e->nkeys >= 1) r = ks265_event_record(main_ctx(e), e->ev_firstp[(e->nkeys - 1) & 1]);
         if (!r && e->nkeys >= 2) r = ks265_stream_wait_event(cx, e->ev_firstp[e->nkeys & 1]);
-    } else if (on_anc) {
-        slot = e->ndpb + 2 + (e->nanch & 3);
+        break;
+    case PATH_ANC:
+        s->slot = e->ndpb + 2 + (e->nanch & 3);
         /* the slot held the anchor four back, which closed mini-GOP nanch - 4; its readers on the main stream were the B pictures of mini-GOPs nanch - 4 and nanch - 3 */
-        if (!r && e->nanch >= 4) r = ks265_stream_wait_event(cx, e->ev_mg[(e->nanch - 3) & 7]);
-    } else slot = dpb_free_slot(e, keep, nk);
-    if (slot < 0) return QY_FAIL;
-    ks265_pic out = e->dpb[slot];
-    if (!r && graphable) {
-        const ks265_pic refp = e->dpb[dpb_find(e, l0[0])], ref1p = kind == 'B' ? e->dpb[dpb_find(e, l1[0])] : refp;
-        const uint64_t key[9] = {(uint64_t)(uintptr_t)refp.y, (uint64_t)(uintptr_t)out.y, (uint64_t)(uintptr_t)e->dev_in[k], (uint64_t)(uintptr_t)e->stg[k],
-                                 (uint64_t)qp, (uint64_t)ks265_frame_p_state(fr), (uint64_t)(e->cfg.calcPsnr != 0) | (uint64_t)e->ssim_on << 1, (uint64_t)kind | ((uint64_t)lean << 8), (uint64_t)(uintptr_t)ref1p.y};
-        void *exec = NULL;
-        for (int i = 0; i < e->ngraph && !exec; ++i) if (!memcmp(e->graph[i].key, key, sizeof key)) exec = e->graph[i].exec;
-        if (recycled) r = ks265_stream_wait_event(cx, e->ev_drained[k]);       /* the staging block of this rotation slot has been copied out */
-        if (!r && exec) {
-            r = ks265_graph_launch(cx, exec);
-            if (!r && kind == 'P') r = ks265_frame_p_advance(fr);              /* a B picture leaves the P pictures' predictor chain alone */
-        } else if (!r) {
-            int keep_it = e->ngraph < MAX_GRAPHS;
-            const int state0 = ks265_frame_p_state(fr);
-            if (keep_it && ks265_capture_begin(cx)) { keep_it = 0; e->use_graph = 0; }   /* no capture on this runtime: launch by launch from here on */
-            if (!r) r = ks265_load_i420(fr, e->dev_in[k], srcp);
-            if (!r) r = kind == 'B' ? ks265_encode_picture_b(fr, srcp, refp, ref1p, out) : ks265_encode_picture(fr, srcp, refp, 0, out);
-            if (!r) r = quality_pass(e, NULL, fr, srcp, out, dsse, dssim);
-            if (!r) r = ks265_frame_pack_compact(fr, e->stg[k], e->cfg.calcPsnr ? dsse : NULL);
-            if (keep_it) {
-                void *ex = NULL;
-                const int rc = ks265_capture_end(cx, &ex);                      /* also ends a capture that failed half-way */
-                if (!r && !rc) { memcpy(e->graph[e->ngraph].key, key, sizeof key); e->graph[e->ngraph].exec = ex; ++e->ngraph; r = ks265_graph_launch(cx, ex); }
-                else if (!r) {                                                  /* recorded but not instantiated: nothing ran.  Do the picture launch by launch, graphs off */
-                    e->use_graph = 0;
-                    r = ks265_frame_p_restore(fr, state0);
-                    if (!r) r = ks265_load_i420(fr, e->dev_in[k], srcp);
-                    if (!r) r = kind == 'B' ? ks265_encode_picture_b(fr, srcp, refp, ref1p, out) : ks265_encode_picture(fr, srcp, refp, 0, out);
-                    if (!r) r = quality_pass(e, NULL, fr, srcp, out, dsse, dssim);
-                    if (!r) r = ks265_frame_pack_compact(fr, e->stg[k], e->cfg.calcPsnr ? dsse : NULL);
-                }
+        if (e->nanch >= 4) r = ks265_stream_wait_event(cx, e->ev_mg[(e->nanch - 3) & 7]);
+        break;
+    default:
+        s->slot = dpb_free_slot(e, s->keep, s->nk);
+    }
+    if (s->slot < 0) return KS265_FAIL;
+    s->out = e->dpb[s->slot];
+    return r;
+}
+
+/* the picture's kernels: THE dispatch onto the device library's four entries - key picture / P / P with several references / B / B with several references per list */
+static int code_picture(Enc *e, const Sub *s)
+{
+    ks265_frame *fr = s->p->frame;
+    ks265_pic r0[4], r1[4];
+    for (int i = 0; i < s->nl0; ++i) r0[i] = e->dpb[dpb_find(e, s->l0[i])];
+    for (int i = 0; i < s->nl1; ++i) r1[i] = e->dpb[dpb_find(e, s->l1[i])];
+    if (s->kind == 'B') return s->nl0 > 1 || s->nl1 > 1 ? ks265_encode_picture_b_mref(fr, s->srcp, r0, s->nl0, r1, s->nl1, s->out) : ks265_encode_picture_b(fr, s->srcp, r0[0], r1[0], s->out);
+    if (s->kind == 'P' && s->nl0 > 1) return ks265_encode_picture_mref(fr, s->srcp, r0, s->nl0, s->out);
+    const int key = s->kind == 'I';
+    return ks265_encode_picture(fr, s->srcp, key ? s->out : r0[0], key, s->out);
+}
+
+/* the reconstruction comes back to the host (reconstruction dump / -md5): on the picture's own stream */
+static int recon_home(Enc *e, const Sub *s)
+{
+    int r = ks265_store_i420(s->p->frame, s->out, e->dev_recon);
+    if (!r) r = ks265_memcpy_d2h_async(s->p->ctx, s->j->recon, e->dev_recon, (size_t)e->W * e->H * 3 / 2);
+    return r;
+}
+
+/* the drain of a coded picture: quality pass, its SSIM sums home, the records packed into the staging set of the rotation slot.  on = NULL: on the picture's own stream - there
+ * the reconstruction goes home in between, and the staging block must have been copied out before it is written.  captured: inside a graph capture (or its launch-by-launch
+ * repeat) - the pass and the packing alone; the wait is in front of the capture, the SSIM copy behind it (not part of the captured picture: every job has its own buffer) */
+static int drain_picture(Enc *e, const Sub *s, ks265_ctx *on, int captured)
+{
+    const PixPath *p = s->p;
+    ks265_ctx *cx = on ? on : p->ctx;
+    const void *extra = e->cfg.calcPsnr ? p->dev_sse : NULL;
+    int r = quality_pass(e, on, p->frame, s->srcp, s->out, p->dev_sse, p->dev_ssim);
+    if (!r && p->dev_ssim && !captured) r = ks265_memcpy_d2h_async(cx, s->j->ssim, p->dev_ssim, 24);
+    if (!on && !captured) {
+        if (!r && e->recon_on) r = recon_home(e, s);
+        /* the records leave the frame object's buffers for a staging set (device to device, a few microseconds), so that the next picture can start
+         * while the copy-out stream drains this one */
+        if (!r && s->recycled) r = ks265_stream_wait_event(cx, e->ev_drained[s->k]);
+    }
+    if (!r) r = on ? ks265_frame_pack_compact_on(on, p->frame, e->stg[s->k], extra) : ks265_frame_pack_compact(p->frame, e->stg[s->k], extra);
+    return r;
+}
+
+/* what a graph holds: the launches of one picture on the main stream - unpack, kernels, drain */
+static int picture_launches(Enc *e, const Sub *s)
+{
+    int r = ks265_load_i420(s->p->frame, e->dev_in[s->k], s->srcp);
+    if (!r) r = code_picture(e, s);
+    if (!r) r = drain_picture(e, s, NULL, 1);
+    return r;
+}
+
+/* single-reference P and B pictures on the main stream as graphs (Enc::use_graph): replay of the captured picture, or its capture */
+static int code_picture_graph(Enc *e, Sub *s)
+{
+    const int k = s->k; PixPath *p = s->p; ks265_ctx *cx = p->ctx; ks265_frame *fr = p->frame;
+    const ks265_pic refp = e->dpb[dpb_find(e, s->l0[0])], ref1p = s->kind == 'B' ? e->dpb[dpb_find(e, s->l1[0])] : refp;
+    const uint64_t key[9] = {(uint64_t)(uintptr_t)refp.y, (uint64_t)(uintptr_t)s->out.y, (uint64_t)(uintptr_t)e->dev_in[k], (uint64_t)(uintptr_t)e->stg[k],
+                             (uint64_t)s->qp, (uint64_t)ks265_frame_p_state(fr), (uint64_t)(e->cfg.calcPsnr != 0) | (uint64_t)e->ssim_on << 1, (uint64_t)s->kind | ((uint64_t)s->lean << 8), (uint64_t)(uintptr_t)ref1p.y};
+    void *exec = NULL;
+    for (int i = 0; i < e->ngraph && !exec; ++i) if (!memcmp(e->graph[i].key, key, sizeof key)) exec = e->graph[i].exec;
+    int r = s->recycled ? ks265_stream_wait_event(cx, e->ev_drained[k]) : 0;       /* the staging block of this rotation slot has been copied out */
+    if (!r && exec) {
+        r = ks265_graph_launch(cx, exec);
+        if (!r && s->kind == 'P') r = ks265_frame_p_advance(fr);              /* a B picture leaves the P pictures' predictor chain alone */
+    } else if (!r) {
+        int keep_it = e->ngraph < MAX_GRAPHS;
+        const int state0 = ks265_frame_p_state(fr);
+        if (keep_it && ks265_capture_begin(cx)) { keep_it = 0; e->use_graph = 0; }   /* no capture on this runtime: launch by launch from here on */
+        r = picture_launches(e, s);
+        if (keep_it) {
+            void *ex = NULL;
+            const int rc = ks265_capture_end(cx, &ex);                      /* also ends a capture that failed half-way */
+            if (!r && !rc) { memcpy(e->graph[e->ngraph].key, key, sizeof key); e->graph[e->ngraph].exec = ex; ++e->ngraph; r = ks265_graph_launch(cx, ex); }
+            else if (!r) {                                                  /* recorded but not instantiated: nothing ran.  Do the picture launch by launch, graphs off */
+                e->use_graph = 0;
+                r = ks265_frame_p_restore(fr, state0);
+                if (!r) r = picture_launches(e, s);
             }
         }
-        if (!r && dssim) r = ks265_memcpy_d2h_async(cx, j->ssim, dssim, 24);  /* (not part of the captured picture: every job has its own buffer) */
-        if (!r) r = ks265_event_record(cx, e->ev_loaded[k]);                  /* the input buffer is free again (a little later than on the plain path) */
-        if (!r) r = ks265_event_record(cx, e->ev_staged[k]);
-        e->dpb_poc[slot] = poc;
-    } else {
-    if (!r) {
-        if (kind == 'I') { r = ks265_encode_picture(fr, srcp, out, 1, out); if (!r && fr == e->frame) r = ks265_frame_p_restore(fr, 0); }   /* (see on_key below) */
-        else if (kind == 'B' && (nl0 > 1 || nl1 > 1)) {
-            ks265_pic r0[4], r1[4];
-            for (int i = 0; i < nl0; ++i) r0[i] = e->dpb[dpb_find(e, l0[i])];
-            for (int i = 0; i < nl1; ++i) r1[i] = e->dpb[dpb_find(e, l1[i])];
-            r = ks265_encode_picture_b_mref(fr, srcp, r0, nl0, r1, nl1, out);
-        }
-        else if (kind == 'B') r = ks265_encode_picture_b(fr, srcp, e->dpb[dpb_find(e, l0[0])], e->dpb[dpb_find(e, l1[0])], out);
-        else if (nl0 > 1) { ks265_pic refs[4]; for (int i = 0; i < nl0; ++i) refs[i] = e->dpb[dpb_find(e, l0[i])]; r = ks265_encode_picture_mref(fr, srcp, refs, nl0, out); }
-        else r = ks265_encode_picture(fr, srcp, e->dpb[dpb_find(e, l0[0])], 0, out);
     }
-    e->dpb_poc[slot] = poc;
-    if (!r && !split) { r = quality_pass(e, NULL, fr, srcp, out, dsse, dssim); if (!r && dssim) r = ks265_memcpy_d2h_async(cx, j->ssim, dssim, 24); }
-    if (!r && e->recon_on) {
-        r = ks265_store_i420(fr, out, e->dev_recon);
-        if (!r) r = ks265_memcpy_d2h_async(cx, j->recon, e->dev_recon, fsz);
-    }
-    if (split) {
-        /* the drain runs on the copy-out stream (in order with the earlier pictures' drains: the staging block of this slot has been copied out before it is written) */
-        if (!r) r = ks265_event_record(cx, e->ev_coded[k]);
-        if (!r) r = ks265_stream_wait_event(e->ctx_out, e->ev_coded[k]);
-        if (!r) r = quality_pass(e, e->ctx_out, fr, srcp, out, dsse, dssim);
-        if (!r && dssim) r = ks265_memcpy_d2h_async(e->ctx_out, j->ssim, dssim, 24);
-        if (!r) r = ks265_frame_pack_compact_on(e->ctx_out, fr, e->stg[k], e->cfg.calcPsnr ? dsse : NULL);
-        if (!r) r = ks265_event_record(e->ctx_out, e->ev_packed[k]);
-        if (!r) r = ks265_event_record(e->ctx_out, e->ev_staged[k]);
-        if (!r) r = ks265_frame_set_records_fence(fr, e->ev_packed[k]);   /* the next picture on this frame object: its search starts now, its first record waits */
-    } else {
-    /* the records leave the frame object's buffers for a staging set (device to device, a few microseconds), so that the next picture can start
-     * while the copy-out stream drains this one */
-    if (!r && recycled) r = ks265_stream_wait_event(cx, e->ev_drained[k]);
-    if (!r) r = ks265_frame_pack_compact(fr, e->stg[k], e->cfg.calcPsnr ? dsse : NULL);
+    if (!r && p->dev_ssim) r = ks265_memcpy_d2h_async(cx, s->j->ssim, p->dev_ssim, 24);  /* (see drain_picture) */
+    if (!r) r = ks265_event_record(cx, e->ev_loaded[k]);                  /* the input buffer is free again (a little later than on the plain path) */
     if (!r) r = ks265_event_record(cx, e->ev_staged[k]);
+    e->dpb_poc[s->slot] = s->poc;
+    return r;
+}
+
+/* launch by launch: the kernels on the path's stream; the drain behind them there, or - split pipeline - on the copy-out stream */
+static int code_picture_plain(Enc *e, Sub *s)
+{
+    const int k = s->k; PixPath *p = s->p; ks265_ctx *cx = p->ctx;
+    int r = code_picture(e, s);
+    if (!r && s->kind == 'I' && s->path == PATH_MAIN) r = ks265_frame_p_restore(p->frame, 0);   /* (a key picture on the main stream: see mark_streams) */
+    e->dpb_poc[s->slot] = s->poc;
+    if (!s->split) {
+        if (!r) r = drain_picture(e, s, NULL, 0);
+        if (!r) r = ks265_event_record(cx, e->ev_staged[k]);
+        return r;
     }
-    }
-    if (on_key) {                                                      /* everything coded after it on the main stream waits for the key picture; its temporal predictors start over */
+    if (!r && e->recon_on) r = recon_home(e, s);
+    /* the drain runs on the copy-out stream (in order with the earlier pictures' drains: the staging block of this slot has been copied out before it is written) */
+    if (!r) r = ks265_event_record(cx, e->ev_coded[k]);
+    if (!r) r = ks265_stream_wait_event(e->ctx_out, e->ev_coded[k]);
+    if (!r) r = drain_picture(e, s, e->ctx_out, 0);
+    if (!r) r = ks265_event_record(e->ctx_out, e->ev_packed[k]);
+    if (!r) r = ks265_event_record(e->ctx_out, e->ev_staged[k]);
+    if (!r) r = ks265_frame_set_records_fence(p->frame, e->ev_packed[k]);   /* the next picture on this frame object: its search starts now, its first record waits */
+    return r;
+}
+
+/* the cross-stream marks behind a key picture or an anchor: who waits for it, whose temporal predictors start over */
+static int mark_streams(Enc *e, Sub *s)
+{
+    ks265_ctx *cx = s->p->ctx;
+    PixPath *anc = &e->path[PATH_ANC];
+    int r = 0;
+    if (s->path == PATH_KEY) {                                         /* everything coded after it on the main stream waits for the key picture; its temporal predictors start over */
         if (!r) r = ks265_event_record(cx, e->ev_key);
-        if (!r) r = ks265_stream_wait_event(e->ctx, e->ev_key);
-        if (!r) r = ks265_frame_p_restore(e->frame, 0);                 /* temporal predictors start over, and so does the ping-pong of the PU record buffers: the graph keys of a GOP's
+        if (!r) r = ks265_stream_wait_event(main_ctx(e), e->ev_key);
+        if (!r) r = ks265_frame_p_restore(main_frame(e), 0);            /* temporal predictors start over, and so does the ping-pong of the PU record buffers: the graph keys of a GOP's
                                                                          * pictures (which hold that state) are the same in every GOP - nothing is captured after the first one */
-        if (!r && e->anc_on) { r = ks265_stream_wait_event(e->ctx_anc, e->ev_key); if (!r) r = ks265_frame_p_restore(e->frame_anc, 0); }   /* the first anchor predicts from it */
+        if (!r && e->anc_on) { r = ks265_stream_wait_event(anc->ctx, e->ev_key); if (!r) r = ks265_frame_p_restore(anc->frame, 0); }   /* the first anchor predicts from it */
         ++e->nkeys;
     }
-    if (kind == 'I' && !on_key && e->anc_on) {                         /* a key picture on the main stream (short intra period): the anchors' stream waits for it there */
-        if (!r) r = ks265_event_record(e->ctx, e->ev_key);
-        if (!r) r = ks265_stream_wait_event(e->ctx_anc, e->ev_key);
-        if (!r) r = ks265_frame_p_restore(e->frame_anc, 0);
+    if (s->kind == 'I' && s->path == PATH_MAIN && e->anc_on) {         /* a key picture on the main stream (short intra period): the anchors' stream waits for it there */
+        if (!r) r = ks265_event_record(main_ctx(e), e->ev_key);
+        if (!r) r = ks265_stream_wait_event(anc->ctx, e->ev_key);
+        if (!r) r = ks265_frame_p_restore(anc->frame, 0);
     }
-    e->last_on_anc = on_anc;
-    if (on_anc) {                                                      /* the B pictures in front of it (and everything else the main stream codes from here on) wait for the anchor */
+    e->last_on_anc = s->path == PATH_ANC;
+    if (s->path == PATH_ANC) {                                         /* the B pictures in front of it (and everything else the main stream codes from here on) wait for the anchor */
         if (!r) r = ks265_event_record(cx, e->ev_anc);
-        if (!r) r = ks265_stream_wait_event(e->ctx, e->ev_anc);
+        if (!r) r = ks265_stream_wait_event(main_ctx(e), e->ev_anc);
         ++e->nanch;
     }
-    /* copy-out stream */
-    if (!r) r = ks265_stream_wait_event(e->ctx_out, e->ev_staged[k]);
+    return r;
+}
+
+/* copy-out stream: the staged records go home, then the picture's event */
+static int copy_out(Enc *e, const Sub *s)
+{
+    const int k = s->k;
+    int r = ks265_stream_wait_event(e->ctx_out, e->ev_staged[k]);
     /* the records go home: the fixed part + the stored lines only (~2 MB for a P picture at 2160p), by a kernel that reads the size on the device (or, KS265_COPYOUT_MB,
      * a fixed amount by hipMemcpyAsync and the rest by that kernel) */
-    if (!r) r = e->copy_mb < 0 ? ks265_copy_out_compact_async(e->ctx_out, e->frame, j->cmp, e->stg[k])
-                               : ks265_copy_out_compact_dma_async(e->ctx_out, e->frame, j->cmp, e->stg[k], kind == 'I' ? e->cmp_off[7] : (size_t)e->copy_mb << 20);
+    if (!r) r = e->copy_mb < 0 ? ks265_copy_out_compact_async(e->ctx_out, main_frame(e), s->j->cmp, e->stg[k])
+                               : ks265_copy_out_compact_dma_async(e->ctx_out, main_frame(e), s->j->cmp, e->stg[k], s->kind == 'I' ? e->cmp_off[7] : (size_t)e->copy_mb << 20);
     if (!r) r = ks265_event_record(e->ctx_out, e->ev_drained[k]);
-    if (!r) r = ks265_event_record(e->ctx_out, j->ev);
-    if (r) return hip_rc(r);
-    ++e->seq;
-    j->no_sao = lean != 0;
-    j->disp = in->disp; j->pts = in->pts; j->poc = poc; j->kind = kind; j->qp = qp; j->is_ref = is_ref; j->key_headers = key_headers; j->rc_delta = e->rc_qp_delta;
+    if (!r) r = ks265_event_record(e->ctx_out, s->j->ev);
+    return r;
+}
+
+/* what the writer needs to know about the picture */
+static void fill_job(Enc *e, const Sub *s, int key_headers)
+{
+    Job *j = s->j; const Input *in = s->in;
+    j->no_sao = s->lean != 0;
+    j->disp = in->disp; j->pts = in->pts; j->poc = s->poc; j->kind = s->kind; j->qp = s->qp; j->is_ref = s->is_ref; j->key_headers = key_headers; j->rc_delta = e->rc_qp_delta;
     j->rc_budget = (double)in->kbps * 1000.0 / (e->cfg.frameRate > 0 ? e->cfg.frameRate : 25.0);
-    j->nal_type = kind == 'I' ? KS265_NAL_IDR_W_RADL : is_ref ? KS265_NAL_TRAIL_R : KS265_NAL_TRAIL_N;
-    j->nl0 = nl0; j->nl1 = nl1;
-    for (int i = 0; i < nl0; ++i) j->l0[i] = l0[i];
-    for (int i = 0; i < nl1; ++i) j->l1[i] = l1[i];
+    j->nal_type = s->kind == 'I' ? KS265_NAL_IDR_W_RADL : s->is_ref ? KS265_NAL_TRAIL_R : KS265_NAL_TRAIL_N;
+    j->nl0 = s->nl0; j->nl1 = s->nl1;
+    for (int i = 0; i < s->nl0; ++i) j->l0[i] = s->l0[i];
+    for (int i = 0; i < s->nl1; ++i) j->l1[i] = s->l1[i];
     /* RPS: everything that must stay (keep_after) + what this picture uses */
     j->nrps = 0;
-    if (kind != 'I')
-        for (int i = 0; i < nk; ++i) {
+    if (s->kind != 'I')
+        for (int i = 0; i < s->nk; ++i) {
             int dup = 0;
-            for (int q = 0; q < j->nrps; ++q) if (j->rps_poc[q] == keep[i]) dup = 1;
-            if (dup || keep[i] == poc) continue;
+            for (int q = 0; q < j->nrps; ++q) if (j->rps_poc[q] == s->keep[i]) dup = 1;
+            if (dup || s->keep[i] == s->poc) continue;
             int used = 0;
-            for (int q = 0; q < nl0; ++q) if (l0[q] == keep[i]) used = 1;
-            for (int q = 0; q < nl1; ++q) if (l1[q] == keep[i]) used = 1;
-            j->rps_poc[j->nrps] = keep[i]; j->rps_used[j->nrps++] = (unsigned char)used;
+            for (int q = 0; q < s->nl0; ++q) if (s->l0[q] == s->keep[i]) used = 1;
+            for (int q = 0; q < s->nl1; ++q) if (s->l1[q] == s->keep[i]) used = 1;
+            j->rps_poc[j->nrps] = s->keep[i]; j->rps_used[j->nrps++] = (unsigned char)used;
         }
     j->t_submit = now_ms();
+}
+
+/* the job joins the ring: the dispatcher waits for its event, the writers take it from there */
+static void publish_job(Enc *e, const Sub *s)
+{
+    Job *j = s->j;
     pthread_mutex_lock(&e->mu);
-    in->used = 2;                                                      /* released when the job's event has fired (output time); under the lock: the caller counts the pictures in flight */
+    s->in->used = 2;                                                   /* released when the job's event has fired (output time); under the lock: the caller counts the pictures in flight */
     j->done = 0; j->error = 0; j->used = 1; j->started = 0; j->nrows = 0; j->next_row = 0; j->rows_done = 0;
     j->sub_seq = e->rc_sub;
     e->job_tail = (e->job_tail + 1) % e->ring; ++e->njobs; ++e->nwait; ++e->rc_sub;
@@ -1099,6 +1217,29 @@ static int submit(Enc *e, Input *in, int kind, int poc, int qp, const int *l0, i
     pthread_cond_signal(&e->cv_disp);
     pthread_cond_broadcast(&e->cv_sched_done);                         /* progress: a caller waiting for the scheduler (input back-pressure, flush) looks again */
     pthread_mutex_unlock(&e->mu);
+}
+
+/* enqueue one picture: GPU work + copies on the streams, then hand it to the writers */
+static int submit(Enc *e, Input *in, int kind, int poc, int qp, const int *l0, int nl0, const int *l1, int nl1, const int *keep_after, int nkeep, int is_ref, int key_headers)
+{
+    Sub s = {.in = in, .kind = kind, .poc = poc, .qp = qp, .l0 = l0, .nl0 = nl0, .l1 = l1, .nl1 = nl1, .is_ref = is_ref};
+    for (int i = 0; i < nkeep; ++i) s.keep[s.nk++] = keep_after[i];
+    for (int i = 0; i < nl0; ++i) s.keep[s.nk++] = l0[i];
+    for (int i = 0; i < nl1; ++i) s.keep[s.nk++] = l1[i];
+    if (!(s.j = wait_job_slot(e))) return QY_FAIL;
+    choose_path(e, &s);
+    int r = stage_input(e, &s);
+    if (!r) r = set_picture_tools(e, &s);
+    if (!r) r = set_rdoq_tables(e, &s);
+    if (!r) r = set_qp_map(e, &s);
+    if (!r) r = choose_recon_slot(e, &s);
+    if (!r) r = s.graphable ? code_picture_graph(e, &s) : code_picture_plain(e, &s);
+    if (!r) r = mark_streams(e, &s);
+    if (!r) r = copy_out(e, &s);
+    if (r) return hip_rc(r);
+    ++e->seq;
+    fill_job(e, &s, key_headers);
+    publish_job(e, &s);
     return QY_OK;
 }
 
@@ -1258,7 +1399,7 @@ static int schedule(Enc *e, int flush, int have /* pictures [0, have) have arriv
             }
         }
         if (e->anc_on && anchor_on_lane) {   /* every B picture that reads the anchors of this mini-GOP is on the main stream now */
-            r = hip_rc(ks265_event_record(e->ctx, e->ev_mg[(e->nanch - 1) & 7]));
+            r = hip_rc(ks265_event_record(main_ctx(e), e->ev_mg[(e->nanch - 1) & 7]));
             if (r) return r;
         }
         pthread_mutex_lock(&e->mu); e->coded_upto = a; pthread_mutex_unlock(&e->mu);
@@ -1388,11 +1529,21 @@ static int take_output(Enc *e, int max_in_flight, int max_pics, QY265Nal **pNals
 /* the reference's line behind `bitrate, psnr:` (or alone with -psnr 0), byte for byte its format (tests/golden/ssim_ref.npz): kbit/s, then the mean over the pictures of
  * every plane's mean over its windows.  hi / lo: the summed fixed-point window sums, hi x 2^30 + lo */
 static double ssim_mean(long long hi, long long lo, double windows, long frames) { return windows > 0 && frames ? ((double)hi + (double)lo / 1073741824.0) / (windows * (double)frames) : 0.0; }
-static void ssim_line(const Enc *e, long frames, long long bytes, const long long hi[3], const long long lo[3])
+/* the end-of-run summary of a lane, or of all lanes of a handle: `bitrate, psnr:` (-psnr), then the ssim line (-ssim) */
+static void run_summary(const Enc *e, long frames, long long bytes, const double sse[3], const long long hi[3], const long long lo[3])
 {
-    const double nw[3] = {(double)(e->W / 8) * (e->H / 8), (double)(e->W / 16) * (e->H / 16), (double)(e->W / 16) * (e->H / 16)};
-    logf_(2, e->log_level, "\t ssim: %.4f\t%.4f\t%.4f\t%.4f\n", bytes * 8.0 * e->cfg.frameRate / frames / 1000.0, ssim_mean(hi[0], lo[0], nw[0], frames), ssim_mean(hi[1], lo[1], nw[1], frames),
-          ssim_mean(hi[2], lo[2], nw[2], frames));
+    if (!frames) return;
+    const double kbps = bytes * 8.0 * e->cfg.frameRate / frames / 1000.0;
+    if (e->cfg.calcPsnr) {
+        const double np[3] = {(double)e->W * e->H, (double)e->W * e->H / 4, (double)e->W * e->H / 4};
+        double ps[3];
+        for (int k = 0; k < 3; ++k) ps[k] = sse[k] > 0 ? 10.0 * log10(255.0 * 255.0 * np[k] * frames / sse[k]) : 99.0;
+        logf_(2, e->log_level, "bitrate, psnr: %.4f\t%.4f\t%.4f\t%.4f\n", kbps, ps[0], ps[1], ps[2]);
+    }
+    if (e->ssim_on) {
+        const double nw[3] = {(double)(e->W / 8) * (e->H / 8), (double)(e->W / 16) * (e->H / 16), (double)(e->W / 16) * (e->H / 16)};
+        logf_(2, e->log_level, "\t ssim: %.4f\t%.4f\t%.4f\t%.4f\n", kbps, ssim_mean(hi[0], lo[0], nw[0], frames), ssim_mean(hi[1], lo[1], nw[1], frames), ssim_mean(hi[2], lo[2], nw[2], frames));
+    }
 }
 
 static void lane_close(Enc *e, int report)
@@ -1404,57 +1555,51 @@ static void lane_close(Enc *e, int report)
         for (int i = 0; i < e->nth; ++i) pthread_join(e->th[i], NULL);
         if (e->disp_on) pthread_join(e->disp, NULL);
     }
-    if (e->ctx) {
+    if (main_ctx(e)) {
         if (e->ctx_in) ks265_synchronize(e->ctx_in);
-        ks265_synchronize(e->ctx);
+        ks265_synchronize(main_ctx(e));
         if (e->ctx_out) ks265_synchronize(e->ctx_out);
         if (report && e->la_on) logf_(1, e->log_level, "ks265enc: lookahead: %ld scene cuts, %ld blocks of 8 pictures coded as 4 + 4\n", e->la_cuts, e->la_mini4);
         if (report && e->la_on && e->in_disp) logf_(1, e->log_level, "ks265enc: lookahead, caller's ms per picture: launches + queue %.3f, of it waiting for results %.3f (%ld waits); pictures handed on by the scheduler thread: %ld\n",
                                                     e->la_t_take / e->in_disp, e->la_t_wait / e->in_disp, e->la_n_wait, e->la_n_poll);
         if (report && e->in_disp) logf_(1, e->log_level, "ks265enc: caller's back-pressure wait %.3f ms per picture\n", e->la_t_bp / e->in_disp);
-        if (report && e->cfg.calcPsnr && e->st.frames) {
-            const double np[3] = {(double)e->W * e->H, (double)e->W * e->H / 4, (double)e->W * e->H / 4};
-            double ps[3];
-            for (int k = 0; k < 3; ++k) ps[k] = e->st.sse[k] > 0 ? 10.0 * log10(255.0 * 255.0 * np[k] * e->st.frames / e->st.sse[k]) : 99.0;
-            logf_(2, e->log_level, "bitrate, psnr: %.4f\t%.4f\t%.4f\t%.4f\n", e->st.bytes * 8.0 * e->cfg.frameRate / e->st.frames / 1000.0, ps[0], ps[1], ps[2]);
-        }
-        if (report && e->ssim_on && e->st.frames) ssim_line(e, e->st.frames, e->st.bytes, e->q_hi, e->q_lo);
+        if (report) run_summary(e, e->st.frames, e->st.bytes, e->st.sse, e->q_hi, e->q_lo);
         for (int i = 0; i < MAX_JOBS; ++i) {
             Job *j = &e->jobs[i];
-            ks265_host_free(e->ctx, j->cmp); ks265_host_free(e->ctx, j->recon); ks265_host_free(e->ctx, j->qp_map); ks265_host_free(e->ctx, j->ssim); ks265_host_free(e->ctx, j->rq_host); free(j->lvlbuf); free(j->dirty);
-            if (j->ev) ks265_event_destroy(e->ctx, j->ev);
+            ks265_host_free(main_ctx(e), j->cmp); ks265_host_free(main_ctx(e), j->recon); ks265_host_free(main_ctx(e), j->qp_map); ks265_host_free(main_ctx(e), j->ssim); ks265_host_free(main_ctx(e), j->rq_host); free(j->lvlbuf); free(j->dirty);
+            if (j->ev) ks265_event_destroy(main_ctx(e), j->ev);
             free(j->nal);
         }
-        for (int i = 0; i < MAX_INPUT; ++i) { ks265_host_free(e->ctx, e->in[i].i420); if (e->in[i].dev) ks265_dev_free(e->ctx, e->in[i].dev); if (e->in[i].ev_up) ks265_event_destroy(e->ctx_up, e->in[i].ev_up); }
+        for (int i = 0; i < MAX_INPUT; ++i) { ks265_host_free(main_ctx(e), e->in[i].i420); if (e->in[i].dev) ks265_dev_free(main_ctx(e), e->in[i].dev); if (e->in[i].ev_up) ks265_event_destroy(e->ctx_up, e->in[i].ev_up); }
         for (int i = 0; i < e->ndpb + 2; ++i) pic_free(e, &e->dpb[i]);
-        for (int i = 0; i < e->nspacer; ++i) ks265_dev_free(e->ctx, e->spacer[i]);
-        pic_free(e, &e->src_key); ks265_dev_free(e->ctx, e->dev_sse_key);
-        if (e->ev_key) ks265_event_destroy(e->ctx, e->ev_key);
-        for (int i = 0; i < 2; ++i) if (e->ev_firstp[i]) ks265_event_destroy(e->ctx, e->ev_firstp[i]);
-        if (e->ctx_key) ks265_synchronize(e->ctx_key);
-        if (e->frame_key) ks265_frame_destroy(e->frame_key);
-        if (e->ctx_anc) ks265_synchronize(e->ctx_anc);
-        if (e->frame_anc) ks265_frame_destroy(e->frame_anc);
-        pic_free(e, &e->src_anc); ks265_dev_free(e->ctx, e->dev_sse_anc);
-        if (e->ev_anc) ks265_event_destroy(e->ctx, e->ev_anc);
-        for (int i = 0; i < 8; ++i) if (e->ev_mg[i]) ks265_event_destroy(e->ctx, e->ev_mg[i]);
+        for (int i = 0; i < e->nspacer; ++i) ks265_dev_free(main_ctx(e), e->spacer[i]);
+        if (e->ev_key) ks265_event_destroy(main_ctx(e), e->ev_key);
+        for (int i = 0; i < 2; ++i) if (e->ev_firstp[i]) ks265_event_destroy(main_ctx(e), e->ev_firstp[i]);
+        for (int i = PATH_KEY; i < NPATH; ++i) {                         /* the paths beside the main one: their streams run dry before their frame objects go (the contexts: last, below) */
+            PixPath *p = &e->path[i];
+            if (p->ctx) ks265_synchronize(p->ctx);
+            if (p->frame) ks265_frame_destroy(p->frame);
+            pic_free(e, &p->src); ks265_dev_free(main_ctx(e), p->dev_sse);
+        }
+        if (e->ev_anc) ks265_event_destroy(main_ctx(e), e->ev_anc);
+        for (int i = 0; i < 8; ++i) if (e->ev_mg[i]) ks265_event_destroy(main_ctx(e), e->ev_mg[i]);
         for (int i = 0; i < 4; ++i) pic_free(e, &e->dpb[e->ndpb + 2 + i]);
-        pic_free(e, &e->src);
+        pic_free(e, &e->path[PATH_MAIN].src);
         for (int k = 0; k < NPIPE; ++k) {
-            ks265_dev_free(e->ctx, e->dev_in[k]); ks265_dev_free(e->ctx, e->stg[k]);
-            if (e->ev_h2d[k]) ks265_event_destroy(e->ctx, e->ev_h2d[k]);
-            if (e->ev_loaded[k]) ks265_event_destroy(e->ctx, e->ev_loaded[k]);
-            if (e->ev_staged[k]) ks265_event_destroy(e->ctx, e->ev_staged[k]);
-            if (e->ev_drained[k]) ks265_event_destroy(e->ctx, e->ev_drained[k]);
-            if (e->ev_coded[k]) ks265_event_destroy(e->ctx, e->ev_coded[k]);
-            if (e->ev_packed[k]) ks265_event_destroy(e->ctx, e->ev_packed[k]);
+            ks265_dev_free(main_ctx(e), e->dev_in[k]); ks265_dev_free(main_ctx(e), e->stg[k]);
+            if (e->ev_h2d[k]) ks265_event_destroy(main_ctx(e), e->ev_h2d[k]);
+            if (e->ev_loaded[k]) ks265_event_destroy(main_ctx(e), e->ev_loaded[k]);
+            if (e->ev_staged[k]) ks265_event_destroy(main_ctx(e), e->ev_staged[k]);
+            if (e->ev_drained[k]) ks265_event_destroy(main_ctx(e), e->ev_drained[k]);
+            if (e->ev_coded[k]) ks265_event_destroy(main_ctx(e), e->ev_coded[k]);
+            if (e->ev_packed[k]) ks265_event_destroy(main_ctx(e), e->ev_packed[k]);
             pic_free(e, &e->srcq[k]);
         }
-        for (int i = 0; i < e->ngraph; ++i) ks265_graph_destroy(e->ctx, e->graph[i].exec);
-        ks265_dev_free(e->ctx, e->dev_sse); ks265_dev_free(e->ctx, e->dev_ssim); ks265_dev_free(e->ctx, e->dev_recon);
-        for (int q = 0; q < 2; ++q) { ks265_dev_free(e->ctx, e->aq_off[q]); ks265_dev_free(e->ctx, e->aq_inv[q]); ks265_dev_free(e->ctx, e->aq_scratch[q]); }
-        for (int k = 0; k < NPIPE; ++k) ks265_dev_free(e->ctx, e->dev_qmap[k]);
-        for (int q = 0; q < 2; ++q) ks265_dev_free(e->ctx, e->dev_qmap_key[q]);
+        for (int i = 0; i < e->ngraph; ++i) ks265_graph_destroy(main_ctx(e), e->graph[i].exec);
+        ks265_dev_free(main_ctx(e), e->path[PATH_MAIN].dev_sse); ks265_dev_free(main_ctx(e), e->path[PATH_MAIN].dev_ssim); ks265_dev_free(main_ctx(e), e->dev_recon);
+        for (int q = PATH_MAIN; q <= PATH_KEY; ++q) { ks265_dev_free(main_ctx(e), e->path[q].aq_off); ks265_dev_free(main_ctx(e), e->path[q].aq_inv); ks265_dev_free(main_ctx(e), e->path[q].aq_scratch); }
+        for (int k = 0; k < NPIPE; ++k) ks265_dev_free(main_ctx(e), e->dev_qmap[k]);
+        for (int q = 0; q < 2; ++q) ks265_dev_free(main_ctx(e), e->dev_qmap_key[q]);
         if (e->recon_fd >= 0) close(e->recon_fd);
         if (e->qmap_fd >= 0) close(e->qmap_fd);
         ct_close(e);
@@ -1466,20 +1611,31 @@ static void lane_close(Enc *e, int report)
             if (e->frame_la) ks265_frame_destroy(e->frame_la);
             ks265_destroy(e->ctx_la);
         }
-        if (e->ctx_up) reg_handle(e->ctx, 0);
+        if (e->ctx_up) reg_handle(main_ctx(e), 0);
         if (e->ctx_upl) { ks265_synchronize(e->ctx_upl); ks265_destroy(e->ctx_upl); }
-        if (e->frame) ks265_frame_destroy(e->frame);
-        if (e->ctx_key) ks265_destroy(e->ctx_key);
-        if (e->ctx_anc) ks265_destroy(e->ctx_anc);
+        if (main_frame(e)) ks265_frame_destroy(main_frame(e));
+        for (int i = PATH_KEY; i < NPATH; ++i) if (e->path[i].ctx) ks265_destroy(e->path[i].ctx);
         if (e->ctx_in) ks265_destroy(e->ctx_in);
         if (e->ctx_out) ks265_destroy(e->ctx_out);
-        ks265_destroy(e->ctx);
+        ks265_destroy(main_ctx(e));
     } else { if (e->ctx_la) ks265_destroy(e->ctx_la); if (e->ctx_upl) ks265_destroy(e->ctx_upl); }                   /* created first (lane_open), before the main context failed: nothing else of the lookahead exists yet */
     for (int i = 0; i < MAX_JOBS; ++i) free(e->jobs[i].wpp);
     free(e->hdr); free(e->outbuf); free(e->md5_ring); free(e->md5_have); free(e->rq_hist);
     pthread_mutex_destroy(&e->la_mu);
     pthread_mutex_destroy(&e->mu); pthread_cond_destroy(&e->cv_work); pthread_cond_destroy(&e->cv_done); pthread_cond_destroy(&e->cv_disp); pthread_cond_destroy(&e->cv_sched); pthread_cond_destroy(&e->cv_sched_done);
     free(e);
+}
+
+/* a pixel path beside the main one (the key pictures', the anchors'): a stream of the given priority, a frame object on it, a source picture, the block of its SSE sums */
+static int path_open(Enc *e, int which, int device, int prio)
+{
+    PixPath *p = &e->path[which];
+    int r = ks265_create_prio(&p->ctx, device, prio);
+    if (!r) r = ks265_frame_create(p->ctx, &e->fcfg, &p->frame);
+    if (!r) r = pic_alloc(e, &p->src);
+    if (!r) r = ks265_dev_malloc(main_ctx(e), (void **)&p->dev_sse, 64);
+    if (e->path[PATH_MAIN].dev_ssim) p->dev_ssim = e->path[PATH_MAIN].dev_ssim + 4 * which;
+    return r;
 }
 
 static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
@@ -1561,7 +1717,7 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
      * creation order) although the caller's input time falls to 0.33 ms; without one the default GOP codes 777 (copying path 758) and IPPP 1 028 (1 025), input 0.88 / 0.26 ms */
     const int upl_order = getenv("KS265_UPL_ORDER") ? atoi(getenv("KS265_UPL_ORDER")) : 4;
     if (e->direct_in && upl_order == 0 && ks265_create(&e->ctx_upl, device)) { e->ctx_upl = NULL; e->direct_in = 0; }
-    int r = ks265_create(&e->ctx, device);
+    int r = ks265_create(&e->path[PATH_MAIN].ctx, device);
     if (r) { *err = hip_rc(r); lane_close(e, 0); return NULL; }       /* KS265_NO_DEVICE -> QY_FAIL: there is no CPU fallback */
     memset(&e->fcfg, 0, sizeof e->fcfg);
     e->fcfg.width = e->W; e->fcfg.height = e->H; e->fcfg.qp = e->base_qp; e->fcfg.lambda_q4 = kLambdaQ4[e->base_qp];
@@ -1592,10 +1748,10 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
     e->fcfg.part = cfg->part ? 1 : 0;                                   /* -part 1 (slower, veryslow, placebo): 2NxN / Nx2N prediction units in P and B pictures (ks265_frame_cfg.part) */
     e->fcfg.bi_refine = getenv("KS265_BI_REFINE") ? atoi(getenv("KS265_BI_REFINE")) : (cfg->preset >= QY265PRESET_SLOWER && cfg->preset <= QY265PRESET_PLACEBO ? 2 : 0);   /* 2 (round 5): after the CU decision, for the CUs it chose; 1 = for every PU of the quadtree.  End of round 6: up to -preset slow it is off - measured on the MI355X at 1080p and 2160p it COSTS 0.5 - 0.7 % bytes at equal PSNR-Y (it lowers the Hadamard cost of residuals the quantiser drops, and pays vector bits) and 134 us per B picture; the presets that trade speed for tools (slower .. placebo) keep it */                                              /* B pictures: joint refinement of the bi-predictive pair (motionSearchBI enc@0x484910) */
     r = ks265_frame_geometry(&e->fcfg, &e->geom);
-    if (!r) r = ks265_frame_create(e->ctx, &e->fcfg, &e->frame);
+    if (!r) r = ks265_frame_create(main_ctx(e), &e->fcfg, &e->path[PATH_MAIN].frame);
     const size_t fsz = (size_t)e->W * e->H * 3 / 2, npx = (size_t)e->W * e->H;
     const int dev_id = device;
-    if (!r) r = ks265_frame_compact_layout(e->frame, e->cmp_off);
+    if (!r) r = ks265_frame_compact_layout(main_frame(e), e->cmp_off);
     if (!r) r = ks265_create(&e->ctx_in, dev_id);
     if (!r) r = ks265_create(&e->ctx_out, dev_id);
     if (!r && e->direct_in && upl_order == 1) { if (ks265_create(&e->ctx_upl, dev_id)) { e->ctx_upl = NULL; e->direct_in = 0; } }
@@ -1603,21 +1759,21 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
     e->split = getenv("KS265_NO_SPLIT") ? 0 : 1;
     e->copy_mb = getenv("KS265_COPYOUT_MB") ? atoi(getenv("KS265_COPYOUT_MB")) : -1;
     for (int k = 0; k < NPIPE && !r; ++k) {
-        r = ks265_dev_malloc(e->ctx, (void **)&e->dev_in[k], fsz);
-        if (!r) r = ks265_dev_malloc(e->ctx, (void **)&e->stg[k], e->cmp_off[7]);
-        if (!r) r = ks265_memset_async(e->ctx, e->stg[k], 0, e->cmp_off[7]);   /* the header's running counters start at zero */
-        if (!r) r = ks265_event_create(e->ctx, &e->ev_h2d[k]);
-        if (!r) r = ks265_event_create(e->ctx, &e->ev_loaded[k]);
-        if (!r) r = ks265_event_create(e->ctx, &e->ev_staged[k]);
-        if (!r) r = ks265_event_create(e->ctx, &e->ev_drained[k]);
-        if (!r) r = ks265_event_create(e->ctx, &e->ev_coded[k]);
-        if (!r) r = ks265_event_create(e->ctx, &e->ev_packed[k]);
+        r = ks265_dev_malloc(main_ctx(e), (void **)&e->dev_in[k], fsz);
+        if (!r) r = ks265_dev_malloc(main_ctx(e), (void **)&e->stg[k], e->cmp_off[7]);
+        if (!r) r = ks265_memset_async(main_ctx(e), e->stg[k], 0, e->cmp_off[7]);   /* the header's running counters start at zero */
+        if (!r) r = ks265_event_create(main_ctx(e), &e->ev_h2d[k]);
+        if (!r) r = ks265_event_create(main_ctx(e), &e->ev_loaded[k]);
+        if (!r) r = ks265_event_create(main_ctx(e), &e->ev_staged[k]);
+        if (!r) r = ks265_event_create(main_ctx(e), &e->ev_drained[k]);
+        if (!r) r = ks265_event_create(main_ctx(e), &e->ev_coded[k]);
+        if (!r) r = ks265_event_create(main_ctx(e), &e->ev_packed[k]);
         if (!r && e->split) r = pic_alloc(e, &e->srcq[k]);
     }
-    if (!r) r = ks265_dev_malloc(e->ctx, (void **)&e->dev_sse, 64);
+    if (!r) r = ks265_dev_malloc(main_ctx(e), (void **)&e->path[PATH_MAIN].dev_sse, 64);
     e->ssim_on = cfg->calcSsim != 0 && ks265_ssim_picture && ks265_ssim_picture_on;
     if (cfg->calcSsim && !e->ssim_on) logf_(2, e->log_level, "ks265enc: SSIM is unavailable: the device library has no ks265_ssim_picture (-ssim is ignored, no ssim line)\n");
-    if (!r && e->ssim_on) r = ks265_dev_malloc(e->ctx, (void **)&e->dev_ssim, 96);
+    if (!r && e->ssim_on) r = ks265_dev_malloc(main_ctx(e), (void **)&e->path[PATH_MAIN].dev_ssim, 96);
     e->aq_on = cfg->iAqMode != 0 && cfg->fAqStrength > 0;
     /* cuTree: -rc 3 (CRF) with the reference's -cutree 1 (its default), B pictures (with -bframes 0 the reference runs no tree: TEncParam+0x388 = 0, every offset it leaves is zero)
      * and a lookahead (not -lookahead 0, not zero latency): a QP per CTU from the lookahead window */
@@ -1638,19 +1794,20 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
               e->ct_depth, e->ct_nx, e->ct_ny, 1 << e->ct_lg);
     }
     if (e->qmap_on) {
-        for (int k = 0; k < NPIPE && !r; ++k) r = ks265_dev_malloc(e->ctx, (void **)&e->dev_qmap[k], (size_t)e->geom.ctu_cols * e->geom.ctu_rows);
-        for (int q = 0; q < 2 && !r; ++q) r = ks265_dev_malloc(e->ctx, (void **)&e->dev_qmap_key[q], (size_t)e->geom.ctu_cols * e->geom.ctu_rows);
+        for (int k = 0; k < NPIPE && !r; ++k) r = ks265_dev_malloc(main_ctx(e), (void **)&e->dev_qmap[k], (size_t)e->geom.ctu_cols * e->geom.ctu_rows);
+        for (int q = 0; q < 2 && !r; ++q) r = ks265_dev_malloc(main_ctx(e), (void **)&e->dev_qmap_key[q], (size_t)e->geom.ctu_cols * e->geom.ctu_rows);
     }
     if (e->aq_on && !e->ct_on) {
         e->aq_nx = (e->W + 15) / 16; e->aq_ny = (e->H + 15) / 16;       /* blocks that hang over the picture read its padding (replicated edges) */
         const size_t nb = (size_t)e->aq_nx * e->aq_ny;
-        for (int q = 0; q < 2 && !r; ++q) {
-            r = ks265_dev_malloc(e->ctx, (void **)&e->aq_off[q], nb * 8);
-            if (!r) r = ks265_dev_malloc(e->ctx, (void **)&e->aq_inv[q], nb * 2);
-            if (!r) r = ks265_dev_malloc(e->ctx, (void **)&e->aq_scratch[q], 16);
+        for (int q = PATH_MAIN; q <= PATH_KEY && !r; ++q) {
+            r = ks265_dev_malloc(main_ctx(e), (void **)&e->path[q].aq_off, nb * 8);
+            if (!r) r = ks265_dev_malloc(main_ctx(e), (void **)&e->path[q].aq_inv, nb * 2);
+            if (!r) r = ks265_dev_malloc(main_ctx(e), (void **)&e->path[q].aq_scratch, 16);
         }
+        e->path[PATH_ANC].aq_off = e->path[PATH_MAIN].aq_off; e->path[PATH_ANC].aq_inv = e->path[PATH_MAIN].aq_inv; e->path[PATH_ANC].aq_scratch = e->path[PATH_MAIN].aq_scratch;
     }
-    if (!r) r = pic_alloc(e, &e->src);
+    if (!r) r = pic_alloc(e, &e->path[PATH_MAIN].src);
     e->ndpb = e->hier ? 10 : e->gop_b ? 4 : e->refs + 2;
     for (int i = 0; i < MAX_DPB; ++i) e->dpb_poc[i] = -1000000;
     for (int i = 0; i < e->ndpb && !r; ++i) r = pic_alloc(e, &e->dpb[i]);
@@ -1666,24 +1823,18 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
     }
     if (e->use_graph) e->split = 0;
     if (e->key_overlap) {
-        if (!r) r = ks265_create_prio(&e->ctx_key, dev_id, getenv("KS265_KEY_PRIO") ? atoi(getenv("KS265_KEY_PRIO")) : 1);   /* the key picture's wavefront must run underneath the P pictures, not behind them */
-        if (!r) r = ks265_frame_create(e->ctx_key, &e->fcfg, &e->frame_key);
-        if (!r) r = pic_alloc(e, &e->src_key);
-        if (!r) r = ks265_dev_malloc(e->ctx, (void **)&e->dev_sse_key, 64);
-        if (!r) r = ks265_event_create(e->ctx, &e->ev_key);
-        for (int i = 0; i < 2 && !r; ++i) { r = pic_alloc(e, &e->dpb[e->ndpb + i]); e->dpb_poc[e->ndpb + i] = -1000000; if (!r) r = ks265_event_create(e->ctx, &e->ev_firstp[i]); }
+        if (!r) r = path_open(e, PATH_KEY, dev_id, getenv("KS265_KEY_PRIO") ? atoi(getenv("KS265_KEY_PRIO")) : 1);   /* the key picture's wavefront must run underneath the P pictures, not behind them */
+        if (!r) r = ks265_event_create(main_ctx(e), &e->ev_key);
+        for (int i = 0; i < 2 && !r; ++i) { r = pic_alloc(e, &e->dpb[e->ndpb + i]); e->dpb_poc[e->ndpb + i] = -1000000; if (!r) r = ks265_event_create(main_ctx(e), &e->ev_firstp[i]); }
     }
     /* opt-in (KS265_ANCHOR_LANE=1): measured on the MI355X at 2160p, default GOP - 561 pictures/s without, 568 with the lane at normal stream priority, 440 at high priority
      * (and 382 before the anchor waited for its upload directly); with 8 hardware queues (GPU_MAX_HW_QUEUES) 449 without and 515 with.  The kernels of a picture fill the
      * device: an anchor running beside B pictures slows them by what it gains */
     e->anc_on = e->hier && e->refs0 == 1 && e->key_overlap && !e->qmap_on && !e->use_graph && getenv("KS265_ANCHOR_LANE") && atoi(getenv("KS265_ANCHOR_LANE")) > 0;
     if (e->anc_on) {
-        if (!r) r = ks265_create_prio(&e->ctx_anc, dev_id, getenv("KS265_ANC_PRIO") ? atoi(getenv("KS265_ANC_PRIO")) : 0);
-        if (!r) r = ks265_frame_create(e->ctx_anc, &e->fcfg, &e->frame_anc);
-        if (!r) r = pic_alloc(e, &e->src_anc);
-        if (!r) r = ks265_dev_malloc(e->ctx, (void **)&e->dev_sse_anc, 64);
-        if (!r) r = ks265_event_create(e->ctx, &e->ev_anc);
-        for (int i = 0; i < 8 && !r; ++i) r = ks265_event_create(e->ctx, &e->ev_mg[i]);
+        if (!r) r = path_open(e, PATH_ANC, dev_id, getenv("KS265_ANC_PRIO") ? atoi(getenv("KS265_ANC_PRIO")) : 0);
+        if (!r) r = ks265_event_create(main_ctx(e), &e->ev_anc);
+        for (int i = 0; i < 8 && !r; ++i) r = ks265_event_create(main_ctx(e), &e->ev_mg[i]);
         for (int i = 0; i < 4 && !r; ++i) { r = pic_alloc(e, &e->dpb[e->ndpb + 2 + i]); e->dpb_poc[e->ndpb + 2 + i] = -1000000; }
     }
     /* ring of pictures in flight: a key picture's slice takes one writer thread many picture periods, and output is in coding order - the ring must
@@ -1726,7 +1877,7 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
     const int njobs_alloc = e->ring;
     for (int i = 0; i < njobs_alloc && !r; ++i) {
         Job *j = &e->jobs[i];
-        r = ks265_host_malloc(e->ctx, (void **)&j->cmp, e->cmp_off[7]);
+        r = ks265_host_malloc(main_ctx(e), (void **)&j->cmp, e->cmp_off[7]);
         if (!r) {
             j->lvlbuf = (uint8_t *)calloc(npx * 3 + 64, 1);                 /* zero pages until a picture touches them */
             j->dirty = (uint64_t *)calloc((e->cmp_off[6] - e->cmp_off[5]) / 8 + 1, 8);
@@ -1734,10 +1885,10 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
             j->cu8 = (ks265_cu8 *)(j->cmp + e->cmp_off[0]); j->sao = (ks265_sao_param *)(j->cmp + e->cmp_off[1]); j->sse = (uint64_t *)(j->cmp + e->cmp_off[2]);
             j->lvl[0] = (int16_t *)j->lvlbuf; j->lvl[1] = (int16_t *)(j->lvlbuf + npx * 2); j->lvl[2] = (int16_t *)(j->lvlbuf + npx * 2 + npx / 2);
         }
-        if (!r && e->qmap_on) r = ks265_host_malloc(e->ctx, (void **)&j->qp_map, (size_t)e->geom.ctu_cols * e->geom.ctu_rows);
-        if (!r && e->ssim_on) r = ks265_host_malloc(e->ctx, (void **)&j->ssim, 32);
-        if (!r && e->rdoq_on) r = ks265_host_malloc(e->ctx, (void **)&j->rq_host, 1440 * sizeof(int32_t) + 104 * sizeof(int64_t));
-        if (!r) r = ks265_event_create(e->ctx, &j->ev);
+        if (!r && e->qmap_on) r = ks265_host_malloc(main_ctx(e), (void **)&j->qp_map, (size_t)e->geom.ctu_cols * e->geom.ctu_rows);
+        if (!r && e->ssim_on) r = ks265_host_malloc(main_ctx(e), (void **)&j->ssim, 32);
+        if (!r && e->rdoq_on) r = ks265_host_malloc(main_ctx(e), (void **)&j->rq_host, 1440 * sizeof(int32_t) + 104 * sizeof(int64_t));
+        if (!r) r = ks265_event_create(main_ctx(e), &j->ev);
         j->nal_cap = npx * 2 + 65536;
         j->nal = (uint8_t *)malloc(j->nal_cap);
         if (!j->nal) r = KS265_OUTOFMEMORY;
@@ -1762,7 +1913,7 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
             e->nin = e->ring + 32;
         }
     }
-    for (int i = 0; i < e->nin && !r; ++i) r = ks265_host_malloc(e->ctx, (void **)&e->in[i].i420, fsz);
+    for (int i = 0; i < e->nin && !r; ++i) r = ks265_host_malloc(main_ctx(e), (void **)&e->in[i].i420, fsz);
     /* with the lookahead every input slot has a twin on the device, uploaded on the lookahead's stream the moment the picture is handed in (nothing on that stream ever waits for
      * the pipeline: an upload enqueued on the copy-in stream, or anywhere on the copy engine behind that stream's uploads, sits behind the pipeline's back-pressure and the
      * analysis would see the picture 10 ms and more late); without it the picture is uploaded when it is scheduled, on the copy-in stream, as before.  One stream for both,
@@ -1772,9 +1923,9 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
     if (e->direct_in == 1 && !e->ctx_upl) e->direct_in = 0;
 
     if ((e->la_on && e->ctx_la) || e->direct_in) {
-        e->ctx_up = e->direct_in == 1 && e->ctx_upl ? e->ctx_upl : e->ctx_la ? e->ctx_la : e->ctx;
-        reg_handle(e->ctx, 1);
-        for (int i = 0; i < e->nin && !r; ++i) { r = ks265_dev_malloc(e->ctx, (void **)&e->in[i].dev, fsz); if (!r) r = ks265_event_create(e->ctx_up, &e->in[i].ev_up); }
+        e->ctx_up = e->direct_in == 1 && e->ctx_upl ? e->ctx_upl : e->ctx_la ? e->ctx_la : main_ctx(e);
+        reg_handle(main_ctx(e), 1);
+        for (int i = 0; i < e->nin && !r; ++i) { r = ks265_dev_malloc(main_ctx(e), (void **)&e->in[i].dev, fsz); if (!r) r = ks265_event_create(e->ctx_up, &e->in[i].ev_up); }
         logf_(2, e->log_level, "ks265enc: %d input slots with a device twin each: %.2f GB of device memory per lane (KS265_INPUT_SLOTS / KS265_PINNED_MB bound the slot count)\n", e->nin, e->nin * (double)fsz / 1073741824.0);
     }
     if (r) { *err = hip_rc(r); lane_close(e, 0); return NULL; }
@@ -2099,8 +2250,8 @@ static int lane_put(Enc *e, const QY265YUV *yuv, const ks265_dev_picture *dp, lo
         int ru = KS265_OK;
         if (whole ? reg_get(e->ctx_up, p0, ny + 2 * nc, evict) : (reg_get(e->ctx_up, p0, ny, evict) && reg_get(e->ctx_up, p1, nc, evict) && reg_get(e->ctx_up, p2, nc, evict))) {
             if (e->direct_in == 2) {                                    /* no stream: the call returns when the picture is on the device */
-                if (whole) ru = ks265_memcpy_h2d_sync(e->ctx, slot->dev, p0, ny + 2 * nc);
-                else { ru = ks265_memcpy_h2d_sync(e->ctx, slot->dev, p0, ny); if (!ru) ru = ks265_memcpy_h2d_sync(e->ctx, slot->dev + ny, p1, nc); if (!ru) ru = ks265_memcpy_h2d_sync(e->ctx, slot->dev + ny + nc, p2, nc); }
+                if (whole) ru = ks265_memcpy_h2d_sync(main_ctx(e), slot->dev, p0, ny + 2 * nc);
+                else { ru = ks265_memcpy_h2d_sync(main_ctx(e), slot->dev, p0, ny); if (!ru) ru = ks265_memcpy_h2d_sync(main_ctx(e), slot->dev + ny, p1, nc); if (!ru) ru = ks265_memcpy_h2d_sync(main_ctx(e), slot->dev + ny + nc, p2, nc); }
                 slot->up_sync = 1;
             } else {
             if (whole) ru = ks265_memcpy_h2d_async(e->ctx_up, slot->dev, p0, ny + 2 * nc);
@@ -2214,8 +2365,8 @@ static int lane_recon_on(Enc *e)                                       /* the re
     if (e->in_disp != 0) return QY_NOTSUPPORTED;
     e->key_overlap = 0;                                                /* the dump shares one device buffer: key pictures stay on the main stream */
     const size_t fsz = (size_t)e->W * e->H * 3 / 2;
-    int r = ks265_dev_malloc(e->ctx, (void **)&e->dev_recon, fsz);
-    for (int i = 0; i < e->ring && !r; ++i) r = ks265_host_malloc(e->ctx, (void **)&e->jobs[i].recon, fsz);
+    int r = ks265_dev_malloc(main_ctx(e), (void **)&e->dev_recon, fsz);
+    for (int i = 0; i < e->ring && !r; ++i) r = ks265_host_malloc(main_ctx(e), (void **)&e->jobs[i].recon, fsz);
     if (r) return hip_rc(r);
     e->recon_on = 1;
     return QY_OK;
@@ -2494,13 +2645,7 @@ void QY265EncoderClose(void *h)
         for (int i = 0; i < t->nlanes; ++i) { const ks265_enc_stats *s = &t->lane[i]->st; st.frames += s->frames; st.bytes += s->bytes; for (int k = 0; k < 3; ++k) st.sse[k] += s->sse[k]; }
         long long hi[3] = {0, 0, 0}, lo[3] = {0, 0, 0};
         for (int i = 0; i < t->nlanes; ++i) for (int k = 0; k < 3; ++k) { hi[k] += t->lane[i]->q_hi[k]; lo[k] += t->lane[i]->q_lo[k]; }
-        if (e0->cfg.calcPsnr && st.frames) {
-            const double np[3] = {(double)e0->W * e0->H, (double)e0->W * e0->H / 4, (double)e0->W * e0->H / 4};
-            double ps[3];
-            for (int k = 0; k < 3; ++k) ps[k] = st.sse[k] > 0 ? 10.0 * log10(255.0 * 255.0 * np[k] * st.frames / st.sse[k]) : 99.0;
-            logf_(2, e0->log_level, "bitrate, psnr: %.4f\t%.4f\t%.4f\t%.4f\n", st.bytes * 8.0 * e0->cfg.frameRate / st.frames / 1000.0, ps[0], ps[1], ps[2]);
-        }
-        if (e0->ssim_on && st.frames) ssim_line(e0, st.frames, st.bytes, hi, lo);
+        run_summary(e0, st.frames, st.bytes, st.sse, hi, lo);
     }
     for (int i = 0; i < t->nlanes; ++i) lane_close(t->lane[i], t->nlanes == 1);
     pthread_mutex_destroy(&t->wake.mu); pthread_cond_destroy(&t->wake.cv);
@@ -2663,11 +2808,11 @@ int ks265_enc_acquire_input(void *h, QY265YUV *yuv)
 static int lane_enable_device_input(Enc *e)
 {
     if (e->dev_in_on) return QY_OK;
-    if (!e->ctx_up) { e->ctx_up = e->ctx_la ? e->ctx_la : e->ctx; reg_handle(e->ctx, 1); }     /* (lane_close lets go of the registrations of every lane with a ctx_up) */
+    if (!e->ctx_up) { e->ctx_up = e->ctx_la ? e->ctx_la : main_ctx(e); reg_handle(main_ctx(e), 1); }     /* (lane_close lets go of the registrations of every lane with a ctx_up) */
     const size_t fsz = (size_t)e->W * e->H * 3 / 2;
     int r = KS265_OK;
     for (int i = 0; i < e->nin && !r; ++i) {
-        if (!e->in[i].dev) r = ks265_dev_malloc(e->ctx, (void **)&e->in[i].dev, fsz);
+        if (!e->in[i].dev) r = ks265_dev_malloc(main_ctx(e), (void **)&e->in[i].dev, fsz);
         if (!r && !e->in[i].ev_up) r = ks265_event_create(e->ctx_up, &e->in[i].ev_up);
     }
     if (r) return hip_rc(r);
@@ -2700,7 +2845,7 @@ int ks265_enc_encode_device_frame(void *h, QY265Nal **pNals, int *iNalCount, con
     const double t0 = now_ms();
     ks265_in_desc d;
     dev_desc(e0, pic, &d);
-    const int rv = ks265_input_validate(e0->ctx, &d);
+    const int rv = ks265_input_validate(main_ctx(e0), &d);
     e0->st.in_copy_ms += now_ms() - t0;
     if (rv) return hip_rc(rv);
     return top_encode(t, pNals, iNalCount, NULL, pic, out);

@@ -7,22 +7,50 @@
  * list of the recorded calls, replayed by ks265_graph_launch. */
 #include "ks265_hip.h"
 #include "../oracle/ks265_pipeline_oracle.h"
+#include <pthread.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
 
-struct ks265_ctx { int capturing; struct Op *ops; int nops; };
+struct ks265_ctx { int capturing; struct Op *ops; int nops; int id; };
 typedef struct Op { int kind; ks265_frame *f; const void *a; ks265_pic p0, p1, p2, p3; int i0; void *dst; } Op;
 typedef struct Graph { Op *ops; int n; } Graph;
 struct ks265_frame {
-    ks265_ctx *ctx; ks265_frame_cfg cfg; ks265_frame_geom g;
+    ks265_ctx *ctx; ks265_frame_cfg cfg; ks265_frame_geom g; int id;
     int cur_pu, have_prev;
     ks265_cu8 *cu8; ks265_sao_param *sao; uint64_t kind_hash, rq_hash;
     int me0, tools0[3];                                            /* intra_inter, bi_refine, sao as created (ks265_frame_set_picture_tools) */
     int16_t *lvl[3];                                          /* level planes, W x H and two W/2 x H/2, packed */
 };
+
+/* KS265_STUB_CALL_LOG = file: one line per call that enqueues work, records an event, waits for one or changes a frame object's state - the entry's name, the context (c), the
+ * frame object (f) and the events (e) it was given as the ordinals of their creation in this process (never addresses), a small integer argument where the entry has one, and
+ * in front of them an ordinal of the calling thread (t, in order of first appearance) - so that a host test can pin the order in which one thread issues its calls.  Not logged:
+ * allocation, creation and destruction, and ks265_event_query (a poll: how often it runs is the caller's timing) */
+static void call_log(const char *name, const ks265_ctx *c, const ks265_frame *f, const void *ev, int arg)
+{
+    static pthread_mutex_t mu = PTHREAD_MUTEX_INITIALIZER;
+    static FILE *fp; static int tried, nthreads;
+    static __thread int tid;
+    if (tried && !fp) return;
+    pthread_mutex_lock(&mu);
+    if (!tried) { const char *p = getenv("KS265_STUB_CALL_LOG"); tried = 1; if (p) fp = fopen(p, "a"); }
+    if (fp) {
+        char sc[16] = "-", sf[16] = "-", se[16] = "-";
+        if (!tid) tid = ++nthreads;
+        if (c) snprintf(sc, sizeof sc, "c%d", c->id);
+        if (f) snprintf(sf, sizeof sf, "f%d", f->id);
+        if (ev) snprintf(se, sizeof se, "e%d", ((const int *)ev)[1]);
+        fprintf(fp, "t%d %s %s %s %s %d\n", tid, name, sc, sf, se, arg);
+        fflush(fp);
+    }
+    pthread_mutex_unlock(&mu);
+}
+#define LOGC(c) call_log(__func__, c, NULL, NULL, 0)
+#define LOGE(c, ev) call_log(__func__, c, NULL, ev, 0)
+#define LOGF(c, f, arg) call_log(__func__, c, f, NULL, arg)
 
 const char *ks265_version(void) { return "ks265hip CPU stub (tests only)"; }
 const char *ks265_last_error(ks265_ctx *c) { (void)c; return "stub"; }
@@ -33,11 +61,13 @@ int ks265_create(ks265_ctx **out, int device)
     const char *nd = getenv("KS265_STUB_DEVICES");                     /* how many GPUs the stand-in "has" (default 8) */
     if (getenv("KS265_STUB_NO_DEVICE") || device < 0 || device >= (nd ? atoi(nd) : 8)) return KS265_NO_DEVICE;
     if (getenv("KS265_STUB_LOG_DEVICES")) fprintf(stderr, "stub: context on device %d\n", device);
+    static int ids;
     *out = (ks265_ctx *)calloc(1, sizeof **out);
+    if (*out) (*out)->id = __atomic_add_fetch(&ids, 1, __ATOMIC_RELAXED);
     return *out ? KS265_OK : KS265_OUTOFMEMORY;
 }
 void ks265_destroy(ks265_ctx *c) { if (c) { free(c->ops); free(c); } }
-int ks265_synchronize(ks265_ctx *c) { (void)c; return KS265_OK; }
+int ks265_synchronize(ks265_ctx *c) { LOGC(c); return KS265_OK; }
 int ks265_take_device_error(ks265_ctx *c)                              /* KS265_STUB_DEVERR_AT = k: the k-th call finds the device error word set (once), like a wavefront time-out */
 {
     static int n, at = -2;
@@ -50,17 +80,23 @@ int ks265_dev_free(ks265_ctx *c, void *p) { (void)c; free(p); return KS265_OK; }
 int ks265_host_malloc(ks265_ctx *c, void **p, size_t n) { return ks265_dev_malloc(c, p, n); }
 int ks265_host_register(ks265_ctx *c, void *p, size_t n) { (void)c; (void)p; (void)n; return getenv("KS265_STUB_NO_REGISTER") ? KS265_FAIL : KS265_OK; }   /* (every byte of the stand-in's host is "DMA-able") */
 int ks265_host_unregister(ks265_ctx *c, void *p) { (void)c; (void)p; return KS265_OK; }
-int ks265_memcpy_h2d_sync(ks265_ctx *c, void *d, const void *s, size_t n) { (void)c; memcpy(d, s, n); return KS265_OK; }
+int ks265_memcpy_h2d_sync(ks265_ctx *c, void *d, const void *s, size_t n) { LOGC(c); memcpy(d, s, n); return KS265_OK; }
 int ks265_host_free(ks265_ctx *c, void *p) { return ks265_dev_free(c, p); }
 static int stub_fast(void);
-int ks265_memcpy_h2d_async(ks265_ctx *c, void *d, const void *s, size_t n) { (void)c; if (n > (1u << 20) && stub_fast()) return KS265_OK;   /* (KS265_STUB_FAST: a picture's upload is the copy engine's time, not the caller's) */
+int ks265_memcpy_h2d_async(ks265_ctx *c, void *d, const void *s, size_t n) { LOGC(c); if (n > (1u << 20) && stub_fast()) return KS265_OK;   /* (KS265_STUB_FAST: a picture's upload is the copy engine's time, not the caller's) */
     memcpy(d, s, n); return KS265_OK; }
-int ks265_memcpy_d2d_async(ks265_ctx *c, void *d, const void *s, size_t n) { (void)c; memcpy(d, s, n); return KS265_OK; }
-int ks265_memcpy_d2h_async(ks265_ctx *c, void *d, const void *s, size_t n) { (void)c; memcpy(d, s, n); return KS265_OK; }
-int ks265_memset_async(ks265_ctx *c, void *d, int v, size_t n) { (void)c; memset(d, v, n); return KS265_OK; }
-int ks265_event_create(ks265_ctx *c, void **ev) { (void)c; *ev = malloc(4); return *ev ? KS265_OK : KS265_OUTOFMEMORY; }
-int ks265_event_record(ks265_ctx *c, void *ev) { (void)c; *(int *)ev = 0; return KS265_OK; }
-int ks265_event_wait(ks265_ctx *c, void *ev) { (void)c; (void)ev; return KS265_OK; }
+int ks265_memcpy_d2d_async(ks265_ctx *c, void *d, const void *s, size_t n) { LOGC(c); memcpy(d, s, n); return KS265_OK; }
+int ks265_memcpy_d2h_async(ks265_ctx *c, void *d, const void *s, size_t n) { LOGC(c); memcpy(d, s, n); return KS265_OK; }
+int ks265_memset_async(ks265_ctx *c, void *d, int v, size_t n) { LOGC(c); memset(d, v, n); return KS265_OK; }
+int ks265_event_create(ks265_ctx *c, void **ev)                        /* an event: the queries since its last record, the ordinal of its creation */
+{
+    static int ids;
+    (void)c; *ev = calloc(2, sizeof(int));
+    if (*ev) ((int *)*ev)[1] = __atomic_add_fetch(&ids, 1, __ATOMIC_RELAXED);
+    return *ev ? KS265_OK : KS265_OUTOFMEMORY;
+}
+int ks265_event_record(ks265_ctx *c, void *ev) { LOGE(c, ev); *(int *)ev = 0; return KS265_OK; }
+int ks265_event_wait(ks265_ctx *c, void *ev) { LOGE(c, ev); return KS265_OK; }
 /* KS265_STUB_EVENT_LAG = n: an event is reported done only at the n-th query after its record (the device stand-in runs everything at once: this is how the host's
  * "not ready yet" paths get exercised) */
 int ks265_event_query(ks265_ctx *c, void *ev, int *done)
@@ -80,7 +116,7 @@ int ks265_event_query(ks265_ctx *c, void *ev, int *done)
     ++*n;
     return KS265_OK;
 }
-int ks265_stream_wait_event(ks265_ctx *c, void *ev) { (void)c; (void)ev; return KS265_OK; }
+int ks265_stream_wait_event(ks265_ctx *c, void *ev) { LOGE(c, ev); return KS265_OK; }
 int ks265_event_destroy(ks265_ctx *c, void *ev) { (void)c; free(ev); return KS265_OK; }
 
 int ks265_frame_geometry(const ks265_frame_cfg *cfg, ks265_frame_geom *geom)
@@ -98,7 +134,8 @@ int ks265_frame_create(ks265_ctx *ctx, const ks265_frame_cfg *cfg, ks265_frame *
 {
     ks265_frame *f = (ks265_frame *)calloc(1, sizeof *f);
     if (!f) return KS265_OUTOFMEMORY;
-    f->ctx = ctx; f->cfg = *cfg;
+    static int ids;
+    f->ctx = ctx; f->cfg = *cfg; f->id = __atomic_add_fetch(&ids, 1, __ATOMIC_RELAXED);
     f->me0 = cfg->me_method; f->tools0[0] = cfg->intra_inter; f->tools0[1] = cfg->bi_refine; f->tools0[2] = cfg->sao;
     if (ks265_frame_geometry(cfg, &f->g)) { free(f); return KS265_NOTSUPPORTED; }
     f->cu8 = (ks265_cu8 *)calloc(1, (size_t)f->g.bytes_cu8); f->sao = (ks265_sao_param *)calloc(1, (size_t)f->g.bytes_sao);
@@ -108,11 +145,12 @@ int ks265_frame_create(ks265_ctx *ctx, const ks265_frame_cfg *cfg, ks265_frame *
     return KS265_OK;
 }
 void ks265_frame_destroy(ks265_frame *f) { if (f) { free(f->cu8); free(f->sao); free(f->lvl[0]); free(f->lvl[1]); free(f->lvl[2]); free(f); } }
-int ks265_frame_set_qp(ks265_frame *f, int qp, int l) { f->cfg.qp = qp; f->cfg.lambda_q4 = l; return KS265_OK; }
+int ks265_frame_set_qp(ks265_frame *f, int qp, int l) { LOGF(NULL, f, qp); f->cfg.qp = qp; f->cfg.lambda_q4 = l; return KS265_OK; }
 /* tools per picture: the stand-in's pictures do not depend on them; KS265_STUB_TOOLS_LOG = file: one line per inter picture handed in - kind, the three values - so that a
  * host test sees which pictures the host lowered them for */
 int ks265_frame_set_picture_tools(ks265_frame *f, int ii, int br, int so, int me)
 {
+    LOGF(NULL, f, (ii + 1) | (br + 1) << 2 | (so + 1) << 4 | (me + 1) << 6);
     if (me > 2) return KS265_NOTSUPPORTED;
     f->cfg.me_method = me < 0 ? f->me0 : me;
     const int v[3] = {ii, br, so};
@@ -133,9 +171,9 @@ static void tools_log(const ks265_frame *f, char kind)
     fclose(fp);
 }
 int ks265_frame_p_state(ks265_frame *f) { return (f->cur_pu & 1) | (f->have_prev ? 2 : 0); }
-int ks265_frame_p_advance(ks265_frame *f) { f->cur_pu ^= 1; f->have_prev = 1; return KS265_OK; }
-int ks265_frame_p_restore(ks265_frame *f, int s) { f->cur_pu = s & 1; f->have_prev = (s >> 1) & 1; return KS265_OK; }
-int ks265_frame_reset_prediction(ks265_frame *f) { f->have_prev = 0; return KS265_OK; }
+int ks265_frame_p_advance(ks265_frame *f) { LOGF(NULL, f, 0); f->cur_pu ^= 1; f->have_prev = 1; return KS265_OK; }
+int ks265_frame_p_restore(ks265_frame *f, int s) { LOGF(NULL, f, s); f->cur_pu = s & 1; f->have_prev = (s >> 1) & 1; return KS265_OK; }
+int ks265_frame_reset_prediction(ks265_frame *f) { LOGF(NULL, f, 0); f->have_prev = 0; return KS265_OK; }
 
 static uint64_t hash_bytes(const uint8_t *p, size_t n) { uint64_t h = 1469598103934665603ull; for (size_t i = 0; i < n; ++i) { h ^= p[i]; h *= 1099511628211ull; } return h; }
 static uint8_t *luma0(const ks265_frame *f, ks265_pic p) { return p.y + (size_t)f->g.pad_y * f->g.stride_y + f->g.pad_y; }
@@ -277,9 +315,10 @@ static int issue(ks265_ctx *c, Op o)
     c->ops = n; c->ops[c->nops++] = o;
     return KS265_OK;
 }
-int ks265_capture_begin(ks265_ctx *c) { if (getenv("KS265_STUB_NO_CAPTURE")) return KS265_FAIL; c->capturing = 1; c->nops = 0; return KS265_OK; }
+int ks265_capture_begin(ks265_ctx *c) { LOGC(c); if (getenv("KS265_STUB_NO_CAPTURE")) return KS265_FAIL; c->capturing = 1; c->nops = 0; return KS265_OK; }
 int ks265_capture_end(ks265_ctx *c, void **exec)
 {
+    LOGC(c);
     *exec = NULL;
     if (!c->capturing) return KS265_FAIL;
     c->capturing = 0;
@@ -289,16 +328,18 @@ int ks265_capture_end(ks265_ctx *c, void **exec)
     *exec = g;
     return KS265_OK;
 }
-int ks265_graph_launch(ks265_ctx *c, void *exec) { (void)c; const Graph *g = (const Graph *)exec; for (int i = 0; i < g->n; ++i) run_op(&g->ops[i]); return KS265_OK; }
+int ks265_graph_launch(ks265_ctx *c, void *exec) { LOGC(c); const Graph *g = (const Graph *)exec; for (int i = 0; i < g->n; ++i) run_op(&g->ops[i]); return KS265_OK; }
 int ks265_graph_destroy(ks265_ctx *c, void *exec) { (void)c; Graph *g = (Graph *)exec; if (g) { free(g->ops); free(g); } return KS265_OK; }
 
-int ks265_load_i420(ks265_frame *f, const uint8_t *i420, ks265_pic dst) { Op o = {OP_LOAD, f, i420, dst, dst, dst, dst, 0, NULL}; return issue(f->ctx, o); }
-int ks265_load_i420_on(ks265_ctx *c, ks265_frame *f, const uint8_t *i420, ks265_pic dst) { (void)c; return ks265_load_i420(f, i420, dst); }   /* the stand-in runs every call at once: streams do not exist */
-int ks265_frame_set_records_fence(ks265_frame *f, void *ev) { (void)f; (void)ev; return KS265_OK; }
-int ks265_frame_set_qp_map(ks265_frame *f, const int8_t *m) { (void)f; (void)m; return KS265_OK; }
+static int stub_load(ks265_frame *f, const uint8_t *i420, ks265_pic dst) { Op o = {OP_LOAD, f, i420, dst, dst, dst, dst, 0, NULL}; return issue(f->ctx, o); }
+int ks265_load_i420(ks265_frame *f, const uint8_t *i420, ks265_pic dst) { LOGF(NULL, f, 0); return stub_load(f, i420, dst); }
+int ks265_load_i420_on(ks265_ctx *c, ks265_frame *f, const uint8_t *i420, ks265_pic dst) { LOGF(c, f, 0); return stub_load(f, i420, dst); }   /* the stand-in runs every call at once: streams do not exist */
+int ks265_frame_set_records_fence(ks265_frame *f, void *ev) { call_log(__func__, NULL, f, ev, 0); return KS265_OK; }
+int ks265_frame_set_qp_map(ks265_frame *f, const int8_t *m) { LOGF(NULL, f, m != NULL); return KS265_OK; }
 /* -rdoq 1: the stand-in has no quantiser; what the tables hold shows in the "coded" picture, so that a test sees whether the tables a picture gets depend on thread timing */
 int ks265_frame_set_rdoq(ks265_frame *f, const int32_t *t, const int64_t *lam, const int64_t *lam_sdh)
 {
+    LOGF(NULL, f, t != NULL);
     f->rq_hash = 0;
     if (t && lam && lam_sdh) f->rq_hash = hash_bytes((const uint8_t *)t, 1440 * 4) ^ (hash_bytes((const uint8_t *)lam, 52 * 8) << 1) ^ (hash_bytes((const uint8_t *)lam_sdh, 52 * 8) << 2) ^ 1;
     return KS265_OK;
@@ -307,7 +348,7 @@ int ks265_frame_set_rdoq(ks265_frame *f, const int32_t *t, const int64_t *lam, c
 #include "../oracle/ks265_lookahead_ref.h"
 int ks265_frame_adapt_quant(ks265_ctx *c, const uint8_t *y, int sy, const uint8_t *u, const uint8_t *v, int sc, int nx, int ny, int count, double strength, double *off, uint16_t *inv, double *scratch)
 {
-    (void)c; (void)scratch;
+    LOGC(c); (void)scratch;
     uint8_t *Y = malloc((size_t)nx * ny * 256), *U = malloc((size_t)nx * ny * 64), *V = malloc((size_t)nx * ny * 64);
     for (int r = 0; r < ny * 16; ++r) memcpy(Y + (size_t)r * nx * 16, y + (long)r * sy, (size_t)nx * 16);
     for (int r = 0; r < ny * 8; ++r) { memcpy(U + (size_t)r * nx * 8, u + (long)r * sc, (size_t)nx * 8); memcpy(V + (size_t)r * nx * 8, v + (long)r * sc, (size_t)nx * 8); }
@@ -315,14 +356,14 @@ int ks265_frame_adapt_quant(ks265_ctx *c, const uint8_t *y, int sy, const uint8_
     free(Y); free(U); free(V);
     return KS265_OK;
 }
-int ks265_aq_ctu_map(ks265_ctx *c, const double *off, int nx, int ny, int base, int lo, int hi, int8_t *map) { (void)c; kso_aq_ctu_map(off, nx, ny, base, lo, hi, map); return KS265_OK; }
+int ks265_aq_ctu_map(ks265_ctx *c, const double *off, int nx, int ny, int base, int lo, int hi, int8_t *map) { call_log(__func__, c, NULL, NULL, base); kso_aq_ctu_map(off, nx, ny, base, lo, hi, map); return KS265_OK; }
 /* cuTree (-rc 3): the oracle's restatements of calcFrameCost, cuTreePropagate and the finish ARE the stand-in's "device" operators, so the host's pass over the lookahead window can
  * be held against the Python mirror of that pass picture for picture (tests/test_host_pipeline_cpu.py) */
 size_t ks265_calc_frame_cost_workspace(int nx, int ny) { (void)nx; (void)ny; return 64; }
 int ks265_calc_frame_cost(ks265_ctx *c, const ks265_cfc_params *q, const uint8_t *cur, const uint8_t *ref0, const uint8_t *ref1, uint16_t *intra, uint8_t *imode, const uint16_t *invq,
                           uint16_t *inter, uint8_t *bits, int32_t *mv0, int32_t *c0, int32_t *mv1, int32_t *c1, ks265_cfc_sums *s, void *ws)
 {
-    (void)c; (void)ws;
+    LOGC(c); (void)ws;
     kso_cfc k; memset(&k, 0, sizeof k);
     k.cur = cur; k.ref0 = ref0; k.ref1 = ref1; k.stride = q->stride; k.w = q->w; k.h = q->h; k.nx = q->nx; k.ny = q->ny; k.cnt = q->cnt;
     k.d0 = q->d0; k.d1 = q->d1; k.flag = q->flag; k.slice_type = q->slice_type;
@@ -341,24 +382,25 @@ int ks265_calc_frame_cost(ks265_ctx *c, const ks265_cfc_params *q, const uint8_t
 int ks265_cutree_propagate(ks265_ctx *c, int lg, int nx, int ny, const uint16_t *intra, const uint16_t *invq, const uint16_t *own, const uint16_t *inter, const uint8_t *bits, const int32_t *mv0,
                            const int32_t *mv1, uint16_t *ref0, uint16_t *ref1, uint64_t *acc)
 {
-    (void)c; (void)acc;
+    LOGC(c); (void)acc;
     kso_ref_cutree_propagate(lg, nx, ny, intra, invq, own, inter, bits, mv0, mv1, ref0, ref1);
     return KS265_OK;
 }
-int ks265_cutree_finish(ks265_ctx *c, int cnt, const uint16_t *intra, const uint16_t *invq, const uint16_t *prop, const double *aq, int dbl, double *out) { (void)c; kso_ref_cutree_finish(cnt, intra, invq, prop, aq, dbl, out);
+int ks265_cutree_finish(ks265_ctx *c, int cnt, const uint16_t *intra, const uint16_t *invq, const uint16_t *prop, const double *aq, int dbl, double *out) { LOGC(c); kso_ref_cutree_finish(cnt, intra, invq, prop, aq, dbl, out);
     return KS265_OK; }
 int ks265_pad_plane(ks265_ctx *c, uint8_t *p, int stride, int w, int h, int pad)
 {
-    (void)c;
+    LOGC(c);
     for (int y = -pad; y < h + pad; ++y)
         for (int x = -pad; x < w + pad; ++x)
             if (x < 0 || x >= w || y < 0 || y >= h) p[(long)y * stride + x] = p[(long)(y < 0 ? 0 : y >= h ? h - 1 : y) * stride + (x < 0 ? 0 : x >= w ? w - 1 : x)];
     return KS265_OK;
 }
-int ks265_fill_u16(ks265_ctx *c, uint16_t *d, int n, int v) { (void)c; for (int i = 0; i < n; ++i) d[i] = (uint16_t)v; return KS265_OK; }
-int ks265_qoff_ctu_map(ks265_ctx *c, const double *off, int nx, int ny, int lg, int cols, int rows, int base, int lo, int hi, int8_t *map) { (void)c; kso_qoff_ctu_map(off, nx, ny, lg, cols, rows, base, lo, hi, map); return KS265_OK; }
+int ks265_fill_u16(ks265_ctx *c, uint16_t *d, int n, int v) { LOGC(c); for (int i = 0; i < n; ++i) d[i] = (uint16_t)v; return KS265_OK; }
+int ks265_qoff_ctu_map(ks265_ctx *c, const double *off, int nx, int ny, int lg, int cols, int rows, int base, int lo, int hi, int8_t *map) { call_log(__func__, c, NULL, NULL, base); kso_qoff_ctu_map(off, nx, ny, lg, cols, rows, base, lo, hi, map); return KS265_OK; }
 int ks265_store_i420(ks265_frame *f, ks265_pic src, uint8_t *i420)
 {
+    LOGF(NULL, f, 0);
     const int W = f->cfg.width, H = f->cfg.height;
     for (int y = 0; y < H; ++y) memcpy(i420 + (size_t)y * W, luma0(f, src) + (size_t)y * f->g.stride_y, (size_t)W);
     memset(i420 + (size_t)W * H, 128, (size_t)W * H / 2);
@@ -370,7 +412,7 @@ static int fail_now(void)                                      /* KS265_STUB_FAI
     if (at == -2) { const char *e = getenv("KS265_STUB_FAIL_AT"); at = e ? atoi(e) : -1; }
     return at >= 0 && __atomic_fetch_add(&n, 1, __ATOMIC_RELAXED) == at;
 }
-int ks265_encode_picture(ks265_frame *f, ks265_pic src, ks265_pic ref, int is_key, ks265_pic out)
+static int stub_encode(ks265_frame *f, ks265_pic src, ks265_pic ref, int is_key, ks265_pic out)
 {
     if (fail_now()) return KS265_FAIL;
     tools_log(f, is_key ? 'I' : 'P');
@@ -379,7 +421,8 @@ int ks265_encode_picture(ks265_frame *f, ks265_pic src, ks265_pic ref, int is_ke
     if (!is_key) { f->cur_pu ^= 1; f->have_prev = 1; } else f->have_prev = 0;
     return r;
 }
-int ks265_encode_picture_b(ks265_frame *f, ks265_pic src, ks265_pic r0, ks265_pic r1, ks265_pic out)
+int ks265_encode_picture(ks265_frame *f, ks265_pic src, ks265_pic ref, int is_key, ks265_pic out) { LOGF(NULL, f, is_key); return stub_encode(f, src, ref, is_key, out); }
+static int stub_encode_b(ks265_frame *f, ks265_pic src, ks265_pic r0, ks265_pic r1, ks265_pic out)
 {
     /* (the P chain's state goes into the record so that a replayed graph with the wrong state shows; KS265_STUB_B_STATELESS leaves it out - the real B pictures do not depend
      * on it, and the host's anchor lane moves the P chain to another frame object) */
@@ -387,16 +430,26 @@ int ks265_encode_picture_b(ks265_frame *f, ks265_pic src, ks265_pic r0, ks265_pi
     Op o = {OP_ENC, f, NULL, src, r0, r1, out, 2 | (getenv("KS265_STUB_B_STATELESS") ? 0 : ks265_frame_p_state(f) << 2), NULL};
     return issue(f->ctx, o);
 }
-int ks265_encode_picture_mref(ks265_frame *f, ks265_pic src, const ks265_pic *refs, int nref, ks265_pic out) { return ks265_encode_picture(f, src, refs[nref - 1], 0, out); }
-int ks265_encode_picture_b_mref(ks265_frame *f, ks265_pic src, const ks265_pic *refs0, int n0, const ks265_pic *refs1, int n1, ks265_pic out) { (void)n0; (void)n1; return ks265_encode_picture_b(f, src, refs0[0], refs1[0], out); }
-int ks265_sse_picture(ks265_frame *f, ks265_pic a, ks265_pic b, uint64_t *sse3) { Op o = {OP_SSE, f, NULL, a, b, b, b, 0, sse3}; return issue(f->ctx, o); }
-int ks265_frame_pack_compact(ks265_frame *f, void *dst, const void *extra) { Op o = {OP_PACK, f, extra, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, 0, dst}; return issue(f->ctx, o); }
-int ks265_copy_out_compact_dma_async(ks265_ctx *c, ks265_frame *f, void *host, const void *dev, size_t n) { (void)n; return ks265_copy_out_compact_async(c, f, host, dev); }
-int ks265_sse_picture_on(ks265_ctx *c, ks265_frame *f, ks265_pic a, ks265_pic b, uint64_t *sse3) { (void)c; return ks265_sse_picture(f, a, b, sse3); }
-int ks265_frame_pack_compact_on(ks265_ctx *c, ks265_frame *f, void *dst, const void *extra) { (void)c; return ks265_frame_pack_compact(f, dst, extra); }
-int ks265_copy_out_compact_async(ks265_ctx *c, ks265_frame *f, void *host, const void *dev)
+int ks265_encode_picture_b(ks265_frame *f, ks265_pic src, ks265_pic r0, ks265_pic r1, ks265_pic out) { LOGF(NULL, f, 0); return stub_encode_b(f, src, r0, r1, out); }
+int ks265_encode_picture_mref(ks265_frame *f, ks265_pic src, const ks265_pic *refs, int nref, ks265_pic out) { LOGF(NULL, f, nref); return stub_encode(f, src, refs[nref - 1], 0, out); }
+int ks265_encode_picture_b_mref(ks265_frame *f, ks265_pic src, const ks265_pic *refs0, int n0, const ks265_pic *refs1, int n1, ks265_pic out) { LOGF(NULL, f, n0 | n1 << 4); return stub_encode_b(f, src, refs0[0], refs1[0], out); }
+static int stub_sse(ks265_frame *f, ks265_pic a, ks265_pic b, uint64_t *sse3) { Op o = {OP_SSE, f, NULL, a, b, b, b, 0, sse3}; return issue(f->ctx, o); }
+static int stub_pack(ks265_frame *f, void *dst, const void *extra) { Op o = {OP_PACK, f, extra, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, 0, dst}; return issue(f->ctx, o); }
+static int stub_copy_out(ks265_frame *f, void *host, const void *dev);
+int ks265_sse_picture(ks265_frame *f, ks265_pic a, ks265_pic b, uint64_t *sse3) { LOGF(NULL, f, 0); return stub_sse(f, a, b, sse3); }
+int ks265_frame_pack_compact(ks265_frame *f, void *dst, const void *extra) { LOGF(NULL, f, extra != NULL); return stub_pack(f, dst, extra); }
+int ks265_copy_out_compact_dma_async(ks265_ctx *c, ks265_frame *f, void *host, const void *dev, size_t n) { (void)n; LOGF(c, f, 0); return stub_copy_out(f, host, dev); }
+int ks265_sse_picture_on(ks265_ctx *c, ks265_frame *f, ks265_pic a, ks265_pic b, uint64_t *sse3) { LOGF(c, f, 0); return stub_sse(f, a, b, sse3); }
+int ks265_frame_pack_compact_on(ks265_ctx *c, ks265_frame *f, void *dst, const void *extra) { LOGF(c, f, extra != NULL); return stub_pack(f, dst, extra); }
+int ks265_copy_out_compact_async(ks265_ctx *c, ks265_frame *f, void *host, const void *dev) { LOGF(c, f, 0); return stub_copy_out(f, host, dev); }
+#ifdef KS265_STUB_SSIM
+/* -DKS265_STUB_SSIM (tests/test_submit_order_cpu.py alone): the fused SSIM + SSE pass as two more entries, so that the host's -ssim path shows in the call log - the SSE sums of
+ * the SSE pass, the SSIM sums zero.  The stand-in every other test builds has neither entry (tests/test_ssim_host_cpu.py) */
+int ks265_ssim_picture(ks265_frame *f, ks265_pic a, ks265_pic b, uint64_t *sse3, int64_t *ssim3) { LOGF(NULL, f, sse3 != NULL); (void)ssim3; return sse3 ? stub_sse(f, a, b, sse3) : KS265_OK; }
+int ks265_ssim_picture_on(ks265_ctx *c, ks265_frame *f, ks265_pic a, ks265_pic b, uint64_t *sse3, int64_t *ssim3) { LOGF(c, f, sse3 != NULL); (void)ssim3; return sse3 ? stub_sse(f, a, b, sse3) : KS265_OK; }
+#endif
+static int stub_copy_out(ks265_frame *f, void *host, const void *dev)
 {
-    (void)c;
     size_t off[8];
     ks265_frame_compact_layout(f, off);
     memcpy(host, dev, off[6] + (size_t)((const uint32_t *)((const uint8_t *)dev + off[3]))[2] * 64);     /* the fixed part + the stored lines */
@@ -410,15 +463,15 @@ void ks265o_downsample(uint8_t *dst, const uint8_t *src, int dstStride, int srcS
 int ks265_downsample_from_host(ks265_ctx *c, const uint8_t *src, int ss, uint8_t *dst, int ds, int w, int h) { return ks265_downsample_rect(c, src, ss, dst, ds, w, h); }
 int ks265_downsample_rect(ks265_ctx *c, const uint8_t *src, int ss, uint8_t *dst, int ds, int w, int h)
 {
-    (void)c;
+    LOGC(c);
     if (stub_fast()) return KS265_OK;                           /* (a real device takes these launches asynchronously: nothing of them is the calling thread's time) */
     ks265o_downsample(dst, src, ds, ss, w, h);                  /* downsample_c enc@0x4a6a60, as the device operator */
     return KS265_OK;
 }
-int ks265_pad_picture(ks265_frame *f, ks265_pic pic) { (void)f; (void)pic; return KS265_OK; }
+int ks265_pad_picture(ks265_frame *f, ks265_pic pic) { LOGF(NULL, f, 0); (void)pic; return KS265_OK; }
 int ks265_lookahead_picture(ks265_frame *f, ks265_pic cur, ks265_pic ref, uint32_t *ws, uint64_t *out)
 {
-    (void)ws;
+    LOGF(NULL, f, 0); (void)ws;
     if (stub_fast()) { out[0] = 1000; out[1] = 100; out[2] = 100; out[3] = (uint64_t)f->cfg.width * f->cfg.height / 64; return KS265_OK; }
     const long org = (long)f->g.pad_y * f->g.stride_y + f->g.pad_y;
     uint64_t intra = 0, inter = 0;
