@@ -93,6 +93,8 @@ int ks265_wpp_begin(const ks265_stream_cfg *cfg, const ks265_slice_in *in, void 
 int ks265_wpp_rows(const void *mem);
 int ks265_wpp_code_row(void *mem, int row);
 long ks265_wpp_finish(void *mem, uint8_t *out, size_t cap);
+/* after all rows: a capacity with which ks265_wpp_finish cannot run short for this picture (header, the coded rows, emulation prevention at its worst) */
+size_t ks265_wpp_nal_bound(const void *mem);
 
 #ifdef __cplusplus
 }

@@ -605,7 +605,13 @@ static void *worker(void *arg)
             if (++j->rows_done == j->nrows) {                    /* the thread that finishes the last row assembles the NAL unit */
                 pthread_mutex_unlock(&e->mu);
                 const double t1 = now_ms();
-                const long n = ks265_wpp_finish(j->wpp, j->nal, j->nal_cap);
+                const size_t need = ks265_wpp_nal_bound(j->wpp);          /* an incompressible picture at a low QP costs more than two bytes per sample: the buffer follows the writer's own bound */
+                int oom = 0;
+                if (need > j->nal_cap) {
+                    uint8_t *nb = (uint8_t *)realloc(j->nal, need);
+                    if (nb) { j->nal = nb; j->nal_cap = need; } else oom = 1;
+                }
+                const long n = oom ? (long)KS265_OUTOFMEMORY : ks265_wpp_finish(j->wpp, j->nal, j->nal_cap);
                 j->fctx_ok = e->rdoq_on && n >= 0 && ks265_slice_final_contexts(&e->scfg, j->wpp, j->fctx, (int)sizeof j->fctx, NULL) > 0;
                 memcpy(j->dirty, j->cmp + e->cmp_off[5], e->cmp_off[6] - e->cmp_off[5]);      /* what the next picture in this slot has to clear */
                 pthread_mutex_lock(&e->mu);

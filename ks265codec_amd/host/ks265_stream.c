@@ -1249,6 +1249,17 @@ static long count_ep(const uint8_t *p, long n)
     }
     return cnt;
 }
+/* what ks265_wpp_finish asks of `cap` at most: per segment (the slice header's 2048 bytes, then every coded row) its bytes, half as many again for emulation
+ * prevention (one byte per two at worst) and the 8 bytes of slack its check keeps, after the 6 bytes of start code and NAL header */
+#define WPP_HDR_CAP 2048
+size_t ks265_wpp_nal_bound(const void *mem)
+{
+    const Wpp *w = (const Wpp *)mem;
+    if (!w) return 0;
+    size_t need = 6 + WPP_HDR_CAP + WPP_HDR_CAP / 2 + 8;
+    for (int i = 0; i < w->rows; ++i) need += (size_t)w->row_len[i] + (size_t)w->row_len[i] / 2 + 8;
+    return need;
+}
 /* after every row has been coded: slice header with the entry points, then the substreams; returns the NAL size */
 long ks265_wpp_finish(void *mem, uint8_t *out, size_t cap)
 {
@@ -1258,7 +1269,7 @@ long ks265_wpp_finish(void *mem, uint8_t *out, size_t cap)
     long entry[256];
     if (w->rows > 256) return KS265_NOTSUPPORTED;
     for (int i = 0; i + 1 < w->rows; ++i) entry[i] = w->row_len[i] + count_ep(w->rowbuf + (size_t)i * w->row_cap, w->row_len[i]);
-    uint8_t hdr[2048];
+    uint8_t hdr[WPP_HDR_CAP];
     BitW b; bw_init(&b, hdr, sizeof hdr);
     const int r = write_slice_header(&b, w->cfg, w->in, w->rows - 1, entry);
     if (r) return r;

@@ -67,6 +67,55 @@ CASES = {
 }
 
 
+# Adversarial content (tests/adversarial_clips.py) through the tool sets of four cases above, at the smallest sizes that keep their structure: every family, every QP
+# in {0, 22, 51} and every tool set at least twice.  Kept beside CASES (whose tuples, clips and MD5s stay as they are): names `adv_<family>_<toolset>_qp<q>`, fixture
+# tests/golden/stream_adversarial_md5.json.
+ADV_TOOLSETS = {
+    # short name: (the case whose tool set (its name's prefixes and suffixes select the tools), GOP and search method are used, W, H)
+    "enc": ("enc_hierb4_416x240_skip_bir2", 136, 72),
+    "rqt": ("rqt_part_hiermr4_200x136_skip_bir2", 136, 72),
+    "wpp": ("wpp_ippp_56x200_qp12", 72, 136),              # one CTU per row and a ragged last row
+    "ippp": ("ippp_64x64_nosao_qp5", 64, 64),
+    # beyond the four tool sets the adversarial work was specified with: the only GOP kind whose P pictures search several list-0 pictures (ks265_encode_picture_mref: ref_decide,
+    # the merge and skip passes on the records' pictures), which the other four never reach - two cases, three mini-GOPs (13 pictures of 136x72: the third anchor is the first
+    # with three reference pictures), so shorter GOPs would not exercise it
+    "hiera": ("enc_hiera3_200x136_qp34_skip_bir2", 136, 72),
+}
+_ADV = [
+    ("flat_flip", "enc", 0), ("flat_flip", "rqt", 22), ("flat_flip", "wpp", 51), ("flat_flip", "ippp", 0),
+    ("cb1_flip", "rqt", 0), ("cb1_flip", "wpp", 22), ("cb1_flip", "ippp", 51), ("cb1_flip", "enc", 51),
+    ("cb8_shift", "wpp", 0), ("cb8_shift", "ippp", 22), ("cb8_shift", "enc", 51), ("cb8_shift", "rqt", 22),
+    ("noise", "ippp", 0), ("noise", "enc", 22), ("noise", "rqt", 51), ("noise", "wpp", 0),
+    ("bnoise_pan", "enc", 0), ("bnoise_pan", "rqt", 22), ("bnoise_pan", "wpp", 51), ("bnoise_pan", "ippp", 22),
+    ("edge_ramp", "rqt", 0), ("edge_ramp", "wpp", 22), ("edge_ramp", "ippp", 51), ("edge_ramp", "enc", 22),
+    ("noise", "rqt", 0), ("bnoise_pan", "rqt", 51), ("bnoise_pan", "hiera", 22), ("cb8_shift", "hiera", 0),
+]
+ADV_CASES, ADV_CONTENT = {}, {}
+for _fam, _ts, _q in _ADV:
+    _base, _w, _h = ADV_TOOLSETS[_ts]
+    ADV_CASES[f"adv_{_fam}_{_ts}_qp{_q}"] = (_w, _h, _q) + CASES[_base][3:]
+    ADV_CONTENT[f"adv_{_fam}_{_ts}_qp{_q}"] = (_fam, _base)
+
+
+def case_params(name: str) -> tuple:
+    return ADV_CASES[name] if name in ADV_CASES else CASES[name]
+
+
+def case_tools(name: str) -> str:
+    """the name the case_*() selectors below are asked with: an adversarial case runs the tool set of the case it is derived from"""
+    return ADV_CONTENT[name][1] if name in ADV_CONTENT else name
+
+
+def case_clip(name: str, n: int) -> np.ndarray:
+    """the case's content: synth.make_clip, or the adversarial family of ADV_CONTENT"""
+    W, H = case_params(name)[:2]
+    if name in ADV_CONTENT:
+        from adversarial_clips import make_adversarial
+        return make_adversarial(ADV_CONTENT[name][0], W, H, n, seed=len(name) * 7 + W)
+    from ks265codec_amd.synth import make_clip
+    return make_clip(W, H, n, seed=len(name) * 7 + W, abc=(17, 23, 9))
+
+
 def case_part(name: str) -> int:
     return 1 if name.startswith("part_") or name.startswith("rqt_part_") else 0
 
@@ -205,11 +254,12 @@ def make_stream(name: str, encode):
     """encode(display index, kind, l0 display indices, l1 display indices, qp) -> (cu8, [lvl_y, lvl_u, lvl_v], sao records or None, recon I420);
     returns (stream bytes, {display index: recon I420})"""
     from ks265codec_amd import stream as S
-    W, H, qp, me, thr, sao, df, kind, par = CASES[name]
+    W, H, qp, me, thr, sao, df, kind, par = case_params(name)
+    tn = case_tools(name)
     sched = schedule(kind, par)
     nref = max([len(s[2]) + len(s[3]) for s in sched] + [1])
     reorder = par if kind in ("hier", "hiermr", "hiera") else 0
-    w = S.StreamWriter(W, H, sao=sao, deblock=df, max_dec_pic_buffering=(par + 4) if kind in ("hiermr", "hiera") else (par + 2) if kind == "hier" else nref + 1, max_num_reorder=reorder, sdh=case_sdh(name), wpp=case_wpp(name), tu_inter=case_rqt(name))      # the C host's rule (ks265_enc.c)
+    w = S.StreamWriter(W, H, sao=sao, deblock=df, max_dec_pic_buffering=(par + 4) if kind in ("hiermr", "hiera") else (par + 2) if kind == "hier" else nref + 1, max_num_reorder=reorder, sdh=case_sdh(tn), wpp=case_wpp(tn), tu_inter=case_rqt(tn))      # the C host's rule (ks265_enc.c)
     bs = w.headers()
     recs = {}
     for d, k, l0, l1, dq, rps, isref in sched:
@@ -225,16 +275,17 @@ def make_stream(name: str, encode):
 
 def oracle_encoder(name: str):
     """the CPU oracle pipeline as the per-picture encoder of make_stream"""
-    from ks265codec_amd.synth import lambda_q4, make_clip
+    from ks265codec_amd.synth import lambda_q4
     from oracle_lib import OraclePipeline
-    W, H, qp, me, thr, sao, df, kind, par = CASES[name]
+    W, H, qp, me, thr, sao, df, kind, par = case_params(name)
     n = 1 + max(s[0] for s in schedule(kind, par))
-    clip = make_clip(W, H, n, seed=len(name) * 7 + W, abc=(17, 23, 9))
-    o = OraclePipeline(W, H, qp, lambda_q4(qp), me_method=me, me_hex_thr=thr, sao=sao, deblock=df, sdh=case_sdh(name), pre_search=case_ps(name), merge=case_merge(name), bi_refine=case_bir(name), decimate=case_dec(name), rdo=case_rdo(name), intra_inter=case_ii(name), propagate=case_prop(name), part=case_part(name), tu_inter=case_rqt(name), skip_rd=case_skip(name), **case_subme(name))
+    clip = case_clip(name, n)
+    tn = case_tools(name)
+    o = OraclePipeline(W, H, qp, lambda_q4(qp), me_method=me, me_hex_thr=thr, sao=sao, deblock=df, sdh=case_sdh(tn), pre_search=case_ps(tn), merge=case_merge(tn), bi_refine=case_bir(tn), decimate=case_dec(tn), rdo=case_rdo(tn), intra_inter=case_ii(tn), propagate=case_prop(tn), part=case_part(tn), tu_inter=case_rqt(tn), skip_rd=case_skip(tn), **case_subme(tn))
     dpb = {}
 
     def encode(d, k, l0, l1, q):
-        o.set_qp(q, case_lambda(name, q, k))
+        o.set_qp(q, case_lambda(tn, q, k))
         if k == "P" and len(l0) > 1:
             dpb[d] = o.encode_mref(clip[d], [dpb[r] for r in l0])
         elif k == "B" and (len(l0) > 1 or len(l1) > 1):

@@ -157,6 +157,84 @@ def test_rgb_formats_exact(hip, W, H):
                     assert (got == exp).all(), (name, matrix, full, off, pad, int((got != exp).sum()))
 
 
+# small and ragged shapes: 8x2 (one thread), 24x6 and 200x134 (widths that are no multiple of 16: the 8-column kernel; H / 2 no multiple of the block's 4 rows), 1032x18 (129
+# threads per row: a third block of which one thread works)
+SMALL = [(8, 2), (24, 6), (200, 134), (1032, 18)]
+SLACK = 256
+
+
+def _convert_guarded(hip, desc: InDesc, W, H):
+    """_convert into a destination SLACK bytes larger than the picture: the 0xA5 canary beyond W * H * 3 / 2 must be intact"""
+    lib, h = hip
+    n = W * H * 3 // 2
+    dst = torch.full((n + SLACK,), 0xA5, dtype=torch.uint8, device="cuda")
+    assert lib.ks265_wait_external(h, C.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
+    rc = lib.ks265_input_convert(h, C.byref(desc), C.c_void_p(dst.data_ptr()))
+    assert rc == 0, (rc, lib.ks265_last_error(h))
+    assert lib.ks265_synchronize(h) == 0
+    out = dst.cpu().numpy()
+    assert (out[n:] == 0xA5).all(), f"{int((out[n:] != 0xA5).sum())} bytes written beyond the picture"
+    return out[:n]
+
+
+@pytest.mark.parametrize("W,H", SMALL)
+def test_yuv_formats_exact_at_small_and_ragged_shapes(hip, W, H):
+    from adversarial_clips import FAMILIES, make_adversarial
+    for kind in FAMILIES:
+        fr = make_adversarial(kind, W, H, 2, seed=W)[1]
+        for off, pad in LAYOUTS:
+            y = fr[:W * H].reshape(H, W); u = fr[W * H:W * H * 5 // 4].reshape(H // 2, W // 2); v = fr[W * H * 5 // 4:].reshape(H // 2, W // 2)
+            d = InDesc(); d.format, d.width, d.height = 0, W, H
+            buf, addr = _place([y, u, v], [W + pad, W // 2 + pad + 5, W // 2 + pad + 3], off)
+            for k in range(3):
+                d.plane[k] = addr[k]
+            d.pitch[0], d.pitch[1], d.pitch[2] = W + pad, W // 2 + pad + 5, W // 2 + pad + 3
+            assert (_convert_guarded(hip, d, W, H) == fr).all(), (kind, "i420", off, pad)
+            nv = _nv12(fr, W, H)
+            d = InDesc(); d.format, d.width, d.height = 1, W, H
+            buf, addr = _place([nv[:H], nv[H:]], [W + pad, W + pad + 7], off)
+            d.plane[0], d.plane[1] = addr
+            d.pitch[0], d.pitch[1] = W + pad, W + pad + 7
+            assert (_convert_guarded(hip, d, W, H) == fr).all(), (kind, "nv12", off, pad)
+
+
+def _rgb_inputs(W, H):
+    """(name, R, G, B): the eight corners of the RGB cube in columns (saturated primaries, black, white) with rows alternating between a corner and its complement; the
+    adversarial families' luma planes as the three channels"""
+    from adversarial_clips import make_adversarial
+    lum = lambda kind, t=0: np.ascontiguousarray(make_adversarial(kind, W, H, 2, seed=H)[t][:W * H].reshape(H, W))
+    yy, xx = np.mgrid[0:H, 0:W]
+    corner = (xx + (yy & 1) * 7) & 7
+    cube = [((corner >> b & 1) * 255).astype(np.uint8) for b in range(3)]
+    return [("cube", *cube), ("cb1 / noise / bnoise", lum("cb1_flip"), lum("noise"), lum("bnoise_pan")), ("flat / edge / cb8", lum("flat_flip", 1), lum("edge_ramp"), lum("cb8_shift", 1)),
+            ("noise", lum("noise"), lum("noise", 1), 255 - lum("noise"))]
+
+
+@pytest.mark.parametrize("W,H", SMALL)
+def test_rgb_formats_exact_at_small_and_ragged_shapes(hip, W, H):
+    for label, r, g, b in _rgb_inputs(W, H):
+        for matrix in (ref.MATRIX_BT709, ref.MATRIX_BT601):
+            for full in (0, 1):
+                exp = ref.rgb_to_i420(r, g, b, matrix, bool(full))
+                for off, pad in LAYOUTS:
+                    for name, step, order in (("rgb24", 3, (0, 1, 2)), ("rgba", 4, (0, 1, 2)), ("bgra", 4, (2, 1, 0)), ("planar", 1, None)):
+                        d = InDesc(); d.format, d.width, d.height, d.pixel_step, d.matrix, d.full_range = 2, W, H, step, matrix, full
+                        if order is None:
+                            buf, addr = _place([r, g, b], [W + pad] * 3, off)
+                            for k in range(3):
+                                d.plane[k] = addr[k]
+                        else:
+                            px = np.full((H, W, step), 255, np.uint8)
+                            for k in range(3):
+                                px[:, :, order[k]] = (r, g, b)[k]
+                            buf, addr = _place([px.reshape(H, W * step)], [W * step + pad], off)
+                            for k in range(3):
+                                d.plane[k] = addr[0] + order[k]
+                        d.pitch[0] = (W * step if order is not None else W) + pad
+                        got = _convert_guarded(hip, d, W, H)
+                        assert (got == exp).all(), (label, name, matrix, full, off, pad, int((got != exp).sum()))
+
+
 # ------------------------------------------------------------------ the encoder
 
 def _open(lib, W, H, params, latency=b"default"):
