@@ -123,7 +123,18 @@ int ks265_enc_get_quality(void *pEncoder, ks265_enc_quality *out);
  * it lags the input by up to that many GOPs, and every lane buffers a GOP of input (pinned host memory + a device twin per picture, capped by KS265_PINNED_MB per lane). */
 int ks265_enc_lanes(void *pEncoder);
 /* extension: the switches of the reference CLI that QY265EncConfig has no field for - "df" (deblocking, default 1), "fixqp" (1 = no per-layer QP offsets: every
- * picture at -qp), "md5" (1 = log `POC n MD5 y,u,v` of every reconstructed picture, display order).  Process-wide defaults read by the next QY265EncoderOpen. */
+ * picture at -qp), "md5" (1 = log `POC n MD5 y,u,v` of every reconstructed picture, display order).  Process-wide defaults read by the next QY265EncoderOpen.
+ * "gpb" (0 / 1, default 0; other values QY265_PARAM_BAD_VALUE; the environment's KS265_GPB=0|1 overrides it at QY265EncoderOpen; `ks265enc -gpb N`): generalised B anchors, as the
+ * reference codes them (its -psnr 2 lines show every anchor of the pyramid as a B slice).  An anchor of a GOP with B pictures takes the pictures it takes anyway - the last
+ * min(-ref0, anchors since the key picture) anchors of its GOP, a1 nearest, the key picture counting - and with
+ *     one of them   stays the P slice on [a1] it is;
+ *     two           goes out as a B slice with list 0 = [a1], list 1 = [a2];
+ *     three / four  as a B slice with list 0 = [a1, a3(, a4)], list 1 = [a2]
+ * (no picture in both lists; bi-prediction pairs the two nearest anchors; every picture is searched once).  Reference picture sets, DPB size and NAL types stay; the lists are not
+ * the default construction, so the stream's PPS carries lists_modification_present_flag = 1 where the switch is in force.  Such a picture remains an anchor to everything else:
+ * QP ladder and lambda, rate control, lookahead / cuTree, scene cuts, -aq, GOP lanes; it keeps the full tool set and runs without the skip pass like a P picture.
+ * QY265Picture.iSliceType and the -psnr 2 lines report it as the stream does: B.  The switch is accepted and does nothing where no anchor searches two anchors: -bframes 0,
+ * zero latency, -ref0 1, and P + n plain B pictures (whose anchors keep one reference); there the stream is byte for byte the one without it.  Measured: DESIGN.md 5d. */
 int ks265_enc_set_default(const char *name, int value);
 /* extension: zero-copy input.  Fills `yuv` with the planes of one of the encoder's pinned input buffers (packed I420, strides = width, width / 2); the caller writes the
  * next picture there and passes the same QY265YUV to QY265EncoderEncodeFrame, which then copies nothing (0.35 ms of the calling thread per 2160p picture otherwise).

@@ -419,6 +419,10 @@ int ks265_frame_set_qp(ks265_frame *f, int qp, int lambda_q4);
  * search method needs no workspace of its own).  With cfg.sao = 0 a B picture is reconstructed and deblocked straight in
  * recon_out (no SAO launch, no copy); its SAO records are written as "off" and the host passes ks265_slice_in.sao = NULL (slice_sao_luma_flag = slice_sao_chroma_flag = 0). */
 int ks265_frame_set_picture_tools(ks265_frame *f, int intra_inter, int bi_refine, int sao, int me_method);
+/* the skip pass per picture (cfg.skip_rd): -1 = the value the frame object was created with, else the value for the pictures coded from now on - 0 (no pass) up to the created
+ * value; above it KS265_NOTSUPPORTED.  All of ks265_encode_picture[_mref|_b|_b_mref] honour it: with 0 a B slice runs without the pass (an anchor coded as a B picture over past
+ * anchors - ks265_enc.h `gpb` - is a B slice to this library and a P picture to the host's rule "B pictures only"), with 0 on a frame object created with 2 so does a P picture */
+int ks265_frame_set_picture_skip(ks265_frame *f, int skip_rd);
 
 /* expandPicture_c enc@0x4a6ae0: replicate the picture edge into the borders of all three planes */
 int ks265_pad_picture(ks265_frame *f, ks265_pic pic);

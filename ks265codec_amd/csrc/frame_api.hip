@@ -128,6 +128,16 @@ int ks265_frame_set_picture_tools(ks265_frame *f, int intra_inter, int bi_refine
     return KS265_OK;
 }
 
+/* the skip pass (stage D2) per picture: -1 = as created, else the value cfg.skip_rd takes for the pictures coded from here on - 0 .. the created value (the spare CU map is the
+ * creation's).  A host that codes an anchor as a B slice over past anchors sets 0 for it: the pass on anchors loses more PSNR than it saves bytes */
+int ks265_frame_set_picture_skip(ks265_frame *f, int skip_rd)
+{
+    KS_FRAME_CHECK(f);
+    if (skip_rd > f->cfg0.skip_rd) return KS265_NOTSUPPORTED;
+    f->cfg.skip_rd = skip_rd < 0 ? f->cfg0.skip_rd : skip_rd;
+    return KS265_OK;
+}
+
 /* stage A (+ A2): the integer search of src in one reference picture, then cfg.propagate rounds of vector propagation; the records end up in pu */
 static int me_search(ks265_frame *f, ks265_pic src, ks265_pic ref, const ks265_pu *prev, ks265_pu *pu)
 {

@@ -7,7 +7,8 @@
     enc.close()
 
 The encoder reads each tensor in the order of torch's current stream and makes that stream wait until it has: the caller may overwrite the tensor with further work on the
-same stream as soon as encode() returns, with no host synchronisation.  Parameters are QY265ConfigParse names (qp, crf, rc, iper, bframes, lookahead, latency, ...)."""
+same stream as soon as encode() returns, with no host synchronisation.  Parameters are QY265ConfigParse names (qp, crf, rc, iper, bframes, lookahead, latency, ...);
+gpb=0|1 is the process default of that name (ks265_enc_set_default: anchors that search two or more past anchors as B slices over them), set before this handle opens."""
 from __future__ import annotations
 
 import ctypes as C
@@ -115,6 +116,9 @@ class Encoder:
         self._cfg = (C.c_uint8 * _CONFIG_BYTES)()
         if self.lib.QY265ConfigDefaultPreset(self._cfg, preset.encode(), None, str(params.pop("latency", "default")).encode()) != 0:
             raise ValueError(f"preset {preset!r}")
+        gpb = params.pop("gpb", None)                           # no QY265EncConfig field: a process default (None leaves it as it is)
+        if gpb is not None and self.lib.ks265_enc_set_default(b"gpb", C.c_int(int(gpb))) != 0:
+            raise ValueError(f"parameter gpb={gpb!r}: bad value")
         for k, v in (("wdt", width), ("hgt", height), *params.items()):
             rc = self.lib.QY265ConfigParse(self._cfg, str(k).replace("_", "-").encode(), str(v).encode())   # keyword form of the names with a dash: sao_ref=2 -> "sao-ref"
             if rc != 0:

@@ -34,6 +34,8 @@
  * and prints no ` ssim:` line */
 #pragma weak ks265_ssim_picture
 #pragma weak ks265_ssim_picture_on
+/* `gpb` switches the skip pass off for its anchors the same way: a device library without the setter - the stand-in has no skip pass - is not asked */
+#pragma weak ks265_frame_set_picture_skip
 
 const char strLibQy265Version[] = "ks265enc 0.2 (MI355X pixel path + host CABAC; API of libqycodec V2.6.1.3)";
 
@@ -86,7 +88,7 @@ static void md5_hex(const uint8_t *data, size_t n, char out[33])
 
 /* CLI-level switches of `appencoder` that the SDK's QY265EncConfig has no field for (-df, -fixqp, -md5): process-wide defaults a front end
  * sets before QY265EncoderOpen (ks265_enc_set_default) */
-static struct { int df, fixqp, md5, scenecut, cutree; } g_cli = {1, 0, 0, 0, 1};
+static struct { int df, fixqp, md5, scenecut, cutree, gpb; } g_cli = {1, 0, 0, 0, 1, 0};
 int ks265_enc_set_default(const char *name, int value)
 {
     if (!name) return QY_POINTER;
@@ -95,6 +97,7 @@ int ks265_enc_set_default(const char *name, int value)
     if (!strcmp(name, "md5")) { if (value < 0 || value > 1) return QY265_PARAM_BAD_VALUE; g_cli.md5 = value; return QY_OK; }
     if (!strcmp(name, "scenecut")) { if (value < 0 || value > 100) return QY265_PARAM_BAD_VALUE; g_cli.scenecut = value; return QY_OK; }   /* the reference's hidden -scenecut N */
     if (!strcmp(name, "cutree")) { if (value < 0 || value > 1) return QY265_PARAM_BAD_VALUE; g_cli.cutree = value; return QY_OK; }        /* the reference's hidden -cutree N (on by default, as there) */
+    if (!strcmp(name, "gpb")) { if (value < 0 || value > 1) return QY265_PARAM_BAD_VALUE; g_cli.gpb = value; return QY_OK; }                /* anchors as B slices over past anchors (ks265_enc.h) */
     return QY265_PARAM_BAD_NAME;
 }
 
@@ -203,6 +206,7 @@ typedef struct TopWake { pthread_mutex_t mu; pthread_cond_t cv; unsigned long se
 typedef struct Job {
     int used, done, error;
     int disp, poc, kind, qp, nal_type, is_ref;            /* kind: 'I' 'P' 'B' */
+    int gpb;                                              /* an anchor (kind 'P' for every rule of the host) that goes out as a B slice: both lists hold past anchors (`gpb`) */
     int no_sao;                                           /* the picture was coded without SAO (lean B pictures): slice_sao_luma_flag = slice_sao_chroma_flag = 0 */
     long long pts;
     int nl0, nl1, l0[4], l1[4], nrps, rps_poc[16]; unsigned char rps_used[16];
@@ -319,6 +323,7 @@ typedef struct Enc {
     CopyPool *pool;                                       /* shared by the lanes of one handle (owned by it) */
     int me_method, hex_thr, subme, refs, use_sao, use_df, gop_b, hier;                  /* resolved tools */
     int lean_b;                                                                         /* B pictures nothing predicts from: no intra candidates, no joint refinement, no SAO (KS265_LEAN_B=0: as the others) */
+    int gpb;                                                                            /* `gpb` in force: an anchor that searches two or more past anchors is coded as a B slice (schedule) */
     int refs0, anc_hist[4], n_anc;                                                      /* -ref0 (qy265enc.h:142, the reference's ActiveRefNumFrm0InGop): how many past anchors an anchor of the pyramid searches; the last anchors' POCs, nearest first */
     int base_qp, iper, nthreads;
     PixPath path[NPATH]; ks265_frame_geom geom; ks265_frame_cfg fcfg; ks265_stream_cfg scfg;
@@ -569,7 +574,7 @@ static void *worker(void *arg)
             if (!err) {
                 ks265_slice_in *s = &j->sin;
                 memset(s, 0, sizeof *s);
-                s->nal_type = j->nal_type; s->slice_type = j->kind == 'I' ? KS265_SLICE_I : j->kind == 'P' ? KS265_SLICE_P : KS265_SLICE_B;
+                s->nal_type = j->nal_type; s->slice_type = j->kind == 'I' ? KS265_SLICE_I : j->kind == 'P' && !j->gpb ? KS265_SLICE_P : KS265_SLICE_B;
                 s->poc = j->poc; s->qp = j->qp; s->num_rps = j->nrps;
                 memcpy(s->rps_poc, j->rps_poc, sizeof s->rps_poc); memcpy(s->rps_used, j->rps_used, sizeof s->rps_used);
                 s->num_l0 = j->nl0; s->num_l1 = j->nl1; memcpy(s->l0_poc, j->l0, sizeof s->l0_poc); memcpy(s->l1_poc, j->l1, sizeof s->l1_poc);
@@ -871,6 +876,7 @@ static int quality_pass(Enc *e, ks265_ctx *on, ks265_frame *fr, ks265_pic src, k
 typedef struct Sub {
     Job *j; Input *in;
     int kind, poc, qp, nl0, nl1, is_ref; const int *l0, *l1;
+    int gpb;                                              /* kind 'P' with a list 1: the anchor is coded and signalled as a B picture, everything else treats it as the P picture it is */
     int keep[32], nk;                                     /* POCs that must stay in the DPB: the caller's keep_after + what this picture uses */
     int k, recycled;                                      /* rotation slot of the input buffer / staging set (seq % NPIPE); it has held a picture before */
     int path; PixPath *p;                                 /* the pixel path that codes the picture (PATH_*) */
@@ -897,7 +903,7 @@ static Job *wait_job_slot(Enc *e)
 static void choose_path(Enc *e, Sub *s)
 {
     const int on_key = s->kind == 'I' && e->key_overlap && (s->in->iper <= 0 || s->in->iper >= 32);
-    const int on_anc = s->kind == 'P' && e->anc_on && e->key_overlap && s->nl0 == 1;      /* (key_overlap goes off with the reconstruction dump: everything on the main stream then) */
+    const int on_anc = s->kind == 'P' && !s->gpb && e->anc_on && e->key_overlap && s->nl0 == 1;      /* (key_overlap goes off with the reconstruction dump: everything on the main stream then) */
     s->path = on_key ? PATH_KEY : on_anc ? PATH_ANC : PATH_MAIN;
     s->p = &e->path[s->path];
     s->k = (int)(e->seq % NPIPE);
@@ -909,7 +915,7 @@ static void choose_path(Enc *e, Sub *s)
      * the last B picture of the mini-GOP before it has left the device */
     s->direct = s->path == PATH_ANC && s->in->dev && !e->use_graph;
     /* graph path: a P picture with one reference on the main stream, once the first pictures have made every lazy allocation */
-    s->graphable = e->use_graph && ((s->kind == 'P' && s->nl0 == 1) || (s->kind == 'B' && s->nl0 == 1 && s->nl1 == 1)) && s->path == PATH_MAIN && !e->recon_on && e->seq >= 8;
+    s->graphable = e->use_graph && ((s->kind == 'P' && s->nl0 == 1 && !s->gpb) || (s->kind == 'B' && s->nl0 == 1 && s->nl1 == 1)) && s->path == PATH_MAIN && !e->recon_on && e->seq >= 8;
 }
 
 /* the input picture reaches the device and, unpacked and padded, the path's source picture */
@@ -951,6 +957,8 @@ static int set_picture_tools(Enc *e, Sub *s)
     const int near = s->kind == 'B' && s->is_ref && s->nl0 > 0 && s->nl1 > 0 && s->poc - s->l0[0] <= 2 && s->l1[0] - s->poc <= 2;
     s->lean = !e->lean_b || s->kind != 'B' ? 0 : !s->is_ref ? 2 : near && e->lean_b != 3 ? 1 : 0;          /* (KS265_LEAN_B=3: the non-reference pictures alone) */
     if (!r) r = s->lean == 2 ? ks265_frame_set_picture_tools(fr, 0, 0, 0, e->lean_b == 2 && e->me_method == 2 ? 1 : -1) : s->lean == 1 ? ks265_frame_set_picture_tools(fr, 0, -1, 0, -1) : ks265_frame_set_picture_tools(fr, -1, -1, -1, -1);
+    /* `gpb`: the device runs the skip pass on every B slice (skip_rd 1 = B pictures only); an anchor is none to this host - its errors propagate through the pyramid */
+    if (!r && e->gpb && ks265_frame_set_picture_skip) r = ks265_frame_set_picture_skip(fr, s->gpb && e->fcfg.skip_rd < 2 ? 0 : -1);
     return r;
 }
 
@@ -968,7 +976,7 @@ static int set_rdoq_tables(Enc *e, Sub *s)
         if (e->rq_hist_kind[q % RQ_HIST] == (char)s->kind) { memcpy(tb, e->rq_hist + (size_t)(q % RQ_HIST) * 1440, 1440 * sizeof(int32_t)); found = 1; }
     pthread_mutex_unlock(&e->mu);
     int r = 0;
-    if (!found) r = ks265_rdoq_tables(&e->scfg, NULL, s->kind == 'P' ? KS265_SLICE_P : KS265_SLICE_B, s->qp, tb) ? KS265_FAIL : 0;
+    if (!found) r = ks265_rdoq_tables(&e->scfg, NULL, s->kind == 'P' && !s->gpb ? KS265_SLICE_P : KS265_SLICE_B, s->qp, tb) ? KS265_FAIL : 0;   /* (the slice type the picture goes out with) */
     memcpy(tb + 1440, e->rq_lam, sizeof e->rq_lam);
     if (!r) r = ks265_frame_set_rdoq(s->p->frame, tb, (const int64_t *)(tb + 1440), (const int64_t *)(tb + 1440) + 52);
     return r;
@@ -1040,7 +1048,7 @@ static int code_picture(Enc *e, const Sub *s)
     ks265_pic r0[4], r1[4];
     for (int i = 0; i < s->nl0; ++i) r0[i] = e->dpb[dpb_find(e, s->l0[i])];
     for (int i = 0; i < s->nl1; ++i) r1[i] = e->dpb[dpb_find(e, s->l1[i])];
-    if (s->kind == 'B') return s->nl0 > 1 || s->nl1 > 1 ? ks265_encode_picture_b_mref(fr, s->srcp, r0, s->nl0, r1, s->nl1, s->out) : ks265_encode_picture_b(fr, s->srcp, r0[0], r1[0], s->out);
+    if (s->kind == 'B' || s->gpb) return s->nl0 > 1 || s->nl1 > 1 ? ks265_encode_picture_b_mref(fr, s->srcp, r0, s->nl0, r1, s->nl1, s->out) : ks265_encode_picture_b(fr, s->srcp, r0[0], r1[0], s->out);
     if (s->kind == 'P' && s->nl0 > 1) return ks265_encode_picture_mref(fr, s->srcp, r0, s->nl0, s->out);
     const int key = s->kind == 'I';
     return ks265_encode_picture(fr, s->srcp, key ? s->out : r0[0], key, s->out);
@@ -1192,6 +1200,7 @@ static void fill_job(Enc *e, const Sub *s, int key_headers)
     j->disp = in->disp; j->pts = in->pts; j->poc = s->poc; j->kind = s->kind; j->qp = s->qp; j->is_ref = s->is_ref; j->key_headers = key_headers; j->rc_delta = e->rc_qp_delta;
     j->rc_budget = (double)in->kbps * 1000.0 / (e->cfg.frameRate > 0 ? e->cfg.frameRate : 25.0);
     j->nal_type = s->kind == 'I' ? KS265_NAL_IDR_W_RADL : s->is_ref ? KS265_NAL_TRAIL_R : KS265_NAL_TRAIL_N;
+    j->gpb = s->gpb;
     j->nl0 = s->nl0; j->nl1 = s->nl1;
     for (int i = 0; i < s->nl0; ++i) j->l0[i] = s->l0[i];
     for (int i = 0; i < s->nl1; ++i) j->l1[i] = s->l1[i];
@@ -1228,7 +1237,7 @@ static void publish_job(Enc *e, const Sub *s)
 /* enqueue one picture: GPU work + copies on the streams, then hand it to the writers */
 static int submit(Enc *e, Input *in, int kind, int poc, int qp, const int *l0, int nl0, const int *l1, int nl1, const int *keep_after, int nkeep, int is_ref, int key_headers)
 {
-    Sub s = {.in = in, .kind = kind, .poc = poc, .qp = qp, .l0 = l0, .nl0 = nl0, .l1 = l1, .nl1 = nl1, .is_ref = is_ref};
+    Sub s = {.in = in, .kind = kind, .poc = poc, .qp = qp, .l0 = l0, .nl0 = nl0, .l1 = l1, .nl1 = nl1, .is_ref = is_ref, .gpb = kind == 'P' && nl1 > 0};
     for (int i = 0; i < nkeep; ++i) s.keep[s.nk++] = keep_after[i];
     for (int i = 0; i < nl0; ++i) s.keep[s.nk++] = l0[i];
     for (int i = 0; i < nl1; ++i) s.keep[s.nk++] = l1[i];
@@ -1368,13 +1377,16 @@ static int schedule(Enc *e, int flush, int have /* pictures [0, have) have arriv
             if (rr) return hip_rc(rr);
         }
         const int pd = d - e->gop_start, pa = a - e->gop_start;
-        int l0[4], nl0 = 0, keep[8], nkeep = 0;
+        int l0[4], nl0 = 0, l1[1], nl1 = 0, keep[8], nkeep = 0;
         if (span == 1) {                                               /* IPPP: the most recent pictures, nearest first */
             for (int i = 0; i < e->refs && pa - 1 - i >= 0; ++i) l0[nl0++] = pa - 1 - i;
             for (int i = 0; i < e->refs - 1 && pa - 1 - i >= 0; ++i) keep[nkeep++] = pa - 1 - i;   /* still needed by the next picture */
         } else if (e->refs0 > 1 && e->n_anc > 0 && e->anc_hist[0] == pd) {
             /* -ref0: the last anchors of this GOP, nearest first (the first one is the previous anchor); all of them but the oldest are the next anchor's too */
-            for (int i = 0; i < e->refs0 && i < e->n_anc; ++i) l0[nl0++] = e->anc_hist[i];
+            /* `gpb`: with two or more of them the anchor goes out as a B slice - the second nearest alone in list 1, the others in list 0: no picture in both lists (the boundary
+             * strength compares list indices), bi-prediction pairs the two nearest anchors, every picture is searched once.  The pictures, and with them the reference picture
+             * sets, are the P anchor's; the order is not the default construction's (8.3.4 gives both lists of past pictures the same order): list_mod */
+            for (int i = 0; i < e->refs0 && i < e->n_anc; ++i) { if (e->gpb && i == 1) l1[nl1++] = e->anc_hist[i]; else l0[nl0++] = e->anc_hist[i]; }
             for (int i = 0; i < e->refs0 - 1 && i < e->n_anc; ++i) keep[nkeep++] = e->anc_hist[i];
         } else { l0[nl0++] = pd; keep[nkeep++] = pd; }
         Input *ina = input_at(e, a);
@@ -1384,7 +1396,7 @@ static int schedule(Enc *e, int flush, int have /* pictures [0, have) have arriv
          * measured with the CPU mirror of this host: - 12 % bytes of the P pictures for - 0.09 dB */
         static const int kIpppCascade[4] = {0, 2, 1, 2};
         const int casc = e->gop_b == 0 ? kIpppCascade[pa & 3] : 0;
-        int r = submit(e, ina, 'P', pa, clampqp(e, ina->base_qp + e->rc_qp_delta + (e->fixqp ? 0 : 1 + casc)), l0, nl0, NULL, 0, keep, nkeep, 1, 0);
+        int r = submit(e, ina, 'P', pa, clampqp(e, ina->base_qp + e->rc_qp_delta + (e->fixqp ? 0 : 1 + casc)), l0, nl0, l1, nl1, keep, nkeep, 1, 0);
         if (r) return r;
         if (span > 1) {                                                /* the anchors' history: this one in front */
             for (int i = 3; i > 0; --i) e->anc_hist[i] = e->anc_hist[i - 1];
@@ -1484,7 +1496,7 @@ static int take_output(Enc *e, int max_in_flight, int max_pics, QY265Nal **pNals
         e->nals[cnt].naltype = j->nal_type; e->nals[cnt].tid = 0; e->nals[cnt].iSize = (int)need; e->nals[cnt].pts = j->pts; e->nals[cnt].pPayload = e->outbuf + e->outpos;
         e->outpos += need;
         ++cnt;
-        if (out) { out->iSliceType = j->kind == 'I' ? 2 : j->kind == 'P' ? 1 : 0; out->poc = j->disp; out->pts = j->pts; out->dts = j->pts; }
+        if (out) { out->iSliceType = j->kind == 'I' ? 2 : j->kind == 'P' && !j->gpb ? 1 : 0; out->poc = j->disp; out->pts = j->pts; out->dts = j->pts; }
         e->st.frames++; e->st.bytes += j->nal_len > 0 ? j->nal_len : 0; e->st.host_write_ms += j->t_write_ms;
         e->st.lat_gpu_ms += j->t_event - j->t_submit; e->st.lat_queue_ms += j->t_taken - j->t_submit;
         if (j->kind == 'I') { e->st.key_wall_ms += j->t_done - j->t_event; e->st.key_cpu_ms += j->t_write_ms; e->st.keys++; }
@@ -1497,7 +1509,7 @@ static int take_output(Enc *e, int max_in_flight, int max_pics, QY265Nal **pNals
                 for (int k = 0; k < 3; ++k) ps[k] = j->sse[k] ? 10.0 * log10(255.0 * 255.0 * np[k] / (double)j->sse[k]) : 99.0;
                 /* appencoder's -psnr 2 table: `poc slice bits psnrY psnrU psnrV qp`, tab separated, one header line */
                 if (!e->psnr_hdr) { e->psnr_hdr = 1; logf_(2, e->log_level, "poc\tslice\tbits\tpsnr\t\t\tqp\n"); }
-                logf_(2, e->log_level, "%d\t%c\t%ld\t%.4f\t%.4f\t%.4f\t%d\n", j->disp, j->kind, (long)j->nal_len * 8, ps[0], ps[1], ps[2], j->qp);
+                logf_(2, e->log_level, "%d\t%c\t%ld\t%.4f\t%.4f\t%.4f\t%d\n", j->disp, j->gpb ? 'B' : j->kind /* (the slice type of the stream, as in the reference's lines) */, (long)j->nal_len * 8, ps[0], ps[1], ps[2], j->qp);
             }
         }
         if (e->ssim_on) {
@@ -1674,6 +1686,8 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
      * nearest first = the default list construction); the older anchors stay in every reference picture set in between.  KS265_REF0 overrides (experiments: 1 = round 5's anchors) */
     e->refs0 = e->hier ? (cfg->ref0 < 1 ? 1 : cfg->ref0 > 4 ? 4 : cfg->ref0) : 1;
     if (getenv("KS265_REF0") && e->hier) { const int v = atoi(getenv("KS265_REF0")); e->refs0 = v < 1 ? 1 : v > 4 ? 4 : v; }
+    /* `gpb` (ks265_enc_set_default, KS265_GPB overrides): in force where an anchor can see two anchors - with B pictures and -ref0 > 1; IPPP and zero latency have no such anchors */
+    e->gpb = (getenv("KS265_GPB") ? atoi(getenv("KS265_GPB")) != 0 : g_cli.gpb) && e->gop_b > 0 && e->refs0 > 1;
     e->base_qp = cfg->rc == 3 ? cfg->crf : cfg->qp;
     if (e->base_qp < 0) e->base_qp = 0;
     if (e->base_qp > 51) e->base_qp = 51;
@@ -1940,6 +1954,7 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
     e->scfg.sdh = e->fcfg.sdh;
     e->zero_latency = cfg->latency == QY265LATENCY_ZERO && e->gop_b == 0 && !e->la_on && !multi;
     e->scfg.cu_qp_delta = e->qmap_on;
+    e->scfg.list_mod = e->gpb;                                          /* the anchors' two lists of past pictures are not the default construction (schedule) */
     e->scfg.tu_inter = e->fcfg.tu_inter;
     e->scfg.wpp = 1;                                                    /* CTU rows as substreams: what lets several writer threads share one picture */
     e->scfg.max_dec_pic_buffering = e->hier ? 10 : e->gop_b ? 4 : e->refs + 1; e->scfg.log2_max_poc_lsb = 16;

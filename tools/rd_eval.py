@@ -52,7 +52,12 @@ def encode_ours(clip, W, H, qp, gop, tools, verbose=False, stats=None, pdelta=1,
     n = len(clip)
     o = OraclePipeline(W, H, qp, lambda_q4(qp), **tools)
     G = int(os.environ.get("RD_G", "8").replace("plain", ""))
-    w = S.StreamWriter(W, H, max_dec_pic_buffering=10 if gop == "hier" else 2, max_num_reorder=7 if gop == "hier" else 0, sdh=tools.get("sdh", 0), wpp=0 if stats else 1, list_mod=1 if os.environ.get('RD_GPB2') else 0, tu_inter=tools.get("tu_inter", 0))
+    # --host follows KS265_GPB like the encoder host (ks265_enc.h `gpb`): an anchor that searches two or more past anchors goes out as a B slice - list 0 = [a1, a3(, a4)], list 1 = [a2] -
+    # without the skip pass, at the anchor's QP and lambda; the stream then signals lists_modification_present_flag
+    nmref = int(os.environ.get('RD_MREF', '3' if lam_scale == -1 else '1'))
+    host_hier = lam_scale == -1 and gop == "hier"
+    gpb = host_hier and nmref > 1 and os.environ.get("KS265_GPB", "0") not in ("", "0")
+    w = S.StreamWriter(W, H, max_dec_pic_buffering=10 if gop == "hier" else 2, max_num_reorder=(3 if G == 4 and host_hier else 7) if gop == "hier" else 0, sdh=tools.get("sdh", 0), wpp=0 if stats else 1, list_mod=1 if gpb else 0, tu_inter=tools.get("tu_inter", 0))
     import ctypes as C
     st = (C.c_double * 6)()
     agg = {}
@@ -66,23 +71,24 @@ def encode_ours(clip, W, H, qp, gop, tools, verbose=False, stats=None, pdelta=1,
         seq = [(t, "I" if t == 0 else "P", t - 1 if t else None, None, 0) for t in range(n)]
     else:
         seq = [s for s in itertools.islice(hier_order(G, 1 << 20), n) if s[0] < n]
-        if os.environ.get('RD_GPB_SAME'):                             # experiment: generalised B at the P positions, both lists = the previous anchor
-            seq = [(d, 'B', r0, r0, 0) if k == 'P' else (d, k, r0, r1, l) for (d, k, r0, r1, l) in seq]
-        if os.environ.get('RD_GPB2'):                                 # generalised B at the P positions: list 0 = the previous anchor, list 1 = the one before it
-            seq = [(d, 'B', r0, r0 - G if r0 >= G else r0, 0) if k == 'P' else (d, k, r0, r1, l) for (d, k, r0, r1, l) in seq]
     encode_ours._cfg0 = {nm: getattr(o.cfg, nm) for nm in ('sao', 'bi_refine', 'propagate', 'intra_inter', 'merge', 'rdo')}
     dpb = {}
     # -ref0 (round 6; the host's default under --host: 3 = what -preset slow resolves to): the anchors of the hierarchy search the last RD_MREF anchors of their GOP, nearest first
-    nmref = int(os.environ.get('RD_MREF', '3' if lam_scale == -1 else '1'))
-    mrs, hist = [], []
+    # keeps: --host with the pyramid GOPs - the pictures the host keeps in every reference picture set (ks265_enc.c schedule / code_hier: the anchors the next anchor searches, the
+    # mini-GOP's reference pictures coded so far), so that the slice headers are the host's to the bit
+    mrs, hist, keeps, mg = [], [], [], []
     for (d, kind, r0, r1, layer) in seq:
         if kind == 'I':
-            hist = [d]; mrs.append([])
+            hist = [d]; mrs.append([]); keeps.append(set())
         elif kind == 'P':
-            mrs.append(hist[:nmref] if (gop == 'hier' and nmref > 1 and hist and hist[0] == r0) else [])
-            hist = [d] + hist
+            multi = gop == 'hier' and nmref > 1 and hist and hist[0] == r0
+            mrs.append(hist[:nmref] if multi else [])
+            keeps.append(set(hist[:nmref - 1]) if multi else {r0})
+            hist = ([d] + hist)[:4]; mg = [r0, d]
         else:
-            mrs.append([])
+            mrs.append([]); keeps.append(set(mg) | set(hist[2:nmref]))
+            if any(d in (a, b) for (_, k2, a, b, _) in seq if k2 == 'B'):
+                mg = mg + [d]
     for i, (d, kind, r0, r1, layer) in enumerate(seq):
         lq = 1 if layer < 0 else layer_qp[min(len(layer_qp) - 1, layer)] if (layer_qp and kind == 'B') else layer      # B layers are numbered 1 (referenced most) .. 3; -1: a plain B picture outside a pyramid (+ 2)
         q = min(51, qp if kind == "I" else qp + pdelta + lq + (cascade[d % len(cascade)] if cascade and gop == "ippp" else 0))
@@ -109,9 +115,16 @@ def encode_ours(clip, W, H, qp, gop, tools, verbose=False, stats=None, pdelta=1,
                 nm, vals = spec.split('='); vals = [int(x) for x in vals.split(',')]
                 setattr(o.cfg, nm, vals[min(len(vals) - 1, max(layer, 1) - 1)] if kind == 'B' else tools.get(nm, getattr(encode_ours, '_cfg0', {}).get(nm, 0)))
         mr = mrs[i]
+        gl0, gl1 = ([mr[0]] + mr[2:], [mr[1]]) if gpb and kind == 'P' and len(mr) > 1 else (None, None)
         if getattr(encode_ours, "rdoq_select", None):
             encode_ours.rdoq_select(kind)
-        if len(mr) > 1:
+        if gl0:
+            skip0, o.skip_rd = o.skip_rd, o.skip_rd if o.skip_rd >= 2 else 0     # the skip pass is the B pictures' (skip_rd 1): an anchor runs without it
+            try:
+                dpb[d] = o.encode_b_mref(clip[d], [dpb[r] for r in gl0], [dpb[r] for r in gl1])
+            finally:
+                o.skip_rd = skip0
+        elif len(mr) > 1:
             dpb[d] = o.encode_mref(clip[d], [dpb[r] for r in mr])
         else:
             dpb[d] = o.encode(clip[d], kind, dpb.get(r0), dpb.get(r1))
@@ -119,12 +132,14 @@ def encode_ours(clip, W, H, qp, gop, tools, verbose=False, stats=None, pdelta=1,
         later = seq[i + 1:]
         needed = {r for j, (dd, kk, a, b, _) in enumerate(later) for r in [a, b] + mrs[i + 1 + j] if r is not None and r in dpb and r != d}
         cur = {r for r in (r0, r1) if r is not None} | set(mr)
-        rps = [(p, p in cur) for p in sorted(needed | cur)]
+        rps = [(p, p in cur) for p in sorted(((keeps[i] - {d}) if host_hier else needed) | cur)]
         isref = any(d in (a, b) for (_, _, a, b, _) in later)
         if stats:
             stats.ks265_bit_stats(st, 1)
         if kind == "I":
             b = w.slice(S.NAL_IDR_W_RADL, S.SLICE_I, 0, q, o.cu8, o.lvl, o.sao)
+        elif gl0:
+            b = w.slice(S.NAL_TRAIL_R, S.SLICE_B, d, q, o.cu8, o.lvl, o.sao, rps=rps, l0=gl0, l1=gl1)
         elif kind == "P":
             b = w.slice(S.NAL_TRAIL_R, S.SLICE_P, d, q, o.cu8, o.lvl, o.sao, rps=rps, l0=mr if len(mr) > 1 else [r0])
         else:
