@@ -166,7 +166,7 @@ static int records_fence(ks265_frame *f)
     f->rec_fence = nullptr;
     return ks265_hip(f->ctx, hipStreamWaitEvent(f->ctx->stream, (hipEvent_t)ev, 0));
 }
-}  // extern "C": the sequencer's helpers take their chains and stage marks as callables
+}  // extern "C": the sequencer and its helpers (the chains of a fork are callables)
 
 /* The searches of one picture as two independent chains (pre-search, integer search, propagation, sub-pel refinement: ~ 0.4 ms each at 2160p, each kernel with a long tail
  * of half-empty CUs - an anchor with three pictures takes two chains' time instead of three).  Where the frame can fork, side_chain is enqueued on the side stream with its own
@@ -203,11 +203,22 @@ static int search_forked(ks265_frame *f, ks265_pic src, bool caller_can, Side si
     return r ? r : rw;
 }
 
-/* The back end of every picture.  mark(n) closes stage n - 1 of the in-situ timing (ks265_encode_picture; the other entry points record no stage events: no_mark).
- * in_place: the picture is coded without SAO and reconstructed and deblocked where it is handed over - no SAO launch, no copy */
-static void no_mark(int) {}
-template <typename Mark>
-static int loop_filters(ks265_frame *f, ks265_pic src, bool in_place, ks265_pic recon_out, Mark mark)
+/* The stage marks of the in-situ timing (ks265_frame_stage_ms): mark(n) records event n, which closes stage n - 1.  Only ks265_encode_picture's two kinds of picture (key,
+ * one-reference P) are timed: every other kind marks nothing */
+struct KsStageMarks {
+    ks265_frame *f; bool on; int evi = 0;
+    void operator()(int stage_done)
+    {
+        if (!on) return;
+        while (evi < stage_done) f->ev_valid[evi++] = false;   // skipped stages of a key picture
+        (void)hipEventRecord(f->ev[stage_done], f->ctx->stream);
+        f->ev_valid[stage_done] = true;
+        evi = stage_done + 1;
+    }
+};
+
+/* The back end of every picture.  in_place: the picture is coded without SAO and reconstructed and deblocked where it is handed over - no SAO launch, no copy */
+static int loop_filters(ks265_frame *f, ks265_pic src, bool in_place, ks265_pic recon_out, KsStageMarks &mark)
 {
     int r;
     const ks265_pic deb = in_place ? recon_out : ks_deb_pic(f);
@@ -220,8 +231,7 @@ static int loop_filters(ks265_frame *f, ks265_pic src, bool in_place, ks265_pic 
 }
 /* an inter picture from its CU map on: reconstruction, skip pass (stage D2: on the coded distortion), the intra CUs' pass, the loop filters.  What differs between the
  * kinds of picture is decided by the caller: skip / ii = whether those passes run */
-template <typename Mark>
-static int inter_back_end(ks265_frame *f, ks265_pic src, const KsPicLists &lists, bool skip, bool ii, bool in_place, ks265_pic recon_out, Mark mark)
+static int inter_back_end(ks265_frame *f, ks265_pic src, const KsPicLists &lists, bool skip, bool ii, bool in_place, ks265_pic recon_out, KsStageMarks &mark)
 {
     int r;
     const ks265_pic deb = in_place ? recon_out : ks_deb_pic(f);
@@ -232,24 +242,77 @@ static int inter_back_end(ks265_frame *f, ks265_pic src, const KsPicLists &lists
     return loop_filters(f, src, in_place, recon_out, mark);
 }
 
+/* Every inter picture: the searches, the PU records, the CU tree, the merge pass, the common back end.  The kinds:
+ *   KS_P1  one list-0 picture; one-list records (ks265_pu), one search on the context's stream; the only kind with stage marks and with -part 1 among the P kinds
+ *   KS_PN  several list-0 pictures: one search per picture, the per-PU choice (ks265_ref_decide) into two-list records whose list 1 does not exist (lists.pslice: in the
+ *          records it is the nearest picture).  Its workspace may be missing on a frame object made for fewer tools: those stages are then left out (icost, cu8_tmp)
+ *   KS_B   list 0 = pictures before this one in display order, list 1 = after it, each nearest first; ks265_ref_pick keeps per PU and list the cheapest picture, the
+ *          bi-predictive decision pairs the winners; ks265_cu8.inter_dir = direction | idx0 << 4 | idx1 << 6
+ * The P kinds seed their nearest picture's search with the previous P picture's vectors and hand theirs on (pu ping-pong); a B picture leaves that chain untouched */
+enum KsInterKind { KS_P1, KS_PN, KS_B };
+static int encode_inter(ks265_frame *f, KsInterKind kind, ks265_pic src, const KsPicLists &lists, ks265_pic recon_out)
+{
+    const bool p1 = kind == KS_P1, b = kind == KS_B;
+    const int n0 = lists.n[0], n1 = lists.n[1];
+    int r;
+    KsStageMarks mark{f, p1 && f->profiling};
+    ks265_pu *pu0 = f->pu[f->cur_pu];                          /* (a B picture: scratch - the next P picture overwrites it) */
+    auto records = [&](int l, int i) { return i == 0 ? (l ? f->pu1 : pu0) : (l ? f->pu1_x[i - 1] : f->pu_x[i - 1]); };
+    /* the chain of pictures first .. last - 1 of list l: each searched and refined on its own (pre-search, integer search, propagation, sub-pel refinement; the temporal
+     * predictor belongs to a P picture's nearest picture only), then, for a whole list of several pictures, the per-PU choice */
+    auto chain = [&](int l, int first, int last) -> int {
+        const ks265_pu *pus[4];
+        int rr = 0;
+        for (int i = first; i < last && !rr; ++i) {
+            ks265_pu *pu = records(l, i);
+            pus[i] = pu;
+            rr = me_search(f, src, lists.pic[l][i], !b && i == 0 && f->have_prev ? f->pu[f->cur_pu ^ 1] : nullptr, pu);
+            if (!rr) mark(1);
+            if (!rr && f->cfg.subme) rr = ks265_me_subpel(f, src, lists.pic[l][i], pu);
+        }
+        if (!rr && b && lists.multi) rr = ks265_ref_pick(f, last, pus, records(l, 0), f->ridx[l]);
+        return rr;
+    };
+    mark(0);
+    /* B: list 1's chain on the side stream beside list 0's.  Several list-0 pictures: the farther pictures' chains beside the nearest picture's - unlike a B picture, this
+     * kind forks only once the side workspace exists (f->pyr2[0]: the first pre-search of the frame object allocates it).  The join is in front of the records' kernel */
+    if (p1) r = chain(0, 0, 1);
+    else if (b) r = search_forked(f, src, true, [&] { return chain(1, 0, n1); }, [&] { return chain(0, 0, n0); });
+    else r = search_forked(f, src, f->pyr2[0] != nullptr, [&] { return chain(0, 1, n0); }, [&] { return chain(0, 0, 1); });
+    if (r) return r;
+    mark(2);
+    const ks265_pu *pus[4] = {pu0, f->pu_x[0], f->pu_x[1], f->pu_x[2]};
+    if ((r = p1 ? KS265_OK : b ? ks_bi_decide(f, src, lists, pu0, f->pu1, f->pub) : ks265_ref_decide(f, n0, pus, f->pub))) return r;
+    const bool ii = f->cfg.intra_inter != 0 && (kind != KS_PN || f->icost);      /* intra CUs may compete: their candidates first, against the records */
+    if (ii && (r = ks265_intra_candidates(f, src, p1 ? (const void *)pu0 : (const void *)f->pub, f->icost))) return r;
+    mark(3);
+    if ((r = records_fence(f))) return r;
+    const uint32_t *ic = ii ? f->icost : nullptr;
+    const bool part = f->cfg.part != 0 && kind != KS_PN;       /* -part 1: the halves of every 64 / 32 / 16 CU priced first, the CU decision then picks among 2Nx2N / 2NxN / Nx2N / split */
+    const bool mg = f->cfg.merge && (kind != KS_PN || f->cu8_tmp);
+    ks265_cu8 *cud = mg ? f->cu8_tmp : f->cu8;                 /* stage C2: the CU decision goes to the spare map, the merge pass writes the final one */
+    if (p1) r = part ? ks265_cu_decide_part(f, src, lists.pic[0][0], pu0, ic, cud) : ks265_cu_decide_ii(f, pu0, ic, cud);
+    else r = part ? ks_cu_decide_part_b(f, src, lists, pu0, f->pu1, f->pub, ic, cud) : ks265_cu_decide_b_ii(f, f->pub, ic, cud);
+    if (r) return r;
+    if (b && f->cfg.bi_refine == 2 && (r = ks_bi_refine_chosen(f, src, lists, pu0, f->pu1, f->pub, cud))) return r;   /* the joint refinement, for the CUs the decision chose */
+    if (mg && (r = ks_merge_pass(f, src, lists, p1 ? pu0 : nullptr, p1 ? nullptr : f->pub, f->cu8_tmp, f->cu8))) return r;
+    mark(4);
+    const bool skip = b ? f->cfg.skip_rd != 0 : f->cfg.skip_rd >= 2 /* (1: B pictures only) */ && (p1 || f->cu8_tmp);
+    if ((r = inter_back_end(f, src, lists, skip, ii, b && f->cfg.sao == 0, recon_out, mark))) return r;
+    if (!b) { f->cur_pu ^= 1; f->have_prev = true; }          /* the nearest picture's vectors seed the next P picture */
+    return KS265_OK;
+}
+
 extern "C" {
 
 int ks265_encode_picture(ks265_frame *f, ks265_pic src, ks265_pic ref, int is_key, ks265_pic recon_out)
 {
     KS_FRAME_CHECK(f);
     if (!src.y || !recon_out.y) return KS265_POINTER;
-    int r;
-    ks265_pu *pu = f->pu[f->cur_pu];
-    int evi = 0;
-    auto mark = [&](int stage_done) {                      // stage boundary: event stage_done closes stage (stage_done - 1)
-        if (!f->profiling) return;
-        while (evi < stage_done) f->ev_valid[evi++] = false;   // skipped stages of a key picture
-        (void)hipEventRecord(f->ev[stage_done], f->ctx->stream);
-        f->ev_valid[stage_done] = true;
-        evi = stage_done + 1;
-    };
     if (is_key) {
         /* intra picture: mode pre-selection + CU tree on the source, then the wavefront reconstruction */
+        int r;
+        KsStageMarks mark{f, f->profiling};
         mark(2);
         if ((r = records_fence(f))) return r;
         if ((r = ks265_intra_decide(f, src, f->cu8))) return r;
@@ -260,79 +323,29 @@ int ks265_encode_picture(ks265_frame *f, ks265_pic src, ks265_pic ref, int is_ke
         return loop_filters(f, src, false, recon_out, mark);
     }
     if (!ref.y) return KS265_POINTER;
-    const KsPicLists lists = ks_pic_lists(ref, ks265_pic{nullptr, nullptr, nullptr});
-    mark(0);
-    if ((r = me_search(f, src, ref, f->have_prev ? f->pu[f->cur_pu ^ 1] : nullptr, pu))) return r;
-    mark(1);
-    if (f->cfg.subme && (r = ks265_me_subpel(f, src, ref, pu))) return r;
-    mark(2);
-    const bool ii = f->cfg.intra_inter != 0;              /* intra CUs may compete: their candidates first */
-    if (ii && (r = ks265_intra_candidates(f, src, pu, f->icost))) return r;
-    mark(3);
-    if ((r = records_fence(f))) return r;
-    const bool part = f->cfg.part != 0;                    /* -part 1: the halves of every 64 / 32 / 16 CU priced first, the CU decision then picks among 2Nx2N / 2NxN / Nx2N / split */
-    ks265_cu8 *cud = f->cfg.merge ? f->cu8_tmp : f->cu8;   /* stage C2: the CU decision goes to the spare map, the merge pass writes the final one */
-    if ((r = part ? ks265_cu_decide_part(f, src, ref, pu, ii ? f->icost : nullptr, cud) : ks265_cu_decide_ii(f, pu, ii ? f->icost : nullptr, cud))) return r;
-    if (f->cfg.merge && (r = ks_merge_pass(f, src, lists, pu, nullptr, f->cu8_tmp, f->cu8))) return r;
-    mark(4);
-    if ((r = inter_back_end(f, src, lists, f->cfg.skip_rd >= 2 /* (1: B pictures only) */, ii, false, recon_out, mark))) return r;
-    f->cur_pu ^= 1; f->have_prev = true;
-    return KS265_OK;
+    return encode_inter(f, KS_P1, src, ks_pic_lists(ref, ks265_pic{nullptr, nullptr, nullptr}), recon_out);
 }
 
-/* P picture with several list-0 pictures: one search per picture, the per-PU choice, the CU tree, then the common back end */
+/* P picture with several list-0 pictures (-ref / -ref0: the anchors of the pyramid GOPs search several past anchors) */
 int ks265_encode_picture_mref(ks265_frame *f, ks265_pic src, const ks265_pic *refs, int nref, ks265_pic recon_out)
 {
     KS_FRAME_CHECK(f);
     if (!src.y || !refs || !recon_out.y) return KS265_POINTER;
     if (nref < 1 || nref > (f->cfg.refs > 1 ? f->cfg.refs : 1)) return KS265_NOTSUPPORTED;
     if (nref == 1) return ks265_encode_picture(f, src, refs[0], 0, recon_out);
-    int r;
-    ks265_pu *pu0 = f->pu[f->cur_pu];
-    const ks265_pu *pus[4] = {pu0, f->pu_x[0], f->pu_x[1], f->pu_x[2]};
     for (int i = 0; i < nref; ++i) if (!refs[i].y) return KS265_POINTER;
-    /* one picture's chain: pre-search, integer search, propagation, sub-pel refinement; the temporal predictor (previous picture's vectors) belongs to the nearest picture only */
-    auto chain = [&](int i) -> int {
-        ks265_pu *pu = i == 0 ? pu0 : f->pu_x[i - 1];
-        int rr = me_search(f, src, refs[i], i == 0 && f->have_prev ? f->pu[f->cur_pu ^ 1] : nullptr, pu);
-        if (!rr && f->cfg.subme) rr = ks265_me_subpel(f, src, refs[i], pu);
-        return rr;
-    };
-    /* round 6: the chains of the farther pictures beside the nearest picture's.  Unlike a B picture, this path forks only once the side workspace exists (f->pyr2[0]: the first
-     * pre-search of the frame object allocates it) */
-    r = search_forked(f, src, f->pyr2[0] != nullptr,
-                      [&] { int rr = 0; for (int i = 1; i < nref && !rr; ++i) rr = chain(i); return rr; }, [&] { return chain(0); });
-    if (r) return r;
-    if ((r = ks265_ref_decide(f, nref, pus, f->pub))) return r;
-    /* round 6 (-ref0: the anchors of the pyramid GOPs search several past anchors): the two-list records go through the stages a one-reference P picture has - intra candidates
-     * against them (cfg.intra_inter), the CU tree, the merge pass on the records' pictures (cfg.merge), the intra CUs' pass; -part 1 stays with one reference picture */
-    const bool ii = f->cfg.intra_inter != 0 && f->icost;
-    if (ii && (r = ks265_intra_candidates(f, src, f->pub, f->icost))) return r;
-    if ((r = records_fence(f))) return r;
-    const bool mg = f->cfg.merge && f->cu8_tmp;
-    if ((r = ks265_cu_decide_b_ii(f, f->pub, ii ? f->icost : nullptr, mg ? f->cu8_tmp : f->cu8))) return r;
-    /* from here on a block's picture comes from its record; list 1 does not exist (pslice): in the records it is the nearest picture */
-    const KsPicLists lists = ks_pic_lists(refs, nref, refs, 1, true, true);
-    if (mg && (r = ks_merge_pass(f, src, lists, nullptr, f->pub, f->cu8_tmp, f->cu8))) return r;
-    if ((r = inter_back_end(f, src, lists, f->cfg.skip_rd >= 2 && f->cu8_tmp, ii, false, recon_out, no_mark))) return r;
-    f->cur_pu ^= 1; f->have_prev = true;                          /* the nearest picture's vectors seed the next picture */
-    return KS265_OK;
+    return encode_inter(f, KS_PN, src, ks_pic_lists(refs, nref, refs, 1, true, true), recon_out);
 }
 
-/* B picture: both uni-directional searches, the bi candidate, the CU tree, then the common back end.
- * The temporal predictor chain of the P pictures (pu ping-pong) is left untouched. */
-static int encode_b_lists(ks265_frame *f, ks265_pic src, const ks265_pic *refs0, int n0, const ks265_pic *refs1, int n1, ks265_pic recon_out);
 int ks265_encode_picture_b(ks265_frame *f, ks265_pic src, ks265_pic ref0, ks265_pic ref1, ks265_pic recon_out)
 {
     KS_FRAME_CHECK(f);
     if (!src.y || !ref0.y || !ref1.y || !recon_out.y) return KS265_POINTER;
     if (!f->pu1) return KS265_NOTSUPPORTED;                   /* created with cfg.bframes == 0 */
-    return encode_b_lists(f, src, &ref0, 1, &ref1, 1, recon_out);
+    return encode_inter(f, KS_B, src, ks_pic_lists(ref0, ref1), recon_out);
 }
-/* a B picture with n0 / n1 <= cfg.refs pictures per list (round 5; -ref with B pictures: config 5 = -preset veryslow resolves to 4 / 4): list 0 = pictures BEFORE this one in
- * display order, nearest first; list 1 = pictures after it, nearest first; no picture in both lists (the boundary strength compares list indices).  Every picture of a list is
- * searched on its own (list 1's chain on the side stream beside list 0's), ks265_ref_pick keeps per PU and list the cheapest (+ lambda x ref_idx bits), the bi-predictive decision
- * pairs the winners; ks265_cu8.inter_dir = direction | idx0 << 4 | idx1 << 6 */
+/* a B picture with n0 / n1 <= cfg.refs pictures per list (-ref with B pictures: config 5 = -preset veryslow resolves to 4 / 4); no picture in both lists (the boundary
+ * strength compares list indices).  Several pictures per list: from the bi-predictive decision on every stage takes a block's pictures from its record */
 int ks265_encode_picture_b_mref(ks265_frame *f, ks265_pic src, const ks265_pic *refs0, int n0, const ks265_pic *refs1, int n1, ks265_pic recon_out)
 {
     KS_FRAME_CHECK(f);
@@ -343,39 +356,7 @@ int ks265_encode_picture_b_mref(ks265_frame *f, ks265_pic src, const ks265_pic *
     if ((n0 > 1 || n1 > 1) && (!f->ridx[0] || !f->pu_x[0])) return KS265_NOTSUPPORTED;
     for (int i = 0; i < n0; ++i) if (!refs0[i].y) return KS265_POINTER;
     for (int i = 0; i < n1; ++i) if (!refs1[i].y) return KS265_POINTER;
-    return encode_b_lists(f, src, refs0, n0, refs1, n1, recon_out);
-}
-static int encode_b_lists(ks265_frame *f, ks265_pic src, const ks265_pic *refs0, int n0, const ks265_pic *refs1, int n1, ks265_pic recon_out)
-{
-    const bool mr = n0 > 1 || n1 > 1;                         /* several pictures per list: from the bi-predictive decision on every stage takes a block's pictures from its record */
-    const KsPicLists lists = ks_pic_lists(refs0, n0, refs1, n1, mr, false);
-    int r;
-    ks265_pu *pu0 = f->pu[f->cur_pu];                         /* scratch: the next P picture overwrites it */
-    /* one list's chain: every picture of the list searched and refined, then (several pictures) the per-PU choice */
-    auto chain = [&](int l) -> int {
-        const ks265_pic *refs = l ? refs1 : refs0; const int n = l ? n1 : n0;
-        const ks265_pu *pus[4];
-        int rr = 0;
-        for (int i = 0; i < n && !rr; ++i) {
-            ks265_pu *pu = i == 0 ? (l ? f->pu1 : pu0) : (l ? f->pu1_x[i - 1] : f->pu_x[i - 1]);
-            pus[i] = pu;
-            rr = me_search(f, src, refs[i], nullptr, pu);
-            if (!rr && f->cfg.subme) rr = ks265_me_subpel(f, src, refs[i], pu);
-        }
-        if (!rr && mr) rr = ks265_ref_pick(f, n, pus, l ? f->pu1 : pu0, f->ridx[l]);
-        return rr;
-    };
-    if ((r = search_forked(f, src, true, [&] { return chain(1); }, [&] { return chain(0); }))) return r;   /* list 1's beside list 0's; the join is in front of the bi-predictive decision */
-    if ((r = ks_bi_decide(f, src, lists, pu0, f->pu1, f->pub))) return r;
-    const bool ii = f->cfg.intra_inter != 0;
-    if (ii && (r = ks265_intra_candidates(f, src, f->pub, f->icost))) return r;
-    if ((r = records_fence(f))) return r;
-    const bool part = f->cfg.part != 0;                        /* -part 1: the halves of every 64 / 32 / 16 CU priced with the motions of the CU and of its quarters (round 5: B pictures too) */
-    ks265_cu8 *cud = f->cfg.merge ? f->cu8_tmp : f->cu8;
-    if ((r = part ? ks_cu_decide_part_b(f, src, lists, pu0, f->pu1, f->pub, ii ? f->icost : nullptr, cud) : ks265_cu_decide_b_ii(f, f->pub, ii ? f->icost : nullptr, cud))) return r;
-    if (f->cfg.bi_refine == 2 && (r = ks_bi_refine_chosen(f, src, lists, pu0, f->pu1, f->pub, cud))) return r;   /* the joint refinement, for the CUs the decision chose (round 5) */
-    if (f->cfg.merge && (r = ks_merge_pass(f, src, lists, nullptr, f->pub, f->cu8_tmp, f->cu8))) return r;
-    return inter_back_end(f, src, lists, f->cfg.skip_rd != 0, ii, f->cfg.sao == 0, recon_out, no_mark);
+    return encode_inter(f, KS_B, src, ks_pic_lists(refs0, n0, refs1, n1, n0 > 1 || n1 > 1, false), recon_out);
 }
 
 /* forget the temporal predictors (the next P picture starts like the first one after a key picture): for hosts that code key pictures on another frame object */

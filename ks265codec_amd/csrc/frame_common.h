@@ -111,6 +111,16 @@ static inline KsPicLists ks_pic_lists(const ks265_pic *refs0, int n0, const ks26
     return L;
 }
 static inline KsPicLists ks_pic_lists(ks265_pic ref0, ks265_pic ref1) { return ks_pic_lists(&ref0, 1, &ref1, 1, false, false); }   // one picture per list (ref1 = null picture: P)
+// one plane (0: Y, 1: Cb, 2: Cr) of list l's pictures as a kernel argument (no list 1: its slots repeat list 0's pictures)
+static inline KsRefList ks_ref_list(const KsPicLists &L, int l, int plane)
+{
+    KsRefList r;
+    for (int i = 0; i < 4; ++i) {
+        const ks265_pic p = L.pic[l][i].y ? L.pic[l][i] : L.pic[0][i];
+        r.p[i] = plane == 0 ? p.y : plane == 1 ? p.u : p.v;
+    }
+    return r;
+}
 
 __device__ __forceinline__ const uint8_t *ks_org_y(const KsGeom &g, const uint8_t *p) { return p + g.org_y; }
 __device__ __forceinline__ uint8_t *ks_org_y(const KsGeom &g, uint8_t *p) { return p + g.org_y; }

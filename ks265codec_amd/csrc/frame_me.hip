@@ -9,6 +9,7 @@
 //   Stage C  ks265_cu_decide  : bottom-up quadtree compare.
 #include "frame_common.h"
 #include "interp_dev.h"
+#include "merge_dev.h"
 #include <type_traits>
 
 using namespace ks265;
@@ -100,7 +101,7 @@ __global__ __launch_bounds__(NC * 64, KS_SUBPEL_OCC) void me_subpel_kernel(KsGeo
                                                                                       // block start in different banks (100 dwords = 4 mod 32; unpadded, all of them hit the same); nine pixel columns in phase H's shared form
     if (lane == 0) s_org[wave] = have ? ((ctu % g.ctu_cols) * 64) | (((ctu / g.ctu_cols) * 64) << 16) : 0;
     // Z-order: lane bits (y2 x2 y1 x1 y0 x0)
-    const int tx = (lane & 1) | ((lane >> 1) & 2) | ((lane >> 2) & 4), ty = ((lane >> 1) & 1) | ((lane >> 2) & 2) | ((lane >> 3) & 4);
+    const int tx = ks_z_x(lane), ty = ks_z_y(lane);
     bool valid[4], dosub[4], qrun[4];
     int pidx[4], bx[4], by[4], mvpx[4], mvpy[4], hmx[4], hmy[4];
     unsigned bc[4], bd[4];
@@ -212,7 +213,7 @@ __global__ __launch_bounds__(NC * 64, KS_SUBPEL_OCC) void me_subpel_kernel(KsGeo
             t.ii = blk * 16 + n16;
             const int it = s_item[t.ii < nitems ? t.ii : blk * 16];    // the last block is padded with copies of its first item
             const int il = it & 63, iw = it >> 8, ikey = s_key[iw][(it >> 6) & 3][il], org = s_org[iw];
-            const int itx = (il & 1) | ((il >> 1) & 2) | ((il >> 2) & 4), ity = ((il >> 1) & 1) | ((il >> 2) & 2) | ((il >> 3) & 4);
+            const int itx = ks_z_x(il), ity = ks_z_y(il);
             t.ro = (unsigned)(((org >> 16) + ity * 8 + 2 * gk) * g.sy + (org & 0xFFFF) + itx * 8);   // this lane's two rows of the tile
             t.cx = (int)(short)(ikey & 0xFFFF); t.cy = ikey >> 16;
             const uint2 a0 = *(const uint2 *)(Sp + t.ro), a1 = *(const uint2 *)(Sp + t.ro + (unsigned)g.sy);
@@ -932,7 +933,7 @@ __global__ __launch_bounds__(256, REFINE ? 2 : 1) void bi_decide_kernel(KsGeom g
     const int tid = threadIdx.x, lane = tid & 63, level = tid >> 6;
     const int ctu = ks_xcd_swizzle(blockIdx.x, g.ctu_cols * g.ctu_rows), cx = ctu % g.ctu_cols, cy = ctu / g.ctu_cols;
     const int G = 1 << (2 * (3 - level));
-    const int tx = (lane & 1) | ((lane >> 1) & 2) | ((lane >> 2) & 4), ty = ((lane >> 1) & 1) | ((lane >> 2) & 2) | ((lane >> 3) & 4);
+    const int tx = ks_z_x(lane), ty = ks_z_y(lane);
     const int x0 = cx * 64 + tx * 8, y0 = cy * 64 + ty * 8;
     const int px = tx >> (3 - level), py = ty >> (3 - level), pidx = ks_level_base(level) + py * (1 << level) + px;
     const ks265_pu a = pu0[(long)ctu * 85 + pidx], b = pu1[(long)ctu * 85 + pidx];
@@ -978,7 +979,7 @@ __global__ __launch_bounds__(64, 2) void bi_refine_chosen_kernel(KsGeom g, int l
 {
     const int lane = threadIdx.x;
     const int ctu = ks_xcd_swizzle(blockIdx.x, g.ctu_cols * g.ctu_rows), cx = ctu % g.ctu_cols, cy = ctu / g.ctu_cols;
-    const int tx = (lane & 1) | ((lane >> 1) & 2) | ((lane >> 2) & 4), ty = ((lane >> 1) & 1) | ((lane >> 2) & 2) | ((lane >> 3) & 4);
+    const int tx = ks_z_x(lane), ty = ks_z_y(lane);
     const int x0 = cx * 64 + tx * 8, y0 = cy * 64 + ty * 8, w8 = g.W >> 3;
     const bool inside = x0 < g.W && y0 < g.H;
     ks265_cu8 *const blk = cu8 + (long)(inside ? y0 >> 3 : 0) * w8 + (inside ? x0 >> 3 : 0);
@@ -1016,8 +1017,8 @@ static KsMrefB ks_mref_args(const ks265_frame *f, const KsPicLists &lists)
     KsMrefB m{};
     if (!lists.multi) return m;
     const int n0 = lists.n[0], n1 = lists.n[1];
+    m.y0 = ks_ref_list(lists, 0, 0); m.y1 = ks_ref_list(lists, 1, 0);
     for (int i = 0; i < 4; ++i) {
-        m.y0.p[i] = lists.pic[0][i].y; m.y1.p[i] = lists.pic[1][i].y;
         const int b0 = n0 <= 1 ? 0 : (i < n0 - 1 ? i + 1 : n0 - 1), b1 = n1 <= 1 ? 0 : (i < n1 - 1 ? i + 1 : n1 - 1);
         m.bits0[i] = (f->cfg.lambda_q4 * b0) >> 4; m.bits1[i] = (f->cfg.lambda_q4 * b1) >> 4;
     }
@@ -1081,7 +1082,7 @@ __global__ __launch_bounds__(192) void rect_eval_kernel(KsGeom g, int lam, const
 {
     const int tid = threadIdx.x, lane = tid & 63, l = tid >> 6;                  // l = level of the CU (0: 64, 1: 32, 2: 16)
     const int ctu = ks_xcd_swizzle(blockIdx.x, g.ctu_cols * g.ctu_rows), cx = ctu % g.ctu_cols, cy = ctu / g.ctu_cols;
-    const int tx = (lane & 1) | ((lane >> 1) & 2) | ((lane >> 2) & 4), ty = ((lane >> 1) & 1) | ((lane >> 2) & 2) | ((lane >> 3) & 4);
+    const int tx = ks_z_x(lane), ty = ks_z_y(lane);
     const int x0 = cx * 64 + tx * 8, y0 = cy * 64 + ty * 8;
     const int cux = tx >> (3 - l), cuy = ty >> (3 - l), qx = (tx >> (2 - l)) & 1, qy = (ty >> (2 - l)) & 1;
     const int pidx = ks_level_base(l) + cuy * (1 << l) + cux;
@@ -1167,7 +1168,7 @@ __global__ __launch_bounds__(192) void rect_eval_b_kernel(KsGeom g, int lam, con
 {
     const int tid = threadIdx.x, lane = tid & 63, l = tid >> 6;
     const int ctu = ks_xcd_swizzle(blockIdx.x, g.ctu_cols * g.ctu_rows), cx = ctu % g.ctu_cols, cy = ctu / g.ctu_cols;
-    const int tx = (lane & 1) | ((lane >> 1) & 2) | ((lane >> 2) & 4), ty = ((lane >> 1) & 1) | ((lane >> 2) & 2) | ((lane >> 3) & 4);
+    const int tx = ks_z_x(lane), ty = ks_z_y(lane);
     const int x0 = cx * 64 + tx * 8, y0 = cy * 64 + ty * 8;
     const int cux = tx >> (3 - l), cuy = ty >> (3 - l), qx = (tx >> (2 - l)) & 1, qy = (ty >> (2 - l)) & 1;
     const int pidx = ks_level_base(l) + cuy * (1 << l) + cux;
@@ -1299,30 +1300,6 @@ extern "C" int ks265_cu_decide_part(ks265_frame *f, ks265_pic src, ks265_pic ref
 // against the CU's search cost + 2 lambda.  All CUs decide on the same input field (cu_in -> cu_out): the result does not depend on any order.
 // One work-group per CTU; lane = 8x8 tile in z-order (as in bi_decide), wave w evaluates candidates w and w + 4; a tile's SATD against the (averaged)
 // plane tiles, CU sums by DPP at the CU's own level, the winner per CU through one LDS minimum.
-struct MergeMotion { int dir, mvx, mvy, mv1x, mv1y; bool ok; };
-__device__ __forceinline__ int z_of_8(int x, int y)
-{
-    const int bx = (x >> 3) & 7, by = (y >> 3) & 7;
-    return (bx & 1) | ((by & 1) << 1) | ((bx & 2) << 1) | ((by & 2) << 2) | ((bx & 4) << 2) | ((by & 4) << 3);
-}
-template <bool MR>
-__device__ __forceinline__ MergeMotion merge_cand(const KsGeom &g, const ks265_cu8 *cu_in, int x, int y, int n, int k, bool bi_zero)
-{
-    MergeMotion m; m.dir = bi_zero ? 3 : 1; m.mvx = m.mvy = m.mv1x = m.mv1y = 0; m.ok = true;
-    if (k == 5) return m;
-    const int nx = k == 1 ? x + n - 1 : k == 2 ? x + n : x - 1, ny = k == 0 ? y + n - 1 : k == 3 ? y + n : y - 1;       // A1 B1 B0 A0 B2
-    m.ok = false;
-    if (nx < 0 || ny < 0 || nx >= g.W || ny >= g.H) return m;
-    const int ctb = (y >> 6) * g.ctu_cols + (x >> 6), nctb = (ny >> 6) * g.ctu_cols + (nx >> 6);
-    if (nctb > ctb || (nctb == ctb && z_of_8(nx, ny) >= z_of_8(x, y))) return m;
-    const ks265_cu8 c = cu_in[(long)(ny >> 3) * g.w8 + (nx >> 3)];
-    if (c.pred_mode != 0 || (c.log2_cu & 15) < 3) return m;
-    m.dir = MR ? (int)c.inter_dir : (c.inter_dir & 3); m.mvx = c.mvx; m.mvy = c.mvy; m.mv1x = c.mv1x; m.mv1y = c.mv1y; m.ok = true;      // (MR: the neighbour's pictures come with its motion)
-    // a neighbour's vector may come from a CTU with another window offset: taken over here it must keep this CU's block inside the planes' margin
-    if ((m.dir & 1) && (x + (m.mvx >> 2) < -70 || x + (m.mvx >> 2) + n > g.W + 70 || y + (m.mvy >> 2) < -70 || y + (m.mvy >> 2) + n > g.H + 70)) m.ok = false;
-    if ((m.dir & 2) && (x + (m.mv1x >> 2) < -70 || x + (m.mv1x >> 2) + n > g.W + 70 || y + (m.mv1y >> 2) < -70 || y + (m.mv1y >> 2) + n > g.H + 70)) m.ok = false;
-    return m;
-}
 template <bool MR>
 __global__ __launch_bounds__(256) void merge_pass_kernel(KsGeom g, int lam, const uint8_t *src, const uint8_t *ref0, const uint8_t *ref1, const ks265_pu *pu,
                                                          const ks265_pu_b *pub, const ks265_cu8 *cu_in, ks265_cu8 *cu_out, const KsMrefB mr, int p_slice)
@@ -1330,7 +1307,7 @@ __global__ __launch_bounds__(256) void merge_pass_kernel(KsGeom g, int lam, cons
     __shared__ unsigned long long jbest[64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int ctu = ks_xcd_swizzle(blockIdx.x, g.ctu_cols * g.ctu_rows), cx = ctu % g.ctu_cols, cy = ctu / g.ctu_cols;
-    const int tx = (lane & 1) | ((lane >> 1) & 2) | ((lane >> 2) & 4), ty = ((lane >> 1) & 1) | ((lane >> 2) & 2) | ((lane >> 3) & 4);
+    const int tx = ks_z_x(lane), ty = ks_z_y(lane);
     const int x0 = cx * 64 + tx * 8, y0 = cy * 64 + ty * 8;
     const bool inside = x0 < g.W && y0 < g.H, is_b = pub != nullptr, bi_zero = is_b && !p_slice;   // (p_slice: the two-list records of a multi-reference P picture - the zero candidate has one list)
     ks265_cu8 c;
@@ -1347,19 +1324,15 @@ __global__ __launch_bounds__(256) void merge_pass_kernel(KsGeom g, int lam, cons
     // with four or fewer of them (the usual case: neighbours share vectors) no wave does a second evaluation
     unsigned mask = 0, distinct = 0;
     {
-        MergeMotion mm[6];
+        KsMotion mm[6];
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
-            mm[k] = merge_cand<MR>(g, cu_in, cux, cuy, n, k, bi_zero);
+            mm[k] = ks_merge_cand<MR>(g, cu_in, cux, cuy, n, k, bi_zero);
             const bool ok = valid && mm[k].ok;
             mask |= (ok ? 1u : 0u) << k;
             bool rep = false;
 #pragma unroll
-            for (int j = 0; j < k; ++j) {
-                const bool same = mm[j].dir == mm[k].dir && (!(mm[k].dir & 1) || (mm[j].mvx == mm[k].mvx && mm[j].mvy == mm[k].mvy)) &&
-                                  (!(mm[k].dir & 2) || (mm[j].mv1x == mm[k].mv1x && mm[j].mv1y == mm[k].mv1y));
-                rep |= ((mask >> j) & 1u) && same;
-            }
+            for (int j = 0; j < k; ++j) rep |= ((mask >> j) & 1u) && ks_motion_same(mm[j], mm[k]);
             distinct |= (ok && !rep ? 1u : 0u) << k;
         }
     }
@@ -1377,7 +1350,7 @@ __global__ __launch_bounds__(256) void merge_pass_kernel(KsGeom g, int lam, cons
         int k = 0;                                                     // the it-th distinct candidate of this lane's CU
         { unsigned d = distinct; for (int q = 0; q < it; ++q) d &= d - 1u; k = d ? __ffs((int)d) - 1 : 0; }
         const bool on = __popc(distinct) > it;
-        const MergeMotion m = merge_cand<MR>(g, cu_in, cux, cuy, n, k, bi_zero);
+        const KsMotion m = ks_merge_cand<MR>(g, cu_in, cux, cuy, n, k, bi_zero);
         const int ax = on ? m.mvx : 0, ay = on ? m.mvy : 0, bx = on ? m.mv1x : 0, by = on ? m.mv1y : 0, dir = on ? m.dir : 1;
         unsigned sd = 0;
         if (__any(on)) {
@@ -1408,7 +1381,7 @@ __global__ __launch_bounds__(256) void merge_pass_kernel(KsGeom g, int lam, cons
         if (valid) {
             const unsigned long long jb = jbest[leader], jc = (unsigned long long)cur + (unsigned long long)((lam * 32) >> 4);
             if ((jb >> 8) < jc) {
-                const MergeMotion m = merge_cand<MR>(g, cu_in, cux, cuy, n, (int)(jb & 255ull), bi_zero);
+                const KsMotion m = ks_merge_cand<MR>(g, cu_in, cux, cuy, n, (int)(jb & 255ull), bi_zero);
                 o.mvx = (int16_t)m.mvx; o.mvy = (int16_t)m.mvy; o.mv1x = (int16_t)m.mv1x; o.mv1y = (int16_t)m.mv1y; o.inter_dir = (uint8_t)(MR ? m.dir : (m.dir & 3));
             }
         }

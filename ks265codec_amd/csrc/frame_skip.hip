@@ -3,7 +3,7 @@
 // enc@0x482990 under processCuMdInter enc@0x485800: closed code).  The CU tree and the merge pass judge on Hadamard cost + rate, which cannot know what a residual costs and
 // what it buys.  This pass runs AFTER the reconstruction of the inter CUs, where both sides of the comparison exist.  Every inter CU that carries residual:
 //   J_cur  = SSE(source, reconstruction) of Y + 4 (Cb + Cr)  +  lambda x (bits of the CU's levels + 6)
-//   J_skip = min over the first two DISTINCT merge candidates k (of A1 B1 B0 A0 B2 of H.265 8.5.3.2.3 + the zero vector; from a snapshot of the CU map, as in the merge pass:
+//   J_skip = min over the first two DISTINCT merge candidates k (of A1 B1 B0 A0 B2 of H.265 8.5.3.2.3 + the zero vector, merge_dev.h; from a snapshot of the CU map:
 //            no order between CUs or CTUs)  of  SSE(source, prediction with k's motion)  +  lambda x (1 + position of k) bits
 // J_skip < J_cur: the CU becomes a 2Nx2N CU without residual carrying k's motion - levels cleared, reconstruction = the prediction (exactly what the decoder predicts).
 // Bits of levels as the coefficient-group pruning prices them (rdo_level_q2 + 10 + 16 - n per 4x4 group, quarter bits); lambda = 1.5 (lambda_q4 / 16)^2, so
@@ -12,6 +12,7 @@
 #include "frame_common.h"
 #include "pred_dev.h"
 #include "interp_dev.h"
+#include "merge_dev.h"
 
 using namespace ks265;
 
@@ -25,37 +26,17 @@ using namespace ks265;
 #define SP_CHROMA_W 16          // weight of the chroma distortion in quarters
 #define SP_CANDS 2              // distinct candidates tried
 
-struct KsSkipRefs { const uint8_t *y0[4], *u0[4], *v0[4], *y1[4], *u1[4], *v1[4]; };
-struct SpMotion { int dir8, mvx, mvy, mv1x, mv1y; bool ok; };
+struct KsSkipRefs { KsRefList y0, u0, v0, y1, u1, v1; };          // the planes of the two lists' pictures
 
-__device__ __forceinline__ const uint8_t *sp_pick(const uint8_t *const (&p)[4], int i) { return i == 0 ? p[0] : (i == 1 ? p[1] : (i == 2 ? p[2] : p[3])); }
-__device__ __forceinline__ int sp_z_of_8(int x, int y)
-{
-    const int bx = (x >> 3) & 7, by = (y >> 3) & 7;
-    return (bx & 1) | ((by & 1) << 1) | ((bx & 2) << 1) | ((by & 2) << 2) | ((bx & 4) << 2) | ((by & 4) << 3);
-}
-// candidate k of the node (x, y, n) from the snapshot: A1 B1 B0 A0 B2, 5 = zero.  Vectors of lists the motion does not use are 0; MR: the neighbour's pictures come with its motion
+// candidate k of the node (x, y, n) from the snapshot (merge_dev.h), as this pass codes it: the vectors of lists the motion does not use are 0 - in the record and in the prediction
 template <bool MR>
-__device__ __forceinline__ SpMotion sp_cand(const KsGeom &g, const ks265_cu8 *snap, int x, int y, int n, int k, bool bi_zero)
+__device__ __forceinline__ KsMotion sp_cand(const KsGeom &g, const ks265_cu8 *snap, int x, int y, int n, int k, bool bi_zero)
 {
-    SpMotion m; m.dir8 = bi_zero ? 3 : 1; m.mvx = m.mvy = m.mv1x = m.mv1y = 0; m.ok = true;
-    if (k == 5) return m;
-    const int nx = k == 1 ? x + n - 1 : k == 2 ? x + n : x - 1, ny = k == 0 ? y + n - 1 : k == 3 ? y + n : y - 1;
-    m.ok = false;
-    if (nx < 0 || ny < 0 || nx >= g.W || ny >= g.H) return m;
-    const int ctb = (y >> 6) * g.ctu_cols + (x >> 6), nctb = (ny >> 6) * g.ctu_cols + (nx >> 6);
-    if (nctb > ctb || (nctb == ctb && sp_z_of_8(nx, ny) >= sp_z_of_8(x, y))) return m;
-    const ks265_cu8 c = snap[(long)(ny >> 3) * g.w8 + (nx >> 3)];
-    if (c.pred_mode != 0 || (c.log2_cu & 15) < 3) return m;
-    m.dir8 = MR ? (int)c.inter_dir : (c.inter_dir & 3);
-    const int dir = m.dir8 & 3;
-    m.mvx = (dir & 1) ? c.mvx : 0; m.mvy = (dir & 1) ? c.mvy : 0; m.mv1x = (dir & 2) ? c.mv1x : 0; m.mv1y = (dir & 2) ? c.mv1y : 0;
-    m.ok = true;
-    if ((dir & 1) && (x + (c.mvx >> 2) < -70 || x + (c.mvx >> 2) + n > g.W + 70 || y + (c.mvy >> 2) < -70 || y + (c.mvy >> 2) + n > g.H + 70)) m.ok = false;
-    if ((dir & 2) && (x + (c.mv1x >> 2) < -70 || x + (c.mv1x >> 2) + n > g.W + 70 || y + (c.mv1y >> 2) < -70 || y + (c.mv1y >> 2) + n > g.H + 70)) m.ok = false;
+    KsMotion m = ks_merge_cand<MR>(g, snap, x, y, n, k, bi_zero);
+    if (!(m.dir & 1)) m.mvx = m.mvy = 0;
+    if (!(m.dir & 2)) m.mv1x = m.mv1y = 0;
     return m;
 }
-__device__ __forceinline__ bool sp_same(const SpMotion &a, const SpMotion &b) { return a.dir8 == b.dir8 && a.mvx == b.mvx && a.mvy == b.mvy && a.mv1x == b.mv1x && a.mv1y == b.mv1y; }
 
 // ---- the prediction of a lane's samples.  Every input row is filtered horizontally once and feeds all output rows that tap it (interp_dev.h's scheme), in RAW form so that
 // uni- and bi-prediction share it:   kind 0: v = sample   1: one filter pass, v = tap sum (scale 64)   2: both passes, v = vertical taps over the 16-bit horizontal sums.
@@ -159,9 +140,9 @@ __device__ __forceinline__ int sp_chroma_raw(const uint8_t *p, long st, int fx, 
     return hor ? 2 : 1;
 }
 // a lane's luma samples (4 rows x 8, packed) for the motion m: pA = the picture of the list a uni-directional motion uses (list 0's for bi), pB = list 1's picture (bi)
-__device__ __forceinline__ void sp_pred_luma(const uint8_t *pA, const uint8_t *pB, long st, int X, int Y, const SpMotion &m, uint2 (&out)[4])
+__device__ __forceinline__ void sp_pred_luma(const uint8_t *pA, const uint8_t *pB, long st, int X, int Y, const KsMotion &m, uint2 (&out)[4])
 {
-    const int dir = m.dir8 & 3;
+    const int dir = m.dir & 3;
     const int ax = (dir & 1) ? m.mvx : m.mv1x, ay = (dir & 1) ? m.mvy : m.mv1y;
     int v[4][8];
     const int k = sp_luma_raw(pA + (long)(Y + (ay >> 2)) * st + X + (ax >> 2), st, ax & 3, ay & 3, v);
@@ -195,9 +176,9 @@ __device__ __forceinline__ void sp_pred_luma(const uint8_t *pA, const uint8_t *p
         out[r] = ks_pack_row8(px);
     }
 }
-__device__ __forceinline__ void sp_pred_chroma(const uint8_t *pA, const uint8_t *pB, long st, int X, int Y, const SpMotion &m, unsigned (&out)[4])
+__device__ __forceinline__ void sp_pred_chroma(const uint8_t *pA, const uint8_t *pB, long st, int X, int Y, const KsMotion &m, unsigned (&out)[4])
 {
-    const int dir = m.dir8 & 3;
+    const int dir = m.dir & 3;
     const int ax = (dir & 1) ? m.mvx : m.mv1x, ay = (dir & 1) ? m.mvy : m.mv1y;
     int v[4][4];
     const int k = sp_chroma_raw(pA + (long)(Y + (ay >> 3)) * st + X + (ax >> 3), st, ax & 7, ay & 7, v);
@@ -248,7 +229,7 @@ __global__ __launch_bounds__(128, KS_SKIP_OCC) void skip_pass_kernel(KsGeom g, l
     __shared__ unsigned keep[12][128];                             // the winning candidate's samples of every lane (lane-private columns: no hand-over between lanes)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, z = tid >> 1, sub = tid & 1;
     const int ctu = ks_xcd_swizzle(blockIdx.x, g.ctu_cols * g.ctu_rows), cx = ctu % g.ctu_cols, cy = ctu / g.ctu_cols;
-    const int tx = (z & 1) | ((z >> 1) & 2) | ((z >> 2) & 4), ty = ((z >> 1) & 1) | ((z >> 2) & 2) | ((z >> 3) & 4);
+    const int tx = ks_z_x(z), ty = ks_z_y(z);
     const int x0 = cx * 64 + tx * 8, y0 = cy * 64 + ty * 8;                // the lane's tile
     const bool inside = x0 < g.W && y0 < g.H, bi_zero = bi_zero_ != 0;
     ks265_cu8 c;
@@ -257,7 +238,8 @@ __global__ __launch_bounds__(128, KS_SKIP_OCC) void skip_pass_kernel(KsGeom g, l
     const int log2c = c.log2_cu & 15;
     const bool inter = inside && c.pred_mode == 0 && log2c >= 3;
     int slot = 0;
-    // sum of v over the lanes of the lane's CU (called by all lanes of the work-group: the 64x64 case goes through LDS)
+    // sum of v over the lanes of the lane's CU.  It holds a barrier (the 64x64 case goes through LDS) and cross-lane reads: every call is reached by all 128 lanes, on every
+    // path - never behind a lane's own condition; a lane with nothing to add passes 0
     auto cusum = [&](unsigned v) -> unsigned {
         const unsigned s3 = v + (unsigned)__shfl_xor((int)v, 1, 64);
         unsigned s2 = s3 + (unsigned)__shfl_xor((int)s3, 2, 64); s2 += (unsigned)__shfl_xor((int)s2, 4, 64);
@@ -270,7 +252,8 @@ __global__ __launch_bounds__(128, KS_SKIP_OCC) void skip_pass_kernel(KsGeom g, l
         return log2c >= 6 ? s0 : log2c == 5 ? s1 : log2c == 4 ? s2 : s3;
     };
     const int n = inter ? 1 << log2c : 8, cux = x0 & ~(n - 1), cuy = y0 & ~(n - 1);     // the lane's CU
-    const bool eval = inter && cusum((inter && sub == 0 && c.cbf) ? 1u : 0u) != 0;      // an inter CU with residual
+    const unsigned nres = cusum((inter && sub == 0 && c.cbf) ? 1u : 0u);
+    const bool eval = inter && nres != 0;                                               // an inter CU with residual
     // the lane's samples: luma rows 4 sub .. 4 sub + 3 of the tile, the 4x4 block of Cb (sub 0) or Cr (sub 1)
     const uint8_t *Sy = ks_org_y(g, src_y), *Sc = ks_org_c(g, sub ? src_v : src_u);
     uint8_t *Ry = ks_org_y(g, rec_y), *Rc = ks_org_c(g, sub ? rec_v : rec_u);
@@ -304,7 +287,7 @@ __global__ __launch_bounds__(128, KS_SKIP_OCC) void skip_pass_kernel(KsGeom g, l
     // ---- the candidates: which exist, their positions, which repeat an earlier one; the first SP_CANDS distinct ones are tried
     unsigned valid = 0, distinct = 0;
     {
-        SpMotion mm[6];
+        KsMotion mm[6];
         int nd = 0;
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
@@ -312,7 +295,7 @@ __global__ __launch_bounds__(128, KS_SKIP_OCC) void skip_pass_kernel(KsGeom g, l
             const bool ok = eval && mm[k].ok;
             bool rep = false;
 #pragma unroll
-            for (int j = 0; j < k; ++j) rep |= ((valid >> j) & 1u) && sp_same(mm[j], mm[k]);
+            for (int j = 0; j < k; ++j) rep |= ((valid >> j) & 1u) && ks_motion_same(mm[j], mm[k]);
             valid |= (ok ? 1u : 0u) << k;
             if (ok && !rep && nd < SP_CANDS) { distinct |= 1u << k; ++nd; }
         }
@@ -320,9 +303,9 @@ __global__ __launch_bounds__(128, KS_SKIP_OCC) void skip_pass_kernel(KsGeom g, l
     unsigned long long best = jcur;
     int bestk = -1;
     // the lane's prediction for the motion of candidate k (a lane that is not `on` gets the zero vector of list 0: valid addresses, result unused)
-    auto motion_of = [&](bool on, int k) -> SpMotion {
-        SpMotion m = sp_cand<MR>(g, snap, cux, cuy, n, k, bi_zero);
-        if (!on) { m.dir8 = 1; m.mvx = m.mvy = m.mv1x = m.mv1y = 0; }
+    auto motion_of = [&](bool on, int k) -> KsMotion {
+        KsMotion m = sp_cand<MR>(g, snap, cux, cuy, n, k, bi_zero);
+        if (!on) { m.dir = 1; m.mvx = m.mvy = m.mv1x = m.mv1y = 0; }
         return m;
     };
 #pragma unroll 1
@@ -331,14 +314,14 @@ __global__ __launch_bounds__(128, KS_SKIP_OCC) void skip_pass_kernel(KsGeom g, l
         if (!__syncthreads_or(on ? 1 : 0)) break;                  // nobody in the CTU has that many candidates
         int k = 0;
         { unsigned d = distinct; for (int i = 0; i < it; ++i) d &= d - 1u; k = d ? __ffs((int)d) - 1 : 0; }
-        const SpMotion m = motion_of(on, k);
-        const int dir = m.dir8 & 3, i0 = MR ? (m.dir8 >> 4) & 3 : 0, i1 = MR ? (m.dir8 >> 6) & 3 : 0;
+        const KsMotion m = motion_of(on, k);
+        const int dir = m.dir & 3, i0 = MR ? (m.dir >> 4) & 3 : 0, i1 = MR ? (m.dir >> 6) & 3 : 0;
         unsigned eY = 0;
         uint2 pY[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) pY[r] = make_uint2(0u, 0u);
         if (__any(on)) {
-            sp_pred_luma(ks_org_y(g, (dir & 1) ? sp_pick(R.y0, i0) : sp_pick(R.y1, i1)), ks_org_y(g, sp_pick(R.y1, i1)), g.sy, lx, ly, m, pY);
+            sp_pred_luma(ks_org_y(g, (dir & 1) ? ks_pick(R.y0, i0) : ks_pick(R.y1, i1)), ks_org_y(g, ks_pick(R.y1, i1)), g.sy, lx, ly, m, pY);
 #pragma unroll
             for (int r = 0; r < 4; ++r) eY += sp_sse4(sY[r].x, pY[r].x) + sp_sse4(sY[r].y, pY[r].y);
         }
@@ -351,8 +334,8 @@ __global__ __launch_bounds__(128, KS_SKIP_OCC) void skip_pass_kernel(KsGeom g, l
         unsigned eC = 0;
         unsigned pC[4] = {0u, 0u, 0u, 0u};
         if (__any(need_c)) {
-            sp_pred_chroma(ks_org_c(g, (dir & 1) ? (sub ? sp_pick(R.v0, i0) : sp_pick(R.u0, i0)) : (sub ? sp_pick(R.v1, i1) : sp_pick(R.u1, i1))),
-                           ks_org_c(g, sub ? sp_pick(R.v1, i1) : sp_pick(R.u1, i1)), g.sc, cxx, cyy, m, pC);
+            sp_pred_chroma(ks_org_c(g, (dir & 1) ? (sub ? ks_pick(R.v0, i0) : ks_pick(R.u0, i0)) : (sub ? ks_pick(R.v1, i1) : ks_pick(R.u1, i1))),
+                           ks_org_c(g, sub ? ks_pick(R.v1, i1) : ks_pick(R.u1, i1)), g.sc, cxx, cyy, m, pC);
 #pragma unroll
             for (int r = 0; r < 4; ++r) eC += sp_sse4(sC[r], pC[r]);
         }
@@ -368,7 +351,7 @@ __global__ __launch_bounds__(128, KS_SKIP_OCC) void skip_pass_kernel(KsGeom g, l
     }
     // ---- a CU that drops its residual: its lanes write the samples they kept and clear their levels, the tile's first lane the record
     if (bestk >= 0) {
-        const SpMotion m = sp_cand<MR>(g, snap, cux, cuy, n, bestk, bi_zero);
+        const KsMotion m = sp_cand<MR>(g, snap, cux, cuy, n, bestk, bi_zero);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             *(uint2 *)(Ry + (long)(ly + r) * g.sy + lx) = make_uint2(keep[2 * r][tid], keep[2 * r + 1][tid]);
@@ -379,7 +362,7 @@ __global__ __launch_bounds__(128, KS_SKIP_OCC) void skip_pass_kernel(KsGeom g, l
         if (sub == 0) {
             ks265_cu8 o;
             o.mvx = (int16_t)m.mvx; o.mvy = (int16_t)m.mvy; o.mv1x = (int16_t)m.mv1x; o.mv1y = (int16_t)m.mv1y;
-            o.log2_cu = (uint8_t)log2c; o.cbf = 0; o.pred_mode = 0; o.inter_dir = (uint8_t)m.dir8;
+            o.log2_cu = (uint8_t)log2c; o.cbf = 0; o.pred_mode = 0; o.inter_dir = (uint8_t)m.dir;
             cu8[(long)(y0 >> 3) * g.w8 + (x0 >> 3)] = o;
         }
     }
@@ -396,11 +379,7 @@ int ks_skip_pass(ks265_frame *f, ks265_pic src, const KsPicLists &lists, ks265_c
     int r = ks265_hip(f->ctx, hipMemcpyAsync(f->cu8_tmp, dev_cu8, (size_t)f->geom.bytes_cu8, hipMemcpyDeviceToDevice, f->ctx->stream));
     if (r) return r;
     const bool is_b = !lists.pslice && lists.pic[1][0].y != nullptr;       // the slice has a list 1
-    KsSkipRefs R;
-    for (int i = 0; i < 4; ++i) {
-        const ks265_pic a = lists.pic[0][i], b = lists.pic[1][i].y ? lists.pic[1][i] : a;      // (no list 1: its slots repeat list 0's picture)
-        R.y0[i] = a.y; R.u0[i] = a.u; R.v0[i] = a.v; R.y1[i] = b.y; R.u1[i] = b.u; R.v1[i] = b.v;
-    }
+    const KsSkipRefs R = {ks_ref_list(lists, 0, 0), ks_ref_list(lists, 0, 1), ks_ref_list(lists, 0, 2), ks_ref_list(lists, 1, 0), ks_ref_list(lists, 1, 1), ks_ref_list(lists, 1, 2)};
     const long long lam2 = ((long long)f->cfg.lambda_q4 * f->cfg.lambda_q4 * SP_LAMBDA_Q4) >> 4;
     const int nctu = f->g.ctu_cols * f->g.ctu_rows;
     if (lists.multi) hipLaunchKernelGGL(skip_pass_kernel<true>, dim3(nctu), dim3(128), 0, f->ctx->stream, f->g, lam2, is_b ? 1 : 0, src.y, src.u, src.v, R, f->cu8_tmp, dev_cu8, dev_lvl_y, dev_lvl_u, dev_lvl_v, recon.y, recon.u, recon.v);
