@@ -30,6 +30,7 @@
  *     them and codes sao_merge_left_flag / sao_merge_up_flag instead of its parameters; "0" leaves sao as it is.  No preset selects it;
  *   - calcSsim (-ssim 1 | 2): the reference's ` ssim:` line behind `bitrate, psnr:` (8x8 windows), computed on the device in the same pass as the SSE; 2 adds one
  *     `ks265enc: poc N ssim Y U V` line per picture (the reference prints nothing per picture); totals and the last picture's values: ks265_enc_get_quality;
+ *   - hash (not in the SDK; ks265_enc_set_default "hash" = `-hash N`, below): a decoded picture hash SEI message behind every picture, CRC or checksum, computed on the device;
  *   - transskip, tuIntra, vpp_*, 2-pass, long-term references, VBV / CVQ: accepted, ignored;
  *   - input pictures: the caller's planes are pinned in place and uploaded from where they lie inside QY265EncoderEncodeFrame; the caller may reuse its buffers when the call returns
  *     (the SDK requires them to stay valid until the frame is done);
@@ -135,6 +136,15 @@ int ks265_enc_lanes(void *pEncoder);
  * QP ladder and lambda, rate control, lookahead / cuTree, scene cuts, -aq, GOP lanes; it keeps the full tool set and runs without the skip pass like a P picture.
  * QY265Picture.iSliceType and the -psnr 2 lines report it as the stream does: B.  The switch is accepted and does nothing where no anchor searches two anchors: -bframes 0,
  * zero latency, -ref0 1, and P + n plain B pictures (whose anchors keep one reference); there the stream is byte for byte the one without it.  Measured: DESIGN.md 5d. */
+/* "hash" (x265's numbering: 0 = off, the default; 2 = CRC; 3 = checksum; the environment's KS265_HASH overrides it at QY265EncoderOpen; `ks265enc -hash N`): every coded picture
+ * is followed by a suffix SEI NAL unit (type 40) with its decoded picture hash message (H.265 D.2.19 / D.3.19, payload type 132; hash_type 1 = picture_crc, 2 =
+ * picture_checksum of the three planes of the output picture), so that any decoder can verify its output against this encoder's reconstruction.  1 (MD5) and every other value:
+ * QY265_PARAM_BAD_VALUE - MD5 is sequential over a plane, which means the whole picture on the host and one thread hashing it; that remains what "md5" does, for log lines.
+ * CRC and checksum are computed by one kernel launch that reads the output picture once (ks265_picture_hash); 24 bytes come home per picture.  The switch works
+ * with GOP lanes and several GPUs (the message travels with its picture; any number of lanes gives the same bytes) and does not bring the reconstruction to the host.
+ * QY265EncoderEncodeFrame hands the message out as one more QY265Nal (naltype 40) behind the picture's, with its pts.  ks265_enc_stats.bytes and the bitrate lines count it; the
+ * rate controllers and the -rdoq tables do not: for every -rc mode the stream minus its type-40 NAL units is byte for byte the stream without the switch.  On a device library
+ * without the pass the encoder logs `ks265enc: picture hash is unavailable: ...` once and writes no messages. */
 int ks265_enc_set_default(const char *name, int value);
 /* extension: zero-copy input.  Fills `yuv` with the planes of one of the encoder's pinned input buffers (packed I420, strides = width, width / 2); the caller writes the
  * next picture there and passes the same QY265YUV to QY265EncoderEncodeFrame, which then copies nothing (0.35 ms of the calling thread per 2160p picture otherwise).

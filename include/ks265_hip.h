@@ -620,6 +620,12 @@ int ks265_sse_picture_on(ks265_ctx *cx, ks265_frame *f, ks265_pic a, ks265_pic b
  * NULL) what ks265_sse_picture gives, bit for bit: the pictures are read once for both. */
 int ks265_ssim_picture(ks265_frame *f, ks265_pic a, ks265_pic b, uint64_t *dev_sse3, int64_t *dev_ssim3);
 int ks265_ssim_picture_on(ks265_ctx *cx, ks265_frame *f, ks265_pic a, ks265_pic b, uint64_t *dev_sse3, int64_t *dev_ssim3);
+/* the decoded picture hash of a padded picture (H.265 D.3.19, 8-bit 4:2:0): dev_hash6[0..2] = picture_crc of Y, Cb, Cr (CRC-16, polynomial 0x1021, preset
+ * 0xFFFF, two zero bytes appended), dev_hash6[3..5] = picture_checksum of Y, Cb, Cr (sum of sample ^ (x & 0xFF) ^ (y & 0xFF) ^ (x >> 8) ^ (y >> 8) modulo 2^32), over the
+ * W x H / W/2 x H/2 samples inside the padding.  One launch that reads the picture once; XOR and 32-bit adds only, so the result does not depend on the order the work-groups
+ * finish in; the accumulators live in the frame object and are left zeroed (no memset launch).  _on: on another context's stream. */
+int ks265_picture_hash(ks265_frame *f, ks265_pic p, uint32_t *dev_hash6);
+int ks265_picture_hash_on(ks265_ctx *cx, ks265_frame *f, ks265_pic p, uint32_t *dev_hash6);
 
 #ifdef __cplusplus
 }

@@ -38,7 +38,7 @@ typedef struct {
 
 enum { KS265_SLICE_B = 0, KS265_SLICE_P = 1, KS265_SLICE_I = 2 };
 enum { KS265_NAL_TRAIL_N = 0, KS265_NAL_TRAIL_R = 1, KS265_NAL_IDR_W_RADL = 19, KS265_NAL_IDR_N_LP = 20, KS265_NAL_CRA = 21,
-       KS265_NAL_VPS = 32, KS265_NAL_SPS = 33, KS265_NAL_PPS = 34 };
+       KS265_NAL_VPS = 32, KS265_NAL_SPS = 33, KS265_NAL_PPS = 34, KS265_NAL_SUFFIX_SEI = 40 };
 
 /* one picture = one slice segment */
 typedef struct {
@@ -71,6 +71,10 @@ typedef struct {
 long ks265_write_vps(const ks265_stream_cfg *cfg, uint8_t *out, size_t cap);
 long ks265_write_sps(const ks265_stream_cfg *cfg, uint8_t *out, size_t cap);
 long ks265_write_pps(const ks265_stream_cfg *cfg, uint8_t *out, size_t cap);
+/* The decoded picture hash SEI message of one picture (H.265 D.2.19 / D.3.19, payload type 132) as one suffix SEI NAL unit (KS265_NAL_SUFFIX_SEI, layer 0, temporal id 0), to
+ * follow the picture's slice NAL unit: hash_type 1 = picture_crc (value[c] & 0xFFFF, u(16)), 2 = picture_checksum (u(32)), c = Y, Cb, Cr; 13 / 19 bytes before emulation
+ * prevention.  Any other hash_type (0 = MD5 included): KS265_NOTSUPPORTED. */
+long ks265_write_picture_hash_sei(int hash_type, const uint32_t value[3], uint8_t *out, size_t cap);
 /* One coded picture (slice segment header + CABAC slice data) as one Annex-B NAL unit.  Thread-safe (no shared state): pictures of a
  * GOP can be written concurrently by different host threads, each into its own buffer.  `scratch` must hold ks265_slice_scratch_bytes()
  * bytes. */

@@ -53,6 +53,7 @@ struct ks265_frame {
     unsigned long long *sse = nullptr;
     unsigned long long *sse_acc = nullptr;   // ks265_sse_picture: three running sums + finished work-groups (zero between calls)
     unsigned long long *ssim_acc = nullptr;  // ks265_ssim_picture: [0..2] SSE sums, [3..5] fixed-point SSIM sums, [6] finished work-groups (zero between calls)
+    unsigned *hash_acc = nullptr;            // ks265_picture_hash: [0..2] CRC parts, [3..5] checksums, [6] finished work-groups (zero between calls)
     short *mats = nullptr;              // forward + transposed DCT matrices of all sizes in the kernels' LDS layout (2 x MAT_SHORTS)
     int *progress = nullptr;            // intra wavefront: z-count per CTU (intra_deps.h), then the key pictures' CTU ticket
     const int8_t *qp_map = nullptr;      // round 4: one QP per CTU (ks265_frame_set_qp_map; null = cfg.qp everywhere), device memory of the host

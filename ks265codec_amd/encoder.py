@@ -8,7 +8,9 @@
 
 The encoder reads each tensor in the order of torch's current stream and makes that stream wait until it has: the caller may overwrite the tensor with further work on the
 same stream as soon as encode() returns, with no host synchronisation.  Parameters are QY265ConfigParse names (qp, crf, rc, iper, bframes, lookahead, latency, ...);
-gpb=0|1 is the process default of that name (ks265_enc_set_default: anchors that search two or more past anchors as B slices over them), set before this handle opens."""
+gpb=0|1 is the process default of that name (ks265_enc_set_default: anchors that search two or more past anchors as B slices over them), set before this handle opens.
+hash=2|3 writes a decoded picture hash SEI message (CRC / checksum, computed on the device) behind every picture of THIS handle; the bytes come out of encode() / flush() with the
+picture's."""
 from __future__ import annotations
 
 import ctypes as C
@@ -119,12 +121,17 @@ class Encoder:
         gpb = params.pop("gpb", None)                           # no QY265EncConfig field: a process default (None leaves it as it is)
         if gpb is not None and self.lib.ks265_enc_set_default(b"gpb", C.c_int(int(gpb))) != 0:
             raise ValueError(f"parameter gpb={gpb!r}: bad value")
+        hash_ = params.pop("hash", None)                        # `hash` (ks265_enc.h): for this handle alone - the process default goes back to off once the handle is open
+        if hash_ is not None and self.lib.ks265_enc_set_default(b"hash", C.c_int(int(hash_))) != 0:
+            raise ValueError(f"parameter hash={hash_!r}: bad value (0, 2 = CRC, 3 = checksum)")
         for k, v in (("wdt", width), ("hgt", height), *params.items()):
             rc = self.lib.QY265ConfigParse(self._cfg, str(k).replace("_", "-").encode(), str(v).encode())   # keyword form of the names with a dash: sao_ref=2 -> "sao-ref"
             if rc != 0:
                 raise ValueError(f"parameter {k}={v!r}: {'unknown name' if rc == -1 else 'bad value'}")
         err = C.c_int(0)
         self.h = self.lib.QY265EncoderOpen(self._cfg, C.byref(err))
+        if hash_ is not None:
+            self.lib.ks265_enc_set_default(b"hash", C.c_int(0))
         if not self.h:
             raise EncoderError("QY265EncoderOpen", err.value)
         rc = self.lib.ks265_enc_enable_device_input(self.h)

@@ -34,6 +34,10 @@
  * and prints no ` ssim:` line */
 #pragma weak ks265_ssim_picture
 #pragma weak ks265_ssim_picture_on
+/* `hash` (decoded picture hash SEI messages) reaches the hash pass the same way: on a device library without it the encoder logs once that the picture hash is unavailable
+ * and writes the stream it writes without the switch */
+#pragma weak ks265_picture_hash
+#pragma weak ks265_picture_hash_on
 /* `gpb` switches the skip pass off for its anchors the same way: a device library without the setter - the stand-in has no skip pass - is not asked */
 #pragma weak ks265_frame_set_picture_skip
 
@@ -88,7 +92,7 @@ static void md5_hex(const uint8_t *data, size_t n, char out[33])
 
 /* CLI-level switches of `appencoder` that the SDK's QY265EncConfig has no field for (-df, -fixqp, -md5): process-wide defaults a front end
  * sets before QY265EncoderOpen (ks265_enc_set_default) */
-static struct { int df, fixqp, md5, scenecut, cutree, gpb; } g_cli = {1, 0, 0, 0, 1, 0};
+static struct { int df, fixqp, md5, scenecut, cutree, gpb, hash; } g_cli = {1, 0, 0, 0, 1, 0, 0};
 int ks265_enc_set_default(const char *name, int value)
 {
     if (!name) return QY_POINTER;
@@ -98,6 +102,8 @@ int ks265_enc_set_default(const char *name, int value)
     if (!strcmp(name, "scenecut")) { if (value < 0 || value > 100) return QY265_PARAM_BAD_VALUE; g_cli.scenecut = value; return QY_OK; }   /* the reference's hidden -scenecut N */
     if (!strcmp(name, "cutree")) { if (value < 0 || value > 1) return QY265_PARAM_BAD_VALUE; g_cli.cutree = value; return QY_OK; }        /* the reference's hidden -cutree N (on by default, as there) */
     if (!strcmp(name, "gpb")) { if (value < 0 || value > 1) return QY265_PARAM_BAD_VALUE; g_cli.gpb = value; return QY_OK; }                /* anchors as B slices over past anchors (ks265_enc.h) */
+    /* decoded picture hash SEI messages, x265's numbering: 0 off, 2 CRC, 3 checksum; 1 (MD5) is refused - MD5 is sequential per plane, it stays with -md5's log lines (ks265_enc.h) */
+    if (!strcmp(name, "hash")) { if (value != 0 && value != 2 && value != 3) return QY265_PARAM_BAD_VALUE; g_cli.hash = value; return QY_OK; }
     return QY265_PARAM_BAD_NAME;
 }
 
@@ -219,6 +225,8 @@ typedef struct Job {
     void *wpp; ks265_slice_in sin; int started, nrows, next_row, rows_done;   /* row-wise writing of the slice (ks265_wpp_*) */
     int8_t *qp_map;                                       /* -aq: the QP of every CTU this picture was coded with (pinned; NULL without) */
     int64_t *ssim;                                        /* -ssim: per plane the sum over its 8x8 windows of llrint(ssim x 2^30) (pinned; NULL without) */
+    uint32_t *hash;                                       /* `hash`: picture_crc [0..2] and picture_checksum [3..5] of the output picture's planes (pinned; NULL without) */
+    uint8_t sei[48]; long sei_len;                        /* ... and the suffix SEI NAL unit a writer made of them: goes out behind the slice NAL unit, counted in no controller's bits */
     uint8_t *recon;                                       /* pinned I420 copy of the reconstruction (only with ks265_enc_set_recon_file / -md5) */
     char md5[3][33];
     void *ev;                                             /* recorded after the D2H copies */
@@ -314,6 +322,7 @@ typedef struct PixPath {
     ks265_ctx *ctx; ks265_frame *frame; ks265_pic src;
     uint64_t *dev_sse;                                    /* 64 bytes: the SSE sums of the path's latest picture */
     int64_t *dev_ssim;                                    /* -ssim: the three sums of the fused pass, 32 bytes apart inside PATH_MAIN's allocation of 96 (NULL without) */
+    uint32_t *dev_hash;                                   /* `hash`: the six values of the hash pass, 32 bytes apart inside PATH_MAIN's allocation of 96 (NULL without) */
     double *aq_off, *aq_scratch; uint16_t *aq_inv;        /* -aq: the key pictures' stream has buffers of its own, the anchors share the main stream's */
 } PixPath;
 
@@ -363,6 +372,7 @@ typedef struct Enc {
     ks265_pic dpb[MAX_DPB]; int dpb_poc[MAX_DPB]; int ndpb;
     /* -ssim: the fused pass is there and asked for (its device sums: PixPath::dev_ssim); the session's
      * totals in output order as exact integers (hi x 2^30 + lo: the same for any number of GOP lanes), the picture accounted last and when (q_seq: across lanes) */
+    int hash_on;                                          /* `hash` in force (2 CRC, 3 checksum) and the hash pass is there: every picture is followed by its decoded picture hash SEI message */
     int ssim_on; long long q_hi[3], q_lo[3]; int q_last_poc; double q_last_sse[3], q_last_ssim[3]; unsigned long q_seq;
     /* key pictures on their own stream and frame object (path[PATH_KEY]): an intra picture keeps 34 of 256 compute units busy for ~26 ms (2160p); coded as soon as its
      * input arrives - the pixel path is tens of pictures behind the input - it runs underneath the P pictures of the previous GOP instead of between
@@ -617,11 +627,13 @@ static void *worker(void *arg)
                     if (nb) { j->nal = nb; j->nal_cap = need; } else oom = 1;
                 }
                 const long n = oom ? (long)KS265_OUTOFMEMORY : ks265_wpp_finish(j->wpp, j->nal, j->nal_cap);
+                /* `hash`: the picture's decoded picture hash SEI message, a NAL unit of its own behind the slice's (the six values came home in front of the picture's event) */
+                j->sei_len = e->hash_on && n >= 0 ? ks265_write_picture_hash_sei(e->hash_on - 1, j->hash + (e->hash_on == 2 ? 0 : 3), j->sei, sizeof j->sei) : 0;
                 j->fctx_ok = e->rdoq_on && n >= 0 && ks265_slice_final_contexts(&e->scfg, j->wpp, j->fctx, (int)sizeof j->fctx, NULL) > 0;
                 memcpy(j->dirty, j->cmp + e->cmp_off[5], e->cmp_off[6] - e->cmp_off[5]);      /* what the next picture in this slot has to clear */
                 pthread_mutex_lock(&e->mu);
                 j->t_write_ms += now_ms() - t1;
-                j->nal_len = n; j->error = n < 0 ? (int)n : 0; j->done = 1; j->t_done = now_ms();
+                j->nal_len = n; j->error = n < 0 ? (int)n : j->sei_len < 0 ? (int)j->sei_len : 0; j->done = 1; j->t_done = now_ms();
                 rc_account(e);
                 pthread_cond_broadcast(&e->cv_done); lane_wake_top(e);
             }
@@ -1072,6 +1084,9 @@ static int drain_picture(Enc *e, const Sub *s, ks265_ctx *on, int captured)
     const void *extra = e->cfg.calcPsnr ? p->dev_sse : NULL;
     int r = quality_pass(e, on, p->frame, s->srcp, s->out, p->dev_sse, p->dev_ssim);
     if (!r && p->dev_ssim && !captured) r = ks265_memcpy_d2h_async(cx, s->j->ssim, p->dev_ssim, 24);
+    /* `hash`: CRC and checksum of the output picture (one read of it), home the same way */
+    if (!r && p->dev_hash) r = on ? ks265_picture_hash_on(on, p->frame, s->out, p->dev_hash) : ks265_picture_hash(p->frame, s->out, p->dev_hash);
+    if (!r && p->dev_hash && !captured) r = ks265_memcpy_d2h_async(cx, s->j->hash, p->dev_hash, 24);
     if (!on && !captured) {
         if (!r && e->recon_on) r = recon_home(e, s);
         /* the records leave the frame object's buffers for a staging set (device to device, a few microseconds), so that the next picture can start
@@ -1097,7 +1112,7 @@ static int code_picture_graph(Enc *e, Sub *s)
     const int k = s->k; PixPath *p = s->p; ks265_ctx *cx = p->ctx; ks265_frame *fr = p->frame;
     const ks265_pic refp = e->dpb[dpb_find(e, s->l0[0])], ref1p = s->kind == 'B' ? e->dpb[dpb_find(e, s->l1[0])] : refp;
     const uint64_t key[9] = {(uint64_t)(uintptr_t)refp.y, (uint64_t)(uintptr_t)s->out.y, (uint64_t)(uintptr_t)e->dev_in[k], (uint64_t)(uintptr_t)e->stg[k],
-                             (uint64_t)s->qp, (uint64_t)ks265_frame_p_state(fr), (uint64_t)(e->cfg.calcPsnr != 0) | (uint64_t)e->ssim_on << 1, (uint64_t)s->kind | ((uint64_t)s->lean << 8), (uint64_t)(uintptr_t)ref1p.y};
+                             (uint64_t)s->qp, (uint64_t)ks265_frame_p_state(fr), (uint64_t)(e->cfg.calcPsnr != 0) | (uint64_t)e->ssim_on << 1 | (uint64_t)(e->hash_on != 0) << 2, (uint64_t)s->kind | ((uint64_t)s->lean << 8), (uint64_t)(uintptr_t)ref1p.y};
     void *exec = NULL;
     for (int i = 0; i < e->ngraph && !exec; ++i) if (!memcmp(e->graph[i].key, key, sizeof key)) exec = e->graph[i].exec;
     int r = s->recycled ? ks265_stream_wait_event(cx, e->ev_drained[k]) : 0;       /* the staging block of this rotation slot has been copied out */
@@ -1121,6 +1136,7 @@ static int code_picture_graph(Enc *e, Sub *s)
         }
     }
     if (!r && p->dev_ssim) r = ks265_memcpy_d2h_async(cx, s->j->ssim, p->dev_ssim, 24);  /* (see drain_picture) */
+    if (!r && p->dev_hash) r = ks265_memcpy_d2h_async(cx, s->j->hash, p->dev_hash, 24);
     if (!r) r = ks265_event_record(cx, e->ev_loaded[k]);                  /* the input buffer is free again (a little later than on the plain path) */
     if (!r) r = ks265_event_record(cx, e->ev_staged[k]);
     e->dpb_poc[s->slot] = s->poc;
@@ -1225,7 +1241,7 @@ static void publish_job(Enc *e, const Sub *s)
     Job *j = s->j;
     pthread_mutex_lock(&e->mu);
     s->in->used = 2;                                                   /* released when the job's event has fired (output time); under the lock: the caller counts the pictures in flight */
-    j->done = 0; j->error = 0; j->used = 1; j->started = 0; j->nrows = 0; j->next_row = 0; j->rows_done = 0;
+    j->done = 0; j->error = 0; j->used = 1; j->started = 0; j->nrows = 0; j->next_row = 0; j->rows_done = 0; j->sei_len = 0;
     j->sub_seq = e->rc_sub;
     e->job_tail = (e->job_tail + 1) % e->ring; ++e->njobs; ++e->nwait; ++e->rc_sub;
     e->st.occ_samples++; e->st.occ_ring += e->njobs; e->st.occ_gpu += e->nwait; e->st.occ_ready += e->npending;
@@ -1478,7 +1494,7 @@ static int take_output(Enc *e, int max_in_flight, int max_pics, QY265Nal **pNals
         Job *j = &e->jobs[e->job_head];
         if (!j->done) { if (e->njobs <= max_in_flight) break; pthread_cond_wait(&e->cv_done, &e->mu); continue; }
         if (j->error) err = hip_rc(j->error);
-        const size_t need = (size_t)(j->nal_len > 0 ? j->nal_len : 0);
+        const size_t nsl = (size_t)(j->nal_len > 0 ? j->nal_len : 0), nsei = (size_t)(j->nal_len > 0 && j->sei_len > 0 ? j->sei_len : 0), need = nsl + nsei;
         if (e->outpos + need > e->outcap) {                             /* the caller reads the payloads after this call: they cannot stay in the job (its slot is reused) */
             if (cnt) break;                                             /* hand out what fits, the rest next time */
             uint8_t *nb = (uint8_t *)realloc(e->outbuf, need + 65536);
@@ -1492,12 +1508,18 @@ static int take_output(Enc *e, int max_in_flight, int max_pics, QY265Nal **pNals
                 ++cnt; off += e->hdr_part[k];
             }
         }
-        memcpy(e->outbuf + e->outpos, j->nal, need);
-        e->nals[cnt].naltype = j->nal_type; e->nals[cnt].tid = 0; e->nals[cnt].iSize = (int)need; e->nals[cnt].pts = j->pts; e->nals[cnt].pPayload = e->outbuf + e->outpos;
-        e->outpos += need;
+        memcpy(e->outbuf + e->outpos, j->nal, nsl);
+        e->nals[cnt].naltype = j->nal_type; e->nals[cnt].tid = 0; e->nals[cnt].iSize = (int)nsl; e->nals[cnt].pts = j->pts; e->nals[cnt].pPayload = e->outbuf + e->outpos;
+        e->outpos += nsl;
         ++cnt;
+        if (nsei) {                                                     /* `hash`: the picture's SEI message, one more NAL unit with the picture's pts */
+            memcpy(e->outbuf + e->outpos, j->sei, nsei);
+            e->nals[cnt].naltype = KS265_NAL_SUFFIX_SEI; e->nals[cnt].tid = 0; e->nals[cnt].iSize = (int)nsei; e->nals[cnt].pts = j->pts; e->nals[cnt].pPayload = e->outbuf + e->outpos;
+            e->outpos += nsei;
+            ++cnt;
+        }
         if (out) { out->iSliceType = j->kind == 'I' ? 2 : j->kind == 'P' && !j->gpb ? 1 : 0; out->poc = j->disp; out->pts = j->pts; out->dts = j->pts; }
-        e->st.frames++; e->st.bytes += j->nal_len > 0 ? j->nal_len : 0; e->st.host_write_ms += j->t_write_ms;
+        e->st.frames++; e->st.bytes += (long long)need; e->st.host_write_ms += j->t_write_ms;
         e->st.lat_gpu_ms += j->t_event - j->t_submit; e->st.lat_queue_ms += j->t_taken - j->t_submit;
         if (j->kind == 'I') { e->st.key_wall_ms += j->t_done - j->t_event; e->st.key_cpu_ms += j->t_write_ms; e->st.keys++; }
         if (j->key_headers && e->cfg.bHeaderBeforeKeyframe) e->st.bytes += e->hdr_len;
@@ -1535,7 +1557,7 @@ static int take_output(Enc *e, int max_in_flight, int max_pics, QY265Nal **pNals
         for (int i = 0; i < MAX_INPUT; ++i) if (e->in[i].used == 2 && e->in[i].disp == j->disp) e->in[i].used = 0;
         j->used = 0;
         e->job_head = (e->job_head + 1) % e->ring; --e->njobs; ++taken;
-        if (cnt >= (int)(sizeof e->nals / sizeof e->nals[0]) - 4) break;
+        if (cnt >= (int)(sizeof e->nals / sizeof e->nals[0]) - 5) break;
     }
     if (taken) pthread_cond_broadcast(&e->cv_done);                    /* the scheduler thread may be waiting for ring space */
     pthread_mutex_unlock(&e->mu);
@@ -1584,7 +1606,7 @@ static void lane_close(Enc *e, int report)
         if (report) run_summary(e, e->st.frames, e->st.bytes, e->st.sse, e->q_hi, e->q_lo);
         for (int i = 0; i < MAX_JOBS; ++i) {
             Job *j = &e->jobs[i];
-            ks265_host_free(main_ctx(e), j->cmp); ks265_host_free(main_ctx(e), j->recon); ks265_host_free(main_ctx(e), j->qp_map); ks265_host_free(main_ctx(e), j->ssim); ks265_host_free(main_ctx(e), j->rq_host); free(j->lvlbuf); free(j->dirty);
+            ks265_host_free(main_ctx(e), j->cmp); ks265_host_free(main_ctx(e), j->recon); ks265_host_free(main_ctx(e), j->qp_map); ks265_host_free(main_ctx(e), j->ssim); ks265_host_free(main_ctx(e), j->hash); ks265_host_free(main_ctx(e), j->rq_host); free(j->lvlbuf); free(j->dirty);
             if (j->ev) ks265_event_destroy(main_ctx(e), j->ev);
             free(j->nal);
         }
@@ -1614,7 +1636,7 @@ static void lane_close(Enc *e, int report)
             pic_free(e, &e->srcq[k]);
         }
         for (int i = 0; i < e->ngraph; ++i) ks265_graph_destroy(main_ctx(e), e->graph[i].exec);
-        ks265_dev_free(main_ctx(e), e->path[PATH_MAIN].dev_sse); ks265_dev_free(main_ctx(e), e->path[PATH_MAIN].dev_ssim); ks265_dev_free(main_ctx(e), e->dev_recon);
+        ks265_dev_free(main_ctx(e), e->path[PATH_MAIN].dev_sse); ks265_dev_free(main_ctx(e), e->path[PATH_MAIN].dev_ssim); ks265_dev_free(main_ctx(e), e->path[PATH_MAIN].dev_hash); ks265_dev_free(main_ctx(e), e->dev_recon);
         for (int q = PATH_MAIN; q <= PATH_KEY; ++q) { ks265_dev_free(main_ctx(e), e->path[q].aq_off); ks265_dev_free(main_ctx(e), e->path[q].aq_inv); ks265_dev_free(main_ctx(e), e->path[q].aq_scratch); }
         for (int k = 0; k < NPIPE; ++k) ks265_dev_free(main_ctx(e), e->dev_qmap[k]);
         for (int q = 0; q < 2; ++q) ks265_dev_free(main_ctx(e), e->dev_qmap_key[q]);
@@ -1653,6 +1675,7 @@ static int path_open(Enc *e, int which, int device, int prio)
     if (!r) r = pic_alloc(e, &p->src);
     if (!r) r = ks265_dev_malloc(main_ctx(e), (void **)&p->dev_sse, 64);
     if (e->path[PATH_MAIN].dev_ssim) p->dev_ssim = e->path[PATH_MAIN].dev_ssim + 4 * which;
+    if (e->path[PATH_MAIN].dev_hash) p->dev_hash = e->path[PATH_MAIN].dev_hash + 8 * which;
     return r;
 }
 
@@ -1794,6 +1817,12 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
     e->ssim_on = cfg->calcSsim != 0 && ks265_ssim_picture && ks265_ssim_picture_on;
     if (cfg->calcSsim && !e->ssim_on) logf_(2, e->log_level, "ks265enc: SSIM is unavailable: the device library has no ks265_ssim_picture (-ssim is ignored, no ssim line)\n");
     if (!r && e->ssim_on) r = ks265_dev_malloc(main_ctx(e), (void **)&e->path[PATH_MAIN].dev_ssim, 96);
+    /* `hash` (ks265_enc_set_default, KS265_HASH overrides; a value the setter would refuse counts as off) */
+    const int hash_req = getenv("KS265_HASH") ? atoi(getenv("KS265_HASH")) : g_cli.hash;
+    e->hash_on = (hash_req == 2 || hash_req == 3) && ks265_picture_hash && ks265_picture_hash_on ? hash_req : 0;
+    if ((hash_req == 2 || hash_req == 3) && !e->hash_on)                 /* (once per handle: the lanes behind the first log errors only) */
+        logf_(2, e->log_level, "ks265enc: picture hash is unavailable: the device library has no ks265_picture_hash (hash is ignored, no SEI messages)\n");
+    if (!r && e->hash_on) r = ks265_dev_malloc(main_ctx(e), (void **)&e->path[PATH_MAIN].dev_hash, 96);
     e->aq_on = cfg->iAqMode != 0 && cfg->fAqStrength > 0;
     /* cuTree: -rc 3 (CRF) with the reference's -cutree 1 (its default), B pictures (with -bframes 0 the reference runs no tree: TEncParam+0x388 = 0, every offset it leaves is zero)
      * and a lookahead (not -lookahead 0, not zero latency): a QP per CTU from the lookahead window */
@@ -1907,6 +1936,7 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
         }
         if (!r && e->qmap_on) r = ks265_host_malloc(main_ctx(e), (void **)&j->qp_map, (size_t)e->geom.ctu_cols * e->geom.ctu_rows);
         if (!r && e->ssim_on) r = ks265_host_malloc(main_ctx(e), (void **)&j->ssim, 32);
+        if (!r && e->hash_on) r = ks265_host_malloc(main_ctx(e), (void **)&j->hash, 32);
         if (!r && e->rdoq_on) r = ks265_host_malloc(main_ctx(e), (void **)&j->rq_host, 1440 * sizeof(int32_t) + 104 * sizeof(int64_t));
         if (!r) r = ks265_event_create(main_ctx(e), &j->ev);
         j->nal_cap = npx * 2 + 65536;

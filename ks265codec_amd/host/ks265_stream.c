@@ -48,6 +48,24 @@ static long nal_wrap(int nal_type, const uint8_t *rbsp, size_t n, uint8_t *out, 
     return (long)o;
 }
 
+/* decoded picture hash SEI message (D.2.19 / D.3.19; payload type 132) as one suffix SEI NAL unit: hash_type 1 = picture_crc (u(16) per plane), 2 = picture_checksum (u(32) per
+ * plane), for the three planes of a 4:2:0 picture.  MD5 (hash_type 0) is not written here (ks265_enc.h: `hash`) */
+long ks265_write_picture_hash_sei(int hash_type, const uint32_t value[3], uint8_t *out, size_t cap)
+{
+    if (!value || !out) return KS265_POINTER;
+    if (hash_type != 1 && hash_type != 2) return KS265_NOTSUPPORTED;
+    const int nb = hash_type == 1 ? 2 : 4;
+    uint8_t buf[16];
+    size_t n = 0;
+    buf[n++] = 132;                                  /* payload_type: decoded picture hash */
+    buf[n++] = (uint8_t)(1 + 3 * nb);                /* payload_size */
+    buf[n++] = (uint8_t)hash_type;
+    for (int c = 0; c < 3; ++c)
+        for (int k = nb - 1; k >= 0; --k) buf[n++] = (uint8_t)(value[c] >> (8 * k));
+    buf[n++] = 0x80;                                 /* rbsp_trailing_bits */
+    return nal_wrap(KS265_NAL_SUFFIX_SEI, buf, n, out, cap);
+}
+
 /* ------------------------------------------------------------------ parameter sets (7.3.2) */
 static void profile_tier_level(BitW *b)
 {

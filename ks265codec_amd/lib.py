@@ -66,6 +66,7 @@ EXPORTS = [
     "ks265_intra_candidates", "ks265_cu_decide_ii", "ks265_cu_decide_b_ii", "ks265_intra_inter_reconstruct", "ks265_frame_set_profiling", "ks265_frame_stage_ms", "ks265_frame_me_int_ms", "ks265_frame_levels", "ks265_frame_pu", "ks265_frame_cu8", "ks265_frame_ibest", "ks265_frame_sao", "ks265_sse_picture",
     "ks265_input_validate", "ks265_input_convert", "ks265_wait_external", "ks265_external_wait_event",
     "ks265_ssim_picture", "ks265_ssim_picture_on",
+    "ks265_picture_hash", "ks265_picture_hash_on",
 ]
 
 
@@ -517,6 +518,16 @@ class KsFrame:
         out = self.ks.zeros(24)
         self.ks._chk(self.lib.ks265_ssim_picture(self.h, a.c(), b.c(), _p(sse), _p(out)))
         return (self.ks.host(sse, np.uint64) if with_sse else None), self.ks.host(out, np.int64)
+
+    def picture_hash(self, p: DevPic, on: "KsContext | None" = None):
+        """uint32[6]: picture_crc of Y, Cb, Cr, then picture_checksum of Y, Cb, Cr (H.265 D.3.19) of the picture inside its padding, from one launch (on: another context's stream)"""
+        out = self.ks.zeros(24)
+        if on is None:
+            self.ks._chk(self.lib.ks265_picture_hash(self.h, p.c(), _p(out)))
+        else:
+            self.ks._chk(self.lib.ks265_picture_hash_on(on.h, self.h, p.c(), _p(out)))
+            on.sync()
+        return self.ks.host(out, np.uint32)
 
     # internal workspace views (device pointers wrapped as ctypes addresses)
     def ws_ptr(self, name: str, comp: int = 0) -> int:

@@ -16,6 +16,8 @@ _lib = None
 
 SLICE_B, SLICE_P, SLICE_I = 0, 1, 2
 NAL_TRAIL_N, NAL_TRAIL_R, NAL_IDR_W_RADL, NAL_IDR_N_LP = 0, 1, 19, 20
+NAL_SUFFIX_SEI = 40
+HASH_CRC, HASH_CHECKSUM = 1, 2                                        # hash_type of the decoded picture hash SEI message (D.3.19)
 
 
 class StreamCfg(C.Structure):
@@ -54,10 +56,20 @@ def lib() -> C.CDLL:
     global _lib
     if _lib is None:
         _lib = C.CDLL(build())
-        for n in ("ks265_write_vps", "ks265_write_sps", "ks265_write_pps", "ks265_write_slice"):
+        for n in ("ks265_write_vps", "ks265_write_sps", "ks265_write_pps", "ks265_write_slice", "ks265_write_picture_hash_sei"):
             getattr(_lib, n).restype = C.c_long
         _lib.ks265_slice_scratch_bytes.restype = C.c_size_t
     return _lib
+
+
+def picture_hash_sei(hash_type: int, values) -> bytes:
+    """ks265_write_picture_hash_sei: the suffix SEI NAL unit (type 40, payload 132) with the picture_crc (hash_type 1) or picture_checksum (2) of the three planes"""
+    v = (C.c_uint32 * 3)(*[int(x) & 0xFFFFFFFF for x in values])
+    out = (C.c_uint8 * 64)()
+    n = lib().ks265_write_picture_hash_sei(C.c_int(hash_type), v, out, C.c_size_t(64))
+    if n < 0:
+        raise RuntimeError(f"ks265_write_picture_hash_sei rc={n}")
+    return bytes(out[:n])
 
 
 class StreamWriter:
