@@ -204,6 +204,7 @@ int QY265ConfigParse(QY265EncConfig *c, const char *name, const char *value)
 
 /* ------------------------------------------------------------------ encoder */
 #define MAX_DPB 18
+#define NO_PIC (-1000000)                                  /* the display index / POC of "no picture": Enc::dpb_poc, Enc::la_last_key, CtPic::disp */
 #define MAX_JOBS 128                                      /* upper bound of the ring of pictures in flight; the encoder sizes its ring (Enc::ring) by picture size */
 typedef struct TopWake { pthread_mutex_t mu; pthread_cond_t cv; unsigned long seq; } TopWake;
 #undef MAX_INPUT                                         /* (<dirent.h> brings the terminal limit of that name along) */
@@ -413,6 +414,15 @@ typedef struct Enc {
     int ct_on, ct_lg, ct_nx, ct_ny, ct_w, ct_h, ct_stride, ct_pad, ct_depth, ct_preset, qmap_on, qmap_fd;
     struct CtPic { int disp, p0, p1, intra_done, used; uint8_t *blk, *low; uint16_t *intra, *invq, *prop, *inter; uint8_t *imode, *bits; int32_t *mv0, *c0, *mv1, *c1; double *aq_off, *qoff; ks265_cfc_sums *sums; void *ev_used; } ct[CT_RING];
     ks265_ctx *ctx_ct; void *ct_ws, *ct_ev; uint64_t *ct_acc; double *ct_scratch; uint8_t *ct_full;
+    /* decisions that only the steps of lane_open and lane_close read (lane_resolve) */
+#define UPL_NONE 99
+    struct {
+        int la_wanted, la_order, la_prio;                 /* the lookahead's stream: asked for; created first (0), behind the copy streams (1), else with the lookahead's objects; KS265_LA_PRIO */
+        int upl_at;                                       /* the uploads' stream: created at position -1 / 0 / 1 / 2 (open_upl_stream), UPL_NONE: there is none */
+        int key_prio, anc_prio, srcq;                     /* stream priorities of the two paths beside the main one; the split pipeline's source pictures are allocated */
+        int input_slots, pinned_mb; size_t spacer;        /* KS265_INPUT_SLOTS (or ENV_UNSET), KS265_PINNED_MB; KS265_PIC_SPACER: bytes in front of every picture (pic_alloc) */
+        const char *qmap_path;                            /* KS265_DUMP_QPMAP */
+    } plan;
     struct TopWake *wake;                                 /* lanes: the handle's caller sleeps here until a picture of ANY lane is finished */
     Job jobs[MAX_JOBS]; int ring, job_head, job_tail, njobs;   /* ring of `ring` pictures in coding order */
     /* workers */
@@ -458,8 +468,7 @@ static int pic_alloc(Enc *e, ks265_pic *p)
 {
     /* KS265_PIC_SPACER = bytes: an unused allocation in front of every picture (where pictures lie against each other in device memory decides what shares a memory channel:
      * round 4) */
-    const char *sp = getenv("KS265_PIC_SPACER");
-    if (sp && atol(sp) > 0 && e->nspacer < 64) { void *d = NULL; if (!ks265_dev_malloc(main_ctx(e), &d, (size_t)atol(sp))) e->spacer[e->nspacer++] = d; }
+    if (e->plan.spacer && e->nspacer < 64) { void *d = NULL; if (!ks265_dev_malloc(main_ctx(e), &d, e->plan.spacer)) e->spacer[e->nspacer++] = d; }
     int r = ks265_dev_malloc(main_ctx(e), (void **)&p->y, (size_t)e->geom.bytes_y);
     if (!r) r = ks265_dev_malloc(main_ctx(e), (void **)&p->u, (size_t)e->geom.bytes_c);
     if (!r) r = ks265_dev_malloc(main_ctx(e), (void **)&p->v, (size_t)e->geom.bytes_c);
@@ -717,17 +726,10 @@ static const uint16_t kCtLambda[52] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1,
 static const struct { int zero_thr, fast_intra, f36c, f538, f3b4, lg4; } kCtPreset[9] = {{4, 4, 0, 120, 2, 1}, {4, 4, 0, 120, 2, 1}, {4, 1, 0, 0, 1, 1}, {0, 0, 1, 0, 1, 0}, {0, 0, 1, 0, 1, 0},
                                                                                               {0, 0, 1, 0, 1, 0}, {0, 0, 1, 0, 1, 0}, {0, 0, 1, 0, 1, 0}, {0, 0, 0, 0, 1, 0}};
 static struct CtPic *ct_slot(Enc *e, int disp) { return &e->ct[((disp % CT_RING) + CT_RING) % CT_RING]; }
-static int ct_open(Enc *e, int device)
+static int ct_open(Enc *e)                                             /* (the geometry - ct_w .. ct_stride - is lane_resolve's) */
 {
-    const int ps = e->ct_preset;
-    e->ct_w = e->W / 2; e->ct_h = e->H / 2;
-    e->ct_lg = (kCtPreset[ps].lg4 || (long)e->W * e->H >= 1280L * 720) ? 4 : 3;
-    const int bs = 1 << e->ct_lg;
-    e->ct_nx = (e->ct_w + bs - 1) / bs; e->ct_ny = (e->ct_h + bs - 1) / bs;
-    e->ct_pad = 40 + bs;                                               /* the search leaves the picture by at most merange / 2 + 1 = 33; the last block row / column may overhang it */
-    e->ct_stride = (e->ct_w + 2 * e->ct_pad + 63) & ~63;
     const size_t n = (size_t)e->ct_nx * e->ct_ny, lowsz = (size_t)e->ct_stride * (size_t)(e->ct_h + 2 * e->ct_pad);
-    int r = ks265_create(&e->ctx_ct, device);
+    int r = ks265_create(&e->ctx_ct, e->dev_id);
     /* one block of device memory per picture of the ring: the padded half-size plane, then the per-block arrays (64-byte aligned) */
     const size_t a64 = 63;
     size_t off[16], o = (lowsz + a64) & ~a64;
@@ -735,7 +737,7 @@ static int ct_open(Enc *e, int device)
     for (int k = 0; k < 13; ++k) { off[k] = o; o = (o + sz[k] + a64) & ~a64; }
     for (int i = 0; i < CT_RING && !r; ++i) {
         struct CtPic *c = &e->ct[i];
-        c->disp = -1000000;
+        c->disp = NO_PIC;
         r = ks265_dev_malloc(e->ctx_ct, (void **)&c->blk, o);
         if (r) break;
         c->low = c->blk + (size_t)e->ct_pad * e->ct_stride + e->ct_pad;
@@ -772,7 +774,7 @@ static int ct_prepare(Enc *e, int disp)
     ks265_ctx *cx = e->ctx_ct;
     const int n = e->ct_nx * e->ct_ny;
     int r = c->used ? ks265_stream_wait_event(cx, c->ev_used) : 0;       /* the picture that held this slot CT_RING pictures ago: its QP map has been taken */
-    c->disp = disp; c->p0 = c->p1 = -1000000; c->intra_done = 0;
+    c->disp = disp; c->p0 = c->p1 = NO_PIC; c->intra_done = 0;
     const uint8_t *full = NULL;
     if (in->dev) { if (!r && !in->up_sync) r = ks265_stream_wait_event(cx, in->ev_up); full = in->dev; }
     else if (e->ct_full) { if (!r) r = ks265_memcpy_h2d_async(cx, e->ct_full, in->i420, (size_t)e->W * e->H * 3 / 2); full = e->ct_full; }
@@ -1364,7 +1366,7 @@ static int schedule(Enc *e, int flush, int have /* pictures [0, have) have arriv
             e->gop_start = nxt; e->mg4_until = -1;
             e->anc_hist[0] = 0; e->n_anc = 1;                           /* the key picture is the GOP's first anchor (POC 0) */
             e->rc_qp_delta = rc_decide(e);                             /* rate control: one offset per key picture / mini-GOP, decided when it is certain to be submitted */
-            for (int i = 0; i < e->ndpb + 2 + 4; ++i) e->dpb_poc[i] = -1000000;
+            for (int i = 0; i < e->ndpb + 2 + 4; ++i) e->dpb_poc[i] = NO_PIC;
             int r = submit(e, in, 'I', 0, clampqp(e, in->base_qp + e->rc_qp_delta), NULL, 0, NULL, 0, NULL, 0, 1, 1);
             if (r) return r;
             pthread_mutex_lock(&e->mu); e->coded_upto = nxt; pthread_mutex_unlock(&e->mu);
@@ -1586,110 +1588,19 @@ static void run_summary(const Enc *e, long frames, long long bytes, const double
     }
 }
 
-static void lane_close(Enc *e, int report)
-{
-    if (!e) return;
-    if (e->nth || e->disp_on || e->sched_on) {
-        pthread_mutex_lock(&e->mu); e->quit = 1; pthread_cond_broadcast(&e->cv_work); pthread_cond_broadcast(&e->cv_disp); pthread_cond_broadcast(&e->cv_sched); pthread_cond_broadcast(&e->cv_done); pthread_mutex_unlock(&e->mu);
-        if (e->sched_on) pthread_join(e->sched, NULL);
-        for (int i = 0; i < e->nth; ++i) pthread_join(e->th[i], NULL);
-        if (e->disp_on) pthread_join(e->disp, NULL);
-    }
-    if (main_ctx(e)) {
-        if (e->ctx_in) ks265_synchronize(e->ctx_in);
-        ks265_synchronize(main_ctx(e));
-        if (e->ctx_out) ks265_synchronize(e->ctx_out);
-        if (report && e->la_on) logf_(1, e->log_level, "ks265enc: lookahead: %ld scene cuts, %ld blocks of 8 pictures coded as 4 + 4\n", e->la_cuts, e->la_mini4);
-        if (report && e->la_on && e->in_disp) logf_(1, e->log_level, "ks265enc: lookahead, caller's ms per picture: launches + queue %.3f, of it waiting for results %.3f (%ld waits); pictures handed on by the scheduler thread: %ld\n",
-                                                    e->la_t_take / e->in_disp, e->la_t_wait / e->in_disp, e->la_n_wait, e->la_n_poll);
-        if (report && e->in_disp) logf_(1, e->log_level, "ks265enc: caller's back-pressure wait %.3f ms per picture\n", e->la_t_bp / e->in_disp);
-        if (report) run_summary(e, e->st.frames, e->st.bytes, e->st.sse, e->q_hi, e->q_lo);
-        for (int i = 0; i < MAX_JOBS; ++i) {
-            Job *j = &e->jobs[i];
-            ks265_host_free(main_ctx(e), j->cmp); ks265_host_free(main_ctx(e), j->recon); ks265_host_free(main_ctx(e), j->qp_map); ks265_host_free(main_ctx(e), j->ssim); ks265_host_free(main_ctx(e), j->hash); ks265_host_free(main_ctx(e), j->rq_host); free(j->lvlbuf); free(j->dirty);
-            if (j->ev) ks265_event_destroy(main_ctx(e), j->ev);
-            free(j->nal);
-        }
-        for (int i = 0; i < MAX_INPUT; ++i) { ks265_host_free(main_ctx(e), e->in[i].i420); if (e->in[i].dev) ks265_dev_free(main_ctx(e), e->in[i].dev); if (e->in[i].ev_up) ks265_event_destroy(e->ctx_up, e->in[i].ev_up); }
-        for (int i = 0; i < e->ndpb + 2; ++i) pic_free(e, &e->dpb[i]);
-        for (int i = 0; i < e->nspacer; ++i) ks265_dev_free(main_ctx(e), e->spacer[i]);
-        if (e->ev_key) ks265_event_destroy(main_ctx(e), e->ev_key);
-        for (int i = 0; i < 2; ++i) if (e->ev_firstp[i]) ks265_event_destroy(main_ctx(e), e->ev_firstp[i]);
-        for (int i = PATH_KEY; i < NPATH; ++i) {                         /* the paths beside the main one: their streams run dry before their frame objects go (the contexts: last, below) */
-            PixPath *p = &e->path[i];
-            if (p->ctx) ks265_synchronize(p->ctx);
-            if (p->frame) ks265_frame_destroy(p->frame);
-            pic_free(e, &p->src); ks265_dev_free(main_ctx(e), p->dev_sse);
-        }
-        if (e->ev_anc) ks265_event_destroy(main_ctx(e), e->ev_anc);
-        for (int i = 0; i < 8; ++i) if (e->ev_mg[i]) ks265_event_destroy(main_ctx(e), e->ev_mg[i]);
-        for (int i = 0; i < 4; ++i) pic_free(e, &e->dpb[e->ndpb + 2 + i]);
-        pic_free(e, &e->path[PATH_MAIN].src);
-        for (int k = 0; k < NPIPE; ++k) {
-            ks265_dev_free(main_ctx(e), e->dev_in[k]); ks265_dev_free(main_ctx(e), e->stg[k]);
-            if (e->ev_h2d[k]) ks265_event_destroy(main_ctx(e), e->ev_h2d[k]);
-            if (e->ev_loaded[k]) ks265_event_destroy(main_ctx(e), e->ev_loaded[k]);
-            if (e->ev_staged[k]) ks265_event_destroy(main_ctx(e), e->ev_staged[k]);
-            if (e->ev_drained[k]) ks265_event_destroy(main_ctx(e), e->ev_drained[k]);
-            if (e->ev_coded[k]) ks265_event_destroy(main_ctx(e), e->ev_coded[k]);
-            if (e->ev_packed[k]) ks265_event_destroy(main_ctx(e), e->ev_packed[k]);
-            pic_free(e, &e->srcq[k]);
-        }
-        for (int i = 0; i < e->ngraph; ++i) ks265_graph_destroy(main_ctx(e), e->graph[i].exec);
-        ks265_dev_free(main_ctx(e), e->path[PATH_MAIN].dev_sse); ks265_dev_free(main_ctx(e), e->path[PATH_MAIN].dev_ssim); ks265_dev_free(main_ctx(e), e->path[PATH_MAIN].dev_hash); ks265_dev_free(main_ctx(e), e->dev_recon);
-        for (int q = PATH_MAIN; q <= PATH_KEY; ++q) { ks265_dev_free(main_ctx(e), e->path[q].aq_off); ks265_dev_free(main_ctx(e), e->path[q].aq_inv); ks265_dev_free(main_ctx(e), e->path[q].aq_scratch); }
-        for (int k = 0; k < NPIPE; ++k) ks265_dev_free(main_ctx(e), e->dev_qmap[k]);
-        for (int q = 0; q < 2; ++q) ks265_dev_free(main_ctx(e), e->dev_qmap_key[q]);
-        if (e->recon_fd >= 0) close(e->recon_fd);
-        if (e->qmap_fd >= 0) close(e->qmap_fd);
-        ct_close(e);
-        if (e->ctx_la) {
-            ks265_synchronize(e->ctx_la);
-            for (int i = 0; i < LA_RING; ++i) { ks265_dev_free(e->ctx_la, e->la_pic[i].y); ks265_dev_free(e->ctx_la, e->la_pic[i].u); ks265_dev_free(e->ctx_la, e->la_pic[i].v); }
-            ks265_dev_free(e->ctx_la, e->la_cost_ws); ks265_dev_free(e->ctx_la, e->la_dev_out); ks265_host_free(e->ctx_la, e->la_host_out);
-            for (int i = 0; i < LA_FLY; ++i) if (e->la_evs[i]) ks265_event_destroy(e->ctx_la, e->la_evs[i]);
-            if (e->frame_la) ks265_frame_destroy(e->frame_la);
-            ks265_destroy(e->ctx_la);
-        }
-        if (e->ctx_up) reg_handle(main_ctx(e), 0);
-        if (e->ctx_upl) { ks265_synchronize(e->ctx_upl); ks265_destroy(e->ctx_upl); }
-        if (main_frame(e)) ks265_frame_destroy(main_frame(e));
-        for (int i = PATH_KEY; i < NPATH; ++i) if (e->path[i].ctx) ks265_destroy(e->path[i].ctx);
-        if (e->ctx_in) ks265_destroy(e->ctx_in);
-        if (e->ctx_out) ks265_destroy(e->ctx_out);
-        ks265_destroy(main_ctx(e));
-    } else { if (e->ctx_la) ks265_destroy(e->ctx_la); if (e->ctx_upl) ks265_destroy(e->ctx_upl); }                   /* created first (lane_open), before the main context failed: nothing else of the lookahead exists yet */
-    for (int i = 0; i < MAX_JOBS; ++i) free(e->jobs[i].wpp);
-    free(e->hdr); free(e->outbuf); free(e->md5_ring); free(e->md5_have); free(e->rq_hist);
-    pthread_mutex_destroy(&e->la_mu);
-    pthread_mutex_destroy(&e->mu); pthread_cond_destroy(&e->cv_work); pthread_cond_destroy(&e->cv_done); pthread_cond_destroy(&e->cv_disp); pthread_cond_destroy(&e->cv_sched); pthread_cond_destroy(&e->cv_sched_done);
-    free(e);
-}
+/* ------------------------------------------------------------------ opening and closing a lane
+ * lane_resolve decides: it fills the fields of Enc that are decisions (Enc::plan: the ones only the steps below read) from the configuration, the CLI-level defaults and the
+ * environment, logs what was narrowed, and calls no entry of the device library.  lane_open is the list of steps that create what the plan says - their order is itself a
+ * measured result (tests/test_lane_open_cpu.py pins it).  Every open_* has its close_* beneath it, which frees what that step may have created and tolerates a step that never
+ * ran or stopped half way (the calloc of Enc zeroed everything); lane_close is the list of those. */
+#define ENV_UNSET (-2147483647 - 1)
+static int env_int(const char *name, int dflt) { const char *s = getenv(name); return s ? atoi(s) : dflt; }
+static int env_set(const char *name) { return getenv(name) != NULL; }
+static void ev_free(ks265_ctx *c, void **ev) { if (*ev) ks265_event_destroy(c, *ev); *ev = NULL; }
+static int lane_base_qp(const QY265EncConfig *cfg, int rc) { const int q = rc == 3 ? cfg->crf : cfg->qp; return q < 0 ? 0 : q > 51 ? 51 : q; }
 
-/* a pixel path beside the main one (the key pictures', the anchors'): a stream of the given priority, a frame object on it, a source picture, the block of its SSE sums */
-static int path_open(Enc *e, int which, int device, int prio)
+static void lane_resolve(Enc *e, const QY265EncConfig *cfg, int device, int multi)
 {
-    PixPath *p = &e->path[which];
-    int r = ks265_create_prio(&p->ctx, device, prio);
-    if (!r) r = ks265_frame_create(p->ctx, &e->fcfg, &p->frame);
-    if (!r) r = pic_alloc(e, &p->src);
-    if (!r) r = ks265_dev_malloc(main_ctx(e), (void **)&p->dev_sse, 64);
-    if (e->path[PATH_MAIN].dev_ssim) p->dev_ssim = e->path[PATH_MAIN].dev_ssim + 4 * which;
-    if (e->path[PATH_MAIN].dev_hash) p->dev_hash = e->path[PATH_MAIN].dev_hash + 8 * which;
-    return r;
-}
-
-static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
-{
-    int dummy; if (!err) err = &dummy;
-    *err = QY_OK;
-    if (!cfg) { *err = QY_POINTER; return NULL; }
-    if (cfg->picWidth <= 0 || cfg->picHeight <= 0 || (cfg->picWidth & 7) || (cfg->picHeight & 7) || cfg->frameRate <= 0 || cfg->rc < 0 || cfg->rc > 5) { *err = QY_NOTSUPPORTED; return NULL; }
-    Enc *e = (Enc *)calloc(1, sizeof *e);
-    if (e) { e->recon_fd = -1; e->qmap_fd = -1; }
-    if (!e) { *err = QY_OUTOFMEMORY; return NULL; }
-    pthread_mutex_init(&e->la_mu, NULL);
-    pthread_mutex_init(&e->mu, NULL); pthread_cond_init(&e->cv_work, NULL); pthread_cond_init(&e->cv_done, NULL); pthread_cond_init(&e->cv_disp, NULL); pthread_cond_init(&e->cv_sched, NULL); pthread_cond_init(&e->cv_sched_done, NULL);
     e->cfg = *cfg; e->W = cfg->picWidth; e->H = cfg->picHeight; e->log_level = cfg->logLevel;
     e->me_method = cfg->me < 0 ? 1 : cfg->me > 2 ? 2 : cfg->me;        /* EPZS / Cross (-me 3 / 4) are not built: UMH instead */
     e->hex_thr = (e->me_method == 2 && (cfg->preset == QY265PRESET_SLOW || cfg->preset == QY265PRESET_SLOWER)) ? 16 : 0;   /* tME+0x368, SURVEY-measured */
@@ -1707,19 +1618,20 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
     if (e->gop_b > 0) e->refs = 1;
     /* round 6: -ref0 (-preset slow resolves to ref 1 / ref0 3): the anchors of a pyramid search the last ref0 anchors of their GOP (ks265_encode_picture_mref, list 0
      * nearest first = the default list construction); the older anchors stay in every reference picture set in between.  KS265_REF0 overrides (experiments: 1 = round 5's anchors) */
-    e->refs0 = e->hier ? (cfg->ref0 < 1 ? 1 : cfg->ref0 > 4 ? 4 : cfg->ref0) : 1;
-    if (getenv("KS265_REF0") && e->hier) { const int v = atoi(getenv("KS265_REF0")); e->refs0 = v < 1 ? 1 : v > 4 ? 4 : v; }
+    const int ref0 = env_int("KS265_REF0", cfg->ref0);
+    e->refs0 = e->hier ? (ref0 < 1 ? 1 : ref0 > 4 ? 4 : ref0) : 1;
     /* `gpb` (ks265_enc_set_default, KS265_GPB overrides): in force where an anchor can see two anchors - with B pictures and -ref0 > 1; IPPP and zero latency have no such anchors */
-    e->gpb = (getenv("KS265_GPB") ? atoi(getenv("KS265_GPB")) != 0 : g_cli.gpb) && e->gop_b > 0 && e->refs0 > 1;
-    e->base_qp = cfg->rc == 3 ? cfg->crf : cfg->qp;
-    if (e->base_qp < 0) e->base_qp = 0;
-    if (e->base_qp > 51) e->base_qp = 51;
+    e->gpb = env_int("KS265_GPB", g_cli.gpb) != 0 && e->gop_b > 0 && e->refs0 > 1;
+    e->base_qp = lane_base_qp(cfg, cfg->rc);
     e->iper = cfg->iIntraPeriod;
     e->coded_upto = -1; e->gop_end = e->gop_end_seen = -1;
-    e->dev_id = device;
+    /* the SDK's config has no device field: the lane's GPU comes from the handle (KS265_DEVICE: one GPU, default 0; KS265_GPUS / KS265_DEVICES: closed GOPs dealt
+     * to lanes on several GPUs, QY265EncoderOpen) */
+    e->dev_id = device; e->multi = multi;
     long ncpu = sysconf(_SC_NPROCESSORS_ONLN);
     e->nthreads = cfg->threads > 0 ? cfg->threads : (int)(ncpu > 0 ? ncpu : 4);
     if (e->nthreads > 64) e->nthreads = 64;
+    const int ps = e->ct_preset = (int)cfg->preset < 0 || (int)cfg->preset > 8 ? QY265PRESET_SLOW : (int)cfg->preset;   /* the sub-pel knobs and cuTree's tables follow it */
 
     e->rdoq_on = cfg->rdoq == 2;                                      /* asked for by name (QY265ConfigParse); the presets' rdoq 1 = this build's seam */
     if (e->rdoq_on) logf_(2, e->log_level, "ks265enc: -rdoq 1: the luma transform blocks of inter CUs go through the reference's rdoQuant (bit tables from the context states of the stream, %d pictures behind)\n", RC_LAG + 1);
@@ -1737,31 +1649,6 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
     if (e->hier && e->refs0 > 1) logf_(2, e->log_level, "ks265enc: the anchors of the pyramid search the last %d anchors (-ref0)\n", e->refs0);
     if (cfg->rc == 5 || cfg->vbv_buffer_size) logf_(1, e->log_level, "ks265enc: CVQ / VBV are not implemented; running the plain controller\n");
 
-    /* the SDK's config has no device field: the lane's GPU comes from the handle (KS265_DEVICE: one GPU, default 0; KS265_GPUS / KS265_DEVICES: closed GOPs dealt
-     * to lanes on several GPUs, QY265EncoderOpen) */
-    /* The ORDER in which the streams are created matters (round 4, measured at 2160p; DESIGN 6c, tools/hw_queues.hip): a process's normal-priority streams are served by a few
-     * in-order hardware queues (four; three where another runtime user - torch in bench.py - holds one) and share them in pairs that depend on the creation order; a stream that
-     * shares the pixel path's queue runs in turn with it.  With the lookahead there is a fifth stream: created fourth, in front of the key pictures' stream, it cost 25 % (hierarchical
-     * B) / 31 % (IPPP) with not one lookahead kernel launched; created last 8 %; created FIRST nothing measurable - it then pairs with the copy-out stream.  (In the CLI's own
-     * process the four normal streams have a queue each; the key pictures' stream is high-priority and has its own.) */
-    const int la_wanted = e->cfg.lookahead > 0 || (e->cfg.lookahead < 0 && e->hier && e->gop_b == 7 && !getenv("KS265_NO_AUTO_LOOKAHEAD"));
-    const int la_order = getenv("KS265_LA_ORDER") ? atoi(getenv("KS265_LA_ORDER")) : 0;      /* (experiments: 1 = fourth, 2 = last) */
-    if (!getenv("KS265_INPUT_COPY") && getenv("KS265_UPL_ORDER") && atoi(getenv("KS265_UPL_ORDER")) == -1 && (size_t)e->W * e->H * 3 / 2 >= ((size_t)1 << 20)) { if (ks265_create(&e->ctx_upl, device)) e->ctx_upl = NULL; }
-    if (la_wanted && la_order == 0 && ks265_create(&e->ctx_la, device)) e->ctx_la = NULL;
-    /* (not with KS265_GRAPH: the host-synchronous copy out of the caller's memory runs on the runtime's null stream from the CALLING thread, and while another thread has a capture open
-     * that fails - 4 of 6 runs of the 2160p default GOP ended in QY_FAIL, 6 of 6 pass with the copying path; found and fixed at the end of round 6) */
-    e->direct_in = !getenv("KS265_INPUT_COPY") && !getenv("KS265_GRAPH") && (size_t)e->W * e->H * 3 / 2 >= ((size_t)1 << 20) && !(cfg->latency == QY265LATENCY_ZERO && !multi);
-    e->hold_in = getenv("KS265_INPUT_HOLD") && atoi(getenv("KS265_INPUT_HOLD")) > 0;
-    /* the uploads' stream: created first, like the lookahead's.  Its own even beside the lookahead's: the caller waits for the upload, and behind the analysis kernels of the picture
-     * before (measured: 1.17 ms per call instead of the 0.3 ms the DMA takes) it would wait for those too */
-    /* how the upload out of the caller's memory runs.  4 (default): host-synchronous, on no stream of the lane's (ks265_memcpy_h2d_sync): the call returns when the picture is on the device.
-     * 0 / -1 / 1 / 2 (experiments): asynchronously on a stream of its own created first / in front of the lookahead's / after the copy streams / last, waited for at the end of the call.
-     * Measured at 2160p (profiles/r06_input_upload.txt): ANY stream more costs the two-lane default GOP a third of its rate (754 -> 515 .. 600 pictures/s: hardware queues are shared in
-     * creation order, DESIGN 6c) although the caller's input time falls to 0.33 ms; without one the default GOP codes 777 (copying path 758) and IPPP 1 028 (1 025), input 0.88 / 0.26 ms */
-    const int upl_order = getenv("KS265_UPL_ORDER") ? atoi(getenv("KS265_UPL_ORDER")) : 4;
-    if (e->direct_in && upl_order == 0 && ks265_create(&e->ctx_upl, device)) { e->ctx_upl = NULL; e->direct_in = 0; }
-    int r = ks265_create(&e->path[PATH_MAIN].ctx, device);
-    if (r) { *err = hip_rc(r); lane_close(e, 0); return NULL; }       /* KS265_NO_DEVICE -> QY_FAIL: there is no CPU fallback */
     memset(&e->fcfg, 0, sizeof e->fcfg);
     e->fcfg.width = e->W; e->fcfg.height = e->H; e->fcfg.qp = e->base_qp; e->fcfg.lambda_q4 = kLambdaQ4[e->base_qp];
     e->fcfg.me_range = cfg->searchrange < 1 ? 64 : cfg->searchrange > 64 ? 64 : cfg->searchrange;
@@ -1770,37 +1657,199 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
      * estimation functions, rates and lambda table (ks265_frame_cfg.sao = 2: CEncSao::modeDecisionBoEo01 enc@0x4af300 without the merge candidates); every other level > 0 = this build's
      * rule over all four edge classes + band offset (the presets' -sao 4: 2.7 - 4.6 % fewer bytes at equal PSNR-Y than level 3, which buys 0.8 - 1.9 dB of chroma: DESIGN.md) */
     e->fcfg.sao = cfg->sao == 6 ? 3 : cfg->sao == 5 ? 2 : e->use_sao;   /* (5 = -sao 3 BY NAME or -sao-ref 1, 6 = -sao-ref 2: + the merge candidates, QY265ConfigParse; the presets' 3 is the build's rule) */
-    {   /* the sub-pel refinement's knobs follow the preset, as in the reference */
-        const int ps = (int)cfg->preset < 0 || (int)cfg->preset > 8 ? QY265PRESET_SLOW : (int)cfg->preset;
-        e->fcfg.sub_satd = kPresetSubme[ps].satd; e->fcfg.sub_thr = kPresetSubme[ps].thr; e->fcfg.sub_flat = kPresetSubme[ps].flat;
-        e->fcfg.sub_cap = kPresetSubme[ps].cap; e->fcfg.sub_cap_step = kPresetSubme[ps].cap_step; e->fcfg.sub_diag_fast = kPresetSubme[ps].diag_fast;
-    }
+    /* the sub-pel refinement's knobs follow the preset, as in the reference */
+    e->fcfg.sub_satd = kPresetSubme[ps].satd; e->fcfg.sub_thr = kPresetSubme[ps].thr; e->fcfg.sub_flat = kPresetSubme[ps].flat;
+    e->fcfg.sub_cap = kPresetSubme[ps].cap; e->fcfg.sub_cap_step = kPresetSubme[ps].cap_step; e->fcfg.sub_diag_fast = kPresetSubme[ps].diag_fast;
     e->fcfg.bframes = e->gop_b; e->fcfg.refs = e->refs > e->refs_b ? e->refs : e->refs_b; if (e->refs0 > e->fcfg.refs) e->fcfg.refs = e->refs0; e->fcfg.me_hex_thr = e->hex_thr;
     e->fcfg.sdh = 1;                                                    /* the reference's streams have sign_data_hiding_enabled_flag = 1 at every preset */
     e->fcfg.pre_search = 1;                                             /* stage A0: pyramid pre-search vectors as start candidates of the integer search */
     e->fcfg.merge = 1;                                                  /* stage C2: merge pass on the motion field (pictures with one reference per list) */
-    e->fcfg.propagate = getenv("KS265_PROPAGATE") ? atoi(getenv("KS265_PROPAGATE")) & 3 : 1;   /* stage A2: rounds of vector propagation between neighbouring PUs after every
+    e->fcfg.propagate = env_int("KS265_PROPAGATE", 1) & 3;              /* stage A2: rounds of vector propagation between neighbouring PUs after every
                                                                          * integer search (measured with one round: - 21 .. - 23 % bytes of the P / B pictures; the variable is a measuring aid) */
     e->fcfg.intra_inter = 1;                                            /* P / B pictures may hold intra CUs (uncovered regions, occlusions); 2 = none of 8x8: measured + 1.6 % bits, no faster */
     e->fcfg.rdo = 4;                                                    /* coefficient-group pruning at lambda x 1 (ks265_frame_cfg.rdo): supersedes the coefficient decimation of round 2 */
-    e->lean_b = getenv("KS265_LEAN_B") ? atoi(getenv("KS265_LEAN_B")) : 1;           /* non-reference B pictures without intra candidates / joint refinement / SAO (submit) */
-    e->fcfg.skip_rd = getenv("KS265_SKIP_RD") ? atoi(getenv("KS265_SKIP_RD")) & 3 : 1;   /* stage D2 (round 6): after the reconstruction of a B picture, nodes whose merge candidate without
+    e->lean_b = env_int("KS265_LEAN_B", 1);                             /* non-reference B pictures without intra candidates / joint refinement / SAO (submit) */
+    e->fcfg.skip_rd = env_int("KS265_SKIP_RD", 1) & 3;                  /* stage D2 (round 6): after the reconstruction of a B picture, nodes whose merge candidate without
                                                                          * residual is the cheaper coding - on the coded distortion - become one CU (ks265_frame_cfg.skip_rd; 2 = P pictures
                                                                          * too, where it gains nothing measurable; the variable is a measuring aid) */
     e->fcfg.tu_inter = cfg->tuInter > 0 ? 1 : 0;                        /* -intertu N (tuInter; veryslow 1, placebo 2): the residual quadtree of inter CUs ONE level deep (ks265_frame_cfg.tu_inter); deeper values run as 1 */
     e->fcfg.part = cfg->part ? 1 : 0;                                   /* -part 1 (slower, veryslow, placebo): 2NxN / Nx2N prediction units in P and B pictures (ks265_frame_cfg.part) */
-    e->fcfg.bi_refine = getenv("KS265_BI_REFINE") ? atoi(getenv("KS265_BI_REFINE")) : (cfg->preset >= QY265PRESET_SLOWER && cfg->preset <= QY265PRESET_PLACEBO ? 2 : 0);   /* 2 (round 5): after the CU decision, for the CUs it chose; 1 = for every PU of the quadtree.  End of round 6: up to -preset slow it is off - measured on the MI355X at 1080p and 2160p it COSTS 0.5 - 0.7 % bytes at equal PSNR-Y (it lowers the Hadamard cost of residuals the quantiser drops, and pays vector bits) and 134 us per B picture; the presets that trade speed for tools (slower .. placebo) keep it */                                              /* B pictures: joint refinement of the bi-predictive pair (motionSearchBI enc@0x484910) */
-    r = ks265_frame_geometry(&e->fcfg, &e->geom);
-    if (!r) r = ks265_frame_create(main_ctx(e), &e->fcfg, &e->path[PATH_MAIN].frame);
+    e->fcfg.bi_refine = env_int("KS265_BI_REFINE", cfg->preset >= QY265PRESET_SLOWER && cfg->preset <= QY265PRESET_PLACEBO ? 2 : 0);   /* 2 (round 5): after the CU decision, for the CUs it chose; 1 = for every PU of the quadtree.  End of round 6: up to -preset slow it is off - measured on the MI355X at 1080p and 2160p it COSTS 0.5 - 0.7 % bytes at equal PSNR-Y (it lowers the Hadamard cost of residuals the quantiser drops, and pays vector bits) and 134 us per B picture; the presets that trade speed for tools (slower .. placebo) keep it */                                              /* B pictures: joint refinement of the bi-predictive pair (motionSearchBI enc@0x484910) */
+
+    /* the pipeline's switches */
+    e->plan.srcq = !env_set("KS265_NO_SPLIT");
+    e->copy_mb = env_int("KS265_COPYOUT_MB", -1);
+    e->key_overlap = !env_set("KS265_NO_KEY_OVERLAP");
+    e->plan.key_prio = env_int("KS265_KEY_PRIO", 1);                    /* the key picture's wavefront must run underneath the P pictures, not behind them */
+    e->plan.anc_prio = env_int("KS265_ANC_PRIO", 0);
+    { const int sp = env_int("KS265_PIC_SPACER", 0); e->plan.spacer = sp > 0 ? (size_t)sp : 0; }
+    e->ssim_on = cfg->calcSsim != 0 && ks265_ssim_picture && ks265_ssim_picture_on;
+    if (cfg->calcSsim && !e->ssim_on) logf_(2, e->log_level, "ks265enc: SSIM is unavailable: the device library has no ks265_ssim_picture (-ssim is ignored, no ssim line)\n");
+    /* `hash` (ks265_enc_set_default, KS265_HASH overrides; a value the setter would refuse counts as off) */
+    const int hash_req = env_int("KS265_HASH", g_cli.hash);
+    e->hash_on = (hash_req == 2 || hash_req == 3) && ks265_picture_hash && ks265_picture_hash_on ? hash_req : 0;
+    if ((hash_req == 2 || hash_req == 3) && !e->hash_on)                 /* (once per handle: the lanes behind the first log errors only) */
+        logf_(2, e->log_level, "ks265enc: picture hash is unavailable: the device library has no ks265_picture_hash (hash is ignored, no SEI messages)\n");
+    e->aq_on = cfg->iAqMode != 0 && cfg->fAqStrength > 0;
+    /* cuTree: -rc 3 (CRF) with the reference's -cutree 1 (its default), B pictures (with -bframes 0 the reference runs no tree: TEncParam+0x388 = 0, every offset it leaves is zero)
+     * and a lookahead (not -lookahead 0, not zero latency): a QP per CTU from the lookahead window */
+    e->ct_on = cfg->rc == 3 && g_cli.cutree && e->gop_b > 0 && cfg->lookahead != 0 && cfg->latency != QY265LATENCY_ZERO && e->W >= 64 && e->H >= 64 && !env_set("KS265_NO_CUTREE");
+    {   /* how far behind a key picture / a mini-GOP's anchor the window reaches - measured inside the reference (the calcFrameCost calls of every batch, -bframes 3): veryfast 8,
+         * fast / medium 12, slow / veryslow 60, -lookahead 20: 16 - i.e. a queue of L pictures (12 / 16 / 64 by preset, or -lookahead N) in whole mini-GOPs: ((L - 1) / span) span */
+        const int L = cfg->lookahead > 0 ? cfg->lookahead : e->ct_preset <= 2 ? 12 : e->ct_preset <= 4 ? 16 : 64, span = e->gop_b + 1;
+        e->ct_depth = ((L - 1) / span) * span;
+    }
+    if (e->ct_depth < e->gop_b + 1) e->ct_depth = e->gop_b + 1;
+    if (e->ct_depth > CT_RING - 40) e->ct_depth = CT_RING - 40;
+    e->qmap_on = e->aq_on || e->ct_on;
+    e->plan.qmap_path = e->qmap_on ? getenv("KS265_DUMP_QPMAP") : NULL;
+    if (e->ct_on) {                                                    /* the lookahead window's pictures: half size, in blocks of 8 or 16 samples */
+        e->ct_w = e->W / 2; e->ct_h = e->H / 2;
+        e->ct_lg = (kCtPreset[ps].lg4 || (long)e->W * e->H >= 1280L * 720) ? 4 : 3;
+        const int bs = 1 << e->ct_lg;
+        e->ct_nx = (e->ct_w + bs - 1) / bs; e->ct_ny = (e->ct_h + bs - 1) / bs;
+        e->ct_pad = 40 + bs;                                               /* the search leaves the picture by at most merange / 2 + 1 = 33; the last block row / column may overhang it */
+        e->ct_stride = (e->ct_w + 2 * e->ct_pad + 63) & ~63;
+        logf_(1, e->log_level, "ks265enc: -rc 3: cuTree over a lookahead of %d pictures (%d x %d blocks of %d half-size samples; -cutree 0 / -lookahead 0 switch it off): QP per CTU = picture QP + the tree's mean offset\n",
+              e->ct_depth, e->ct_nx, e->ct_ny, 1 << e->ct_lg);
+    }
+    if (e->aq_on && !e->ct_on) { e->aq_nx = (e->W + 15) / 16; e->aq_ny = (e->H + 15) / 16; }       /* blocks that hang over the picture read its padding (replicated edges) */
+    e->ndpb = e->hier ? 10 : e->gop_b ? 4 : e->refs + 2;
+    for (int i = 0; i < MAX_DPB; ++i) e->dpb_poc[i] = NO_PIC;
+    const int graph_asked = env_set("KS265_GRAPH");
+    e->use_graph = graph_asked;                                         /* opt-in since round 4: launch by launch is faster on this runtime (843 against 817 pictures/s, 2160p IPPP) and the split pipeline needs the launches apart */
+    if (e->qmap_on) e->use_graph = 0;                                    /* (a captured picture would replay one map) */
+    if (e->rdoq_on) {
+        e->use_graph = 0;                                                /* (a captured picture would replay one set of tables) */
+        /* rdoQuant's two lambdas by QP (luma weights 256 / 256 = -rdoql / -rdoqls of the reference): (int64)(weight x 0.85 x 2^((qp - 12) / 3) + 0.5) */
+        for (int q = 0; q < 52; ++q) { const double lam = 0.85 * pow(2.0, (q - 12) / 3.0); e->rq_lam[q] = e->rq_lam[52 + q] = (int64_t)(256 * lam + 0.5); }
+    }
+    e->split = e->plan.srcq && !e->use_graph;                           /* (the graph experiment leaves the split pipeline's source pictures allocated and unused) */
+    /* opt-in (KS265_ANCHOR_LANE=1): measured on the MI355X at 2160p, default GOP - 561 pictures/s without, 568 with the lane at normal stream priority, 440 at high priority
+     * (and 382 before the anchor waited for its upload directly); with 8 hardware queues (GPU_MAX_HW_QUEUES) 449 without and 515 with.  The kernels of a picture fill the
+     * device: an anchor running beside B pictures slows them by what it gains */
+    e->anc_on = e->hier && e->refs0 == 1 && e->key_overlap && !e->qmap_on && !e->use_graph && env_int("KS265_ANCHOR_LANE", 0) > 0;
+
+    /* the lookahead and the two optional streams */
+    /* no -lookahead on the command line and the SDK's default GOP (hierarchical B, 8): the slice-type decision runs by itself (round 4: it costs a search of the half-size
+     * picture every fourth picture, and the caller does not wait for it) - the reference's adaptive BiPredFrames is on by default as well.  -lookahead 0 switches it off. */
+    e->la_auto = cfg->lookahead < 0 && e->hier && e->gop_b == 7 && !env_set("KS265_NO_AUTO_LOOKAHEAD");
+    e->plan.la_wanted = cfg->lookahead > 0 || e->la_auto;
+    e->plan.la_order = env_int("KS265_LA_ORDER", 0);                    /* (experiments: 1 = fourth, 2 = last) */
+    e->plan.la_prio = env_int("KS265_LA_PRIO", ENV_UNSET);
+    e->la_w = (e->W / 2) & ~7; e->la_h = (e->H / 2) & ~7;              /* the analysis sees the picture without its last columns / rows when half the size is no multiple of 8 */
+    if (e->plan.la_wanted && (e->la_w < 16 || e->la_h < 16)) { if (!e->la_auto) logf_(1, e->log_level, "ks265enc: -lookahead %d: the analysis needs a picture of at least 32 x 32: off\n", cfg->lookahead); }
+    else if (e->plan.la_wanted) {
+        /* how many pictures may wait for their analysis before the caller waits for the oldest one: five with one lane (the caller is paced by the output anyway); a GOP lane
+         * takes a whole GOP in ahead of its pixel path - its analyses queue up behind two lanes' kernels, and a caller that waited for them fed 770 pictures/s (round 5) */
+        const int keep = env_int("KS265_LA_KEEP", 0);
+        e->la_keep = keep > 0 && keep < LA_QMAX - 8 ? keep : multi ? 48 : 5;
+        e->la_on = 1; e->la_last_key = NO_PIC; e->la_prev_icost = -1; e->mg_adapt = e->hier; e->mg4_until = -1;
+    }
+    if (!e->la_on) e->la_auto = 0;
+    const int big = (size_t)e->W * e->H * 3 / 2 >= ((size_t)1 << 20), in_copy = env_set("KS265_INPUT_COPY");
+    /* (not with KS265_GRAPH: the host-synchronous copy out of the caller's memory runs on the runtime's null stream from the CALLING thread, and while another thread has a capture open
+     * that fails - 4 of 6 runs of the 2160p default GOP ended in QY_FAIL, 6 of 6 pass with the copying path; found and fixed at the end of round 6) */
+    e->direct_in = !in_copy && !graph_asked && big && !(cfg->latency == QY265LATENCY_ZERO && !multi);
+    e->hold_in = env_int("KS265_INPUT_HOLD", 0) > 0;
+    /* how the upload out of the caller's memory runs.  4 (default): host-synchronous, on no stream of the lane's (ks265_memcpy_h2d_sync): the call returns when the picture is on the device.
+     * 0 / -1 / 1 / 2 (experiments): asynchronously on a stream of its own created first / in front of the lookahead's / after the copy streams / last, waited for at the end of the call.
+     * Measured at 2160p (profiles/r06_input_upload.txt): ANY stream more costs the two-lane default GOP a third of its rate (754 -> 515 .. 600 pictures/s: hardware queues are shared in
+     * creation order, DESIGN 6c) although the caller's input time falls to 0.33 ms; without one the default GOP codes 777 (copying path 758) and IPPP 1 028 (1 025), input 0.88 / 0.26 ms */
+    const int upl_order = env_int("KS265_UPL_ORDER", 4);
+    e->plan.upl_at = upl_order == -1 ? (!in_copy && big ? -1 : UPL_NONE) : e->direct_in && upl_order >= 0 && upl_order <= 2 ? upl_order : UPL_NONE;
+    if (e->direct_in && upl_order == 4) e->direct_in = 2;              /* host-synchronous uploads: no stream of their own */
+    else if (e->direct_in && e->plan.upl_at == UPL_NONE) e->direct_in = 0;
+    e->plan.input_slots = env_int("KS265_INPUT_SLOTS", ENV_UNSET);
+    e->plan.pinned_mb = env_int("KS265_PINNED_MB", 4096);
+
+    /* the stream's parameter sets */
+    memset(&e->scfg, 0, sizeof e->scfg);
+    e->scfg.width = e->W; e->scfg.height = e->H; e->scfg.sao = e->use_sao; e->scfg.deblock = e->use_df;
+    e->scfg.sdh = e->fcfg.sdh;
+    e->zero_latency = cfg->latency == QY265LATENCY_ZERO && e->gop_b == 0 && !e->la_on && !multi;
+    e->scfg.cu_qp_delta = e->qmap_on;
+    e->scfg.list_mod = e->gpb;                                          /* the anchors' two lists of past pictures are not the default construction (schedule) */
+    e->scfg.tu_inter = e->fcfg.tu_inter;
+    e->scfg.wpp = 1;                                                    /* CTU rows as substreams: what lets several writer threads share one picture */
+    e->scfg.max_dec_pic_buffering = e->hier ? 10 : e->gop_b ? 4 : e->refs + 1; e->scfg.log2_max_poc_lsb = 16;
+    /* pictures that precede a picture in decoding order and follow it in output order: the whole GOP for the hierarchy (7, as before), ONE (the anchor) for
+     * P + n non-reference B whatever n is (-bframes 1..15) */
+    e->scfg.max_num_reorder = e->hier ? e->gop_b : e->gop_b ? 1 : 0;
+}
+
+/* the sizes that need the frame object's compact layout (cmp_off[7]): the ring of pictures in flight, the writer threads it can feed, the input slots */
+static void lane_rings(Enc *e)
+{
     const size_t fsz = (size_t)e->W * e->H * 3 / 2, npx = (size_t)e->W * e->H;
-    const int dev_id = device;
+    /* ring of pictures in flight: a key picture's slice takes one writer thread many picture periods, and output is in coding order - the ring must
+     * hold everything that is coded meanwhile, or the GPU idles behind it.  About 6 GB of records (pinned compact block + expanded level planes + pinned input), at least 24 and at most MAX_JOBS pictures. */
+    e->ring = (int)(((size_t)6 << 30) / (e->cmp_off[7] + npx * 3 + fsz));
+    if (e->ring > MAX_JOBS) e->ring = MAX_JOBS;
+    if (e->ring < 24) e->ring = 24;
+    if (e->nthreads > e->ring - 14) e->nthreads = e->ring - 14;               /* more writers than pictures that can be in flight would idle */
+    /* input slots: the ring + a mini-GOP.  A GOP lane takes a whole GOP more: the caller hands the GOPs out in stream order, so a lane that could not hold its next GOP
+     * while it is still coding the current one would make the caller wait - and the OTHER lanes, whose next GOPs come after, run dry (measured: lanes idle a third of
+     * the time with ring + 32 slots) */
+    e->nin = e->ring + 32 + (e->la_on ? 8 : 0) + (e->ct_on ? e->ct_depth : 0) + (e->multi ? (e->cfg.iIntraPeriod < 256 ? e->cfg.iIntraPeriod : 256) : 0);
+    if (e->plan.input_slots != ENV_UNSET) e->nin = e->plan.input_slots;
+    if (e->nin < e->ring + 32) e->nin = e->ring + 32;
+    if (e->nin > MAX_INPUT) e->nin = MAX_INPUT;
+    {   /* pinned host memory is a machine-wide resource: a lane's input slots stay under KS265_PINNED_MB (default 4096 MB; the ring + one mini-GOP is the floor).  At 2160p
+         * a slot is 12.4 MB: ring + 32 = 132 slots = 1.6 GB; a GOP lane at -iper 128 asks for 260 = 3.2 GB; eight GPUs with two lanes each = 52 GB without the cap (ADVICE r3) */
+        const long long budget = e->plan.pinned_mb * 1048576LL;
+        const int fit = (int)(budget / (long long)fsz);
+        if (e->nin > fit && fit >= e->ring + 32) {
+            logf_(1, e->log_level, "ks265enc: %d input slots of %.1f MB would pin %.1f GB per lane: %d slots (KS265_PINNED_MB=%lld)\n", e->nin, fsz / 1048576.0, e->nin * (double)fsz / 1073741824.0, fit, budget / 1048576LL);
+            e->nin = fit;
+        } else if (e->nin > fit) {
+            logf_(1, e->log_level, "ks265enc: the ring + one mini-GOP (%d input slots, %.1f GB pinned) is above KS265_PINNED_MB=%lld and is the floor\n", e->ring + 32, (e->ring + 32) * (double)fsz / 1073741824.0, budget / 1048576LL);
+            e->nin = e->ring + 32;
+        }
+    }
+}
+
+/* the lookahead's stream (position 0: first; 1: behind the copy streams; 2: with the lookahead's objects - there also whatever position 0 could not create) and the uploads'
+ * (plan.upl_at): each is created where the plan's position matches.  An uploads' stream that cannot be created means the copying path; the first position of the lookahead's
+ * stream may fail, the others may not */
+static int open_la_stream(Enc *e, int pos)
+{
+    if (!e->plan.la_wanted || e->ctx_la) return KS265_OK;
+    if (pos == 0) { if (e->plan.la_order == 0 && ks265_create(&e->ctx_la, e->dev_id)) e->ctx_la = NULL; return KS265_OK; }
+    if (pos == 1) return e->plan.la_order == 1 ? ks265_create(&e->ctx_la, e->dev_id) : KS265_OK;
+    return e->plan.la_prio != ENV_UNSET ? ks265_create_prio(&e->ctx_la, e->dev_id, e->plan.la_prio) : ks265_create(&e->ctx_la, e->dev_id);
+}
+static void open_upl_stream(Enc *e, int pos)
+{
+    if (e->plan.upl_at == pos && ks265_create(&e->ctx_upl, e->dev_id)) { e->ctx_upl = NULL; if (e->direct_in == 1) e->direct_in = 0; }
+}
+
+static int open_early_streams(Enc *e) { open_upl_stream(e, -1); (void)open_la_stream(e, 0); open_upl_stream(e, 0); return KS265_OK; }
+
+static int open_main(Enc *e)
+{
+    int r = ks265_create(&e->path[PATH_MAIN].ctx, e->dev_id);         /* KS265_NO_DEVICE -> QY_FAIL: there is no CPU fallback */
+    if (!r) r = ks265_frame_geometry(&e->fcfg, &e->geom);
+    if (!r) r = ks265_frame_create(main_ctx(e), &e->fcfg, &e->path[PATH_MAIN].frame);
     if (!r) r = ks265_frame_compact_layout(main_frame(e), e->cmp_off);
-    if (!r) r = ks265_create(&e->ctx_in, dev_id);
-    if (!r) r = ks265_create(&e->ctx_out, dev_id);
-    if (!r && e->direct_in && upl_order == 1) { if (ks265_create(&e->ctx_upl, dev_id)) { e->ctx_upl = NULL; e->direct_in = 0; } }
-    if (!r && la_wanted && la_order == 1) r = ks265_create(&e->ctx_la, dev_id);
-    e->split = getenv("KS265_NO_SPLIT") ? 0 : 1;
-    e->copy_mb = getenv("KS265_COPYOUT_MB") ? atoi(getenv("KS265_COPYOUT_MB")) : -1;
+    if (!r) lane_rings(e);
+    return r;
+}
+static void close_main(Enc *e) { if (main_frame(e)) ks265_frame_destroy(main_frame(e)); }
+
+static int open_copy_streams(Enc *e)
+{
+    int r = ks265_create(&e->ctx_in, e->dev_id);
+    if (!r) r = ks265_create(&e->ctx_out, e->dev_id);
+    if (!r) open_upl_stream(e, 1);
+    if (!r) r = open_la_stream(e, 1);
+    return r;
+}
+
+static int open_pipeline(Enc *e)
+{
+    const size_t fsz = (size_t)e->W * e->H * 3 / 2;
+    int r = KS265_OK;
     for (int k = 0; k < NPIPE && !r; ++k) {
         r = ks265_dev_malloc(main_ctx(e), (void **)&e->dev_in[k], fsz);
         if (!r) r = ks265_dev_malloc(main_ctx(e), (void **)&e->stg[k], e->cmp_off[7]);
@@ -1811,43 +1860,40 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
         if (!r) r = ks265_event_create(main_ctx(e), &e->ev_drained[k]);
         if (!r) r = ks265_event_create(main_ctx(e), &e->ev_coded[k]);
         if (!r) r = ks265_event_create(main_ctx(e), &e->ev_packed[k]);
-        if (!r && e->split) r = pic_alloc(e, &e->srcq[k]);
+        if (!r && e->plan.srcq) r = pic_alloc(e, &e->srcq[k]);
     }
-    if (!r) r = ks265_dev_malloc(main_ctx(e), (void **)&e->path[PATH_MAIN].dev_sse, 64);
-    e->ssim_on = cfg->calcSsim != 0 && ks265_ssim_picture && ks265_ssim_picture_on;
-    if (cfg->calcSsim && !e->ssim_on) logf_(2, e->log_level, "ks265enc: SSIM is unavailable: the device library has no ks265_ssim_picture (-ssim is ignored, no ssim line)\n");
+    return r;
+}
+static void close_pipeline(Enc *e)
+{
+    for (int k = 0; k < NPIPE; ++k) {
+        ks265_dev_free(main_ctx(e), e->dev_in[k]); ks265_dev_free(main_ctx(e), e->stg[k]);
+        ev_free(main_ctx(e), &e->ev_h2d[k]); ev_free(main_ctx(e), &e->ev_loaded[k]); ev_free(main_ctx(e), &e->ev_staged[k]);
+        ev_free(main_ctx(e), &e->ev_drained[k]); ev_free(main_ctx(e), &e->ev_coded[k]); ev_free(main_ctx(e), &e->ev_packed[k]);
+        pic_free(e, &e->srcq[k]);
+    }
+}
+
+static int open_quality(Enc *e)
+{
+    int r = ks265_dev_malloc(main_ctx(e), (void **)&e->path[PATH_MAIN].dev_sse, 64);
     if (!r && e->ssim_on) r = ks265_dev_malloc(main_ctx(e), (void **)&e->path[PATH_MAIN].dev_ssim, 96);
-    /* `hash` (ks265_enc_set_default, KS265_HASH overrides; a value the setter would refuse counts as off) */
-    const int hash_req = getenv("KS265_HASH") ? atoi(getenv("KS265_HASH")) : g_cli.hash;
-    e->hash_on = (hash_req == 2 || hash_req == 3) && ks265_picture_hash && ks265_picture_hash_on ? hash_req : 0;
-    if ((hash_req == 2 || hash_req == 3) && !e->hash_on)                 /* (once per handle: the lanes behind the first log errors only) */
-        logf_(2, e->log_level, "ks265enc: picture hash is unavailable: the device library has no ks265_picture_hash (hash is ignored, no SEI messages)\n");
     if (!r && e->hash_on) r = ks265_dev_malloc(main_ctx(e), (void **)&e->path[PATH_MAIN].dev_hash, 96);
-    e->aq_on = cfg->iAqMode != 0 && cfg->fAqStrength > 0;
-    /* cuTree: -rc 3 (CRF) with the reference's -cutree 1 (its default), B pictures (with -bframes 0 the reference runs no tree: TEncParam+0x388 = 0, every offset it leaves is zero)
-     * and a lookahead (not -lookahead 0, not zero latency): a QP per CTU from the lookahead window */
-    e->ct_preset = (int)cfg->preset < 0 || (int)cfg->preset > 8 ? QY265PRESET_SLOW : (int)cfg->preset;
-    e->ct_on = cfg->rc == 3 && g_cli.cutree && e->gop_b > 0 && cfg->lookahead != 0 && cfg->latency != QY265LATENCY_ZERO && e->W >= 64 && e->H >= 64 && !getenv("KS265_NO_CUTREE");
-    {   /* how far behind a key picture / a mini-GOP's anchor the window reaches - measured inside the reference (the calcFrameCost calls of every batch, -bframes 3): veryfast 8,
-         * fast / medium 12, slow / veryslow 60, -lookahead 20: 16 - i.e. a queue of L pictures (12 / 16 / 64 by preset, or -lookahead N) in whole mini-GOPs: ((L - 1) / span) span */
-        const int L = cfg->lookahead > 0 ? cfg->lookahead : e->ct_preset <= 2 ? 12 : e->ct_preset <= 4 ? 16 : 64, span = e->gop_b + 1;
-        e->ct_depth = ((L - 1) / span) * span;
-    }
-    if (e->ct_depth < e->gop_b + 1) e->ct_depth = e->gop_b + 1;
-    if (e->ct_depth > CT_RING - 40) e->ct_depth = CT_RING - 40;
-    e->qmap_on = e->aq_on || e->ct_on;
-    if (e->qmap_on && getenv("KS265_DUMP_QPMAP")) e->qmap_fd = open(getenv("KS265_DUMP_QPMAP"), O_WRONLY | O_CREAT | O_APPEND, 0644);
-    if (!r && e->ct_on) {
-        r = ct_open(e, dev_id);
-        logf_(1, e->log_level, "ks265enc: -rc 3: cuTree over a lookahead of %d pictures (%d x %d blocks of %d half-size samples; -cutree 0 / -lookahead 0 switch it off): QP per CTU = picture QP + the tree's mean offset\n",
-              e->ct_depth, e->ct_nx, e->ct_ny, 1 << e->ct_lg);
-    }
+    return r;
+}
+static void close_quality(Enc *e) { ks265_dev_free(main_ctx(e), e->path[PATH_MAIN].dev_sse); ks265_dev_free(main_ctx(e), e->path[PATH_MAIN].dev_ssim); ks265_dev_free(main_ctx(e), e->path[PATH_MAIN].dev_hash); }
+
+/* what a QP per CTU needs: cuTree's stream and ring (ct_open), the maps of the pipeline's slots and of the key pictures, -aq's buffers where cuTree does not compute the offsets */
+static int open_qmaps(Enc *e)
+{
+    int r = KS265_OK;
+    if (e->plan.qmap_path) e->qmap_fd = open(e->plan.qmap_path, O_WRONLY | O_CREAT | O_APPEND, 0644);
+    if (e->ct_on) r = ct_open(e);
     if (e->qmap_on) {
         for (int k = 0; k < NPIPE && !r; ++k) r = ks265_dev_malloc(main_ctx(e), (void **)&e->dev_qmap[k], (size_t)e->geom.ctu_cols * e->geom.ctu_rows);
         for (int q = 0; q < 2 && !r; ++q) r = ks265_dev_malloc(main_ctx(e), (void **)&e->dev_qmap_key[q], (size_t)e->geom.ctu_cols * e->geom.ctu_rows);
     }
     if (e->aq_on && !e->ct_on) {
-        e->aq_nx = (e->W + 15) / 16; e->aq_ny = (e->H + 15) / 16;       /* blocks that hang over the picture read its padding (replicated edges) */
         const size_t nb = (size_t)e->aq_nx * e->aq_ny;
         for (int q = PATH_MAIN; q <= PATH_KEY && !r; ++q) {
             r = ks265_dev_malloc(main_ctx(e), (void **)&e->path[q].aq_off, nb * 8);
@@ -1856,75 +1902,122 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
         }
         e->path[PATH_ANC].aq_off = e->path[PATH_MAIN].aq_off; e->path[PATH_ANC].aq_inv = e->path[PATH_MAIN].aq_inv; e->path[PATH_ANC].aq_scratch = e->path[PATH_MAIN].aq_scratch;
     }
-    if (!r) r = pic_alloc(e, &e->path[PATH_MAIN].src);
-    e->ndpb = e->hier ? 10 : e->gop_b ? 4 : e->refs + 2;
-    for (int i = 0; i < MAX_DPB; ++i) e->dpb_poc[i] = -1000000;
+    return r;
+}
+static void close_qmaps(Enc *e)
+{
+    for (int q = PATH_MAIN; q <= PATH_KEY; ++q) { ks265_dev_free(main_ctx(e), e->path[q].aq_off); ks265_dev_free(main_ctx(e), e->path[q].aq_inv); ks265_dev_free(main_ctx(e), e->path[q].aq_scratch); }
+    for (int k = 0; k < NPIPE; ++k) ks265_dev_free(main_ctx(e), e->dev_qmap[k]);
+    for (int q = 0; q < 2; ++q) ks265_dev_free(main_ctx(e), e->dev_qmap_key[q]);
+    if (e->qmap_fd >= 0) close(e->qmap_fd);
+    ct_close(e);
+}
+
+static int open_dpb(Enc *e)
+{
+    int r = pic_alloc(e, &e->path[PATH_MAIN].src);
     for (int i = 0; i < e->ndpb && !r; ++i) r = pic_alloc(e, &e->dpb[i]);
-    e->key_overlap = getenv("KS265_NO_KEY_OVERLAP") ? 0 : 1;
-    e->use_graph = getenv("KS265_GRAPH") ? 1 : 0;                     /* opt-in since round 4: launch by launch is faster on this runtime (843 against 817 pictures/s, 2160p IPPP) and the split pipeline needs the launches apart */
-    if (e->qmap_on) e->use_graph = 0;                                    /* (a captured picture would replay one map) */
-    if (e->rdoq_on) {
-        e->use_graph = 0;                                                /* (a captured picture would replay one set of tables) */
-        e->rq_hist = (int32_t *)calloc((size_t)RQ_HIST * 1440, sizeof(int32_t));
-        if (!e->rq_hist) r = KS265_OUTOFMEMORY;
-        /* rdoQuant's two lambdas by QP (luma weights 256 / 256 = -rdoql / -rdoqls of the reference): (int64)(weight x 0.85 x 2^((qp - 12) / 3) + 0.5) */
-        for (int q = 0; q < 52; ++q) { const double lam = 0.85 * pow(2.0, (q - 12) / 3.0); e->rq_lam[q] = e->rq_lam[52 + q] = (int64_t)(256 * lam + 0.5); }
+    return r;
+}
+static void close_dpb(Enc *e)                                          /* (and the spacers in front of the lane's pictures: pic_alloc) */
+{
+    for (int i = 0; i < e->ndpb; ++i) pic_free(e, &e->dpb[i]);
+    for (int i = 0; i < e->nspacer; ++i) ks265_dev_free(main_ctx(e), e->spacer[i]);
+    pic_free(e, &e->path[PATH_MAIN].src);
+}
+
+/* a pixel path beside the main one (the key pictures', the anchors'): a stream of the given priority, a frame object on it, a source picture, the block of its SSE sums */
+static int path_open(Enc *e, int which, int prio)
+{
+    PixPath *p = &e->path[which];
+    int r = ks265_create_prio(&p->ctx, e->dev_id, prio);
+    if (!r) r = ks265_frame_create(p->ctx, &e->fcfg, &p->frame);
+    if (!r) r = pic_alloc(e, &p->src);
+    if (!r) r = ks265_dev_malloc(main_ctx(e), (void **)&p->dev_sse, 64);
+    if (e->path[PATH_MAIN].dev_ssim) p->dev_ssim = e->path[PATH_MAIN].dev_ssim + 4 * which;
+    if (e->path[PATH_MAIN].dev_hash) p->dev_hash = e->path[PATH_MAIN].dev_hash + 8 * which;
+    return r;
+}
+static void path_close(Enc *e, int which)                              /* the path's stream runs dry before its frame object goes (the contexts: last, lane_close) */
+{
+    PixPath *p = &e->path[which];
+    if (p->ctx) ks265_synchronize(p->ctx);
+    if (p->frame) ks265_frame_destroy(p->frame);
+    pic_free(e, &p->src); ks265_dev_free(main_ctx(e), p->dev_sse);
+}
+
+static int open_key_path(Enc *e)
+{
+    if (!e->key_overlap) return KS265_OK;
+    int r = path_open(e, PATH_KEY, e->plan.key_prio);
+    if (!r) r = ks265_event_create(main_ctx(e), &e->ev_key);
+    for (int i = 0; i < 2 && !r; ++i) { r = pic_alloc(e, &e->dpb[e->ndpb + i]); if (!r) r = ks265_event_create(main_ctx(e), &e->ev_firstp[i]); }
+    return r;
+}
+static void close_key_path(Enc *e)
+{
+    for (int i = 0; i < 2; ++i) { pic_free(e, &e->dpb[e->ndpb + i]); ev_free(main_ctx(e), &e->ev_firstp[i]); }
+    ev_free(main_ctx(e), &e->ev_key);
+    path_close(e, PATH_KEY);
+}
+
+static int open_anchor_path(Enc *e)
+{
+    if (!e->anc_on) return KS265_OK;
+    int r = path_open(e, PATH_ANC, e->plan.anc_prio);
+    if (!r) r = ks265_event_create(main_ctx(e), &e->ev_anc);
+    for (int i = 0; i < 8 && !r; ++i) r = ks265_event_create(main_ctx(e), &e->ev_mg[i]);
+    for (int i = 0; i < 4 && !r; ++i) r = pic_alloc(e, &e->dpb[e->ndpb + 2 + i]);
+    return r;
+}
+static void close_anchor_path(Enc *e)
+{
+    path_close(e, PATH_ANC);
+    ev_free(main_ctx(e), &e->ev_anc);
+    for (int i = 0; i < 8; ++i) ev_free(main_ctx(e), &e->ev_mg[i]);
+    for (int i = 0; i < 4; ++i) pic_free(e, &e->dpb[e->ndpb + 2 + i]);
+}
+
+static int open_lookahead(Enc *e)
+{
+    if (!e->la_on) return KS265_OK;
+    ks265_frame_cfg lc; memset(&lc, 0, sizeof lc);
+    lc.width = e->la_w; lc.height = e->la_h; lc.qp = e->base_qp > 0 ? e->base_qp : 27; lc.lambda_q4 = kLambdaQ4[lc.qp < 52 ? lc.qp : 51]; lc.me_range = 32; lc.me_method = 1; lc.subme = 0;
+    lc.bframes = 0; lc.refs = 1;
+    int r = open_la_stream(e, 2);
+    if (!r) r = ks265_frame_geometry(&lc, &e->geom_la);
+    if (!r) r = ks265_frame_create(e->ctx_la, &lc, &e->frame_la);
+    for (int i = 0; i < LA_RING && !r; ++i) {
+        r = ks265_dev_malloc(e->ctx_la, (void **)&e->la_pic[i].y, (size_t)e->geom_la.bytes_y);
+        if (!r) r = ks265_dev_malloc(e->ctx_la, (void **)&e->la_pic[i].u, (size_t)e->geom_la.bytes_c);
+        if (!r) r = ks265_dev_malloc(e->ctx_la, (void **)&e->la_pic[i].v, (size_t)e->geom_la.bytes_c);
+        if (!r) r = ks265_memset_async(e->ctx_la, e->la_pic[i].u, 128, (size_t)e->geom_la.bytes_c);     /* the analysis is luma only */
+        if (!r) r = ks265_memset_async(e->ctx_la, e->la_pic[i].v, 128, (size_t)e->geom_la.bytes_c);
     }
-    if (e->use_graph) e->split = 0;
-    if (e->key_overlap) {
-        if (!r) r = path_open(e, PATH_KEY, dev_id, getenv("KS265_KEY_PRIO") ? atoi(getenv("KS265_KEY_PRIO")) : 1);   /* the key picture's wavefront must run underneath the P pictures, not behind them */
-        if (!r) r = ks265_event_create(main_ctx(e), &e->ev_key);
-        for (int i = 0; i < 2 && !r; ++i) { r = pic_alloc(e, &e->dpb[e->ndpb + i]); e->dpb_poc[e->ndpb + i] = -1000000; if (!r) r = ks265_event_create(main_ctx(e), &e->ev_firstp[i]); }
-    }
-    /* opt-in (KS265_ANCHOR_LANE=1): measured on the MI355X at 2160p, default GOP - 561 pictures/s without, 568 with the lane at normal stream priority, 440 at high priority
-     * (and 382 before the anchor waited for its upload directly); with 8 hardware queues (GPU_MAX_HW_QUEUES) 449 without and 515 with.  The kernels of a picture fill the
-     * device: an anchor running beside B pictures slows them by what it gains */
-    e->anc_on = e->hier && e->refs0 == 1 && e->key_overlap && !e->qmap_on && !e->use_graph && getenv("KS265_ANCHOR_LANE") && atoi(getenv("KS265_ANCHOR_LANE")) > 0;
-    if (e->anc_on) {
-        if (!r) r = path_open(e, PATH_ANC, dev_id, getenv("KS265_ANC_PRIO") ? atoi(getenv("KS265_ANC_PRIO")) : 0);
-        if (!r) r = ks265_event_create(main_ctx(e), &e->ev_anc);
-        for (int i = 0; i < 8 && !r; ++i) r = ks265_event_create(main_ctx(e), &e->ev_mg[i]);
-        for (int i = 0; i < 4 && !r; ++i) { r = pic_alloc(e, &e->dpb[e->ndpb + 2 + i]); e->dpb_poc[e->ndpb + 2 + i] = -1000000; }
-    }
-    /* ring of pictures in flight: a key picture's slice takes one writer thread many picture periods, and output is in coding order - the ring must
-     * hold everything that is coded meanwhile, or the GPU idles behind it.  About 6 GB of records (pinned compact block + expanded level planes + pinned input), at least 24 and at most MAX_JOBS pictures. */
-    /* (the lookahead's objects; its stream was created first - see the top of this function) */
-    /* no -lookahead on the command line and the SDK's default GOP (hierarchical B, 8): the slice-type decision runs by itself (round 4: it costs a search of the half-size
-     * picture every fourth picture, and the caller does not wait for it) - the reference's adaptive BiPredFrames is on by default as well.  -lookahead 0 switches it off. */
-    const int la_auto = cfg->lookahead < 0 && e->hier && e->gop_b == 7 && !getenv("KS265_NO_AUTO_LOOKAHEAD");
-    if (!r && (cfg->lookahead > 0 || la_auto)) {
-        const int w = (e->W / 2) & ~7, h = (e->H / 2) & ~7;            /* the analysis sees the picture without its last columns / rows when half the size is no multiple of 8 */
-        if (w < 16 || h < 16) { if (!la_auto) logf_(1, e->log_level, "ks265enc: -lookahead %d: the analysis needs a picture of at least 32 x 32: off\n", cfg->lookahead); }
-        else {
-            ks265_frame_cfg lc; memset(&lc, 0, sizeof lc);
-            lc.width = w; lc.height = h; lc.qp = e->base_qp > 0 ? e->base_qp : 27; lc.lambda_q4 = kLambdaQ4[lc.qp < 52 ? lc.qp : 51]; lc.me_range = 32; lc.me_method = 1; lc.subme = 0;
-            lc.bframes = 0; lc.refs = 1;
-            r = e->ctx_la ? 0 : getenv("KS265_LA_PRIO") ? ks265_create_prio(&e->ctx_la, dev_id, atoi(getenv("KS265_LA_PRIO"))) : ks265_create(&e->ctx_la, dev_id);
-            if (!r) r = ks265_frame_geometry(&lc, &e->geom_la);
-            if (!r) r = ks265_frame_create(e->ctx_la, &lc, &e->frame_la);
-            for (int i = 0; i < LA_RING && !r; ++i) {
-                r = ks265_dev_malloc(e->ctx_la, (void **)&e->la_pic[i].y, (size_t)e->geom_la.bytes_y);
-                if (!r) r = ks265_dev_malloc(e->ctx_la, (void **)&e->la_pic[i].u, (size_t)e->geom_la.bytes_c);
-                if (!r) r = ks265_dev_malloc(e->ctx_la, (void **)&e->la_pic[i].v, (size_t)e->geom_la.bytes_c);
-                if (!r) r = ks265_memset_async(e->ctx_la, e->la_pic[i].u, 128, (size_t)e->geom_la.bytes_c);     /* the analysis is luma only */
-                if (!r) r = ks265_memset_async(e->ctx_la, e->la_pic[i].v, 128, (size_t)e->geom_la.bytes_c);
-            }
-            if (!r) r = ks265_dev_malloc(e->ctx_la, (void **)&e->la_cost_ws, (size_t)e->geom_la.ctu_cols * e->geom_la.ctu_rows * 85 * sizeof(uint32_t));
-            if (!r) r = ks265_dev_malloc(e->ctx_la, (void **)&e->la_dev_out, LA_FLY * 128);
-            if (!r) r = ks265_host_malloc(e->ctx_la, (void **)&e->la_host_out, LA_FLY * 128);
-            for (int i = 0; i < LA_FLY && !r; ++i) r = ks265_event_create(e->ctx_la, &e->la_evs[i]);
-            /* how many pictures may wait for their analysis before the caller waits for the oldest one: five with one lane (the caller is paced by the output anyway); a GOP lane
-             * takes a whole GOP in ahead of its pixel path - its analyses queue up behind two lanes' kernels, and a caller that waited for them fed 770 pictures/s (round 5) */
-            e->la_keep = getenv("KS265_LA_KEEP") && atoi(getenv("KS265_LA_KEEP")) > 0 && atoi(getenv("KS265_LA_KEEP")) < LA_QMAX - 8 ? atoi(getenv("KS265_LA_KEEP")) : multi ? 48 : 5;
-            if (!r) { e->la_on = 1; e->la_auto = la_auto; e->la_last_key = -1000000; e->la_prev_icost = -1; e->la_w = w; e->la_h = h; e->mg_adapt = e->hier; e->mg4_until = -1; }
-        }
-    }
-    e->ring = (int)(((size_t)6 << 30) / (e->cmp_off[7] + npx * 3 + fsz));
-    if (e->ring > MAX_JOBS) e->ring = MAX_JOBS;
-    if (e->ring < 24) e->ring = 24;
-    if (e->nthreads > e->ring - 14) e->nthreads = e->ring - 14;               /* more writers than pictures that can be in flight would idle */
-    const int njobs_alloc = e->ring;
-    for (int i = 0; i < njobs_alloc && !r; ++i) {
+    if (!r) r = ks265_dev_malloc(e->ctx_la, (void **)&e->la_cost_ws, (size_t)e->geom_la.ctu_cols * e->geom_la.ctu_rows * 85 * sizeof(uint32_t));
+    if (!r) r = ks265_dev_malloc(e->ctx_la, (void **)&e->la_dev_out, LA_FLY * 128);
+    if (!r) r = ks265_host_malloc(e->ctx_la, (void **)&e->la_host_out, LA_FLY * 128);
+    for (int i = 0; i < LA_FLY && !r; ++i) r = ks265_event_create(e->ctx_la, &e->la_evs[i]);
+    return r;
+}
+static void close_lookahead(Enc *e)                                    /* (the stream may be all there is: it is created first, before the main context) */
+{
+    if (!e->ctx_la) return;
+    ks265_synchronize(e->ctx_la);
+    for (int i = 0; i < LA_RING; ++i) { ks265_dev_free(e->ctx_la, e->la_pic[i].y); ks265_dev_free(e->ctx_la, e->la_pic[i].u); ks265_dev_free(e->ctx_la, e->la_pic[i].v); }
+    ks265_dev_free(e->ctx_la, e->la_cost_ws); ks265_dev_free(e->ctx_la, e->la_dev_out); ks265_host_free(e->ctx_la, e->la_host_out);
+    for (int i = 0; i < LA_FLY; ++i) ev_free(e->ctx_la, &e->la_evs[i]);
+    if (e->frame_la) ks265_frame_destroy(e->frame_la);
+    ks265_destroy(e->ctx_la);
+    e->ctx_la = NULL;
+}
+
+static int open_jobs(Enc *e)
+{
+    const size_t npx = (size_t)e->W * e->H;
+    int r = KS265_OK;
+    if (e->rdoq_on && !(e->rq_hist = (int32_t *)calloc((size_t)RQ_HIST * 1440, sizeof(int32_t)))) r = KS265_OUTOFMEMORY;
+    for (int i = 0; i < e->ring && !r; ++i) {
         Job *j = &e->jobs[i];
         r = ks265_host_malloc(main_ctx(e), (void **)&j->cmp, e->cmp_off[7]);
         if (!r) {
@@ -1943,72 +2036,158 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
         j->nal = (uint8_t *)malloc(j->nal_cap);
         if (!j->nal) r = KS265_OUTOFMEMORY;
     }
-    /* input slots: the ring + a mini-GOP.  A GOP lane takes a whole GOP more: the caller hands the GOPs out in stream order, so a lane that could not hold its next GOP
-     * while it is still coding the current one would make the caller wait - and the OTHER lanes, whose next GOPs come after, run dry (measured: lanes idle a third of
-     * the time with ring + 32 slots) */
-    e->nin = e->ring + 32 + (e->la_on ? 8 : 0) + (e->ct_on ? e->ct_depth : 0) + (multi ? (cfg->iIntraPeriod < 256 ? cfg->iIntraPeriod : 256) : 0);
-    if (getenv("KS265_INPUT_SLOTS")) e->nin = atoi(getenv("KS265_INPUT_SLOTS"));
-    if (e->nin < e->ring + 32) e->nin = e->ring + 32;
-    if (e->nin > MAX_INPUT) e->nin = MAX_INPUT;
-    {   /* pinned host memory is a machine-wide resource: a lane's input slots stay under KS265_PINNED_MB (default 4096 MB; the ring + one mini-GOP is the floor).  At 2160p
-         * a slot is 12.4 MB: ring + 32 = 132 slots = 1.6 GB; a GOP lane at -iper 128 asks for 260 = 3.2 GB; eight GPUs with two lanes each = 52 GB without the cap (ADVICE r3) */
-        const char *pm = getenv("KS265_PINNED_MB");
-        const long long budget = (pm ? atoll(pm) : 4096) * 1048576LL;
-        const int fit = (int)(budget / (long long)fsz);
-        if (e->nin > fit && fit >= e->ring + 32) {
-            logf_(1, e->log_level, "ks265enc: %d input slots of %.1f MB would pin %.1f GB per lane: %d slots (KS265_PINNED_MB=%lld)\n", e->nin, fsz / 1048576.0, e->nin * (double)fsz / 1073741824.0, fit, budget / 1048576LL);
-            e->nin = fit;
-        } else if (e->nin > fit) {
-            logf_(1, e->log_level, "ks265enc: the ring + one mini-GOP (%d input slots, %.1f GB pinned) is above KS265_PINNED_MB=%lld and is the floor\n", e->ring + 32, (e->ring + 32) * (double)fsz / 1073741824.0, budget / 1048576LL);
-            e->nin = e->ring + 32;
-        }
+    return r;
+}
+static void close_jobs(Enc *e)
+{
+    for (int i = 0; i < MAX_JOBS; ++i) {
+        Job *j = &e->jobs[i];
+        ks265_host_free(main_ctx(e), j->cmp); ks265_host_free(main_ctx(e), j->recon); ks265_host_free(main_ctx(e), j->qp_map); ks265_host_free(main_ctx(e), j->ssim); ks265_host_free(main_ctx(e), j->hash); ks265_host_free(main_ctx(e), j->rq_host); free(j->lvlbuf); free(j->dirty);
+        ev_free(main_ctx(e), &j->ev);
+        free(j->nal);
     }
+    free(e->rq_hist);
+}
+
+static int open_inputs(Enc *e)
+{
+    const size_t fsz = (size_t)e->W * e->H * 3 / 2;
+    int r = KS265_OK;
     for (int i = 0; i < e->nin && !r; ++i) r = ks265_host_malloc(main_ctx(e), (void **)&e->in[i].i420, fsz);
     /* with the lookahead every input slot has a twin on the device, uploaded on the lookahead's stream the moment the picture is handed in (nothing on that stream ever waits for
      * the pipeline: an upload enqueued on the copy-in stream, or anywhere on the copy engine behind that stream's uploads, sits behind the pipeline's back-pressure and the
      * analysis would see the picture 10 ms and more late); without it the picture is uploaded when it is scheduled, on the copy-in stream, as before.  One stream for both,
-     * not a sixth: a stream more is a hardware queue shared with somebody (top of this function) */
-    if (e->direct_in && upl_order == 2) { if (ks265_create(&e->ctx_upl, dev_id)) { e->ctx_upl = NULL; e->direct_in = 0; } }
-    if (e->direct_in && upl_order == 4) e->direct_in = 2;              /* host-synchronous uploads: no stream of their own */
-    if (e->direct_in == 1 && !e->ctx_upl) e->direct_in = 0;
-
+     * not a sixth: a stream more is a hardware queue shared with somebody (lane_open) */
+    open_upl_stream(e, 2);
     if ((e->la_on && e->ctx_la) || e->direct_in) {
         e->ctx_up = e->direct_in == 1 && e->ctx_upl ? e->ctx_upl : e->ctx_la ? e->ctx_la : main_ctx(e);
         reg_handle(main_ctx(e), 1);
         for (int i = 0; i < e->nin && !r; ++i) { r = ks265_dev_malloc(main_ctx(e), (void **)&e->in[i].dev, fsz); if (!r) r = ks265_event_create(e->ctx_up, &e->in[i].ev_up); }
         logf_(2, e->log_level, "ks265enc: %d input slots with a device twin each: %.2f GB of device memory per lane (KS265_INPUT_SLOTS / KS265_PINNED_MB bound the slot count)\n", e->nin, e->nin * (double)fsz / 1073741824.0);
     }
-    if (r) { *err = hip_rc(r); lane_close(e, 0); return NULL; }
-    memset(&e->scfg, 0, sizeof e->scfg);
-    e->scfg.width = e->W; e->scfg.height = e->H; e->scfg.sao = e->use_sao; e->scfg.deblock = e->use_df;
-    e->scfg.sdh = e->fcfg.sdh;
-    e->zero_latency = cfg->latency == QY265LATENCY_ZERO && e->gop_b == 0 && !e->la_on && !multi;
-    e->scfg.cu_qp_delta = e->qmap_on;
-    e->scfg.list_mod = e->gpb;                                          /* the anchors' two lists of past pictures are not the default construction (schedule) */
-    e->scfg.tu_inter = e->fcfg.tu_inter;
-    e->scfg.wpp = 1;                                                    /* CTU rows as substreams: what lets several writer threads share one picture */
-    e->scfg.max_dec_pic_buffering = e->hier ? 10 : e->gop_b ? 4 : e->refs + 1; e->scfg.log2_max_poc_lsb = 16;
-    /* pictures that precede a picture in decoding order and follow it in output order: the whole GOP for the hierarchy (7, as before), ONE (the anchor) for
-     * P + n non-reference B whatever n is (-bframes 1..15) */
-    e->scfg.max_num_reorder = e->hier ? e->gop_b : e->gop_b ? 1 : 0;
+    return r;
+}
+static void close_inputs(Enc *e)                                       /* (also what lane_enable_device_input added: twins, their events, the handle's count) */
+{
+    for (int i = 0; i < MAX_INPUT; ++i) { ks265_host_free(main_ctx(e), e->in[i].i420); ks265_dev_free(main_ctx(e), e->in[i].dev); ev_free(e->ctx_up, &e->in[i].ev_up); }
+}
+static void close_input_streams(Enc *e)                                /* behind the lookahead (ctx_up may be its stream) */
+{
+    if (e->ctx_up) reg_handle(main_ctx(e), 0);
+    if (e->ctx_upl) { ks265_synchronize(e->ctx_upl); ks265_destroy(e->ctx_upl); }
+}
+
+static int open_output(Enc *e)                                         /* host memory only: the parameter sets, the NAL buffer, the writers' job memory */
+{
     e->hdr = (uint8_t *)malloc(512);
     if (e->hdr) {
         long a = ks265_write_vps(&e->scfg, e->hdr, 512), b = a > 0 ? ks265_write_sps(&e->scfg, e->hdr + a, 512 - (size_t)a) : -1, c = b > 0 ? ks265_write_pps(&e->scfg, e->hdr + a + b, 512 - (size_t)(a + b)) : -1;
         e->hdr_len = c > 0 ? a + b + c : -1;
         e->hdr_part[0] = a; e->hdr_part[1] = b; e->hdr_part[2] = c;
     }
-    e->outcap = npx + 65536;
+    e->outcap = (size_t)e->W * e->H + 65536;
     e->outbuf = (uint8_t *)malloc(e->outcap);
-    if (!e->hdr || e->hdr_len < 0 || !e->outbuf) { *err = QY_FAIL; lane_close(e, 0); return NULL; }
-    for (int i = 0; i < e->ring; ++i) { e->jobs[i].wpp = malloc(ks265_wpp_bytes(&e->scfg)); if (!e->jobs[i].wpp) { *err = QY_OUTOFMEMORY; lane_close(e, 0); return NULL; } }   /* virtual until used */
-    if (e->md5) {                                                       /* -md5 1: plane MD5s of every reconstructed picture */
-        e->md5_ring = calloc(256, sizeof *e->md5_ring); e->md5_have = calloc(256, 1);
-        if (!e->md5_ring || !e->md5_have || lane_recon_on(e)) { *err = QY_OUTOFMEMORY; lane_close(e, 0); return NULL; }
-    }
+    if (!e->hdr || e->hdr_len < 0 || !e->outbuf) return KS265_FAIL;
+    for (int i = 0; i < e->ring; ++i) if (!(e->jobs[i].wpp = malloc(ks265_wpp_bytes(&e->scfg)))) return KS265_OUTOFMEMORY;   /* virtual until used */
+    return KS265_OK;
+}
+static void close_output(Enc *e)
+{
+    for (int i = 0; i < MAX_JOBS; ++i) free(e->jobs[i].wpp);
+    free(e->hdr); free(e->outbuf);
+}
+
+static int open_md5(Enc *e)                                            /* -md5 1: plane MD5s of every reconstructed picture */
+{
+    if (!e->md5) return KS265_OK;
+    e->md5_ring = calloc(256, sizeof *e->md5_ring); e->md5_have = calloc(256, 1);
+    return !e->md5_ring || !e->md5_have || lane_recon_on(e) ? KS265_OUTOFMEMORY : KS265_OK;
+}
+static void close_md5(Enc *e) { free(e->md5_ring); free(e->md5_have); }   /* (what lane_recon_on made goes with the jobs and in lane_close) */
+
+static int open_threads(Enc *e)
+{
     for (int i = 0; i < e->nthreads; ++i) { e->warg[i].e = e; e->warg[i].idx = i; if (pthread_create(&e->th[i], NULL, worker, &e->warg[i])) break; ++e->nth; }
     if (e->nth && !pthread_create(&e->disp, NULL, dispatcher, e)) e->disp_on = 1;
     if (e->disp_on && !pthread_create(&e->sched, NULL, scheduler, e)) e->sched_on = 1;
-    if (!e->nth || !e->disp_on || !e->sched_on) { *err = QY_FAIL; lane_close(e, 0); return NULL; }
+    return !e->nth || !e->disp_on || !e->sched_on ? KS265_FAIL : KS265_OK;
+}
+static void close_threads(Enc *e)
+{
+    if (!e->nth && !e->disp_on && !e->sched_on) return;
+    pthread_mutex_lock(&e->mu); e->quit = 1; pthread_cond_broadcast(&e->cv_work); pthread_cond_broadcast(&e->cv_disp); pthread_cond_broadcast(&e->cv_sched); pthread_cond_broadcast(&e->cv_done); pthread_mutex_unlock(&e->mu);
+    if (e->sched_on) pthread_join(e->sched, NULL);
+    for (int i = 0; i < e->nth; ++i) pthread_join(e->th[i], NULL);
+    if (e->disp_on) pthread_join(e->disp, NULL);
+}
+
+static void lane_close(Enc *e, int report)
+{
+    if (!e) return;
+    close_threads(e);
+    if (main_ctx(e)) {                                                 /* (without it nothing but the two early streams exists) */
+        if (e->ctx_in) ks265_synchronize(e->ctx_in);
+        ks265_synchronize(main_ctx(e));
+        if (e->ctx_out) ks265_synchronize(e->ctx_out);
+        if (report && e->la_on) logf_(1, e->log_level, "ks265enc: lookahead: %ld scene cuts, %ld blocks of 8 pictures coded as 4 + 4\n", e->la_cuts, e->la_mini4);
+        if (report && e->la_on && e->in_disp) logf_(1, e->log_level, "ks265enc: lookahead, caller's ms per picture: launches + queue %.3f, of it waiting for results %.3f (%ld waits); pictures handed on by the scheduler thread: %ld\n",
+                                                    e->la_t_take / e->in_disp, e->la_t_wait / e->in_disp, e->la_n_wait, e->la_n_poll);
+        if (report && e->in_disp) logf_(1, e->log_level, "ks265enc: caller's back-pressure wait %.3f ms per picture\n", e->la_t_bp / e->in_disp);
+        if (report) run_summary(e, e->st.frames, e->st.bytes, e->st.sse, e->q_hi, e->q_lo);
+        close_jobs(e); close_inputs(e); close_dpb(e); close_key_path(e); close_anchor_path(e); close_pipeline(e);
+        for (int i = 0; i < e->ngraph; ++i) ks265_graph_destroy(main_ctx(e), e->graph[i].exec);
+        close_quality(e);
+        ks265_dev_free(main_ctx(e), e->dev_recon);
+        if (e->recon_fd >= 0) close(e->recon_fd);
+        close_qmaps(e);
+    }
+    close_lookahead(e); close_input_streams(e);
+    close_main(e);
+    for (int i = PATH_KEY; i < NPATH; ++i) if (e->path[i].ctx) ks265_destroy(e->path[i].ctx);   /* the contexts: last */
+    if (e->ctx_in) ks265_destroy(e->ctx_in);
+    if (e->ctx_out) ks265_destroy(e->ctx_out);
+    if (main_ctx(e)) ks265_destroy(main_ctx(e));
+    close_output(e); close_md5(e);
+    pthread_mutex_destroy(&e->la_mu);
+    pthread_mutex_destroy(&e->mu); pthread_cond_destroy(&e->cv_work); pthread_cond_destroy(&e->cv_done); pthread_cond_destroy(&e->cv_disp); pthread_cond_destroy(&e->cv_sched); pthread_cond_destroy(&e->cv_sched_done);
+    free(e);
+}
+
+static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
+{
+    int dummy; if (!err) err = &dummy;
+    *err = QY_OK;
+    if (!cfg) { *err = QY_POINTER; return NULL; }
+    if (cfg->picWidth <= 0 || cfg->picHeight <= 0 || (cfg->picWidth & 7) || (cfg->picHeight & 7) || cfg->frameRate <= 0 || cfg->rc < 0 || cfg->rc > 5) { *err = QY_NOTSUPPORTED; return NULL; }
+    Enc *e = (Enc *)calloc(1, sizeof *e);
+    if (e) { e->recon_fd = -1; e->qmap_fd = -1; }
+    if (!e) { *err = QY_OUTOFMEMORY; return NULL; }
+    pthread_mutex_init(&e->la_mu, NULL);
+    pthread_mutex_init(&e->mu, NULL); pthread_cond_init(&e->cv_work, NULL); pthread_cond_init(&e->cv_done, NULL); pthread_cond_init(&e->cv_disp, NULL); pthread_cond_init(&e->cv_sched, NULL); pthread_cond_init(&e->cv_sched_done, NULL);
+    lane_resolve(e, cfg, device, multi);
+    /* The ORDER in which the streams are created matters (round 4, measured at 2160p; DESIGN 6c, tools/hw_queues.hip): a process's normal-priority streams are served by a few
+     * in-order hardware queues (four; three where another runtime user - torch in bench.py - holds one) and share them in pairs that depend on the creation order; a stream that
+     * shares the pixel path's queue runs in turn with it.  With the lookahead there is a fifth stream: created fourth, in front of the key pictures' stream, it cost 25 % (hierarchical
+     * B) / 31 % (IPPP) with not one lookahead kernel launched; created last 8 %; created FIRST nothing measurable - it then pairs with the copy-out stream.  (In the CLI's own
+     * process the four normal streams have a queue each; the key pictures' stream is high-priority and has its own.) */
+    /* the uploads' stream: created first, like the lookahead's.  Its own even beside the lookahead's: the caller waits for the upload, and behind the analysis kernels of the picture
+     * before (measured: 1.17 ms per call instead of the 0.3 ms the DMA takes) it would wait for those too */
+    int r = open_early_streams(e);
+    if (!r) r = open_main(e);                                          /* the main context, its frame object and the records' layout; with it the ring and the input slots' count (lane_rings) */
+    if (!r) r = open_copy_streams(e);
+    if (!r) r = open_pipeline(e);
+    if (!r) r = open_quality(e);
+    if (!r) r = open_qmaps(e);
+    if (!r) r = open_dpb(e);
+    if (!r) r = open_key_path(e);
+    if (!r) r = open_anchor_path(e);
+    if (!r) r = open_lookahead(e);                                     /* (the lookahead's objects; its stream was created first - see above) */
+    if (!r) r = open_jobs(e);
+    if (!r) r = open_inputs(e);
+    if (!r) r = open_output(e);
+    if (!r) r = open_md5(e);
+    if (!r) r = open_threads(e);
+    if (r) { *err = hip_rc(r); lane_close(e, 0); return NULL; }
     logf_(0, e->log_level, "ks265enc: GPU %d: %dx%d %.2f fps, qp %d, -me %d (hex below %d), subme %d, refs %d, %s, sao %d (%s), key period %d, %d slice writer threads, %s\n", device, e->W, e->H,
           cfg->frameRate, e->base_qp, e->me_method, e->hex_thr, e->subme, e->refs, e->hier ? (e->gop_b == 3 ? "hierarchical-B GOP 4" : "hierarchical-B GOP 8") : e->gop_b ? "P + non-reference B" : "IPPP", e->use_sao,
           e->fcfg.sao == 3 ? "the reference's decision with merge candidates" : e->fcfg.sao == 2 ? "the reference's decision" : e->fcfg.sao ? "the build's rule" : "off", e->iper,
@@ -2021,9 +2200,7 @@ static void lane_reconfig(Enc *e, QY265EncConfig *cfg)
     if (!e || !cfg) return;
     pthread_mutex_lock(&e->mu);                                        /* lane_put snapshots base_qp / iper into the input slot under this lock */
     e->cfg.qp = cfg->qp; e->cfg.crf = cfg->crf; e->cfg.bitrateInkbps = cfg->bitrateInkbps; e->cfg.iIntraPeriod = cfg->iIntraPeriod;
-    e->base_qp = e->cfg.rc == 3 ? cfg->crf : cfg->qp; e->iper = cfg->iIntraPeriod;   /* the rate-control mode itself is not reconfigurable: the handle's own rc picks crf / qp */
-    if (e->base_qp < 0) e->base_qp = 0;
-    if (e->base_qp > 51) e->base_qp = 51;
+    e->base_qp = lane_base_qp(cfg, e->cfg.rc); e->iper = cfg->iIntraPeriod;   /* the rate-control mode itself is not reconfigurable: the handle's own rc picks crf / qp */
     pthread_mutex_unlock(&e->mu);
 }
 static int lane_headers(Enc *e, QY265Nal **pNals, int *n)
@@ -2078,7 +2255,7 @@ static void la_publish(Enc *e, Input *slot, int cut, int mini4)
     const int nd = slot->disp;
     pthread_mutex_lock(&e->mu);
     if (!e->la_auto) {                                                 /* (auto: no scene cuts, the key positions are known when the picture is handed in - la_take keeps them) */
-        const int periodic = slot->iper > 0 && e->la_last_key > -1000000 && nd - e->la_last_key >= slot->iper;    /* (the scheduler's own rule: key positions are the same there) */
+        const int periodic = slot->iper > 0 && e->la_last_key > NO_PIC && nd - e->la_last_key >= slot->iper;    /* (the scheduler's own rule: key positions are the same there) */
         if (cut) ++e->la_cuts;
         if (cut || slot->key || nd == 0 || periodic) e->la_last_key = nd;
     }
@@ -2109,7 +2286,7 @@ static void la_decide(Enc *e, const Input *slot, int *cut_out, int *mini4_out)
             }
             if (verdict < 0) {
                 const int keyint = slot->iper > 0 ? (slot->iper < 320 ? slot->iper : 320) : 256;
-                const double bias = (double)(nd - (e->la_last_key > -1000000 ? e->la_last_key : 0)) * ((double)g_cli.scenecut / 100.0) / (double)keyint;
+                const double bias = (double)(nd - (e->la_last_key > NO_PIC ? e->la_last_key : 0)) * ((double)g_cli.scenecut / 100.0) / (double)keyint;
                 verdict = (double)pcost >= (1.0 - bias) * (double)icost;
             }
             cut = verdict;
@@ -2173,7 +2350,7 @@ static int la_take_locked(Enc *e, Input *slot)
     while (e->la_flying >= LA_FLY || e->la_qn >= LA_QMAX - 1) if ((r = la_drain_locked(e, e->la_qn - 1))) return r;
     const int nd = slot->disp, c = nd % LA_RING, w = e->la_w, h = e->la_h;
     const size_t org = (size_t)e->geom_la.pad_y * e->geom_la.stride_y + e->geom_la.pad_y;
-    const int keynow = slot->key || nd == 0 || (slot->iper > 0 && e->la_last_key > -1000000 && nd - e->la_last_key >= slot->iper);   /* (but for a scene cut, not known yet) */
+    const int keynow = slot->key || nd == 0 || (slot->iper > 0 && e->la_last_key > NO_PIC && nd - e->la_last_key >= slot->iper);   /* (but for a scene cut, not known yet) */
     const int p = keynow ? 0 : nd - e->la_last_key;                    /* position inside the GOP */
     if (e->la_auto && keynow) e->la_last_key = nd;
     int what = -1;

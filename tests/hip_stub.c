@@ -8,6 +8,7 @@
 #include "ks265_hip.h"
 #include "../oracle/ks265_pipeline_oracle.h"
 #include <pthread.h>
+#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -54,19 +55,42 @@ static void call_log(const char *name, const ks265_ctx *c, const ks265_frame *f,
 
 const char *ks265_version(void) { return "ks265hip CPU stub (tests only)"; }
 const char *ks265_last_error(ks265_ctx *c) { (void)c; return "stub"; }
-int ks265_create(ks265_ctx **out, int device);
-int ks265_create_prio(ks265_ctx **out, int device, int high_priority) { (void)high_priority; return ks265_create(out, device); }
-int ks265_create(ks265_ctx **out, int device)
+/* ---- what a lane creates (tests/lane_open_main.c): every call that creates a context, a frame object, an event or a block of device / pinned memory, and ks265_memset_async, is a
+ * CREATING CALL.  They are counted across all kinds; while a trace is armed (ks265_stub_open_trace) each writes one line - its kind, the context's creation ordinal, its sizes -
+ * in call order; the k-th one after ks265_stub_fail_at(k) returns KS265_OUTOFMEMORY, once; and the objects alive are counted per kind (ks265_stub_live).  None of it shows in
+ * the call log above */
+enum { LIVE_CTX, LIVE_FRAME, LIVE_EVENT, LIVE_DEV, LIVE_PINNED, LIVE_KINDS };
+static pthread_mutex_t g_ot_mu = PTHREAD_MUTEX_INITIALIZER;
+static FILE *g_ot_fp; static long g_ot_calls, g_ot_fail_at, g_live[LIVE_KINDS];
+void ks265_stub_open_trace(FILE *fp) { pthread_mutex_lock(&g_ot_mu); g_ot_fp = fp; pthread_mutex_unlock(&g_ot_mu); }      /* NULL disarms */
+void ks265_stub_fail_at(long k) { pthread_mutex_lock(&g_ot_mu); g_ot_calls = 0; g_ot_fail_at = k; pthread_mutex_unlock(&g_ot_mu); }   /* counts from here; 0: no failure */
+long ks265_stub_creating_calls(void) { return __atomic_load_n(&g_ot_calls, __ATOMIC_RELAXED); }
+long ks265_stub_live(int kind) { return kind >= 0 && kind < LIVE_KINDS ? __atomic_load_n(&g_live[kind], __ATOMIC_RELAXED) : -1; }
+static void live(int kind, int d) { __atomic_add_fetch(&g_live[kind], d, __ATOMIC_RELAXED); }
+__attribute__((format(printf, 1, 2))) static int creating_fails(const char *fmt, ...)      /* one creating call: counted, traced; nonzero: this is the one that fails */
+{
+    pthread_mutex_lock(&g_ot_mu);
+    const int fail = ++g_ot_calls == g_ot_fail_at;
+    if (g_ot_fp) { va_list ap; va_start(ap, fmt); vfprintf(g_ot_fp, fmt, ap); va_end(ap); fputc('\n', g_ot_fp); }
+    pthread_mutex_unlock(&g_ot_mu);
+    return fail;
+}
+static int ctx_ordinal(const ks265_ctx *c) { return c ? c->id : 0; }
+
+static int stub_create(ks265_ctx **out, int device, const char *entry, int prio)
 {
     const char *nd = getenv("KS265_STUB_DEVICES");                     /* how many GPUs the stand-in "has" (default 8) */
     if (getenv("KS265_STUB_NO_DEVICE") || device < 0 || device >= (nd ? atoi(nd) : 8)) return KS265_NO_DEVICE;
     if (getenv("KS265_STUB_LOG_DEVICES")) fprintf(stderr, "stub: context on device %d\n", device);
+    if (creating_fails("%s dev %d prio %d", entry, device, prio)) { *out = NULL; return KS265_OUTOFMEMORY; }
     static int ids;
     *out = (ks265_ctx *)calloc(1, sizeof **out);
-    if (*out) (*out)->id = __atomic_add_fetch(&ids, 1, __ATOMIC_RELAXED);
+    if (*out) { (*out)->id = __atomic_add_fetch(&ids, 1, __ATOMIC_RELAXED); live(LIVE_CTX, 1); }
     return *out ? KS265_OK : KS265_OUTOFMEMORY;
 }
-void ks265_destroy(ks265_ctx *c) { if (c) { free(c->ops); free(c); } }
+int ks265_create_prio(ks265_ctx **out, int device, int high_priority) { return stub_create(out, device, "create_prio", high_priority); }
+int ks265_create(ks265_ctx **out, int device) { return stub_create(out, device, "create", 0); }
+void ks265_destroy(ks265_ctx *c) { if (c) { live(LIVE_CTX, -1); free(c->ops); free(c); } }
 int ks265_synchronize(ks265_ctx *c) { LOGC(c); return KS265_OK; }
 int ks265_take_device_error(ks265_ctx *c)                              /* KS265_STUB_DEVERR_AT = k: the k-th call finds the device error word set (once), like a wavefront time-out */
 {
@@ -75,24 +99,30 @@ int ks265_take_device_error(ks265_ctx *c)                              /* KS265_
     if (at == -2) { const char *e = getenv("KS265_STUB_DEVERR_AT"); at = e ? atoi(e) : -1; }
     return at >= 0 && __atomic_fetch_add(&n, 1, __ATOMIC_RELAXED) == at ? KS265_FAIL : KS265_OK;
 }
-int ks265_dev_malloc(ks265_ctx *c, void **p, size_t n) { (void)c; *p = calloc(1, n ? n : 1); return *p ? KS265_OK : KS265_OUTOFMEMORY; }
-int ks265_dev_free(ks265_ctx *c, void *p) { (void)c; free(p); return KS265_OK; }
-int ks265_host_malloc(ks265_ctx *c, void **p, size_t n) { return ks265_dev_malloc(c, p, n); }
+static int stub_malloc(ks265_ctx *c, void **p, size_t n, const char *entry, int kind)
+{
+    *p = creating_fails("%s c%d %zu", entry, ctx_ordinal(c), n) ? NULL : calloc(1, n ? n : 1);
+    if (*p) live(kind, 1);
+    return *p ? KS265_OK : KS265_OUTOFMEMORY;
+}
+int ks265_dev_malloc(ks265_ctx *c, void **p, size_t n) { return stub_malloc(c, p, n, "dev_malloc", LIVE_DEV); }
+int ks265_dev_free(ks265_ctx *c, void *p) { (void)c; if (p) live(LIVE_DEV, -1); free(p); return KS265_OK; }
+int ks265_host_malloc(ks265_ctx *c, void **p, size_t n) { return stub_malloc(c, p, n, "host_malloc", LIVE_PINNED); }
 int ks265_host_register(ks265_ctx *c, void *p, size_t n) { (void)c; (void)p; (void)n; return getenv("KS265_STUB_NO_REGISTER") ? KS265_FAIL : KS265_OK; }   /* (every byte of the stand-in's host is "DMA-able") */
 int ks265_host_unregister(ks265_ctx *c, void *p) { (void)c; (void)p; return KS265_OK; }
 int ks265_memcpy_h2d_sync(ks265_ctx *c, void *d, const void *s, size_t n) { LOGC(c); memcpy(d, s, n); return KS265_OK; }
-int ks265_host_free(ks265_ctx *c, void *p) { return ks265_dev_free(c, p); }
+int ks265_host_free(ks265_ctx *c, void *p) { (void)c; if (p) live(LIVE_PINNED, -1); free(p); return KS265_OK; }
 static int stub_fast(void);
 int ks265_memcpy_h2d_async(ks265_ctx *c, void *d, const void *s, size_t n) { LOGC(c); if (n > (1u << 20) && stub_fast()) return KS265_OK;   /* (KS265_STUB_FAST: a picture's upload is the copy engine's time, not the caller's) */
     memcpy(d, s, n); return KS265_OK; }
 int ks265_memcpy_d2d_async(ks265_ctx *c, void *d, const void *s, size_t n) { LOGC(c); memcpy(d, s, n); return KS265_OK; }
 int ks265_memcpy_d2h_async(ks265_ctx *c, void *d, const void *s, size_t n) { LOGC(c); memcpy(d, s, n); return KS265_OK; }
-int ks265_memset_async(ks265_ctx *c, void *d, int v, size_t n) { LOGC(c); memset(d, v, n); return KS265_OK; }
+int ks265_memset_async(ks265_ctx *c, void *d, int v, size_t n) { LOGC(c); if (creating_fails("memset c%d %d %zu", ctx_ordinal(c), v, n)) return KS265_OUTOFMEMORY; memset(d, v, n); return KS265_OK; }
 int ks265_event_create(ks265_ctx *c, void **ev)                        /* an event: the queries since its last record, the ordinal of its creation */
 {
     static int ids;
-    (void)c; *ev = calloc(2, sizeof(int));
-    if (*ev) ((int *)*ev)[1] = __atomic_add_fetch(&ids, 1, __ATOMIC_RELAXED);
+    *ev = creating_fails("event c%d", ctx_ordinal(c)) ? NULL : calloc(2, sizeof(int));
+    if (*ev) { ((int *)*ev)[1] = __atomic_add_fetch(&ids, 1, __ATOMIC_RELAXED); live(LIVE_EVENT, 1); }
     return *ev ? KS265_OK : KS265_OUTOFMEMORY;
 }
 int ks265_event_record(ks265_ctx *c, void *ev) { LOGE(c, ev); *(int *)ev = 0; return KS265_OK; }
@@ -117,7 +147,7 @@ int ks265_event_query(ks265_ctx *c, void *ev, int *done)
     return KS265_OK;
 }
 int ks265_stream_wait_event(ks265_ctx *c, void *ev) { LOGE(c, ev); return KS265_OK; }
-int ks265_event_destroy(ks265_ctx *c, void *ev) { (void)c; free(ev); return KS265_OK; }
+int ks265_event_destroy(ks265_ctx *c, void *ev) { (void)c; if (ev) live(LIVE_EVENT, -1); free(ev); return KS265_OK; }
 
 int ks265_frame_geometry(const ks265_frame_cfg *cfg, ks265_frame_geom *geom)
 {
@@ -132,7 +162,7 @@ int ks265_frame_geometry(const ks265_frame_cfg *cfg, ks265_frame_geom *geom)
 }
 int ks265_frame_create(ks265_ctx *ctx, const ks265_frame_cfg *cfg, ks265_frame **out)
 {
-    ks265_frame *f = (ks265_frame *)calloc(1, sizeof *f);
+    ks265_frame *f = creating_fails("frame c%d %dx%d", ctx_ordinal(ctx), cfg->width, cfg->height) ? NULL : (ks265_frame *)calloc(1, sizeof *f);
     if (!f) return KS265_OUTOFMEMORY;
     static int ids;
     f->ctx = ctx; f->cfg = *cfg; f->id = __atomic_add_fetch(&ids, 1, __ATOMIC_RELAXED);
@@ -141,10 +171,10 @@ int ks265_frame_create(ks265_ctx *ctx, const ks265_frame_cfg *cfg, ks265_frame *
     f->cu8 = (ks265_cu8 *)calloc(1, (size_t)f->g.bytes_cu8); f->sao = (ks265_sao_param *)calloc(1, (size_t)f->g.bytes_sao);
     const size_t npx = (size_t)cfg->width * cfg->height;
     f->lvl[0] = (int16_t *)calloc(npx, 2); f->lvl[1] = (int16_t *)calloc(npx / 4 + 1, 2); f->lvl[2] = (int16_t *)calloc(npx / 4 + 1, 2);
-    *out = f;
+    *out = f; live(LIVE_FRAME, 1);
     return KS265_OK;
 }
-void ks265_frame_destroy(ks265_frame *f) { if (f) { free(f->cu8); free(f->sao); free(f->lvl[0]); free(f->lvl[1]); free(f->lvl[2]); free(f); } }
+void ks265_frame_destroy(ks265_frame *f) { if (f) { live(LIVE_FRAME, -1); free(f->cu8); free(f->sao); free(f->lvl[0]); free(f->lvl[1]); free(f->lvl[2]); free(f); } }
 int ks265_frame_set_qp(ks265_frame *f, int qp, int l) { LOGF(NULL, f, qp); f->cfg.qp = qp; f->cfg.lambda_q4 = l; return KS265_OK; }
 /* tools per picture: the stand-in's pictures do not depend on them; KS265_STUB_TOOLS_LOG = file: one line per inter picture handed in - kind, the three values - so that a
  * host test sees which pictures the host lowered them for */
