@@ -60,7 +60,7 @@ typedef struct QY265EncConfig {
     int bHeaderBeforeKeyframe;                /* VPS / SPS / PPS in front of every key picture */
     int picWidth, picHeight;                  /* multiples of 8 */
     double frameRate;
-    int bframes;                              /* -1: preset / latency default (hierarchical GOP 8 at default latency, else 0); 0: IPPP; 3 / 7: pyramids of 4 / 8 as in the reference; other n: n non-reference B pictures per anchor */
+    int bframes;                              /* -1: preset / latency default (hierarchical GOP 8 at default latency, else 0); 0: IPPP; 3 / 7: pyramids of 4 / 8 as in the reference; other n: n non-reference B pictures per anchor (at most 16: more is QY_NOTSUPPORTED at open) */
     int temporalLayer;
     int vpp_denoise, vpp_edge, vpp_color, vpp_hdr; double vpp_hdr_strength; int vpp_hdr_iter; double vpp_hdr_sigma_s, vpp_hdr_sigma_r, vpp_recur_filter;
     int rc;                                   /* 0 CQP, 1 CBR, 2 ABR, 3 CRF, 4 CVBR, 5 CVQ */

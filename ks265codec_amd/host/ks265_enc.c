@@ -14,6 +14,7 @@
 #define _GNU_SOURCE
 #include "ks265_enc.h"
 #include "ks265_stream.h"
+#include "ks265_gop.h"
 #include <dirent.h>
 #include <fcntl.h>
 #include <math.h>
@@ -333,8 +334,8 @@ typedef struct Enc {
     CopyPool *pool;                                       /* shared by the lanes of one handle (owned by it) */
     int me_method, hex_thr, subme, refs, use_sao, use_df, gop_b, hier;                  /* resolved tools */
     int lean_b;                                                                         /* B pictures nothing predicts from: no intra candidates, no joint refinement, no SAO (KS265_LEAN_B=0: as the others) */
-    int gpb;                                                                            /* `gpb` in force: an anchor that searches two or more past anchors is coded as a B slice (schedule) */
-    int refs0, anc_hist[4], n_anc;                                                      /* -ref0 (qy265enc.h:142, the reference's ActiveRefNumFrm0InGop): how many past anchors an anchor of the pyramid searches; the last anchors' POCs, nearest first */
+    int gpb;                                                                            /* `gpb` in force: an anchor that searches two or more past anchors is coded as a B slice (gop_plan) */
+    int refs0;                                                                          /* -ref0 (qy265enc.h:142, the reference's ActiveRefNumFrm0InGop): how many past anchors an anchor of the pyramid searches */
     int base_qp, iper, nthreads;
     PixPath path[NPATH]; ks265_frame_geom geom; ks265_frame_cfg fcfg; ks265_stream_cfg scfg;
     /* device: three streams - copy-in (ctx_in), the pixel path (path[].ctx), copy-out (ctx_out) - so that the H2D of picture n+1 and the D2H of
@@ -387,7 +388,7 @@ typedef struct Enc {
     int key_overlap, nkeys; void *ev_key, *ev_firstp[2];
     /* scheduling */
     Input in[MAX_INPUT]; int nin, next_disp, in_disp;          /* next_disp: pictures handed to the scheduler; in_disp: pictures taken in (= next_disp + the lookahead's queue la_q) */
-    int gop_start;                                        /* display index of the last key picture */
+    GopRules rules; GopState gs;                          /* ks265_gop.h: what the planner reads of the resolved tools (lane_resolve fills it last), and what it carries from unit to unit */
     int coded_upto;                                       /* display index up to which everything is scheduled */
     int force_key;
     int gop_end, gop_end_seen;                            /* GOP lanes: display index of the last picture of a GOP that ended early (-1: none); what the scheduler has acted on */
@@ -396,7 +397,7 @@ typedef struct Enc {
      * input picture is compared with its predecessor before the scheduler sees it (ks265_lookahead_picture: per 8x8 block of the half-size picture the intra
      * pre-selection cost against the integer-search cost) - where prediction from the previous picture is not clearly cheaper than intra coding a closed GOP starts */
     int la_on, la_have_prev, la_last_key, la_w, la_h; long la_cuts, la_mini4;
-    int mg_adapt, mg4_until;                                          /* slice-type decision (-lookahead N with the hierarchical GOP): a block of 8 pictures is coded as 8 or as 4 + 4; display index up to which 4 is in force */
+    int mg_adapt;                                                     /* slice-type decision (-lookahead N with the hierarchical GOP): a block of 8 pictures is coded as 8 or as 4 + 4 */
     long long la_prev_icost;                                           /* -scenecut N: the previous picture's intra cost (-1: none yet) */
     unsigned long long la_c4_prev;                                     /* inter cost of the previous picture on the GOP's grid of 4 against the picture 4 back */
     int la_auto;                                                       /* no -lookahead given, hierarchical GOP: the slice-type decision alone (pictures on the GOP's grid of 4), no scene cuts - works in GOP lanes */
@@ -805,8 +806,8 @@ static int ct_cost(Enc *e, int b, int p0, int p1)
     if (q.d1 == 0) c->intra_done = 1;                                  /* (the reference marks the intra costs done after a pass without a list-1 picture only, enc@0x4a8be5) */
     return r;
 }
-/* the pictures of (lo, end] in coding order as this scheduler will code them: mini-GOPs (lo, hi], (hi, hi + span], .. - the anchor P picture first, then the B pictures (pyramid:
- * breadth first, references = the interval's ends; else every B picture between the two anchors) */
+/* the pictures of (lo, end] in coding order: mini-GOPs (lo, hi], (hi, hi + span], .. - the anchor P picture first, then its B pictures as the planner's walk gives them
+ * (gop_walk).  The mini-GOPs behind the first are taken to be gop_b + 1 long: with the slice-type decision on as well that is a guess */
 static int ct_structure(const Enc *e, int lo, int hi, int end, CtNode *out, int cap)
 {
     int n = 0;
@@ -814,31 +815,18 @@ static int ct_structure(const Enc *e, int lo, int hi, int end, CtNode *out, int 
     while (lo < end && n < cap) {
         if (hi > end) hi = end;
         out[n++] = (CtNode){hi, lo, -1, 1};
-        if (hi - lo > 1) {
-            if (e->hier && ((hi - lo) & (hi - lo - 1)) == 0) {
-                struct { int lo, hi; } cur[8], nxt[8]; int nc = 1;
-                cur[0].lo = lo; cur[0].hi = hi;
-                while (nc) {
-                    int nn = 0;
-                    for (int i = 0; i < nc; ++i) {
-                        if (cur[i].hi - cur[i].lo < 2) continue;
-                        const int mid = (cur[i].lo + cur[i].hi) / 2;
-                        if (n < cap) out[n++] = (CtNode){mid, cur[i].lo, cur[i].hi, (mid - cur[i].lo >= 2) || (cur[i].hi - mid >= 2)};
-                        nxt[nn].lo = cur[i].lo; nxt[nn++].hi = mid; nxt[nn].lo = mid; nxt[nn++].hi = cur[i].hi;
-                    }
-                    memcpy(cur, nxt, sizeof cur); nc = nn;
-                }
-            } else for (int b = lo + 1; b < hi && n < cap; ++b) out[n++] = (CtNode){b, lo, hi, 0};
-        }
+        GopNode b[GOP_VIEW];
+        const int nb = gop_walk(lo, hi, e->hier, b);
+        for (int i = 0; i < nb && n < cap; ++i) out[n++] = (CtNode){b[i].b, b[i].lo, b[i].hi, b[i].is_ref};
         lo = hi; hi = lo + span;
     }
     return n;
 }
 /* the window's end for a mini-GOP that ends at display index a: ct_depth pictures further, inside this closed GOP, inside what has arrived.  -1: not all of it is there yet */
-static int ct_window_end(Enc *e, int a, int iper, int have, int flush, int gop_end)
+static int ct_window_end(Enc *e, int gop_start, int a, int iper, int have, int flush, int gop_end)
 {
     int end = a + e->ct_depth;
-    if (iper > 0 && end > e->gop_start + iper - 1) end = e->gop_start + iper - 1;
+    if (iper > 0 && end > gop_start + iper - 1) end = gop_start + iper - 1;
     if (gop_end >= a && end > gop_end) end = gop_end;
     for (int k = a + 1; k <= end && k < have; ++k) { const Input *ik = input_at(e, k); if (ik && ik->key) { end = k - 1; break; } }   /* a requested key picture closes the GOP in front of it */
     if (end >= have) { if (!flush) return -1; end = have - 1; }
@@ -889,12 +877,10 @@ static int quality_pass(Enc *e, ks265_ctx *on, ks265_frame *fr, ks265_pic src, k
  *      Sub that submit() owns; nothing of it outlives the call.  Every device-library call of a step is skipped once an earlier one has failed (the lane is lost then: sched_err) */
 typedef struct Sub {
     Job *j; Input *in;
-    int kind, poc, qp, nl0, nl1, is_ref; const int *l0, *l1;
-    int gpb;                                              /* kind 'P' with a list 1: the anchor is coded and signalled as a B picture, everything else treats it as the P picture it is */
-    int keep[32], nk;                                     /* POCs that must stay in the DPB: the caller's keep_after + what this picture uses */
+    const GopPic *pic; int qp;                            /* what the planner decided about the picture (kind, POC, lists, keep set ..), and its QP */
     int k, recycled;                                      /* rotation slot of the input buffer / staging set (seq % NPIPE); it has held a picture before */
     int path; PixPath *p;                                 /* the pixel path that codes the picture (PATH_*) */
-    int split, direct, graphable, lean;
+    int split, direct, graphable;
     const uint8_t *din; ks265_pic srcp; int slot; ks265_pic out;   /* the packed input on the device, the unpacked source picture, the reconstruction's DPB slot */
 } Sub;
 
@@ -916,8 +902,8 @@ static Job *wait_job_slot(Enc *e)
 /* pixel path: the main stream / frame object, the key pictures' own or the anchors' own - the ONE place that decides it - and what follows from the choice */
 static void choose_path(Enc *e, Sub *s)
 {
-    const int on_key = s->kind == 'I' && e->key_overlap && (s->in->iper <= 0 || s->in->iper >= 32);
-    const int on_anc = s->kind == 'P' && !s->gpb && e->anc_on && e->key_overlap && s->nl0 == 1;      /* (key_overlap goes off with the reconstruction dump: everything on the main stream then) */
+    const int on_key = s->pic->kind == 'I' && e->key_overlap && (s->in->iper <= 0 || s->in->iper >= 32);
+    const int on_anc = s->pic->kind == 'P' && !s->pic->gpb && e->anc_on && e->key_overlap && s->pic->nl0 == 1;      /* (key_overlap goes off with the reconstruction dump: everything on the main stream then) */
     s->path = on_key ? PATH_KEY : on_anc ? PATH_ANC : PATH_MAIN;
     s->p = &e->path[s->path];
     s->k = (int)(e->seq % NPIPE);
@@ -929,7 +915,7 @@ static void choose_path(Enc *e, Sub *s)
      * the last B picture of the mini-GOP before it has left the device */
     s->direct = s->path == PATH_ANC && s->in->dev && !e->use_graph;
     /* graph path: a P picture with one reference on the main stream, once the first pictures have made every lazy allocation */
-    s->graphable = e->use_graph && ((s->kind == 'P' && s->nl0 == 1 && !s->gpb) || (s->kind == 'B' && s->nl0 == 1 && s->nl1 == 1)) && s->path == PATH_MAIN && !e->recon_on && e->seq >= 8;
+    s->graphable = e->use_graph && ((s->pic->kind == 'P' && s->pic->nl0 == 1 && !s->pic->gpb) || (s->pic->kind == 'B' && s->pic->nl0 == 1 && s->pic->nl1 == 1)) && s->path == PATH_MAIN && !e->recon_on && e->seq >= 8;
 }
 
 /* the input picture reaches the device and, unpacked and padded, the path's source picture */
@@ -963,16 +949,11 @@ static int stage_input(Enc *e, Sub *s)
 static int set_picture_tools(Enc *e, Sub *s)
 {
     ks265_frame *fr = s->p->frame;
-    int r = ks265_frame_set_qp(fr, s->qp, s->kind == 'I' ? kLambdaQ4[s->qp] : kLambdaInterQ4[s->qp]);
-    /* round 6: a B picture nothing predicts from (half the pictures of a pyramid of 8) runs without intra candidates, without the joint refinement of its bi-predictive CUs and
-     * without SAO - on the CPU mirror and on the MI355X its bytes at equal PSNR-Y stay (the refinement even costs bytes at QP + 4), a quarter of its kernel time goes */
-    /* ... and a B picture others predict from whose own references are at most two pictures away (the second-deepest layer of a pyramid) keeps the refinement but runs without intra
-     * candidates and without SAO: neutral at equal PSNR-Y on the mirror's three clips (profiles/r06_lean_b.txt) */
-    const int near = s->kind == 'B' && s->is_ref && s->nl0 > 0 && s->nl1 > 0 && s->poc - s->l0[0] <= 2 && s->l1[0] - s->poc <= 2;
-    s->lean = !e->lean_b || s->kind != 'B' ? 0 : !s->is_ref ? 2 : near && e->lean_b != 3 ? 1 : 0;          /* (KS265_LEAN_B=3: the non-reference pictures alone) */
-    if (!r) r = s->lean == 2 ? ks265_frame_set_picture_tools(fr, 0, 0, 0, e->lean_b == 2 && e->me_method == 2 ? 1 : -1) : s->lean == 1 ? ks265_frame_set_picture_tools(fr, 0, -1, 0, -1) : ks265_frame_set_picture_tools(fr, -1, -1, -1, -1);
+    int r = ks265_frame_set_qp(fr, s->qp, s->pic->kind == 'I' ? kLambdaQ4[s->qp] : kLambdaInterQ4[s->qp]);
+    /* the B pictures that run without intra candidates and SAO (lean 1), and without the joint refinement as well (lean 2): GopPic::lean */
+    if (!r) r = s->pic->lean == 2 ? ks265_frame_set_picture_tools(fr, 0, 0, 0, e->lean_b == 2 && e->me_method == 2 ? 1 : -1) : s->pic->lean == 1 ? ks265_frame_set_picture_tools(fr, 0, -1, 0, -1) : ks265_frame_set_picture_tools(fr, -1, -1, -1, -1);
     /* `gpb`: the device runs the skip pass on every B slice (skip_rd 1 = B pictures only); an anchor is none to this host - its errors propagate through the pyramid */
-    if (!r && e->gpb && ks265_frame_set_picture_skip) r = ks265_frame_set_picture_skip(fr, s->gpb && e->fcfg.skip_rd < 2 ? 0 : -1);
+    if (!r && e->gpb && ks265_frame_set_picture_skip) r = ks265_frame_set_picture_skip(fr, s->pic->gpb && e->fcfg.skip_rd < 2 ? 0 : -1);
     return r;
 }
 
@@ -980,17 +961,17 @@ static int set_picture_tools(Enc *e, Sub *s)
 static int set_rdoq_tables(Enc *e, Sub *s)
 {
     if (!e->rdoq_on) return 0;
-    if (s->kind == 'I') { e->rq_gop_seq = e->rc_sub; return 0; }
+    if (s->pic->kind == 'I') { e->rq_gop_seq = e->rc_sub; return 0; }
     int32_t *tb = s->j->rq_host;
     pthread_mutex_lock(&e->mu);
     const long s0 = e->rc_sub, need = s0 - RC_LAG;
     for (;;) { rc_account(e); if (e->rc_acc_seq >= need || e->quit) break; pthread_cond_wait(&e->cv_done, &e->mu); }
     int found = 0;
     for (long q = need - 1; q >= 0 && q > e->rq_gop_seq && q >= need - (RQ_HIST - RC_LAG - 8) && !found; --q)
-        if (e->rq_hist_kind[q % RQ_HIST] == (char)s->kind) { memcpy(tb, e->rq_hist + (size_t)(q % RQ_HIST) * 1440, 1440 * sizeof(int32_t)); found = 1; }
+        if (e->rq_hist_kind[q % RQ_HIST] == (char)s->pic->kind) { memcpy(tb, e->rq_hist + (size_t)(q % RQ_HIST) * 1440, 1440 * sizeof(int32_t)); found = 1; }
     pthread_mutex_unlock(&e->mu);
     int r = 0;
-    if (!found) r = ks265_rdoq_tables(&e->scfg, NULL, s->kind == 'P' && !s->gpb ? KS265_SLICE_P : KS265_SLICE_B, s->qp, tb) ? KS265_FAIL : 0;   /* (the slice type the picture goes out with) */
+    if (!found) r = ks265_rdoq_tables(&e->scfg, NULL, s->pic->kind == 'P' && !s->pic->gpb ? KS265_SLICE_P : KS265_SLICE_B, s->qp, tb) ? KS265_FAIL : 0;   /* (the slice type the picture goes out with) */
     memcpy(tb + 1440, e->rq_lam, sizeof e->rq_lam);
     if (!r) r = ks265_frame_set_rdoq(s->p->frame, tb, (const int64_t *)(tb + 1440), (const int64_t *)(tb + 1440) + 52);
     return r;
@@ -1048,7 +1029,7 @@ static int choose_recon_slot(Enc *e, Sub *s)
         if (e->nanch >= 4) r = ks265_stream_wait_event(cx, e->ev_mg[(e->nanch - 3) & 7]);
         break;
     default:
-        s->slot = dpb_free_slot(e, s->keep, s->nk);
+        s->slot = dpb_free_slot(e, s->pic->keep, s->pic->nk);
     }
     if (s->slot < 0) return KS265_FAIL;
     s->out = e->dpb[s->slot];
@@ -1060,11 +1041,11 @@ static int code_picture(Enc *e, const Sub *s)
 {
     ks265_frame *fr = s->p->frame;
     ks265_pic r0[4], r1[4];
-    for (int i = 0; i < s->nl0; ++i) r0[i] = e->dpb[dpb_find(e, s->l0[i])];
-    for (int i = 0; i < s->nl1; ++i) r1[i] = e->dpb[dpb_find(e, s->l1[i])];
-    if (s->kind == 'B' || s->gpb) return s->nl0 > 1 || s->nl1 > 1 ? ks265_encode_picture_b_mref(fr, s->srcp, r0, s->nl0, r1, s->nl1, s->out) : ks265_encode_picture_b(fr, s->srcp, r0[0], r1[0], s->out);
-    if (s->kind == 'P' && s->nl0 > 1) return ks265_encode_picture_mref(fr, s->srcp, r0, s->nl0, s->out);
-    const int key = s->kind == 'I';
+    for (int i = 0; i < s->pic->nl0; ++i) r0[i] = e->dpb[dpb_find(e, s->pic->l0[i])];
+    for (int i = 0; i < s->pic->nl1; ++i) r1[i] = e->dpb[dpb_find(e, s->pic->l1[i])];
+    if (s->pic->kind == 'B' || s->pic->gpb) return s->pic->nl0 > 1 || s->pic->nl1 > 1 ? ks265_encode_picture_b_mref(fr, s->srcp, r0, s->pic->nl0, r1, s->pic->nl1, s->out) : ks265_encode_picture_b(fr, s->srcp, r0[0], r1[0], s->out);
+    if (s->pic->kind == 'P' && s->pic->nl0 > 1) return ks265_encode_picture_mref(fr, s->srcp, r0, s->pic->nl0, s->out);
+    const int key = s->pic->kind == 'I';
     return ks265_encode_picture(fr, s->srcp, key ? s->out : r0[0], key, s->out);
 }
 
@@ -1112,15 +1093,15 @@ static int picture_launches(Enc *e, const Sub *s)
 static int code_picture_graph(Enc *e, Sub *s)
 {
     const int k = s->k; PixPath *p = s->p; ks265_ctx *cx = p->ctx; ks265_frame *fr = p->frame;
-    const ks265_pic refp = e->dpb[dpb_find(e, s->l0[0])], ref1p = s->kind == 'B' ? e->dpb[dpb_find(e, s->l1[0])] : refp;
+    const ks265_pic refp = e->dpb[dpb_find(e, s->pic->l0[0])], ref1p = s->pic->kind == 'B' ? e->dpb[dpb_find(e, s->pic->l1[0])] : refp;
     const uint64_t key[9] = {(uint64_t)(uintptr_t)refp.y, (uint64_t)(uintptr_t)s->out.y, (uint64_t)(uintptr_t)e->dev_in[k], (uint64_t)(uintptr_t)e->stg[k],
-                             (uint64_t)s->qp, (uint64_t)ks265_frame_p_state(fr), (uint64_t)(e->cfg.calcPsnr != 0) | (uint64_t)e->ssim_on << 1 | (uint64_t)(e->hash_on != 0) << 2, (uint64_t)s->kind | ((uint64_t)s->lean << 8), (uint64_t)(uintptr_t)ref1p.y};
+                             (uint64_t)s->qp, (uint64_t)ks265_frame_p_state(fr), (uint64_t)(e->cfg.calcPsnr != 0) | (uint64_t)e->ssim_on << 1 | (uint64_t)(e->hash_on != 0) << 2, (uint64_t)s->pic->kind | ((uint64_t)s->pic->lean << 8), (uint64_t)(uintptr_t)ref1p.y};
     void *exec = NULL;
     for (int i = 0; i < e->ngraph && !exec; ++i) if (!memcmp(e->graph[i].key, key, sizeof key)) exec = e->graph[i].exec;
     int r = s->recycled ? ks265_stream_wait_event(cx, e->ev_drained[k]) : 0;       /* the staging block of this rotation slot has been copied out */
     if (!r && exec) {
         r = ks265_graph_launch(cx, exec);
-        if (!r && s->kind == 'P') r = ks265_frame_p_advance(fr);              /* a B picture leaves the P pictures' predictor chain alone */
+        if (!r && s->pic->kind == 'P') r = ks265_frame_p_advance(fr);              /* a B picture leaves the P pictures' predictor chain alone */
     } else if (!r) {
         int keep_it = e->ngraph < MAX_GRAPHS;
         const int state0 = ks265_frame_p_state(fr);
@@ -1141,7 +1122,7 @@ static int code_picture_graph(Enc *e, Sub *s)
     if (!r && p->dev_hash) r = ks265_memcpy_d2h_async(cx, s->j->hash, p->dev_hash, 24);
     if (!r) r = ks265_event_record(cx, e->ev_loaded[k]);                  /* the input buffer is free again (a little later than on the plain path) */
     if (!r) r = ks265_event_record(cx, e->ev_staged[k]);
-    e->dpb_poc[s->slot] = s->poc;
+    e->dpb_poc[s->slot] = s->pic->poc;
     return r;
 }
 
@@ -1150,8 +1131,8 @@ static int code_picture_plain(Enc *e, Sub *s)
 {
     const int k = s->k; PixPath *p = s->p; ks265_ctx *cx = p->ctx;
     int r = code_picture(e, s);
-    if (!r && s->kind == 'I' && s->path == PATH_MAIN) r = ks265_frame_p_restore(p->frame, 0);   /* (a key picture on the main stream: see mark_streams) */
-    e->dpb_poc[s->slot] = s->poc;
+    if (!r && s->pic->kind == 'I' && s->path == PATH_MAIN) r = ks265_frame_p_restore(p->frame, 0);   /* (a key picture on the main stream: see mark_streams) */
+    e->dpb_poc[s->slot] = s->pic->poc;
     if (!s->split) {
         if (!r) r = drain_picture(e, s, NULL, 0);
         if (!r) r = ks265_event_record(cx, e->ev_staged[k]);
@@ -1182,7 +1163,7 @@ static int mark_streams(Enc *e, Sub *s)
         if (!r && e->anc_on) { r = ks265_stream_wait_event(anc->ctx, e->ev_key); if (!r) r = ks265_frame_p_restore(anc->frame, 0); }   /* the first anchor predicts from it */
         ++e->nkeys;
     }
-    if (s->kind == 'I' && s->path == PATH_MAIN && e->anc_on) {         /* a key picture on the main stream (short intra period): the anchors' stream waits for it there */
+    if (s->pic->kind == 'I' && s->path == PATH_MAIN && e->anc_on) {         /* a key picture on the main stream (short intra period): the anchors' stream waits for it there */
         if (!r) r = ks265_event_record(main_ctx(e), e->ev_key);
         if (!r) r = ks265_stream_wait_event(anc->ctx, e->ev_key);
         if (!r) r = ks265_frame_p_restore(anc->frame, 0);
@@ -1204,35 +1185,35 @@ static int copy_out(Enc *e, const Sub *s)
     /* the records go home: the fixed part + the stored lines only (~2 MB for a P picture at 2160p), by a kernel that reads the size on the device (or, KS265_COPYOUT_MB,
      * a fixed amount by hipMemcpyAsync and the rest by that kernel) */
     if (!r) r = e->copy_mb < 0 ? ks265_copy_out_compact_async(e->ctx_out, main_frame(e), s->j->cmp, e->stg[k])
-                               : ks265_copy_out_compact_dma_async(e->ctx_out, main_frame(e), s->j->cmp, e->stg[k], s->kind == 'I' ? e->cmp_off[7] : (size_t)e->copy_mb << 20);
+                               : ks265_copy_out_compact_dma_async(e->ctx_out, main_frame(e), s->j->cmp, e->stg[k], s->pic->kind == 'I' ? e->cmp_off[7] : (size_t)e->copy_mb << 20);
     if (!r) r = ks265_event_record(e->ctx_out, e->ev_drained[k]);
     if (!r) r = ks265_event_record(e->ctx_out, s->j->ev);
     return r;
 }
 
 /* what the writer needs to know about the picture */
-static void fill_job(Enc *e, const Sub *s, int key_headers)
+static void fill_job(Enc *e, const Sub *s)
 {
     Job *j = s->j; const Input *in = s->in;
-    j->no_sao = s->lean != 0;
-    j->disp = in->disp; j->pts = in->pts; j->poc = s->poc; j->kind = s->kind; j->qp = s->qp; j->is_ref = s->is_ref; j->key_headers = key_headers; j->rc_delta = e->rc_qp_delta;
+    j->no_sao = s->pic->lean != 0;
+    j->disp = in->disp; j->pts = in->pts; j->poc = s->pic->poc; j->kind = s->pic->kind; j->qp = s->qp; j->is_ref = s->pic->is_ref; j->key_headers = s->pic->key_headers; j->rc_delta = e->rc_qp_delta;
     j->rc_budget = (double)in->kbps * 1000.0 / (e->cfg.frameRate > 0 ? e->cfg.frameRate : 25.0);
-    j->nal_type = s->kind == 'I' ? KS265_NAL_IDR_W_RADL : s->is_ref ? KS265_NAL_TRAIL_R : KS265_NAL_TRAIL_N;
-    j->gpb = s->gpb;
-    j->nl0 = s->nl0; j->nl1 = s->nl1;
-    for (int i = 0; i < s->nl0; ++i) j->l0[i] = s->l0[i];
-    for (int i = 0; i < s->nl1; ++i) j->l1[i] = s->l1[i];
-    /* RPS: everything that must stay (keep_after) + what this picture uses */
+    j->nal_type = s->pic->kind == 'I' ? KS265_NAL_IDR_W_RADL : s->pic->is_ref ? KS265_NAL_TRAIL_R : KS265_NAL_TRAIL_N;
+    j->gpb = s->pic->gpb;
+    j->nl0 = s->pic->nl0; j->nl1 = s->pic->nl1;
+    for (int i = 0; i < s->pic->nl0; ++i) j->l0[i] = s->pic->l0[i];
+    for (int i = 0; i < s->pic->nl1; ++i) j->l1[i] = s->pic->l1[i];
+    /* RPS: the picture's keep set - what must stay for later pictures + what this picture uses */
     j->nrps = 0;
-    if (s->kind != 'I')
-        for (int i = 0; i < s->nk; ++i) {
+    if (s->pic->kind != 'I')
+        for (int i = 0; i < s->pic->nk; ++i) {
             int dup = 0;
-            for (int q = 0; q < j->nrps; ++q) if (j->rps_poc[q] == s->keep[i]) dup = 1;
-            if (dup || s->keep[i] == s->poc) continue;
+            for (int q = 0; q < j->nrps; ++q) if (j->rps_poc[q] == s->pic->keep[i]) dup = 1;
+            if (dup || s->pic->keep[i] == s->pic->poc) continue;
             int used = 0;
-            for (int q = 0; q < s->nl0; ++q) if (s->l0[q] == s->keep[i]) used = 1;
-            for (int q = 0; q < s->nl1; ++q) if (s->l1[q] == s->keep[i]) used = 1;
-            j->rps_poc[j->nrps] = s->keep[i]; j->rps_used[j->nrps++] = (unsigned char)used;
+            for (int q = 0; q < s->pic->nl0; ++q) if (s->pic->l0[q] == s->pic->keep[i]) used = 1;
+            for (int q = 0; q < s->pic->nl1; ++q) if (s->pic->l1[q] == s->pic->keep[i]) used = 1;
+            j->rps_poc[j->nrps] = s->pic->keep[i]; j->rps_used[j->nrps++] = (unsigned char)used;
         }
     j->t_submit = now_ms();
 }
@@ -1253,12 +1234,9 @@ static void publish_job(Enc *e, const Sub *s)
 }
 
 /* enqueue one picture: GPU work + copies on the streams, then hand it to the writers */
-static int submit(Enc *e, Input *in, int kind, int poc, int qp, const int *l0, int nl0, const int *l1, int nl1, const int *keep_after, int nkeep, int is_ref, int key_headers)
+static int submit(Enc *e, Input *in, const GopPic *pic, int qp)
 {
-    Sub s = {.in = in, .kind = kind, .poc = poc, .qp = qp, .l0 = l0, .nl0 = nl0, .l1 = l1, .nl1 = nl1, .is_ref = is_ref, .gpb = kind == 'P' && nl1 > 0};
-    for (int i = 0; i < nkeep; ++i) s.keep[s.nk++] = keep_after[i];
-    for (int i = 0; i < nl0; ++i) s.keep[s.nk++] = l0[i];
-    for (int i = 0; i < nl1; ++i) s.keep[s.nk++] = l1[i];
+    Sub s = {.in = in, .pic = pic, .qp = qp};
     if (!(s.j = wait_job_slot(e))) return QY_FAIL;
     choose_path(e, &s);
     int r = stage_input(e, &s);
@@ -1271,7 +1249,7 @@ static int submit(Enc *e, Input *in, int kind, int poc, int qp, const int *l0, i
     if (!r) r = copy_out(e, &s);
     if (r) return hip_rc(r);
     ++e->seq;
-    fill_job(e, &s, key_headers);
+    fill_job(e, &s);
     publish_job(e, &s);
     return QY_OK;
 }
@@ -1287,158 +1265,54 @@ static Input *input_at(Enc *e, int disp)
 }
 static int clampqp(Enc *e, int q) { int lo = e->cfg.rc ? e->cfg.qpmin : 0, hi = e->cfg.rc ? (e->cfg.qpmax ? e->cfg.qpmax : 51) : 51; return q < lo ? lo : q > hi ? hi : q; }
 
-/* hierarchical-B mini-GOP: anchor `a` is coded, now the B pictures of (d, a) breadth first; POCs are relative to the GOP's key picture */
-static int code_hier(Enc *e, int d, int a)
+/* what the planner may ask about the pictures behind display index d, and their slots for the executor: one lock, one pass over the table */
+static void gather_view(Enc *e, int d, int flush, int have, int gop_end, GopView *v, Input *slot[GOP_VIEW])
 {
-    typedef struct { int lo, hi; } Iv;
-    Iv cur[8], nxt[8]; int nc = 1, layer = 1;
-    cur[0].lo = d; cur[0].hi = a;
-    /* every picture of the mini-GOP that is a reference stays until its interval is done; simplest exact rule: keep all already coded
-     * pictures of [d, a] plus d and a themselves (at most 9 with GOP 8) */
-    int coded[16], ncoded = 0;
-    coded[ncoded++] = d - e->gop_start; coded[ncoded++] = a - e->gop_start;
-    while (nc) {
-        int nn = 0;
-        for (int i = 0; i < nc; ++i) {
-            if (cur[i].hi - cur[i].lo < 2) continue;
-            const int mid = (cur[i].lo + cur[i].hi) / 2;
-            Input *in = input_at(e, mid);
-            if (!in) return QY_FAIL;                                   /* (the picture has left the input table: the encoder is being torn down after an error) */
-            const int is_ref = (mid - cur[i].lo >= 2) || (cur[i].hi - mid >= 2);
-            /* list 0: the nearest pictures before `mid` among those this mini-GOP keeps (all its reference pictures coded so far), nearest first; list 1: those after it.  The
-             * interval's ends come first; -ref > 1 adds the next nearest ones */
-            int l0[4], l1[4], nl0 = 0, nl1 = 0;
-            {
-                const int pm = mid - e->gop_start;
-                for (int want = 0; want < e->refs_b; ++want) {
-                    int b0 = -1000000, b1 = 1000000;
-                    for (int q = 0; q < ncoded; ++q) {
-                        if (coded[q] < pm && coded[q] > b0 && (nl0 == 0 || coded[q] < l0[nl0 - 1])) b0 = coded[q];
-                        if (coded[q] > pm && coded[q] < b1 && (nl1 == 0 || coded[q] > l1[nl1 - 1])) b1 = coded[q];
-                    }
-                    if (b0 > -1000000) l0[nl0++] = b0;
-                    if (b1 < 1000000) l1[nl1++] = b1;
-                }
-            }
-            /* B pictures of the pyramid: + 2 / + 4 / + 4 on the key picture's QP by layer - the reference's own ladder (appencoder -qp 27 -psnr 2: anchors 28, B pictures 29 / 31 / 31; ours was
-             * + 2 / + 3 / + 4 until the end of round 3).  Larger offsets keep paying (+ 3 / + 5 / + 6: 1.51 x -> 1.44 x the reference's bitrate at its PSNR-Y on the 1080p clip, every B picture within 0.1 dB
-             * of the anchors - their quality comes from their references), but -qp would no longer mean what it means in the reference */
-            static const int kHierLayerQp[4] = {0, 1, 3, 3}, kPyr4LayerQp[4] = {0, 1, 2, 2};                       /* (-bframes 3: + 2 / + 3) */
-            /* (the adaptive GOP's blocks of 4 keep + 2 / + 4: the reference's + 2 / + 3 there cost 1.3 % more bytes for + 0.004 dB on the 2160p clip, measured on the GPU at the end of round 4) */
-            const int *lq = e->gop_b == 3 ? kPyr4LayerQp : kHierLayerQp;
-            /* -ref0: the anchors the NEXT anchor searches besides d and a stay in this picture's reference picture set (they are in no list of it: the lists above are built
-             * from the mini-GOP's own pictures) */
-            int keepx[24], nkx = 0;
-            for (int q = 0; q < ncoded; ++q) keepx[nkx++] = coded[q];
-            for (int q = 2; q < e->refs0 && q < e->n_anc; ++q) keepx[nkx++] = e->anc_hist[q];
-            int r = submit(e, in, 'B', mid - e->gop_start, clampqp(e, in->base_qp + e->rc_qp_delta + (e->fixqp ? 0 : 1 + lq[layer < 3 ? layer : 3])), l0, nl0, l1, nl1, keepx, nkx, is_ref, 0);
-            if (r) return r;
-            if (is_ref) coded[ncoded++] = mid - e->gop_start;
-            nxt[nn].lo = cur[i].lo; nxt[nn++].hi = mid; nxt[nn].lo = mid; nxt[nn++].hi = cur[i].hi;
-        }
-        memcpy(cur, nxt, sizeof cur); nc = nn; ++layer;
+    memset(v, 0, sizeof *v); memset(slot, 0, GOP_VIEW * sizeof *slot);
+    v->have = have; v->flush = flush; v->gop_end = gop_end;
+    pthread_mutex_lock(&e->mu);
+    for (int i = 0; i < MAX_INPUT; ++i) {
+        Input *in = &e->in[i];
+        const int k = in->disp - (d + 1);
+        if (in->used != 1 || k < 0 || k >= GOP_VIEW || slot[k]) continue;
+        slot[k] = in; v->at[k].present = 1; v->at[k].key = in->key; v->at[k].mini4 = in->mini4; v->at[k].iper = in->iper;
     }
-    return QY_OK;
+    pthread_mutex_unlock(&e->mu);
 }
 
-/* schedule whatever can be coded with the pictures received so far; flush = no more input will come */
+/* schedule whatever can be coded with the pictures received so far; flush = no more input will come.  View -> plan -> execute: every GOP decision is gop_plan's (ks265_gop.h);
+ * this loop waits, asks the rate controller and enqueues.  Nothing of a unit has happened before it is certain to be submitted: the plan is made on a copy of the state */
 static int schedule(Enc *e, int flush, int have /* pictures [0, have) have arrived */, int gop_end /* a GOP ends at this picture whatever follows, or -1 */)
 {
     for (;;) {
         const int d = e->coded_upto;                                   /* last anchor / last coded display index; -1 before the first picture */
-        if (d + 1 >= have) return QY_OK;
-        const int nxt = d + 1;
-        Input *in = input_at(e, nxt);
-        const int iper = in ? in->iper : 0;                            /* the period in force when this picture was handed in (QY265EncoderReconfig) */
-        const int key = d < 0 || (iper > 0 && nxt - e->gop_start >= iper) || (in && in->key);
-        if (key && e->ct_on) {                                         /* cuTree: the key picture's offsets need the window behind it */
-            const int gs = e->gop_start; e->gop_start = nxt;
-            const int end = ct_window_end(e, nxt, iper, have, flush, gop_end);
-            e->gop_start = gs;
+        GopView v; Input *slot[GOP_VIEW]; GopUnit u;
+        GopState st = e->gs;
+        gather_view(e, d, flush, have, gop_end, &v, slot);
+        const int what = gop_plan(&e->rules, &st, &v, d, &u);
+        if (what != GOP_UNIT) return what == GOP_WAIT ? QY_OK : QY_FAIL;   /* (gone: an error elsewhere emptied the input table under the scheduler) */
+        if (e->ct_on) {                                                /* cuTree: costs and propagation over the window behind this key picture / mini-GOP, offsets for its pictures */
+            const int end = ct_window_end(e, st.gop_start, u.a, u.iper, have, flush, gop_end);
             if (end < 0) return QY_OK;
-            e->gop_start = nxt;
-            const int rr = ct_run(e, nxt, nxt, nxt, end);
-            e->gop_start = gs;
+            const int rr = u.key ? ct_run(e, u.a, u.a, u.a, end) : ct_run(e, -1, d, u.a, end);
             if (rr) return hip_rc(rr);
         }
-        if (key) {
-            if (!in) return QY_FAIL;
-            e->gop_start = nxt; e->mg4_until = -1;
-            e->anc_hist[0] = 0; e->n_anc = 1;                           /* the key picture is the GOP's first anchor (POC 0) */
-            e->rc_qp_delta = rc_decide(e);                             /* rate control: one offset per key picture / mini-GOP, decided when it is certain to be submitted */
-            for (int i = 0; i < e->ndpb + 2 + 4; ++i) e->dpb_poc[i] = NO_PIC;
-            int r = submit(e, in, 'I', 0, clampqp(e, in->base_qp + e->rc_qp_delta), NULL, 0, NULL, 0, NULL, 0, 1, 1);
+        e->gs = st;
+        e->rc_qp_delta = rc_decide(e);                                 /* rate control: one offset per key picture / mini-GOP, decided when it is certain to be submitted */
+        if (u.key) for (int i = 0; i < e->ndpb + 2 + 4; ++i) e->dpb_poc[i] = NO_PIC;
+        int anchor_on_lane = 0;
+        for (int i = 0; i < u.n; ++i) {
+            const GopPic *p = &u.pic[i];
+            Input *in = slot[p->disp - (d + 1)];                       /* (looked up once per unit: a tear-down that empties the table while the unit is submitted is noticed at the next unit, or by submit itself - wait_job_slot) */
+            const int r = submit(e, in, p, clampqp(e, in->base_qp + e->rc_qp_delta + p->qp_off));
             if (r) return r;
-            pthread_mutex_lock(&e->mu); e->coded_upto = nxt; pthread_mutex_unlock(&e->mu);
-            continue;
+            if (i == 0) anchor_on_lane = e->last_on_anc;
         }
-        int span = e->gop_b + 1;                                       /* anchor distance */
-        if (e->mg_adapt && span == 8) {                                /* slice-type decision (lane_put): this block of 8 as two mini-GOPs of 4 */
-            if (d < e->mg4_until) span = 4;                            /* its second half */
-            else {
-                const Input *i8 = d + 8 < have ? input_at(e, d + 8) : NULL;   /* the decision travels with the block's last picture; not there yet: nothing is coded before it arrives (or a key picture / the flush cuts the block short) */
-                if (i8 && i8->mini4 && !i8->key) { span = 4; e->mg4_until = d + 8; }
-            }
-        }
-        int a = d + span;
-        if (iper > 0 && a - e->gop_start >= iper) a = e->gop_start + iper - 1;   /* the mini-GOP in front of a key picture is shortened */
-        for (int k = nxt + 1; k <= a && k < have; ++k) {                 /* a picture asked to be a key picture: the mini-GOP in front of it is shortened as well */
-            const Input *ik = input_at(e, k);
-            if (ik && ik->key) { a = k - 1; break; }
-        }
-        if (gop_end >= nxt && a > gop_end) a = gop_end;                 /* the GOP was closed behind this picture (its successor goes to another lane) */
-        if (a >= have) { if (!flush) return QY_OK; a = have - 1; }
-        if (e->ct_on) {                                                /* cuTree: costs and propagation over the window behind this mini-GOP, offsets for its pictures */
-            const int end = ct_window_end(e, a, iper, have, flush, gop_end);
-            if (end < 0) return QY_OK;
-            const int rr = ct_run(e, -1, d, a, end);
-            if (rr) return hip_rc(rr);
-        }
-        const int pd = d - e->gop_start, pa = a - e->gop_start;
-        int l0[4], nl0 = 0, l1[1], nl1 = 0, keep[8], nkeep = 0;
-        if (span == 1) {                                               /* IPPP: the most recent pictures, nearest first */
-            for (int i = 0; i < e->refs && pa - 1 - i >= 0; ++i) l0[nl0++] = pa - 1 - i;
-            for (int i = 0; i < e->refs - 1 && pa - 1 - i >= 0; ++i) keep[nkeep++] = pa - 1 - i;   /* still needed by the next picture */
-        } else if (e->refs0 > 1 && e->n_anc > 0 && e->anc_hist[0] == pd) {
-            /* -ref0: the last anchors of this GOP, nearest first (the first one is the previous anchor); all of them but the oldest are the next anchor's too */
-            /* `gpb`: with two or more of them the anchor goes out as a B slice - the second nearest alone in list 1, the others in list 0: no picture in both lists (the boundary
-             * strength compares list indices), bi-prediction pairs the two nearest anchors, every picture is searched once.  The pictures, and with them the reference picture
-             * sets, are the P anchor's; the order is not the default construction's (8.3.4 gives both lists of past pictures the same order): list_mod */
-            for (int i = 0; i < e->refs0 && i < e->n_anc; ++i) { if (e->gpb && i == 1) l1[nl1++] = e->anc_hist[i]; else l0[nl0++] = e->anc_hist[i]; }
-            for (int i = 0; i < e->refs0 - 1 && i < e->n_anc; ++i) keep[nkeep++] = e->anc_hist[i];
-        } else { l0[nl0++] = pd; keep[nkeep++] = pd; }
-        Input *ina = input_at(e, a);
-        if (!ina) return QY_FAIL;                                      /* (as above: an error elsewhere emptied the input table under the scheduler) */
-        e->rc_qp_delta = rc_decide(e);
-        /* the QP ladder of P pictures: + 1 on the key picture's; IPPP: the reference's own cascade over four pictures (appencoder -bframes 0 -qp 27 -psnr 2: 30 / 29 / 30 / 28 / 30 ..),
-         * measured with the CPU mirror of this host: - 12 % bytes of the P pictures for - 0.09 dB */
-        static const int kIpppCascade[4] = {0, 2, 1, 2};
-        const int casc = e->gop_b == 0 ? kIpppCascade[pa & 3] : 0;
-        int r = submit(e, ina, 'P', pa, clampqp(e, ina->base_qp + e->rc_qp_delta + (e->fixqp ? 0 : 1 + casc)), l0, nl0, l1, nl1, keep, nkeep, 1, 0);
-        if (r) return r;
-        if (span > 1) {                                                /* the anchors' history: this one in front */
-            for (int i = 3; i > 0; --i) e->anc_hist[i] = e->anc_hist[i - 1];
-            e->anc_hist[0] = pa; if (e->n_anc < 4) ++e->n_anc;
-        }
-        const int anchor_on_lane = e->last_on_anc;
-        if (a - d > 1) {
-            if (e->hier && ((a - d) & (a - d - 1)) == 0) { r = code_hier(e, d, a); if (r) return r; }
-            else {
-                int kp[6] = {pd, pa}, nkp = 2;
-                for (int i = 2; i < e->refs0 && i < e->n_anc; ++i) kp[nkp++] = e->anc_hist[i];      /* (-ref0: what the next anchor still searches) */
-                for (int b = d + 1; b < a; ++b) {
-                    Input *inb = input_at(e, b);
-                    if (!inb) return QY_FAIL;
-                    r = submit(e, inb, 'B', b - e->gop_start, clampqp(e, inb->base_qp + e->rc_qp_delta + (e->fixqp ? 0 : 2)), &pd, 1, &pa, 1, kp, nkp, 0, 0);
-                    if (r) return r;
-                }
-            }
-        }
-        if (e->anc_on && anchor_on_lane) {   /* every B picture that reads the anchors of this mini-GOP is on the main stream now */
-            r = hip_rc(ks265_event_record(main_ctx(e), e->ev_mg[(e->nanch - 1) & 7]));
+        if (!u.key && e->anc_on && anchor_on_lane) {   /* every B picture that reads the anchors of this mini-GOP is on the main stream now */
+            const int r = hip_rc(ks265_event_record(main_ctx(e), e->ev_mg[(e->nanch - 1) & 7]));
             if (r) return r;
         }
-        pthread_mutex_lock(&e->mu); e->coded_upto = a; pthread_mutex_unlock(&e->mu);
+        pthread_mutex_lock(&e->mu); e->coded_upto = u.a; pthread_mutex_unlock(&e->mu);
     }
 }
 
@@ -1613,7 +1487,7 @@ static void lane_resolve(Enc *e, const QY265EncConfig *cfg, int device, int mult
      * -bframes 1 / 2: the reference codes both as anchors 2 apart with one B picture at Q + 2; ours: P + n plain B at Q + 2 */
     e->hier = e->gop_b == 7 || cfg->bframes == 3;
     /* with B pictures the anchors keep one reference; round 5: the B pictures of the pyramid search up to -ref pictures per list (ks265_encode_picture_b_mref: config 5 = -preset
-     * veryslow resolves to 4 / 4) - of the pictures the mini-GOP keeps anyway (code_hier), so the reference picture sets do not change */
+     * veryslow resolves to 4 / 4) - of the pictures the mini-GOP keeps anyway (gop_plan), so the reference picture sets do not change */
     e->refs_b = e->hier ? e->refs : 1;
     if (e->gop_b > 0) e->refs = 1;
     /* round 6: -ref0 (-preset slow resolves to ref 1 / ref0 3): the anchors of a pyramid search the last ref0 anchors of their GOP (ks265_encode_picture_mref, list 0
@@ -1668,7 +1542,7 @@ static void lane_resolve(Enc *e, const QY265EncConfig *cfg, int device, int mult
                                                                          * integer search (measured with one round: - 21 .. - 23 % bytes of the P / B pictures; the variable is a measuring aid) */
     e->fcfg.intra_inter = 1;                                            /* P / B pictures may hold intra CUs (uncovered regions, occlusions); 2 = none of 8x8: measured + 1.6 % bits, no faster */
     e->fcfg.rdo = 4;                                                    /* coefficient-group pruning at lambda x 1 (ks265_frame_cfg.rdo): supersedes the coefficient decimation of round 2 */
-    e->lean_b = env_int("KS265_LEAN_B", 1);                             /* non-reference B pictures without intra candidates / joint refinement / SAO (submit) */
+    e->lean_b = env_int("KS265_LEAN_B", 1);                             /* non-reference B pictures without intra candidates / joint refinement / SAO (GopPic::lean) */
     e->fcfg.skip_rd = env_int("KS265_SKIP_RD", 1) & 3;                  /* stage D2 (round 6): after the reconstruction of a B picture, nodes whose merge candidate without
                                                                          * residual is the cheaper coding - on the coded distortion - become one CU (ks265_frame_cfg.skip_rd; 2 = P pictures
                                                                          * too, where it gains nothing measurable; the variable is a measuring aid) */
@@ -1744,7 +1618,7 @@ static void lane_resolve(Enc *e, const QY265EncConfig *cfg, int device, int mult
          * takes a whole GOP in ahead of its pixel path - its analyses queue up behind two lanes' kernels, and a caller that waited for them fed 770 pictures/s (round 5) */
         const int keep = env_int("KS265_LA_KEEP", 0);
         e->la_keep = keep > 0 && keep < LA_QMAX - 8 ? keep : multi ? 48 : 5;
-        e->la_on = 1; e->la_last_key = NO_PIC; e->la_prev_icost = -1; e->mg_adapt = e->hier; e->mg4_until = -1;
+        e->la_on = 1; e->la_last_key = NO_PIC; e->la_prev_icost = -1; e->mg_adapt = e->hier;
     }
     if (!e->la_on) e->la_auto = 0;
     const int big = (size_t)e->W * e->H * 3 / 2 >= ((size_t)1 << 20), in_copy = env_set("KS265_INPUT_COPY");
@@ -1769,13 +1643,16 @@ static void lane_resolve(Enc *e, const QY265EncConfig *cfg, int device, int mult
     e->scfg.sdh = e->fcfg.sdh;
     e->zero_latency = cfg->latency == QY265LATENCY_ZERO && e->gop_b == 0 && !e->la_on && !multi;
     e->scfg.cu_qp_delta = e->qmap_on;
-    e->scfg.list_mod = e->gpb;                                          /* the anchors' two lists of past pictures are not the default construction (schedule) */
+    e->scfg.list_mod = e->gpb;                                          /* the anchors' two lists of past pictures are not the default construction (gop_plan) */
     e->scfg.tu_inter = e->fcfg.tu_inter;
     e->scfg.wpp = 1;                                                    /* CTU rows as substreams: what lets several writer threads share one picture */
     e->scfg.max_dec_pic_buffering = e->hier ? 10 : e->gop_b ? 4 : e->refs + 1; e->scfg.log2_max_poc_lsb = 16;
     /* pictures that precede a picture in decoding order and follow it in output order: the whole GOP for the hierarchy (7, as before), ONE (the anchor) for
      * P + n non-reference B whatever n is (-bframes 1..15) */
     e->scfg.max_num_reorder = e->hier ? e->gop_b : e->gop_b ? 1 : 0;
+    /* what the GOP planner reads of all this (nothing above changes after this point) */
+    e->rules = (GopRules){.gop_b = e->gop_b, .hier = e->hier, .refs = e->refs, .refs_b = e->refs_b, .refs0 = e->refs0, .gpb = e->gpb, .fixqp = e->fixqp, .lean_b = e->lean_b, .mg_adapt = e->mg_adapt};
+    e->gs.mg4_until = -1;
 }
 
 /* the sizes that need the frame object's compact layout (cmp_off[7]): the ring of pictures in flight, the writer threads it can feed, the input slots */
@@ -2158,7 +2035,7 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
     int dummy; if (!err) err = &dummy;
     *err = QY_OK;
     if (!cfg) { *err = QY_POINTER; return NULL; }
-    if (cfg->picWidth <= 0 || cfg->picHeight <= 0 || (cfg->picWidth & 7) || (cfg->picHeight & 7) || cfg->frameRate <= 0 || cfg->rc < 0 || cfg->rc > 5) { *err = QY_NOTSUPPORTED; return NULL; }
+    if (cfg->picWidth <= 0 || cfg->picHeight <= 0 || (cfg->picWidth & 7) || (cfg->picHeight & 7) || cfg->frameRate <= 0 || cfg->rc < 0 || cfg->rc > 5 || cfg->bframes > GOP_MAX_B) { *err = QY_NOTSUPPORTED; return NULL; }
     Enc *e = (Enc *)calloc(1, sizeof *e);
     if (e) { e->recon_fd = -1; e->qmap_fd = -1; }
     if (!e) { *err = QY_OUTOFMEMORY; return NULL; }

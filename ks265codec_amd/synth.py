@@ -72,7 +72,7 @@ def subme_knobs(preset: str) -> dict:
 ENCODER_TOOLS = dict(me_method=2, me_hex_thr=16, sdh=1, pre_search=1, merge=1, bi_refine=0, rdo=4, intra_inter=1, propagate=1, skip_rd=1, **subme_knobs("slow"))     # (bi_refine: 2 from -preset slower on)
 
 
-# the encoder host's QP ladders at -rc 0 (host/ks265_enc.c kIpppCascade / kHierLayerQp = the reference's own, read from its -psnr 2 lines): the QP of a picture is the
+# the encoder host's QP ladders at -rc 0 (host/ks265_gop.h kIpppCascade / kHierLayerQp = the reference's own, read from its -psnr 2 lines): the QP of a picture is the
 # key picture's + host_qp_offset(...).  bench.py's hot-path leg, tests/stream_cases.py and tools/rd_eval.py --host use these.
 HOST_IPPP_CASCADE = (0, 2, 1, 2)
 HOST_HIER_LAYER_QP = (0, 1, 3, 3)

@@ -71,7 +71,7 @@ def _mirror(clip, W, H, per, refs_of, rec, tools, upto, aq=0.0, maps=None, ref0=
     o = OraclePipeline(W, H, 27, lambda_q4(27), **tools)
     dpb = {}
     spread = set()
-    # the references of every picture first: a B picture nothing predicts from is coded without intra candidates, joint refinement and SAO (the host's lean B pictures, ks265_enc.c submit)
+    # the references of every picture first: a B picture nothing predicts from is coded without intra candidates, joint refinement and SAO (the host's lean B pictures, ks265_gop.h GopPic::lean)
     all_refs = [refs_of(i, poc, kind) for i, (poc, kind, _, _) in enumerate(per)]
     used = set()
     for a, b in all_refs:
@@ -90,7 +90,7 @@ def _mirror(clip, W, H, per, refs_of, rec, tools, upto, aq=0.0, maps=None, ref0=
             o.set_qp_map(qmap)
             spread |= set(qmap.tolist())
         r0, r1 = all_refs[i]
-        if kind == "P" and r0 is not None and not isinstance(r0, list):    # round 6: an anchor of a pyramid searches the last ref0 anchors of its GOP, nearest first (-ref0; ks265_enc.c)
+        if kind == "P" and r0 is not None and not isinstance(r0, list):    # round 6: an anchor of a pyramid searches the last ref0 anchors of its GOP, nearest first (-ref0; ks265_gop.h gop_plan)
             last_key = max(j for j, (_, k, _, _) in enumerate(per[:i]) if k == "I")
             hist = [p for p, k, _, _ in per[last_key:i] if k != "B"][::-1]
             if ref0 > 1 and hist and hist[0] == r0:
@@ -191,7 +191,7 @@ def test_config5_command_line(tmp_path):
     _decoder_check(tmp_path, out, rec, n, W * H * 3 // 2)
     tools = dict(ENCODER_TOOLS, me_hex_thr=0, part=1, tu_inter=1, bi_refine=2, **subme_knobs("veryslow"))    # veryslow: always UMH, -subme 2 judged by Hadamard, -part 1 (P and B pictures)
     assert "up to 4 pictures per list" in log, log[:1200]
-    st = {"keep": [], "anchor": None}                                          # the host's code_hier: the reference pictures of the mini-GOP coded so far (its two ends first)
+    st = {"keep": [], "anchor": None}                                          # the host's planner (ks265_gop.h gop_plan): the reference pictures of the mini-GOP coded so far (its two ends first)
 
     def refs(i, poc, kind):
         if kind == "I":

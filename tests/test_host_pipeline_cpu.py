@@ -516,7 +516,7 @@ def test_scene_cuts_with_gop_lanes(stub_lib):
 
 
 def _hier_order(d, a):
-    """coding order of the mini-GOP (d, a]: the anchor, then the B pictures breadth first (code_hier)"""
+    """coding order of the mini-GOP (d, a]: the anchor, then the B pictures breadth first (ks265_gop.h gop_walk)"""
     out, cur = [a], [(d, a)]
     while cur:
         nxt = []

@@ -74,7 +74,7 @@ def encode_ours(clip, W, H, qp, gop, tools, verbose=False, stats=None, pdelta=1,
     encode_ours._cfg0 = {nm: getattr(o.cfg, nm) for nm in ('sao', 'bi_refine', 'propagate', 'intra_inter', 'merge', 'rdo')}
     dpb = {}
     # -ref0 (round 6; the host's default under --host: 3 = what -preset slow resolves to): the anchors of the hierarchy search the last RD_MREF anchors of their GOP, nearest first
-    # keeps: --host with the pyramid GOPs - the pictures the host keeps in every reference picture set (ks265_enc.c schedule / code_hier: the anchors the next anchor searches, the
+    # keeps: --host with the pyramid GOPs - the pictures the host keeps in every reference picture set (ks265_gop.h gop_plan: the anchors the next anchor searches, the
     # mini-GOP's reference pictures coded so far), so that the slice headers are the host's to the bit
     mrs, hist, keeps, mg = [], [], [], []
     for (d, kind, r0, r1, layer) in seq:
@@ -106,7 +106,7 @@ def encode_ours(clip, W, H, qp, gop, tools, verbose=False, stats=None, pdelta=1,
             o.cfg.intra_inter = iil[min(len(iil) - 1, max(layer, 1) - 1)]
         elif os.environ.get('RD_II_LAYERS'):
             o.cfg.intra_inter = tools.get('intra_inter', 0)
-        if lam_scale == -1 and not os.environ.get('RD_NO_LEAN_B'):     # --host: the host's lean B pictures (ks265_enc.c submit) - a B picture nothing predicts from runs without intra candidates, joint refinement, SAO
+        if lam_scale == -1 and not os.environ.get('RD_NO_LEAN_B'):     # --host: the host's lean B pictures (ks265_gop.h GopPic::lean) - a B picture nothing predicts from runs without intra candidates, joint refinement, SAO
             lean = kind == 'B' and not any(d in (a, b) for (_, _, a, b, _) in seq[i + 1:])
             near = kind == 'B' and not lean and d - r0 <= 2 and r1 - d <= 2 and not os.environ.get('RD_LEAN_NONREF_ONLY')      # a reference B picture with both references at most two pictures away: no intra candidates, no SAO
             o.set_picture_tools(*((0, 0, 0) if lean else (0, -1, 0) if near else (-1, -1, -1)))
@@ -177,7 +177,7 @@ def encode_ours(clip, W, H, qp, gop, tools, verbose=False, stats=None, pdelta=1,
 
 
 def mini_gop(lo, hi):
-    """coding order of the mini-GOP (lo, hi] as the host codes it: the anchor, then - a power of two apart - the B pictures breadth first (code_hier), else plain
+    """coding order of the mini-GOP (lo, hi] as the host codes it: the anchor, then - a power of two apart - the B pictures breadth first (ks265_gop.h gop_walk), else plain
     non-reference B pictures between the two anchors at QP + 2 (the flush of a clip that does not end on the grid); entries of encode_ours' seq"""
     if (hi - lo) & (hi - lo - 1):
         return [(hi, "P", lo, None, 0)] + [(b, "B", lo, hi, -1) for b in range(lo + 1, hi)]
@@ -312,9 +312,9 @@ def main():
     if a.host:
         tools = dict(HOST_TOOLS); a.lam_scale = -1.0
         if a.gop == "ippp" and not a.cascade:
-            a.cascade = "0,2,1,2"                                   # ks265_enc.c kIpppCascade
+            a.cascade = "0,2,1,2"                                   # ks265_gop.h kIpppCascade
         if a.gop == "hier" and not a.layer_qp:
-            a.layer_qp = "0,1,3,3"                                  # ks265_enc.c kHierLayerQp
+            a.layer_qp = "0,1,3,3"                                  # ks265_gop.h kHierLayerQp
     for kv in filter(None, a.tools.split(",")):
         k, v = kv.split("=")
         tools[k] = int(v)
