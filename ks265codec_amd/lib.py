@@ -91,9 +91,10 @@ def _p(t) -> C.c_void_p:
 
 
 class KsContext:
-    """Owns a ks265_ctx bound to torch's current HIP stream on `device`."""
+    """Owns a ks265_ctx bound to torch's current HIP stream on `device` (own_stream: the non-blocking stream ks265_create made stays - a second stream beside torch's,
+    ordered against it with events as the encoder host orders its streams)."""
 
-    def __init__(self, device: int = 0):
+    def __init__(self, device: int = 0, own_stream: bool = False):
         import torch
 
         self.lib = load_library()
@@ -105,7 +106,8 @@ class KsContext:
         self._chk(self.lib.ks265_create(C.byref(h), C.c_int(device)), None)
         self.h = h
         torch.cuda.set_device(device)
-        self._chk(self.lib.ks265_set_stream(self.h, C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+        if not own_stream:
+            self._chk(self.lib.ks265_set_stream(self.h, C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
 
     def _chk(self, rc: int, h="self"):
         if rc != 0:
@@ -146,6 +148,31 @@ class KsContext:
 
     def marker(self, ident: int = 0):
         self._chk(self.lib.ks265_marker(self.h, C.c_int(ident)))
+
+    # ---- events and pinned memory (hosts that order several contexts' streams)
+    def event_create(self) -> C.c_void_p:
+        ev = C.c_void_p()
+        self._chk(self.lib.ks265_event_create(self.h, C.byref(ev)))
+        return ev
+
+    def event_record(self, ev):
+        self._chk(self.lib.ks265_event_record(self.h, ev))
+
+    def stream_wait_event(self, ev):
+        """everything enqueued on this context's stream from here on waits for `ev` (recorded on another context's stream)"""
+        self._chk(self.lib.ks265_stream_wait_event(self.h, ev))
+
+    def event_destroy(self, ev):
+        self._chk(self.lib.ks265_event_destroy(self.h, ev))
+
+    def host_malloc(self, nbytes: int) -> "tuple[C.c_void_p, np.ndarray]":
+        """pinned, device-mapped host memory of the library: (pointer for ks265_host_free / the copy-outs, uint8 view of it)"""
+        hp = C.c_void_p()
+        self._chk(self.lib.ks265_host_malloc(self.h, C.byref(hp), C.c_size_t(nbytes)))
+        return hp, np.ctypeslib.as_array((C.c_uint8 * int(nbytes)).from_address(hp.value))
+
+    def host_free(self, hp):
+        self._chk(self.lib.ks265_host_free(self.h, hp))
 
     # ---- section 2: batched operator tables (names follow the reference tables, SURVEY.md §2.3)
     def _dist(self, fn, a, sa, b, sb, blks: np.ndarray, k: int) -> np.ndarray:
@@ -533,6 +560,43 @@ class KsFrame:
     def ws_ptr(self, name: str, comp: int = 0) -> int:
         fn = getattr(self.lib, "ks265_frame_" + name)
         return fn(self.h, C.c_int(comp)) if name == "levels" else fn(self.h)
+
+    def ws_write(self, name: str, data: np.ndarray, comp: int = 0, offset: int = 0):
+        """put the bytes of `data` into an internal workspace buffer, `offset` bytes from its start (ks265_memcpy_h2d_sync: on the device when the call returns)"""
+        a = np.ascontiguousarray(data).reshape(-1).view(np.uint8)
+        self.ks.sync()
+        self.ks._chk(self.lib.ks265_memcpy_h2d_sync(self.ks.h, C.c_void_p(self.ws_ptr(name, comp) + int(offset)), C.c_void_p(a.ctypes.data), C.c_size_t(a.size)))
+
+    # ---- the picture's records as one block (include/ks265_hip.h: ks265_frame_records_layout, ks265_frame_compact_layout)
+    def records_layout(self) -> list:
+        off = (C.c_size_t * 7)()
+        self.ks._chk(self.lib.ks265_frame_records_layout(self.h, off))
+        return [int(x) for x in off]
+
+    def compact_layout(self) -> list:
+        off = (C.c_size_t * 8)()
+        self.ks._chk(self.lib.ks265_frame_compact_layout(self.h, off))
+        return [int(x) for x in off]
+
+    def pack_records(self, dst, extra64=None):
+        """dst: device byte tensor of records_layout()[6] bytes; extra64: device tensor of 64 bytes or None"""
+        self.ks._chk(self.lib.ks265_frame_pack_records(self.h, _p(dst), _p(extra64) if extra64 is not None else None))
+
+    def pack_compact(self, dst, extra64=None, on: "KsContext | None" = None):
+        """dst: device byte tensor of compact_layout()[7] bytes whose header was zero when it was allocated; on: another context's stream (the caller orders it)"""
+        ex = _p(extra64) if extra64 is not None else None
+        if on is None:
+            self.ks._chk(self.lib.ks265_frame_pack_compact(self.h, _p(dst), ex))
+        else:
+            on._chk(self.lib.ks265_frame_pack_compact_on(on.h, self.h, _p(dst), ex))
+
+    def copy_out_compact(self, ctx: KsContext, pinned, block, data_bytes: "int | None" = None):
+        """a compact block to pinned memory (KsContext.host_malloc) on ctx's stream: by the copy kernel alone, or (data_bytes given) the copy engine for the fixed part and
+        the first data_bytes of the data area + the kernel for what lies beyond"""
+        if data_bytes is None:
+            ctx._chk(self.lib.ks265_copy_out_compact_async(ctx.h, self.h, pinned, _p(block)))
+        else:
+            ctx._chk(self.lib.ks265_copy_out_compact_dma_async(ctx.h, self.h, pinned, _p(block), C.c_size_t(int(data_bytes))))
 
     def ws_read(self, name: str, nbytes: int, comp: int = 0) -> np.ndarray:
         """copy `nbytes` of an internal workspace buffer to the host"""

@@ -204,6 +204,7 @@ int ks265_frame_p_state(ks265_frame *f) { return (f->cur_pu & 1) | (f->have_prev
 int ks265_frame_p_advance(ks265_frame *f) { LOGF(NULL, f, 0); f->cur_pu ^= 1; f->have_prev = 1; return KS265_OK; }
 int ks265_frame_p_restore(ks265_frame *f, int s) { LOGF(NULL, f, s); f->cur_pu = s & 1; f->have_prev = (s >> 1) & 1; return KS265_OK; }
 int ks265_frame_reset_prediction(ks265_frame *f) { LOGF(NULL, f, 0); f->have_prev = 0; return KS265_OK; }
+int16_t *ks265_frame_levels(ks265_frame *f, int comp) { return f && comp >= 0 && comp < 3 ? f->lvl[comp] : NULL; }      /* (the real library's accessor: tests put planes of their own there) */
 
 static uint64_t hash_bytes(const uint8_t *p, size_t n) { uint64_t h = 1469598103934665603ull; for (size_t i = 0; i < n; ++i) { h ^= p[i]; h *= 1099511628211ull; } return h; }
 static uint8_t *luma0(const ks265_frame *f, ks265_pic p) { return p.y + (size_t)f->g.pad_y * f->g.stride_y + f->g.pad_y; }
@@ -281,6 +282,23 @@ static void do_encode(ks265_frame *f, int kind /*0 key, 1 P, 2 B*/, ks265_pic sr
     f->kind_hash = mix;
 }
 int ks265_frame_compact_layout(ks265_frame *f, size_t off[8]);
+/* KS265_STUB_PACK_ORDER = n: the order in which the chunks of a compact block (1024 lines each) lie in its data area - the device's work-groups reserve their room in the
+ * order they get there, the chunk table says where.  Unset or 0: ascending; negative: descending; any other value seeds a permutation (another one for every picture).  Inside
+ * a chunk the lines keep their order */
+static void pack_chunk_order(const ks265_frame *f, size_t nchunk, uint32_t *ord)
+{
+    static int order = -2147483647;
+    if (order == -2147483647) order = getenv("KS265_STUB_PACK_ORDER") ? atoi(getenv("KS265_STUB_PACK_ORDER")) : 0;
+    for (size_t i = 0; i < nchunk; ++i) ord[i] = (uint32_t)(order < 0 ? nchunk - 1 - i : i);
+    if (order <= 0) return;
+    uint64_t st = ((uint64_t)order * 0x9E3779B97F4A7C15ull) ^ f->kind_hash;
+    if (!st) st = 1;
+    for (size_t i = nchunk; i > 1; --i) {
+        st ^= st << 13; st ^= st >> 7; st ^= st << 17;
+        const size_t k = (size_t)(st % i);
+        const uint32_t t = ord[i - 1]; ord[i - 1] = ord[k]; ord[k] = t;
+    }
+}
 static void do_pack(ks265_frame *f, uint8_t *dst, const uint64_t *extra)
 {
     size_t off[8];
@@ -295,20 +313,30 @@ static void do_pack(ks265_frame *f, uint8_t *dst, const uint64_t *extra)
     uint64_t *bm = (uint64_t *)(dst + off[5]);
     uint8_t *data = dst + off[6];
     memset(bm, 0, nchunk * 128);
+    memset(table, 0, nchunk * 4);
     uint32_t stored = 0;
-    if (stub_fast()) memset(table, 0, nchunk * 4);               /* (no levels: nothing stored, nothing to look through) */
-    else
-    for (size_t L = 0; L < nlines; ++L) {                        /* the stored lines in line order; the device packs chunk by chunk in any order, the table says where */
-        if ((L & 1023) == 0) table[L >> 10] = stored;
-        const int p = L >= first[2] ? 2 : L >= first[1] ? 1 : 0;
-        const size_t o = (L - first[p]) * 64, n = pb[p] - o < 64 ? pb[p] - o : 64;
-        const uint8_t *src = (const uint8_t *)f->lvl[p] + o;
-        int nz = 0;
-        for (size_t k = 0; k < n; ++k) nz |= src[k];
-        if (!nz) continue;
-        bm[L >> 6] |= 1ull << (L & 63);
-        memset(data + (size_t)stored * 64, 0, 64); memcpy(data + (size_t)stored * 64, src, n);
-        ++stored;
+    if (!stub_fast()) {                                          /* (KS265_STUB_FAST: no levels: nothing stored, nothing to look through) */
+        uint32_t *cnt = (uint32_t *)calloc(2 * nchunk, sizeof *cnt), *ord = cnt + nchunk;
+        for (int pass = 0; pass < 2; ++pass) {                   /* 0: the bitmap and every chunk's number of stored lines; 1: the lines, each chunk from where the table says */
+            if (pass) {
+                pack_chunk_order(f, nchunk, ord);
+                for (size_t i = 0; i < nchunk; ++i) { table[ord[i]] = stored; stored += cnt[ord[i]]; }
+                memset(cnt, 0, nchunk * sizeof *cnt);
+            }
+            for (size_t L = 0; L < nlines; ++L) {
+                const int p = L >= first[2] ? 2 : L >= first[1] ? 1 : 0;
+                const size_t o = (L - first[p]) * 64, n = pb[p] - o < 64 ? pb[p] - o : 64;
+                const uint8_t *src = (const uint8_t *)f->lvl[p] + o;
+                int nz = 0;
+                for (size_t k = 0; k < n; ++k) nz |= src[k];
+                if (!nz) continue;
+                const size_t at = (size_t)cnt[L >> 10]++;
+                if (!pass) { bm[L >> 6] |= 1ull << (L & 63); continue; }
+                uint8_t *d = data + ((size_t)table[L >> 10] + at) * 64;
+                memset(d, 0, 64); memcpy(d, src, n);
+            }
+        }
+        free(cnt);
     }
     memset(hdr, 0, 64); hdr[2] = stored; hdr[3] = (uint32_t)nlines;
 }

@@ -54,6 +54,19 @@ def test_lanes_hand_out_the_one_lane_stream(stub_lib, tmp_path, bframes):
         assert d.returncode == 0 and os.path.getsize(tmp_path / "d.yuv") == 150 * 128 * 72 * 3 // 2, d.stdout[-300:] + d.stderr[-300:]
 
 
+@pytest.mark.parametrize("W,H", [(200, 136), (416, 240)])
+def test_expander_takes_the_chunks_in_any_order(stub_lib, W, H):
+    """The device's work-groups lay the 1024-line chunks of a compact block into its data area in the order they get there; the chunk table says where.  The stand-in
+    packs them ascending, descending or in a seeded permutation per picture (KS265_STUB_PACK_ORDER): the host's expand_levels must rebuild the same level planes, so
+    the stream is the same - with one writer thread and with five, where the CTU rows of the key pictures (one in four here) are expanded by different threads.
+    200x136: two chunks, lines that straddle picture rows, partial chroma lines; 416x240: five chunks.  This ties the permuted orders to the ascending order, whose
+    stream the other tests of the suite pin; it is not an independent check of the expander."""
+    res = {(order, th): run(stub_lib, 21, 4, 0, W=W, H=H, KS265_STUB_PACK_ORDER=order, KS_TEST_THREADS=th) for order in (0, -1, 7, 1234) for th in (1, 5)}
+    plain = run(stub_lib, 21, 4, 0, W=W, H=H)
+    for k, r in res.items():
+        assert r["vcl"] == 21 and r["idr"] == 6 and r["md5"] == plain["md5"], k
+
+
 @pytest.mark.parametrize("n,iper", [(700, 300), (420, 140)])
 def test_lanes_with_gops_longer_than_the_ring(stub_lib, n, iper):
     """64x64 pictures: the ring holds 128 pictures, a GOP more - a lane that may not hand out yet fills up completely (scheduler waiting for ring space, input waiting
