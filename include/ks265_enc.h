@@ -34,7 +34,8 @@
  *   - transskip, tuIntra, vpp_*, 2-pass, long-term references, VBV / CVQ: accepted, ignored;
  *   - input pictures: the caller's planes are pinned in place and uploaded from where they lie inside QY265EncoderEncodeFrame; the caller may reuse its buffers when the call returns
  *     (the SDK requires them to stay valid until the frame is done);
- *   - pictures in device memory (not in the SDK): ks265_enc_encode_device_frame takes I420, NV12 or RGB(A) planes on the GPU and converts them there, in the caller's stream
+ *   - reconstructed pictures in device memory (not in the SDK; ks265_enc_set_default "devrecon", ks265_enc_get_device_recon below): I420, NV12 or RGB(A), in the caller's stream order;
+   - pictures in device memory (not in the SDK): ks265_enc_encode_device_frame takes I420, NV12 or RGB(A) planes on the GPU and converts them there, in the caller's stream
  *     order (ks265_dev_picture below) - no host copy, no upload, no pinning.
  */
 #ifndef KS265_ENC_H
@@ -181,6 +182,32 @@ typedef struct ks265_dev_picture {
 } ks265_dev_picture;
 int ks265_enc_enable_device_input(void *pEncoder);
 int ks265_enc_encode_device_frame(void *pEncoder, QY265Nal **pNals, int *iNalCount, const ks265_dev_picture *pic, QY265Picture *pOutpic);
+/* extension: reconstructed pictures in device memory - the pictures a decoder of this stream will show, where they already lie.
+ * "devrecon" (ks265_enc_set_default, 0 / 1, default 0; other values QY265_PARAM_BAD_VALUE; a process default read by the next QY265EncoderOpen, like "hash"; the environment's
+ * KS265_DEVRECON=0|1 overrides it at open): every picture's output picture is packed as I420 into a slot of a pool in device memory (per lane the ring of pictures in flight,
+ * + a GOP for a GOP lane; its bytes are logged at open), on whichever stream codes the picture - key pictures stay on their own stream, the stream is byte for byte the one without
+ * the switch, and with the switch off not one call is added.  The scheduler waits for a free slot as it waits for ring space: it never drops a picture and never fails.  Refused at
+ * open, with one `ks265enc: device reconstruction is unavailable: ...` line and the switch then off: a device library without ks265_output_convert, GOP lanes on several GPUs,
+ * the KS265_GRAPH experiment.
+ * When a call hands a picture's NAL units out, its reconstruction joins the handle's list, in the order of the call's NAL units (coding order).
+ *   ks265_enc_device_recon_pending  how many reconstructions the last call handed out that have not been fetched yet;
+ *   ks265_enc_get_device_recon      converts the OLDEST pending one into `dst` and fills info->poc (the display index in the stream, as pOutpic reports it, GOP lanes
+ *                                   included), iSliceType and pts (info may be NULL).  Of `dst`: format, plane, pitch, pixel_step, matrix, full_range, device, stream; pts is
+ *                                   ignored.  KS265_IN_I420 / _NV12 as for the input; KS265_IN_RGB with pixel_step 1 (planar), 3 (RGB24) or 4 - there the three channel
+ *                                   pointers name three bytes of one four-byte pixel that begins at the lowest of them (RGBA, BGRA), and its fourth byte is written as 255.
+ *                                   YCbCr -> RGB in exact integer arithmetic, chroma interpolated bilinearly at HEVC's default siting (tests/yuv_output_ref.py).  Nothing
+ *                                   outside [row start, row start + row bytes) of a row is written: the padding behind a pitch stays.
+ *                                   QY_FAIL: nothing pending.  QY_POINTER: a plane whose whole extent does not lie inside one device allocation of the handle's GPU (host and
+ *                                   managed memory, short buffers, pitches below the row) - the picture stays pending and nothing is enqueued.  QY_NOTSUPPORTED: the switch is
+ *                                   off, dst->device is not the handle's GPU, or a format / pixel step outside the list.
+ * CONTRACT: reconstructions live as long as the call's NAL array: the next QY265EncoderEncodeFrame / ks265_enc_encode_device_frame / QY265EncoderClose on the handle returns
+ * every slot of the previous call to the pool, fetched or not.  The conversion is ordered as the input is, mirrored: it waits for the picture's pack and for everything the caller
+ * enqueued on dst->stream before the call, and everything enqueued on dst->stream after the call waits for it (it runs as one kernel IN dst->stream, which must be a stream of
+ * the handle's GPU and alive until the handle is closed) - the caller reads `dst` with further work on that stream at once.
+ * No host synchronisation happens anywhere and ks265_enc_get_device_recon does not block on the GPU; a slot that is written again waits on its stream for the last conversion
+ * that read it (an event per slot), so a conversion still in flight when its slot goes back to the pool is safe. */
+int ks265_enc_device_recon_pending(void *pEncoder);
+int ks265_enc_get_device_recon(void *pEncoder, const ks265_dev_picture *dst, QY265Picture *info);
 /* extension: write the reconstruction (I420, display order) to `path` - the reference CLI's `-o`; call between Open and the first picture */
 int ks265_enc_set_recon_file(void *pEncoder, const char *path);
 

@@ -112,6 +112,19 @@ typedef struct {
 } ks265_in_desc;
 int ks265_input_validate(ks265_ctx *, const ks265_in_desc *src);
 int ks265_input_convert(ks265_ctx *, const ks265_in_desc *src, uint8_t *dev_i420);
+/* The way back (output_convert.hip): a packed I420 picture in device memory (Y width x height, then U and V width / 2 x height / 2, no padding; width and height even, no
+ * alignment asked of the address) into the picture `dst` describes, by one kernel on the context's stream.  The descriptor keeps its meaning:
+ *   KS265_IN_I420  three planes with their own pitches;   KS265_IN_NV12  Y, then interleaved UV (height / 2 rows);
+ *   KS265_IN_RGB   plane[0..2] = the R, G, B bytes of pixel (0, 0), pixel_step 1 (planar), 3 (RGB24) or 4, pitch[0] between rows.  With pixel_step 4 the three pointers name three
+ *                  different bytes of ONE four-byte pixel, which begins at the lowest of them (RGBA: base + 0 / 1 / 2, BGRA: base + 2 / 1 / 0); the kernel writes the pixel's
+ *                  fourth byte as 255 - a pixel is one word store where pixel and pitch are multiples of 4.  With steps 1 and 3 it writes nothing but the channels.
+ *                  YCbCr -> RGB in exact integer arithmetic, BT.709 or BT.601, limited or full range, chroma brought to the luma grid bilinearly at HEVC's default siting
+ *                  (tests/yuv_output_ref.py is the specification).
+ * No byte outside [row start, row start + row bytes) of any destination row is written: what lies behind a pitch stays.  ks265_output_validate enqueues nothing and judges
+ * `dst` as ks265_input_validate judges a source, for WRITING: KS265_POINTER unless every plane's whole extent lies inside one device allocation on the context's device,
+ * KS265_NOTSUPPORTED for a format / size / step / matrix outside the list.  ks265_output_convert validates destination and source the same way before it launches anything. */
+int ks265_output_validate(ks265_ctx *, const ks265_in_desc *dst);
+int ks265_output_convert(ks265_ctx *, const uint8_t *dev_i420, const ks265_in_desc *dst);
 /* Launch sequences as graphs: between ks265_capture_begin and ks265_capture_end everything enqueued on this context's stream by THIS thread (kernel launches,
  * async memsets of the stage functions) is recorded instead of run (hipStreamBeginCapture, relaxed mode: other threads may go on using the runtime);
  * ks265_capture_end returns an executable graph, ks265_graph_launch enqueues all of it with one runtime call.  A host whose pictures repeat the same

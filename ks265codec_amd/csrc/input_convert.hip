@@ -205,6 +205,9 @@ int q16(double x) { return (int)std::floor(x * 65536 + 0.5); }
 
 }  // namespace
 
+// check_extent for the other translation units that take pictures of the application (output_convert.hip)
+int ks265_check_extent(ks265_ctx *c, const void *p, long long pitch, int rows, long long row_bytes, const char *what) { return check_extent(c, p, pitch, rows, row_bytes, what); }
+
 extern "C" {
 
 int ks265_wait_external(ks265_ctx *c, void *s)

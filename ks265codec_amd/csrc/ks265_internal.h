@@ -33,6 +33,8 @@ static inline int ks265_check_launch(ks265_ctx *ctx)
     ctx->last_error = hipGetErrorString(e);
     return KS265_FAIL;
 }
+// [p, p + pitch (rows - 1) + row_bytes) lies inside one device allocation on the context's device, else KS265_POINTER and last_error (input_convert.hip)
+int ks265_check_extent(ks265_ctx *c, const void *p, long long pitch, int rows, long long row_bytes, const char *what);
 static inline int ks265_hip(ks265_ctx *ctx, hipError_t e)
 {
     if (e == hipSuccess) return KS265_OK;

@@ -1,0 +1,244 @@
+// output_convert.hip — a packed I420 picture of the encoder (its reconstruction) into the caller's picture in device memory (include/ks265_hip.h ks265_output_convert):
+// an I420 repack onto arbitrary pitches, an NV12 interleave, and YCbCr -> RGB (RGB24, RGBA / BGRA, planar) in exact integer arithmetic (tests/yuv_output_ref.py is the
+// specification).  The mirror image of input_convert.hip: one thread owns a run of 8 luma columns across the two luma rows of one chroma row - the rows that share their
+// vertical chroma neighbours - so the three chroma rows it interpolates from are 2 x 3 x 5 bytes in registers (no LDS round trip).  Wide accesses where the address allows, a
+// byte path for the rest; nothing is written outside [row start, row start + row bytes) of any destination row.
+#include "ks265_internal.h"
+#include <cmath>
+
+namespace {
+
+struct OutArgs {
+    const uint8_t *src;           // packed I420: Y W x H, U and V W/2 x H/2
+    uint8_t *p[3];                // I420: Y, U, V; NV12: Y, UV; RGB: R, G, B of pixel (0, 0)
+    long long pitch[3];           // RGB: pitch[0] for all three
+    int step, W, H;
+    int ky8, rv, gu, gv, bu, oy;  // Q16 coefficients (ky8 = 8 ky)
+    int mode;                     // RGB: 0 bytes, 1 planar (8-byte stores per channel), 2 four-byte pixels on word addresses (16-byte stores)
+    uint8_t *px0;                 // pixel_step 4: the first byte of pixel (0, 0) = the lowest channel pointer; the channels are bytes sh[c] / 8 of the pixel, 255 goes to byte asel
+    int sh[3], asel;
+};
+
+// n (8, or an even number below it at the right edge) bytes at p
+__device__ inline void load_run(const uint8_t *p, int n, int (&b)[8])
+{
+    const uintptr_t a = (uintptr_t)p;
+    if (n == 8 && !(a & 3)) {
+        uint32_t lo, hi;
+        if (!(a & 7)) { const uint2 v = *(const uint2 *)p; lo = v.x; hi = v.y; }
+        else { lo = ((const uint32_t *)p)[0]; hi = ((const uint32_t *)p)[1]; }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { b[k] = (int)(lo >> 8 * k & 255); b[4 + k] = (int)(hi >> 8 * k & 255); }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) b[k] = k < n ? p[k] : 0;
+    }
+}
+// chroma columns j0 .. j0 + 4 of one row, clamped to the plane's last column w - 1: four bytes of the run and the right neighbour
+__device__ inline void load_chroma(const uint8_t *row, int j0, int w, int nc, int (&b)[5])
+{
+    const uint8_t *p = row + j0;
+    if (nc == 4 && !((uintptr_t)p & 3)) {
+        const uint32_t v = *(const uint32_t *)p;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) b[k] = (int)(v >> 8 * k & 255);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) b[k] = row[j0 + k < w ? j0 + k : w - 1];
+    }
+    b[4] = row[j0 + 4 < w ? j0 + 4 : w - 1];
+}
+// the n lowest bytes of w[0], w[1] to p
+__device__ inline void store_run(uint8_t *p, int n, uint32_t w0, uint32_t w1)
+{
+    const uintptr_t a = (uintptr_t)p;
+    if (n == 8 && !(a & 7)) *(uint2 *)p = make_uint2(w0, w1);
+    else if (n == 8 && !(a & 3)) { ((uint32_t *)p)[0] = w0; ((uint32_t *)p)[1] = w1; }
+    else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) if (k < n) p[k] = (uint8_t)((k < 4 ? w0 >> 8 * k : w1 >> 8 * (k - 4)) & 255);
+    }
+}
+__device__ inline void store_half(uint8_t *p, int n, uint32_t w)
+{
+    if (n == 4 && !((uintptr_t)p & 3)) *(uint32_t *)p = w;
+    else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) if (k < n) p[k] = (uint8_t)(w >> 8 * k & 255);
+    }
+}
+__device__ inline uint32_t pack4(const int *b) { return (uint32_t)b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24; }
+
+// I420 / NV12: 8 luma columns x the two rows of chroma row i; 4 samples of U and of V
+template <bool NV12> __global__ __launch_bounds__(256) void i420_to_yuv_kernel(OutArgs a)
+{
+    const int x0 = (blockIdx.x * 64 + threadIdx.x) * 8, i = blockIdx.y * 4 + threadIdx.y;
+    if (x0 >= a.W || 2 * i >= a.H) return;
+    const size_t W = (size_t)a.W, npx = W * a.H;
+    const int n = a.W - x0 < 8 ? a.W - x0 : 8, w = a.W / 2, j0 = x0 / 2;
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+        int y[8];
+        load_run(a.src + (2 * i + dy) * W + x0, n, y);
+        store_run(a.p[0] + (2 * i + dy) * a.pitch[0] + x0, n, pack4(y), pack4(y + 4));
+    }
+    int u[5], v[5];
+    load_chroma(a.src + npx + (size_t)i * w, j0, w, n / 2, u);
+    load_chroma(a.src + npx + npx / 4 + (size_t)i * w, j0, w, n / 2, v);
+    if constexpr (NV12) {
+        const int uv[8] = {u[0], v[0], u[1], v[1], u[2], v[2], u[3], v[3]};
+        store_run(a.p[1] + i * a.pitch[1] + x0, n, pack4(uv), pack4(uv + 4));
+    } else {
+        store_half(a.p[1] + i * a.pitch[1] + j0, n / 2, pack4(u));
+        store_half(a.p[2] + i * a.pitch[2] + j0, n / 2, pack4(v));
+    }
+}
+
+// clip255(v >> 19) as a clamp before a logical shift (input_convert.hip shr_clip255: hipcc for gfx950 miscompiles clip255(v >> n) of pairs)
+__device__ inline uint32_t shr19_clip255(int v)
+{
+    const int hi = (256 << 19) - 1;
+    return (uint32_t)(v < 0 ? 0 : v > hi ? hi : v) >> 19;
+}
+
+// RGB: 8 luma columns x the two rows of chroma row i -> 16 pixels
+__global__ __launch_bounds__(256) void i420_to_rgb_kernel(OutArgs a)
+{
+    const int x0 = (blockIdx.x * 64 + threadIdx.x) * 8, i = blockIdx.y * 4 + threadIdx.y;
+    if (x0 >= a.W || 2 * i >= a.H) return;
+    const size_t W = (size_t)a.W, npx = W * a.H;
+    const int n = a.W - x0 < 8 ? a.W - x0 : 8, w = a.W / 2, h = a.H / 2, j0 = x0 / 2;
+    // chroma rows i - 1, i, i + 1 (clamped), columns j0 .. j0 + 4 (clamped) of both planes
+    int cu[3][5], cv[3][5];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const int ci = i + r - 1 < 0 ? 0 : i + r - 1 > h - 1 ? h - 1 : i + r - 1;
+        load_chroma(a.src + npx + (size_t)ci * w, j0, w, n / 2, cu[r]);
+        load_chroma(a.src + npx + npx / 4 + (size_t)ci * w, j0, w, n / 2, cv[r]);
+    }
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+        int y[8];
+        load_run(a.src + (2 * i + dy) * W + x0, n, y);
+        int vu[5], vv[5];                                              // vertical step, weight 4: the row's own chroma row x 3 + the nearer neighbour
+#pragma unroll
+        for (int k = 0; k < 5; ++k) { vu[k] = 3 * cu[1][k] + cu[2 * dy][k]; vv[k] = 3 * cv[1][k] + cv[2 * dy][k]; }
+        uint32_t px[3][8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int j = k >> 1;
+            const int us = (k & 1 ? vu[j] + vu[j + 1] : 2 * vu[j]) - 1024, vs = (k & 1 ? vv[j] + vv[j + 1] : 2 * vv[j]) - 1024;
+            const int y8 = (y[k] - a.oy) * a.ky8 + (1 << 18);
+            px[0][k] = shr19_clip255(y8 + a.rv * vs);
+            px[1][k] = shr19_clip255(y8 + a.gu * us + a.gv * vs);
+            px[2][k] = shr19_clip255(y8 + a.bu * us);
+        }
+        const long long ro = (long long)(2 * i + dy) * a.pitch[0];
+        if (a.mode == 2) {                                             // one word per pixel, the fourth byte 255
+            uint32_t wd[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) wd[k] = px[0][k] << a.sh[0] | px[1][k] << a.sh[1] | px[2][k] << a.sh[2] | 255u << a.asel;
+            uint8_t *q = a.px0 + ro + (long long)x0 * 4;
+            if (n == 8 && !((uintptr_t)q & 15)) {
+                ((uint4 *)q)[0] = make_uint4(wd[0], wd[1], wd[2], wd[3]);
+                ((uint4 *)q)[1] = make_uint4(wd[4], wd[5], wd[6], wd[7]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) if (k < n) ((uint32_t *)q)[k] = wd[k];
+            }
+        } else if (a.mode == 1) {                                      // planar
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch)
+                store_run(a.p[ch] + ro + x0, n, px[ch][0] | px[ch][1] << 8 | px[ch][2] << 16 | px[ch][3] << 24, px[ch][4] | px[ch][5] << 8 | px[ch][6] << 16 | px[ch][7] << 24);
+        } else {                                                       // bytes: RGB24, and four-byte pixels that lie on no word address
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                if (k >= n) continue;
+                const long long o = ro + (long long)(x0 + k) * a.step;
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) a.p[ch][o] = (uint8_t)px[ch][k];
+                if (a.step == 4) a.px0[o + (a.asel >> 3)] = 255;
+            }
+        }
+    }
+}
+
+int q16(double x) { return (int)std::floor(x * 65536 + 0.5); }
+
+int check_out_desc(ks265_ctx *c, const ks265_in_desc *d)
+{
+    if (d->width <= 0 || d->height <= 0 || (d->width & 1) || (d->height & 1)) { c->last_error = "output: width and height even"; return KS265_NOTSUPPORTED; }
+    if (d->format != KS265_IN_I420 && d->format != KS265_IN_NV12 && d->format != KS265_IN_RGB) { c->last_error = "output: unknown format"; return KS265_NOTSUPPORTED; }
+    const long long W = d->width, H = d->height;
+    int r = KS265_OK;
+    if (d->format == KS265_IN_RGB) {
+        if ((d->pixel_step != 1 && d->pixel_step != 3 && d->pixel_step != 4) || (d->matrix != KS265_MATRIX_BT709 && d->matrix != KS265_MATRIX_BT601)) {
+            c->last_error = "output: RGB pixel step 1, 3 or 4, matrix BT.709 or BT.601"; return KS265_NOTSUPPORTED;
+        }
+        if (d->pitch[0] < W * d->pixel_step) { c->last_error = "output: RGB pitch below width x pixel step"; return KS265_POINTER; }
+        if (d->pixel_step == 4) {                                      // the three channels are three different bytes of one four-byte pixel, which begins at the lowest of them
+            const uintptr_t p0 = (uintptr_t)d->plane[0], p1 = (uintptr_t)d->plane[1], p2 = (uintptr_t)d->plane[2];
+            const uintptr_t lo = p0 < p1 ? (p0 < p2 ? p0 : p2) : (p1 < p2 ? p1 : p2), hi = p0 > p1 ? (p0 > p2 ? p0 : p2) : (p1 > p2 ? p1 : p2);
+            if (!d->plane[0] || !d->plane[1] || !d->plane[2]) { c->last_error = "output: NULL"; return KS265_POINTER; }
+            if (hi - lo > 3 || p0 == p1 || p0 == p2 || p1 == p2) { c->last_error = "output: pixel step 4 needs the three channels inside one four-byte pixel"; return KS265_NOTSUPPORTED; }
+            return ks265_check_extent(c, (const void *)lo, d->pitch[0], (int)H, W * 4, "RGBA");
+        }
+        const long long rb = (W - 1) * d->pixel_step + 1;
+        for (int k = 0; k < 3 && !r; ++k) r = ks265_check_extent(c, d->plane[k], d->pitch[0], (int)H, rb, k == 0 ? "R" : k == 1 ? "G" : "B");
+    } else {
+        r = ks265_check_extent(c, d->plane[0], d->pitch[0], (int)H, W, "Y");
+        if (!r && d->format == KS265_IN_NV12) r = ks265_check_extent(c, d->plane[1], d->pitch[1], (int)(H / 2), W, "UV");
+        for (int k = 1; k < 3 && !r && d->format == KS265_IN_I420; ++k) r = ks265_check_extent(c, d->plane[k], d->pitch[k], (int)(H / 2), W / 2, k == 1 ? "U" : "V");
+    }
+    return r;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ks265_output_validate(ks265_ctx *c, const ks265_in_desc *d)
+{
+    if (!c || !d) return KS265_POINTER;
+    ks_use_device(c);
+    return check_out_desc(c, d);
+}
+
+int ks265_output_convert(ks265_ctx *c, const uint8_t *src, const ks265_in_desc *d)
+{
+    if (!c || !d) return KS265_POINTER;
+    ks_use_device(c);
+    int r = check_out_desc(c, d);
+    if (r) return r;
+    const long long W = d->width, H = d->height;
+    if ((r = ks265_check_extent(c, src, W * H * 3 / 2, 1, W * H * 3 / 2, "source"))) return r;
+    OutArgs a = {};
+    a.src = src;
+    for (int k = 0; k < 3; ++k) { a.p[k] = (uint8_t *)d->plane[k]; a.pitch[k] = d->pitch[k]; }
+    a.W = (int)W; a.H = (int)H; a.step = d->pixel_step;
+    const dim3 blk(64, 4), grid((unsigned)(((W + 7) / 8 + 63) / 64), (unsigned)((H / 2 + 3) / 4));
+    if (d->format != KS265_IN_RGB) {
+        if (d->format == KS265_IN_NV12) hipLaunchKernelGGL((i420_to_yuv_kernel<true>), grid, blk, 0, c->stream, a);
+        else hipLaunchKernelGGL((i420_to_yuv_kernel<false>), grid, blk, 0, c->stream, a);
+        return ks265_check_launch(c);
+    }
+    const double Kr = d->matrix == KS265_MATRIX_BT601 ? 0.299 : 0.2126, Kb = d->matrix == KS265_MATRIX_BT601 ? 0.114 : 0.0722, Kg = 1 - Kr - Kb;
+    const double sy = d->full_range ? 1.0 : 219.0 / 255.0, sc = d->full_range ? 1.0 : 224.0 / 255.0;
+    a.oy = d->full_range ? 0 : 16;
+    a.ky8 = 8 * q16(1 / sy);
+    a.rv = q16(2 * (1 - Kr) / sc); a.gu = q16(-2 * Kb * (1 - Kb) / (Kg * sc)); a.gv = q16(-2 * Kr * (1 - Kr) / (Kg * sc)); a.bu = q16(2 * (1 - Kb) / sc);
+    a.mode = d->pixel_step == 1 ? 1 : 0;
+    if (d->pixel_step == 4) {
+        const uintptr_t p0 = (uintptr_t)d->plane[0], p1 = (uintptr_t)d->plane[1], p2 = (uintptr_t)d->plane[2];
+        const uintptr_t lo = p0 < p1 ? (p0 < p2 ? p0 : p2) : (p1 < p2 ? p1 : p2);
+        a.px0 = (uint8_t *)lo;
+        unsigned used = 0;
+        for (int k = 0; k < 3; ++k) { a.sh[k] = 8 * (int)((uintptr_t)d->plane[k] - lo); used |= 1u << (a.sh[k] / 8); }
+        a.asel = 8 * (used == 7 ? 3 : used == 11 ? 2 : 1);                // the byte of the pixel no channel names (byte 0 is always one: the pixel begins at a channel)
+        if (!(lo & 3) && !(d->pitch[0] & 3)) a.mode = 2;
+    }
+    hipLaunchKernelGGL(i420_to_rgb_kernel, grid, blk, 0, c->stream, a);
+    return ks265_check_launch(c);
+}
+
+}  // extern "C"

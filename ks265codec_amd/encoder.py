@@ -10,10 +10,16 @@ The encoder reads each tensor in the order of torch's current stream and makes t
 same stream as soon as encode() returns, with no host synchronisation.  Parameters are QY265ConfigParse names (qp, crf, rc, iper, bframes, lookahead, latency, ...);
 gpb=0|1 is the process default of that name (ks265_enc_set_default: anchors that search two or more past anchors as B slices over them), set before this handle opens.
 hash=2|3 writes a decoded picture hash SEI message (CRC / checksum, computed on the device) behind every picture of THIS handle; the bytes come out of encode() / flush() with the
-picture's."""
+picture's.
+
+recon="rgb"|"bgr"|"rgba"|"bgra"|"rgb_planar"|"nv12"|"i420" (with recon_matrix=, recon_full_range=) keeps the reconstruction of every picture of THIS handle fetchable on the
+device (`devrecon`, include/ks265_enc.h): after every encode() / flush(), enc.recon() returns [(poc, tensor), ...] - the pictures a decoder of the stream will show, as fresh
+uint8 tensors in that format, filled in the order of torch's current stream with no host synchronisation.  They must be fetched before the next encode(): the encoder takes
+the pictures back then."""
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 from . import stream as _stream
 
@@ -66,6 +72,8 @@ def library() -> C.CDLL:
         _lib.QY265EncoderEncodeFrame.argtypes = [C.c_void_p, C.POINTER(C.POINTER(Nal)), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int]
         _lib.ks265_enc_get_quality.argtypes = [C.c_void_p, C.POINTER(Quality)]
         _lib.ks265_enc_encode_device_frame.argtypes = [C.c_void_p, C.POINTER(C.POINTER(Nal)), C.POINTER(C.c_int), C.POINTER(DevPicture), C.c_void_p]
+        _lib.ks265_enc_device_recon_pending.argtypes = [C.c_void_p]
+        _lib.ks265_enc_get_device_recon.argtypes = [C.c_void_p, C.POINTER(DevPicture), C.c_void_p]
     return _lib
 
 
@@ -124,6 +132,12 @@ class Encoder:
         hash_ = params.pop("hash", None)                        # `hash` (ks265_enc.h): for this handle alone - the process default goes back to off once the handle is open
         if hash_ is not None and self.lib.ks265_enc_set_default(b"hash", C.c_int(int(hash_))) != 0:
             raise ValueError(f"parameter hash={hash_!r}: bad value (0, 2 = CRC, 3 = checksum)")
+        self._recon = params.pop("recon", None)                 # `devrecon` (ks265_enc.h) for this handle alone, like `hash`; the format recon() fills its tensors in
+        self._recon_matrix, self._recon_full = int(params.pop("recon_matrix", MATRIX_BT709)), bool(params.pop("recon_full_range", False))
+        if self._recon is not None and self._recon not in _FORMATS:
+            raise ValueError(f"recon: one of {sorted(_FORMATS)}")
+        if self._recon is not None and self.lib.ks265_enc_set_default(b"devrecon", C.c_int(1)) != 0:
+            raise ValueError("parameter recon: the library has no devrecon switch")
         for k, v in (("wdt", width), ("hgt", height), *params.items()):
             rc = self.lib.QY265ConfigParse(self._cfg, str(k).replace("_", "-").encode(), str(v).encode())   # keyword form of the names with a dash: sao_ref=2 -> "sao-ref"
             if rc != 0:
@@ -132,6 +146,8 @@ class Encoder:
         self.h = self.lib.QY265EncoderOpen(self._cfg, C.byref(err))
         if hash_ is not None:
             self.lib.ks265_enc_set_default(b"hash", C.c_int(0))
+        if self._recon is not None:
+            self.lib.ks265_enc_set_default(b"devrecon", C.c_int(0))
         if not self.h:
             raise EncoderError("QY265EncoderOpen", err.value)
         rc = self.lib.ks265_enc_enable_device_input(self.h)
@@ -140,6 +156,13 @@ class Encoder:
             self.h = None
             raise EncoderError("ks265_enc_enable_device_input", rc)
         self._nal, self._nn, self._out, self._pts = C.POINTER(Nal)(), C.c_int(0), Picture(), 0
+        self._flushed, self._held, self._next_display = [], {}, 0  # recon(): what flush() fetched call by call; order="display": early pictures by poc, the next index to return
+        if self._recon is not None:                             # refused at open (a device library without the way back, lanes on several GPUs, KS265_GRAPH)?  Nothing is pending: QY_FAIL if on
+            probe = DevPicture()
+            probe.device = int(os.environ.get("KS265_DEVICE", "0"))
+            if self.lib.ks265_enc_get_device_recon(self.h, C.byref(probe), None) == QY_NOTSUPPORTED:
+                self.close()
+                raise EncoderError("recon=: device reconstruction is unavailable on this handle (see the log)", QY_NOTSUPPORTED)
 
     def _take(self) -> bytes:
         return b"".join(C.string_at(self._nal[i].pPayload, self._nal[i].iSize) for i in range(self._nn.value) if self._nal[i].iSize > 0)
@@ -160,12 +183,48 @@ class Encoder:
 
     def flush(self) -> bytes:
         out = bytearray()
+        self._flushed += self._fetch()                          # (what the last encode() handed out and nobody fetched yet: the first flush call takes it back)
         while self.h is not None and self.lib.QY265EncoderDelayedFrames(self.h):
             rc = self.lib.QY265EncoderEncodeFrame(self.h, C.byref(self._nal), C.byref(self._nn), None, C.addressof(self._out), 0)
             if rc != QY_OK:
                 raise EncoderError("QY265EncoderEncodeFrame (flush)", rc)
             out += self._take()
+            self._flushed += self._fetch()                      # every call of the loop takes the previous call's reconstructions back: they are fetched here, for the next recon()
         return bytes(out)
+
+    def _fetch(self) -> list:
+        """every pending reconstruction (ks265_enc_get_device_recon), oldest first, each into a fresh tensor on torch's current stream"""
+        if self._recon is None or self.h is None:
+            return []
+        import torch
+        W, H, out = self.width, self.height, []
+        shape = {"rgb": (H, W, 3), "bgr": (H, W, 3), "rgba": (H, W, 4), "bgra": (H, W, 4), "rgb_planar": (3, H, W), "nv12": (H * 3 // 2, W), "i420": (H * 3 // 2, W)}[self._recon]
+        info = Picture()
+        while self.lib.ks265_enc_device_recon_pending(self.h) > 0:
+            t = torch.empty(shape, dtype=torch.uint8, device="cuda")
+            rc = self.lib.ks265_enc_get_device_recon(self.h, C.byref(describe(t, self._recon, self._recon_matrix, self._recon_full)), C.addressof(info))
+            if rc != QY_OK:
+                raise EncoderError("ks265_enc_get_device_recon", rc)
+            out.append((info.poc, t))
+        return out
+
+    def recon(self, order: str = "coding") -> list:
+        """[(poc, tensor), ...]: the reconstructions of the pictures the last encode() / flush() handed out (poc = display index in the stream), in the format of recon=.
+        order="coding": as the NAL units came.  order="display": early pictures are kept back - only the run of consecutive display indices that continues what earlier calls
+        returned comes out, the rest with later calls (after flush(): everything)."""
+        if self._recon is None:
+            raise RuntimeError("Encoder(..., recon=FORMAT) switches the reconstructions on")
+        if order not in ("coding", "display"):
+            raise ValueError('order: "coding" or "display"')
+        pics, self._flushed = self._flushed + self._fetch(), []
+        if order == "coding":
+            return pics
+        self._held.update(pics)
+        out = []
+        while self._next_display in self._held:
+            out.append((self._next_display, self._held.pop(self._next_display)))
+            self._next_display += 1
+        return out
 
     def quality(self) -> dict:
         """quality figures of the pictures handed out so far (ks265_enc_get_quality): `frames`; `sse` = summed squared error per plane (psnr=1, else None); `ssim` = per plane the

@@ -15,6 +15,7 @@
 #include "ks265_enc.h"
 #include "ks265_stream.h"
 #include "ks265_gop.h"
+#include "ks265_recon.h"
 #include <dirent.h>
 #include <fcntl.h>
 #include <math.h>
@@ -39,6 +40,11 @@
  * and writes the stream it writes without the switch */
 #pragma weak ks265_picture_hash
 #pragma weak ks265_picture_hash_on
+/* `devrecon` (reconstructed pictures handed out in device memory) reaches the way back the same way: on a device library without it the encoder logs once that device
+ * reconstruction is unavailable and ks265_enc_get_device_recon is QY_NOTSUPPORTED */
+#pragma weak ks265_output_validate
+#pragma weak ks265_output_convert
+#pragma weak ks265_set_stream
 /* `gpb` switches the skip pass off for its anchors the same way: a device library without the setter - the stand-in has no skip pass - is not asked */
 #pragma weak ks265_frame_set_picture_skip
 
@@ -93,7 +99,7 @@ static void md5_hex(const uint8_t *data, size_t n, char out[33])
 
 /* CLI-level switches of `appencoder` that the SDK's QY265EncConfig has no field for (-df, -fixqp, -md5): process-wide defaults a front end
  * sets before QY265EncoderOpen (ks265_enc_set_default) */
-static struct { int df, fixqp, md5, scenecut, cutree, gpb, hash; } g_cli = {1, 0, 0, 0, 1, 0, 0};
+static struct { int df, fixqp, md5, scenecut, cutree, gpb, hash, devrecon; } g_cli = {1, 0, 0, 0, 1, 0, 0, 0};
 int ks265_enc_set_default(const char *name, int value)
 {
     if (!name) return QY_POINTER;
@@ -105,6 +111,7 @@ int ks265_enc_set_default(const char *name, int value)
     if (!strcmp(name, "gpb")) { if (value < 0 || value > 1) return QY265_PARAM_BAD_VALUE; g_cli.gpb = value; return QY_OK; }                /* anchors as B slices over past anchors (ks265_enc.h) */
     /* decoded picture hash SEI messages, x265's numbering: 0 off, 2 CRC, 3 checksum; 1 (MD5) is refused - MD5 is sequential per plane, it stays with -md5's log lines (ks265_enc.h) */
     if (!strcmp(name, "hash")) { if (value != 0 && value != 2 && value != 3) return QY265_PARAM_BAD_VALUE; g_cli.hash = value; return QY_OK; }
+    if (!strcmp(name, "devrecon")) { if (value < 0 || value > 1) return QY265_PARAM_BAD_VALUE; g_cli.devrecon = value; return QY_OK; }   /* reconstructions stay fetchable in device memory (ks265_enc.h) */
     return QY265_PARAM_BAD_NAME;
 }
 
@@ -230,6 +237,7 @@ typedef struct Job {
     uint32_t *hash;                                       /* `hash`: picture_crc [0..2] and picture_checksum [3..5] of the output picture's planes (pinned; NULL without) */
     uint8_t sei[48]; long sei_len;                        /* ... and the suffix SEI NAL unit a writer made of them: goes out behind the slice NAL unit, counted in no controller's bits */
     uint8_t *recon;                                       /* pinned I420 copy of the reconstruction (only with ks265_enc_set_recon_file / -md5) */
+    int rslot;                                            /* `devrecon`: the slot of the lane's pool that holds the picture's packed reconstruction (travels with the picture) */
     char md5[3][33];
     void *ev;                                             /* recorded after the D2H copies */
     uint8_t *nal; size_t nal_cap; long nal_len;
@@ -369,6 +377,12 @@ typedef struct Enc {
      * depends on a few rotating device pointers, the QP and two bits of frame state; each combination is captured once and replayed with one runtime call */
 #define MAX_GRAPHS 256
     int use_graph, ngraph; struct { uint64_t key[9]; void *exec; } graph[MAX_GRAPHS];
+    /* `devrecon` (ks265_enc.h): a pool of packed-I420 pictures on the device, one slot per picture from its submission until the call after the one that handed it out
+     * (ks265_recon.h keeps the books, under mu).  ev_packed: behind the pack on the picture's stream; ev_read: behind the last conversion that read the slot (read_on: there
+     * was one) - the next pack into the slot waits for it.  ctx_rec: the context the conversions run on (the calling thread's alone: it adopts the caller's stream).  taken: what take_output just moved out
+     * of the ring, for the caller of take_output (the calling thread) to hand out or stash */
+    int devrecon, lane_idx; ReconPool rpool; struct ReconSlot { uint8_t *dev; void *ev_packed, *ev_read; int read_on; } rslot[RECON_POOL_MAX];
+    ks265_ctx *ctx_rec; ReconList taken;
     int recon_fd, recon_on; uint8_t *dev_recon;           /* reconstruction dump (the CLI's -o) and / or plane MD5s (-md5 1): recon_on = the pictures come back to the host */
     int md5, fixqp, psnr_hdr; int md5_next; char (*md5_ring)[3][33]; unsigned char *md5_have;   /* MD5 lines go out in display order (ring of 256 by display index) */
     ks265_pic dpb[MAX_DPB]; int dpb_poc[MAX_DPB]; int ndpb;
@@ -421,6 +435,7 @@ typedef struct Enc {
         int la_wanted, la_order, la_prio;                 /* the lookahead's stream: asked for; created first (0), behind the copy streams (1), else with the lookahead's objects; KS265_LA_PRIO */
         int upl_at;                                       /* the uploads' stream: created at position -1 / 0 / 1 / 2 (open_upl_stream), UPL_NONE: there is none */
         int key_prio, anc_prio, srcq;                     /* stream priorities of the two paths beside the main one; the split pipeline's source pictures are allocated */
+        int recon_slots;                                  /* `devrecon`: slots of the pool */
         int input_slots, pinned_mb; size_t spacer;        /* KS265_INPUT_SLOTS (or ENV_UNSET), KS265_PINNED_MB; KS265_PIC_SPACER: bytes in front of every picture (pic_alloc) */
         const char *qmap_path;                            /* KS265_DUMP_QPMAP */
     } plan;
@@ -881,6 +896,7 @@ typedef struct Sub {
     int k, recycled;                                      /* rotation slot of the input buffer / staging set (seq % NPIPE); it has held a picture before */
     int path; PixPath *p;                                 /* the pixel path that codes the picture (PATH_*) */
     int split, direct, graphable;
+    int rslot;                                            /* `devrecon`: the pool slot the reconstruction is packed into (-1 without) */
     const uint8_t *din; ks265_pic srcp; int slot; ks265_pic out;   /* the packed input on the device, the unpacked source picture, the reconstruction's DPB slot */
 } Sub;
 
@@ -897,6 +913,21 @@ static Job *wait_job_slot(Enc *e)
     Job *j = e->quit ? NULL : &e->jobs[e->job_tail];                    /* drained by take_output() of the calling thread itself: never full here */
     pthread_mutex_unlock(&e->mu);
     return j;
+}
+
+/* `devrecon`: a free slot of the pool, waited for like ring space (the calling thread's next call releases what its last one handed out); -1: the lane is closing */
+static int wait_recon_slot(Enc *e)
+{
+    pthread_mutex_lock(&e->mu);
+    const double tw0 = now_ms();
+    int s;
+    while ((s = recon_pool_take(&e->rpool)) < 0 && !e->quit) {
+        pthread_cond_broadcast(&e->cv_sched_done);                      /* (as in wait_job_slot) */
+        pthread_cond_wait(&e->cv_done, &e->mu);
+    }
+    e->st.submit_wait_ms += now_ms() - tw0;
+    pthread_mutex_unlock(&e->mu);
+    return s;
 }
 
 /* pixel path: the main stream / frame object, the key pictures' own or the anchors' own - the ONE place that decides it - and what follows from the choice */
@@ -1057,6 +1088,16 @@ static int recon_home(Enc *e, const Sub *s)
     return r;
 }
 
+/* `devrecon`: the output picture packed into the picture's own pool slot, on the picture's own stream - behind the last conversion that read the slot's previous picture */
+static int recon_pack(Enc *e, const Sub *s)
+{
+    struct ReconSlot *q = &e->rslot[s->rslot];
+    int r = q->read_on ? ks265_stream_wait_event(s->p->ctx, q->ev_read) : 0;
+    if (!r) r = ks265_store_i420(s->p->frame, s->out, q->dev);
+    if (!r) r = ks265_event_record(s->p->ctx, q->ev_packed);
+    return r;
+}
+
 /* the drain of a coded picture: quality pass, its SSIM sums home, the records packed into the staging set of the rotation slot.  on = NULL: on the picture's own stream - there
  * the reconstruction goes home in between, and the staging block must have been copied out before it is written.  captured: inside a graph capture (or its launch-by-launch
  * repeat) - the pass and the packing alone; the wait is in front of the capture, the SSIM copy behind it (not part of the captured picture: every job has its own buffer) */
@@ -1072,6 +1113,7 @@ static int drain_picture(Enc *e, const Sub *s, ks265_ctx *on, int captured)
     if (!r && p->dev_hash && !captured) r = ks265_memcpy_d2h_async(cx, s->j->hash, p->dev_hash, 24);
     if (!on && !captured) {
         if (!r && e->recon_on) r = recon_home(e, s);
+        if (!r && e->devrecon) r = recon_pack(e, s);
         /* the records leave the frame object's buffers for a staging set (device to device, a few microseconds), so that the next picture can start
          * while the copy-out stream drains this one */
         if (!r && s->recycled) r = ks265_stream_wait_event(cx, e->ev_drained[s->k]);
@@ -1139,6 +1181,7 @@ static int code_picture_plain(Enc *e, Sub *s)
         return r;
     }
     if (!r && e->recon_on) r = recon_home(e, s);
+    if (!r && e->devrecon) r = recon_pack(e, s);                        /* (the split pipeline's drain_picture runs on the copy-out stream: the pack stays on the picture's own) */
     /* the drain runs on the copy-out stream (in order with the earlier pictures' drains: the staging block of this slot has been copied out before it is written) */
     if (!r) r = ks265_event_record(cx, e->ev_coded[k]);
     if (!r) r = ks265_stream_wait_event(e->ctx_out, e->ev_coded[k]);
@@ -1196,6 +1239,7 @@ static void fill_job(Enc *e, const Sub *s)
 {
     Job *j = s->j; const Input *in = s->in;
     j->no_sao = s->pic->lean != 0;
+    j->rslot = s->rslot;
     j->disp = in->disp; j->pts = in->pts; j->poc = s->pic->poc; j->kind = s->pic->kind; j->qp = s->qp; j->is_ref = s->pic->is_ref; j->key_headers = s->pic->key_headers; j->rc_delta = e->rc_qp_delta;
     j->rc_budget = (double)in->kbps * 1000.0 / (e->cfg.frameRate > 0 ? e->cfg.frameRate : 25.0);
     j->nal_type = s->pic->kind == 'I' ? KS265_NAL_IDR_W_RADL : s->pic->is_ref ? KS265_NAL_TRAIL_R : KS265_NAL_TRAIL_N;
@@ -1238,6 +1282,8 @@ static int submit(Enc *e, Input *in, const GopPic *pic, int qp)
 {
     Sub s = {.in = in, .pic = pic, .qp = qp};
     if (!(s.j = wait_job_slot(e))) return QY_FAIL;
+    s.rslot = -1;
+    if (e->devrecon && (s.rslot = wait_recon_slot(e)) < 0) return QY_FAIL;
     choose_path(e, &s);
     int r = stage_input(e, &s);
     if (!r) r = set_picture_tools(e, &s);
@@ -1247,7 +1293,10 @@ static int submit(Enc *e, Input *in, const GopPic *pic, int qp)
     if (!r) r = s.graphable ? code_picture_graph(e, &s) : code_picture_plain(e, &s);
     if (!r) r = mark_streams(e, &s);
     if (!r) r = copy_out(e, &s);
-    if (r) return hip_rc(r);
+    if (r) {
+        if (s.rslot >= 0) { pthread_mutex_lock(&e->mu); (void)recon_pool_untake(&e->rpool, s.rslot); pthread_mutex_unlock(&e->mu); }
+        return hip_rc(r);
+    }
     ++e->seq;
     fill_job(e, &s);
     publish_job(e, &s);
@@ -1395,6 +1444,10 @@ static int take_output(Enc *e, int max_in_flight, int max_pics, QY265Nal **pNals
             ++cnt;
         }
         if (out) { out->iSliceType = j->kind == 'I' ? 2 : j->kind == 'P' && !j->gpb ? 1 : 0; out->poc = j->disp; out->pts = j->pts; out->dts = j->pts; }
+        if (e->devrecon) {                                              /* the picture's reconstruction leaves the ring with it: the caller of this function hands it out, or stashes it */
+            const ReconRef ref = {e->lane_idx, j->rslot, j->disp, j->kind == 'I' ? 2 : j->kind == 'P' && !j->gpb ? 1 : 0, j->pts};
+            if (recon_list_push(&e->taken, &ref)) err = QY_OUTOFMEMORY;
+        }
         e->st.frames++; e->st.bytes += (long long)need; e->st.host_write_ms += j->t_write_ms;
         e->st.lat_gpu_ms += j->t_event - j->t_submit; e->st.lat_queue_ms += j->t_taken - j->t_submit;
         if (j->kind == 'I') { e->st.key_wall_ms += j->t_done - j->t_event; e->st.key_cpu_ms += j->t_write_ms; e->st.keys++; }
@@ -1604,6 +1657,16 @@ static void lane_resolve(Enc *e, const QY265EncConfig *cfg, int device, int mult
      * device: an anchor running beside B pictures slows them by what it gains */
     e->anc_on = e->hier && e->refs0 == 1 && e->key_overlap && !e->qmap_on && !e->use_graph && env_int("KS265_ANCHOR_LANE", 0) > 0;
 
+    /* `devrecon` (ks265_enc_set_default, KS265_DEVRECON overrides): every picture's reconstruction is packed into a pool slot and stays fetchable on the device until the call
+     * after the one that handed it out.  Refused - logged, the switch then off - without the way back in the device library, with lanes on several GPUs (multi == 2: the
+     * caller fetches on ONE device) and with the graph experiment (a captured picture would replay one slot) */
+    const int rec_req = env_int("KS265_DEVRECON", g_cli.devrecon) != 0;
+    const int rec_lib = ks265_output_convert && ks265_output_validate && ks265_set_stream;
+    e->devrecon = rec_req && rec_lib && multi != 2 && !graph_asked;
+    if (rec_req && !e->devrecon)
+        logf_(2, e->log_level, "ks265enc: device reconstruction is unavailable: %s (devrecon is ignored)\n",
+              !rec_lib ? "the device library has no ks265_output_convert" : multi == 2 ? "the handle's GOP lanes run on several GPUs" : "the KS265_GRAPH experiment replays captured pictures");
+
     /* the lookahead and the two optional streams */
     /* no -lookahead on the command line and the SDK's default GOP (hierarchical B, 8): the slice-type decision runs by itself (round 4: it costs a search of the half-size
      * picture every fourth picture, and the caller does not wait for it) - the reference's adaptive BiPredFrames is on by default as well.  -lookahead 0 switches it off. */
@@ -1672,6 +1735,15 @@ static void lane_rings(Enc *e)
     if (e->plan.input_slots != ENV_UNSET) e->nin = e->plan.input_slots;
     if (e->nin < e->ring + 32) e->nin = e->ring + 32;
     if (e->nin > MAX_INPUT) e->nin = MAX_INPUT;
+    /* `devrecon`: a slot per picture of the ring - a picture holds its slot while it is in the ring, and the slots the last call handed out come back at the start of the next
+     * one, before anything waits: with fewer slots than the ring the scheduler would wait for the caller with job slots free.  A GOP lane adds a GOP: the pictures of a GOP that is
+     * not yet at the head of the output order leave the ring for the handle's stash and keep their slots there (KS265_DEVRECON_SLOTS: a count above the ring's, experiments) */
+    if (e->devrecon) {
+        e->plan.recon_slots = e->ring + (e->multi ? (e->cfg.iIntraPeriod < 128 ? e->cfg.iIntraPeriod : 128) : 0);
+        const int asked = env_int("KS265_DEVRECON_SLOTS", 0);
+        if (asked > e->ring) e->plan.recon_slots = asked;
+        if (e->plan.recon_slots > RECON_POOL_MAX) e->plan.recon_slots = RECON_POOL_MAX;
+    }
     {   /* pinned host memory is a machine-wide resource: a lane's input slots stay under KS265_PINNED_MB (default 4096 MB; the ring + one mini-GOP is the floor).  At 2160p
          * a slot is 12.4 MB: ring + 32 = 132 slots = 1.6 GB; a GOP lane at -iper 128 asks for 260 = 3.2 GB; eight GPUs with two lanes each = 52 GB without the cap */
         const long long budget = e->plan.pinned_mb * 1048576LL;
@@ -1982,6 +2054,31 @@ static int open_md5(Enc *e)                                            /* -md5 1
 }
 static void close_md5(Enc *e) { free(e->md5_ring); free(e->md5_have); }   /* (what lane_recon_on made goes with the jobs and in lane_close) */
 
+/* `devrecon`: the pool's pictures and events.  No stream: a conversion runs IN the caller's stream, through a context that adopts it (ks265_enc_get_device_recon makes that
+ * context at the first fetch) - measured at 2160p with two lanes, one more stream per lane, idle, cost 7.6 % (846 -> 781 pictures/s: it moves the streams of the lane opened
+ * behind it to other hardware queues, as every stream more does - lane_open) */
+static int open_devrecon(Enc *e)
+{
+    if (!e->devrecon) return KS265_OK;
+    const size_t fsz = (size_t)e->W * e->H * 3 / 2;
+    if (recon_pool_init(&e->rpool, e->plan.recon_slots)) return KS265_FAIL;
+    int r = KS265_OK;
+    for (int i = 0; i < e->rpool.n && !r; ++i) {
+        r = ks265_dev_malloc(main_ctx(e), (void **)&e->rslot[i].dev, fsz);
+        if (!r) r = ks265_event_create(main_ctx(e), &e->rslot[i].ev_packed);
+        if (!r) r = ks265_event_create(main_ctx(e), &e->rslot[i].ev_read);
+    }
+    logf_(1, e->log_level, "ks265enc: device reconstruction: a pool of %d packed I420 pictures, %.1f MB of device memory per lane (the ring of %d pictures in flight%s)\n", e->rpool.n,
+          e->rpool.n * (double)fsz / 1048576.0, e->ring, e->multi ? " + a GOP in the stash" : "");
+    return r;
+}
+static void close_devrecon(Enc *e)                                     /* a conversion still in flight on a stream of the caller's reads its slot: waited for, by its event (the context: last, lane_close) */
+{
+    for (int i = 0; i < RECON_POOL_MAX; ++i) if (e->rslot[i].read_on) (void)ks265_event_wait(main_ctx(e), e->rslot[i].ev_read);
+    for (int i = 0; i < RECON_POOL_MAX; ++i) { ks265_dev_free(main_ctx(e), e->rslot[i].dev); ev_free(main_ctx(e), &e->rslot[i].ev_packed); ev_free(main_ctx(e), &e->rslot[i].ev_read); }
+    recon_list_free(&e->taken);
+}
+
 static int open_threads(Enc *e)
 {
     for (int i = 0; i < e->nthreads; ++i) { e->warg[i].e = e; e->warg[i].idx = i; if (pthread_create(&e->th[i], NULL, worker, &e->warg[i])) break; ++e->nth; }
@@ -2011,6 +2108,7 @@ static void lane_close(Enc *e, int report)
                                                     e->la_t_take / e->in_disp, e->la_t_wait / e->in_disp, e->la_n_wait, e->la_n_poll);
         if (report && e->in_disp) logf_(1, e->log_level, "ks265enc: caller's back-pressure wait %.3f ms per picture\n", e->la_t_bp / e->in_disp);
         if (report) run_summary(e, e->st.frames, e->st.bytes, e->st.sse, e->q_hi, e->q_lo);
+        close_devrecon(e);
         close_jobs(e); close_inputs(e); close_dpb(e); close_key_path(e); close_anchor_path(e); close_pipeline(e);
         for (int i = 0; i < e->ngraph; ++i) ks265_graph_destroy(main_ctx(e), e->graph[i].exec);
         close_quality(e);
@@ -2023,6 +2121,7 @@ static void lane_close(Enc *e, int report)
     for (int i = PATH_KEY; i < NPATH; ++i) if (e->path[i].ctx) ks265_destroy(e->path[i].ctx);   /* the contexts: last */
     if (e->ctx_in) ks265_destroy(e->ctx_in);
     if (e->ctx_out) ks265_destroy(e->ctx_out);
+    if (e->ctx_rec) ks265_destroy(e->ctx_rec);
     if (main_ctx(e)) ks265_destroy(main_ctx(e));
     close_output(e); close_md5(e);
     pthread_mutex_destroy(&e->la_mu);
@@ -2063,6 +2162,7 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
     if (!r) r = open_inputs(e);
     if (!r) r = open_output(e);
     if (!r) r = open_md5(e);
+    if (!r) r = open_devrecon(e);
     if (!r) r = open_threads(e);
     if (r) { *err = hip_rc(r); lane_close(e, 0); return NULL; }
     logf_(0, e->log_level, "ks265enc: GPU %d: %dx%d %.2f fps, qp %d, -me %d (hex below %d), subme %d, refs %d, %s, sao %d (%s), key period %d, %d slice writer threads, %s\n", device, e->W, e->H,
@@ -2506,6 +2606,7 @@ static int lane_set_recon_file(Enc *e, const char *path)
 typedef struct Chunk {
     int lane, closed; long count, delivered, base; int disp0; /* the lane's own display index of the GOP's first picture */
     long stashed; QY265Nal *snal; size_t *soff; int sn, sn_cap; uint8_t *sbuf; size_t scap, spos; QY265Picture sout;
+    ReconList srec;                                                  /* `devrecon`: the stashed pictures' reconstructions (their slots stay with them), in the order of snal */
 } Chunk;
 typedef struct Top {
     int nlanes; Enc *lane[MAX_LANES];
@@ -2517,7 +2618,48 @@ typedef struct Top {
     uint8_t *obuf; size_t ocap, opos;
     double output_ms;
     TopWake wake;
+    ReconList handed;                                                /* `devrecon`: the reconstructions the last call handed out, in the order of its NAL units (ks265_recon.h) */
 } Top;
+
+/* `devrecon`: what take_output just moved out of lane e's ring (Enc::taken) joins `dst` - the handle's list: the slots are handed out; a chunk's stash: they go on travelling.
+ * c: the GOP the pictures belong to (lanes report their own display index), NULL with one lane */
+static int recon_taken(Top *t, Enc *e, const Chunk *c, ReconList *dst)
+{
+    int r = QY_OK;
+    for (int i = 0; i < e->taken.n; ++i) {
+        ReconRef ref = e->taken.v[i];
+        if (c) ref.poc = (int)(c->base + (ref.poc - c->disp0));
+        if (dst == &t->handed) { pthread_mutex_lock(&e->mu); if (recon_pool_hand_out(&e->rpool, ref.slot)) r = QY_FAIL; pthread_mutex_unlock(&e->mu); }
+        if (recon_list_push(dst, &ref)) r = QY_OUTOFMEMORY;
+    }
+    recon_list_clear(&e->taken);
+    return r;
+}
+/* a stashed GOP goes out: its reconstructions are handed out behind what the call has handed out so far */
+static int recon_unstash(Top *t, Chunk *c)
+{
+    Enc *e = t->lane[c->lane];
+    int r = QY_OK;
+    pthread_mutex_lock(&e->mu);
+    for (int i = 0; i < c->srec.n; ++i) if (recon_pool_hand_out(&e->rpool, c->srec.v[i].slot)) r = QY_FAIL;
+    pthread_mutex_unlock(&e->mu);
+    if (recon_list_move(&t->handed, &c->srec)) r = QY_OUTOFMEMORY;
+    return r;
+}
+/* the start of every call on the handle (and its close): every slot the previous call handed out goes back to its lane's pool, fetched or not */
+static void recon_release(Top *t)
+{
+    if (!t->handed.n) return;
+    for (int l = 0; l < t->nlanes; ++l) {
+        Enc *e = t->lane[l];
+        int any = 0;
+        pthread_mutex_lock(&e->mu);
+        for (int i = 0; i < t->handed.n; ++i) if (t->handed.v[i].lane == l) { (void)recon_pool_release(&e->rpool, t->handed.v[i].slot); any = 1; }
+        if (any) pthread_cond_broadcast(&e->cv_done);                  /* the scheduler thread may be waiting for a slot (wait_recon_slot) */
+        pthread_mutex_unlock(&e->mu);
+    }
+    recon_list_clear(&t->handed);
+}
 
 /* is there room for the picture whose first plane is `data`?  A slot in the caller's hands (4: ks265_enc_acquire_input) counts only if THIS picture is the one that was
  * produced into it - a caller may acquire a buffer and then hand in its own, or the picture may be routed to another lane */
@@ -2565,12 +2707,15 @@ static int top_collect_pass(Top *t, QY265Picture *out, long *progress, long *pen
             for (int i = 0; i < c->sn; ++i) c->snal[i].pPayload = c->sbuf + c->soff[i];
             const int ra = top_append(t, c->snal, c->sn);
             if (ra) return ra;
+            const int rr = recon_unstash(t, c);
+            if (rr) return rr;
             c->delivered += c->stashed; *progress += c->stashed; c->stashed = 0; c->sn = 0; c->spos = 0;
             if (out) { out->iSliceType = c->sout.iSliceType; out->pts = c->sout.pts; out->dts = c->sout.dts; out->poc = (int)(c->base + (c->sout.poc - c->disp0)); }
         }
         if (c->delivered == c->count) {
             if (!c->closed) break;                                      /* the GOP still receives input */
             free(c->snal); free(c->soff); free(c->sbuf); c->snal = NULL; c->soff = NULL; c->sbuf = NULL; c->sn_cap = 0; c->scap = 0;
+            recon_list_free(&c->srec);
             t->ch_head = (t->ch_head + 1) % MAX_CHUNKS; --t->ch_n;
             continue;
         }
@@ -2579,9 +2724,11 @@ static int top_collect_pass(Top *t, QY265Picture *out, long *progress, long *pen
         /* (a picture that failed on the device has left the lane's ring like any other - without a payload: it is on the books before the error goes up, or this GOP
          *  would wait for it for ever) */
         const int ra = pics ? top_append(t, nals, n) : QY_OK;
+        const int rr = recon_taken(t, t->lane[c->lane], c, &t->handed);
         c->delivered += pics; *progress += pics;
         if (r) return r;
         if (ra) return ra;
+        if (rr) return rr;
         if (!pics) break;
         if (out) out->poc = (int)(c->base + (out->poc - c->disp0));    /* the lane reports its own display index */
     }
@@ -2601,9 +2748,11 @@ static int top_collect_pass(Top *t, QY265Picture *out, long *progress, long *pen
             QY265Nal *nals; int n = 0, pics = 0;
             const int r = take_output(t->lane[c->lane], MAX_JOBS + 1, (int)left, &nals, &n, &c->sout, &pics);
             const int ra = pics ? nal_append(&c->snal, &c->soff, &c->sn, &c->sn_cap, &c->sbuf, &c->scap, &c->spos, nals, n) : QY_OK;
+            const int rr = recon_taken(t, t->lane[c->lane], c, &c->srec);
             c->stashed += pics; *progress += pics; *pending -= pics;
             if (r) return r;
             if (ra) return ra;
+            if (rr) return rr;
             if (!pics) break;
         }
     }
@@ -2723,9 +2872,11 @@ void *QY265EncoderOpen(QY265EncConfig *cfg, int *err)
         if (lc.threads > 32) lc.threads = 32;
         if (lc.threads < 2) lc.threads = 2;
     }
+    int spread = 0;
+    for (int i = 1; i < t->nlanes; ++i) if (dev[i % ndev] != dev[0]) spread = 1;
     for (int i = 0; i < t->nlanes; ++i) {
         if (i) lc.logLevel = cfg->logLevel > 2 ? cfg->logLevel : 3;     /* one start-up line */
-        t->lane[i] = lane_open(&lc, dev[i % ndev], t->nlanes > 1, err);
+        t->lane[i] = lane_open(&lc, dev[i % ndev], t->nlanes > 1 ? 1 + spread : 0, err);   /* (2: lanes on several GPUs - lane_resolve's `devrecon`) */
         if (!t->lane[i]) {
             if (i == 0) { free(t); return NULL; }
             t->nlanes = i;                                              /* e.g. out of memory for another pipeline: go on with the lanes there are */
@@ -2735,7 +2886,7 @@ void *QY265EncoderOpen(QY265EncConfig *cfg, int *err)
     }
     if ((size_t)cfg->picWidth * cfg->picHeight >= ((size_t)1 << 20)) t->pool = copy_pool_create();
     pthread_mutex_init(&t->wake.mu, NULL); pthread_cond_init(&t->wake.cv, NULL);
-    for (int i = 0; i < t->nlanes; ++i) { t->lane[i]->pool = t->pool; t->lane[i]->multi = t->nlanes > 1; t->lane[i]->wake = t->nlanes > 1 ? &t->wake : NULL; }
+    for (int i = 0; i < t->nlanes; ++i) { t->lane[i]->lane_idx = i; t->lane[i]->pool = t->pool; t->lane[i]->multi = t->nlanes > 1; t->lane[i]->wake = t->nlanes > 1 ? &t->wake : NULL; }
     if (t->nlanes > 1) logf_(0, cfg->logLevel, "ks265enc: %d GOP lanes on %d GPU(s) (closed GOPs of %d pictures coded concurrently, output in GOP order)\n", t->nlanes, ndev < t->nlanes ? ndev : t->nlanes, t->iper);
     return t;
 }
@@ -2752,10 +2903,12 @@ void QY265EncoderClose(void *h)
         for (int i = 0; i < t->nlanes; ++i) for (int k = 0; k < 3; ++k) { hi[k] += t->lane[i]->q_hi[k]; lo[k] += t->lane[i]->q_lo[k]; }
         run_summary(e0, st.frames, st.bytes, st.sse, hi, lo);
     }
+    recon_release(t);
     for (int i = 0; i < t->nlanes; ++i) lane_close(t->lane[i], t->nlanes == 1);
+    recon_list_free(&t->handed);
     pthread_mutex_destroy(&t->wake.mu); pthread_cond_destroy(&t->wake.cv);
     copy_pool_destroy(t->pool);
-    for (int i = 0; i < MAX_CHUNKS; ++i) { free(t->ch[i].snal); free(t->ch[i].soff); free(t->ch[i].sbuf); }
+    for (int i = 0; i < MAX_CHUNKS; ++i) { free(t->ch[i].snal); free(t->ch[i].soff); free(t->ch[i].sbuf); recon_list_free(&t->ch[i].srec); }
     free(t->onals); free(t->ooff); free(t->obuf);
     free(t);
 }
@@ -2792,7 +2945,12 @@ int QY265EncoderDelayedFrames(void *h)
 /* one call of the API: a host picture (in), a device picture (dp) or, neither, the flush */
 static int top_encode(Top *t, QY265Nal **pNals, int *iNalCount, QY265Picture *in, const ks265_dev_picture *dp, QY265Picture *out)
 {
-    if (t->nlanes == 1) return lane_encode_frame(t->lane[0], pNals, iNalCount, in, dp, out);
+    recon_release(t);                                                 /* `devrecon`: the previous call's reconstructions are the pool's again */
+    if (t->nlanes == 1) {
+        const int r1 = lane_encode_frame(t->lane[0], pNals, iNalCount, in, dp, out);
+        const int rr = t->lane[0]->devrecon ? recon_taken(t, t->lane[0], NULL, &t->handed) : QY_OK;
+        return r1 ? r1 : rr;
+    }
     *pNals = NULL; *iNalCount = 0;
     t->on = 0; t->opos = 0;
     int r = QY_OK;
@@ -2954,6 +3112,40 @@ int ks265_enc_encode_device_frame(void *h, QY265Nal **pNals, int *iNalCount, con
     e0->st.in_copy_ms += now_ms() - t0;
     if (rv) return hip_rc(rv);
     return top_encode(t, pNals, iNalCount, NULL, pic, out);
+}
+
+int ks265_enc_device_recon_pending(void *h)
+{
+    const Top *t = (const Top *)h;
+    return t ? recon_list_pending(&t->handed) : 0;
+}
+
+int ks265_enc_get_device_recon(void *h, const ks265_dev_picture *dst, QY265Picture *info)
+{
+    Top *t = (Top *)h;
+    if (!t || !dst) return QY_POINTER;
+    if (!t->lane[0]->devrecon || dst->device != t->lane[0]->dev_id) return QY_NOTSUPPORTED;
+    const ReconRef *ref = recon_list_front(&t->handed);
+    if (!ref) return QY_FAIL;
+    Enc *e = t->lane[ref->lane];
+    struct ReconSlot *q = &e->rslot[ref->slot];
+    /* the whole destination is checked before anything is enqueued: a refused one leaves the picture pending */
+    ks265_in_desc d;
+    dev_desc(e, dst, &d);
+    int r = e->ctx_rec ? KS265_OK : ks265_create(&e->ctx_rec, e->dev_id);   /* (its own stream goes at once: ks265_set_stream below) */
+    if (!r) r = ks265_set_stream(e->ctx_rec, dst->stream);
+    if (!r) r = ks265_output_validate(e->ctx_rec, &d);
+    if (r) return hip_rc(r);
+    /* the conversion runs IN the caller's stream - behind everything enqueued there before the call, in front of everything enqueued after it - once that stream has waited for the
+     * picture's pack; ev_read behind it is what the slot's next pack waits for */
+    r = ks265_stream_wait_event(e->ctx_rec, q->ev_packed);
+    if (!r) r = ks265_output_convert(e->ctx_rec, q->dev, &d);
+    if (!r) r = ks265_event_record(e->ctx_rec, q->ev_read);
+    if (!r) q->read_on = 1;                                             /* (read by the scheduler thread when it takes the slot again: after this call's successor released it, under mu) */
+    if (r) return hip_rc(r);
+    if (info) { info->iSliceType = ref->slice_type; info->poc = ref->poc; info->pts = ref->pts; info->dts = ref->pts; }
+    recon_list_pop(&t->handed);
+    return QY_OK;
 }
 
 int ks265_enc_set_recon_file(void *h, const char *path)

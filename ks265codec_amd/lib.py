@@ -65,6 +65,7 @@ EXPORTS = [
     "ks265_encode_picture", "ks265_encode_picture_b", "ks265_encode_picture_mref", "ks265_encode_picture_b_mref", "ks265_ref_pick", "ks265_ref_decide", "ks265_reconstruct_mref",
     "ks265_intra_candidates", "ks265_cu_decide_ii", "ks265_cu_decide_b_ii", "ks265_intra_inter_reconstruct", "ks265_frame_set_profiling", "ks265_frame_stage_ms", "ks265_frame_me_int_ms", "ks265_frame_levels", "ks265_frame_pu", "ks265_frame_cu8", "ks265_frame_ibest", "ks265_frame_sao", "ks265_sse_picture",
     "ks265_input_validate", "ks265_input_convert", "ks265_wait_external", "ks265_external_wait_event",
+    "ks265_output_validate", "ks265_output_convert",
     "ks265_ssim_picture", "ks265_ssim_picture_on",
     "ks265_picture_hash", "ks265_picture_hash_on",
 ]
