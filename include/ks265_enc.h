@@ -208,6 +208,32 @@ int ks265_enc_encode_device_frame(void *pEncoder, QY265Nal **pNals, int *iNalCou
  * that read it (an event per slot), so a conversion still in flight when its slot goes back to the pool is safe. */
 int ks265_enc_device_recon_pending(void *pEncoder);
 int ks265_enc_get_device_recon(void *pEncoder, const ks265_dev_picture *dst, QY265Picture *info);
+/* extension: ROI - a map of quantiser offsets per picture, from host or device memory ("spend bits here, save them there"; x265's quantOffsets, a QP-delta map).
+ * "roi" (ks265_enc_set_default, 0 / 1, default 0; other values QY265_PARAM_BAD_VALUE; a process default read by the next QY265EncoderOpen, like "hash"; the environment's
+ * KS265_ROI=0|1 overrides it at open; `ks265enc -roi x:y:w:h:dqp` implies it): the stream carries one QP per CTU (cu_qp_delta_enabled_flag = 1 in the PPS, as with -aq and the
+ * cuTree - and, like them, no KS265_GRAPH experiment and no anchor lane).  With the switch off not one call is added and every stream keeps its bytes.  Refused at open, with one
+ * `ks265enc: ROI maps are unavailable: ...` line and the switch then off: a device library without ks265_roi_reduce / ks265_roi_ctu_map, GOP lanes on several GPUs.
+ * A map is a 2-D array of QP offsets, positive = coarser: KS265_ROI_INT8 or KS265_ROI_FLOAT32 elements, one per b x b luma block, b = 1 << log2_block (0 .. 6: from a per-pixel
+ * mask to one value per CTU), ceil(width / b) x ceil(height / b) elements, `pitch` bytes between rows (at least the row, a multiple of the element size).  The CTU's offset is
+ * the mean of its elements (each clipped to [-51, 51]; a non-finite float counts 0), exact in 1/256 QP (tests/roi_map_ref.py is the definition); it is added to
+ * the mean of the CTU's -aq or cuTree offsets before that sum is rounded and clipped to +-12 around the picture's QP.  The lookahead and the cuTree do NOT see the caller's
+ * offsets: slice types, the tree's propagation and the rate controllers' complexity figures are those of the stream without maps.
+ *   ks265_enc_set_next_roi  describes the map of the NEXT picture handed in, by either encode entry point (a flush call does not consume it); NULL withdraws a pending one.  A
+ *                           picture handed in with nothing pending is coded without caller offsets.  Validated at once; on any refusal nothing is pending:
+ *                           QY_NOTSUPPORTED  the switch is off, roi->device is neither -1 nor the handle's GPU, or a type / log2_block / pitch outside the list;
+ *                           QY_POINTER       NULL data, or a device map whose extent [data, data + pitch (rows - 1) + row bytes) does not lie inside one device allocation.
+ * CONTRACT: the map is read inside the next encode call.  A host map (device = -1) must stay valid until that call returns.  A device map is read in the order of roi->stream,
+ * as ks265_dev_picture's planes are: the encoder's read waits for everything enqueued there before the encode call, and everything enqueued there after it waits for the read -
+ * the caller may overwrite the map on that stream as soon as the encode call returns. */
+#define KS265_ROI_INT8 0
+#define KS265_ROI_FLOAT32 1
+typedef struct ks265_roi {
+    int type;                                  /* KS265_ROI_INT8 / _FLOAT32 */
+    int log2_block;                            /* 0 .. 6 */
+    int device;                                /* HIP ordinal, -1 = host memory */
+    const void *data; int pitch; void *stream;
+} ks265_roi;
+int ks265_enc_set_next_roi(void *pEncoder, const ks265_roi *roi);   /* NULL withdraws */
 /* extension: write the reconstruction (I420, display order) to `path` - the reference CLI's `-o`; call between Open and the first picture */
 int ks265_enc_set_recon_file(void *pEncoder, const char *path);
 

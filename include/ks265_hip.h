@@ -639,6 +639,31 @@ int ks265_ssim_picture_on(ks265_ctx *cx, ks265_frame *f, ks265_pic a, ks265_pic 
  * finish in; the accumulators live in the frame object and are left zeroed (no memset launch).  _on: on another context's stream. */
 int ks265_picture_hash(ks265_frame *f, ks265_pic p, uint32_t *dev_hash6);
 int ks265_picture_hash_on(ks265_ctx *cx, ks265_frame *f, ks265_pic p, uint32_t *dev_hash6);
+/* ROI: a caller's per-picture map of quantiser offsets in device memory (roi_map.hip; tests/roi_map_ref.py is the specification).  The map is a 2-D array of QP
+ * offsets, positive = coarser: int8 or float32 elements, one per b x b luma block, b = 1 << log2_block (0 .. 6: from a per-pixel mask to one value per CTU),
+ * cols x rows = ceil(width / b) x ceil(height / b) elements, pitch in bytes (at least the row, a multiple of the element size; the address a multiple of it too).
+ *   ks265_roi_validate  enqueues nothing and judges the map as ks265_input_validate judges a plane: KS265_POINTER unless [data, data + pitch (rows - 1) + row bytes) lies
+ *                       inside ONE device allocation on the context's device; KS265_NOTSUPPORTED for a type, log2_block, size or pitch outside the list.
+ *   ks265_roi_reduce    one launch on the context's stream: dev_records[ctu] (ceil(width / 64) x ceil(height / 64) int32, raster order) = the CTU's mean offset in 1/256 QP.
+ *                       An element counts clip(v, -51, 51) x 256 - a float by rint in float32, half to even, a non-finite one as 0; S = the integer sum over the CTU's
+ *                       elements inside the map, cnt their number, the record floor((2 S + cnt) / (2 cnt)).  Integer sums: the result does not depend on the order of
+ *                       summation.  16-byte loads where the map's address and pitch are multiples of 16, element loads otherwise.  Validates the map and the records
+ *                       (device memory, 4-byte aligned) before it launches.
+ *   ks265_roi_ctu_map   one QP per CTU: d = floor(mean + record / 256.0 + 0.5) with mean = the double sum / count of the CTU's blocks_per_ctu_side^2 block offsets of
+ *                       dev_base (nx x ny doubles, summed row by row; NULL: 0), clipped to +-12, then clip(base_qp + d, qp_lo, qp_hi).  dev_records may be NULL: then
+ *                       d = floor(mean + 0.5), which is bit for bit ks265_aq_ctu_map (blocks_per_ctu_side 4, ctu_cols x ctu_rows = ceil(nx / 4) x ceil(ny / 4)) and
+ *                       ks265_qoff_ctu_map (blocks_per_ctu_side 64 >> (lg + 1)). */
+#define KS265_ROI_INT8 0
+#define KS265_ROI_FLOAT32 1
+typedef struct {
+    int32_t type, log2_block;
+    int32_t cols, rows;                        /* the map's size in elements */
+    const void *data; int32_t pitch;
+} ks265_roi_desc;
+int ks265_roi_validate(ks265_ctx *, const ks265_roi_desc *map);
+int ks265_roi_reduce(ks265_ctx *, const ks265_roi_desc *map, int width, int height, int32_t *dev_records);
+int ks265_roi_ctu_map(ks265_ctx *, const int32_t *dev_records, const double *dev_base, int nx, int ny, int blocks_per_ctu_side, int ctu_cols, int ctu_rows,
+                      int base_qp, int qp_lo, int qp_hi, int8_t *dev_map);
 
 #ifdef __cplusplus
 }

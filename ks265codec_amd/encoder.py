@@ -15,7 +15,12 @@ picture's.
 recon="rgb"|"bgr"|"rgba"|"bgra"|"rgb_planar"|"nv12"|"i420" (with recon_matrix=, recon_full_range=) keeps the reconstruction of every picture of THIS handle fetchable on the
 device (`devrecon`, include/ks265_enc.h): after every encode() / flush(), enc.recon() returns [(poc, tensor), ...] - the pictures a decoder of the stream will show, as fresh
 uint8 tensors in that format, filled in the order of torch's current stream with no host synchronisation.  They must be fetched before the next encode(): the encoder takes
-the pictures back then."""
+the pictures back then.
+
+roi=True lets THIS handle take a map of quantiser offsets with every picture (`roi`, include/ks265_enc.h): encode(tensor, format, roi=MAP, roi_block=16) with MAP a 2-D int8 or
+float32 array of QP offsets (positive = coarser), one element per roi_block x roi_block luma samples (1, 2, 4 .. 64), ceil(H / roi_block) x ceil(W / roi_block) elements, unit
+column stride - a CUDA tensor, read in the order of torch's current stream like the picture (it may be overwritten on that stream as soon as encode() returns), or a NumPy array
+in host memory (read before encode() returns)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -46,6 +51,14 @@ class DevPicture(C.Structure):
                 ("matrix", C.c_int), ("full_range", C.c_int), ("stream", C.c_void_p), ("pts", C.c_longlong)]
 
 
+class Roi(C.Structure):
+    """ks265_roi of include/ks265_enc.h"""
+    _fields_ = [("type", C.c_int), ("log2_block", C.c_int), ("device", C.c_int), ("data", C.c_void_p), ("pitch", C.c_int), ("stream", C.c_void_p)]
+
+
+ROI_INT8, ROI_FLOAT32 = 0, 1
+
+
 class Quality(C.Structure):
     """ks265_enc_quality of include/ks265_enc.h"""
     _fields_ = [("frames", C.c_long), ("have_sse", C.c_int), ("have_ssim", C.c_int), ("sse", C.c_double * 3), ("ssim", C.c_double * 3), ("last_poc", C.c_int),
@@ -74,6 +87,7 @@ def library() -> C.CDLL:
         _lib.ks265_enc_encode_device_frame.argtypes = [C.c_void_p, C.POINTER(C.POINTER(Nal)), C.POINTER(C.c_int), C.POINTER(DevPicture), C.c_void_p]
         _lib.ks265_enc_device_recon_pending.argtypes = [C.c_void_p]
         _lib.ks265_enc_get_device_recon.argtypes = [C.c_void_p, C.POINTER(DevPicture), C.c_void_p]
+        _lib.ks265_enc_set_next_roi.argtypes = [C.c_void_p, C.POINTER(Roi)]
     return _lib
 
 
@@ -118,6 +132,26 @@ def describe(t, format: str, matrix: int = MATRIX_BT709, full_range: bool = Fals
     return p
 
 
+def describe_roi(m, block: int = 16) -> Roi:
+    """the ks265_roi of a 2-D int8 / float32 map with unit column stride: a GPU tensor (no copy; read on torch's current stream) or a NumPy array in host memory"""
+    import numpy as np
+    if block not in (1, 2, 4, 8, 16, 32, 64):
+        raise ValueError("roi_block: 1, 2, 4, 8, 16, 32 or 64")
+    r = Roi()
+    r.log2_block = block.bit_length() - 1
+    if isinstance(m, np.ndarray):
+        if m.ndim != 2 or m.dtype not in (np.int8, np.float32) or (m.shape[1] > 1 and m.strides[1] != m.itemsize) or m.strides[0] < m.shape[1] * m.itemsize:
+            raise ValueError("roi: a 2-D int8 or float32 array with unit column stride")
+        r.type, r.device, r.data, r.pitch = ROI_INT8 if m.dtype == np.int8 else ROI_FLOAT32, -1, m.ctypes.data, m.strides[0]
+        return r
+    import torch
+    if not isinstance(m, torch.Tensor) or m.device.type != "cuda" or m.dim() != 2 or m.dtype not in (torch.int8, torch.float32) or (m.shape[1] > 1 and m.stride(1) != 1) or m.stride(0) < m.shape[1]:
+        raise ValueError("roi: a 2-D int8 or float32 GPU tensor (or NumPy array) with unit column stride")
+    r.type, r.device = ROI_INT8 if m.dtype == torch.int8 else ROI_FLOAT32, m.device.index if m.device.index is not None else torch.cuda.current_device()
+    r.data, r.pitch, r.stream = m.data_ptr(), m.stride(0) * m.element_size(), torch.cuda.current_stream(m.device).cuda_stream
+    return r
+
+
 class Encoder:
     """one encoder handle with device input enabled; encode() returns the bytes of the NAL units that call produced (the encoder's output lags its input)"""
 
@@ -138,6 +172,9 @@ class Encoder:
             raise ValueError(f"recon: one of {sorted(_FORMATS)}")
         if self._recon is not None and self.lib.ks265_enc_set_default(b"devrecon", C.c_int(1)) != 0:
             raise ValueError("parameter recon: the library has no devrecon switch")
+        self._roi = bool(params.pop("roi", False))              # `roi` (ks265_enc.h) for this handle alone, like `hash`
+        if self._roi and self.lib.ks265_enc_set_default(b"roi", C.c_int(1)) != 0:
+            raise ValueError("parameter roi: the library has no roi switch")
         for k, v in (("wdt", width), ("hgt", height), *params.items()):
             rc = self.lib.QY265ConfigParse(self._cfg, str(k).replace("_", "-").encode(), str(v).encode())   # keyword form of the names with a dash: sao_ref=2 -> "sao-ref"
             if rc != 0:
@@ -148,6 +185,8 @@ class Encoder:
             self.lib.ks265_enc_set_default(b"hash", C.c_int(0))
         if self._recon is not None:
             self.lib.ks265_enc_set_default(b"devrecon", C.c_int(0))
+        if self._roi:
+            self.lib.ks265_enc_set_default(b"roi", C.c_int(0))
         if not self.h:
             raise EncoderError("QY265EncoderOpen", err.value)
         rc = self.lib.ks265_enc_enable_device_input(self.h)
@@ -167,17 +206,30 @@ class Encoder:
     def _take(self) -> bytes:
         return b"".join(C.string_at(self._nal[i].pPayload, self._nal[i].iSize) for i in range(self._nn.value) if self._nal[i].iSize > 0)
 
-    def encode(self, tensor, format: str = "rgba", matrix: int = MATRIX_BT709, full_range: bool = False) -> bytes:
+    def encode(self, tensor, format: str = "rgba", matrix: int = MATRIX_BT709, full_range: bool = False, roi=None, roi_block: int = 16) -> bytes:
         if self.h is None:
             raise RuntimeError("encoder closed")
         pic = describe(tensor, format, matrix, full_range)
+        if roi is not None:
+            if not self._roi:
+                raise RuntimeError("Encoder(..., roi=True) switches the ROI maps on")
+            rd = describe_roi(roi, roi_block)
+            b = 1 << rd.log2_block
+            if tuple(roi.shape) != ((self.height + b - 1) // b, (self.width + b - 1) // b):
+                raise ValueError(f"roi {tuple(roi.shape)}: a {self.width}x{self.height} picture in blocks of {b} is {((self.height + b - 1) // b, (self.width + b - 1) // b)}")
         shape = (tensor.shape[0], tensor.shape[1]) if format not in ("i420", "nv12", "rgb_planar") else (tensor.shape[1], tensor.shape[2]) if format == "rgb_planar" \
             else (tensor.shape[0] * 2 // 3, tensor.shape[1])
         if shape != (self.height, self.width):
             raise ValueError(f"picture {shape[1]}x{shape[0]}, encoder {self.width}x{self.height}")
+        if roi is not None:                                     # (behind every check of the picture: a refused picture leaves nothing pending)
+            rc = self.lib.ks265_enc_set_next_roi(self.h, C.byref(rd))
+            if rc != QY_OK:
+                raise EncoderError("ks265_enc_set_next_roi", rc)
         pic.pts, self._pts = self._pts, self._pts + 1
         rc = self.lib.ks265_enc_encode_device_frame(self.h, C.byref(self._nal), C.byref(self._nn), C.byref(pic), C.addressof(self._out))
         if rc != QY_OK:
+            if roi is not None:
+                self.lib.ks265_enc_set_next_roi(self.h, None)       # a picture refused before it was handed in has not taken its map: withdrawn
             raise EncoderError("ks265_enc_encode_device_frame", rc)
         return self._take()
 

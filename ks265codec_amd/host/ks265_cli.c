@@ -5,11 +5,14 @@
  * (the Android demo parses the latter; with -ssim the reference's ` ssim: kbps Y U V` line follows it), `H265 encoder passed!!!` at the end. */
 #define _GNU_SOURCE
 #include "ks265_enc.h"
+#include "ks265_roi.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
 #include <pthread.h>
+/* -roi reaches the entry behind it as a weak symbol: an encoder library without it leaves it NULL, and the option is ignored with a line */
+#pragma weak ks265_enc_set_next_roi
 
 static double now_ms(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec * 1e3 + t.tv_nsec * 1e-6; }
 
@@ -56,7 +59,7 @@ static void usage(void)
 {
     puts("usage: ks265enc -i in.yuv -wdt W -hgt H [-fr FPS] [-preset ultrafast..placebo] [-latency zerolatency|lowdelay|livestreaming|default] [-tune T]\n"
          "                [-rc 0..5] [-qp Q] [-crf C] [-br KBPS] [-iper N] [-bframes N] [-frms N] [-threads N] [-psnr 0|1|2] [-ssim 0|1|2] [-b out.265] [-o recon.yuv]\n"
-         "                [-me 0|1|2] [-subme 0|1|2] [-merange R] [-ref N] [-sao 0..4] [-sao-ref 0|1|2 (the reference's SAO decision: 1 = as -sao 3, 2 = with its left / up merge candidates)] [-df 0|1] [-fixqp 0|1] [-md5 0|1] [-scenecut N (with -lookahead: the reference's scene-cut rule at threshold N)] [-cutree 0|1 (-rc 3: the reference's macroblock tree over the lookahead, a QP per CTU; default 1)] [-gpb 0|1 (anchors of the B-picture GOPs that search two or more past anchors go out as B slices over them; default 0)] [-hash 0|2|3 (a decoded picture hash SEI message behind every picture: 2 = CRC, 3 = checksum; default 0)] [-aq 0|1 -aqs S (adaptive quantisation: a QP per CTU from the reference's block-variance rule)] [-c config_file] [-gpus N] [-v]\n"
+         "                [-me 0|1|2] [-subme 0|1|2] [-merange R] [-ref N] [-sao 0..4] [-sao-ref 0|1|2 (the reference's SAO decision: 1 = as -sao 3, 2 = with its left / up merge candidates)] [-df 0|1] [-fixqp 0|1] [-md5 0|1] [-scenecut N (with -lookahead: the reference's scene-cut rule at threshold N)] [-cutree 0|1 (-rc 3: the reference's macroblock tree over the lookahead, a QP per CTU; default 1)] [-gpb 0|1 (anchors of the B-picture GOPs that search two or more past anchors go out as B slices over them; default 0)] [-hash 0|2|3 (a decoded picture hash SEI message behind every picture: 2 = CRC, 3 = checksum; default 0)] [-aq 0|1 -aqs S (adaptive quantisation: a QP per CTU from the reference's block-variance rule)] [-roi x:y:w:h:dqp (up to 8 times: dqp is added to the QP of the CTUs under the rectangle, in luma samples, for the whole stream; later rectangles win)] [-c config_file] [-gpus N] [-v]\n"
          "  I420 8-bit input; width and height multiples of 8.  Needs one MI355X (gfx950): there is no CPU fallback.");
 }
 
@@ -99,6 +102,7 @@ int main(int argc, char **argv)
     const char *in_path = NULL, *out_path = NULL, *preset = "medium", *latency = "default", *tune = "default";
     const char *rec_path = NULL;
     int frames = -1;
+    ks265_roi_rect roi_rect[KS265_ROI_MAX_RECTS]; int nroi = 0;
     /* two passes over the arguments: preset / latency / tune first (they reset every field), then the explicit settings */
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "-v")) { printf("%s\n", strLibQy265Version); return 0; }
@@ -125,6 +129,13 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "-df") || !strcmp(a, "-fixqp") || !strcmp(a, "-md5") || !strcmp(a, "-scenecut") || !strcmp(a, "-cutree") || !strcmp(a, "-gpb") || !strcmp(a, "-hash")) {       /* CLI switches without a QY265EncConfig field */
             if (ks265_enc_set_default(a + 1, atoi(v)) != QY_OK) { fprintf(stderr, "bad value for %s: %s\n", a, v); return 2; }
         }
+        else if (!strcmp(a, "-roi")) {                                                       /* a rectangle of QP offsets for the whole stream (ks265_enc.h `roi`): implies the switch */
+            ks265_roi_rect *q = &roi_rect[nroi < KS265_ROI_MAX_RECTS ? nroi : 0];
+            char tail;
+            if (nroi >= KS265_ROI_MAX_RECTS || sscanf(v, "%d:%d:%d:%d:%d%c", &q->x, &q->y, &q->w, &q->h, &q->dqp, &tail) != 5) { fprintf(stderr, "bad value for -roi: %s (x:y:w:h:dqp, at most %d rectangles)\n", v, KS265_ROI_MAX_RECTS); return 2; }
+            ++nroi;
+            if (ks265_enc_set_default("roi", 1) != QY_OK) return 2;
+        }
         else if (!strcmp(a, "-gpus")) setenv("KS265_GPUS", v, 1);                            /* closed GOPs dealt to N GPUs behind this one handle (ks265_enc.h) */
         else {
             const int r = QY265ConfigParse(&cfg, a + 1, v);
@@ -145,6 +156,11 @@ int main(int argc, char **argv)
     if (!h) { fprintf(stderr, "QY265EncoderOpen failed: 0x%08x\n", (unsigned)err); return 1; }
     if (rec_path && ks265_enc_set_recon_file(h, rec_path) != QY_OK) { fprintf(stderr, "cannot write the reconstruction to %s\n", rec_path); return 1; }
     const size_t luma = (size_t)cfg.picWidth * cfg.picHeight, fsz = luma * 3 / 2;
+    /* -roi: the rectangles rasterised once at 16 x 16 into an int8 map in host memory, handed in with every picture */
+    ks265_roi roi = {KS265_ROI_INT8, KS265_ROI_RECT_LOG2, -1, NULL, ks265_roi_map_cols(cfg.picWidth, KS265_ROI_RECT_LOG2), NULL};
+    int8_t *roi_map = nroi ? (int8_t *)malloc((size_t)roi.pitch * (size_t)ks265_roi_map_rows(cfg.picHeight, KS265_ROI_RECT_LOG2)) : NULL;
+    if (nroi && (!roi_map || ks265_roi_rasterise(roi_rect, nroi, cfg.picWidth, cfg.picHeight, roi_map, roi.pitch))) { fprintf(stderr, "-roi: cannot make the map\n"); return 1; }
+    roi.data = roi_map;
     Reader rd;
     memset(&rd, 0, sizeof rd);
     rd.f = fi; rd.fsz = fsz; rd.limit = frames;
@@ -169,6 +185,10 @@ int main(int argc, char **argv)
         if (!buf) break;
         yuv.pData[0] = buf; yuv.pData[1] = buf + luma; yuv.pData[2] = buf + luma + luma / 4;
         pic.pts = n;
+        if (nroi && (err = ks265_enc_set_next_roi ? ks265_enc_set_next_roi(h, &roi) : QY_NOTSUPPORTED) != QY_OK) {
+            if (err != QY_NOTSUPPORTED) { fprintf(stderr, "-roi: the map was refused: 0x%08x\n", (unsigned)err); return 1; }
+            fprintf(stderr, "-roi is ignored: this handle takes no ROI maps\n"); nroi = 0;      /* (the encoder has logged why at open) */
+        }
         err = QY265EncoderEncodeFrame(h, &nal, &nnal, &pic, &outp, 0);
         if (err) { fprintf(stderr, "EncodeFrame failed: 0x%08x\n", (unsigned)err); return 1; }
         for (int k = 0; k < nnal && fo; ++k) fwrite(nal[k].pPayload, 1, (size_t)nal[k].iSize, fo);
@@ -190,6 +210,7 @@ int main(int argc, char **argv)
     printf("per picture: enqueue -> records on the host %.2f ms, enqueue -> writer pick-up %.2f ms\n", st.frames ? st.lat_gpu_ms / st.frames : 0.0, st.frames ? st.lat_queue_ms / st.frames : 0.0);
     QY265EncoderClose(h);                                            /* prints "bitrate, psnr: ..." */
     puts("H265 encoder passed!!!");
+    free(roi_map);
     free(rd.buf[0]); free(rd.buf[1]); fclose(fi); if (fo) fclose(fo);
     return 0;
 }

@@ -16,6 +16,7 @@
 #include "ks265_stream.h"
 #include "ks265_gop.h"
 #include "ks265_recon.h"
+#include "ks265_roi.h"
 #include <dirent.h>
 #include <fcntl.h>
 #include <math.h>
@@ -45,6 +46,11 @@
 #pragma weak ks265_output_validate
 #pragma weak ks265_output_convert
 #pragma weak ks265_set_stream
+/* `roi` (the caller's quantiser offset maps) reaches the map's reduction and the combination with the -aq / cuTree offsets the same way: on a device library without them the
+ * encoder logs once that ROI maps are unavailable and ks265_enc_set_next_roi is QY_NOTSUPPORTED */
+#pragma weak ks265_roi_validate
+#pragma weak ks265_roi_reduce
+#pragma weak ks265_roi_ctu_map
 /* `gpb` switches the skip pass off for its anchors the same way: a device library without the setter - the stand-in has no skip pass - is not asked */
 #pragma weak ks265_frame_set_picture_skip
 
@@ -99,7 +105,7 @@ static void md5_hex(const uint8_t *data, size_t n, char out[33])
 
 /* CLI-level switches of `appencoder` that the SDK's QY265EncConfig has no field for (-df, -fixqp, -md5): process-wide defaults a front end
  * sets before QY265EncoderOpen (ks265_enc_set_default) */
-static struct { int df, fixqp, md5, scenecut, cutree, gpb, hash, devrecon; } g_cli = {1, 0, 0, 0, 1, 0, 0, 0};
+static struct { int df, fixqp, md5, scenecut, cutree, gpb, hash, devrecon, roi; } g_cli = {1, 0, 0, 0, 1, 0, 0, 0, 0};
 int ks265_enc_set_default(const char *name, int value)
 {
     if (!name) return QY_POINTER;
@@ -112,6 +118,7 @@ int ks265_enc_set_default(const char *name, int value)
     /* decoded picture hash SEI messages, x265's numbering: 0 off, 2 CRC, 3 checksum; 1 (MD5) is refused - MD5 is sequential per plane, it stays with -md5's log lines (ks265_enc.h) */
     if (!strcmp(name, "hash")) { if (value != 0 && value != 2 && value != 3) return QY265_PARAM_BAD_VALUE; g_cli.hash = value; return QY_OK; }
     if (!strcmp(name, "devrecon")) { if (value < 0 || value > 1) return QY265_PARAM_BAD_VALUE; g_cli.devrecon = value; return QY_OK; }   /* reconstructions stay fetchable in device memory (ks265_enc.h) */
+    if (!strcmp(name, "roi")) { if (value < 0 || value > 1) return QY265_PARAM_BAD_VALUE; g_cli.roi = value; return QY_OK; }             /* quantiser offset maps of the caller's (ks265_enc.h) */
     return QY265_PARAM_BAD_NAME;
 }
 
@@ -322,7 +329,9 @@ static void copy_shared(CopyPool *p, uint8_t *d, const uint8_t *s, size_t n)
  * QP in force when the picture was handed in (QY265EncoderReconfig) - iper: the key period in force then - all three travel WITH the picture: the scheduler thread may be several
  * pictures behind the caller.  dev / ev_up: the slot's twin on the device, uploaded when the picture is handed in (round 4), and the event behind that upload; up_sync: the twin
  * was filled by a host-synchronous copy (nothing to wait for) */
-typedef struct Input { int used, disp, key, base_qp, iper, mini4, kbps, la_what, la_p, la_buf, up_sync; long long pts; uint8_t *i420; uint8_t *dev; void *ev_up; } Input;
+typedef struct Input { int used, disp, key, base_qp, iper, mini4, kbps, la_what, la_p, la_buf, up_sync; long long pts; uint8_t *i420; uint8_t *dev; void *ev_up;
+                       /* `roi`: the picture's record (one int32 per CTU, ks265_roi_reduce's) on the device, its pinned twin for a map in host memory, the event behind its filling */
+                       int roi_has; int32_t *roi_rec, *roi_host; void *ev_roi; } Input;
 
 /* one pixel path: a stream (context), the frame object that codes on it, its source picture and what its quality pass and -aq write on the device.  PATH_MAIN codes every picture
  * that has no path of its own (and is the context that owns the lane's allocations and events); PATH_KEY: the key pictures (Enc::key_overlap); PATH_ANC: the anchors of the
@@ -381,6 +390,7 @@ typedef struct Enc {
      * (ks265_recon.h keeps the books, under mu).  ev_packed: behind the pack on the picture's stream; ev_read: behind the last conversion that read the slot (read_on: there
      * was one) - the next pack into the slot waits for it.  ctx_rec: the context the conversions run on (the calling thread's alone: it adopts the caller's stream).  taken: what take_output just moved out
      * of the ring, for the caller of take_output (the calling thread) to hand out or stash */
+    int roi_on;                                           /* `roi` (ks265_enc.h): pictures may come with a map of quantiser offsets; one QP per CTU in the stream */
     int devrecon, lane_idx; ReconPool rpool; struct ReconSlot { uint8_t *dev; void *ev_packed, *ev_read; int read_on; } rslot[RECON_POOL_MAX];
     ks265_ctx *ctx_rec; ReconList taken;
     int recon_fd, recon_on; uint8_t *dev_recon;           /* reconstruction dump (the CLI's -o) and / or plane MD5s (-md5 1): recon_on = the pictures come back to the host */
@@ -1008,10 +1018,20 @@ static int set_rdoq_tables(Enc *e, Sub *s)
     return r;
 }
 
-/* one QP per CTU around this picture's QP (cuTree, else -aq): the map is made, handed to the frame object and copied home for the writer */
+/* `roi`: one QP per CTU from the base offsets (the cuTree's, -aq's or none) and the picture's record (none: the base alone, bit for bit the plain entries) - in the base's
+ * place, behind the same waits, + the wait for the record's filling (ks265_roi_reduce or the upload, on ctx_up) */
+static int roi_ctu_map(Enc *e, Sub *s, ks265_ctx *ca, const double *base, int nx, int ny, int bpc, int lo, int hi, int8_t *qm)
+{
+    const Input *in = s->in;
+    int r = in->roi_has ? ks265_stream_wait_event(ca, in->ev_roi) : 0;
+    if (!r) r = ks265_roi_ctu_map(ca, in->roi_has ? in->roi_rec : NULL, base, nx, ny, bpc, e->geom.ctu_cols, e->geom.ctu_rows, s->qp, lo, hi, qm);
+    return r;
+}
+
+/* one QP per CTU around this picture's QP (cuTree, else -aq; `roi`: + the caller's offsets): the map is made, handed to the frame object and copied home for the writer */
 static int set_qp_map(Enc *e, Sub *s)
 {
-    if (!e->ct_on && !e->aq_on) return 0;
+    if (!e->qmap_on) return 0;
     const int k = s->k; PixPath *p = s->p;
     ks265_ctx *ca = s->split ? e->ctx_in : p->ctx;
     /* a key picture on its own stream runs beside the pictures of earlier GOPs - among them the one three submissions back, whose kernels still read dev_qmap[k]
@@ -1023,18 +1043,20 @@ static int set_qp_map(Enc *e, Sub *s)
         struct CtPic *cp = ct_slot(e, s->in->disp);
         if (cp->disp != s->in->disp) r = KS265_FAIL;
         if (!r) r = ks265_stream_wait_event(ca, e->ct_ev);
-        if (!r) r = ks265_qoff_ctu_map(ca, cp->qoff, e->ct_nx, e->ct_ny, e->ct_lg, e->geom.ctu_cols, e->geom.ctu_rows, s->qp, e->cfg.qpmin, e->cfg.qpmax ? e->cfg.qpmax : 51, qm);
+        if (!r && e->roi_on) r = roi_ctu_map(e, s, ca, cp->qoff, e->ct_nx, e->ct_ny, 64 >> (e->ct_lg + 1), e->cfg.qpmin, e->cfg.qpmax ? e->cfg.qpmax : 51, qm);
+        else if (!r) r = ks265_qoff_ctu_map(ca, cp->qoff, e->ct_nx, e->ct_ny, e->ct_lg, e->geom.ctu_cols, e->geom.ctu_rows, s->qp, e->cfg.qpmin, e->cfg.qpmax ? e->cfg.qpmax : 51, qm);
         if (!r) r = ks265_event_record(ca, cp->ev_used);
         cp->used = 1;
-    } else {
+    } else if (e->aq_on) {
         /* the source picture is on the device: block variances -> offsets (the reference's arithmetic) -> one QP per CTU around this picture's QP.  With the split pipeline
          * this runs on the copy-in stream right behind the unpack (off the pixel path's chain: the mean is a sequential sum, 0.15 ms at 2160p); the map stays in its rotation
          * slot while the picture's kernels and the copy-home run */
         const size_t oy = (size_t)e->geom.pad_y * e->geom.stride_y + e->geom.pad_y, oc = (size_t)e->geom.pad_c * e->geom.stride_c + e->geom.pad_c;
         r = ks265_frame_adapt_quant(ca, s->srcp.y + oy, e->geom.stride_y, s->srcp.u + oc, s->srcp.v + oc, e->geom.stride_c, e->aq_nx, e->aq_ny, e->aq_nx * e->aq_ny, e->cfg.fAqStrength,
                                     p->aq_off, p->aq_inv, p->aq_scratch);
-        if (!r) r = ks265_aq_ctu_map(ca, p->aq_off, e->aq_nx, e->aq_ny, s->qp, e->cfg.rc ? e->cfg.qpmin : 0, e->cfg.rc && e->cfg.qpmax ? e->cfg.qpmax : 51, qm);
-    }
+        if (!r && e->roi_on) r = roi_ctu_map(e, s, ca, p->aq_off, e->aq_nx, e->aq_ny, 4, e->cfg.rc ? e->cfg.qpmin : 0, e->cfg.rc && e->cfg.qpmax ? e->cfg.qpmax : 51, qm);
+        else if (!r) r = ks265_aq_ctu_map(ca, p->aq_off, e->aq_nx, e->aq_ny, s->qp, e->cfg.rc ? e->cfg.qpmin : 0, e->cfg.rc && e->cfg.qpmax ? e->cfg.qpmax : 51, qm);
+    } else r = roi_ctu_map(e, s, ca, NULL, 0, 0, 4, e->cfg.rc ? e->cfg.qpmin : 0, e->cfg.rc && e->cfg.qpmax ? e->cfg.qpmax : 51, qm);   /* `roi` alone: the picture's QP + the caller's offsets (-aq's bounds) */
     if (!r) r = ks265_frame_set_qp_map(p->frame, qm);
     if (!r) r = ks265_memcpy_d2h_async(ca, s->j->qp_map, qm, (size_t)e->geom.ctu_cols * e->geom.ctu_rows);
     if (!r && s->split) { r = ks265_event_record(e->ctx_in, e->ev_h2d[k]); if (!r) r = ks265_stream_wait_event(p->ctx, e->ev_h2d[k]); }   /* (recorded again behind the map: the pixel path waits for this one) */
@@ -1628,7 +1650,14 @@ static void lane_resolve(Enc *e, const QY265EncConfig *cfg, int device, int mult
     }
     if (e->ct_depth < e->gop_b + 1) e->ct_depth = e->gop_b + 1;
     if (e->ct_depth > CT_RING - 40) e->ct_depth = CT_RING - 40;
-    e->qmap_on = e->aq_on || e->ct_on;
+    /* `roi` (ks265_enc_set_default, KS265_ROI overrides): refused - logged, the switch then off - without the entries in the device library and with lanes on several GPUs
+     * (multi == 2: the caller's maps lie on ONE device) */
+    const int roi_req = env_int("KS265_ROI", g_cli.roi) != 0;
+    const int roi_lib = ks265_roi_validate && ks265_roi_reduce && ks265_roi_ctu_map && ks265_wait_external && ks265_external_wait_event;
+    e->roi_on = roi_req && roi_lib && multi != 2;
+    if (roi_req && !e->roi_on)
+        logf_(2, e->log_level, "ks265enc: ROI maps are unavailable: %s (roi is ignored)\n", !roi_lib ? "the device library has no ks265_roi_reduce" : "the handle's GOP lanes run on several GPUs");
+    e->qmap_on = e->aq_on || e->ct_on || e->roi_on;
     e->plan.qmap_path = e->qmap_on ? getenv("KS265_DUMP_QPMAP") : NULL;
     if (e->ct_on) {                                                    /* the lookahead window's pictures: half size, in blocks of 8 or 16 samples */
         e->ct_w = e->W / 2; e->ct_h = e->H / 2;
@@ -2014,11 +2043,21 @@ static int open_inputs(Enc *e)
         for (int i = 0; i < e->nin && !r; ++i) { r = ks265_dev_malloc(main_ctx(e), (void **)&e->in[i].dev, fsz); if (!r) r = ks265_event_create(e->ctx_up, &e->in[i].ev_up); }
         logf_(2, e->log_level, "ks265enc: %d input slots with a device twin each: %.2f GB of device memory per lane (KS265_INPUT_SLOTS / KS265_PINNED_MB bound the slot count)\n", e->nin, e->nin * (double)fsz / 1073741824.0);
     }
+    if (e->roi_on) {                                                    /* every slot: the picture's record on the device, its pinned twin, the event behind its filling - on the upload stream there is, no stream more */
+        const size_t nb = (size_t)e->geom.ctu_cols * e->geom.ctu_rows * sizeof(int32_t);
+        if (!e->ctx_up) { e->ctx_up = e->ctx_la ? e->ctx_la : main_ctx(e); reg_handle(main_ctx(e), 1); }
+        for (int i = 0; i < e->nin && !r; ++i) {
+            r = ks265_dev_malloc(main_ctx(e), (void **)&e->in[i].roi_rec, nb);
+            if (!r) r = ks265_host_malloc(main_ctx(e), (void **)&e->in[i].roi_host, nb);
+            if (!r) r = ks265_event_create(e->ctx_up, &e->in[i].ev_roi);
+        }
+    }
     return r;
 }
 static void close_inputs(Enc *e)                                       /* (also what lane_enable_device_input added: twins, their events, the handle's count) */
 {
-    for (int i = 0; i < MAX_INPUT; ++i) { ks265_host_free(main_ctx(e), e->in[i].i420); ks265_dev_free(main_ctx(e), e->in[i].dev); ev_free(e->ctx_up, &e->in[i].ev_up); }
+    for (int i = 0; i < MAX_INPUT; ++i) { ks265_host_free(main_ctx(e), e->in[i].i420); ks265_dev_free(main_ctx(e), e->in[i].dev); ev_free(e->ctx_up, &e->in[i].ev_up);
+                                          ks265_dev_free(main_ctx(e), e->in[i].roi_rec); ks265_host_free(main_ctx(e), e->in[i].roi_host); ev_free(e->ctx_up, &e->in[i].ev_roi); }
 }
 static void close_input_streams(Enc *e)                                /* behind the lookahead (ctx_up may be its stream) */
 {
@@ -2416,7 +2455,7 @@ static void dev_desc(const Enc *e, const ks265_dev_picture *p, ks265_in_desc *d)
 
 /* one picture into the lane - a host picture (yuv: copied to a pinned slot or uploaded from where it lies) or a device picture (dp, validated by the caller: converted into the
  * slot's twin on ctx_up in the order of the caller's stream) - and on to the scheduler thread.  key: it starts a closed GOP regardless of the period */
-static int lane_put(Enc *e, const QY265YUV *yuv, const ks265_dev_picture *dp, long long pts, int key)
+static int lane_put(Enc *e, const QY265YUV *yuv, const ks265_dev_picture *dp, const ks265_roi *roi, long long pts, int key)
 {
     if (!dp && (!yuv || !yuv->pData[0] || !yuv->pData[1] || !yuv->pData[2])) return QY_POINTER;
     if (!dp && (yuv->iWidth != e->W || yuv->iHeight != e->H)) return QY_NOTSUPPORTED;
@@ -2434,11 +2473,27 @@ static int lane_put(Enc *e, const QY265YUV *yuv, const ks265_dev_picture *dp, lo
     for (int i = 0; i < e->nin && !slot; ++i) if (!e->in[i].used) slot = &e->in[i];
     for (int i = 0; i < e->nin && !slot; ++i) if (e->in[i].used == 4) slot = &e->in[i];   /* last resort: a buffer the caller acquired and did not use for this picture - copy into it
                                                                                             * (the caller's pointer to it is dead from here on, as after any EncodeFrame call) */
-    if (slot) { slot->used = 3; slot->up_sync = 0; }                   /* being filled */
+    if (slot) { slot->used = 3; slot->up_sync = 0; slot->roi_has = 0; }   /* being filled */
     pthread_mutex_unlock(&e->mu);
     if (!slot) return QY_FAIL;                                         /* one lane: cannot happen (more input slots than pictures in flight + one mini-GOP); lanes: the caller checked lane_has_slot */
     uint8_t *u = slot->i420 + (size_t)e->W * e->H, *v = u + (size_t)e->W * e->H / 4;
     int direct = 0;
+    if (roi && e->roi_on) {                                            /* (validated by ks265_enc_set_next_roi) the map becomes the slot's record on ctx_up, beside the picture's own way in */
+        int ru;
+        if (roi->device >= 0) {                                        /* the caller's stream -> ctx_up: the reduction -> ev_roi -> the caller's stream waits for it */
+            const ks265_roi_desc d = {roi->type, roi->log2_block, ks265_roi_map_cols(e->W, roi->log2_block), ks265_roi_map_rows(e->H, roi->log2_block), roi->data, roi->pitch};
+            ru = ks265_wait_external(e->ctx_up, roi->stream);
+            if (!ru) ru = ks265_roi_reduce(e->ctx_up, &d, e->W, e->H, slot->roi_rec);
+            if (!ru) ru = ks265_event_record(e->ctx_up, slot->ev_roi);
+            if (!ru) ru = ks265_external_wait_event(e->ctx_up, roi->stream, slot->ev_roi);
+        } else {                                                       /* host memory: reduced here, on the calling thread (ks265_roi.h); the record is uploaded */
+            ru = ks265_roi_reduce_host(roi->type, roi->log2_block, roi->data, roi->pitch, e->W, e->H, slot->roi_host) ? KS265_NOTSUPPORTED : KS265_OK;
+            if (!ru) ru = ks265_memcpy_h2d_async(e->ctx_up, slot->roi_rec, slot->roi_host, (size_t)e->geom.ctu_cols * e->geom.ctu_rows * sizeof(int32_t));
+            if (!ru) ru = ks265_event_record(e->ctx_up, slot->ev_roi);
+        }
+        if (ru) { pthread_mutex_lock(&e->mu); slot->used = 0; e->sched_err = hip_rc(ru); pthread_mutex_unlock(&e->mu); return hip_rc(ru); }
+        slot->roi_has = 1;
+    }
     if (dp) {                                                          /* the caller's stream -> ctx_up: conversion into the twin -> ev_up -> the caller's stream waits for it */
         ks265_in_desc d;
         dev_desc(e, dp, &d);
@@ -2522,12 +2577,12 @@ static int lane_flush_begin(Enc *e, int wait)
     return all;
 }
 
-static int lane_encode_frame(Enc *e, QY265Nal **pNals, int *iNalCount, QY265Picture *in, const ks265_dev_picture *dp, QY265Picture *out)
+static int lane_encode_frame(Enc *e, QY265Nal **pNals, int *iNalCount, QY265Picture *in, const ks265_dev_picture *dp, const ks265_roi *roi, QY265Picture *out)
 {
     *pNals = e->nals; *iNalCount = 0;
     int r = QY_OK;
     if (in || dp) {
-        r = in ? lane_put(e, in->yuv, NULL, in->pts, 0) : lane_put(e, NULL, dp, dp->pts, 0);
+        r = in ? lane_put(e, in->yuv, NULL, roi, in->pts, 0) : lane_put(e, NULL, dp, roi, dp->pts, 0);
         if (r) return r;
         /* finished pictures (copied to the output buffer); when the ring of in-flight pictures is nearly full, wait for the oldest ones -
          * only as many as needed, the writers keep running */
@@ -2619,6 +2674,7 @@ typedef struct Top {
     double output_ms;
     TopWake wake;
     ReconList handed;                                                /* `devrecon`: the reconstructions the last call handed out, in the order of its NAL units (ks265_recon.h) */
+    ks265_roi roi; int roi_set;                                      /* `roi`: the map of the next picture handed in (ks265_enc_set_next_roi) */
 } Top;
 
 /* `devrecon`: what take_output just moved out of lane e's ring (Enc::taken) joins `dst` - the handle's list: the slots are handed out; a chunk's stash: they go on travelling.
@@ -2946,8 +3002,10 @@ int QY265EncoderDelayedFrames(void *h)
 static int top_encode(Top *t, QY265Nal **pNals, int *iNalCount, QY265Picture *in, const ks265_dev_picture *dp, QY265Picture *out)
 {
     recon_release(t);                                                 /* `devrecon`: the previous call's reconstructions are the pool's again */
+    const ks265_roi *roi = (in || dp) && t->roi_set ? &t->roi : NULL;  /* `roi`: the pending map goes with this picture - whatever becomes of the call, nothing stays pending (a flush: it stays) */
+    if (in || dp) t->roi_set = 0;
     if (t->nlanes == 1) {
-        const int r1 = lane_encode_frame(t->lane[0], pNals, iNalCount, in, dp, out);
+        const int r1 = lane_encode_frame(t->lane[0], pNals, iNalCount, in, dp, roi, out);
         const int rr = t->lane[0]->devrecon ? recon_taken(t, t->lane[0], NULL, &t->handed) : QY_OK;
         return r1 ? r1 : rr;
     }
@@ -2975,7 +3033,7 @@ static int top_encode(Top *t, QY265Nal **pNals, int *iNalCount, QY265Picture *in
             if (r) return r;
         }
         t->output_ms += now_ms() - t0;
-        r = in ? lane_put(e, in->yuv, NULL, in->pts, first) : lane_put(e, NULL, dp, dp->pts, first);
+        r = in ? lane_put(e, in->yuv, NULL, roi, in->pts, first) : lane_put(e, NULL, dp, roi, dp->pts, first);
         if (r) return r;
         ++t->ch[(t->ch_head + t->ch_n - 1) % MAX_CHUNKS].count; ++t->n_in; --t->chunk_left;
         const double t1 = now_ms();
@@ -3112,6 +3170,26 @@ int ks265_enc_encode_device_frame(void *h, QY265Nal **pNals, int *iNalCount, con
     e0->st.in_copy_ms += now_ms() - t0;
     if (rv) return hip_rc(rv);
     return top_encode(t, pNals, iNalCount, NULL, pic, out);
+}
+
+int ks265_enc_set_next_roi(void *h, const ks265_roi *roi)
+{
+    Top *t = (Top *)h;
+    if (!t) return QY_POINTER;
+    t->roi_set = 0;                                                     /* withdrawn; on any refusal below nothing is pending */
+    if (!roi) return QY_OK;
+    Enc *e0 = t->lane[0];
+    if (!e0->roi_on) return QY_NOTSUPPORTED;
+    if (roi->device != -1 && roi->device != e0->dev_id) return QY_NOTSUPPORTED;
+    if (ks265_roi_check(roi->type, roi->log2_block, roi->pitch, e0->W, e0->H)) return QY_NOTSUPPORTED;
+    if (!roi->data) return QY_POINTER;
+    if (roi->device >= 0) {                                             /* the whole map is checked before anything of it is enqueued */
+        const ks265_roi_desc d = {roi->type, roi->log2_block, ks265_roi_map_cols(e0->W, roi->log2_block), ks265_roi_map_rows(e0->H, roi->log2_block), roi->data, roi->pitch};
+        const int rv = ks265_roi_validate(main_ctx(e0), &d);
+        if (rv) return hip_rc(rv);
+    }
+    t->roi = *roi; t->roi_set = 1;
+    return QY_OK;
 }
 
 int ks265_enc_device_recon_pending(void *h)

@@ -42,6 +42,13 @@ class Pic(C.Structure):
     _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p)]
 
 
+class RoiDesc(C.Structure):                   # ks265_roi_desc
+    _fields_ = [("type", C.c_int32), ("log2_block", C.c_int32), ("cols", C.c_int32), ("rows", C.c_int32), ("data", C.c_void_p), ("pitch", C.c_int32)]
+
+
+ROI_INT8, ROI_FLOAT32 = 0, 1
+
+
 class Ks265Error(RuntimeError):
     pass
 
@@ -68,6 +75,7 @@ EXPORTS = [
     "ks265_output_validate", "ks265_output_convert",
     "ks265_ssim_picture", "ks265_ssim_picture_on",
     "ks265_picture_hash", "ks265_picture_hash_on",
+    "ks265_roi_validate", "ks265_roi_reduce", "ks265_roi_ctu_map",
 ]
 
 
@@ -330,6 +338,33 @@ class KsContext:
     def cutree_finish(self, cnt: int, intra, invq, prop, aq_off, dbl: int, out):
         """the cuTree finish (enc@0x480964..0x480a54) on device arrays; out (float64) updated in place"""
         self._chk(self.lib.ks265_cutree_finish(self.h, C.c_int(cnt), _p(intra), _p(invq), _p(prop), _p(aq_off), C.c_int(dbl), _p(out)))
+
+    # ---- ROI quantiser offset maps (include/ks265_hip.h ks265_roi_*)
+    def roi_desc(self, m, log2_block: int) -> RoiDesc:
+        """descriptor of a 2-D int8 / float32 device tensor with unit column stride (any row stride)"""
+        t = self.torch
+        if m.dim() != 2 or m.dtype not in (t.int8, t.float32) or (m.shape[1] > 1 and m.stride(1) != 1):
+            raise Ks265Error("a ROI map is a 2-D int8 or float32 tensor with unit column stride")
+        return RoiDesc(ROI_INT8 if m.dtype == t.int8 else ROI_FLOAT32, log2_block, m.shape[1], m.shape[0], m.data_ptr(), m.stride(0) * m.element_size())
+
+    def roi_validate(self, desc: RoiDesc) -> int:
+        """the library's return code (0, KS265_POINTER -3, KS265_NOTSUPPORTED -4): nothing is enqueued"""
+        return int(self.lib.ks265_roi_validate(self.h, C.byref(desc)))
+
+    def roi_reduce(self, m, log2_block: int, width: int, height: int, out=None):
+        """one int32 per CTU, the CTU's mean offset in 1/256 QP (device tensor, raster order); out: an int32 device tensor of ceil(width / 64) * ceil(height / 64) words"""
+        n = ((width + 63) // 64) * ((height + 63) // 64)
+        if out is None:
+            out = self.torch.empty(n, dtype=self.torch.int32, device=self.device)
+        self._chk(self.lib.ks265_roi_reduce(self.h, C.byref(self.roi_desc(m, log2_block)), C.c_int(width), C.c_int(height), _p(out)))
+        return out
+
+    def roi_ctu_map(self, records, base, nx: int, ny: int, blocks_per_ctu_side: int, ctu_cols: int, ctu_rows: int, base_qp: int, lo: int, hi: int) -> np.ndarray:
+        """one QP per CTU (int8, raster) from the records (int32 device tensor or None) and the block offsets (float64 device tensor or None)"""
+        out = self.zeros(ctu_cols * ctu_rows)
+        self._chk(self.lib.ks265_roi_ctu_map(self.h, _p(records) if records is not None else None, _p(base) if base is not None else None, C.c_int(nx), C.c_int(ny),
+                                             C.c_int(blocks_per_ctu_side), C.c_int(ctu_cols), C.c_int(ctu_rows), C.c_int(base_qp), C.c_int(lo), C.c_int(hi), _p(out)))
+        return self.host(out, np.int8)
 
     def intra_pred(self, ref, dst, blks: np.ndarray):
         """g_IntraPredFunction: predict every described block from dev `ref` into dev `dst` (in place)"""

@@ -40,7 +40,7 @@ HIPLIB = os.path.join(HERE, "libks265hip.so")
 def build(force: bool = False) -> str:
     """libks265enc.so = bitstream writer + the SDK-compatible encoder API (links libks265hip.so when that has been built; without it only
     the writer is available, which is all the CPU tests need); ks265enc = the appencoder-compatible CLI"""
-    deps = SRC + ENC_SRC + [CLI_SRC] + [os.path.join(INC, h) for h in ("ks265_stream.h", "ks265_hip.h", "ks265_enc.h")] + [os.path.join(HERE, "host", h) for h in ("ks265_gop.h", "ks265_recon.h")]
+    deps = SRC + ENC_SRC + [CLI_SRC] + [os.path.join(INC, h) for h in ("ks265_stream.h", "ks265_hip.h", "ks265_enc.h")] + [os.path.join(HERE, "host", h) for h in ("ks265_gop.h", "ks265_recon.h", "ks265_roi.h")]
     have_hip = os.path.exists(HIPLIB)
     if force or not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps) or (have_hip and os.path.getmtime(HIPLIB) > os.path.getmtime(LIB)):
         flags = ["gcc", "-O2", "-std=c11", "-fPIC", "-Wall", "-Wextra", "-I", INC]
