@@ -182,6 +182,21 @@ typedef struct ks265_dev_picture {
 } ks265_dev_picture;
 int ks265_enc_enable_device_input(void *pEncoder);
 int ks265_enc_encode_device_frame(void *pEncoder, QY265Nal **pNals, int *iNalCount, const ks265_dev_picture *pic, QY265Picture *pOutpic);
+/* extension: device pictures of ANOTHER size, scaled to the encoder's on the GPU (one decoded or rendered picture into a ladder of handles).  The resampler is separable and
+ * exact (tests/yuv_scale_ref.py is the specification): filter 0 = triangle (bilinear, widened when shrinking), 1 = Catmull-Rom (widened the same way); luma and
+ * vertical chroma centre-sited, horizontal chroma cosited as HEVC's default siting; an RGB source is converted at ITS size as above and the I420 picture is scaled.
+ *   ks265_enc_enable_device_scale  after ks265_enc_enable_device_input, before the first picture: allocates per GOP lane one I420 picture of the largest source size (the RGB
+ *       sources' way station) and nothing else.  QY_NOTSUPPORTED: device input off; after the first picture; a device library without the scaler (one log line "ks265enc: input
+ *       scaling is unavailable: ..."); max_src_width no multiple of 8, max_src_height odd, either above 8192 or above 8 times the encoder's; an encoder whose width or height is
+ *       no multiple of 8.
+ *   ks265_enc_encode_device_frame_scaled  as ks265_enc_encode_device_frame - the same contract on `stream`, the same two events, no stream more - for a picture of
+ *       src_width x src_height: width a multiple of 8, height even, within the maximum, each ratio to the encoder's size at most 8 either way (else QY_NOTSUPPORTED); planes are
+ *       judged at the SOURCE's size (QY_POINTER).  A refused picture enqueues nothing and consumes no pending ROI map.  A source of the encoder's own size IS
+ *       ks265_enc_encode_device_frame.  The scaled picture is what the encoder sees everywhere: lookahead, -aq, cuTree, lanes, hash, devrecon; a `roi` map refers to the
+ *       encoder's size.  Each lane keeps the tables of its four most recent (source size, filter) pairs; a fifth replaces the least recently used: built on the calling thread, after a wait for
+ *       the lane's upload stream - a source that cycles through more than four sizes pays that wait and the tables with every picture. */
+int ks265_enc_enable_device_scale(void *pEncoder, int max_src_width, int max_src_height);
+int ks265_enc_encode_device_frame_scaled(void *pEncoder, QY265Nal **pNals, int *iNalCount, const ks265_dev_picture *pic, int src_width, int src_height, int filter, QY265Picture *pOutpic);
 /* extension: reconstructed pictures in device memory - the pictures a decoder of this stream will show, where they already lie.
  * "devrecon" (ks265_enc_set_default, 0 / 1, default 0; other values QY265_PARAM_BAD_VALUE; a process default read by the next QY265EncoderOpen, like "hash"; the environment's
  * KS265_DEVRECON=0|1 overrides it at open): every picture's output picture is packed as I420 into a slot of a pool in device memory (per lane the ring of pictures in flight,

@@ -112,6 +112,27 @@ typedef struct {
 } ks265_in_desc;
 int ks265_input_validate(ks265_ctx *, const ks265_in_desc *src);
 int ks265_input_convert(ks265_ctx *, const ks265_in_desc *src, uint8_t *dev_i420);
+/* Pictures of ANOTHER size (input_scale.hip; tests/yuv_scale_ref.py is the specification): a separable resampler in exact integer arithmetic - filter 0 a
+ * triangle (bilinear, widened when shrinking), 1 Catmull-Rom (widened the same way); luma and vertical chroma centre-sited, horizontal chroma cosited (HEVC's default siting);
+ * Q14 coefficients that sum to 16384, taps outside the source dropped and the rest renormalised; an int16 intermediate with 6 fractional bits; every output byte is the
+ * specification's.  Sizes: source width a multiple of 8 and height even, destination width and height multiples of 8, all at most 8192, each ratio at most 8 either way.
+ *   ks265_scale_plan_create    builds the four tables (host/ks265_scale.h) and puts them into device memory: every allocation and copy of the scaler happens here, it returns
+ *                              when they are done.  KS265_NOTSUPPORTED for sizes, ratios or a filter outside the list.  A plan belongs to the context's device and may be used
+ *                              by any context of that device, one picture after another.
+ *   ks265_scale_plan_destroy   frees the tables; the caller has waited for every ks265_input_scale that uses the plan (the encoder host waits for its upload stream before
+ *                              it replaces a cached plan).
+ *   ks265_input_scale_validate enqueues nothing: `src` (with the SOURCE's width and height, which must be the plan's: KS265_NOTSUPPORTED otherwise) is judged as
+ *                              ks265_input_validate judges it - KS265_POINTER for extents, KS265_NOTSUPPORTED for formats and sizes.
+ *   ks265_input_scale          validates source, destination (plan's width x height x 3 / 2 bytes of device memory, 16-byte aligned) and scratch before anything is launched.
+ *                              An I420 or NV12 source is read where it lies, with its pitches; scratch may be NULL.  An RGB source is first converted by ks265_input_convert
+ *                              into scratch_i420 - source width x height x 3 / 2 bytes of device memory, 16-byte aligned, the caller's (NULL: KS265_POINTER) - and that picture
+ *                              is scaled, on the same stream.  One kernel makes all three planes.  No byte outside [row start, row start + row bytes) of a source row is
+ *                              read, none outside the destination picture written.  A plan whose sizes are equal is ks265_input_convert alone. */
+typedef struct ks265_scale_plan ks265_scale_plan;
+int ks265_scale_plan_create(ks265_ctx *, int src_width, int src_height, int dst_width, int dst_height, int filter, ks265_scale_plan **plan);
+int ks265_scale_plan_destroy(ks265_ctx *, ks265_scale_plan *plan);
+int ks265_input_scale_validate(ks265_ctx *, const ks265_scale_plan *plan, const ks265_in_desc *src);
+int ks265_input_scale(ks265_ctx *, const ks265_scale_plan *plan, const ks265_in_desc *src, uint8_t *scratch_i420, uint8_t *dev_i420);
 /* The way back (output_convert.hip): a packed I420 picture in device memory (Y width x height, then U and V width / 2 x height / 2, no padding; width and height even, no
  * alignment asked of the address) into the picture `dst` describes, by one kernel on the context's stream.  The descriptor keeps its meaning:
  *   KS265_IN_I420  three planes with their own pitches;   KS265_IN_NV12  Y, then interleaved UV (height / 2 rows);

@@ -20,7 +20,12 @@ the pictures back then.
 roi=True lets THIS handle take a map of quantiser offsets with every picture (`roi`, include/ks265_enc.h): encode(tensor, format, roi=MAP, roi_block=16) with MAP a 2-D int8 or
 float32 array of QP offsets (positive = coarser), one element per roi_block x roi_block luma samples (1, 2, 4 .. 64), ceil(H / roi_block) x ceil(W / roi_block) elements, unit
 column stride - a CUDA tensor, read in the order of torch's current stream like the picture (it may be overwritten on that stream as soon as encode() returns), or a NumPy array
-in host memory (read before encode() returns)."""
+in host memory (read before encode() returns).
+
+scale="bicubic"|"bilinear" (with scale_from=(W, H), the largest source; default 8 times the encoder's size, at most 8192 x 8192) lets THIS handle take tensors of other sizes
+(`ks265_enc_enable_device_scale`, include/ks265_enc.h): encode() scales them to the encoder's size on the GPU, in the order of torch's current stream like any other picture -
+Catmull-Rom or a triangle, both widened when shrinking, exact integer arithmetic (tests/yuv_scale_ref.py is the specification).  Source width a multiple of 8, height even, each
+ratio at most 8 either way.  One tensor may feed a ladder of handles of different sizes in one loop; a roi= map refers to the encoder's size."""
 from __future__ import annotations
 
 import ctypes as C
@@ -57,6 +62,7 @@ class Roi(C.Structure):
 
 
 ROI_INT8, ROI_FLOAT32 = 0, 1
+_SCALE_FILTERS = {"bilinear": 0, "bicubic": 1}                 # KS_SCALE_TRIANGLE, KS_SCALE_CATMULL_ROM
 
 
 class Quality(C.Structure):
@@ -88,6 +94,8 @@ def library() -> C.CDLL:
         _lib.ks265_enc_device_recon_pending.argtypes = [C.c_void_p]
         _lib.ks265_enc_get_device_recon.argtypes = [C.c_void_p, C.POINTER(DevPicture), C.c_void_p]
         _lib.ks265_enc_set_next_roi.argtypes = [C.c_void_p, C.POINTER(Roi)]
+        _lib.ks265_enc_enable_device_scale.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        _lib.ks265_enc_encode_device_frame_scaled.argtypes = [C.c_void_p, C.POINTER(C.POINTER(Nal)), C.POINTER(C.c_int), C.POINTER(DevPicture), C.c_int, C.c_int, C.c_int, C.c_void_p]
     return _lib
 
 
@@ -175,6 +183,12 @@ class Encoder:
         self._roi = bool(params.pop("roi", False))              # `roi` (ks265_enc.h) for this handle alone, like `hash`
         if self._roi and self.lib.ks265_enc_set_default(b"roi", C.c_int(1)) != 0:
             raise ValueError("parameter roi: the library has no roi switch")
+        self._scale = params.pop("scale", None)                 # ks265_enc_enable_device_scale for this handle: the filter encode() scales tensors of other sizes with
+        scale_from = params.pop("scale_from", None)
+        if self._scale is not None and self._scale not in _SCALE_FILTERS:
+            raise ValueError(f"scale: one of {sorted(_SCALE_FILTERS)}")
+        if scale_from is not None and self._scale is None:
+            raise ValueError("scale_from: needs scale=")
         for k, v in (("wdt", width), ("hgt", height), *params.items()):
             rc = self.lib.QY265ConfigParse(self._cfg, str(k).replace("_", "-").encode(), str(v).encode())   # keyword form of the names with a dash: sao_ref=2 -> "sao-ref"
             if rc != 0:
@@ -194,6 +208,13 @@ class Encoder:
             self.lib.QY265EncoderClose(self.h)
             self.h = None
             raise EncoderError("ks265_enc_enable_device_input", rc)
+        if self._scale is not None:
+            mw, mh = scale_from if scale_from is not None else (min(8192, 8 * width), min(8192, 8 * height))
+            rc = self.lib.ks265_enc_enable_device_scale(self.h, int(mw), int(mh))
+            if rc != QY_OK:
+                self.lib.QY265EncoderClose(self.h)
+                self.h = None
+                raise EncoderError(f"ks265_enc_enable_device_scale({mw}, {mh})", rc)
         self._nal, self._nn, self._out, self._pts = C.POINTER(Nal)(), C.c_int(0), Picture(), 0
         self._flushed, self._held, self._next_display = [], {}, 0  # recon(): what flush() fetched call by call; order="display": early pictures by poc, the next index to return
         if self._recon is not None:                             # refused at open (a device library without the way back, lanes on several GPUs, KS265_GRAPH)?  Nothing is pending: QY_FAIL if on
@@ -219,18 +240,23 @@ class Encoder:
                 raise ValueError(f"roi {tuple(roi.shape)}: a {self.width}x{self.height} picture in blocks of {b} is {((self.height + b - 1) // b, (self.width + b - 1) // b)}")
         shape = (tensor.shape[0], tensor.shape[1]) if format not in ("i420", "nv12", "rgb_planar") else (tensor.shape[1], tensor.shape[2]) if format == "rgb_planar" \
             else (tensor.shape[0] * 2 // 3, tensor.shape[1])
-        if shape != (self.height, self.width):
+        if shape != (self.height, self.width) and self._scale is None:
             raise ValueError(f"picture {shape[1]}x{shape[0]}, encoder {self.width}x{self.height}")
         if roi is not None:                                     # (behind every check of the picture: a refused picture leaves nothing pending)
             rc = self.lib.ks265_enc_set_next_roi(self.h, C.byref(rd))
             if rc != QY_OK:
                 raise EncoderError("ks265_enc_set_next_roi", rc)
         pic.pts, self._pts = self._pts, self._pts + 1
-        rc = self.lib.ks265_enc_encode_device_frame(self.h, C.byref(self._nal), C.byref(self._nn), C.byref(pic), C.addressof(self._out))
+        scaled = shape != (self.height, self.width)
+        if scaled:                                              # scale=: scaled into the input slot on the GPU (a refused size: QY_NOTSUPPORTED, nothing enqueued)
+            rc = self.lib.ks265_enc_encode_device_frame_scaled(self.h, C.byref(self._nal), C.byref(self._nn), C.byref(pic), shape[1], shape[0], _SCALE_FILTERS[self._scale],
+                                                               C.addressof(self._out))
+        else:
+            rc = self.lib.ks265_enc_encode_device_frame(self.h, C.byref(self._nal), C.byref(self._nn), C.byref(pic), C.addressof(self._out))
         if rc != QY_OK:
             if roi is not None:
                 self.lib.ks265_enc_set_next_roi(self.h, None)       # a picture refused before it was handed in has not taken its map: withdrawn
-            raise EncoderError("ks265_enc_encode_device_frame", rc)
+            raise EncoderError(f"ks265_enc_encode_device_frame_scaled: picture {shape[1]}x{shape[0]}, encoder {self.width}x{self.height}" if scaled else "ks265_enc_encode_device_frame", rc)
         return self._take()
 
     def flush(self) -> bytes:

@@ -17,6 +17,7 @@
 #include "ks265_gop.h"
 #include "ks265_recon.h"
 #include "ks265_roi.h"
+#include "ks265_scale.h"
 #include <dirent.h>
 #include <fcntl.h>
 #include <math.h>
@@ -53,6 +54,10 @@
 #pragma weak ks265_roi_ctu_map
 /* `gpb` switches the skip pass off for its anchors the same way: a device library without the setter - the stand-in has no skip pass - is not asked */
 #pragma weak ks265_frame_set_picture_skip
+/* device input of another size (ks265_enc_enable_device_scale): the scaler's entries; without them the switch is refused with one log line */
+#pragma weak ks265_scale_plan_create
+#pragma weak ks265_scale_plan_destroy
+#pragma weak ks265_input_scale
 
 const char strLibQy265Version[] = "ks265enc 0.2 (MI355X pixel path + host CABAC; API of libqycodec V2.6.1.3)";
 
@@ -475,6 +480,12 @@ typedef struct Enc {
     int rdoq_on; int32_t *rq_hist; char rq_hist_kind[RQ_HIST]; int64_t rq_lam[104]; long rq_gop_seq;   /* rq_gop_seq: the submission number of the current GOP's key picture - tables never cross a key picture (closed GOPs: the stream does not depend on how GOPs are dealt to lanes) */
     double rc_sum_norm, rc_hist[RC_HIST]; long rc_acc_seq, rc_sub; int rc_acc_idx; int rc_qp_delta;
     double rc_sum_budget, rc_bhist[RC_HIST], rc_sum_real, rc_rhist[RC_HIST];   /* the budget and the bits really produced, summed picture by picture like rc_sum_norm */
+    /* ks265_enc_enable_device_scale: device pictures of other sizes are scaled into the slot's twin (ks265_input_scale on ctx_up, where ks265_input_convert stands).  sc_scratch: the
+     * RGB sources' I420 picture at the largest source size; sc_plan: the lane's plans by (source size, filter), the least recently used one replaced (a picture's plan reaches
+     * lane_put as an argument, `sc`).  Behind every other field: the layout in front of them is the one the lanes have always had */
+#define SCALE_PLANS 4
+    int sc_on, sc_max_w, sc_max_h; uint8_t *sc_scratch; long sc_tick;
+    struct ScalePlan { ks265_scale_plan *plan; int sw, sh, filter; long used; } sc_plan[SCALE_PLANS];
 } Enc;
 
 static ks265_ctx *main_ctx(const Enc *e) { return e->path[PATH_MAIN].ctx; }
@@ -2118,6 +2129,14 @@ static void close_devrecon(Enc *e)                                     /* a conv
     recon_list_free(&e->taken);
 }
 
+/* ks265_enc_enable_device_scale: the RGB sources' scratch picture, nothing else (the plans come with the sizes, on the caller's thread: lane_scale_plan) */
+static int open_scale(Enc *e) { return ks265_dev_malloc(main_ctx(e), (void **)&e->sc_scratch, (size_t)e->sc_max_w * e->sc_max_h * 3 / 2); }
+static void close_scale(Enc *e)
+{
+    for (int i = 0; i < SCALE_PLANS; ++i) if (e->sc_plan[i].plan) { (void)ks265_scale_plan_destroy(main_ctx(e), e->sc_plan[i].plan); e->sc_plan[i].plan = NULL; }
+    ks265_dev_free(main_ctx(e), e->sc_scratch); e->sc_scratch = NULL;
+}
+
 static int open_threads(Enc *e)
 {
     for (int i = 0; i < e->nthreads; ++i) { e->warg[i].e = e; e->warg[i].idx = i; if (pthread_create(&e->th[i], NULL, worker, &e->warg[i])) break; ++e->nth; }
@@ -2148,6 +2167,7 @@ static void lane_close(Enc *e, int report)
         if (report && e->in_disp) logf_(1, e->log_level, "ks265enc: caller's back-pressure wait %.3f ms per picture\n", e->la_t_bp / e->in_disp);
         if (report) run_summary(e, e->st.frames, e->st.bytes, e->st.sse, e->q_hi, e->q_lo);
         close_devrecon(e);
+        if (e->sc_on) close_scale(e);
         close_jobs(e); close_inputs(e); close_dpb(e); close_key_path(e); close_anchor_path(e); close_pipeline(e);
         for (int i = 0; i < e->ngraph; ++i) ks265_graph_destroy(main_ctx(e), e->graph[i].exec);
         close_quality(e);
@@ -2455,7 +2475,7 @@ static void dev_desc(const Enc *e, const ks265_dev_picture *p, ks265_in_desc *d)
 
 /* one picture into the lane - a host picture (yuv: copied to a pinned slot or uploaded from where it lies) or a device picture (dp, validated by the caller: converted into the
  * slot's twin on ctx_up in the order of the caller's stream) - and on to the scheduler thread.  key: it starts a closed GOP regardless of the period */
-static int lane_put(Enc *e, const QY265YUV *yuv, const ks265_dev_picture *dp, const ks265_roi *roi, long long pts, int key)
+static int lane_put(Enc *e, const QY265YUV *yuv, const ks265_dev_picture *dp, const struct ScalePlan *sc, const ks265_roi *roi, long long pts, int key)
 {
     if (!dp && (!yuv || !yuv->pData[0] || !yuv->pData[1] || !yuv->pData[2])) return QY_POINTER;
     if (!dp && (yuv->iWidth != e->W || yuv->iHeight != e->H)) return QY_NOTSUPPORTED;
@@ -2497,8 +2517,9 @@ static int lane_put(Enc *e, const QY265YUV *yuv, const ks265_dev_picture *dp, co
     if (dp) {                                                          /* the caller's stream -> ctx_up: conversion into the twin -> ev_up -> the caller's stream waits for it */
         ks265_in_desc d;
         dev_desc(e, dp, &d);
+        if (sc) { d.width = sc->sw; d.height = sc->sh; }                /* a picture of another size: scaled into the twin, in the same place between the same two events */
         int ru = ks265_wait_external(e->ctx_up, dp->stream);
-        if (!ru) ru = ks265_input_convert(e->ctx_up, &d, slot->dev);
+        if (!ru) ru = sc ? ks265_input_scale(e->ctx_up, sc->plan, &d, e->sc_scratch, slot->dev) : ks265_input_convert(e->ctx_up, &d, slot->dev);
         if (!ru) ru = ks265_event_record(e->ctx_up, slot->ev_up);
         if (!ru) ru = ks265_external_wait_event(e->ctx_up, dp->stream, slot->ev_up);
         if (ru) { pthread_mutex_lock(&e->mu); slot->used = 0; e->sched_err = hip_rc(ru); pthread_mutex_unlock(&e->mu); return hip_rc(ru); }
@@ -2577,12 +2598,12 @@ static int lane_flush_begin(Enc *e, int wait)
     return all;
 }
 
-static int lane_encode_frame(Enc *e, QY265Nal **pNals, int *iNalCount, QY265Picture *in, const ks265_dev_picture *dp, const ks265_roi *roi, QY265Picture *out)
+static int lane_encode_frame(Enc *e, QY265Nal **pNals, int *iNalCount, QY265Picture *in, const ks265_dev_picture *dp, const struct ScalePlan *sc, const ks265_roi *roi, QY265Picture *out)
 {
     *pNals = e->nals; *iNalCount = 0;
     int r = QY_OK;
     if (in || dp) {
-        r = in ? lane_put(e, in->yuv, NULL, roi, in->pts, 0) : lane_put(e, NULL, dp, roi, dp->pts, 0);
+        r = in ? lane_put(e, in->yuv, NULL, NULL, roi, in->pts, 0) : lane_put(e, NULL, dp, sc, roi, dp->pts, 0);
         if (r) return r;
         /* finished pictures (copied to the output buffer); when the ring of in-flight pictures is nearly full, wait for the oldest ones -
          * only as many as needed, the writers keep running */
@@ -2999,13 +3020,16 @@ int QY265EncoderDelayedFrames(void *h)
 }
 
 /* one call of the API: a host picture (in), a device picture (dp) or, neither, the flush */
-static int top_encode(Top *t, QY265Nal **pNals, int *iNalCount, QY265Picture *in, const ks265_dev_picture *dp, QY265Picture *out)
+/* the lane the NEXT picture goes to: a new GOP starts on the next lane (top_encode, ks265_enc_acquire_input, ks265_enc_encode_device_frame_scaled) */
+static int top_next_lane(const Top *t) { return t->nlanes == 1 ? 0 : (t->chunk_left <= 0 || t->key_request) ? (t->cur_lane + 1) % t->nlanes : t->cur_lane; }
+
+static int top_encode(Top *t, QY265Nal **pNals, int *iNalCount, QY265Picture *in, const ks265_dev_picture *dp, const struct ScalePlan *sc, QY265Picture *out)
 {
     recon_release(t);                                                 /* `devrecon`: the previous call's reconstructions are the pool's again */
     const ks265_roi *roi = (in || dp) && t->roi_set ? &t->roi : NULL;  /* `roi`: the pending map goes with this picture - whatever becomes of the call, nothing stays pending (a flush: it stays) */
     if (in || dp) t->roi_set = 0;
     if (t->nlanes == 1) {
-        const int r1 = lane_encode_frame(t->lane[0], pNals, iNalCount, in, dp, roi, out);
+        const int r1 = lane_encode_frame(t->lane[0], pNals, iNalCount, in, dp, sc, roi, out);
         const int rr = t->lane[0]->devrecon ? recon_taken(t, t->lane[0], NULL, &t->handed) : QY_OK;
         return r1 ? r1 : rr;
     }
@@ -3014,11 +3038,12 @@ static int top_encode(Top *t, QY265Nal **pNals, int *iNalCount, QY265Picture *in
     int r = QY_OK;
     if (in || dp) {
         int first = 0;
+        const int next = top_next_lane(t);
         if (t->chunk_left <= 0 || t->key_request) {                     /* a new GOP: the next lane */
             if (t->ch_n) top_close_chunk(t, t->chunk_left > 0);
             while (t->ch_n == MAX_CHUNKS && !r) r = top_collect(t, 1, out);
             if (r) return r;
-            t->cur_lane = (t->cur_lane + 1) % t->nlanes;
+            t->cur_lane = next;
             Chunk *c = &t->ch[(t->ch_head + t->ch_n) % MAX_CHUNKS];
             memset(c, 0, sizeof *c);
             c->lane = t->cur_lane; c->base = t->n_in; c->disp0 = t->lane[t->cur_lane]->in_disp;
@@ -3033,7 +3058,7 @@ static int top_encode(Top *t, QY265Nal **pNals, int *iNalCount, QY265Picture *in
             if (r) return r;
         }
         t->output_ms += now_ms() - t0;
-        r = in ? lane_put(e, in->yuv, NULL, roi, in->pts, first) : lane_put(e, NULL, dp, roi, dp->pts, first);
+        r = in ? lane_put(e, in->yuv, NULL, NULL, roi, in->pts, first) : lane_put(e, NULL, dp, sc, roi, dp->pts, first);
         if (r) return r;
         ++t->ch[(t->ch_head + t->ch_n - 1) % MAX_CHUNKS].count; ++t->n_in; --t->chunk_left;
         const double t1 = now_ms();
@@ -3068,7 +3093,7 @@ int QY265EncoderEncodeFrame(void *h, QY265Nal **pNals, int *iNalCount, QY265Pict
     (void)bForceLogo;
     Top *t = (Top *)h;
     if (!t || !pNals || !iNalCount) return QY_POINTER;
-    return top_encode(t, pNals, iNalCount, in, NULL, out);
+    return top_encode(t, pNals, iNalCount, in, NULL, NULL, out);
 }
 
 int ks265_enc_get_stats(void *h, ks265_enc_stats *out)
@@ -3119,9 +3144,7 @@ int ks265_enc_acquire_input(void *h, QY265YUV *yuv)
 {
     Top *t = (Top *)h;
     if (!t || !yuv) return QY_POINTER;
-    /* the lane the NEXT picture goes to (QY265EncoderEncodeFrame: a new GOP starts on the next lane) */
-    const int lane = t->nlanes == 1 ? 0 : (t->chunk_left <= 0 || t->key_request) ? (t->cur_lane + 1) % t->nlanes : t->cur_lane;
-    return lane_acquire(t->lane[lane], yuv);
+    return lane_acquire(t->lane[top_next_lane(t)], yuv);
 }
 
 /* every input slot of the lane gets a device twin (and the event behind its filling) if it has none yet, and the lane a stream for filling them: the lookahead's when there is one
@@ -3169,7 +3192,72 @@ int ks265_enc_encode_device_frame(void *h, QY265Nal **pNals, int *iNalCount, con
     const int rv = ks265_input_validate(main_ctx(e0), &d);
     e0->st.in_copy_ms += now_ms() - t0;
     if (rv) return hip_rc(rv);
-    return top_encode(t, pNals, iNalCount, NULL, pic, out);
+    return top_encode(t, pNals, iNalCount, NULL, pic, NULL, out);
+}
+
+/* the lane's plan for (source size, filter) into *out: the cached one, or a new one in the place of the least recently used - created here, on the caller's thread; the one that
+ * goes may still be read by a picture in flight on ctx_up, which is waited for first.  More than SCALE_PLANS sizes in turn pay that wait and the tables with every picture */
+static int lane_scale_plan(Enc *e, int sw, int sh, int filter, const struct ScalePlan **out)
+{
+    int at = -1;
+    for (int i = 0; i < SCALE_PLANS; ++i)
+        if (e->sc_plan[i].plan && e->sc_plan[i].sw == sw && e->sc_plan[i].sh == sh && e->sc_plan[i].filter == filter) { e->sc_plan[i].used = ++e->sc_tick; *out = &e->sc_plan[i]; return KS265_OK; }
+    for (int i = 0; i < SCALE_PLANS && at < 0; ++i) if (!e->sc_plan[i].plan) at = i;
+    for (int i = 0; i < SCALE_PLANS && (at < 0 || e->sc_plan[at].plan); ++i) if (at < 0 || e->sc_plan[i].used < e->sc_plan[at].used) at = i;
+    ks265_scale_plan *np = NULL;
+    const int r = ks265_scale_plan_create(main_ctx(e), sw, sh, e->W, e->H, filter, &np);
+    if (r) return r;
+    if (e->sc_plan[at].plan) { (void)ks265_synchronize(e->ctx_up); (void)ks265_scale_plan_destroy(main_ctx(e), e->sc_plan[at].plan); }
+    e->sc_plan[at].plan = np; e->sc_plan[at].sw = sw; e->sc_plan[at].sh = sh; e->sc_plan[at].filter = filter; e->sc_plan[at].used = ++e->sc_tick;
+    *out = &e->sc_plan[at];
+    return KS265_OK;
+}
+
+int ks265_enc_enable_device_scale(void *h, int max_src_width, int max_src_height)
+{
+    Top *t = (Top *)h;
+    if (!t) return QY_POINTER;
+    Enc *e0 = t->lane[0];
+    if (!e0->dev_in_on) return QY_NOTSUPPORTED;
+    for (int i = 0; i < t->nlanes; ++i) if (t->lane[i]->in_disp) return QY_NOTSUPPORTED;   /* after the first picture */
+    if (!ks265_scale_plan_create || !ks265_scale_plan_destroy || !ks265_input_scale) {
+        logf_(2, e0->log_level, "ks265enc: input scaling is unavailable: the device library has no ks265_input_scale\n");
+        return QY_NOTSUPPORTED;
+    }
+    if (max_src_width <= 0 || max_src_height <= 0 || (max_src_width & 7) || (max_src_height & 1) || max_src_width > KS_SCALE_MAX_DIM || max_src_height > KS_SCALE_MAX_DIM
+        || max_src_width > KS_SCALE_MAX_RATIO * e0->W || max_src_height > KS_SCALE_MAX_RATIO * e0->H || (e0->W & 7) || (e0->H & 7)) return QY_NOTSUPPORTED;
+    if (e0->sc_on) return e0->sc_max_w == max_src_width && e0->sc_max_h == max_src_height ? QY_OK : QY_NOTSUPPORTED;
+    for (int i = 0; i < t->nlanes; ++i) {
+        Enc *e = t->lane[i];
+        e->sc_max_w = max_src_width; e->sc_max_h = max_src_height;
+        const int r = open_scale(e);
+        if (r) { for (int k = 0; k < i; ++k) { close_scale(t->lane[k]); t->lane[k]->sc_on = 0; } return hip_rc(r); }   /* lane i itself got nothing */
+        e->sc_on = 1;
+    }
+    return QY_OK;
+}
+
+int ks265_enc_encode_device_frame_scaled(void *h, QY265Nal **pNals, int *iNalCount, const ks265_dev_picture *pic, int src_width, int src_height, int filter, QY265Picture *out)
+{
+    Top *t = (Top *)h;
+    if (!t || !pNals || !iNalCount || !pic) return QY_POINTER;
+    Enc *e0 = t->lane[0];
+    if (src_width == e0->W && src_height == e0->H) return ks265_enc_encode_device_frame(h, pNals, iNalCount, pic, out);
+    *iNalCount = 0;
+    if (!e0->sc_on || pic->device != e0->dev_id) return QY_NOTSUPPORTED;
+    if (!ks265_scale_size_ok(src_width, src_height, e0->W, e0->H) || src_width > e0->sc_max_w || src_height > e0->sc_max_h) return QY_NOTSUPPORTED;
+    if (filter != KS_SCALE_TRIANGLE && filter != KS_SCALE_CATMULL_ROM) return QY_NOTSUPPORTED;
+    /* the whole source is checked, and its plan is there, before anything is enqueued or counted: a refused picture leaves the handle as it was (a pending ROI map too) */
+    const double t0 = now_ms();
+    ks265_in_desc d;
+    dev_desc(e0, pic, &d);
+    d.width = src_width; d.height = src_height;
+    int rv = ks265_input_validate(main_ctx(e0), &d);
+    const struct ScalePlan *sc = NULL;                                  /* kept by the lane this picture goes to; any context of the device may run it */
+    if (!rv) rv = lane_scale_plan(t->lane[top_next_lane(t)], src_width, src_height, filter, &sc);
+    e0->st.in_copy_ms += now_ms() - t0;
+    if (rv) return hip_rc(rv);
+    return top_encode(t, pNals, iNalCount, NULL, pic, sc, out);
 }
 
 int ks265_enc_set_next_roi(void *h, const ks265_roi *roi)

@@ -76,6 +76,7 @@ EXPORTS = [
     "ks265_ssim_picture", "ks265_ssim_picture_on",
     "ks265_picture_hash", "ks265_picture_hash_on",
     "ks265_roi_validate", "ks265_roi_reduce", "ks265_roi_ctu_map",
+    "ks265_scale_plan_create", "ks265_scale_plan_destroy", "ks265_input_scale_validate", "ks265_input_scale",
 ]
 
 
@@ -365,6 +366,20 @@ class KsContext:
         self._chk(self.lib.ks265_roi_ctu_map(self.h, _p(records) if records is not None else None, _p(base) if base is not None else None, C.c_int(nx), C.c_int(ny),
                                              C.c_int(blocks_per_ctu_side), C.c_int(ctu_cols), C.c_int(ctu_rows), C.c_int(base_qp), C.c_int(lo), C.c_int(hi), _p(out)))
         return self.host(out, np.int8)
+
+    # ---- device input of another size (include/ks265_hip.h ks265_scale_plan_*, ks265_input_scale)
+    def scale_plan(self, src_w: int, src_h: int, dst_w: int, dst_h: int, filter: int = 1) -> C.c_void_p:
+        """a plan (the tables in device memory) for src -> dst, filter 0 triangle / 1 Catmull-Rom; scale_plan_destroy frees it"""
+        plan = C.c_void_p()
+        self._chk(self.lib.ks265_scale_plan_create(self.h, C.c_int(src_w), C.c_int(src_h), C.c_int(dst_w), C.c_int(dst_h), C.c_int(filter), C.byref(plan)))
+        return plan
+
+    def scale_plan_destroy(self, plan: C.c_void_p) -> None:
+        self._chk(self.lib.ks265_scale_plan_destroy(self.h, plan))
+
+    def input_scale(self, plan: C.c_void_p, desc, dst, scratch=None) -> None:
+        """desc: a ks265_in_desc (ctypes structure) of the source at the plan's source size; dst: uint8 device tensor of dst_w * dst_h * 3 / 2 bytes; scratch: for RGB sources"""
+        self._chk(self.lib.ks265_input_scale(self.h, plan, C.byref(desc), _p(scratch), _p(dst)))
 
     def intra_pred(self, ref, dst, blks: np.ndarray):
         """g_IntraPredFunction: predict every described block from dev `ref` into dev `dst` (in place)"""
