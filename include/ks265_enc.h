@@ -163,16 +163,23 @@ int ks265_enc_acquire_input(void *pEncoder, QY265YUV *yuv);
  *   KS265_IN_RGB   plane[0..2] = the R, G, B samples of pixel (0, 0), pixel_step bytes apart horizontally, pitch[0] bytes between rows: RGB24 (step 3), RGBA (step 4,
  *                  base + 0 / 1 / 2), BGRA (step 4, base + 2 / 1 / 0), planar (step 1); converted with the BT.709 (default) or BT.601 matrix, limited (default) or full range,
  *                  in exact integer arithmetic (the stream signals no colour description: the application knows what it asked for).
+ *   KS265_IN_RGB_F16 / _BF16 / _F32   the same layouts with float16, bfloat16 or float32 samples, [0, 1] the full 8-bit range (a model's or renderer's output as it lies):
+ *                  plane, pixel_step and pitch[0] still in BYTES and multiples of the element size es (2, 2, 4), es <= pixel_step <= 64 (else QY_NOTSUPPORTED) - planar
+ *                  (step es), HWC (3 es), four-element pixels (4 es).  One kernel reads the samples once; a float32 picture u8 / 255 codes as the picture u8 does, the
+ *                  16-bit types within one code of it (tests/yuv_float_ref.py is the specification).
  * CONTRACT: the encoder reads the planes in the order of `stream` (a hipStream_t; NULL = the null stream): its work waits for everything the caller enqueued there before the
  * call, and everything the caller enqueues there after the call waits until the encoder has read the picture.  So the caller may overwrite the buffer with further work on that
  * same stream as soon as the call returns - no host synchronisation.  Work on OTHER streams must order itself against `stream`.  The call does not block on the GPU. */
 #define KS265_IN_I420 0
 #define KS265_IN_NV12 1
 #define KS265_IN_RGB 2
+#define KS265_IN_RGB_F16 16
+#define KS265_IN_RGB_BF16 17
+#define KS265_IN_RGB_F32 18
 #define KS265_MATRIX_BT709 0
 #define KS265_MATRIX_BT601 1
 typedef struct ks265_dev_picture {
-    int format;                                /* KS265_IN_I420 / _NV12 / _RGB */
+    int format;                                /* KS265_IN_I420 / _NV12 / _RGB / _RGB_F16 / _RGB_BF16 / _RGB_F32 */
     int device;                                /* HIP ordinal the planes live on */
     const void *plane[3]; int pitch[3];        /* bytes; RGB: channel pointers R, G, B and pitch[0] */
     int pixel_step;                            /* RGB only */
@@ -212,6 +219,9 @@ int ks265_enc_encode_device_frame_scaled(void *pEncoder, QY265Nal **pNals, int *
  *                                   pointers name three bytes of one four-byte pixel that begins at the lowest of them (RGBA, BGRA), and its fourth byte is written as 255.
  *                                   YCbCr -> RGB in exact integer arithmetic, chroma interpolated bilinearly at HEVC's default siting (tests/yuv_output_ref.py).  Nothing
  *                                   outside [row start, row start + row bytes) of a row is written: the padding behind a pitch stays.
+ *                                   KS265_IN_RGB_F16 / _BF16 / _F32: the same picture as float samples - the float32 of byte / 255, correctly rounded (the 16-bit
+ *                                   types rounded once more, to nearest even), so that sample x 255 is the uint8 reconstruction; pixel_step es (planar), 3 es or 4 es
+ *                                   with es the element size, everything in bytes and a multiple of es; the fourth element of a four-element pixel is written as 1.0.
  *                                   QY_FAIL: nothing pending.  QY_POINTER: a plane whose whole extent does not lie inside one device allocation of the handle's GPU (host and
  *                                   managed memory, short buffers, pitches below the row) - the picture stays pending and nothing is enqueued.  QY_NOTSUPPORTED: the switch is
  *                                   off, dst->device is not the handle's GPU, or a format / pixel step outside the list.

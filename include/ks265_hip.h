@@ -96,6 +96,12 @@ int ks265_external_wait_event(ks265_ctx *, void *hip_stream, void *ev);
  *   KS265_IN_RGB   plane[0..2] = the R, G and B samples of pixel (0, 0); pixel_step = bytes between horizontally adjacent samples, pitch[0] = bytes between rows, for all three:
  *                  packed RGB24 (step 3), RGBA (step 4, base + 0 / 1 / 2), BGRA (step 4, base + 2 / 1 / 0), planar CHW (step 1, three plane pointers).  Exact integer
  *                  arithmetic, BT.709 or BT.601, limited or full range, chroma by a (1, 2, 1) x (1, 1) filter at HEVC's default siting (tests/yuv_convert_ref.py is the specification)
+ *   KS265_IN_RGB_F16 / _BF16 / _F32   RGB as float16, bfloat16 or float32 samples, [0, 1] the full 8-bit range.  The descriptor means what it means for KS265_IN_RGB, in
+ *                  BYTES: plane[0..2] address the R, G, B element of pixel (0, 0), pixel_step lies between horizontally adjacent samples, pitch[0] between rows.  With the
+ *                  element size es (2, 2, 4): every channel pointer, pixel_step and pitch[0] a multiple of es and es <= pixel_step <= 64 (else KS265_NOTSUPPORTED); a row's
+ *                  bytes are (width - 1) pixel_step + es per channel.  Planar CHW (step es), HWC (3 es), four-element pixels (4 es) in any channel order.  A sample v counts
+ *                  q = rint(clamp(v * 65280, 0, 65280)) (one float32 multiply, ties to even, NaN = 0) in 1 / 256 of a code; matrix, range and chroma filter as for
+ *                  KS265_IN_RGB, in 64-bit integers (tests/yuv_float_ref.py is the specification): a float32 picture u8 / 255 gives byte for byte the picture of u8
  * width a multiple of 8, height even.  ks265_input_validate enqueues nothing: KS265_POINTER unless the whole extent of every plane - [p, p + pitch (rows - 1) + row bytes) -
  * lies inside ONE device allocation on the context's device (host, managed and other devices' memory, short buffers, pitches below the row are refused); KS265_NOTSUPPORTED for a
  * format / size / matrix outside the list.  ks265_input_convert validates the source and the destination (width x height x 3 / 2 bytes of device memory, 16-byte aligned) the
@@ -103,12 +109,15 @@ int ks265_external_wait_event(ks265_ctx *, void *hip_stream, void *ev);
 #define KS265_IN_I420 0
 #define KS265_IN_NV12 1
 #define KS265_IN_RGB 2
+#define KS265_IN_RGB_F16 16
+#define KS265_IN_RGB_BF16 17
+#define KS265_IN_RGB_F32 18
 #define KS265_MATRIX_BT709 0
 #define KS265_MATRIX_BT601 1
 typedef struct {
     int32_t format, width, height;
     const void *plane[3]; int32_t pitch[3];
-    int32_t pixel_step, matrix, full_range;    /* KS265_IN_RGB only */
+    int32_t pixel_step, matrix, full_range;    /* the RGB formats only */
 } ks265_in_desc;
 int ks265_input_validate(ks265_ctx *, const ks265_in_desc *src);
 int ks265_input_convert(ks265_ctx *, const ks265_in_desc *src, uint8_t *dev_i420);
@@ -141,6 +150,10 @@ int ks265_input_scale(ks265_ctx *, const ks265_scale_plan *plan, const ks265_in_
  *                  fourth byte as 255 - a pixel is one word store where pixel and pitch are multiples of 4.  With steps 1 and 3 it writes nothing but the channels.
  *                  YCbCr -> RGB in exact integer arithmetic, BT.709 or BT.601, limited or full range, chroma brought to the luma grid bilinearly at HEVC's default siting
  *                  (tests/yuv_output_ref.py is the specification).
+ *   KS265_IN_RGB_F16 / _BF16 / _F32   the same picture as float samples: with k the byte KS265_IN_RGB writes, the correctly rounded float32 of k / 255, for the 16-bit types
+ *                  rounded once more to nearest even (tests/yuv_float_ref.py) - sample x 255 is the uint8 reconstruction.  Pointers, pixel_step and pitch[0] in bytes and
+ *                  multiples of the element size es; pixel_step es (planar), 3 es or 4 es; with 4 es the three pointers name three different elements of one four-element
+ *                  pixel that begins at the lowest of them, and its fourth element is written as 1.0.
  * No byte outside [row start, row start + row bytes) of any destination row is written: what lies behind a pitch stays.  ks265_output_validate enqueues nothing and judges
  * `dst` as ks265_input_validate judges a source, for WRITING: KS265_POINTER unless every plane's whole extent lies inside one device allocation on the context's device,
  * KS265_NOTSUPPORTED for a format / size / step / matrix outside the list.  ks265_output_convert validates destination and source the same way before it launches anything. */

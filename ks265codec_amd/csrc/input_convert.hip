@@ -2,7 +2,8 @@
 // an I420 repack with arbitrary pitches, an NV12 deinterleave, and RGB (any pixel step: RGB24, RGBA, BGRA, planar) -> YCbCr in exact integer arithmetic
 // (tests/yuv_convert_ref.py is the specification).  Memory-bound with no reuse beyond the neighbouring columns: one thread owns a run of luma columns across the
 // two rows of one chroma row, so every chroma sample is made from registers (no LDS round trip).  Wide loads where the address allows, a byte path for the rest;
-// the stores are always aligned (width a multiple of 8, the destination 16-byte aligned).
+// the stores are always aligned (width a multiple of 8, the destination 16-byte aligned).  RGB as float16 / bfloat16 / float32 in [0, 1] goes the same way in one pass over the
+// samples, with 64-bit sums (tests/yuv_float_ref.py).
 #include "ks265_internal.h"
 #include <cmath>
 
@@ -163,6 +164,138 @@ __global__ __launch_bounds__(256) void rgb_to_i420_kernel(CvtArgs a)
     *(uint32_t *)(dc + npx / 4) = v;
 }
 
+// ---- float RGB (KS265_IN_RGB_F16 / _BF16 / _F32; tests/yuv_float_ref.py is the specification): the shape of rgb_to_i420_kernel with samples q in 1 / 256 of a code (17 bits)
+// and 64-bit sums.  Everything below is in ELEMENTS of the type except the pointers, pitch and step (bytes).
+struct CvtFArgs {
+    const uint8_t *p[3];          // R, G, B of pixel (0, 0)
+    long long pitch;
+    int step, W, H;
+    int cy[3], cb[3], cr[3], oy;  // Q16 coefficients
+    const uint8_t *base;          // NPIX 3 / 4: where the run of pixel (0, 0) begins (NPIX 4: the lowest channel pointer rounded down to a pixel); the channels are its elements off[c]
+    int off[3];
+    const uint8_t *lo; long long ext;   // NPIX 3 / 4: the union of the channels' extents in row 0 is [lo, lo + ext) - a wide load must lie inside it
+    uint8_t *dst;
+};
+
+template <int FMT> struct FElem { typedef uint16_t type; };
+template <> struct FElem<KS265_IN_RGB_F32> { typedef uint32_t type; };
+
+// the bit pattern of a sample -> float32, exactly
+template <int FMT> __device__ inline float sample_f32(uint32_t bits)
+{
+    if constexpr (FMT == KS265_IN_RGB_F32) return __uint_as_float(bits);
+    else if constexpr (FMT == KS265_IN_RGB_BF16) return __uint_as_float(bits << 16);
+    else { const uint16_t b = (uint16_t)bits; _Float16 h; __builtin_memcpy(&h, &b, 2); return (float)h; }
+}
+// q of the specification: ONE IEEE multiply (this translation unit is built without fast-math), NaN and everything below zero 0 (both comparisons are false for NaN), ties to even.
+// A denormal times 65280 stays below 1 / 2 whether or not it is flushed.
+__device__ inline int sample_q(float v)
+{
+    float t = v * 65280.0f;
+    t = t > 0.0f ? t : 0.0f;
+    t = t < 65280.0f ? t : 65280.0f;
+    return (int)rintf(t);
+}
+// element k of a run of 16-byte loads
+template <int ES> __device__ inline uint32_t run_elem(const uint32_t *w, int k) { return ES == 4 ? w[k] : w[k >> 1] >> 16 * (k & 1) & 0xffff; }
+
+// one row of a float RGB picture: q of columns x0 - 1 (clamped to 0) .. x0 + 7 into c[0][0..8] (R), c[1] (G), c[2] (B).  NPIX 1: planar, 3 / 4: the three channels are elements of
+// one pixel of 3 / 4 elements, 0: anything else.  16-byte loads where the run's address is on 16 bytes and the run inside the row; else element by element.
+template <int FMT, int NPIX> __device__ inline void load_rgbf_row(const CvtFArgs &a, int y, int x0, int (&c)[3][9])
+{
+    typedef typename FElem<FMT>::type E;
+    constexpr int ES = (int)sizeof(E);
+    const long long ro = (long long)y * a.pitch;
+    const long long xl = (long long)(x0 > 0 ? x0 - 1 : 0) * a.step;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) c[ch][0] = sample_q(sample_f32<FMT>(*(const E *)(a.p[ch] + ro + xl)));
+    if constexpr (NPIX == 1) {
+        const uint8_t *q[3] = {a.p[0] + ro + (long long)x0 * ES, a.p[1] + ro + (long long)x0 * ES, a.p[2] + ro + (long long)x0 * ES};
+        if (!(((uintptr_t)q[0] | (uintptr_t)q[1] | (uintptr_t)q[2]) & 15)) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                uint32_t w[2 * ES];
+#pragma unroll
+                for (int k = 0; k < ES / 2; ++k) { const uint4 v = ((const uint4 *)q[ch])[k]; w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w; }
+#pragma unroll
+                for (int k = 0; k < 8; ++k) c[ch][k + 1] = sample_q(sample_f32<FMT>(run_elem<ES>(w, k)));
+            }
+            return;
+        }
+    } else if constexpr (NPIX >= 3) {
+        const uint8_t *q = a.base + ro + (long long)x0 * (NPIX * ES);
+        if (!((uintptr_t)q & 15) && q >= a.lo + ro && q + 8 * NPIX * ES <= a.lo + ro + a.ext) {
+            uint32_t w[2 * NPIX * ES];                                  // 8 pixels of NPIX elements: NPIX * ES / 2 loads of 16 bytes
+#pragma unroll
+            for (int k = 0; k < NPIX * ES / 2; ++k) { const uint4 v = ((const uint4 *)q)[k]; w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w; }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                uint32_t e[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) e[j] = j < NPIX ? run_elem<ES>(w, k * NPIX + j) : 0;
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) c[ch][k + 1] = sample_q(sample_f32<FMT>(a.off[ch] == 0 ? e[0] : a.off[ch] == 1 ? e[1] : a.off[ch] == 2 ? e[2] : e[3]));
+            }
+            return;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) c[ch][k + 1] = sample_q(sample_f32<FMT>(*(const E *)(a.p[ch] + ro + (long long)(x0 + k) * a.step)));
+    }
+}
+
+// clip255(v >> sh) of a 64-bit sum, in shr_clip255's form: the clamp in front of a logical shift
+__device__ inline uint32_t shr_clip255_64(long long v, int sh)
+{
+    const long long hi = (256LL << sh) - 1;
+    return (uint32_t)((unsigned long long)(v < 0 ? 0 : v > hi ? hi : v) >> sh);
+}
+
+// float RGB: 8 luma columns x the two rows of chroma row i -> 16 Y, 4 Cb, 4 Cr.  A row's q live only until its luma is stored and its (1, 2, 1) sums are taken.
+template <int FMT, int NPIX> __global__ __launch_bounds__(256) void rgbf_to_i420_kernel(CvtFArgs a)
+{
+    const int x0 = (blockIdx.x * 64 + threadIdx.x) * 8, i = blockIdx.y * 4 + threadIdx.y;
+    if (x0 >= a.W || 2 * i >= a.H) return;
+    const size_t W = (size_t)a.W, npx = W * a.H;
+    const long long yoff = ((long long)a.oy << 24) + (1 << 23);
+    int s[3][4] = {};
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+        int c[3][9];
+        load_rgbf_row<FMT, NPIX>(a, 2 * i + dy, x0, c);
+        uint32_t w[2] = {0, 0};
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            w[k >> 2] |= shr_clip255_64((long long)a.cy[0] * c[0][k + 1] + (long long)a.cy[1] * c[1][k + 1] + (long long)a.cy[2] * c[2][k + 1] + yoff, 24) << 8 * (k & 3);
+        *(uint2 *)(a.dst + (2 * i + dy) * W + x0) = make_uint2(w[0], w[1]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {                                  // chroma column x0 / 2 + k: entries 2k, 2k + 1, 2k + 2
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) s[ch][k] += c[ch][2 * k] + 2 * c[ch][2 * k + 1] + c[ch][2 * k + 2];
+        }
+    }
+    uint32_t u = 0, v = 0;
+    const long long rnd = (128LL << 27) + (1 << 26);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        u |= shr_clip255_64((long long)a.cb[0] * s[0][k] + (long long)a.cb[1] * s[1][k] + (long long)a.cb[2] * s[2][k] + rnd, 27) << 8 * k;
+        v |= shr_clip255_64((long long)a.cr[0] * s[0][k] + (long long)a.cr[1] * s[1][k] + (long long)a.cr[2] * s[2][k] + rnd, 27) << 8 * k;
+    }
+    uint8_t *dc = a.dst + npx + (size_t)i * (W / 2) + x0 / 2;
+    *(uint32_t *)dc = u;
+    *(uint32_t *)(dc + npx / 4) = v;
+}
+
+template <int FMT> void launch_rgbf(hipStream_t st, dim3 grid, dim3 blk, int npix, const CvtFArgs &a)
+{
+    if (npix == 1) hipLaunchKernelGGL((rgbf_to_i420_kernel<FMT, 1>), grid, blk, 0, st, a);
+    else if (npix == 3) hipLaunchKernelGGL((rgbf_to_i420_kernel<FMT, 3>), grid, blk, 0, st, a);
+    else if (npix == 4) hipLaunchKernelGGL((rgbf_to_i420_kernel<FMT, 4>), grid, blk, 0, st, a);
+    else hipLaunchKernelGGL((rgbf_to_i420_kernel<FMT, 0>), grid, blk, 0, st, a);
+}
+
 // [p, p + pitch (rows - 1) + row_bytes) inside one device allocation on the context's device
 int check_extent(ks265_ctx *c, const void *p, long long pitch, int rows, long long row_bytes, const char *what)
 {
@@ -183,14 +316,23 @@ int check_extent(ks265_ctx *c, const void *p, long long pitch, int rows, long lo
 int check_desc(ks265_ctx *c, const ks265_in_desc *d)
 {
     if (d->width <= 0 || d->height <= 0 || (d->width & 7) || (d->height & 1)) { c->last_error = "input: width a multiple of 8, height even"; return KS265_NOTSUPPORTED; }
-    if (d->format != KS265_IN_I420 && d->format != KS265_IN_NV12 && d->format != KS265_IN_RGB) { c->last_error = "input: unknown format"; return KS265_NOTSUPPORTED; }
+    const int es = ks265_rgb_elem_size(d->format);
+    if (d->format != KS265_IN_I420 && d->format != KS265_IN_NV12 && !es) { c->last_error = "input: unknown format"; return KS265_NOTSUPPORTED; }
     if (d->format == KS265_IN_RGB && (d->pixel_step < 1 || d->pixel_step > 16 || (d->matrix != KS265_MATRIX_BT709 && d->matrix != KS265_MATRIX_BT601))) {
         c->last_error = "input: RGB pixel step 1 .. 16, matrix BT.709 or BT.601"; return KS265_NOTSUPPORTED;
     }
+    if (es > 1) {
+        if (d->pixel_step < es || d->pixel_step > 64 || (d->matrix != KS265_MATRIX_BT709 && d->matrix != KS265_MATRIX_BT601)) {
+            c->last_error = "input: float RGB pixel step element size .. 64, matrix BT.709 or BT.601"; return KS265_NOTSUPPORTED;
+        }
+        if (((uintptr_t)d->plane[0] | (uintptr_t)d->plane[1] | (uintptr_t)d->plane[2] | (uintptr_t)d->pixel_step | (uintptr_t)d->pitch[0]) & (uintptr_t)(es - 1)) {
+            c->last_error = "input: float RGB pointers, pixel step and pitch are multiples of the element size"; return KS265_NOTSUPPORTED;
+        }
+    }
     const long long W = d->width, H = d->height;
     int r = KS265_OK;
-    if (d->format == KS265_IN_RGB) {
-        const long long rb = (W - 1) * d->pixel_step + 1;
+    if (es) {
+        const long long rb = (W - 1) * d->pixel_step + es;
         if (d->pitch[0] < W * d->pixel_step) { c->last_error = "input: RGB pitch below width x pixel step"; return KS265_POINTER; }
         for (int k = 0; k < 3 && !r; ++k) r = check_extent(c, d->plane[k], d->pitch[0], (int)H, rb, k == 0 ? "R" : k == 1 ? "G" : "B");
     } else {
@@ -245,7 +387,8 @@ int ks265_input_convert(ks265_ctx *c, const ks265_in_desc *d, uint8_t *dst)
     for (int k = 0; k < 3; ++k) { a.p[k] = (const uint8_t *)d->plane[k]; a.pitch[k] = d->pitch[k]; }
     a.W = (int)W; a.H = (int)H; a.dst = dst; a.step = d->pixel_step;
     const dim3 blk(64, 4);
-    if (d->format != KS265_IN_RGB) {
+    const int es = ks265_rgb_elem_size(d->format);
+    if (!es) {
         const int run = W % 16 == 0 ? 16 : 8;
         const dim3 grid((unsigned)((W / run + 63) / 64), (unsigned)((H / 2 + 3) / 4));
         if (d->format == KS265_IN_NV12) {
@@ -266,6 +409,24 @@ int ks265_input_convert(ks265_ctx *c, const ks265_in_desc *d, uint8_t *dst)
     a.yoff = (oy << 16) + 32768;
     const uintptr_t p0 = (uintptr_t)d->plane[0], p1 = (uintptr_t)d->plane[1], p2 = (uintptr_t)d->plane[2];
     const uintptr_t lo = p0 < p1 ? (p0 < p2 ? p0 : p2) : (p1 < p2 ? p1 : p2), hi = p0 > p1 ? (p0 > p2 ? p0 : p2) : (p1 > p2 ? p1 : p2);
+    const dim3 grid((unsigned)((W / 8 + 63) / 64), (unsigned)((H / 2 + 3) / 4));
+    if (es > 1) {                                                      // float samples: the kernel by type and pixel shape
+        CvtFArgs f = {};
+        for (int k = 0; k < 3; ++k) { f.p[k] = a.p[k]; f.cy[k] = a.cy[k]; f.cb[k] = a.cb[k]; f.cr[k] = a.cr[k]; }
+        f.pitch = d->pitch[0]; f.step = d->pixel_step; f.W = (int)W; f.H = (int)H; f.oy = oy; f.dst = dst;
+        int npix = d->pixel_step == es ? 1 : 0;
+        const uintptr_t base = d->pixel_step == 4 * es ? lo & ~(uintptr_t)(4 * es - 1) : lo;   // a four-element pixel lies on its own size; one of three begins at its lowest channel
+        if ((d->pixel_step == 3 * es || d->pixel_step == 4 * es) && hi - base < (uintptr_t)d->pixel_step) {
+            npix = d->pixel_step / es;
+            f.base = (const uint8_t *)base;
+            for (int k = 0; k < 3; ++k) f.off[k] = (int)(((uintptr_t)d->plane[k] - base) / (uintptr_t)es);
+            f.lo = (const uint8_t *)lo; f.ext = (long long)(hi - lo) + (W - 1) * d->pixel_step + es;
+        }
+        if (d->format == KS265_IN_RGB_F16) launch_rgbf<KS265_IN_RGB_F16>(c->stream, grid, blk, npix, f);
+        else if (d->format == KS265_IN_RGB_BF16) launch_rgbf<KS265_IN_RGB_BF16>(c->stream, grid, blk, npix, f);
+        else launch_rgbf<KS265_IN_RGB_F32>(c->stream, grid, blk, npix, f);
+        return ks265_check_launch(c);
+    }
     a.mode = d->pixel_step == 1 ? 1 : 0;
     if (d->pixel_step == 4 && hi - (lo & ~(uintptr_t)3) < 4) {         // the three channels are bytes of one 32-bit word per pixel (RGBA, BGRA, ARGB, ...)
         a.mode = 2;
@@ -273,7 +434,6 @@ int ks265_input_convert(ks265_ctx *c, const ks265_in_desc *d, uint8_t *dst)
         for (int k = 0; k < 3; ++k) a.sh[k] = 8 * (int)((uintptr_t)d->plane[k] - (lo & ~(uintptr_t)3));
         a.lo = (const uint8_t *)lo; a.ext = (long long)(hi - lo) + (W - 1) * 4 + 1;
     }
-    const dim3 grid((unsigned)((W / 8 + 63) / 64), (unsigned)((H / 2 + 3) / 4));
     hipLaunchKernelGGL(rgb_to_i420_kernel, grid, blk, 0, c->stream, a);
     return ks265_check_launch(c);
 }

@@ -259,7 +259,7 @@ int ks265_input_scale(ks265_ctx *c, const ks265_scale_plan *p, const ks265_in_de
     if ((uintptr_t)dst & 15) { c->last_error = "scale: destination not 16-byte aligned"; return KS265_NOTSUPPORTED; }
     if ((r = ks265_check_extent(c, dst, dn * 3 / 2, 1, dn * 3 / 2, "destination"))) return r;
     ScaleArgs a = {};
-    if (s->format == KS265_IN_RGB) {
+    if (ks265_rgb_elem_size(s->format)) {                              // RGB of any sample type
         if (!scratch) { c->last_error = "scale: an RGB source needs the scratch picture"; return KS265_POINTER; }
         if ((uintptr_t)scratch & 15) { c->last_error = "scale: scratch not 16-byte aligned"; return KS265_NOTSUPPORTED; }
         if ((r = ks265_check_extent(c, scratch, sn * 3 / 2, 1, sn * 3 / 2, "scratch"))) return r;

@@ -35,6 +35,11 @@ static inline int ks265_check_launch(ks265_ctx *ctx)
 }
 // [p, p + pitch (rows - 1) + row_bytes) lies inside one device allocation on the context's device, else KS265_POINTER and last_error (input_convert.hip)
 int ks265_check_extent(ks265_ctx *c, const void *p, long long pitch, int rows, long long row_bytes, const char *what);
+// bytes per sample of an RGB format of ks265_in_desc (KS265_IN_RGB 1; _F16 and _BF16 2; _F32 4); 0 for I420, NV12 and every unknown code
+static inline int ks265_rgb_elem_size(int format)
+{
+    return format == KS265_IN_RGB ? 1 : format == KS265_IN_RGB_F16 || format == KS265_IN_RGB_BF16 ? 2 : format == KS265_IN_RGB_F32 ? 4 : 0;
+}
 static inline int ks265_hip(ks265_ctx *ctx, hipError_t e)
 {
     if (e == hipSuccess) return KS265_OK;

@@ -2,7 +2,8 @@
 // an I420 repack onto arbitrary pitches, an NV12 interleave, and YCbCr -> RGB (RGB24, RGBA / BGRA, planar) in exact integer arithmetic (tests/yuv_output_ref.py is the
 // specification).  The mirror image of input_convert.hip: one thread owns a run of 8 luma columns across the two luma rows of one chroma row - the rows that share their
 // vertical chroma neighbours - so the three chroma rows it interpolates from are 2 x 3 x 5 bytes in registers (no LDS round trip).  Wide accesses where the address allows, a
-// byte path for the rest; nothing is written outside [row start, row start + row bytes) of any destination row.
+// byte path for the rest; nothing is written outside [row start, row start + row bytes) of any destination row.  The RGB picture also goes out as float16 / bfloat16 / float32
+// samples byte / 255 (tests/yuv_float_ref.py).
 #include "ks265_internal.h"
 #include <cmath>
 
@@ -163,27 +164,142 @@ __global__ __launch_bounds__(256) void i420_to_rgb_kernel(OutArgs a)
     }
 }
 
+// ---- float RGB (KS265_IN_RGB_F16 / _BF16 / _F32; tests/yuv_float_ref.py is the specification): the picture i420_to_rgb_kernel makes, each byte k as the sample k / 255
+struct OutFArgs {
+    const uint8_t *src;
+    uint8_t *p[3];                // R, G, B of pixel (0, 0)
+    long long pitch;
+    int step, W, H;               // step in bytes
+    int ky8, rv, gu, gv, bu, oy;
+    uint8_t *px0;                 // NPIX 3 / 4: the first byte of pixel (0, 0) = the lowest channel pointer; the channels are its elements off[c], 1.0 goes to the element none names
+    int off[3];
+};
+
+template <int FMT> struct FElem { typedef uint16_t type; };
+template <> struct FElem<KS265_IN_RGB_F32> { typedef uint32_t type; };
+
+// the bit pattern of the sample of byte k: the correctly rounded float32 of k / 255 - an IEEE division (this translation unit is built without fast-math, and hipcc keeps float32
+// division correctly rounded; tests/test_gpu_float_recon.py drives all 256 codes through every channel) - and for the 16-bit types that value rounded to nearest even
+template <int FMT> __device__ inline uint32_t code_bits(uint32_t k)
+{
+    const float f = (float)k / 255.0f;
+    if constexpr (FMT == KS265_IN_RGB_F32) return __float_as_uint(f);
+    else if constexpr (FMT == KS265_IN_RGB_BF16) { const uint32_t b = __float_as_uint(f); return (b + 0x7fffu + (b >> 16 & 1u)) >> 16; }
+    else { const _Float16 h = (_Float16)f; uint16_t b; __builtin_memcpy(&b, &h, 2); return b; }
+}
+template <int FMT> __device__ constexpr uint32_t one_bits() { return FMT == KS265_IN_RGB_F32 ? 0x3f800000u : FMT == KS265_IN_RGB_BF16 ? 0x3f80u : 0x3c00u; }
+
+// the first n of NE elements (bit patterns) to p: 16-byte stores where all NE are there and p is on 16 bytes, else element by element
+template <int ES, int NE> __device__ inline void store_elems(uint8_t *p, int n, const uint32_t (&e)[NE])
+{
+    if (n == NE && !((uintptr_t)p & 15)) {
+#pragma unroll
+        for (int k = 0; k < NE * ES / 16; ++k) {
+            uint32_t w[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) w[j] = ES == 4 ? e[4 * k + j] : e[8 * k + 2 * j] | e[8 * k + 2 * j + 1] << 16;
+            ((uint4 *)p)[k] = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < NE; ++k) {
+            if (k >= n) continue;
+            if constexpr (ES == 4) ((uint32_t *)p)[k] = e[k]; else ((uint16_t *)p)[k] = (uint16_t)e[k];
+        }
+    }
+}
+
+// float RGB: 8 luma columns x the two rows of chroma row i -> 16 pixels.  NPIX 1: planar; 3 / 4: the channels are elements of one pixel of 3 / 4 elements that begins at px0 (a run of
+// 8 pixels is one contiguous store); 0: three channels that share no pixel (step 3 elements), element by element
+template <int FMT, int NPIX> __global__ __launch_bounds__(256) void i420_to_rgbf_kernel(OutFArgs a)
+{
+    typedef typename FElem<FMT>::type E;
+    constexpr int ES = (int)sizeof(E);
+    const int x0 = (blockIdx.x * 64 + threadIdx.x) * 8, i = blockIdx.y * 4 + threadIdx.y;
+    if (x0 >= a.W || 2 * i >= a.H) return;
+    const size_t W = (size_t)a.W, npx = W * a.H;
+    const int n = a.W - x0 < 8 ? a.W - x0 : 8, w = a.W / 2, h = a.H / 2, j0 = x0 / 2;
+    int cu[3][5], cv[3][5];                                            // as i420_to_rgb_kernel: chroma rows i - 1, i, i + 1, columns j0 .. j0 + 4, clamped
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const int ci = i + r - 1 < 0 ? 0 : i + r - 1 > h - 1 ? h - 1 : i + r - 1;
+        load_chroma(a.src + npx + (size_t)ci * w, j0, w, n / 2, cu[r]);
+        load_chroma(a.src + npx + npx / 4 + (size_t)ci * w, j0, w, n / 2, cv[r]);
+    }
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+        int y[8];
+        load_run(a.src + (2 * i + dy) * W + x0, n, y);
+        int vu[5], vv[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) { vu[k] = 3 * cu[1][k] + cu[2 * dy][k]; vv[k] = 3 * cv[1][k] + cv[2 * dy][k]; }
+        uint32_t px[3][8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int j = k >> 1;
+            const int us = (k & 1 ? vu[j] + vu[j + 1] : 2 * vu[j]) - 1024, vs = (k & 1 ? vv[j] + vv[j + 1] : 2 * vv[j]) - 1024;
+            const int y8 = (y[k] - a.oy) * a.ky8 + (1 << 18);
+            px[0][k] = code_bits<FMT>(shr19_clip255(y8 + a.rv * vs));
+            px[1][k] = code_bits<FMT>(shr19_clip255(y8 + a.gu * us + a.gv * vs));
+            px[2][k] = code_bits<FMT>(shr19_clip255(y8 + a.bu * us));
+        }
+        const long long ro = (long long)(2 * i + dy) * a.pitch;
+        if constexpr (NPIX == 1) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) store_elems<ES, 8>(a.p[ch] + ro + (long long)x0 * ES, n, px[ch]);
+        } else if constexpr (NPIX >= 3) {
+            uint32_t e[8 * NPIX];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+#pragma unroll
+                for (int j = 0; j < NPIX; ++j) e[k * NPIX + j] = j == a.off[0] ? px[0][k] : j == a.off[1] ? px[1][k] : j == a.off[2] ? px[2][k] : one_bits<FMT>();
+            }
+            store_elems<ES, 8 * NPIX>(a.px0 + ro + (long long)x0 * (NPIX * ES), n * NPIX, e);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                if (k >= n) continue;
+                const long long o = ro + (long long)(x0 + k) * a.step;
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) *(E *)(a.p[ch] + o) = (E)px[ch][k];
+            }
+        }
+    }
+}
+
+template <int FMT> void launch_rgbf(hipStream_t st, dim3 grid, dim3 blk, int npix, const OutFArgs &a)
+{
+    if (npix == 1) hipLaunchKernelGGL((i420_to_rgbf_kernel<FMT, 1>), grid, blk, 0, st, a);
+    else if (npix == 3) hipLaunchKernelGGL((i420_to_rgbf_kernel<FMT, 3>), grid, blk, 0, st, a);
+    else if (npix == 4) hipLaunchKernelGGL((i420_to_rgbf_kernel<FMT, 4>), grid, blk, 0, st, a);
+    else hipLaunchKernelGGL((i420_to_rgbf_kernel<FMT, 0>), grid, blk, 0, st, a);
+}
+
 int q16(double x) { return (int)std::floor(x * 65536 + 0.5); }
 
 int check_out_desc(ks265_ctx *c, const ks265_in_desc *d)
 {
     if (d->width <= 0 || d->height <= 0 || (d->width & 1) || (d->height & 1)) { c->last_error = "output: width and height even"; return KS265_NOTSUPPORTED; }
-    if (d->format != KS265_IN_I420 && d->format != KS265_IN_NV12 && d->format != KS265_IN_RGB) { c->last_error = "output: unknown format"; return KS265_NOTSUPPORTED; }
+    const int es = ks265_rgb_elem_size(d->format);
+    if (d->format != KS265_IN_I420 && d->format != KS265_IN_NV12 && !es) { c->last_error = "output: unknown format"; return KS265_NOTSUPPORTED; }
     const long long W = d->width, H = d->height;
     int r = KS265_OK;
-    if (d->format == KS265_IN_RGB) {
-        if ((d->pixel_step != 1 && d->pixel_step != 3 && d->pixel_step != 4) || (d->matrix != KS265_MATRIX_BT709 && d->matrix != KS265_MATRIX_BT601)) {
-            c->last_error = "output: RGB pixel step 1, 3 or 4, matrix BT.709 or BT.601"; return KS265_NOTSUPPORTED;
+    if (es) {                                                          // RGB: bytes (es 1) or float samples; steps and offsets in elements of es bytes
+        if ((d->pixel_step != es && d->pixel_step != 3 * es && d->pixel_step != 4 * es) || (d->matrix != KS265_MATRIX_BT709 && d->matrix != KS265_MATRIX_BT601)) {
+            c->last_error = "output: RGB pixel step 1, 3 or 4 elements, matrix BT.709 or BT.601"; return KS265_NOTSUPPORTED;
+        }
+        if (((uintptr_t)d->plane[0] | (uintptr_t)d->plane[1] | (uintptr_t)d->plane[2] | (uintptr_t)d->pitch[0]) & (uintptr_t)(es - 1)) {
+            c->last_error = "output: float RGB pointers and pitch are multiples of the element size"; return KS265_NOTSUPPORTED;
         }
         if (d->pitch[0] < W * d->pixel_step) { c->last_error = "output: RGB pitch below width x pixel step"; return KS265_POINTER; }
-        if (d->pixel_step == 4) {                                      // the three channels are three different bytes of one four-byte pixel, which begins at the lowest of them
+        if (d->pixel_step == 4 * es) {                                 // the three channels are three different elements of one four-element pixel, which begins at the lowest of them
             const uintptr_t p0 = (uintptr_t)d->plane[0], p1 = (uintptr_t)d->plane[1], p2 = (uintptr_t)d->plane[2];
             const uintptr_t lo = p0 < p1 ? (p0 < p2 ? p0 : p2) : (p1 < p2 ? p1 : p2), hi = p0 > p1 ? (p0 > p2 ? p0 : p2) : (p1 > p2 ? p1 : p2);
             if (!d->plane[0] || !d->plane[1] || !d->plane[2]) { c->last_error = "output: NULL"; return KS265_POINTER; }
-            if (hi - lo > 3 || p0 == p1 || p0 == p2 || p1 == p2) { c->last_error = "output: pixel step 4 needs the three channels inside one four-byte pixel"; return KS265_NOTSUPPORTED; }
-            return ks265_check_extent(c, (const void *)lo, d->pitch[0], (int)H, W * 4, "RGBA");
+            if (hi - lo > (uintptr_t)(3 * es) || p0 == p1 || p0 == p2 || p1 == p2) { c->last_error = "output: pixel step 4 needs the three channels inside one four-element pixel"; return KS265_NOTSUPPORTED; }
+            return ks265_check_extent(c, (const void *)lo, d->pitch[0], (int)H, W * 4 * es, "RGBA");
         }
-        const long long rb = (W - 1) * d->pixel_step + 1;
+        const long long rb = (W - 1) * d->pixel_step + es;
         for (int k = 0; k < 3 && !r; ++k) r = ks265_check_extent(c, d->plane[k], d->pitch[0], (int)H, rb, k == 0 ? "R" : k == 1 ? "G" : "B");
     } else {
         r = ks265_check_extent(c, d->plane[0], d->pitch[0], (int)H, W, "Y");
@@ -217,7 +333,8 @@ int ks265_output_convert(ks265_ctx *c, const uint8_t *src, const ks265_in_desc *
     for (int k = 0; k < 3; ++k) { a.p[k] = (uint8_t *)d->plane[k]; a.pitch[k] = d->pitch[k]; }
     a.W = (int)W; a.H = (int)H; a.step = d->pixel_step;
     const dim3 blk(64, 4), grid((unsigned)(((W + 7) / 8 + 63) / 64), (unsigned)((H / 2 + 3) / 4));
-    if (d->format != KS265_IN_RGB) {
+    const int es = ks265_rgb_elem_size(d->format);
+    if (!es) {
         if (d->format == KS265_IN_NV12) hipLaunchKernelGGL((i420_to_yuv_kernel<true>), grid, blk, 0, c->stream, a);
         else hipLaunchKernelGGL((i420_to_yuv_kernel<false>), grid, blk, 0, c->stream, a);
         return ks265_check_launch(c);
@@ -227,6 +344,24 @@ int ks265_output_convert(ks265_ctx *c, const uint8_t *src, const ks265_in_desc *
     a.oy = d->full_range ? 0 : 16;
     a.ky8 = 8 * q16(1 / sy);
     a.rv = q16(2 * (1 - Kr) / sc); a.gu = q16(-2 * Kb * (1 - Kb) / (Kg * sc)); a.gv = q16(-2 * Kr * (1 - Kr) / (Kg * sc)); a.bu = q16(2 * (1 - Kb) / sc);
+    if (es > 1) {                                                      // float samples: the kernel by type and pixel shape
+        OutFArgs f = {};
+        f.src = src; f.pitch = d->pitch[0]; f.step = d->pixel_step; f.W = (int)W; f.H = (int)H;
+        f.ky8 = a.ky8; f.rv = a.rv; f.gu = a.gu; f.gv = a.gv; f.bu = a.bu; f.oy = a.oy;
+        const uintptr_t p0 = (uintptr_t)d->plane[0], p1 = (uintptr_t)d->plane[1], p2 = (uintptr_t)d->plane[2];
+        const uintptr_t lo = p0 < p1 ? (p0 < p2 ? p0 : p2) : (p1 < p2 ? p1 : p2), hi = p0 > p1 ? (p0 > p2 ? p0 : p2) : (p1 > p2 ? p1 : p2);
+        unsigned used = 0;
+        for (int k = 0; k < 3; ++k) { f.p[k] = a.p[k]; const uintptr_t o = ((uintptr_t)d->plane[k] - lo) / (uintptr_t)es; f.off[k] = o < 4 ? (int)o : 4; used |= 1u << f.off[k]; }
+        int npix = d->pixel_step == es ? 1 : 0;
+        if (d->pixel_step == 4 * es || (d->pixel_step == 3 * es && hi - lo == (uintptr_t)(2 * es) && used == 7)) {   // (4: checked above; 3: R, G, B are the three elements of one pixel)
+            npix = d->pixel_step / es;
+            f.px0 = (uint8_t *)lo;
+        }
+        if (d->format == KS265_IN_RGB_F16) launch_rgbf<KS265_IN_RGB_F16>(c->stream, grid, blk, npix, f);
+        else if (d->format == KS265_IN_RGB_BF16) launch_rgbf<KS265_IN_RGB_BF16>(c->stream, grid, blk, npix, f);
+        else launch_rgbf<KS265_IN_RGB_F32>(c->stream, grid, blk, npix, f);
+        return ks265_check_launch(c);
+    }
     a.mode = d->pixel_step == 1 ? 1 : 0;
     if (d->pixel_step == 4) {
         const uintptr_t p0 = (uintptr_t)d->plane[0], p1 = (uintptr_t)d->plane[1], p2 = (uintptr_t)d->plane[2];

@@ -1,10 +1,13 @@
 """Encoder for torch users: pictures that are GPU tensors already go into the encoder without leaving the device (include/ks265_enc.h ks265_enc_encode_device_frame).
 
     enc = Encoder(3840, 2160, preset="slow", qp=27, iper=128)
-    for frame in frames:                          # uint8 CUDA/HIP tensors: (H, W, 3 / 4) RGB(A) / BGR(A), (3, H, W) planar RGB, (H * 3 / 2, W) I420 / NV12
-        out += enc.encode(frame, format="rgba")
+    for frame in frames:                          # CUDA/HIP tensors: (H, W, 3 / 4) RGB(A) / BGR(A) or (3, H, W) planar RGB as uint8, or as float16 / bfloat16 /
+        out += enc.encode(frame, format="rgba")   # float32 with values in [0, 1]; (H * 3 / 2, W) I420 / NV12 as uint8
     out += enc.flush()
     enc.close()
+
+A float tensor is read where it lies, once, by one kernel (KS265_IN_RGB_F16 / _BF16 / _F32 of include/ks265_enc.h; tests/yuv_float_ref.py is the specification): [0, 1] is the
+full 8-bit range, values outside are clamped, NaN counts 0.  A float32 picture u8 / 255 writes the stream of the uint8 picture u8; the 16-bit types land within one code of it.
 
 The encoder reads each tensor in the order of torch's current stream and makes that stream wait until it has: the caller may overwrite the tensor with further work on the
 same stream as soon as encode() returns, with no host synchronisation.  Parameters are QY265ConfigParse names (qp, crf, rc, iper, bframes, lookahead, latency, ...);
@@ -15,7 +18,8 @@ picture's.
 recon="rgb"|"bgr"|"rgba"|"bgra"|"rgb_planar"|"nv12"|"i420" (with recon_matrix=, recon_full_range=) keeps the reconstruction of every picture of THIS handle fetchable on the
 device (`devrecon`, include/ks265_enc.h): after every encode() / flush(), enc.recon() returns [(poc, tensor), ...] - the pictures a decoder of the stream will show, as fresh
 uint8 tensors in that format, filled in the order of torch's current stream with no host synchronisation.  They must be fetched before the next encode(): the encoder takes
-the pictures back then.
+the pictures back then.  recon_dtype=torch.float16|torch.bfloat16|torch.float32 (RGB formats only; default torch.uint8) returns them as float tensors instead: every sample is
+the uint8 reconstruction's byte / 255, correctly rounded - recon * 255 is the uint8 picture.
 
 roi=True lets THIS handle take a map of quantiser offsets with every picture (`roi`, include/ks265_enc.h): encode(tensor, format, roi=MAP, roi_block=16) with MAP a 2-D int8 or
 float32 array of QP offsets (positive = coarser), one element per roi_block x roi_block luma samples (1, 2, 4 .. 64), ceil(H / roi_block) x ceil(W / roi_block) elements, unit
@@ -34,6 +38,7 @@ import os
 from . import stream as _stream
 
 IN_I420, IN_NV12, IN_RGB = 0, 1, 2
+IN_RGB_F16, IN_RGB_BF16, IN_RGB_F32 = 16, 17, 18              # RGB as float samples in [0, 1]; pointers, pixel step and pitch stay in bytes
 MATRIX_BT709, MATRIX_BT601 = 0, 1
 QY_OK, QY_FAIL, QY_OUTOFMEMORY, QY_POINTER, QY_NOTSUPPORTED = 0, -0x7FFFFFFF, -0x7FFFFFFE, -0x7FFFFFFD, -0x7FFFFFFC
 # format name -> (code, byte offsets of R, G, B inside a pixel of an HWC tensor)
@@ -99,31 +104,40 @@ def library() -> C.CDLL:
     return _lib
 
 
-def describe(t, format: str, matrix: int = MATRIX_BT709, full_range: bool = False) -> DevPicture:
-    """the ks265_dev_picture of a uint8 GPU tensor (no copy: its storage, its strides); ValueError for a layout the encoder cannot read in place"""
+def _rgb_code(dtype) -> int:
+    """the format code of an RGB tensor's dtype"""
     import torch
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.device.type != "cuda":
-        raise ValueError("a uint8 tensor on the GPU")
+    return {torch.uint8: IN_RGB, torch.float16: IN_RGB_F16, torch.bfloat16: IN_RGB_BF16, torch.float32: IN_RGB_F32}[dtype]
+
+
+def describe(t, format: str, matrix: int = MATRIX_BT709, full_range: bool = False) -> DevPicture:
+    """the ks265_dev_picture of a GPU tensor (no copy: its storage, its strides): uint8, or for the RGB formats float16 / bfloat16 / float32 in [0, 1]; ValueError for a layout the
+    encoder cannot read in place"""
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype not in (torch.uint8, torch.float16, torch.bfloat16, torch.float32) or t.device.type != "cuda":
+        raise ValueError("a uint8, float16, bfloat16 or float32 tensor on the GPU")
     if format not in _FORMATS:
         raise ValueError(f"format: one of {sorted(_FORMATS)}")
     code, offs = _FORMATS[format]
+    if code != IN_RGB and t.dtype != torch.uint8:
+        raise ValueError(f"{format}: a uint8 tensor (float samples are RGB only)")
     p = DevPicture()
-    p.format, p.device = code, t.device.index if t.device.index is not None else torch.cuda.current_device()
+    p.format, p.device = _rgb_code(t.dtype) if code == IN_RGB else code, t.device.index if t.device.index is not None else torch.cuda.current_device()
     p.matrix, p.full_range = matrix, int(bool(full_range))
-    base, es = t.data_ptr(), t.element_size()
+    base, es = t.data_ptr(), t.element_size()                   # strides are in elements, the descriptor in bytes
     if code == IN_RGB and format == "rgb_planar":
         if t.dim() != 3 or t.shape[0] != 3 or t.stride(2) != 1 or t.stride(1) < t.shape[2]:
             raise ValueError("rgb_planar: a (3, H, W) tensor with unit column stride")
         for k in range(3):
             p.plane[k] = base + k * t.stride(0) * es
-        p.pitch[0], p.pixel_step = t.stride(1), 1
+        p.pitch[0], p.pixel_step = t.stride(1) * es, es
     elif code == IN_RGB:
         n = 4 if format.endswith("a") else 3
         if t.dim() != 3 or t.shape[2] != n or t.stride(2) != 1 or t.stride(1) < n:
             raise ValueError(f"{format}: an (H, W, {n}) tensor with contiguous pixels")
         for k in range(3):
-            p.plane[k] = base + offs[k]
-        p.pitch[0], p.pixel_step = t.stride(0), t.stride(1)
+            p.plane[k] = base + offs[k] * es
+        p.pitch[0], p.pixel_step = t.stride(0) * es, t.stride(1) * es
     else:                                                       # (H * 3 / 2, W): Y rows, then the chroma rows
         if t.dim() != 2 or t.shape[0] % 3 or t.stride(1) != 1:
             raise ValueError(f"{format}: an (H * 3 / 2, W) tensor with unit column stride")
@@ -176,8 +190,15 @@ class Encoder:
             raise ValueError(f"parameter hash={hash_!r}: bad value (0, 2 = CRC, 3 = checksum)")
         self._recon = params.pop("recon", None)                 # `devrecon` (ks265_enc.h) for this handle alone, like `hash`; the format recon() fills its tensors in
         self._recon_matrix, self._recon_full = int(params.pop("recon_matrix", MATRIX_BT709)), bool(params.pop("recon_full_range", False))
+        self._recon_dtype = params.pop("recon_dtype", None)    # the dtype of recon()'s tensors: None = torch.uint8; float16 / bfloat16 / float32 for the RGB formats
         if self._recon is not None and self._recon not in _FORMATS:
             raise ValueError(f"recon: one of {sorted(_FORMATS)}")
+        if self._recon_dtype is not None:
+            import torch
+            if self._recon_dtype not in (torch.uint8, torch.float16, torch.bfloat16, torch.float32):
+                raise ValueError("recon_dtype: torch.uint8, torch.float16, torch.bfloat16 or torch.float32")
+            if self._recon_dtype != torch.uint8 and (self._recon is None or _FORMATS[self._recon][0] != IN_RGB):
+                raise ValueError("recon_dtype: a float dtype needs an RGB format in recon=")
         if self._recon is not None and self.lib.ks265_enc_set_default(b"devrecon", C.c_int(1)) != 0:
             raise ValueError("parameter recon: the library has no devrecon switch")
         self._roi = bool(params.pop("roi", False))              # `roi` (ks265_enc.h) for this handle alone, like `hash`
@@ -279,7 +300,7 @@ class Encoder:
         shape = {"rgb": (H, W, 3), "bgr": (H, W, 3), "rgba": (H, W, 4), "bgra": (H, W, 4), "rgb_planar": (3, H, W), "nv12": (H * 3 // 2, W), "i420": (H * 3 // 2, W)}[self._recon]
         info = Picture()
         while self.lib.ks265_enc_device_recon_pending(self.h) > 0:
-            t = torch.empty(shape, dtype=torch.uint8, device="cuda")
+            t = torch.empty(shape, dtype=self._recon_dtype or torch.uint8, device="cuda")
             rc = self.lib.ks265_enc_get_device_recon(self.h, C.byref(describe(t, self._recon, self._recon_matrix, self._recon_full)), C.addressof(info))
             if rc != QY_OK:
                 raise EncoderError("ks265_enc_get_device_recon", rc)

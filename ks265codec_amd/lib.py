@@ -49,6 +49,16 @@ class RoiDesc(C.Structure):                   # ks265_roi_desc
 ROI_INT8, ROI_FLOAT32 = 0, 1
 
 
+class InDesc(C.Structure):                    # ks265_in_desc
+    _fields_ = [("format", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("plane", C.c_void_p * 3), ("pitch", C.c_int32 * 3),
+                ("pixel_step", C.c_int32), ("matrix", C.c_int32), ("full_range", C.c_int32)]
+
+
+IN_I420, IN_NV12, IN_RGB = 0, 1, 2
+IN_RGB_F16, IN_RGB_BF16, IN_RGB_F32 = 16, 17, 18          # RGB as float samples in [0, 1]: plane, pixel_step and pitch stay in bytes
+RGB_ELEM_SIZE = {IN_RGB: 1, IN_RGB_F16: 2, IN_RGB_BF16: 2, IN_RGB_F32: 4}
+
+
 class Ks265Error(RuntimeError):
     pass
 
