@@ -34,6 +34,7 @@
  *   - transskip, tuIntra, vpp_*, 2-pass, long-term references, VBV / CVQ: accepted, ignored;
  *   - input pictures: the caller's planes are pinned in place and uploaded from where they lie inside QY265EncoderEncodeFrame; the caller may reuse its buffers when the call returns
  *     (the SDK requires them to stay valid until the frame is done);
+ *   - analysis out (not in the SDK; ks265_enc_set_default "analysis", ks265_enc_get_device_analysis below): motion, modes, QP and block error of every picture as device arrays;
  *   - reconstructed pictures in device memory (not in the SDK; ks265_enc_set_default "devrecon", ks265_enc_get_device_recon below): I420, NV12 or RGB(A), in the caller's stream order;
    - pictures in device memory (not in the SDK): ks265_enc_encode_device_frame takes I420, NV12 or RGB(A) planes on the GPU and converts them there, in the caller's stream
  *     order (ks265_dev_picture below) - no host copy, no upload, no pinning.
@@ -233,6 +234,43 @@ int ks265_enc_encode_device_frame_scaled(void *pEncoder, QY265Nal **pNals, int *
  * that read it (an event per slot), so a conversion still in flight when its slot goes back to the pool is safe. */
 int ks265_enc_device_recon_pending(void *pEncoder);
 int ks265_enc_get_device_recon(void *pEncoder, const ks265_dev_picture *dst, QY265Picture *info);
+/* extension: analysis out - what the encoder DECIDED about every picture, as arrays in device memory: the motion field and the reference each block points at, the CU tree,
+ * intra / inter, the residual flags, the QP every CTU was finally coded with (after -aq, the cuTree and the caller's `roi` offsets) and the squared error every block was left with.
+ * "analysis" (ks265_enc_set_default, 0 / 1, default 0; other values QY265_PARAM_BAD_VALUE; a process default read by the next QY265EncoderOpen, like "devrecon"; the environment's
+ * KS265_ANALYSIS=0|1 overrides it at open): every picture's analysis is packed into a block in device memory by ONE kernel on whichever stream codes the picture, beside the
+ * reconstruction's pack where "devrecon" is on too - the two switches share one pool (the slot numbers, the pool's size and the scheduler's wait for a free slot are devrecon's; a
+ * slot owns a packed picture if devrecon is on and an analysis block if analysis is on; the added bytes are logged at open).  The stream is byte for byte the one without the
+ * switch, and with the switch off not one call is added.  Refused at open, with one `ks265enc: analysis is unavailable: ...` line and the switch then off: a device library
+ * without ks265_analysis_pack, GOP lanes on several GPUs, the KS265_GRAPH experiment.
+ * With w8 x h8 = width / 8 x height / 8 blocks of 8 x 8 luma samples and cc x cr = ceil(width / 64) x ceil(height / 64) CTUs, the five fields (tests/analysis_ref.py is the
+ * definition):
+ *   mv   int16 [2][h8][w8][2]  list L's motion vector (x, y) in quarter samples; (0, 0) where the block does not use the list or is intra.  SIGN: a block at (x, y) predicts from
+ *                              (x + mv.x / 4, y + mv.y / 4) of its reference picture - content that moves right between the reference and this picture has a NEGATIVE x
+ *   ref  int8  [2][h8][w8]     display index of the reference picture the block uses in list L minus this picture's: negative = past; 0 = list unused or intra
+ *   cu   uint8 [5][h8][w8]     plane 0: 0 intra, 1 list 0, 2 list 1, 3 bi-predicted; plane 1: log2 of the CU size (3 .. 6); plane 2: 0 = 2Nx2N, 1 / 2 = the two rectangular
+ *                              shapes, 3 = four transform units; plane 3: coded block flags (bit 0 Y, 1 Cb, 2 Cr); plane 4: intra luma mode 0 .. 34, 255 for inter blocks
+ *   qp   int8  [cr][cc]        the CTU's QP
+ *   sse  int32 [3][h8][w8]     sum of (source - reconstruction)^2 over the block's 8 x 8 luma, 4 x 4 Cb and 4 x 4 Cr samples; a plane's sum is the picture's -psnr SSE
+ * (Skip and merge flags are decided by the slice writer on the host and are not part of the analysis.)
+ * Each field of ks265_dev_analysis: data (NULL = not wanted), pitch = bytes between rows, plane = bytes between planes (ignored for qp); rows are dense.
+ * When a call hands a picture's NAL units out, its analysis joins the handle's list, in the order of the call's NAL units (coding order).
+ *   ks265_enc_device_analysis_pending  how many analyses the last call handed out that have not been fetched yet;
+ *   ks265_enc_get_device_analysis      copies the wanted fields of the OLDEST pending one into `dst` and fills info->poc (the display index in the stream, as pOutpic reports
+ *                                      it, GOP lanes included), iSliceType and pts (info may be NULL).  Nothing outside [row start, row start + row bytes) of a row is
+ *                                      written.  QY_FAIL: nothing pending.  QY_POINTER: a wanted field whose whole extent does not lie inside one device allocation of the
+ *                                      handle's GPU, whose pitch is below its row, whose pitch, plane step or address is no multiple of its element size, or no field wanted
+ *                                      at all - the picture stays pending and nothing is enqueued.  QY_NOTSUPPORTED: the switch is off or dst->device is not the handle's GPU.
+ * CONTRACT: that of ks265_enc_get_device_recon.  Analyses live as long as the call's NAL array: the next encode, flush or close call on the handle takes every slot back,
+ * fetched or not.  The copy waits for the picture's packs and for everything the caller enqueued on dst->stream before the call, runs as one kernel IN dst->stream, and
+ * everything enqueued there after the call waits for it.  The call never blocks on the GPU; a block that is written again waits on its stream for the last copy that read it.
+ * Analyses and reconstructions of the same call are fetched independently of each other, in any interleaving. */
+typedef struct ks265_dev_analysis {
+    int device;                                /* HIP ordinal the arrays live on */
+    void *stream;                              /* hipStream_t the arrays are used on; NULL = the null stream */
+    struct { void *data; int pitch; long long plane; } mv, ref, cu, qp, sse;
+} ks265_dev_analysis;
+int ks265_enc_device_analysis_pending(void *pEncoder);
+int ks265_enc_get_device_analysis(void *pEncoder, const ks265_dev_analysis *dst, QY265Picture *info);
 /* extension: ROI - a map of quantiser offsets per picture, from host or device memory ("spend bits here, save them there"; x265's quantOffsets, a QP-delta map).
  * "roi" (ks265_enc_set_default, 0 / 1, default 0; other values QY265_PARAM_BAD_VALUE; a process default read by the next QY265EncoderOpen, like "hash"; the environment's
  * KS265_ROI=0|1 overrides it at open; `ks265enc -roi x:y:w:h:dqp` implies it): the stream carries one QP per CTU (cu_qp_delta_enabled_flag = 1 in the PPS, as with -aq and the

@@ -698,6 +698,37 @@ int ks265_roi_validate(ks265_ctx *, const ks265_roi_desc *map);
 int ks265_roi_reduce(ks265_ctx *, const ks265_roi_desc *map, int width, int height, int32_t *dev_records);
 int ks265_roi_ctu_map(ks265_ctx *, const int32_t *dev_records, const double *dev_base, int nx, int ny, int blocks_per_ctu_side, int ctu_cols, int ctu_rows,
                       int base_qp, int qp_lo, int qp_hi, int8_t *dev_map);
+/* Analysis out: what the encoder decided about a picture, as arrays in device memory (analysis.hip; tests/analysis_ref.py is the specification).  A picture of
+ * W x H has w8 x h8 = W / 8 x H / 8 blocks of 8 x 8 luma samples and cc x cr = ceil(W / 64) x ceil(H / 64) CTUs.  Five fields:
+ *   mv   int16 [2][h8][w8][2]  list L's vector (x, y) in quarter samples (ks265_cu8 mvx, mvy / mv1x, mv1y); (0, 0) where the block does not use the list or is intra
+ *   ref  int8  [2][h8][w8]     POC(the picture the block predicts from in list L) - POC(this picture): negative = past; 0 = list unused or intra (a reference never has
+ *                              delta 0).  The list index comes from ks265_cu8.inter_dir (bits 4..5 list 0, bits 6..7 list 1), the deltas from the caller's delta[L][index]
+ *   cu   uint8 [5][h8][w8]     plane 0 kind: 0 intra (pred_mode != 0), else inter_dir & 3 (1 = L0, 2 = L1, 3 = bi); plane 1 log2 of the CU size (log2_cu & 15); plane 2
+ *                              (log2_cu >> 4) & 3: 0 = 2Nx2N, 1 / 2 = the two rectangular shapes, 3 = four transform units; plane 3 cbf (bit 0 Y, 1 Cb, 2 Cr); plane 4 the
+ *                              intra luma mode (pred_mode 2: mvx, 0 .. 34), 255 for every other block
+ *   qp   int8  [cr][cc]        the CTU's QP: the entry of the map ks265_frame_set_qp_map takes, or the picture's QP everywhere
+ *   sse  int32 [3][h8][w8]     sum of (source - reconstruction)^2 over the block's 8 x 8 luma, 4 x 4 Cb and 4 x 4 Cr samples (at most 4 161 600 / 1 040 400); a plane's
+ *                              sum is what ks265_sse_picture gives for it, bit for bit
+ * (Skip and merge flags are the slice writer's, on the host: not here.)
+ *   ks265_analysis_pack      ONE launch on the frame's stream (_on: another context's): reads the CU map (NULL: the frame's own, the one ks265_frame_pack_compact packs), the
+ *                            QP map (NULL: picture_qp everywhere) and the two padded pictures once and writes a self-contained packed block of ks265_analysis_bytes bytes
+ *                            (256-byte aligned; ks265_analysis_layout: off[0..4] = byte offsets of mv, ref, cu, sse, qp - rows padded to a multiple of four entries -
+ *                            off[5] = the size).  Integer arithmetic, one writer per word: the result does not depend on the order the work-groups run in.
+ *   ks265_analysis_validate  enqueues nothing and judges every wanted field (data != NULL) as ks265_output_validate judges a plane: KS265_POINTER unless the field's whole
+ *                            extent - [data, data + plane (planes - 1) + pitch (rows - 1) + row bytes) - lies inside ONE device allocation on the context's device;
+ *                            KS265_NOTSUPPORTED for a pitch below the row, a pitch, plane step or address that is no multiple of the element size, a plane step below
+ *                            a plane's bytes, a size that is no multiple of 8, or no field wanted.
+ *   ks265_analysis_export    ONE launch on the context's stream: validates, then copies the wanted fields out of the packed block.  No byte outside
+ *                            [row start, row start + row bytes) of any row is written: what lies behind a pitch stays. */
+typedef struct { void *data; int32_t pitch; int64_t plane; } ks265_an_field;     /* data NULL = not wanted; pitch = bytes between rows, plane = bytes between planes */
+typedef struct { int32_t width, height; ks265_an_field mv, ref, cu, qp, sse; } ks265_analysis_desc;
+int ks265_analysis_layout(int width, int height, size_t off[6]);
+size_t ks265_analysis_bytes(ks265_frame *f);
+int ks265_analysis_pack(ks265_frame *f, ks265_pic src, ks265_pic recon, const ks265_cu8 *dev_cu8, const int8_t *dev_qp_map, int picture_qp, const int8_t delta[2][4], void *dev_block);
+int ks265_analysis_pack_on(ks265_ctx *cx, ks265_frame *f, ks265_pic src, ks265_pic recon, const ks265_cu8 *dev_cu8, const int8_t *dev_qp_map, int picture_qp,
+                           const int8_t delta[2][4], void *dev_block);
+int ks265_analysis_validate(ks265_ctx *, const ks265_analysis_desc *dst);
+int ks265_analysis_export(ks265_ctx *, const void *dev_block, const ks265_analysis_desc *dst);
 
 #ifdef __cplusplus
 }

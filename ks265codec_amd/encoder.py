@@ -29,7 +29,13 @@ in host memory (read before encode() returns).
 scale="bicubic"|"bilinear" (with scale_from=(W, H), the largest source; default 8 times the encoder's size, at most 8192 x 8192) lets THIS handle take tensors of other sizes
 (`ks265_enc_enable_device_scale`, include/ks265_enc.h): encode() scales them to the encoder's size on the GPU, in the order of torch's current stream like any other picture -
 Catmull-Rom or a triangle, both widened when shrinking, exact integer arithmetic (tests/yuv_scale_ref.py is the specification).  Source width a multiple of 8, height even, each
-ratio at most 8 either way.  One tensor may feed a ladder of handles of different sizes in one loop; a roi= map refers to the encoder's size."""
+ratio at most 8 either way.  One tensor may feed a ladder of handles of different sizes in one loop; a roi= map refers to the encoder's size.
+
+analysis=True keeps what the encoder DECIDED about every picture of THIS handle fetchable on the device (`analysis`, include/ks265_enc.h): after every encode() / flush(),
+enc.analysis() returns [{"poc", "slice_type", "mv", "ref", "cu", "qp", "sse"}, ...] for the pictures that call handed out, in coding order - fresh tensors filled on torch's
+current stream with no host synchronisation: mv int16 (2, H/8, W/8, 2) quarter-sample vectors per list, ref int8 (2, H/8, W/8) display-index deltas (negative = past, 0 = list
+unused or intra), cu uint8 (5, H/8, W/8) kind / log2 size / partition / cbf / intra mode, qp int8 (ceil(H/64), ceil(W/64)) the QP each CTU was coded with, sse int32
+(3, H/8, W/8) the squared error each 8x8 block was left with.  A block's displacement per picture, in samples: flow = mv / 4 / ref (where ref != 0)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -59,6 +65,15 @@ class DevPicture(C.Structure):
     """ks265_dev_picture of include/ks265_enc.h"""
     _fields_ = [("format", C.c_int), ("device", C.c_int), ("plane", C.c_void_p * 3), ("pitch", C.c_int * 3), ("pixel_step", C.c_int),
                 ("matrix", C.c_int), ("full_range", C.c_int), ("stream", C.c_void_p), ("pts", C.c_longlong)]
+
+
+class AnField(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("pitch", C.c_int), ("plane", C.c_longlong)]
+
+
+class DevAnalysis(C.Structure):
+    """ks265_dev_analysis of include/ks265_enc.h"""
+    _fields_ = [("device", C.c_int), ("stream", C.c_void_p), ("mv", AnField), ("ref", AnField), ("cu", AnField), ("qp", AnField), ("sse", AnField)]
 
 
 class Roi(C.Structure):
@@ -99,6 +114,8 @@ def library() -> C.CDLL:
         _lib.ks265_enc_device_recon_pending.argtypes = [C.c_void_p]
         _lib.ks265_enc_get_device_recon.argtypes = [C.c_void_p, C.POINTER(DevPicture), C.c_void_p]
         _lib.ks265_enc_set_next_roi.argtypes = [C.c_void_p, C.POINTER(Roi)]
+        _lib.ks265_enc_device_analysis_pending.argtypes = [C.c_void_p]
+        _lib.ks265_enc_get_device_analysis.argtypes = [C.c_void_p, C.POINTER(DevAnalysis), C.c_void_p]
         _lib.ks265_enc_enable_device_scale.argtypes = [C.c_void_p, C.c_int, C.c_int]
         _lib.ks265_enc_encode_device_frame_scaled.argtypes = [C.c_void_p, C.POINTER(C.POINTER(Nal)), C.POINTER(C.c_int), C.POINTER(DevPicture), C.c_int, C.c_int, C.c_int, C.c_void_p]
     return _lib
@@ -204,6 +221,9 @@ class Encoder:
         self._roi = bool(params.pop("roi", False))              # `roi` (ks265_enc.h) for this handle alone, like `hash`
         if self._roi and self.lib.ks265_enc_set_default(b"roi", C.c_int(1)) != 0:
             raise ValueError("parameter roi: the library has no roi switch")
+        self._analysis = bool(params.pop("analysis", False))    # `analysis` (ks265_enc.h) for this handle alone, like `hash`
+        if self._analysis and self.lib.ks265_enc_set_default(b"analysis", C.c_int(1)) != 0:
+            raise ValueError("parameter analysis: the library has no analysis switch")
         self._scale = params.pop("scale", None)                 # ks265_enc_enable_device_scale for this handle: the filter encode() scales tensors of other sizes with
         scale_from = params.pop("scale_from", None)
         if self._scale is not None and self._scale not in _SCALE_FILTERS:
@@ -222,6 +242,8 @@ class Encoder:
             self.lib.ks265_enc_set_default(b"devrecon", C.c_int(0))
         if self._roi:
             self.lib.ks265_enc_set_default(b"roi", C.c_int(0))
+        if self._analysis:
+            self.lib.ks265_enc_set_default(b"analysis", C.c_int(0))
         if not self.h:
             raise EncoderError("QY265EncoderOpen", err.value)
         rc = self.lib.ks265_enc_enable_device_input(self.h)
@@ -244,6 +266,13 @@ class Encoder:
             if self.lib.ks265_enc_get_device_recon(self.h, C.byref(probe), None) == QY_NOTSUPPORTED:
                 self.close()
                 raise EncoderError("recon=: device reconstruction is unavailable on this handle (see the log)", QY_NOTSUPPORTED)
+        self._flushed_an = []                                   # analysis(): what flush() fetched call by call
+        if self._analysis:                                      # refused at open?  Nothing is pending: QY_FAIL if the switch is on
+            probe = DevAnalysis()
+            probe.device = int(os.environ.get("KS265_DEVICE", "0"))
+            if self.lib.ks265_enc_get_device_analysis(self.h, C.byref(probe), None) == QY_NOTSUPPORTED:
+                self.close()
+                raise EncoderError("analysis=: the analysis is unavailable on this handle (see the log)", QY_NOTSUPPORTED)
 
     def _take(self) -> bytes:
         return b"".join(C.string_at(self._nal[i].pPayload, self._nal[i].iSize) for i in range(self._nn.value) if self._nal[i].iSize > 0)
@@ -283,12 +312,14 @@ class Encoder:
     def flush(self) -> bytes:
         out = bytearray()
         self._flushed += self._fetch()                          # (what the last encode() handed out and nobody fetched yet: the first flush call takes it back)
+        self._flushed_an += self._fetch_analysis()
         while self.h is not None and self.lib.QY265EncoderDelayedFrames(self.h):
             rc = self.lib.QY265EncoderEncodeFrame(self.h, C.byref(self._nal), C.byref(self._nn), None, C.addressof(self._out), 0)
             if rc != QY_OK:
                 raise EncoderError("QY265EncoderEncodeFrame (flush)", rc)
             out += self._take()
             self._flushed += self._fetch()                      # every call of the loop takes the previous call's reconstructions back: they are fetched here, for the next recon()
+            self._flushed_an += self._fetch_analysis()
         return bytes(out)
 
     def _fetch(self) -> list:
@@ -323,6 +354,35 @@ class Encoder:
         while self._next_display in self._held:
             out.append((self._next_display, self._held.pop(self._next_display)))
             self._next_display += 1
+        return out
+
+    def _fetch_analysis(self) -> list:
+        """every pending analysis (ks265_enc_get_device_analysis), oldest first, each into fresh tensors on torch's current stream"""
+        if not self._analysis or self.h is None:
+            return []
+        import torch
+        w8, h8, cc, cr = self.width // 8, self.height // 8, (self.width + 63) // 64, (self.height + 63) // 64
+        shapes = {"mv": (torch.int16, (2, h8, w8, 2)), "ref": (torch.int8, (2, h8, w8)), "cu": (torch.uint8, (5, h8, w8)), "qp": (torch.int8, (cr, cc)), "sse": (torch.int32, (3, h8, w8))}
+        info, out = Picture(), []
+        while self.lib.ks265_enc_device_analysis_pending(self.h) > 0:
+            a = {n: torch.empty(shape, dtype=dt, device="cuda") for n, (dt, shape) in shapes.items()}
+            d = DevAnalysis()
+            d.device, d.stream = torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream
+            for n, t in a.items():
+                es = t.element_size()
+                setattr(d, n, AnField(t.data_ptr(), t.stride(0) * es, 0) if n == "qp" else AnField(t.data_ptr(), t.stride(1) * es, t.stride(0) * es))
+            rc = self.lib.ks265_enc_get_device_analysis(self.h, C.byref(d), C.addressof(info))
+            if rc != QY_OK:
+                raise EncoderError("ks265_enc_get_device_analysis", rc)
+            out.append({"poc": info.poc, "slice_type": info.iSliceType, **a})
+        return out
+
+    def analysis(self) -> list:
+        """[{"poc", "slice_type", "mv", "ref", "cu", "qp", "sse"}, ...]: what the encoder decided about the pictures the last encode() / flush() handed out, in coding order
+        (poc = display index in the stream; slice_type 2 = I, 1 = P, 0 = B); the arrays as the module's header describes them"""
+        if not self._analysis:
+            raise RuntimeError("Encoder(..., analysis=True) switches the analysis on")
+        out, self._flushed_an = self._flushed_an + self._fetch_analysis(), []
         return out
 
     def quality(self) -> dict:

@@ -58,6 +58,12 @@
 #pragma weak ks265_scale_plan_create
 #pragma weak ks265_scale_plan_destroy
 #pragma weak ks265_input_scale
+/* `analysis` (what the encoder decided about a picture, fetched as arrays in device memory) reaches the pack and the export the same way: on a device library without them the
+ * encoder logs once that the analysis is unavailable and ks265_enc_get_device_analysis is QY_NOTSUPPORTED */
+#pragma weak ks265_analysis_bytes
+#pragma weak ks265_analysis_pack
+#pragma weak ks265_analysis_validate
+#pragma weak ks265_analysis_export
 
 const char strLibQy265Version[] = "ks265enc 0.2 (MI355X pixel path + host CABAC; API of libqycodec V2.6.1.3)";
 
@@ -110,7 +116,7 @@ static void md5_hex(const uint8_t *data, size_t n, char out[33])
 
 /* CLI-level switches of `appencoder` that the SDK's QY265EncConfig has no field for (-df, -fixqp, -md5): process-wide defaults a front end
  * sets before QY265EncoderOpen (ks265_enc_set_default) */
-static struct { int df, fixqp, md5, scenecut, cutree, gpb, hash, devrecon, roi; } g_cli = {1, 0, 0, 0, 1, 0, 0, 0, 0};
+static struct { int df, fixqp, md5, scenecut, cutree, gpb, hash, devrecon, roi, analysis; } g_cli = {1, 0, 0, 0, 1, 0, 0, 0, 0, 0};
 int ks265_enc_set_default(const char *name, int value)
 {
     if (!name) return QY_POINTER;
@@ -124,6 +130,7 @@ int ks265_enc_set_default(const char *name, int value)
     if (!strcmp(name, "hash")) { if (value != 0 && value != 2 && value != 3) return QY265_PARAM_BAD_VALUE; g_cli.hash = value; return QY_OK; }
     if (!strcmp(name, "devrecon")) { if (value < 0 || value > 1) return QY265_PARAM_BAD_VALUE; g_cli.devrecon = value; return QY_OK; }   /* reconstructions stay fetchable in device memory (ks265_enc.h) */
     if (!strcmp(name, "roi")) { if (value < 0 || value > 1) return QY265_PARAM_BAD_VALUE; g_cli.roi = value; return QY_OK; }             /* quantiser offset maps of the caller's (ks265_enc.h) */
+    if (!strcmp(name, "analysis")) { if (value < 0 || value > 1) return QY265_PARAM_BAD_VALUE; g_cli.analysis = value; return QY_OK; }   /* motion, modes, QP and block error stay fetchable in device memory (ks265_enc.h) */
     return QY265_PARAM_BAD_NAME;
 }
 
@@ -396,7 +403,10 @@ typedef struct Enc {
      * was one) - the next pack into the slot waits for it.  ctx_rec: the context the conversions run on (the calling thread's alone: it adopts the caller's stream).  taken: what take_output just moved out
      * of the ring, for the caller of take_output (the calling thread) to hand out or stash */
     int roi_on;                                           /* `roi` (ks265_enc.h): pictures may come with a map of quantiser offsets; one QP per CTU in the stream */
-    int devrecon, lane_idx; ReconPool rpool; struct ReconSlot { uint8_t *dev; void *ev_packed, *ev_read; int read_on; } rslot[RECON_POOL_MAX];
+    /* `analysis` (ks265_enc.h): the same pool, the same slot numbers - a slot owns a reconstruction if devrecon is on and an analysis block (an: ks265_analysis_bytes) if analysis
+     * is on; pool_on: either.  ev_packed is recorded once, behind the picture's last pack; each fetch kind has its own read event (ev_read_an / read_on_an: the exports) */
+    int devrecon, analysis, pool_on, lane_idx; ReconPool rpool;
+    struct ReconSlot { uint8_t *dev; void *ev_packed, *ev_read; int read_on; uint8_t *an; void *ev_read_an; int read_on_an; } rslot[RECON_POOL_MAX];
     ks265_ctx *ctx_rec; ReconList taken;
     int recon_fd, recon_on; uint8_t *dev_recon;           /* reconstruction dump (the CLI's -o) and / or plane MD5s (-md5 1): recon_on = the pictures come back to the host */
     int md5, fixqp, psnr_hdr; int md5_next; char (*md5_ring)[3][33]; unsigned char *md5_have;   /* MD5 lines go out in display order (ring of 256 by display index) */
@@ -917,7 +927,8 @@ typedef struct Sub {
     int k, recycled;                                      /* rotation slot of the input buffer / staging set (seq % NPIPE); it has held a picture before */
     int path; PixPath *p;                                 /* the pixel path that codes the picture (PATH_*) */
     int split, direct, graphable;
-    int rslot;                                            /* `devrecon`: the pool slot the reconstruction is packed into (-1 without) */
+    int rslot;                                            /* `devrecon` / `analysis`: the pool slot the reconstruction and the analysis block are packed into (-1 without) */
+    const int8_t *qmap;                                   /* the QP map set_qp_map handed to the frame object (NULL: the picture's QP everywhere) */
     const uint8_t *din; ks265_pic srcp; int slot; ks265_pic out;   /* the packed input on the device, the unpacked source picture, the reconstruction's DPB slot */
 } Sub;
 
@@ -1069,6 +1080,7 @@ static int set_qp_map(Enc *e, Sub *s)
         else if (!r) r = ks265_aq_ctu_map(ca, p->aq_off, e->aq_nx, e->aq_ny, s->qp, e->cfg.rc ? e->cfg.qpmin : 0, e->cfg.rc && e->cfg.qpmax ? e->cfg.qpmax : 51, qm);
     } else r = roi_ctu_map(e, s, ca, NULL, 0, 0, 4, e->cfg.rc ? e->cfg.qpmin : 0, e->cfg.rc && e->cfg.qpmax ? e->cfg.qpmax : 51, qm);   /* `roi` alone: the picture's QP + the caller's offsets (-aq's bounds) */
     if (!r) r = ks265_frame_set_qp_map(p->frame, qm);
+    s->qmap = qm;
     if (!r) r = ks265_memcpy_d2h_async(ca, s->j->qp_map, qm, (size_t)e->geom.ctu_cols * e->geom.ctu_rows);
     if (!r && s->split) { r = ks265_event_record(e->ctx_in, e->ev_h2d[k]); if (!r) r = ks265_stream_wait_event(p->ctx, e->ev_h2d[k]); }   /* (recorded again behind the map: the pixel path waits for this one) */
     return r;
@@ -1127,7 +1139,28 @@ static int recon_pack(Enc *e, const Sub *s)
     struct ReconSlot *q = &e->rslot[s->rslot];
     int r = q->read_on ? ks265_stream_wait_event(s->p->ctx, q->ev_read) : 0;
     if (!r) r = ks265_store_i420(s->p->frame, s->out, q->dev);
-    if (!r) r = ks265_event_record(s->p->ctx, q->ev_packed);
+    return r;
+}
+
+/* `analysis`: the picture's CU map, QP map and block error packed into the slot's analysis block, on the picture's own stream - behind the last export that read the block.  The
+ * reference indices of the CU map are resolved here: delta[L][i] = POC of list L's picture i - the picture's POC */
+static int analysis_pack(Enc *e, const Sub *s)
+{
+    struct ReconSlot *q = &e->rslot[s->rslot];
+    int8_t delta[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+    for (int i = 0; i < s->pic->nl0 && i < 4; ++i) { const int d = s->pic->l0[i] - s->pic->poc; delta[0][i] = (int8_t)(d < -128 ? -128 : d > 127 ? 127 : d); }
+    for (int i = 0; i < s->pic->nl1 && i < 4; ++i) { const int d = s->pic->l1[i] - s->pic->poc; delta[1][i] = (int8_t)(d < -128 ? -128 : d > 127 ? 127 : d); }
+    int r = q->read_on_an ? ks265_stream_wait_event(s->p->ctx, q->ev_read_an) : 0;
+    if (!r) r = ks265_analysis_pack(s->p->frame, s->srcp, s->out, NULL, s->qmap, s->qp, delta, q->an);
+    return r;
+}
+
+/* what a picture leaves in its pool slot (pool_on), and ONE record of the slot's ev_packed behind the last of it */
+static int slot_packs(Enc *e, const Sub *s)
+{
+    int r = e->devrecon ? recon_pack(e, s) : 0;
+    if (!r && e->analysis) r = analysis_pack(e, s);
+    if (!r) r = ks265_event_record(s->p->ctx, e->rslot[s->rslot].ev_packed);
     return r;
 }
 
@@ -1146,7 +1179,7 @@ static int drain_picture(Enc *e, const Sub *s, ks265_ctx *on, int captured)
     if (!r && p->dev_hash && !captured) r = ks265_memcpy_d2h_async(cx, s->j->hash, p->dev_hash, 24);
     if (!on && !captured) {
         if (!r && e->recon_on) r = recon_home(e, s);
-        if (!r && e->devrecon) r = recon_pack(e, s);
+        if (!r && e->pool_on) r = slot_packs(e, s);
         /* the records leave the frame object's buffers for a staging set (device to device, a few microseconds), so that the next picture can start
          * while the copy-out stream drains this one */
         if (!r && s->recycled) r = ks265_stream_wait_event(cx, e->ev_drained[s->k]);
@@ -1214,7 +1247,7 @@ static int code_picture_plain(Enc *e, Sub *s)
         return r;
     }
     if (!r && e->recon_on) r = recon_home(e, s);
-    if (!r && e->devrecon) r = recon_pack(e, s);                        /* (the split pipeline's drain_picture runs on the copy-out stream: the pack stays on the picture's own) */
+    if (!r && e->pool_on) r = slot_packs(e, s);                         /* (the split pipeline's drain_picture runs on the copy-out stream: the packs stay on the picture's own) */
     /* the drain runs on the copy-out stream (in order with the earlier pictures' drains: the staging block of this slot has been copied out before it is written) */
     if (!r) r = ks265_event_record(cx, e->ev_coded[k]);
     if (!r) r = ks265_stream_wait_event(e->ctx_out, e->ev_coded[k]);
@@ -1316,7 +1349,7 @@ static int submit(Enc *e, Input *in, const GopPic *pic, int qp)
     Sub s = {.in = in, .pic = pic, .qp = qp};
     if (!(s.j = wait_job_slot(e))) return QY_FAIL;
     s.rslot = -1;
-    if (e->devrecon && (s.rslot = wait_recon_slot(e)) < 0) return QY_FAIL;
+    if (e->pool_on && (s.rslot = wait_recon_slot(e)) < 0) return QY_FAIL;
     choose_path(e, &s);
     int r = stage_input(e, &s);
     if (!r) r = set_picture_tools(e, &s);
@@ -1477,7 +1510,7 @@ static int take_output(Enc *e, int max_in_flight, int max_pics, QY265Nal **pNals
             ++cnt;
         }
         if (out) { out->iSliceType = j->kind == 'I' ? 2 : j->kind == 'P' && !j->gpb ? 1 : 0; out->poc = j->disp; out->pts = j->pts; out->dts = j->pts; }
-        if (e->devrecon) {                                              /* the picture's reconstruction leaves the ring with it: the caller of this function hands it out, or stashes it */
+        if (e->pool_on) {                                               /* the picture's reconstruction leaves the ring with it: the caller of this function hands it out, or stashes it */
             const ReconRef ref = {e->lane_idx, j->rslot, j->disp, j->kind == 'I' ? 2 : j->kind == 'P' && !j->gpb ? 1 : 0, j->pts};
             if (recon_list_push(&e->taken, &ref)) err = QY_OUTOFMEMORY;
         }
@@ -1706,6 +1739,15 @@ static void lane_resolve(Enc *e, const QY265EncConfig *cfg, int device, int mult
     if (rec_req && !e->devrecon)
         logf_(2, e->log_level, "ks265enc: device reconstruction is unavailable: %s (devrecon is ignored)\n",
               !rec_lib ? "the device library has no ks265_output_convert" : multi == 2 ? "the handle's GOP lanes run on several GPUs" : "the KS265_GRAPH experiment replays captured pictures");
+    /* `analysis` (ks265_enc_set_default, KS265_ANALYSIS overrides): every picture's analysis block is packed into its pool slot and stays fetchable as devrecon's picture does;
+     * refused for the same three reasons */
+    const int an_req = env_int("KS265_ANALYSIS", g_cli.analysis) != 0;
+    const int an_lib = ks265_analysis_bytes && ks265_analysis_pack && ks265_analysis_validate && ks265_analysis_export && ks265_set_stream;
+    e->analysis = an_req && an_lib && multi != 2 && !graph_asked;
+    if (an_req && !e->analysis)
+        logf_(2, e->log_level, "ks265enc: analysis is unavailable: %s (analysis is ignored)\n",
+              !an_lib ? "the device library has no ks265_analysis_pack" : multi == 2 ? "the handle's GOP lanes run on several GPUs" : "the KS265_GRAPH experiment replays captured pictures");
+    e->pool_on = e->devrecon || e->analysis;
 
     /* the lookahead and the two optional streams */
     /* no -lookahead on the command line and the SDK's default GOP (hierarchical B, 8): the slice-type decision runs by itself (round 4: it costs a search of the half-size
@@ -1778,7 +1820,7 @@ static void lane_rings(Enc *e)
     /* `devrecon`: a slot per picture of the ring - a picture holds its slot while it is in the ring, and the slots the last call handed out come back at the start of the next
      * one, before anything waits: with fewer slots than the ring the scheduler would wait for the caller with job slots free.  A GOP lane adds a GOP: the pictures of a GOP that is
      * not yet at the head of the output order leave the ring for the handle's stash and keep their slots there (KS265_DEVRECON_SLOTS: a count above the ring's, experiments) */
-    if (e->devrecon) {
+    if (e->pool_on) {
         e->plan.recon_slots = e->ring + (e->multi ? (e->cfg.iIntraPeriod < 128 ? e->cfg.iIntraPeriod : 128) : 0);
         const int asked = env_int("KS265_DEVRECON_SLOTS", 0);
         if (asked > e->ring) e->plan.recon_slots = asked;
@@ -2109,23 +2151,31 @@ static void close_md5(Enc *e) { free(e->md5_ring); free(e->md5_have); }   /* (wh
  * behind it to other hardware queues, as every stream more does - lane_open) */
 static int open_devrecon(Enc *e)
 {
-    if (!e->devrecon) return KS265_OK;
-    const size_t fsz = (size_t)e->W * e->H * 3 / 2;
+    if (!e->pool_on) return KS265_OK;
+    const size_t fsz = (size_t)e->W * e->H * 3 / 2, asz = e->analysis ? ks265_analysis_bytes(main_frame(e)) : 0;
     if (recon_pool_init(&e->rpool, e->plan.recon_slots)) return KS265_FAIL;
     int r = KS265_OK;
     for (int i = 0; i < e->rpool.n && !r; ++i) {
-        r = ks265_dev_malloc(main_ctx(e), (void **)&e->rslot[i].dev, fsz);
+        if (e->devrecon) r = ks265_dev_malloc(main_ctx(e), (void **)&e->rslot[i].dev, fsz);
         if (!r) r = ks265_event_create(main_ctx(e), &e->rslot[i].ev_packed);
-        if (!r) r = ks265_event_create(main_ctx(e), &e->rslot[i].ev_read);
+        if (!r && e->devrecon) r = ks265_event_create(main_ctx(e), &e->rslot[i].ev_read);
+        if (!r && e->analysis) r = ks265_dev_malloc(main_ctx(e), (void **)&e->rslot[i].an, asz);
+        if (!r && e->analysis) r = ks265_event_create(main_ctx(e), &e->rslot[i].ev_read_an);
     }
-    logf_(1, e->log_level, "ks265enc: device reconstruction: a pool of %d packed I420 pictures, %.1f MB of device memory per lane (the ring of %d pictures in flight%s)\n", e->rpool.n,
-          e->rpool.n * (double)fsz / 1048576.0, e->ring, e->multi ? " + a GOP in the stash" : "");
+    if (e->devrecon)
+        logf_(1, e->log_level, "ks265enc: device reconstruction: a pool of %d packed I420 pictures, %.1f MB of device memory per lane (the ring of %d pictures in flight%s)\n", e->rpool.n,
+              e->rpool.n * (double)fsz / 1048576.0, e->ring, e->multi ? " + a GOP in the stash" : "");
+    if (e->analysis)
+        logf_(1, e->log_level, "ks265enc: analysis: a pool of %d blocks of %zu bytes, %.1f MB of device memory per lane (%s)\n", e->rpool.n, asz, e->rpool.n * (double)asz / 1048576.0,
+              e->devrecon ? "the slots of the device reconstruction's pool" : e->multi ? "the ring of pictures in flight + a GOP in the stash" : "the ring of pictures in flight");
     return r;
 }
 static void close_devrecon(Enc *e)                                     /* a conversion still in flight on a stream of the caller's reads its slot: waited for, by its event (the context: last, lane_close) */
 {
     for (int i = 0; i < RECON_POOL_MAX; ++i) if (e->rslot[i].read_on) (void)ks265_event_wait(main_ctx(e), e->rslot[i].ev_read);
+    for (int i = 0; i < RECON_POOL_MAX; ++i) if (e->rslot[i].read_on_an) (void)ks265_event_wait(main_ctx(e), e->rslot[i].ev_read_an);
     for (int i = 0; i < RECON_POOL_MAX; ++i) { ks265_dev_free(main_ctx(e), e->rslot[i].dev); ev_free(main_ctx(e), &e->rslot[i].ev_packed); ev_free(main_ctx(e), &e->rslot[i].ev_read); }
+    for (int i = 0; i < RECON_POOL_MAX; ++i) { ks265_dev_free(main_ctx(e), e->rslot[i].an); ev_free(main_ctx(e), &e->rslot[i].ev_read_an); }
     recon_list_free(&e->taken);
 }
 
@@ -3030,7 +3080,7 @@ static int top_encode(Top *t, QY265Nal **pNals, int *iNalCount, QY265Picture *in
     if (in || dp) t->roi_set = 0;
     if (t->nlanes == 1) {
         const int r1 = lane_encode_frame(t->lane[0], pNals, iNalCount, in, dp, sc, roi, out);
-        const int rr = t->lane[0]->devrecon ? recon_taken(t, t->lane[0], NULL, &t->handed) : QY_OK;
+        const int rr = t->lane[0]->pool_on ? recon_taken(t, t->lane[0], NULL, &t->handed) : QY_OK;
         return r1 ? r1 : rr;
     }
     *pNals = NULL; *iNalCount = 0;
@@ -3283,7 +3333,7 @@ int ks265_enc_set_next_roi(void *h, const ks265_roi *roi)
 int ks265_enc_device_recon_pending(void *h)
 {
     const Top *t = (const Top *)h;
-    return t ? recon_list_pending(&t->handed) : 0;
+    return t && t->lane[0]->devrecon ? recon_list_pending(&t->handed) : 0;
 }
 
 int ks265_enc_get_device_recon(void *h, const ks265_dev_picture *dst, QY265Picture *info)
@@ -3311,6 +3361,39 @@ int ks265_enc_get_device_recon(void *h, const ks265_dev_picture *dst, QY265Pictu
     if (r) return hip_rc(r);
     if (info) { info->iSliceType = ref->slice_type; info->poc = ref->poc; info->pts = ref->pts; info->dts = ref->pts; }
     recon_list_pop(&t->handed);
+    return QY_OK;
+}
+
+int ks265_enc_device_analysis_pending(void *h)
+{
+    const Top *t = (const Top *)h;
+    return t && t->lane[0]->analysis ? recon_list_pending_an(&t->handed) : 0;
+}
+
+int ks265_enc_get_device_analysis(void *h, const ks265_dev_analysis *dst, QY265Picture *info)
+{
+    Top *t = (Top *)h;
+    if (!t || !dst) return QY_POINTER;
+    if (!t->lane[0]->analysis || dst->device != t->lane[0]->dev_id) return QY_NOTSUPPORTED;
+    const ReconRef *ref = recon_list_front_an(&t->handed);
+    if (!ref) return QY_FAIL;
+    Enc *e = t->lane[ref->lane];
+    struct ReconSlot *q = &e->rslot[ref->slot];
+    /* every wanted field is checked before anything is enqueued: a refused one leaves the picture pending */
+    const ks265_analysis_desc d = {e->W, e->H, {dst->mv.data, dst->mv.pitch, dst->mv.plane}, {dst->ref.data, dst->ref.pitch, dst->ref.plane}, {dst->cu.data, dst->cu.pitch, dst->cu.plane},
+                                   {dst->qp.data, dst->qp.pitch, dst->qp.plane}, {dst->sse.data, dst->sse.pitch, dst->sse.plane}};
+    int r = e->ctx_rec ? KS265_OK : ks265_create(&e->ctx_rec, e->dev_id);   /* (the context the reconstructions' conversions run on, if any ran: the calling thread's alone) */
+    if (!r) r = ks265_set_stream(e->ctx_rec, dst->stream);
+    if (!r) r = ks265_analysis_validate(e->ctx_rec, &d);
+    if (r) return r == KS265_NOTSUPPORTED ? QY_POINTER : hip_rc(r);         /* (a pitch or an address the field cannot have: a bad field like any other) */
+    /* the export runs IN the caller's stream once that stream has waited for the picture's packs; ev_read_an behind it is what the block's next pack waits for */
+    r = ks265_stream_wait_event(e->ctx_rec, q->ev_packed);
+    if (!r) r = ks265_analysis_export(e->ctx_rec, q->an, &d);
+    if (!r) r = ks265_event_record(e->ctx_rec, q->ev_read_an);
+    if (!r) q->read_on_an = 1;                                          /* (read by the scheduler thread when it takes the slot again: after this call's successor released it, under mu) */
+    if (r) return hip_rc(r);
+    if (info) { info->iSliceType = ref->slice_type; info->poc = ref->poc; info->pts = ref->pts; info->dts = ref->pts; }
+    recon_list_pop_an(&t->handed);
     return QY_OK;
 }
 

@@ -61,8 +61,9 @@ static inline int recon_pool_untake(ReconPool *p, int s)
 
 /* one reconstruction on its way to the caller: the lane whose pool holds it, its slot there, and what ks265_enc_get_device_recon reports about the picture */
 typedef struct ReconRef { int lane, slot, poc, slice_type; long long pts; } ReconRef;
-/* in hand-out order; [0, next) have been fetched, [next, n) are pending */
-typedef struct ReconList { ReconRef *v; int n, cap, next; } ReconList;
+/* in hand-out order; [0, next) have been fetched, [next, n) are pending.  `analysis` (include/ks265_enc.h) hands a second thing out with every picture - the slot's analysis
+ * block - which is fetched on its own: a second cursor, next_an, over the same entries; neither cursor knows of the other */
+typedef struct ReconList { ReconRef *v; int n, cap, next, next_an; } ReconList;
 
 static inline int recon_list_push(ReconList *l, const ReconRef *r)
 {
@@ -78,7 +79,11 @@ static inline int recon_list_push(ReconList *l, const ReconRef *r)
 static inline int recon_list_pending(const ReconList *l) { return l->n - l->next; }
 static inline const ReconRef *recon_list_front(const ReconList *l) { return l->next < l->n ? &l->v[l->next] : NULL; }   /* the oldest pending one */
 static inline void recon_list_pop(ReconList *l) { if (l->next < l->n) ++l->next; }                                    /* ... has been fetched */
-static inline void recon_list_clear(ReconList *l) { l->n = l->next = 0; }                                              /* (after every entry was released) */
+static inline void recon_list_clear(ReconList *l) { l->n = l->next = l->next_an = 0; }                                 /* (after every entry was released) */
+/* the analyses of the same entries: pending, the oldest pending one, fetched */
+static inline int recon_list_pending_an(const ReconList *l) { return l->n - l->next_an; }
+static inline const ReconRef *recon_list_front_an(const ReconList *l) { return l->next_an < l->n ? &l->v[l->next_an] : NULL; }
+static inline void recon_list_pop_an(ReconList *l) { if (l->next_an < l->n) ++l->next_an; }
 static inline void recon_list_free(ReconList *l) { free(l->v); memset(l, 0, sizeof *l); }
 /* src's entries behind dst's, src left empty (a stashed GOP goes out) */
 static inline int recon_list_move(ReconList *dst, ReconList *src)

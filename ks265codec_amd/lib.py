@@ -49,6 +49,23 @@ class RoiDesc(C.Structure):                   # ks265_roi_desc
 ROI_INT8, ROI_FLOAT32 = 0, 1
 
 
+class AnField(C.Structure):                   # ks265_an_field
+    _fields_ = [("data", C.c_void_p), ("pitch", C.c_int32), ("plane", C.c_int64)]
+
+
+class AnalysisDesc(C.Structure):              # ks265_analysis_desc
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("mv", AnField), ("ref", AnField), ("cu", AnField), ("qp", AnField), ("sse", AnField)]
+
+
+ANALYSIS_FIELDS = ("mv", "ref", "cu", "qp", "sse")
+
+
+def analysis_shapes(width: int, height: int) -> dict:
+    """field -> (torch dtype name, shape) of a width x height picture's analysis (include/ks265_hip.h)"""
+    w8, h8, cc, cr = width // 8, height // 8, (width + 63) // 64, (height + 63) // 64
+    return {"mv": ("int16", (2, h8, w8, 2)), "ref": ("int8", (2, h8, w8)), "cu": ("uint8", (5, h8, w8)), "qp": ("int8", (cr, cc)), "sse": ("int32", (3, h8, w8))}
+
+
 class InDesc(C.Structure):                    # ks265_in_desc
     _fields_ = [("format", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("plane", C.c_void_p * 3), ("pitch", C.c_int32 * 3),
                 ("pixel_step", C.c_int32), ("matrix", C.c_int32), ("full_range", C.c_int32)]
@@ -87,6 +104,7 @@ EXPORTS = [
     "ks265_picture_hash", "ks265_picture_hash_on",
     "ks265_roi_validate", "ks265_roi_reduce", "ks265_roi_ctu_map",
     "ks265_scale_plan_create", "ks265_scale_plan_destroy", "ks265_input_scale_validate", "ks265_input_scale",
+    "ks265_analysis_layout", "ks265_analysis_bytes", "ks265_analysis_pack", "ks265_analysis_pack_on", "ks265_analysis_validate", "ks265_analysis_export",
 ]
 
 
@@ -377,6 +395,42 @@ class KsContext:
                                              C.c_int(blocks_per_ctu_side), C.c_int(ctu_cols), C.c_int(ctu_rows), C.c_int(base_qp), C.c_int(lo), C.c_int(hi), _p(out)))
         return self.host(out, np.int8)
 
+    # ---- analysis out (include/ks265_hip.h ks265_analysis_*)
+    def analysis_desc(self, width: int, height: int, **fields) -> AnalysisDesc:
+        """descriptor of the given device tensors (mv=, ref=, cu=, qp=, sse=; a field left out is not wanted): each of the field's dtype and shape (analysis_shapes), its
+        innermost dimension(s) dense, rows and planes at any stride"""
+        t = self.torch
+        d = AnalysisDesc(width, height)
+        shapes = analysis_shapes(width, height)
+        for name, x in fields.items():
+            if x is None:
+                continue
+            dt, shape = shapes[name]
+            dense = x.stride(-1) == 1 and (name != "mv" or x.stride(-2) == 2)
+            if x.dtype != getattr(t, dt) or tuple(x.shape) != shape or not dense:
+                raise Ks265Error(f"analysis field {name}: a {dt} tensor of shape {shape} with dense rows")
+            es = x.element_size()
+            if name == "qp":
+                setattr(d, name, AnField(x.data_ptr(), x.stride(0) * es, 0))
+            else:
+                setattr(d, name, AnField(x.data_ptr(), x.stride(1) * es, x.stride(0) * es))
+        return d
+
+    def analysis_validate(self, desc: AnalysisDesc) -> int:
+        """the library's return code (0, KS265_POINTER -3, KS265_NOTSUPPORTED -4): nothing is enqueued"""
+        return int(self.lib.ks265_analysis_validate(self.h, C.byref(desc)))
+
+    def analysis_export(self, block, desc: AnalysisDesc) -> None:
+        """one launch on the context's stream: the wanted fields of a packed block (KsFrame.analysis_pack) into the descriptor's arrays"""
+        self._chk(self.lib.ks265_analysis_export(self.h, _p(block), C.byref(desc)))
+
+    def analysis_tensors(self, block, width: int, height: int, fields=ANALYSIS_FIELDS) -> dict:
+        """fresh device tensors of the wanted fields, filled from a packed block on the context's stream"""
+        t = self.torch
+        out = {n: t.empty(analysis_shapes(width, height)[n][1], dtype=getattr(t, analysis_shapes(width, height)[n][0]), device=self.device) for n in fields}
+        self.analysis_export(block, self.analysis_desc(width, height, **out))
+        return out
+
     # ---- device input of another size (include/ks265_hip.h ks265_scale_plan_*, ks265_input_scale)
     def scale_plan(self, src_w: int, src_h: int, dst_w: int, dst_h: int, filter: int = 1) -> C.c_void_p:
         """a plan (the tables in device memory) for src -> dst, filter 0 triangle / 1 Catmull-Rom; scale_plan_destroy frees it"""
@@ -606,6 +660,29 @@ class KsFrame:
         out = self.ks.zeros(24)
         self.ks._chk(self.lib.ks265_ssim_picture(self.h, a.c(), b.c(), _p(sse), _p(out)))
         return (self.ks.host(sse, np.uint64) if with_sse else None), self.ks.host(out, np.int64)
+
+    def analysis_bytes(self) -> int:
+        self.lib.ks265_analysis_bytes.restype = C.c_size_t
+        return int(self.lib.ks265_analysis_bytes(self.h))
+
+    def analysis_layout(self) -> list:
+        """byte offsets of the packed block's mv, ref, cu, sse and qp segments, then its size"""
+        off = (C.c_size_t * 6)()
+        self.ks._chk(self.lib.ks265_analysis_layout(C.c_int(self.width), C.c_int(self.height), off))
+        return [int(x) for x in off]
+
+    def analysis_pack(self, src: DevPic, recon: DevPic, picture_qp: int, deltas=((0, 0, 0, 0), (0, 0, 0, 0)), qp_map=None, cu8=None, block=None, on: "KsContext | None" = None):
+        """one launch: the packed analysis block of the picture whose CU map is cu8 (device tensor; None = the frame's own) - deltas[L][i] = POC delta of list L's picture i,
+        qp_map = int8 device tensor of one QP per CTU or None; returns the block (a uint8 device tensor of analysis_bytes())"""
+        if block is None:
+            block = self.ks.torch.empty(self.analysis_bytes(), dtype=self.ks.torch.uint8, device=self.ks.device)
+        d = (C.c_int8 * 4 * 2)(*[(C.c_int8 * 4)(*[int(x) for x in row]) for row in deltas])
+        args = (src.c(), recon.c(), _p(cu8), _p(qp_map), C.c_int(picture_qp), d, _p(block))
+        if on is None:
+            self.ks._chk(self.lib.ks265_analysis_pack(self.h, *args))
+        else:
+            on._chk(self.lib.ks265_analysis_pack_on(on.h, self.h, *args))
+        return block
 
     def picture_hash(self, p: DevPic, on: "KsContext | None" = None):
         """uint32[6]: picture_crc of Y, Cb, Cr, then picture_checksum of Y, Cb, Cr (H.265 D.3.19) of the picture inside its padding, from one launch (on: another context's stream)"""
