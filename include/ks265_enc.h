@@ -168,6 +168,14 @@ int ks265_enc_acquire_input(void *pEncoder, QY265YUV *yuv);
  *                  plane, pixel_step and pitch[0] still in BYTES and multiples of the element size es (2, 2, 4), es <= pixel_step <= 64 (else QY_NOTSUPPORTED) - planar
  *                  (step es), HWC (3 es), four-element pixels (4 es).  One kernel reads the samples once; a float32 picture u8 / 255 codes as the picture u8 does, the
  *                  16-bit types within one code of it (tests/yuv_float_ref.py is the specification).
+ *   KS265_IN_YUV(layout, sub, depth, msb)   what decoders, capture cards and renderers leave in device memory: YUV of 8 to 16 bits in 4:2:0, 4:2:2 or 4:4:4, reduced to the
+ *                  encoder's 8-bit 4:2:0 by one kernel that reads the source once (tests/yuv_hibit_ref.py is the specification).  layout 0 planar (plane[0..2] = Y, U, V with
+ *                  their own pitches), 1 semi-planar (plane[0] = Y, plane[1] = U,V interleaved, U first), 2 packed YUYV, 3 packed UYVY (plane[0] alone; 4:2:2 only); sub 0 =
+ *                  4:2:0, 1 = 4:2:2, 2 = 4:4:4; depth 8 (bytes; msb 0) or 9 .. 16 (two-byte little-endian words: msb 1 = the sample is the TOP depth bits, as in P010 and
+ *                  Y210, msb 0 = the LOW bits, as in yuv420p10le).  The names below cover the common ones.  Two-byte formats want even plane addresses and pitches.  Any other
+ *                  combination is QY_NOTSUPPORTED.  Luma is rounded to 8 bits (ties up, clipped to 255); chroma is filtered at full depth - 4:2:2 by the vertical (1, 1)
+ *                  filter, 4:4:4 by (1, 2, 1) x (1, 1) at HEVC's default siting, as the RGB path does - and rounded ONCE, together with the depth reduction.  No dither, and
+ *                  no range or matrix conversion: the range that goes in comes out; pixel_step, matrix and full_range are ignored.
  * CONTRACT: the encoder reads the planes in the order of `stream` (a hipStream_t; NULL = the null stream): its work waits for everything the caller enqueued there before the
  * call, and everything the caller enqueues there after the call waits until the encoder has read the picture.  So the caller may overwrite the buffer with further work on that
  * same stream as soon as the call returns - no host synchronisation.  Work on OTHER streams must order itself against `stream`.  The call does not block on the GPU. */
@@ -177,10 +185,27 @@ int ks265_enc_acquire_input(void *pEncoder, QY265YUV *yuv);
 #define KS265_IN_RGB_F16 16
 #define KS265_IN_RGB_BF16 17
 #define KS265_IN_RGB_F32 18
+#define KS265_IN_YUV(layout, sub, depth, msb) (0x1000 | (layout) << 8 | (sub) << 6 | (msb) << 5 | (depth))
+#define KS265_IN_I422 KS265_IN_YUV(0, 1, 8, 0)
+#define KS265_IN_I444 KS265_IN_YUV(0, 2, 8, 0)
+#define KS265_IN_NV16 KS265_IN_YUV(1, 1, 8, 0)
+#define KS265_IN_NV24 KS265_IN_YUV(1, 2, 8, 0)
+#define KS265_IN_YUYV KS265_IN_YUV(2, 1, 8, 0)
+#define KS265_IN_UYVY KS265_IN_YUV(3, 1, 8, 0)
+#define KS265_IN_I010 KS265_IN_YUV(0, 0, 10, 0)               /* planar, the low bits (yuv420p10le / yuv422p10le / yuv444p10le) */
+#define KS265_IN_I210 KS265_IN_YUV(0, 1, 10, 0)
+#define KS265_IN_I410 KS265_IN_YUV(0, 2, 10, 0)
+#define KS265_IN_P010 KS265_IN_YUV(1, 0, 10, 1)               /* semi-planar, the top bits */
+#define KS265_IN_P012 KS265_IN_YUV(1, 0, 12, 1)
+#define KS265_IN_P016 KS265_IN_YUV(1, 0, 16, 1)
+#define KS265_IN_P210 KS265_IN_YUV(1, 1, 10, 1)
+#define KS265_IN_P410 KS265_IN_YUV(1, 2, 10, 1)
+#define KS265_IN_Y210 KS265_IN_YUV(2, 1, 10, 1)               /* YUYV order, the top bits */
+#define KS265_IN_Y216 KS265_IN_YUV(2, 1, 16, 1)
 #define KS265_MATRIX_BT709 0
 #define KS265_MATRIX_BT601 1
 typedef struct ks265_dev_picture {
-    int format;                                /* KS265_IN_I420 / _NV12 / _RGB / _RGB_F16 / _RGB_BF16 / _RGB_F32 */
+    int format;                                /* KS265_IN_I420 / _NV12 / _RGB / _RGB_F16 / _RGB_BF16 / _RGB_F32 / KS265_IN_YUV(...) (input only) */
     int device;                                /* HIP ordinal the planes live on */
     const void *plane[3]; int pitch[3];        /* bytes; RGB: channel pointers R, G, B and pitch[0] */
     int pixel_step;                            /* RGB only */
@@ -192,7 +217,7 @@ int ks265_enc_enable_device_input(void *pEncoder);
 int ks265_enc_encode_device_frame(void *pEncoder, QY265Nal **pNals, int *iNalCount, const ks265_dev_picture *pic, QY265Picture *pOutpic);
 /* extension: device pictures of ANOTHER size, scaled to the encoder's on the GPU (one decoded or rendered picture into a ladder of handles).  The resampler is separable and
  * exact (tests/yuv_scale_ref.py is the specification): filter 0 = triangle (bilinear, widened when shrinking), 1 = Catmull-Rom (widened the same way); luma and
- * vertical chroma centre-sited, horizontal chroma cosited as HEVC's default siting; an RGB source is converted at ITS size as above and the I420 picture is scaled.
+ * vertical chroma centre-sited, horizontal chroma cosited as HEVC's default siting; an RGB or KS265_IN_YUV source is converted at ITS size as above and the I420 picture is scaled.
  *   ks265_enc_enable_device_scale  after ks265_enc_enable_device_input, before the first picture: allocates per GOP lane one I420 picture of the largest source size (the RGB
  *       sources' way station) and nothing else.  QY_NOTSUPPORTED: device input off; after the first picture; a device library without the scaler (one log line "ks265enc: input
  *       scaling is unavailable: ..."); max_src_width no multiple of 8, max_src_height odd, either above 8192 or above 8 times the encoder's; an encoder whose width or height is

@@ -102,6 +102,17 @@ int ks265_external_wait_event(ks265_ctx *, void *hip_stream, void *ev);
  *                  bytes are (width - 1) pixel_step + es per channel.  Planar CHW (step es), HWC (3 es), four-element pixels (4 es) in any channel order.  A sample v counts
  *                  q = rint(clamp(v * 65280, 0, 65280)) (one float32 multiply, ties to even, NaN = 0) in 1 / 256 of a code; matrix, range and chroma filter as for
  *                  KS265_IN_RGB, in 64-bit integers (tests/yuv_float_ref.py is the specification): a float32 picture u8 / 255 gives byte for byte the picture of u8
+ *   KS265_IN_YUV(layout, sub, depth, msb)   YUV of 8 to 16 bits in 4:2:0, 4:2:2 or 4:4:4, reduced to 8-bit 4:2:0 by one kernel that reads the source once where it lies
+ *                  (input_yuv.hip; tests/yuv_hibit_ref.py is the specification).  layout 0 planar (plane[0..2] = Y, U, V, own pitches), 1 semi-planar (plane[0] = Y, plane[1] =
+ *                  U,V interleaved, U first), 2 packed YUYV (plane[0]: Y0 U Y1 V per pixel pair), 3 packed UYVY (U Y0 V Y1); sub 0 = 4:2:0, 1 = 4:2:2, 2 = 4:4:4 (packed: 4:2:2
+ *                  only); depth 8 = one-byte elements (msb 0), 9 .. 16 = two-byte little-endian elements whose sample is the TOP depth bits (msb 1: P010, Y210) or the LOW
+ *                  bits (msb 0: yuv420p10le) - stray bits on the other side are ignored.  Any other bit, depth, or combination: KS265_NOTSUPPORTED.  With the element size es,
+ *                  cw = width (4:4:4) or width / 2 and ch = height / 2 (4:2:0) or height, the planes are: planar height x width es, ch x cw es, ch x cw es; semi-planar
+ *                  height x width es, ch x 2 cw es; packed height x 2 width es.  Two-byte formats: every plane address and pitch even (else KS265_NOTSUPPORTED).
+ *                  Luma Y = min(255, (n + half) >> (depth - 8)).  Chroma is summed at full depth and rounded ONCE, together with the depth reduction, ties up: 4:2:2 by the
+ *                  vertical (1, 1) filter (centre-sited), 4:4:4 by (1, 2, 1) x (1, 1) with the left edge clamped (horizontally co-sited: the RGB path's filter, HEVC's default
+ *                  siting).  There is NO dither, and no range or matrix conversion: limited range in gives limited range out; pixel_step, matrix, full_range are ignored.
+ *                  KS265_IN_YUV(0, 0, 8, 0) and KS265_IN_YUV(1, 0, 8, 0) ARE KS265_IN_I420 and KS265_IN_NV12.
  * width a multiple of 8, height even.  ks265_input_validate enqueues nothing: KS265_POINTER unless the whole extent of every plane - [p, p + pitch (rows - 1) + row bytes) -
  * lies inside ONE device allocation on the context's device (host, managed and other devices' memory, short buffers, pitches below the row are refused); KS265_NOTSUPPORTED for a
  * format / size / matrix outside the list.  ks265_input_convert validates the source and the destination (width x height x 3 / 2 bytes of device memory, 16-byte aligned) the
@@ -112,6 +123,23 @@ int ks265_external_wait_event(ks265_ctx *, void *hip_stream, void *ev);
 #define KS265_IN_RGB_F16 16
 #define KS265_IN_RGB_BF16 17
 #define KS265_IN_RGB_F32 18
+#define KS265_IN_YUV(layout, sub, depth, msb) (0x1000 | (layout) << 8 | (sub) << 6 | (msb) << 5 | (depth))
+#define KS265_IN_I422 KS265_IN_YUV(0, 1, 8, 0)
+#define KS265_IN_I444 KS265_IN_YUV(0, 2, 8, 0)
+#define KS265_IN_NV16 KS265_IN_YUV(1, 1, 8, 0)
+#define KS265_IN_NV24 KS265_IN_YUV(1, 2, 8, 0)
+#define KS265_IN_YUYV KS265_IN_YUV(2, 1, 8, 0)
+#define KS265_IN_UYVY KS265_IN_YUV(3, 1, 8, 0)
+#define KS265_IN_I010 KS265_IN_YUV(0, 0, 10, 0)               /* planar, the low bits (yuv420p10le / yuv422p10le / yuv444p10le) */
+#define KS265_IN_I210 KS265_IN_YUV(0, 1, 10, 0)
+#define KS265_IN_I410 KS265_IN_YUV(0, 2, 10, 0)
+#define KS265_IN_P010 KS265_IN_YUV(1, 0, 10, 1)               /* semi-planar, the top bits */
+#define KS265_IN_P012 KS265_IN_YUV(1, 0, 12, 1)
+#define KS265_IN_P016 KS265_IN_YUV(1, 0, 16, 1)
+#define KS265_IN_P210 KS265_IN_YUV(1, 1, 10, 1)
+#define KS265_IN_P410 KS265_IN_YUV(1, 2, 10, 1)
+#define KS265_IN_Y210 KS265_IN_YUV(2, 1, 10, 1)               /* YUYV order, the top bits */
+#define KS265_IN_Y216 KS265_IN_YUV(2, 1, 16, 1)
 #define KS265_MATRIX_BT709 0
 #define KS265_MATRIX_BT601 1
 typedef struct {
@@ -133,7 +161,7 @@ int ks265_input_convert(ks265_ctx *, const ks265_in_desc *src, uint8_t *dev_i420
  *   ks265_input_scale_validate enqueues nothing: `src` (with the SOURCE's width and height, which must be the plan's: KS265_NOTSUPPORTED otherwise) is judged as
  *                              ks265_input_validate judges it - KS265_POINTER for extents, KS265_NOTSUPPORTED for formats and sizes.
  *   ks265_input_scale          validates source, destination (plan's width x height x 3 / 2 bytes of device memory, 16-byte aligned) and scratch before anything is launched.
- *                              An I420 or NV12 source is read where it lies, with its pitches; scratch may be NULL.  An RGB source is first converted by ks265_input_convert
+ *                              An I420 or NV12 source is read where it lies, with its pitches; scratch may be NULL.  An RGB source, and a KS265_IN_YUV source other than its two aliases of those, is first converted by ks265_input_convert
  *                              into scratch_i420 - source width x height x 3 / 2 bytes of device memory, 16-byte aligned, the caller's (NULL: KS265_POINTER) - and that picture
  *                              is scaled, on the same stream.  One kernel makes all three planes.  No byte outside [row start, row start + row bytes) of a source row is
  *                              read, none outside the destination picture written.  A plan whose sizes are equal is ks265_input_convert alone. */

@@ -3,7 +3,7 @@
 // (tests/yuv_convert_ref.py is the specification).  Memory-bound with no reuse beyond the neighbouring columns: one thread owns a run of luma columns across the
 // two rows of one chroma row, so every chroma sample is made from registers (no LDS round trip).  Wide loads where the address allows, a byte path for the rest;
 // the stores are always aligned (width a multiple of 8, the destination 16-byte aligned).  RGB as float16 / bfloat16 / float32 in [0, 1] goes the same way in one pass over the
-// samples, with 64-bit sums (tests/yuv_float_ref.py).
+// samples, with 64-bit sums (tests/yuv_float_ref.py).  YUV of more bits or more chroma (KS265_IN_YUV) is judged here first (check_any) and converted by input_yuv.hip.
 #include "ks265_internal.h"
 #include <cmath>
 
@@ -343,6 +343,16 @@ int check_desc(ks265_ctx *c, const ks265_in_desc *d)
     return r;
 }
 
+// a description judged whichever family it belongs to.  *fam = 1: the YUV family (input_yuv.hip), the fields in *f; 0: a format of this file - KS265_IN_YUV(0 / 1, 0, 8, 0)
+// are KS265_IN_I420 / _NV12, and *d then points at `loc`, the description under that code
+int check_any(ks265_ctx *c, const ks265_in_desc *&d, ks265_in_desc &loc, ks265_yuv_fmt *f, int *fam)
+{
+    *fam = ks265_yuv_decode(d->format, f);
+    if (*fam < 0) { c->last_error = "input: unknown format"; return KS265_NOTSUPPORTED; }
+    if (*fam && f->alias) { loc = *d; loc.format = f->layout ? KS265_IN_NV12 : KS265_IN_I420; d = &loc; *fam = 0; }
+    return *fam ? ks265_yuv_check_desc(c, d, *f) : check_desc(c, d);
+}
+
 int q16(double x) { return (int)std::floor(x * 65536 + 0.5); }
 
 }  // namespace
@@ -371,18 +381,21 @@ int ks265_input_validate(ks265_ctx *c, const ks265_in_desc *d)
 {
     if (!c || !d) return KS265_POINTER;
     ks_use_device(c);
-    return check_desc(c, d);
+    ks265_in_desc loc; ks265_yuv_fmt f; int fam;
+    return check_any(c, d, loc, &f, &fam);
 }
 
 int ks265_input_convert(ks265_ctx *c, const ks265_in_desc *d, uint8_t *dst)
 {
     if (!c || !d) return KS265_POINTER;
     ks_use_device(c);
-    int r = check_desc(c, d);
+    ks265_in_desc loc; ks265_yuv_fmt yf; int fam;
+    int r = check_any(c, d, loc, &yf, &fam);
     if (r) return r;
     const long long W = d->width, H = d->height;
     if ((uintptr_t)dst & 15) { c->last_error = "input: destination not 16-byte aligned"; return KS265_NOTSUPPORTED; }
     if ((r = check_extent(c, dst, W * H * 3 / 2, 1, W * H * 3 / 2, "destination"))) return r;
+    if (fam) return ks265_yuv_launch(c, d, yf, dst);
     CvtArgs a = {};
     for (int k = 0; k < 3; ++k) { a.p[k] = (const uint8_t *)d->plane[k]; a.pitch[k] = d->pitch[k]; }
     a.W = (int)W; a.H = (int)H; a.dst = dst; a.step = d->pixel_step;

@@ -259,15 +259,18 @@ int ks265_input_scale(ks265_ctx *c, const ks265_scale_plan *p, const ks265_in_de
     if ((uintptr_t)dst & 15) { c->last_error = "scale: destination not 16-byte aligned"; return KS265_NOTSUPPORTED; }
     if ((r = ks265_check_extent(c, dst, dn * 3 / 2, 1, dn * 3 / 2, "destination"))) return r;
     ScaleArgs a = {};
-    if (ks265_rgb_elem_size(s->format)) {                              // RGB of any sample type
-        if (!scratch) { c->last_error = "scale: an RGB source needs the scratch picture"; return KS265_POINTER; }
+    ks265_yuv_fmt yf;
+    const int fam = ks265_yuv_decode(s->format, &yf);                  // (validated above: a valid code of the YUV family, or none of it)
+    const bool nv12 = s->format == KS265_IN_NV12 || (fam > 0 && yf.alias && yf.layout == 1);
+    if (ks265_rgb_elem_size(s->format) || (fam > 0 && !yf.alias)) {    // RGB of any sample type, YUV of more bits or more chroma: converted at the source's size first
+        if (!scratch) { c->last_error = "scale: an RGB or KS265_IN_YUV source needs the scratch picture"; return KS265_POINTER; }
         if ((uintptr_t)scratch & 15) { c->last_error = "scale: scratch not 16-byte aligned"; return KS265_NOTSUPPORTED; }
         if ((r = ks265_check_extent(c, scratch, sn * 3 / 2, 1, sn * 3 / 2, "scratch"))) return r;
         if ((r = ks265_input_convert(c, s, scratch))) return r;        // the conversion at the source's size, then the scaler on the same stream
         a.pl[0] = {scratch, p->sw, 0, 1, p->sw, 0, 0, 0, 0, nullptr};
         a.pl[1] = {scratch + sn, p->sw / 2, 0, 1, p->sw / 2, 0, 0, 0, 0, nullptr};
         a.pl[2] = {scratch + sn + sn / 4, p->sw / 2, 0, 1, p->sw / 2, 0, 0, 0, 0, nullptr};
-    } else if (s->format == KS265_IN_NV12) {
+    } else if (nv12) {
         a.pl[0] = {(const uint8_t *)s->plane[0], s->pitch[0], 0, 1, p->sw, 0, 0, 0, 0, nullptr};
         a.pl[1] = {(const uint8_t *)s->plane[1], s->pitch[1], 0, 2, p->sw, 0, 0, 0, 0, nullptr};
         a.pl[2] = {(const uint8_t *)s->plane[1], s->pitch[1], 1, 2, p->sw, 0, 0, 0, 0, nullptr};
@@ -284,7 +287,7 @@ int ks265_input_scale(ks265_ctx *c, const ks265_scale_plan *p, const ks265_in_de
         a.fy[k] = p->first[2 * k + 1]; a.cy[k] = p->coef[2 * k + 1]; a.Ty[k] = p->T[2 * k + 1];
         a.nbx[k] = (a.pl[k].dw + TILE_W - 1) / TILE_W; a.nby[k] = (a.pl[k].dh + p->tile_rows - 1) / p->tile_rows;
     }
-    a.tile_rows = p->tile_rows; a.chunk_rows = p->chunk_rows; a.lstr = s->format == KS265_IN_NV12 ? p->lstr : p->lstr_planar; a.span_rows = p->span_rows; a.tx_max = p->tx_max; a.ty_max = p->ty_max;
+    a.tile_rows = p->tile_rows; a.chunk_rows = p->chunk_rows; a.lstr = nv12 ? p->lstr : p->lstr_planar; a.span_rows = p->span_rows; a.tx_max = p->tx_max; a.ty_max = p->ty_max;
     const unsigned blocks = (unsigned)(a.nbx[0] * a.nby[0] + 2 * a.nbx[1] * a.nby[1]);
     hipLaunchKernelGGL(scale_i420_kernel, dim3(blocks), dim3(NT), p->lds_bytes - (unsigned)(p->chunk_rows * (p->lstr - a.lstr)), c->stream, a);
     return ks265_check_launch(c);

@@ -40,6 +40,22 @@ static inline int ks265_rgb_elem_size(int format)
 {
     return format == KS265_IN_RGB ? 1 : format == KS265_IN_RGB_F16 || format == KS265_IN_RGB_BF16 ? 2 : format == KS265_IN_RGB_F32 ? 4 : 0;
 }
+// the YUV family KS265_IN_YUV(layout, sub, depth, msb) of ks265_in_desc: 0 for a code outside it, 1 for one of its valid codes (the fields then in f), -1 for any other code
+// with a bit at or above 0x1000 (refused everywhere).  f->alias: the code is KS265_IN_I420 / KS265_IN_NV12 under its other name and goes the way of that format
+struct ks265_yuv_fmt { int layout, sub, depth, msb, es, alias; };
+static inline int ks265_yuv_decode(int format, ks265_yuv_fmt *f)
+{
+    if (!(format & ~0xFFF)) return 0;
+    if ((format & ~0x3FF) != 0x1000) return -1;
+    f->layout = format >> 8 & 3; f->sub = format >> 6 & 3; f->msb = format >> 5 & 1; f->depth = format & 31;
+    if (f->depth < 8 || f->depth > 16 || f->sub > 2 || (f->depth == 8 && f->msb) || (f->layout >= 2 && f->sub != 1)) return -1;
+    f->es = f->depth == 8 ? 1 : 2;
+    f->alias = f->depth == 8 && f->sub == 0 && f->layout < 2;
+    return 1;
+}
+// input_yuv.hip: the family's side of ks265_input_validate / ks265_input_convert (d->format a valid code that is no alias; the destination already judged)
+int ks265_yuv_check_desc(ks265_ctx *c, const ks265_in_desc *d, const ks265_yuv_fmt &f);
+int ks265_yuv_launch(ks265_ctx *c, const ks265_in_desc *d, const ks265_yuv_fmt &f, uint8_t *dst);
 static inline int ks265_hip(ks265_ctx *ctx, hipError_t e)
 {
     if (e == hipSuccess) return KS265_OK;

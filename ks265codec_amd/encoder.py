@@ -9,6 +9,11 @@
 A float tensor is read where it lies, once, by one kernel (KS265_IN_RGB_F16 / _BF16 / _F32 of include/ks265_enc.h; tests/yuv_float_ref.py is the specification): [0, 1] is the
 full 8-bit range, values outside are clamped, NaN counts 0.  A float32 picture u8 / 255 writes the stream of the uint8 picture u8; the 16-bit types land within one code of it.
 
+YUV of more bits or more chroma (KS265_IN_YUV of include/ks265_enc.h; tests/yuv_hibit_ref.py is the specification) goes in as its planes, each a 2-D tensor with its own row
+stride: enc.encode((y, uv), "nv12", depth=10) is a decoder's P010 surface, (y, u, v) with "i420" | "i422" | "i444", (y, uv) with "nv12" | "nv16" | "nv24", one (H, 2W) tensor with
+"yuyv" | "uyvy"; uint8 planes are 8-bit, int16 / uint16 planes need depth=9..16 and msb= (the sample in the top bits of its word: the default for semi-planar and packed; in the
+low bits: the default for planar).  One kernel reads the picture once: luma rounded to 8 bits, chroma filtered at full depth and rounded once, no dither, the range passes through.
+
 The encoder reads each tensor in the order of torch's current stream and makes that stream wait until it has: the caller may overwrite the tensor with further work on the
 same stream as soon as encode() returns, with no host synchronisation.  Parameters are QY265ConfigParse names (qp, crf, rc, iper, bframes, lookahead, latency, ...);
 gpb=0|1 is the process default of that name (ks265_enc_set_default: anchors that search two or more past anchors as B slices over them), set before this handle opens.
@@ -50,7 +55,9 @@ QY_OK, QY_FAIL, QY_OUTOFMEMORY, QY_POINTER, QY_NOTSUPPORTED = 0, -0x7FFFFFFF, -0
 # format name -> (code, byte offsets of R, G, B inside a pixel of an HWC tensor)
 _FORMATS = {"i420": (IN_I420, None), "nv12": (IN_NV12, None), "rgb": (IN_RGB, (0, 1, 2)), "bgr": (IN_RGB, (2, 1, 0)),
             "rgba": (IN_RGB, (0, 1, 2)), "bgra": (IN_RGB, (2, 1, 0)), "rgb_planar": (IN_RGB, None)}
-_CONFIG_BYTES = 4096                                           # more than sizeof(QY265EncConfig): the library writes only its own layout
+# YUV given as its planes: format name -> (layout, subsampling) of KS265_IN_YUV
+_YUV_FORMATS = {"i420": (0, 0), "i422": (0, 1), "i444": (0, 2), "nv12": (1, 0), "nv16": (1, 1), "nv24": (1, 2), "yuyv": (2, 1), "uyvy": (3, 1)}
+_CONFIG_BYTES = 4096                                          # more than sizeof(QY265EncConfig): the library writes only its own layout
 
 
 class Nal(C.Structure):
@@ -127,10 +134,68 @@ def _rgb_code(dtype) -> int:
     return {torch.uint8: IN_RGB, torch.float16: IN_RGB_F16, torch.bfloat16: IN_RGB_BF16, torch.float32: IN_RGB_F32}[dtype]
 
 
-def describe(t, format: str, matrix: int = MATRIX_BT709, full_range: bool = False) -> DevPicture:
-    """the ks265_dev_picture of a GPU tensor (no copy: its storage, its strides): uint8, or for the RGB formats float16 / bfloat16 / float32 in [0, 1]; ValueError for a layout the
-    encoder cannot read in place"""
+def _describe_yuv(t, format: str, depth, msb) -> DevPicture:
+    """the ks265_dev_picture of a YUV picture given as its planes - (y, u, v), (y, uv), or the one (H, 2W) tensor of a packed format - with KS265_IN_YUV's code"""
     import torch
+    layout, sub = _YUV_FORMATS[format]
+    planes = [t] if isinstance(t, torch.Tensor) else list(t)
+    want = 3 if layout == 0 else 2 if layout == 1 else 1
+    if len(planes) != want:
+        raise ValueError(f"{format}: {('(y, u, v)', '(y, uv)', 'one (H, 2W) tensor')[min(layout, 2)]}")
+    words = (torch.int16,) + ((torch.uint16,) if hasattr(torch, "uint16") else ())
+    for x in planes:
+        if not isinstance(x, torch.Tensor) or x.device.type != "cuda" or x.dim() != 2 or x.dtype != planes[0].dtype or x.device != planes[0].device or (x.shape[1] > 1 and x.stride(1) != 1):
+            raise ValueError(f"{format}: 2-D GPU tensors of one dtype on one device, each with unit column stride")
+    if planes[0].dtype == torch.uint8:
+        if depth not in (None, 8) or msb:
+            raise ValueError(f"{format}: uint8 planes are depth 8 (no msb=)")
+        depth, msb = 8, False
+    elif planes[0].dtype in words:
+        if depth is None or not 9 <= int(depth) <= 16:
+            raise ValueError(f"{format}: int16 / uint16 planes need depth=9..16")
+        depth, msb = int(depth), (layout != 0) if msb is None else bool(msb)
+    else:
+        raise ValueError(f"{format}: uint8, int16 or uint16 planes")
+    H, W = planes[0].shape[0], planes[0].shape[1] // (2 if layout >= 2 else 1)
+    cw, ch = (W if sub == 2 else W // 2), (H // 2 if sub == 0 else H)
+    shapes = [(H, W), (ch, cw), (ch, cw)] if layout == 0 else [(H, W), (ch, 2 * cw)] if layout == 1 else [(H, 2 * W)]
+    if W % 2 or H % 2 or [tuple(x.shape) for x in planes] != shapes:
+        raise ValueError(f"{format}: planes of a {W}x{H} picture are {shapes}")
+    es = planes[0].element_size()
+    p = DevPicture()
+    p.format = (IN_I420, IN_NV12)[layout] if depth == 8 and sub == 0 else 0x1000 | layout << 8 | sub << 6 | int(msb) << 5 | depth
+    p.device = planes[0].device.index if planes[0].device.index is not None else torch.cuda.current_device()
+    for k, x in enumerate(planes):
+        if x.stride(0) < x.shape[1]:
+            raise ValueError(f"{format}: a row stride below the row")
+        p.plane[k], p.pitch[k] = x.data_ptr(), x.stride(0) * es
+    p.stream = torch.cuda.current_stream(planes[0].device).cuda_stream
+    return p
+
+
+def picture_size(t, format: str) -> tuple:
+    """(height, width) of the picture describe(t, format) describes"""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        return (t[0].shape[0], t[0].shape[1])
+    if format in ("yuyv", "uyvy"):
+        return (t.shape[0], t.shape[1] // 2)
+    if format in ("i420", "nv12"):
+        return (t.shape[0] * 2 // 3, t.shape[1])
+    return (t.shape[1], t.shape[2]) if format == "rgb_planar" else (t.shape[0], t.shape[1])
+
+
+def describe(t, format: str, matrix: int = MATRIX_BT709, full_range: bool = False, depth=None, msb=None) -> DevPicture:
+    """the ks265_dev_picture of a GPU tensor (no copy: its storage, its strides): uint8, or for the RGB formats float16 / bfloat16 / float32 in [0, 1]; ValueError for a layout the
+    encoder cannot read in place.  YUV beyond 8-bit 4:2:0 (KS265_IN_YUV of include/ks265_enc.h; tests/yuv_hibit_ref.py is the specification) comes as its planes: format "i420" |
+    "i422" | "i444" with a sequence (y, u, v), "nv12" | "nv16" | "nv24" with (y, uv), "yuyv" | "uyvy" with one (H, 2W) tensor - 2-D tensors with their own row strides and unit
+    column stride, on one device, all read on torch's current stream.  uint8 planes are depth 8; int16 / uint16 planes need depth=9..16 and say with msb= whether the sample is
+    the top bits of its word (the default for semi-planar and packed: P010, Y210) or the low bits (the default for planar: yuv420p10le).  The range that goes in comes out."""
+    import torch
+    if format in _YUV_FORMATS and (not isinstance(t, torch.Tensor) or format not in ("i420", "nv12")):
+        return _describe_yuv(t, format, depth, msb)
+    if depth is not None or msb is not None:
+        raise ValueError("depth= / msb=: for YUV pictures given as their planes")
     if not isinstance(t, torch.Tensor) or t.dtype not in (torch.uint8, torch.float16, torch.bfloat16, torch.float32) or t.device.type != "cuda":
         raise ValueError("a uint8, float16, bfloat16 or float32 tensor on the GPU")
     if format not in _FORMATS:
@@ -277,10 +342,11 @@ class Encoder:
     def _take(self) -> bytes:
         return b"".join(C.string_at(self._nal[i].pPayload, self._nal[i].iSize) for i in range(self._nn.value) if self._nal[i].iSize > 0)
 
-    def encode(self, tensor, format: str = "rgba", matrix: int = MATRIX_BT709, full_range: bool = False, roi=None, roi_block: int = 16) -> bytes:
+    def encode(self, tensor, format: str = "rgba", matrix: int = MATRIX_BT709, full_range: bool = False, roi=None, roi_block: int = 16, depth=None, msb=None) -> bytes:
+        """one picture in: a tensor, or the planes of a YUV picture with depth= / msb= (describe)"""
         if self.h is None:
             raise RuntimeError("encoder closed")
-        pic = describe(tensor, format, matrix, full_range)
+        pic = describe(tensor, format, matrix, full_range, depth, msb)
         if roi is not None:
             if not self._roi:
                 raise RuntimeError("Encoder(..., roi=True) switches the ROI maps on")
@@ -288,8 +354,7 @@ class Encoder:
             b = 1 << rd.log2_block
             if tuple(roi.shape) != ((self.height + b - 1) // b, (self.width + b - 1) // b):
                 raise ValueError(f"roi {tuple(roi.shape)}: a {self.width}x{self.height} picture in blocks of {b} is {((self.height + b - 1) // b, (self.width + b - 1) // b)}")
-        shape = (tensor.shape[0], tensor.shape[1]) if format not in ("i420", "nv12", "rgb_planar") else (tensor.shape[1], tensor.shape[2]) if format == "rgb_planar" \
-            else (tensor.shape[0] * 2 // 3, tensor.shape[1])
+        shape = picture_size(tensor, format)
         if shape != (self.height, self.width) and self._scale is None:
             raise ValueError(f"picture {shape[1]}x{shape[0]}, encoder {self.width}x{self.height}")
         if roi is not None:                                     # (behind every check of the picture: a refused picture leaves nothing pending)

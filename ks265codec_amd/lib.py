@@ -74,6 +74,19 @@ class InDesc(C.Structure):                    # ks265_in_desc
 IN_I420, IN_NV12, IN_RGB = 0, 1, 2
 IN_RGB_F16, IN_RGB_BF16, IN_RGB_F32 = 16, 17, 18          # RGB as float samples in [0, 1]: plane, pixel_step and pitch stay in bytes
 RGB_ELEM_SIZE = {IN_RGB: 1, IN_RGB_F16: 2, IN_RGB_BF16: 2, IN_RGB_F32: 4}
+YUV_PLANAR, YUV_SEMI, YUV_YUYV, YUV_UYVY = 0, 1, 2, 3     # KS265_IN_YUV's layout
+YUV_420, YUV_422, YUV_444 = 0, 1, 2                       # and its subsampling
+
+
+def in_yuv(layout: int, sub: int, depth: int = 8, msb: int = 0) -> int:
+    """KS265_IN_YUV(layout, sub, depth, msb): 8- to 16-bit YUV in 4:2:0 / 4:2:2 / 4:4:4 (depth > 8: two-byte elements, msb = the sample is their top bits)"""
+    return 0x1000 | layout << 8 | sub << 6 | int(bool(msb)) << 5 | depth
+
+
+IN_I422, IN_I444, IN_NV16, IN_NV24, IN_YUYV, IN_UYVY = in_yuv(0, 1), in_yuv(0, 2), in_yuv(1, 1), in_yuv(1, 2), in_yuv(2, 1), in_yuv(3, 1)
+IN_I010, IN_I210, IN_I410 = in_yuv(0, 0, 10), in_yuv(0, 1, 10), in_yuv(0, 2, 10)
+IN_P010, IN_P012, IN_P016, IN_P210, IN_P410 = in_yuv(1, 0, 10, 1), in_yuv(1, 0, 12, 1), in_yuv(1, 0, 16, 1), in_yuv(1, 1, 10, 1), in_yuv(1, 2, 10, 1)
+IN_Y210, IN_Y216 = in_yuv(2, 1, 10, 1), in_yuv(2, 1, 16, 1)
 
 
 class Ks265Error(RuntimeError):
@@ -442,7 +455,7 @@ class KsContext:
         self._chk(self.lib.ks265_scale_plan_destroy(self.h, plan))
 
     def input_scale(self, plan: C.c_void_p, desc, dst, scratch=None) -> None:
-        """desc: a ks265_in_desc (ctypes structure) of the source at the plan's source size; dst: uint8 device tensor of dst_w * dst_h * 3 / 2 bytes; scratch: for RGB sources"""
+        """desc: a ks265_in_desc (ctypes structure) of the source at the plan's source size; dst: uint8 device tensor of dst_w * dst_h * 3 / 2 bytes; scratch: for RGB and KS265_IN_YUV sources"""
         self._chk(self.lib.ks265_input_scale(self.h, plan, C.byref(desc), _p(scratch), _p(dst)))
 
     def intra_pred(self, ref, dst, blks: np.ndarray):
