@@ -60,7 +60,7 @@ typedef struct QY265EncConfig {
     QY265Tune tune; QY265Preset preset; QY265Latency latency;
     int profileId;                            /* 1 = Main (the only one written) */
     int bHeaderBeforeKeyframe;                /* VPS / SPS / PPS in front of every key picture */
-    int picWidth, picHeight;                  /* multiples of 8 */
+    int picWidth, picHeight;                  /* even (PICTURE SIZES below: a size that is no multiple of 8 is coded with a conformance window) */
     double frameRate;
     int bframes;                              /* -1: preset / latency default (hierarchical GOP 8 at default latency, else 0); 0: IPPP; 3 / 7: pyramids of 4 / 8 as in the reference; other n: n non-reference B pictures per anchor (at most 16: more is QY_NOTSUPPORTED at open) */
     int temporalLayer;
@@ -213,6 +213,19 @@ typedef struct ks265_dev_picture {
     void *stream;                              /* hipStream_t the planes were produced on; NULL = the null stream */
     long long pts;
 } ks265_dev_picture;
+/* PICTURE SIZES.  QY265EncoderOpen takes any EVEN picWidth / picHeight up to 8192 (odd: QY_NOTSUPPORTED).  A size that is no multiple of 8 is coded at the next multiple of 8 (the
+ * minimum CU size) and the SPS carries a conformance window - conf_win_right_offset = (coded width - picWidth) / 2, conf_win_bottom_offset likewise, left and top 0 - so a decoder
+ * outputs picWidth x picHeight: what the reference's encoder does (854x480 -> 856x480 and 0, 1, 0, 0).  The device library pads (ks265_input_pad: last column and last row replicated),
+ * crops and corrects the SSE; against a device library without those entries such a size is QY_NOTSUPPORTED with a log line.  On such a handle:
+ *   - every picture is described at picWidth x picHeight: QY265YUV (QY265EncoderEncodeFrame, ks265_enc_acquire_input), ks265_dev_picture, the CLI's input file;
+ *   - ks265_enc_encode_device_frame takes 8-bit KS265_IN_I420 and KS265_IN_NV12 only, planes at any pitch >= the row and any byte address; every other format, and
+ *     ks265_enc_enable_device_scale / ks265_enc_encode_device_frame_scaled, return QY_NOTSUPPORTED - nothing is enqueued, the handle stays usable;
+ *   - ks265_enc_get_device_recon fills picWidth x picHeight pictures in every format; ks265_enc_set_recon_file / -o writes picWidth x picHeight pictures;
+ *   - -psnr / ks265_enc_get_quality: SSE and PSNR over the picWidth x picHeight window.  SSIM (-ssim) stays over the CODED picture, padding included; so does the decoded picture
+ *     hash SEI, as H.265 D.3.19 defines it;
+ *   - a `roi` map describes the source picture: ceil(picWidth / b) x ceil(picHeight / b) elements;
+ *   - `analysis` arrays describe the CODED picture: ceil(picWidth / 8) x ceil(picHeight / 8) blocks (and ceil(. / 64) CTUs), block errors with the padding in them.
+ * For sizes that are multiples of 8 nothing differs from before: no byte of a stream, no device-library call. */
 int ks265_enc_enable_device_input(void *pEncoder);
 int ks265_enc_encode_device_frame(void *pEncoder, QY265Nal **pNals, int *iNalCount, const ks265_dev_picture *pic, QY265Picture *pOutpic);
 /* extension: device pictures of ANOTHER size, scaled to the encoder's on the GPU (one decoded or rendered picture into a ladder of handles).  The resampler is separable and
@@ -256,7 +269,10 @@ int ks265_enc_encode_device_frame_scaled(void *pEncoder, QY265Nal **pNals, int *
  * enqueued on dst->stream before the call, and everything enqueued on dst->stream after the call waits for it (it runs as one kernel IN dst->stream, which must be a stream of
  * the handle's GPU and alive until the handle is closed) - the caller reads `dst` with further work on that stream at once.
  * No host synchronisation happens anywhere and ks265_enc_get_device_recon does not block on the GPU; a slot that is written again waits on its stream for the last conversion
- * that read it (an event per slot), so a conversion still in flight when its slot goes back to the pool is safe. */
+ * that read it (an event per slot), so a conversion still in flight when its slot goes back to the pool is safe.
+ * A handle whose size is no multiple of 8 (PICTURE SIZES above): TWO kernels run in dst->stream - the crop of the coded picture into a scratch picture of the lane (allocated at
+ * QY265EncoderOpen with the pool: no allocation inside the call), then the conversion out of it.  Successive calls may name different streams: each call's crop waits in its
+ * stream for the conversion that read the scratch picture last (one more event), so fetching on several streams is safe; those conversions then run one after another. */
 int ks265_enc_device_recon_pending(void *pEncoder);
 int ks265_enc_get_device_recon(void *pEncoder, const ks265_dev_picture *dst, QY265Picture *info);
 /* extension: analysis out - what the encoder DECIDED about every picture, as arrays in device memory: the motion field and the reference each block points at, the CU tree,

@@ -187,6 +187,24 @@ int ks265_input_scale(ks265_ctx *, const ks265_scale_plan *plan, const ks265_in_
  * KS265_NOTSUPPORTED for a format / size / step / matrix outside the list.  ks265_output_convert validates destination and source the same way before it launches anything. */
 int ks265_output_validate(ks265_ctx *, const ks265_in_desc *dst);
 int ks265_output_convert(ks265_ctx *, const uint8_t *dev_i420, const ks265_in_desc *dst);
+/* Picture sizes that are no multiple of 8 (picture_window.hip; tests/picture_window_ref.py is the specification of every byte).  The encoder codes the size
+ * rounded up to 8 and signals a conformance window; these are the only entries that know both sizes.  One launch each on the context's stream.
+ *   ks265_input_pad    `src`: 8-bit KS265_IN_I420 or KS265_IN_NV12 only, width and height even and > 0, src.width <= coded_w < src.width + 8 and the same for the height,
+ *                      coded_w and coded_h multiples of 8; every plane with its own pitch >= the row's bytes, at ANY byte alignment.  Writes the packed I420 picture of
+ *                      coded_w x coded_h (device memory, 16-byte aligned): the source with its last column and last row replicated into the padding, luma and chroma alike
+ *                      (numpy's pad, mode "edge", per plane); NV12 is de-interleaved on the way.  No byte outside [row start, row start + row bytes) of a source row is
+ *                      read, none outside the destination picture written; the source is read once.
+ *   ks265_input_pad_validate   enqueues nothing: KS265_POINTER unless every plane's whole extent lies inside ONE device allocation on the context's device,
+ *                      KS265_NOTSUPPORTED for anything else outside the rules (format, sizes, a pitch below the row).  ks265_input_pad judges source and destination the
+ *                      same way before it launches anything.
+ *   ks265_output_crop  the top-left w x h of a packed coded_w x coded_h I420 picture (8-byte aligned) as a packed w x h I420 picture (any address); sizes as above.
+ *                      ks265_output_convert takes any even size, so crop + convert gives every output format.
+ *   ks265_sse_window   dev_sse3[0..2] -= the squared error, between the padded pictures a and b of the frame object's (coded) size, of the samples outside the top-left
+ *                      w x h: at most 7 columns and 7 rows of luma, half that of chroma.  Enqueued behind ks265_sse_picture[_on] / ks265_ssim_picture[_on] on the same
+ *                      stream it turns their plane sums into the window's; exact integers.  w x h = the frame's size: nothing is launched. */
+int ks265_input_pad_validate(ks265_ctx *, const ks265_in_desc *src, int coded_w, int coded_h);
+int ks265_input_pad(ks265_ctx *, const ks265_in_desc *src, int coded_w, int coded_h, uint8_t *dev_i420);
+int ks265_output_crop(ks265_ctx *, const uint8_t *dev_i420_coded, int coded_w, int coded_h, int w, int h, uint8_t *dev_i420);
 /* Launch sequences as graphs: between ks265_capture_begin and ks265_capture_end everything enqueued on this context's stream by THIS thread (kernel launches,
  * async memsets of the stage functions) is recorded instead of run (hipStreamBeginCapture, relaxed mode: other threads may go on using the runtime);
  * ks265_capture_end returns an executable graph, ks265_graph_launch enqueues all of it with one runtime call.  A host whose pictures repeat the same
@@ -695,6 +713,8 @@ int ks265_sse_picture_on(ks265_ctx *cx, ks265_frame *f, ks265_pic a, ks265_pic b
  * NULL) what ks265_sse_picture gives, bit for bit: the pictures are read once for both. */
 int ks265_ssim_picture(ks265_frame *f, ks265_pic a, ks265_pic b, uint64_t *dev_sse3, int64_t *dev_ssim3);
 int ks265_ssim_picture_on(ks265_ctx *cx, ks265_frame *f, ks265_pic a, ks265_pic b, uint64_t *dev_sse3, int64_t *dev_ssim3);
+/* the plane sums of the two calls above reduced to the top-left w x h window, on cx's stream (picture_window.hip; described with ks265_input_pad) */
+int ks265_sse_window(ks265_ctx *cx, ks265_frame *f, ks265_pic a, ks265_pic b, int w, int h, uint64_t *dev_sse3);
 /* the decoded picture hash of a padded picture (H.265 D.3.19, 8-bit 4:2:0): dev_hash6[0..2] = picture_crc of Y, Cb, Cr (CRC-16, polynomial 0x1021, preset
  * 0xFFFF, two zero bytes appended), dev_hash6[3..5] = picture_checksum of Y, Cb, Cr (sum of sample ^ (x & 0xFF) ^ (y & 0xFF) ^ (x >> 8) ^ (y >> 8) modulo 2^32), over the
  * W x H / W/2 x H/2 samples inside the padding.  One launch that reads the picture once; XOR and 32-bit adds only, so the result does not depend on the order the work-groups

@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 typedef struct {
-    int32_t width, height;                 /* luma, multiples of 8 (= MinCbSizeY)                                                   */
+    int32_t width, height;                 /* luma, multiples of 8 (= MinCbSizeY): the CODED size (see crop_right, crop_bottom)     */
     int32_t fps_num, fps_den;              /* only informative (no VUI is written unless > 0)                                       */
     int32_t sao, deblock;                  /* sample_adaptive_offset_enabled_flag / !pps_deblocking_filter_disabled_flag            */
     int32_t beta_offset_div2, tc_offset_div2;
@@ -34,6 +34,10 @@ typedef struct {
     int32_t cu_qp_delta;                   /* cu_qp_delta_enabled_flag with diff_cu_qp_delta_depth = 0 (quantisation group = CTU): slices carry a QP per CTU (qp_map)     */
     int32_t tu_inter;                      /* max_transform_hierarchy_depth_inter = 1 (-intertu 1): inter CUs of 32 / 16 / 8 samples code split_transform_flag; ks265_cu8.log2_cu
                                               bits 4..5 = 3 marks a 2Nx2N CU with four transform units (ks265_frame_cfg.tu_inter)                                          */
+    int32_t crop_right, crop_bottom;       /* conformance window, in luma samples: the decoder outputs the top-left (width - crop_right) x (height - crop_bottom) of every
+                                              picture.  Each 0, 2, 4 or 6 (anything else: KS265_NOTSUPPORTED).  Both 0: conformance_window_flag = 0, the SPS as it always was;
+                                              else the SPS carries conf_win_right_offset = crop_right / 2 and conf_win_bottom_offset = crop_bottom / 2 (left and top 0).  VPS,
+                                              PPS and slices do not know the window: they code width x height                                                              */
 } ks265_stream_cfg;
 
 enum { KS265_SLICE_B = 0, KS265_SLICE_P = 1, KS265_SLICE_I = 2 };

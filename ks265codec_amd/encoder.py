@@ -40,7 +40,12 @@ analysis=True keeps what the encoder DECIDED about every picture of THIS handle 
 enc.analysis() returns [{"poc", "slice_type", "mv", "ref", "cu", "qp", "sse"}, ...] for the pictures that call handed out, in coding order - fresh tensors filled on torch's
 current stream with no host synchronisation: mv int16 (2, H/8, W/8, 2) quarter-sample vectors per list, ref int8 (2, H/8, W/8) display-index deltas (negative = past, 0 = list
 unused or intra), cu uint8 (5, H/8, W/8) kind / log2 size / partition / cbf / intra mode, qp int8 (ceil(H/64), ceil(W/64)) the QP each CTU was coded with, sse int32
-(3, H/8, W/8) the squared error each 8x8 block was left with.  A block's displacement per picture, in samples: flow = mv / 4 / ref (where ref != 0)."""
+(3, H/8, W/8) the squared error each 8x8 block was left with.  A block's displacement per picture, in samples: flow = mv / 4 / ref (where ref != 0).
+
+Any EVEN width and height opens (Encoder(854, 480), Encoder(960, 540)): a size that is no multiple of 8 is coded at the next multiple of 8 with a conformance window, the
+picture padded on the GPU by replicating its last column and row (tests/picture_window_ref.py is the specification).  On such a handle encode() takes uint8 "i420" and "nv12"
+tensors of the SOURCE shape only (every other format, and scale=, raises ValueError); recon() returns W x H pictures in every format and dtype; quality() counts the window;
+a roi= map describes the source picture; analysis() describes the CODED picture - ceil(H / 8) x ceil(W / 8) blocks, block errors with the padding in them."""
 from __future__ import annotations
 
 import ctypes as C
@@ -295,6 +300,9 @@ class Encoder:
             raise ValueError(f"scale: one of {sorted(_SCALE_FILTERS)}")
         if scale_from is not None and self._scale is None:
             raise ValueError("scale_from: needs scale=")
+        self._ragged = bool(width % 8 or height % 8)            # coded at the next multiple of 8 with a conformance window (ks265_enc.h)
+        if self._ragged and self._scale is not None:
+            raise ValueError(f"scale=: the scaler writes sizes that are multiples of 8, not {width}x{height}")
         for k, v in (("wdt", width), ("hgt", height), *params.items()):
             rc = self.lib.QY265ConfigParse(self._cfg, str(k).replace("_", "-").encode(), str(v).encode())   # keyword form of the names with a dash: sao_ref=2 -> "sao-ref"
             if rc != 0:
@@ -347,6 +355,8 @@ class Encoder:
         if self.h is None:
             raise RuntimeError("encoder closed")
         pic = describe(tensor, format, matrix, full_range, depth, msb)
+        if self._ragged and pic.format not in (IN_I420, IN_NV12):
+            raise ValueError(f"format {format!r}: a {self.width}x{self.height} encoder (no multiple of 8) takes 8-bit i420 and nv12 pictures only")
         if roi is not None:
             if not self._roi:
                 raise RuntimeError("Encoder(..., roi=True) switches the ROI maps on")
@@ -426,7 +436,7 @@ class Encoder:
         if not self._analysis or self.h is None:
             return []
         import torch
-        w8, h8, cc, cr = self.width // 8, self.height // 8, (self.width + 63) // 64, (self.height + 63) // 64
+        w8, h8, cc, cr = (self.width + 7) // 8, (self.height + 7) // 8, (self.width + 63) // 64, (self.height + 63) // 64   # (the coded picture's blocks)
         shapes = {"mv": (torch.int16, (2, h8, w8, 2)), "ref": (torch.int8, (2, h8, w8)), "cu": (torch.uint8, (5, h8, w8)), "qp": (torch.int8, (cr, cc)), "sse": (torch.int32, (3, h8, w8))}
         info, out = Picture(), []
         while self.lib.ks265_enc_device_analysis_pending(self.h) > 0:
@@ -452,7 +462,9 @@ class Encoder:
 
     def quality(self) -> dict:
         """quality figures of the pictures handed out so far (ks265_enc_get_quality): `frames`; `sse` = summed squared error per plane (psnr=1, else None); `ssim` = per plane the
-        mean over the pictures of the reference's `-ssim` figure (ssim=1, else None); `last` = display index, SSE and SSIM of the picture accounted last"""
+        mean over the pictures of the reference's `-ssim` figure (ssim=1, else None); `last` = display index, SSE and SSIM of the picture accounted last; `psnr` = per plane
+        the PSNR over all pictures from those sums (None without psnr=1 or before the first picture; 99.0 for a zero sum, as the encoder's own lines print).  A size that is no
+        multiple of 8: SSE and PSNR count the width x height window, SSIM the coded picture"""
         if self.h is None:
             raise RuntimeError("encoder closed")
         q = Quality()
@@ -460,7 +472,10 @@ class Encoder:
         if rc != QY_OK:
             raise EncoderError("ks265_enc_get_quality", rc)
         n = max(1, q.frames)
-        return {"frames": q.frames, "sse": list(q.sse) if q.have_sse else None, "ssim": [v / n for v in q.ssim] if q.have_ssim else None,
+        import math
+        npx = [self.width * self.height, self.width * self.height // 4, self.width * self.height // 4]
+        psnr = [10.0 * math.log10(255.0 * 255.0 * npx[k] * q.frames / q.sse[k]) if q.sse[k] > 0 else 99.0 for k in range(3)] if q.have_sse and q.frames else None
+        return {"frames": q.frames, "psnr": psnr, "sse": list(q.sse) if q.have_sse else None, "ssim": [v / n for v in q.ssim] if q.have_ssim else None,
                 "last": {"poc": q.last_poc, "sse": list(q.last_sse) if q.have_sse else None, "ssim": list(q.last_ssim) if q.have_ssim else None}}
 
     def close(self) -> None:

@@ -64,6 +64,12 @@
 #pragma weak ks265_analysis_pack
 #pragma weak ks265_analysis_validate
 #pragma weak ks265_analysis_export
+/* picture sizes that are no multiple of 8 reach the padding, the crop and the window's SSE the same way: on a device library without them such a size is
+ * QY_NOTSUPPORTED at QY265EncoderOpen, with one log line, as every such size was before */
+#pragma weak ks265_input_pad_validate
+#pragma weak ks265_input_pad
+#pragma weak ks265_output_crop
+#pragma weak ks265_sse_window
 
 const char strLibQy265Version[] = "ks265enc 0.2 (MI355X pixel path + host CABAC; API of libqycodec V2.6.1.3)";
 
@@ -199,7 +205,7 @@ int QY265ConfigParse(QY265EncConfig *c, const char *name, const char *value)
     const double dv = strtod(value, &end);
     const int num_ok = end && end != value && *end == 0, iv = (int)dv;
 #define INTP(NAME, FIELD, LO, HI) if (!strcmp(name, NAME)) { if (!num_ok || iv < (LO) || iv > (HI)) return QY265_PARAM_BAD_VALUE; c->FIELD = iv; return 0; }
-    INTP("wdt", picWidth, 8, 8192) INTP("hgt", picHeight, 8, 8192) INTP("bframes", bframes, -1, 15) INTP("rc", rc, 0, 5) INTP("br", bitrateInkbps, 1, 1000000)
+    INTP("wdt", picWidth, 2, 8192) INTP("hgt", picHeight, 2, 8192) INTP("bframes", bframes, -1, 15) INTP("rc", rc, 0, 5) INTP("br", bitrateInkbps, 1, 1000000)
     INTP("qp", qp, 0, 51) INTP("crf", crf, 0, 51) INTP("iper", iIntraPeriod, -1, 100000) INTP("qpmin", qpmin, 0, 51) INTP("qpmax", qpmax, 0, 51)
     INTP("threads", threads, 0, 1024) INTP("psnr", calcPsnr, 0, 2) INTP("ssim", calcSsim, 0, 2) INTP("log", logLevel, -1, 3) INTP("lookahead", lookahead, -1, 250)
     /* rdoq (qy265enc.h:129): every preset from `fast` up resolves to 1, which this build runs as its own seam (dead zone, coefficient-group pruning, sign-data hiding); asked for BY
@@ -342,6 +348,7 @@ static void copy_shared(CopyPool *p, uint8_t *d, const uint8_t *s, size_t n)
  * pictures behind the caller.  dev / ev_up: the slot's twin on the device, uploaded when the picture is handed in (round 4), and the event behind that upload; up_sync: the twin
  * was filled by a host-synchronous copy (nothing to wait for) */
 typedef struct Input { int used, disp, key, base_qp, iper, mini4, kbps, la_what, la_p, la_buf, up_sync; long long pts; uint8_t *i420; uint8_t *dev; void *ev_up;
+                       uint8_t *raw;                      /* a ragged lane (Enc::ragged): the picture as the caller gave it, srcW x srcH, on the device - ks265_input_pad makes `dev` of it */
                        /* `roi`: the picture's record (one int32 per CTU, ks265_roi_reduce's) on the device, its pinned twin for a map in host memory, the event behind its filling */
                        int roi_has; int32_t *roi_rec, *roi_host; void *ev_roi; } Input;
 
@@ -360,6 +367,11 @@ typedef struct PixPath {
 typedef struct Enc {
     QY265EncConfig cfg;
     int W, H, log_level;
+    /* W x H is the CODED size: the caller's size rounded up to the minimum CU size (8), which is what every kernel, the lookahead, the rate control, the records and the slice
+     * writers see.  srcW x srcH is the caller's (both even); ragged = they differ: pictures come in and go out at srcW x srcH (ks265_input_pad on the way in, ks265_output_crop on
+     * the way out), the SPS carries the conformance window, PSNR counts the window.  crop_scr: the scratch picture ks265_enc_get_device_recon crops into (a ragged lane with
+     * `devrecon`: made at open); ev_crop: recorded behind the conversion that read it last, in that call's stream - the next call's crop, in whatever stream, waits for it (crop_used) */
+    int srcW, srcH, ragged; uint8_t *crop_scr; void *ev_crop; int crop_used;
     CopyPool *pool;                                       /* shared by the lanes of one handle (owned by it) */
     int me_method, hex_thr, subme, refs, use_sao, use_df, gop_b, hier;                  /* resolved tools */
     int lean_b;                                                                         /* B pictures nothing predicts from: no intra candidates, no joint refinement, no SAO (KS265_LEAN_B=0: as the others) */
@@ -630,7 +642,13 @@ static void *worker(void *arg)
             j->t_taken = now_ms();
             int err = j->ev_err;                                 /* the dispatcher saw this picture's records reach the host */
             if (!err && e->recon_fd >= 0 && j->recon) {
-                const size_t fsz = (size_t)e->W * e->H * 3 / 2;
+                const size_t fsz = (size_t)e->srcW * e->srcH * 3 / 2;
+                if (e->ragged) {                                         /* the window, as a decoder writes it */
+                    uint8_t *win = (uint8_t *)malloc(fsz);
+                    if (win) ks265_recon_crop(j->recon, e->W, e->H, e->srcW, e->srcH, win);
+                    if (!win || pwrite(e->recon_fd, win, fsz, (off_t)j->disp * (off_t)fsz) != (ssize_t)fsz) err = KS265_FAIL;
+                    free(win);
+                } else
                 if (pwrite(e->recon_fd, j->recon, fsz, (off_t)j->disp * (off_t)fsz) != (ssize_t)fsz) err = KS265_FAIL;
             }
             if (!err && e->md5 && j->recon) {
@@ -1173,6 +1191,7 @@ static int drain_picture(Enc *e, const Sub *s, ks265_ctx *on, int captured)
     ks265_ctx *cx = on ? on : p->ctx;
     const void *extra = e->cfg.calcPsnr ? p->dev_sse : NULL;
     int r = quality_pass(e, on, p->frame, s->srcp, s->out, p->dev_sse, p->dev_ssim);
+    if (!r && e->ragged && e->cfg.calcPsnr) r = ks265_sse_window(cx, p->frame, s->srcp, s->out, e->srcW, e->srcH, p->dev_sse);   /* behind the pass, on its stream: the window's sums */
     if (!r && p->dev_ssim && !captured) r = ks265_memcpy_d2h_async(cx, s->j->ssim, p->dev_ssim, 24);
     /* `hash`: CRC and checksum of the output picture (one read of it), home the same way */
     if (!r && p->dev_hash) r = on ? ks265_picture_hash_on(on, p->frame, s->out, p->dev_hash) : ks265_picture_hash(p->frame, s->out, p->dev_hash);
@@ -1521,7 +1540,7 @@ static int take_output(Enc *e, int max_in_flight, int max_pics, QY265Nal **pNals
         if (e->cfg.calcPsnr) {
             for (int k = 0; k < 3; ++k) e->st.sse[k] += (double)j->sse[k];
             if (e->cfg.calcPsnr >= 2) {
-                const double np[3] = {(double)e->W * e->H, (double)e->W * e->H / 4, (double)e->W * e->H / 4};
+                const double np[3] = {(double)e->srcW * e->srcH, (double)e->srcW * e->srcH / 4, (double)e->srcW * e->srcH / 4};
                 double ps[3];
                 for (int k = 0; k < 3; ++k) ps[k] = j->sse[k] ? 10.0 * log10(255.0 * 255.0 * np[k] / (double)j->sse[k]) : 99.0;
                 /* appencoder's -psnr 2 table: `poc slice bits psnrY psnrU psnrV qp`, tab separated, one header line */
@@ -1570,7 +1589,7 @@ static void run_summary(const Enc *e, long frames, long long bytes, const double
     if (!frames) return;
     const double kbps = bytes * 8.0 * e->cfg.frameRate / frames / 1000.0;
     if (e->cfg.calcPsnr) {
-        const double np[3] = {(double)e->W * e->H, (double)e->W * e->H / 4, (double)e->W * e->H / 4};
+        const double np[3] = {(double)e->srcW * e->srcH, (double)e->srcW * e->srcH / 4, (double)e->srcW * e->srcH / 4};
         double ps[3];
         for (int k = 0; k < 3; ++k) ps[k] = sse[k] > 0 ? 10.0 * log10(255.0 * 255.0 * np[k] * frames / sse[k]) : 99.0;
         logf_(2, e->log_level, "bitrate, psnr: %.4f\t%.4f\t%.4f\t%.4f\n", kbps, ps[0], ps[1], ps[2]);
@@ -1594,7 +1613,8 @@ static int lane_base_qp(const QY265EncConfig *cfg, int rc) { const int q = rc ==
 
 static void lane_resolve(Enc *e, const QY265EncConfig *cfg, int device, int multi)
 {
-    e->cfg = *cfg; e->W = cfg->picWidth; e->H = cfg->picHeight; e->log_level = cfg->logLevel;
+    e->cfg = *cfg; e->log_level = cfg->logLevel;
+    e->srcW = cfg->picWidth; e->srcH = cfg->picHeight; e->W = (e->srcW + 7) & ~7; e->H = (e->srcH + 7) & ~7; e->ragged = e->W != e->srcW || e->H != e->srcH;
     e->me_method = cfg->me < 0 ? 1 : cfg->me > 2 ? 2 : cfg->me;        /* EPZS / Cross (-me 3 / 4) are not built: UMH instead */
     e->hex_thr = (e->me_method == 2 && (cfg->preset == QY265PRESET_SLOW || cfg->preset == QY265PRESET_SLOWER)) ? 16 : 0;   /* tME+0x368, SURVEY-measured */
     e->subme = cfg->subme < 0 ? 1 : cfg->subme > 2 ? 2 : cfg->subme;      /* 0 off, 1 fast, 2 square full (qy265enc.h:137): the reference's refinement, ks265_frame_cfg.subme */
@@ -1785,6 +1805,7 @@ static void lane_resolve(Enc *e, const QY265EncConfig *cfg, int device, int mult
     /* the stream's parameter sets */
     memset(&e->scfg, 0, sizeof e->scfg);
     e->scfg.width = e->W; e->scfg.height = e->H; e->scfg.sao = e->use_sao; e->scfg.deblock = e->use_df;
+    e->scfg.crop_right = e->W - e->srcW; e->scfg.crop_bottom = e->H - e->srcH;   /* the conformance window of a ragged size (0, 0 otherwise: the SPS as it always was) */
     e->scfg.sdh = e->fcfg.sdh;
     e->zero_latency = cfg->latency == QY265LATENCY_ZERO && e->gop_b == 0 && !e->la_on && !multi;
     e->scfg.cu_qp_delta = e->qmap_on;
@@ -2090,12 +2111,14 @@ static int open_inputs(Enc *e)
      * analysis would see the picture 10 ms and more late); without it the picture is uploaded when it is scheduled, on the copy-in stream, as before.  One stream for both,
      * not a sixth: a stream more is a hardware queue shared with somebody (lane_open) */
     open_upl_stream(e, 2);
-    if ((e->la_on && e->ctx_la) || e->direct_in) {
+    if ((e->la_on && e->ctx_la) || e->direct_in || e->ragged) {        /* (ragged: the padded picture exists on the device only - every consumer reads the twin) */
         e->ctx_up = e->direct_in == 1 && e->ctx_upl ? e->ctx_upl : e->ctx_la ? e->ctx_la : main_ctx(e);
         reg_handle(main_ctx(e), 1);
         for (int i = 0; i < e->nin && !r; ++i) { r = ks265_dev_malloc(main_ctx(e), (void **)&e->in[i].dev, fsz); if (!r) r = ks265_event_create(e->ctx_up, &e->in[i].ev_up); }
         logf_(2, e->log_level, "ks265enc: %d input slots with a device twin each: %.2f GB of device memory per lane (KS265_INPUT_SLOTS / KS265_PINNED_MB bound the slot count)\n", e->nin, e->nin * (double)fsz / 1073741824.0);
     }
+    if (e->ragged)                                                      /* every slot: the staging area of the picture as it came */
+        for (int i = 0; i < e->nin && !r; ++i) r = ks265_dev_malloc(main_ctx(e), (void **)&e->in[i].raw, (size_t)e->srcW * e->srcH * 3 / 2);
     if (e->roi_on) {                                                    /* every slot: the picture's record on the device, its pinned twin, the event behind its filling - on the upload stream there is, no stream more */
         const size_t nb = (size_t)e->geom.ctu_cols * e->geom.ctu_rows * sizeof(int32_t);
         if (!e->ctx_up) { e->ctx_up = e->ctx_la ? e->ctx_la : main_ctx(e); reg_handle(main_ctx(e), 1); }
@@ -2110,6 +2133,7 @@ static int open_inputs(Enc *e)
 static void close_inputs(Enc *e)                                       /* (also what lane_enable_device_input added: twins, their events, the handle's count) */
 {
     for (int i = 0; i < MAX_INPUT; ++i) { ks265_host_free(main_ctx(e), e->in[i].i420); ks265_dev_free(main_ctx(e), e->in[i].dev); ev_free(e->ctx_up, &e->in[i].ev_up);
+                                          if (e->in[i].raw) ks265_dev_free(main_ctx(e), e->in[i].raw);
                                           ks265_dev_free(main_ctx(e), e->in[i].roi_rec); ks265_host_free(main_ctx(e), e->in[i].roi_host); ev_free(e->ctx_up, &e->in[i].ev_roi); }
 }
 static void close_input_streams(Enc *e)                                /* behind the lookahead (ctx_up may be its stream) */
@@ -2162,6 +2186,10 @@ static int open_devrecon(Enc *e)
         if (!r && e->analysis) r = ks265_dev_malloc(main_ctx(e), (void **)&e->rslot[i].an, asz);
         if (!r && e->analysis) r = ks265_event_create(main_ctx(e), &e->rslot[i].ev_read_an);
     }
+    if (!r && e->devrecon && e->ragged) {                               /* the window of a ragged lane's pictures: one scratch picture of the caller's size and the event that guards it */
+        r = ks265_dev_malloc(main_ctx(e), (void **)&e->crop_scr, (size_t)e->srcW * e->srcH * 3 / 2);
+        if (!r) r = ks265_event_create(main_ctx(e), &e->ev_crop);
+    }
     if (e->devrecon)
         logf_(1, e->log_level, "ks265enc: device reconstruction: a pool of %d packed I420 pictures, %.1f MB of device memory per lane (the ring of %d pictures in flight%s)\n", e->rpool.n,
               e->rpool.n * (double)fsz / 1048576.0, e->ring, e->multi ? " + a GOP in the stash" : "");
@@ -2176,6 +2204,9 @@ static void close_devrecon(Enc *e)                                     /* a conv
     for (int i = 0; i < RECON_POOL_MAX; ++i) if (e->rslot[i].read_on_an) (void)ks265_event_wait(main_ctx(e), e->rslot[i].ev_read_an);
     for (int i = 0; i < RECON_POOL_MAX; ++i) { ks265_dev_free(main_ctx(e), e->rslot[i].dev); ev_free(main_ctx(e), &e->rslot[i].ev_packed); ev_free(main_ctx(e), &e->rslot[i].ev_read); }
     for (int i = 0; i < RECON_POOL_MAX; ++i) { ks265_dev_free(main_ctx(e), e->rslot[i].an); ev_free(main_ctx(e), &e->rslot[i].ev_read_an); }
+    if (e->crop_used) (void)ks265_event_wait(main_ctx(e), e->ev_crop);
+    if (e->crop_scr) { ks265_dev_free(main_ctx(e), e->crop_scr); e->crop_scr = NULL; }
+    if (e->ev_crop) ev_free(main_ctx(e), &e->ev_crop);
     recon_list_free(&e->taken);
 }
 
@@ -2243,7 +2274,14 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
     int dummy; if (!err) err = &dummy;
     *err = QY_OK;
     if (!cfg) { *err = QY_POINTER; return NULL; }
-    if (cfg->picWidth <= 0 || cfg->picHeight <= 0 || (cfg->picWidth & 7) || (cfg->picHeight & 7) || cfg->frameRate <= 0 || cfg->rc < 0 || cfg->rc > 5 || cfg->bframes > GOP_MAX_B) { *err = QY_NOTSUPPORTED; return NULL; }
+    if ((cfg->picWidth & 7) || (cfg->picHeight & 7)) {                  /* a ragged size: even, and the device library has the three entries of picture_window.hip */
+        if (cfg->picWidth <= 0 || cfg->picHeight <= 0 || (cfg->picWidth & 1) || (cfg->picHeight & 1) || cfg->picWidth > 8192 || cfg->picHeight > 8192) { *err = QY_NOTSUPPORTED; return NULL; }
+        if (!ks265_input_pad || !ks265_input_pad_validate || !ks265_output_crop || !ks265_sse_window) {
+            logf_(2, cfg->logLevel, "ks265enc: %dx%d is no multiple of 8 and the device library has no ks265_input_pad\n", cfg->picWidth, cfg->picHeight);
+            *err = QY_NOTSUPPORTED; return NULL;
+        }
+    }
+    if (cfg->picWidth <= 0 || cfg->picHeight <= 0 || (cfg->picWidth & 1) || (cfg->picHeight & 1) || cfg->frameRate <= 0 || cfg->rc < 0 || cfg->rc > 5 || cfg->bframes > GOP_MAX_B) { *err = QY_NOTSUPPORTED; return NULL; }
     Enc *e = (Enc *)calloc(1, sizeof *e);
     if (e) { e->recon_fd = -1; e->qmap_fd = -1; }
     if (!e) { *err = QY_OUTOFMEMORY; return NULL; }
@@ -2322,9 +2360,9 @@ static int lane_acquire(Enc *e, QY265YUV *yuv)
     if (slot) slot->used = 4;
     pthread_mutex_unlock(&e->mu);
     if (!slot) return QY_FAIL;
-    yuv->iWidth = e->W; yuv->iHeight = e->H;
-    yuv->pData[0] = slot->i420; yuv->pData[1] = slot->i420 + (size_t)e->W * e->H; yuv->pData[2] = yuv->pData[1] + (size_t)e->W * e->H / 4;
-    yuv->iStride[0] = e->W; yuv->iStride[1] = e->W / 2; yuv->iStride[2] = e->W / 2;
+    yuv->iWidth = e->srcW; yuv->iHeight = e->srcH;                     /* (the caller's size: the coded one unless the lane is ragged) */
+    yuv->pData[0] = slot->i420; yuv->pData[1] = slot->i420 + (size_t)e->srcW * e->srcH; yuv->pData[2] = yuv->pData[1] + (size_t)e->srcW * e->srcH / 4;
+    yuv->iStride[0] = e->srcW; yuv->iStride[1] = e->srcW / 2; yuv->iStride[2] = e->srcW / 2;
     return QY_OK;
 }
 
@@ -2518,9 +2556,23 @@ static void reg_handle(ks265_ctx *c, int open)
 static void dev_desc(const Enc *e, const ks265_dev_picture *p, ks265_in_desc *d)
 {
     memset(d, 0, sizeof *d);
-    d->format = p->format; d->width = e->W; d->height = e->H;
+    d->format = p->format; d->width = e->srcW; d->height = e->srcH;    /* (the caller's size: the coded one unless the lane is ragged) */
     for (int k = 0; k < 3; ++k) { d->plane[k] = p->plane[k]; d->pitch[k] = p->pitch[k]; }
     d->pixel_step = p->pixel_step; d->matrix = p->matrix; d->full_range = p->full_range;
+}
+
+/* a ragged lane: the picture that lies (or, on ctx_up, is on its way) in the slot's staging area becomes the slot's twin of the coded size, and ev_up is recorded behind that */
+static int lane_pad_slot(Enc *e, Input *slot)
+{
+    const size_t ny = (size_t)e->srcW * e->srcH;
+    ks265_in_desc d;
+    memset(&d, 0, sizeof d);
+    d.format = KS265_IN_I420; d.width = e->srcW; d.height = e->srcH;
+    d.plane[0] = slot->raw; d.plane[1] = slot->raw + ny; d.plane[2] = slot->raw + ny + ny / 4;
+    d.pitch[0] = e->srcW; d.pitch[1] = d.pitch[2] = e->srcW / 2;
+    int r = ks265_input_pad(e->ctx_up, &d, e->W, e->H, slot->dev);
+    if (!r) r = ks265_event_record(e->ctx_up, slot->ev_up);
+    return r;
 }
 
 /* one picture into the lane - a host picture (yuv: copied to a pinned slot or uploaded from where it lies) or a device picture (dp, validated by the caller: converted into the
@@ -2528,7 +2580,8 @@ static void dev_desc(const Enc *e, const ks265_dev_picture *p, ks265_in_desc *d)
 static int lane_put(Enc *e, const QY265YUV *yuv, const ks265_dev_picture *dp, const struct ScalePlan *sc, const ks265_roi *roi, long long pts, int key)
 {
     if (!dp && (!yuv || !yuv->pData[0] || !yuv->pData[1] || !yuv->pData[2])) return QY_POINTER;
-    if (!dp && (yuv->iWidth != e->W || yuv->iHeight != e->H)) return QY_NOTSUPPORTED;
+    if (!dp && (yuv->iWidth != e->srcW || yuv->iHeight != e->srcH)) return QY_NOTSUPPORTED;
+    const int sw = e->srcW, sh = e->srcH;                               /* the caller's size: W x H unless the lane is ragged */
     Input *slot = NULL;
     const double tc0 = now_ms();
     pthread_mutex_lock(&e->mu);
@@ -2546,18 +2599,19 @@ static int lane_put(Enc *e, const QY265YUV *yuv, const ks265_dev_picture *dp, co
     if (slot) { slot->used = 3; slot->up_sync = 0; slot->roi_has = 0; }   /* being filled */
     pthread_mutex_unlock(&e->mu);
     if (!slot) return QY_FAIL;                                         /* one lane: cannot happen (more input slots than pictures in flight + one mini-GOP); lanes: the caller checked lane_has_slot */
-    uint8_t *u = slot->i420 + (size_t)e->W * e->H, *v = u + (size_t)e->W * e->H / 4;
+    uint8_t *u = slot->i420 + (size_t)sw * sh, *v = u + (size_t)sw * sh / 4;
+    uint8_t *const up = e->ragged ? slot->raw : slot->dev;              /* where an upload goes: a ragged lane's staging area, ks265_input_pad behind it */
     int direct = 0;
     if (roi && e->roi_on) {                                            /* (validated by ks265_enc_set_next_roi) the map becomes the slot's record on ctx_up, beside the picture's own way in */
         int ru;
         if (roi->device >= 0) {                                        /* the caller's stream -> ctx_up: the reduction -> ev_roi -> the caller's stream waits for it */
-            const ks265_roi_desc d = {roi->type, roi->log2_block, ks265_roi_map_cols(e->W, roi->log2_block), ks265_roi_map_rows(e->H, roi->log2_block), roi->data, roi->pitch};
+            const ks265_roi_desc d = {roi->type, roi->log2_block, ks265_roi_map_cols(sw, roi->log2_block), ks265_roi_map_rows(sh, roi->log2_block), roi->data, roi->pitch};
             ru = ks265_wait_external(e->ctx_up, roi->stream);
-            if (!ru) ru = ks265_roi_reduce(e->ctx_up, &d, e->W, e->H, slot->roi_rec);
+            if (!ru) ru = ks265_roi_reduce(e->ctx_up, &d, sw, sh, slot->roi_rec);   /* (a map describes the caller's picture; the CTU grid is the coded picture's) */
             if (!ru) ru = ks265_event_record(e->ctx_up, slot->ev_roi);
             if (!ru) ru = ks265_external_wait_event(e->ctx_up, roi->stream, slot->ev_roi);
         } else {                                                       /* host memory: reduced here, on the calling thread (ks265_roi.h); the record is uploaded */
-            ru = ks265_roi_reduce_host(roi->type, roi->log2_block, roi->data, roi->pitch, e->W, e->H, slot->roi_host) ? KS265_NOTSUPPORTED : KS265_OK;
+            ru = ks265_roi_reduce_host(roi->type, roi->log2_block, roi->data, roi->pitch, sw, sh, slot->roi_host) ? KS265_NOTSUPPORTED : KS265_OK;
             if (!ru) ru = ks265_memcpy_h2d_async(e->ctx_up, slot->roi_rec, slot->roi_host, (size_t)e->geom.ctu_cols * e->geom.ctu_rows * sizeof(int32_t));
             if (!ru) ru = ks265_event_record(e->ctx_up, slot->ev_roi);
         }
@@ -2569,25 +2623,26 @@ static int lane_put(Enc *e, const QY265YUV *yuv, const ks265_dev_picture *dp, co
         dev_desc(e, dp, &d);
         if (sc) { d.width = sc->sw; d.height = sc->sh; }                /* a picture of another size: scaled into the twin, in the same place between the same two events */
         int ru = ks265_wait_external(e->ctx_up, dp->stream);
-        if (!ru) ru = sc ? ks265_input_scale(e->ctx_up, sc->plan, &d, e->sc_scratch, slot->dev) : ks265_input_convert(e->ctx_up, &d, slot->dev);
+        if (!ru) ru = sc ? ks265_input_scale(e->ctx_up, sc->plan, &d, e->sc_scratch, slot->dev) : e->ragged ? ks265_input_pad(e->ctx_up, &d, e->W, e->H, slot->dev) : ks265_input_convert(e->ctx_up, &d, slot->dev);
         if (!ru) ru = ks265_event_record(e->ctx_up, slot->ev_up);
         if (!ru) ru = ks265_external_wait_event(e->ctx_up, dp->stream, slot->ev_up);
         if (ru) { pthread_mutex_lock(&e->mu); slot->used = 0; e->sched_err = hip_rc(ru); pthread_mutex_unlock(&e->mu); return hip_rc(ru); }
         direct = 1;
-    } else if (e->direct_in && !own && slot->dev && yuv->iStride[0] == e->W && yuv->iStride[1] == e->W / 2 && yuv->iStride[2] == e->W / 2) {
-        const size_t ny = (size_t)e->W * e->H, nc = ny / 4;
+    } else if (e->direct_in && !own && slot->dev && yuv->iStride[0] == sw && yuv->iStride[1] == sw / 2 && yuv->iStride[2] == sw / 2) {
+        const size_t ny = (size_t)sw * sh, nc = ny / 4;
         uint8_t *p0 = yuv->pData[0], *p1 = yuv->pData[1], *p2 = yuv->pData[2];
         const int whole = p1 == p0 + ny && p2 == p1 + nc, evict = !e->hold_in;      /* (hold: an old registration may still be read by a DMA in flight - then the table only grows) */
         int ru = KS265_OK;
         if (whole ? reg_get(e->ctx_up, p0, ny + 2 * nc, evict) : (reg_get(e->ctx_up, p0, ny, evict) && reg_get(e->ctx_up, p1, nc, evict) && reg_get(e->ctx_up, p2, nc, evict))) {
             if (e->direct_in == 2) {                                    /* no stream: the call returns when the picture is on the device */
-                if (whole) ru = ks265_memcpy_h2d_sync(main_ctx(e), slot->dev, p0, ny + 2 * nc);
-                else { ru = ks265_memcpy_h2d_sync(main_ctx(e), slot->dev, p0, ny); if (!ru) ru = ks265_memcpy_h2d_sync(main_ctx(e), slot->dev + ny, p1, nc); if (!ru) ru = ks265_memcpy_h2d_sync(main_ctx(e), slot->dev + ny + nc, p2, nc); }
-                slot->up_sync = 1;
+                if (whole) ru = ks265_memcpy_h2d_sync(main_ctx(e), up, p0, ny + 2 * nc);
+                else { ru = ks265_memcpy_h2d_sync(main_ctx(e), up, p0, ny); if (!ru) ru = ks265_memcpy_h2d_sync(main_ctx(e), up + ny, p1, nc); if (!ru) ru = ks265_memcpy_h2d_sync(main_ctx(e), up + ny + nc, p2, nc); }
+                if (!e->ragged) slot->up_sync = 1;
+                else if (!ru) ru = lane_pad_slot(e, slot);              /* the twin is made on ctx_up: its readers wait for ev_up as after any other upload */
             } else {
-            if (whole) ru = ks265_memcpy_h2d_async(e->ctx_up, slot->dev, p0, ny + 2 * nc);
-            else { ru = ks265_memcpy_h2d_async(e->ctx_up, slot->dev, p0, ny); if (!ru) ru = ks265_memcpy_h2d_async(e->ctx_up, slot->dev + ny, p1, nc); if (!ru) ru = ks265_memcpy_h2d_async(e->ctx_up, slot->dev + ny + nc, p2, nc); }
-            if (!ru) ru = ks265_event_record(e->ctx_up, slot->ev_up);
+            if (whole) ru = ks265_memcpy_h2d_async(e->ctx_up, up, p0, ny + 2 * nc);
+            else { ru = ks265_memcpy_h2d_async(e->ctx_up, up, p0, ny); if (!ru) ru = ks265_memcpy_h2d_async(e->ctx_up, up + ny, p1, nc); if (!ru) ru = ks265_memcpy_h2d_async(e->ctx_up, up + ny + nc, p2, nc); }
+            if (!ru) ru = e->ragged ? lane_pad_slot(e, slot) : ks265_event_record(e->ctx_up, slot->ev_up);
             if (!e->hold_in) e->pending_up = slot;                      /* waited for at the end of the call, behind the output's hand-over */
             }
             if (ru) { e->pending_up = NULL; pthread_mutex_lock(&e->mu); slot->used = 0; e->sched_err = hip_rc(ru); pthread_mutex_unlock(&e->mu); return hip_rc(ru); }
@@ -2596,20 +2651,20 @@ static int lane_put(Enc *e, const QY265YUV *yuv, const ks265_dev_picture *dp, co
     }
     if (direct) { /* on its way from the caller's own memory (host: DMA; device: the conversion) */ }
     else if (own) { /* in place */ }
-    else if (yuv->iStride[0] == e->W && yuv->iStride[1] == e->W / 2 && yuv->iStride[2] == e->W / 2) {    /* packed planes: three block copies */
-        copy_shared(e->pool, slot->i420, yuv->pData[0], (size_t)e->W * e->H);
-        copy_shared(e->pool, u, yuv->pData[1], (size_t)e->W * e->H / 4);
-        copy_shared(e->pool, v, yuv->pData[2], (size_t)e->W * e->H / 4);
+    else if (yuv->iStride[0] == sw && yuv->iStride[1] == sw / 2 && yuv->iStride[2] == sw / 2) {    /* packed planes: three block copies */
+        copy_shared(e->pool, slot->i420, yuv->pData[0], (size_t)sw * sh);
+        copy_shared(e->pool, u, yuv->pData[1], (size_t)sw * sh / 4);
+        copy_shared(e->pool, v, yuv->pData[2], (size_t)sw * sh / 4);
     } else {
-        for (int y = 0; y < e->H; ++y) memcpy(slot->i420 + (size_t)y * e->W, yuv->pData[0] + (size_t)y * yuv->iStride[0], (size_t)e->W);
-        for (int y = 0; y < e->H / 2; ++y) {
-            memcpy(u + (size_t)y * (e->W / 2), yuv->pData[1] + (size_t)y * yuv->iStride[1], (size_t)e->W / 2);
-            memcpy(v + (size_t)y * (e->W / 2), yuv->pData[2] + (size_t)y * yuv->iStride[2], (size_t)e->W / 2);
+        for (int y = 0; y < sh; ++y) memcpy(slot->i420 + (size_t)y * sw, yuv->pData[0] + (size_t)y * yuv->iStride[0], (size_t)sw);
+        for (int y = 0; y < sh / 2; ++y) {
+            memcpy(u + (size_t)y * (sw / 2), yuv->pData[1] + (size_t)y * yuv->iStride[1], (size_t)sw / 2);
+            memcpy(v + (size_t)y * (sw / 2), yuv->pData[2] + (size_t)y * yuv->iStride[2], (size_t)sw / 2);
         }
     }
     if (slot->dev && !direct) {   /* on its way to the device at once, on the lookahead's stream (nothing there waits for the pipeline) */
-        int ru = ks265_memcpy_h2d_async(e->ctx_up, slot->dev, slot->i420, (size_t)e->W * e->H * 3 / 2);
-        if (!ru) ru = ks265_event_record(e->ctx_up, slot->ev_up);
+        int ru = ks265_memcpy_h2d_async(e->ctx_up, up, slot->i420, (size_t)sw * sh * 3 / 2);
+        if (!ru) ru = e->ragged ? lane_pad_slot(e, slot) : ks265_event_record(e->ctx_up, slot->ev_up);
         if (ru) { pthread_mutex_lock(&e->mu); slot->used = 0; e->sched_err = hip_rc(ru); pthread_mutex_unlock(&e->mu); return hip_rc(ru); }
     }
     /* the picture's own fields travel with it from now; with the lookahead it becomes visible to the scheduler when its results are there (la_drain) */
@@ -3239,7 +3294,8 @@ int ks265_enc_encode_device_frame(void *h, QY265Nal **pNals, int *iNalCount, con
     const double t0 = now_ms();
     ks265_in_desc d;
     dev_desc(e0, pic, &d);
-    const int rv = ks265_input_validate(main_ctx(e0), &d);
+    if (e0->ragged && d.format != KS265_IN_I420 && d.format != KS265_IN_NV12) return QY_NOTSUPPORTED;   /* a ragged handle pads 8-bit I420 and NV12 only (ks265_enc.h) */
+    const int rv = e0->ragged ? ks265_input_pad_validate(main_ctx(e0), &d, e0->W, e0->H) : ks265_input_validate(main_ctx(e0), &d);
     e0->st.in_copy_ms += now_ms() - t0;
     if (rv) return hip_rc(rv);
     return top_encode(t, pNals, iNalCount, NULL, pic, NULL, out);
@@ -3275,7 +3331,7 @@ int ks265_enc_enable_device_scale(void *h, int max_src_width, int max_src_height
         return QY_NOTSUPPORTED;
     }
     if (max_src_width <= 0 || max_src_height <= 0 || (max_src_width & 7) || (max_src_height & 1) || max_src_width > KS_SCALE_MAX_DIM || max_src_height > KS_SCALE_MAX_DIM
-        || max_src_width > KS_SCALE_MAX_RATIO * e0->W || max_src_height > KS_SCALE_MAX_RATIO * e0->H || (e0->W & 7) || (e0->H & 7)) return QY_NOTSUPPORTED;
+        || max_src_width > KS_SCALE_MAX_RATIO * e0->W || max_src_height > KS_SCALE_MAX_RATIO * e0->H || (e0->W & 7) || (e0->H & 7) || e0->ragged) return QY_NOTSUPPORTED;
     if (e0->sc_on) return e0->sc_max_w == max_src_width && e0->sc_max_h == max_src_height ? QY_OK : QY_NOTSUPPORTED;
     for (int i = 0; i < t->nlanes; ++i) {
         Enc *e = t->lane[i];
@@ -3292,6 +3348,7 @@ int ks265_enc_encode_device_frame_scaled(void *h, QY265Nal **pNals, int *iNalCou
     Top *t = (Top *)h;
     if (!t || !pNals || !iNalCount || !pic) return QY_POINTER;
     Enc *e0 = t->lane[0];
+    if (e0->ragged) { *iNalCount = 0; return QY_NOTSUPPORTED; }         /* the scaler writes coded sizes only (ks265_enc.h) */
     if (src_width == e0->W && src_height == e0->H) return ks265_enc_encode_device_frame(h, pNals, iNalCount, pic, out);
     *iNalCount = 0;
     if (!e0->sc_on || pic->device != e0->dev_id) return QY_NOTSUPPORTED;
@@ -3319,10 +3376,10 @@ int ks265_enc_set_next_roi(void *h, const ks265_roi *roi)
     Enc *e0 = t->lane[0];
     if (!e0->roi_on) return QY_NOTSUPPORTED;
     if (roi->device != -1 && roi->device != e0->dev_id) return QY_NOTSUPPORTED;
-    if (ks265_roi_check(roi->type, roi->log2_block, roi->pitch, e0->W, e0->H)) return QY_NOTSUPPORTED;
+    if (ks265_roi_check(roi->type, roi->log2_block, roi->pitch, e0->srcW, e0->srcH)) return QY_NOTSUPPORTED;
     if (!roi->data) return QY_POINTER;
     if (roi->device >= 0) {                                             /* the whole map is checked before anything of it is enqueued */
-        const ks265_roi_desc d = {roi->type, roi->log2_block, ks265_roi_map_cols(e0->W, roi->log2_block), ks265_roi_map_rows(e0->H, roi->log2_block), roi->data, roi->pitch};
+        const ks265_roi_desc d = {roi->type, roi->log2_block, ks265_roi_map_cols(e0->srcW, roi->log2_block), ks265_roi_map_rows(e0->srcH, roi->log2_block), roi->data, roi->pitch};
         const int rv = ks265_roi_validate(main_ctx(e0), &d);
         if (rv) return hip_rc(rv);
     }
@@ -3355,7 +3412,12 @@ int ks265_enc_get_device_recon(void *h, const ks265_dev_picture *dst, QY265Pictu
     /* the conversion runs IN the caller's stream - behind everything enqueued there before the call, in front of everything enqueued after it - once that stream has waited for the
      * picture's pack; ev_read behind it is what the slot's next pack waits for */
     r = ks265_stream_wait_event(e->ctx_rec, q->ev_packed);
-    if (!r) r = ks265_output_convert(e->ctx_rec, q->dev, &d);
+    /* a ragged lane: the window first, into the lane's scratch picture, in the same stream - which may be another stream than the last call's: this crop waits for the conversion that
+     * read the scratch picture last (ev_crop), as the slot's next pack waits for ev_read */
+    if (!r && e->ragged && e->crop_used) r = ks265_stream_wait_event(e->ctx_rec, e->ev_crop);
+    if (!r && e->ragged) r = ks265_output_crop(e->ctx_rec, q->dev, e->W, e->H, e->srcW, e->srcH, e->crop_scr);
+    if (!r) r = ks265_output_convert(e->ctx_rec, e->ragged ? e->crop_scr : q->dev, &d);
+    if (!r && e->ragged) { r = ks265_event_record(e->ctx_rec, e->ev_crop); if (!r) e->crop_used = 1; }
     if (!r) r = ks265_event_record(e->ctx_rec, q->ev_read);
     if (!r) q->read_on = 1;                                             /* (read by the scheduler thread when it takes the slot again: after this call's successor released it, under mu) */
     if (r) return hip_rc(r);

@@ -10,6 +10,7 @@
  * Every transition checks the state it leaves: a slot is never taken twice, handed out twice or released while a picture still travels with it. */
 #ifndef KS265_RECON_H
 #define KS265_RECON_H
+#include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -91,6 +92,16 @@ static inline int recon_list_move(ReconList *dst, ReconList *src)
     for (int i = 0; i < src->n; ++i) if (recon_list_push(dst, &src->v[i])) return -1;
     recon_list_clear(src);
     return 0;
+}
+
+/* a ragged size's dump (-o / ks265_enc_set_recon_file): the top-left w x h of a packed I420 picture of cw x ch, packed - what a decoder writes for the stream's conformance window */
+static inline void ks265_recon_crop(const uint8_t *src, int cw, int ch, int w, int h, uint8_t *dst)
+{
+    for (int p = 0; p < 3; ++p) {
+        const int s = p ? 2 : 1;
+        for (int y = 0; y < h / s; ++y) memcpy(dst + (size_t)y * (w / s), src + (size_t)y * (cw / s), (size_t)(w / s));
+        src += (size_t)(cw / s) * (ch / s); dst += (size_t)(w / s) * (h / s);
+    }
 }
 
 #endif

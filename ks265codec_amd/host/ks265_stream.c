@@ -108,7 +108,8 @@ long ks265_write_vps(const ks265_stream_cfg *cfg, uint8_t *out, size_t cap)
 static int cfg_ok(const ks265_stream_cfg *c)
 {
     return c->width > 0 && c->height > 0 && !(c->width & 7) && !(c->height & 7) && c->width <= 8192 && c->height <= 8192 && c->max_dec_pic_buffering >= 1 &&
-           c->max_dec_pic_buffering <= 16 && c->max_num_reorder >= 0 && c->max_num_reorder < c->max_dec_pic_buffering && c->log2_max_poc_lsb >= 4 && c->log2_max_poc_lsb <= 16;
+           c->max_dec_pic_buffering <= 16 && c->max_num_reorder >= 0 && c->max_num_reorder < c->max_dec_pic_buffering && c->log2_max_poc_lsb >= 4 && c->log2_max_poc_lsb <= 16 &&
+           !(c->crop_right & ~6) && !(c->crop_bottom & ~6);       /* 0, 2, 4 or 6 luma samples: less than the minimum CU, even (chroma units) */
 }
 
 long ks265_write_sps(const ks265_stream_cfg *cfg, uint8_t *out, size_t cap)
@@ -125,7 +126,12 @@ long ks265_write_sps(const ks265_stream_cfg *cfg, uint8_t *out, size_t cap)
     bw_ue(&b, 1);                        /* chroma_format_idc = 4:2:0 */
     bw_ue(&b, (uint32_t)cfg->width);
     bw_ue(&b, (uint32_t)cfg->height);
-    bw_put(&b, 0, 1);                    /* conformance_window_flag */
+    if (cfg->crop_right | cfg->crop_bottom) {
+        bw_put(&b, 1, 1);                /* conformance_window_flag: the source picture is the top-left corner of the coded one */
+        bw_ue(&b, 0); bw_ue(&b, (uint32_t)cfg->crop_right / 2);     /* conf_win_left_offset, conf_win_right_offset (chroma units: SubWidthC = 2) */
+        bw_ue(&b, 0); bw_ue(&b, (uint32_t)cfg->crop_bottom / 2);    /* conf_win_top_offset, conf_win_bottom_offset (SubHeightC = 2) */
+    } else
+        bw_put(&b, 0, 1);                /* conformance_window_flag */
     bw_ue(&b, 0); bw_ue(&b, 0);          /* bit_depth_luma_minus8, bit_depth_chroma_minus8 */
     bw_ue(&b, (uint32_t)(cfg->log2_max_poc_lsb - 4));
     bw_put(&b, 1, 1);                    /* sps_sub_layer_ordering_info_present_flag */

@@ -62,7 +62,7 @@ ANALYSIS_FIELDS = ("mv", "ref", "cu", "qp", "sse")
 
 def analysis_shapes(width: int, height: int) -> dict:
     """field -> (torch dtype name, shape) of a width x height picture's analysis (include/ks265_hip.h)"""
-    w8, h8, cc, cr = width // 8, height // 8, (width + 63) // 64, (height + 63) // 64
+    w8, h8, cc, cr = (width + 7) // 8, (height + 7) // 8, (width + 63) // 64, (height + 63) // 64
     return {"mv": ("int16", (2, h8, w8, 2)), "ref": ("int8", (2, h8, w8)), "cu": ("uint8", (5, h8, w8)), "qp": ("int8", (cr, cc)), "sse": ("int32", (3, h8, w8))}
 
 
@@ -118,6 +118,7 @@ EXPORTS = [
     "ks265_roi_validate", "ks265_roi_reduce", "ks265_roi_ctu_map",
     "ks265_scale_plan_create", "ks265_scale_plan_destroy", "ks265_input_scale_validate", "ks265_input_scale",
     "ks265_analysis_layout", "ks265_analysis_bytes", "ks265_analysis_pack", "ks265_analysis_pack_on", "ks265_analysis_validate", "ks265_analysis_export",
+    "ks265_input_pad_validate", "ks265_input_pad", "ks265_output_crop", "ks265_sse_window",
 ]
 
 

@@ -22,7 +22,8 @@ HASH_CRC, HASH_CHECKSUM = 1, 2                                        # hash_typ
 
 class StreamCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("width", "height", "fps_num", "fps_den", "sao", "deblock", "beta_offset_div2", "tc_offset_div2",
-                                          "max_dec_pic_buffering", "max_num_reorder", "log2_max_poc_lsb", "sdh", "wpp", "list_mod", "cu_qp_delta", "tu_inter")]
+                                          "max_dec_pic_buffering", "max_num_reorder", "log2_max_poc_lsb", "sdh", "wpp", "list_mod", "cu_qp_delta", "tu_inter",
+                                          "crop_right", "crop_bottom")]       # the conformance window in luma samples (default 0: none)
 
 
 class SliceIn(C.Structure):
@@ -76,9 +77,11 @@ class StreamWriter:
     """Annex-B HEVC stream from per-picture records (host numpy arrays with the dtypes of ks265codec_amd.lib)."""
 
     def __init__(self, width: int, height: int, sao: int = 1, deblock: int = 1, beta_offset_div2: int = 0, tc_offset_div2: int = 0,
-                 max_dec_pic_buffering: int = 2, max_num_reorder: int = 0, sdh: int = 0, wpp: int = 0, list_mod: int = 0, cu_qp_delta: int = 0, tu_inter: int = 0):
+                 max_dec_pic_buffering: int = 2, max_num_reorder: int = 0, sdh: int = 0, wpp: int = 0, list_mod: int = 0, cu_qp_delta: int = 0, tu_inter: int = 0,
+                 crop_right: int = 0, crop_bottom: int = 0):
         self.l = lib()
-        self.cfg = StreamCfg(width, height, 0, 0, sao, deblock, beta_offset_div2, tc_offset_div2, max_dec_pic_buffering, max_num_reorder, 16, sdh, wpp, list_mod, cu_qp_delta, tu_inter)
+        self.cfg = StreamCfg(width, height, 0, 0, sao, deblock, beta_offset_div2, tc_offset_div2, max_dec_pic_buffering, max_num_reorder, 16, sdh, wpp, list_mod, cu_qp_delta, tu_inter,
+                             crop_right, crop_bottom)
         self.scratch = np.zeros(self.l.ks265_slice_scratch_bytes(C.byref(self.cfg)), np.uint8)
         self.out = np.zeros(width * height * 4 + 65536, np.uint8)
 
