@@ -347,6 +347,16 @@ static void copy_shared(CopyPool *p, uint8_t *d, const uint8_t *s, size_t n)
  * QP in force when the picture was handed in (QY265EncoderReconfig) - iper: the key period in force then - all three travel WITH the picture: the scheduler thread may be several
  * pictures behind the caller.  dev / ev_up: the slot's twin on the device, uploaded when the picture is handed in (round 4), and the event behind that upload; up_sync: the twin
  * was filled by a host-synchronous copy (nothing to wait for) */
+/* Input::used, the slot's state.  Every move is made under Enc::mu (the numbers stay: 1 and 2 are what the pictures waiting and in flight are counted by):
+ *   IN_FREE -> IN_ACQUIRED                the calling thread (lane_acquire): the caller writes its next picture into the slot's pinned memory; acquired again, it is the same slot
+ *   IN_FREE / IN_ACQUIRED -> IN_FILLING   the calling thread (take_input_slot): the picture is on its way into the slot and its twin - the caller's own acquired slot in place,
+ *                                         else a free one, else (last resort) an acquired one the caller did not use for this picture
+ *   IN_FILLING -> IN_READY                the scheduler may take it: the calling thread (publish_input) without the lookahead; with it, whichever thread finds the picture's
+ *                                         analysis through - the calling thread or the scheduler thread (la_publish, holding la_mu as well)
+ *   IN_FILLING -> IN_FREE                 a device-library call of the way in failed: the calling thread (input_fail); the lookahead's queue is dropped whole (la_drain_locked)
+ *   IN_READY -> IN_CODING                 the scheduler thread (publish_job): submitted, the twin and the pinned copy are still read
+ *   IN_CODING -> IN_FREE                  the calling thread (take_output): the picture's NAL units have been handed out */
+enum { IN_FREE = 0, IN_READY = 1, IN_CODING = 2, IN_FILLING = 3, IN_ACQUIRED = 4 };
 typedef struct Input { int used, disp, key, base_qp, iper, mini4, kbps, la_what, la_p, la_buf, up_sync; long long pts; uint8_t *i420; uint8_t *dev; void *ev_up;
                        uint8_t *raw;                      /* a ragged lane (Enc::ragged): the picture as the caller gave it, srcW x srcH, on the device - ks265_input_pad makes `dev` of it */
                        /* `roi`: the picture's record (one int32 per CTU, ks265_roi_reduce's) on the device, its pinned twin for a map in host memory, the event behind its filling */
@@ -1352,7 +1362,7 @@ static void publish_job(Enc *e, const Sub *s)
 {
     Job *j = s->j;
     pthread_mutex_lock(&e->mu);
-    s->in->used = 2;                                                   /* released when the job's event has fired (output time); under the lock: the caller counts the pictures in flight */
+    s->in->used = IN_CODING;                                           /* under the lock: the caller counts the pictures in flight */
     j->done = 0; j->error = 0; j->used = 1; j->started = 0; j->nrows = 0; j->next_row = 0; j->rows_done = 0; j->sei_len = 0;
     j->sub_seq = e->rc_sub;
     e->job_tail = (e->job_tail + 1) % e->ring; ++e->njobs; ++e->nwait; ++e->rc_sub;
@@ -1393,7 +1403,7 @@ static Input *input_at(Enc *e, int disp)
 {
     Input *r = NULL;
     pthread_mutex_lock(&e->mu);
-    for (int i = 0; i < MAX_INPUT && !r; ++i) if (e->in[i].used == 1 && e->in[i].disp == disp) r = &e->in[i];
+    for (int i = 0; i < MAX_INPUT && !r; ++i) if (e->in[i].used == IN_READY && e->in[i].disp == disp) r = &e->in[i];
     pthread_mutex_unlock(&e->mu);
     return r;
 }
@@ -1408,7 +1418,7 @@ static void gather_view(Enc *e, int d, int flush, int have, int gop_end, GopView
     for (int i = 0; i < MAX_INPUT; ++i) {
         Input *in = &e->in[i];
         const int k = in->disp - (d + 1);
-        if (in->used != 1 || k < 0 || k >= GOP_VIEW || slot[k]) continue;
+        if (in->used != IN_READY || k < 0 || k >= GOP_VIEW || slot[k]) continue;
         slot[k] = in; v->at[k].present = 1; v->at[k].key = in->key; v->at[k].mini4 = in->mini4; v->at[k].iper = in->iper;
     }
     pthread_mutex_unlock(&e->mu);
@@ -1568,7 +1578,7 @@ static int take_output(Enc *e, int max_in_flight, int max_pics, QY265Nal **pNals
             }
         }
         rc_account(e);                                                  /* rate control: this picture's bits are on the books before its slot is reused */
-        for (int i = 0; i < MAX_INPUT; ++i) if (e->in[i].used == 2 && e->in[i].disp == j->disp) e->in[i].used = 0;
+        for (int i = 0; i < MAX_INPUT; ++i) if (e->in[i].used == IN_CODING && e->in[i].disp == j->disp) e->in[i].used = IN_FREE;
         j->used = 0;
         e->job_head = (e->job_head + 1) % e->ring; --e->njobs; ++taken;
         if (cnt >= (int)(sizeof e->nals / sizeof e->nals[0]) - 5) break;
@@ -2343,7 +2353,7 @@ static int lane_delayed(Enc *e)
     if (!e) return 0;
     int n = 0;
     pthread_mutex_lock(&e->mu);                                        /* one snapshot: a picture moves from "waiting" to "in flight" under this lock */
-    for (int i = 0; i < MAX_INPUT; ++i) if (e->in[i].used == 1) ++n;
+    for (int i = 0; i < MAX_INPUT; ++i) if (e->in[i].used == IN_READY) ++n;
     n += e->njobs + e->la_qn;                                          /* (la_q: at the input, their analysis still running) */
     pthread_mutex_unlock(&e->mu);
     return n;
@@ -2355,9 +2365,9 @@ static int lane_acquire(Enc *e, QY265YUV *yuv)
 {
     Input *slot = NULL;
     pthread_mutex_lock(&e->mu);
-    for (int i = 0; i < e->nin && !slot; ++i) if (e->in[i].used == 4) slot = &e->in[i];          /* acquired before and not handed in yet: the same one again */
-    for (int i = 0; i < e->nin && !slot; ++i) if (!e->in[i].used) slot = &e->in[i];
-    if (slot) slot->used = 4;
+    for (int i = 0; i < e->nin && !slot; ++i) if (e->in[i].used == IN_ACQUIRED) slot = &e->in[i];
+    for (int i = 0; i < e->nin && !slot; ++i) if (e->in[i].used == IN_FREE) slot = &e->in[i];
+    if (slot) slot->used = IN_ACQUIRED;
     pthread_mutex_unlock(&e->mu);
     if (!slot) return QY_FAIL;
     yuv->iWidth = e->srcW; yuv->iHeight = e->srcH;                     /* (the caller's size: the coded one unless the lane is ragged) */
@@ -2383,7 +2393,7 @@ static void la_publish(Enc *e, Input *slot, int cut, int mini4)
         if (cut) ++e->la_cuts;
         if (cut || slot->key || nd == 0 || periodic) e->la_last_key = nd;
     }
-    slot->mini4 = mini4; slot->key = slot->key || cut; slot->used = 1; e->next_disp = nd + 1;
+    slot->mini4 = mini4; slot->key = slot->key || cut; slot->used = IN_READY; e->next_disp = nd + 1;
     pthread_cond_signal(&e->cv_sched);
     pthread_mutex_unlock(&e->mu);
 }
@@ -2444,7 +2454,7 @@ static int la_drain_locked(Enc *e, int keep)
             int r, done = 1;
             if (e->la_qn > keep) { const double t0 = now_ms(); r = ks265_event_wait(e->ctx_la, e->la_evs[h->la_buf]); e->la_t_wait += now_ms() - t0; ++e->la_n_wait; }
             else r = ks265_event_query(e->ctx_la, e->la_evs[h->la_buf], &done);
-            if (r) { pthread_mutex_lock(&e->mu); for (int i = 0; i < e->la_qn; ++i) e->la_q[i]->used = 0; e->la_qn = 0; e->la_flying = 0; e->sched_err = hip_rc(r); pthread_mutex_unlock(&e->mu); return hip_rc(r); }
+            if (r) { pthread_mutex_lock(&e->mu); for (int i = 0; i < e->la_qn; ++i) e->la_q[i]->used = IN_FREE; e->la_qn = 0; e->la_flying = 0; e->sched_err = hip_rc(r); pthread_mutex_unlock(&e->mu); return hip_rc(r); }
             if (!done) break;
             la_decide(e, h, &cut, &mini4);
             --e->la_flying;
@@ -2555,135 +2565,159 @@ static void reg_handle(ks265_ctx *c, int open)
 /* the conversion's view of a device picture of the lane's size */
 static void dev_desc(const Enc *e, const ks265_dev_picture *p, ks265_in_desc *d)
 {
-    memset(d, 0, sizeof *d);
-    d->format = p->format; d->width = e->srcW; d->height = e->srcH;    /* (the caller's size: the coded one unless the lane is ragged) */
+    *d = (ks265_in_desc){.format = p->format, .width = e->srcW, .height = e->srcH, .pixel_step = p->pixel_step, .matrix = p->matrix, .full_range = p->full_range};   /* (the caller's size: the coded one unless the lane is ragged) */
     for (int k = 0; k < 3; ++k) { d->plane[k] = p->plane[k]; d->pitch[k] = p->pitch[k]; }
-    d->pixel_step = p->pixel_step; d->matrix = p->matrix; d->full_range = p->full_range;
 }
 
 /* a ragged lane: the picture that lies (or, on ctx_up, is on its way) in the slot's staging area becomes the slot's twin of the coded size, and ev_up is recorded behind that */
 static int lane_pad_slot(Enc *e, Input *slot)
 {
     const size_t ny = (size_t)e->srcW * e->srcH;
-    ks265_in_desc d;
-    memset(&d, 0, sizeof d);
-    d.format = KS265_IN_I420; d.width = e->srcW; d.height = e->srcH;
-    d.plane[0] = slot->raw; d.plane[1] = slot->raw + ny; d.plane[2] = slot->raw + ny + ny / 4;
-    d.pitch[0] = e->srcW; d.pitch[1] = d.pitch[2] = e->srcW / 2;
-    int r = ks265_input_pad(e->ctx_up, &d, e->W, e->H, slot->dev);
-    if (!r) r = ks265_event_record(e->ctx_up, slot->ev_up);
-    return r;
+    const ks265_in_desc d = {.format = KS265_IN_I420, .width = e->srcW, .height = e->srcH, .plane = {slot->raw, slot->raw + ny, slot->raw + ny + ny / 4}, .pitch = {e->srcW, e->srcW / 2, e->srcW / 2}};
+    const int r = ks265_input_pad(e->ctx_up, &d, e->W, e->H, slot->dev);
+    return r ? r : ks265_event_record(e->ctx_up, slot->ev_up);
 }
 
-/* one picture into the lane - a host picture (yuv: copied to a pinned slot or uploaded from where it lies) or a device picture (dp, validated by the caller: converted into the
- * slot's twin on ctx_up in the order of the caller's stream) - and on to the scheduler thread.  key: it starts a closed GOP regardless of the period */
-static int lane_put(Enc *e, const QY265YUV *yuv, const ks265_dev_picture *dp, const struct ScalePlan *sc, const ks265_roi *roi, long long pts, int key)
+/* the picture being handed in, filled once by the API entry (QY265EncoderEncodeFrame, resolve_device) and passed down as it is: top_encode adds the pending ROI map, lane_put
+ * runs what `how` says and decides nothing again.  how: a host picture (yuv); a device picture (dp, validated; d: the operation's view of it) converted / padded (a ragged lane) /
+ * scaled (d at the source's size; sc: kept by the lane this picture goes to, any context of the device may run it) into the slot's twin.  roi: the pending map or NULL */
+enum { PIC_HOST, PIC_CONVERT, PIC_PAD, PIC_SCALE };
+typedef struct PicIn { int how; long long pts; const QY265YUV *yuv; const ks265_dev_picture *dp; ks265_in_desc d; const struct ScalePlan *sc; const ks265_roi *roi; } PicIn;
+/* back-pressure on the input side (mu held): at most 16 pictures wait for the scheduler thread (it may itself be waiting for ring space, which only the caller's take_output
+ * frees - then go on and collect).  GOP lanes (multi): the input slots are the limit (lane_has_slot) - a lane takes a whole GOP in while it is still coding the previous one, or
+ * the caller would wait here while the other lanes run dry.  cuTree: the scheduler itself holds a mini-GOP back until its window has arrived - that many more may wait */
+static void wait_input_room(Enc *e, double since)
 {
-    if (!dp && (!yuv || !yuv->pData[0] || !yuv->pData[1] || !yuv->pData[2])) return QY_POINTER;
-    if (!dp && (yuv->iWidth != e->srcW || yuv->iHeight != e->srcH)) return QY_NOTSUPPORTED;
-    const int sw = e->srcW, sh = e->srcH;                               /* the caller's size: W x H unless the lane is ragged */
-    Input *slot = NULL;
-    const double tc0 = now_ms();
-    pthread_mutex_lock(&e->mu);
-    /* back-pressure on the input side: at most 16 pictures wait for the scheduler thread (it may itself be waiting for ring space, which only the
-     * caller's take_output frees - then go on and collect).  GOP lanes (multi): the input slots are the limit (lane_has_slot) - a lane takes a whole GOP in
-     * while it is still coding the previous one, or the caller would wait here while the other lanes run dry */
-    /* (cuTree: the scheduler itself holds a mini-GOP back until its window has arrived - that many more may wait) */
     while (!e->multi && !e->quit && !e->sched_err && e->next_disp - (e->coded_upto + 1) > 16 + (e->ct_on ? e->ct_depth + e->gop_b + 1 : 0) && e->njobs <= e->ring - 12) pthread_cond_wait(&e->cv_sched_done, &e->mu);
-    e->la_t_bp += now_ms() - tc0;   /* a scheduler that failed makes no more progress */
-    int own = 0;                                                       /* the caller wrote the picture into a slot it had acquired (ks265_enc_acquire_input): nothing to copy */
-    for (int i = 0; i < e->nin && !slot && !dp; ++i) if (e->in[i].used == 4 && e->in[i].i420 == yuv->pData[0]) { slot = &e->in[i]; own = 1; }
-    for (int i = 0; i < e->nin && !slot; ++i) if (!e->in[i].used) slot = &e->in[i];
-    for (int i = 0; i < e->nin && !slot; ++i) if (e->in[i].used == 4) slot = &e->in[i];   /* last resort: a buffer the caller acquired and did not use for this picture - copy into it
-                                                                                            * (the caller's pointer to it is dead from here on, as after any EncodeFrame call) */
-    if (slot) { slot->used = 3; slot->up_sync = 0; slot->roi_has = 0; }   /* being filled */
-    pthread_mutex_unlock(&e->mu);
-    if (!slot) return QY_FAIL;                                         /* one lane: cannot happen (more input slots than pictures in flight + one mini-GOP); lanes: the caller checked lane_has_slot */
+    e->la_t_bp += now_ms() - since;                                    /* (a scheduler that failed makes no more progress) */
+}
+/* the slot the picture goes into (mu held), IN_FILLING from here; *own: the caller wrote the picture into this slot after acquiring it (ks265_enc_acquire_input): nothing to copy.
+ * NULL - one lane: cannot happen (more input slots than pictures in flight + one mini-GOP); lanes: the caller checked lane_has_slot */
+static Input *take_input_slot(Enc *e, const uint8_t *data, int *own)
+{
+    Input *slot = NULL; *own = 0;
+    for (int i = 0; i < e->nin && !slot && data; ++i) if (e->in[i].used == IN_ACQUIRED && e->in[i].i420 == data) { slot = &e->in[i]; *own = 1; }
+    for (int i = 0; i < e->nin && !slot; ++i) if (e->in[i].used == IN_FREE) slot = &e->in[i];
+    for (int i = 0; i < e->nin && !slot; ++i) if (e->in[i].used == IN_ACQUIRED) slot = &e->in[i];   /* last resort: the caller's pointer to it is dead from here on, as after any EncodeFrame call */
+    if (slot) { slot->used = IN_FILLING; slot->up_sync = 0; slot->roi_has = 0; }
+    return slot;
+}
+/* the bracket around work on ctx_up that reads memory of a stream of the caller's: that stream -> ctx_up (in), the work, then its event and the caller's stream waits for it (out) */
+static int caller_stream_in(Enc *e, void *stream) { return ks265_wait_external(e->ctx_up, stream); }
+static int caller_stream_out(Enc *e, void *stream, void *ev) { const int r = ks265_event_record(e->ctx_up, ev); return r ? r : ks265_external_wait_event(e->ctx_up, stream, ev); }
+/* the map becomes the slot's record on ctx_up, beside the picture's own way in.  A map describes the caller's picture; the CTU grid is the coded picture's */
+static int stage_roi(Enc *e, Input *slot, const ks265_roi *roi)
+{
+    const int sw = e->srcW, sh = e->srcH; int r;
+    if (roi->device >= 0) {
+        const ks265_roi_desc d = {roi->type, roi->log2_block, ks265_roi_map_cols(sw, roi->log2_block), ks265_roi_map_rows(sh, roi->log2_block), roi->data, roi->pitch};
+        r = caller_stream_in(e, roi->stream);
+        if (!r) r = ks265_roi_reduce(e->ctx_up, &d, sw, sh, slot->roi_rec);
+        if (!r) r = caller_stream_out(e, roi->stream, slot->ev_roi);
+    } else {                                                           /* host memory: reduced here, on the calling thread (ks265_roi.h); the record is uploaded */
+        r = ks265_roi_reduce_host(roi->type, roi->log2_block, roi->data, roi->pitch, sw, sh, slot->roi_host) ? KS265_NOTSUPPORTED : KS265_OK;
+        if (!r) r = ks265_memcpy_h2d_async(e->ctx_up, slot->roi_rec, slot->roi_host, (size_t)e->geom.ctu_cols * e->geom.ctu_rows * sizeof(int32_t));
+        if (!r) r = ks265_event_record(e->ctx_up, slot->ev_roi);
+    }
+    if (!r) slot->roi_has = 1;
+    return r;
+}
+/* a device picture: the resolved operation into the twin, in the order of the caller's stream (a scaled one in the same place between the same two events) */
+static int stage_device(Enc *e, Input *slot, const PicIn *p)
+{
+    int r = caller_stream_in(e, p->dp->stream);
+    if (!r) r = p->how == PIC_SCALE ? ks265_input_scale(e->ctx_up, p->sc->plan, &p->d, e->sc_scratch, slot->dev)
+              : p->how == PIC_PAD ? ks265_input_pad(e->ctx_up, &p->d, e->W, e->H, slot->dev) : ks265_input_convert(e->ctx_up, &p->d, slot->dev);
+    return r ? r : caller_stream_out(e, p->dp->stream, slot->ev_up);
+}
+static uint8_t *upload_dst(const Enc *e, const Input *slot) { return e->ragged ? slot->raw : slot->dev; }   /* a ragged lane's staging area: ks265_input_pad behind it (lane_pad_slot) */
+static int packed_strides(const Enc *e, const QY265YUV *yuv) { return yuv->iStride[0] == e->srcW && yuv->iStride[1] == e->srcW / 2 && yuv->iStride[2] == e->srcW / 2; }
+/* packed planes that the runtime can pin where they lie go up from there, whole or plane by plane - *took (else nothing has happened: the picture is copied).  direct_in 2: no stream, the call returns when the
+ * picture is on the device (a ragged lane's twin is still made on ctx_up: its readers wait for ev_up as after any other upload); 1: on ctx_up, waited for at the end of the API call (finish_upload) */
+static int stage_host_direct(Enc *e, Input *slot, const QY265YUV *yuv, int *took)
+{
+    const size_t ny = (size_t)e->srcW * e->srcH, nc = ny / 4;
+    uint8_t *const up = upload_dst(e, slot);
+    const int whole = yuv->pData[1] == yuv->pData[0] + ny && yuv->pData[2] == yuv->pData[1] + nc, np = whole ? 1 : 3, sync = e->direct_in == 2;
+    const struct { uint8_t *dst, *src; size_t n; } piece[3] = {{up, yuv->pData[0], whole ? ny + 2 * nc : ny}, {up + ny, yuv->pData[1], nc}, {up + ny + nc, yuv->pData[2], nc}};
+    for (int k = 0; k < np; ++k) if (!reg_get(e->ctx_up, piece[k].src, piece[k].n, !e->hold_in)) return KS265_OK;   /* (hold: an old registration may still be read by a DMA in flight - then the table only grows) */
+    int r = KS265_OK; *took = 1;
+    for (int k = 0; k < np && !r; ++k) r = sync ? ks265_memcpy_h2d_sync(main_ctx(e), piece[k].dst, piece[k].src, piece[k].n) : ks265_memcpy_h2d_async(e->ctx_up, piece[k].dst, piece[k].src, piece[k].n);
+    if (sync && !e->ragged) slot->up_sync = 1;
+    else if (!r) r = e->ragged ? lane_pad_slot(e, slot) : ks265_event_record(e->ctx_up, slot->ev_up);
+    if (!sync && !e->hold_in) e->pending_up = slot;
+    return r;
+}
+/* into the slot's pinned memory (own: it lies there) - packed planes as three block copies, else row by row - and from there to the device at once, on the lookahead's stream
+ * (nothing there waits for the pipeline) */
+static int stage_host_copy(Enc *e, Input *slot, const QY265YUV *yuv, int own)
+{
+    const int sw = e->srcW, sh = e->srcH;
     uint8_t *u = slot->i420 + (size_t)sw * sh, *v = u + (size_t)sw * sh / 4;
-    uint8_t *const up = e->ragged ? slot->raw : slot->dev;              /* where an upload goes: a ragged lane's staging area, ks265_input_pad behind it */
-    int direct = 0;
-    if (roi && e->roi_on) {                                            /* (validated by ks265_enc_set_next_roi) the map becomes the slot's record on ctx_up, beside the picture's own way in */
-        int ru;
-        if (roi->device >= 0) {                                        /* the caller's stream -> ctx_up: the reduction -> ev_roi -> the caller's stream waits for it */
-            const ks265_roi_desc d = {roi->type, roi->log2_block, ks265_roi_map_cols(sw, roi->log2_block), ks265_roi_map_rows(sh, roi->log2_block), roi->data, roi->pitch};
-            ru = ks265_wait_external(e->ctx_up, roi->stream);
-            if (!ru) ru = ks265_roi_reduce(e->ctx_up, &d, sw, sh, slot->roi_rec);   /* (a map describes the caller's picture; the CTU grid is the coded picture's) */
-            if (!ru) ru = ks265_event_record(e->ctx_up, slot->ev_roi);
-            if (!ru) ru = ks265_external_wait_event(e->ctx_up, roi->stream, slot->ev_roi);
-        } else {                                                       /* host memory: reduced here, on the calling thread (ks265_roi.h); the record is uploaded */
-            ru = ks265_roi_reduce_host(roi->type, roi->log2_block, roi->data, roi->pitch, sw, sh, slot->roi_host) ? KS265_NOTSUPPORTED : KS265_OK;
-            if (!ru) ru = ks265_memcpy_h2d_async(e->ctx_up, slot->roi_rec, slot->roi_host, (size_t)e->geom.ctu_cols * e->geom.ctu_rows * sizeof(int32_t));
-            if (!ru) ru = ks265_event_record(e->ctx_up, slot->ev_roi);
-        }
-        if (ru) { pthread_mutex_lock(&e->mu); slot->used = 0; e->sched_err = hip_rc(ru); pthread_mutex_unlock(&e->mu); return hip_rc(ru); }
-        slot->roi_has = 1;
-    }
-    if (dp) {                                                          /* the caller's stream -> ctx_up: conversion into the twin -> ev_up -> the caller's stream waits for it */
-        ks265_in_desc d;
-        dev_desc(e, dp, &d);
-        if (sc) { d.width = sc->sw; d.height = sc->sh; }                /* a picture of another size: scaled into the twin, in the same place between the same two events */
-        int ru = ks265_wait_external(e->ctx_up, dp->stream);
-        if (!ru) ru = sc ? ks265_input_scale(e->ctx_up, sc->plan, &d, e->sc_scratch, slot->dev) : e->ragged ? ks265_input_pad(e->ctx_up, &d, e->W, e->H, slot->dev) : ks265_input_convert(e->ctx_up, &d, slot->dev);
-        if (!ru) ru = ks265_event_record(e->ctx_up, slot->ev_up);
-        if (!ru) ru = ks265_external_wait_event(e->ctx_up, dp->stream, slot->ev_up);
-        if (ru) { pthread_mutex_lock(&e->mu); slot->used = 0; e->sched_err = hip_rc(ru); pthread_mutex_unlock(&e->mu); return hip_rc(ru); }
-        direct = 1;
-    } else if (e->direct_in && !own && slot->dev && yuv->iStride[0] == sw && yuv->iStride[1] == sw / 2 && yuv->iStride[2] == sw / 2) {
-        const size_t ny = (size_t)sw * sh, nc = ny / 4;
-        uint8_t *p0 = yuv->pData[0], *p1 = yuv->pData[1], *p2 = yuv->pData[2];
-        const int whole = p1 == p0 + ny && p2 == p1 + nc, evict = !e->hold_in;      /* (hold: an old registration may still be read by a DMA in flight - then the table only grows) */
-        int ru = KS265_OK;
-        if (whole ? reg_get(e->ctx_up, p0, ny + 2 * nc, evict) : (reg_get(e->ctx_up, p0, ny, evict) && reg_get(e->ctx_up, p1, nc, evict) && reg_get(e->ctx_up, p2, nc, evict))) {
-            if (e->direct_in == 2) {                                    /* no stream: the call returns when the picture is on the device */
-                if (whole) ru = ks265_memcpy_h2d_sync(main_ctx(e), up, p0, ny + 2 * nc);
-                else { ru = ks265_memcpy_h2d_sync(main_ctx(e), up, p0, ny); if (!ru) ru = ks265_memcpy_h2d_sync(main_ctx(e), up + ny, p1, nc); if (!ru) ru = ks265_memcpy_h2d_sync(main_ctx(e), up + ny + nc, p2, nc); }
-                if (!e->ragged) slot->up_sync = 1;
-                else if (!ru) ru = lane_pad_slot(e, slot);              /* the twin is made on ctx_up: its readers wait for ev_up as after any other upload */
-            } else {
-            if (whole) ru = ks265_memcpy_h2d_async(e->ctx_up, up, p0, ny + 2 * nc);
-            else { ru = ks265_memcpy_h2d_async(e->ctx_up, up, p0, ny); if (!ru) ru = ks265_memcpy_h2d_async(e->ctx_up, up + ny, p1, nc); if (!ru) ru = ks265_memcpy_h2d_async(e->ctx_up, up + ny + nc, p2, nc); }
-            if (!ru) ru = e->ragged ? lane_pad_slot(e, slot) : ks265_event_record(e->ctx_up, slot->ev_up);
-            if (!e->hold_in) e->pending_up = slot;                      /* waited for at the end of the call, behind the output's hand-over */
-            }
-            if (ru) { e->pending_up = NULL; pthread_mutex_lock(&e->mu); slot->used = 0; e->sched_err = hip_rc(ru); pthread_mutex_unlock(&e->mu); return hip_rc(ru); }
-            direct = 1;
-        }
-    }
-    if (direct) { /* on its way from the caller's own memory (host: DMA; device: the conversion) */ }
-    else if (own) { /* in place */ }
-    else if (yuv->iStride[0] == sw && yuv->iStride[1] == sw / 2 && yuv->iStride[2] == sw / 2) {    /* packed planes: three block copies */
+    if (!own && packed_strides(e, yuv)) {
         copy_shared(e->pool, slot->i420, yuv->pData[0], (size_t)sw * sh);
         copy_shared(e->pool, u, yuv->pData[1], (size_t)sw * sh / 4);
         copy_shared(e->pool, v, yuv->pData[2], (size_t)sw * sh / 4);
-    } else {
+    } else if (!own) {
         for (int y = 0; y < sh; ++y) memcpy(slot->i420 + (size_t)y * sw, yuv->pData[0] + (size_t)y * yuv->iStride[0], (size_t)sw);
         for (int y = 0; y < sh / 2; ++y) {
             memcpy(u + (size_t)y * (sw / 2), yuv->pData[1] + (size_t)y * yuv->iStride[1], (size_t)sw / 2);
             memcpy(v + (size_t)y * (sw / 2), yuv->pData[2] + (size_t)y * yuv->iStride[2], (size_t)sw / 2);
         }
     }
-    if (slot->dev && !direct) {   /* on its way to the device at once, on the lookahead's stream (nothing there waits for the pipeline) */
-        int ru = ks265_memcpy_h2d_async(e->ctx_up, up, slot->i420, (size_t)sw * sh * 3 / 2);
-        if (!ru) ru = e->ragged ? lane_pad_slot(e, slot) : ks265_event_record(e->ctx_up, slot->ev_up);
-        if (ru) { pthread_mutex_lock(&e->mu); slot->used = 0; e->sched_err = hip_rc(ru); pthread_mutex_unlock(&e->mu); return hip_rc(ru); }
-    }
-    /* the picture's own fields travel with it from now; with the lookahead it becomes visible to the scheduler when its results are there (la_drain) */
+    if (!slot->dev) return KS265_OK;
+    const int r = ks265_memcpy_h2d_async(e->ctx_up, upload_dst(e, slot), slot->i420, (size_t)sw * sh * 3 / 2);
+    return r ? r : e->ragged ? lane_pad_slot(e, slot) : ks265_event_record(e->ctx_up, slot->ev_up);
+}
+/* the picture's own fields travel with it from now, and it goes on to the scheduler thread - at once, or with the lookahead when its results are there (la_drain).  A QY code */
+static int publish_input(Enc *e, Input *slot, long long pts, int key)
+{
     pthread_mutex_lock(&e->mu);
-    slot->mini4 = 0;
-    slot->disp = e->in_disp++; slot->pts = pts; slot->key = key || e->force_key; slot->base_qp = e->base_qp; slot->iper = e->iper; slot->kbps = e->cfg.bitrateInkbps;
+    slot->mini4 = 0; slot->disp = e->in_disp++; slot->pts = pts; slot->key = key || e->force_key; slot->base_qp = e->base_qp; slot->iper = e->iper; slot->kbps = e->cfg.bitrateInkbps;
     e->force_key = 0;
-    if (!e->la_on) { slot->used = 1; e->next_disp = e->in_disp; pthread_cond_signal(&e->cv_sched); }   /* the scheduler thread takes it from here */
+    if (!e->la_on) { slot->used = IN_READY; e->next_disp = e->in_disp; pthread_cond_signal(&e->cv_sched); }
     pthread_mutex_unlock(&e->mu);
-    if (e->la_on) {
-        const double t0 = now_ms();
-        const int r = la_take(e, slot);
-        e->la_t_take += now_ms() - t0;
-        if (r) { pthread_mutex_lock(&e->mu); slot->used = 0; e->sched_err = r; pthread_mutex_unlock(&e->mu); return r; }
-    }
+    if (!e->la_on) return QY_OK;
+    const double t0 = now_ms();
+    const int r = la_take(e, slot);
+    e->la_t_take += now_ms() - t0;
+    return r;
+}
+/* the one way out of a failed way in: the slot is free again and the lane has failed */
+static int input_fail(Enc *e, Input *slot, int rc) { pthread_mutex_lock(&e->mu); slot->used = IN_FREE; e->sched_err = rc; pthread_mutex_unlock(&e->mu); return rc; }
+/* one picture into the lane and on to the scheduler thread.  key: it starts a closed GOP regardless of the period */
+static int lane_put(Enc *e, const PicIn *p, int key)
+{
+    const QY265YUV *yuv = p->yuv;
+    if (p->how == PIC_HOST && (!yuv || !yuv->pData[0] || !yuv->pData[1] || !yuv->pData[2])) return QY_POINTER;
+    if (p->how == PIC_HOST && (yuv->iWidth != e->srcW || yuv->iHeight != e->srcH)) return QY_NOTSUPPORTED;
+    const double tc0 = now_ms();
+    int own, direct = 0;
+    pthread_mutex_lock(&e->mu);
+    wait_input_room(e, tc0);
+    Input *slot = take_input_slot(e, p->how == PIC_HOST ? yuv->pData[0] : NULL, &own);
+    pthread_mutex_unlock(&e->mu);
+    if (!slot) return QY_FAIL;
+    int r = p->roi && e->roi_on ? stage_roi(e, slot, p->roi) : KS265_OK;
+    if (!r && p->how != PIC_HOST) r = stage_device(e, slot, p);
+    if (!r && p->how == PIC_HOST && e->direct_in && !own && slot->dev && packed_strides(e, yuv)) r = stage_host_direct(e, slot, yuv, &direct);
+    if (!r && p->how == PIC_HOST && !direct) r = stage_host_copy(e, slot, yuv, own);
+    if (r) { e->pending_up = NULL; r = hip_rc(r); }                    /* (nothing of a failed picture is waited for) */
+    else r = publish_input(e, slot, p->pts, key);
+    if (r) return input_fail(e, slot, r);
     e->st.in_copy_ms += now_ms() - tc0;
     return QY_OK;
 }
 
+/* the caller's buffer is its own again when the API call returns: the upload out of it (stage_host_direct on ctx_up) has finished.  A QY code */
+static int finish_upload(Enc *e)
+{
+    if (!e->pending_up) return QY_OK;
+    const double tw = now_ms();
+    const int ru = ks265_event_wait(e->ctx_up, e->pending_up->ev_up);
+    e->pending_up = NULL; e->st.in_copy_ms += now_ms() - tw;
+    return hip_rc(ru);
+}
 /* flush, first half: everything that has arrived gets scheduled (short mini-GOPs at the end).  Returns 1 when the scheduler is through, 0 when the ring
  * filled up first (the scheduler then waits for the caller to collect output: hand out what is ready and come back, as the SDK's flush loop does anyway -
  * EncodeFrame(NULL) while DelayedFrames() > 0) */
@@ -2703,12 +2737,12 @@ static int lane_flush_begin(Enc *e, int wait)
     return all;
 }
 
-static int lane_encode_frame(Enc *e, QY265Nal **pNals, int *iNalCount, QY265Picture *in, const ks265_dev_picture *dp, const struct ScalePlan *sc, const ks265_roi *roi, QY265Picture *out)
+static int lane_encode_frame(Enc *e, QY265Nal **pNals, int *iNalCount, const PicIn *p, QY265Picture *out)
 {
     *pNals = e->nals; *iNalCount = 0;
     int r = QY_OK;
-    if (in || dp) {
-        r = in ? lane_put(e, in->yuv, NULL, NULL, roi, in->pts, 0) : lane_put(e, NULL, dp, sc, roi, dp->pts, 0);
+    if (p) {
+        r = lane_put(e, p, 0);
         if (r) return r;
         /* finished pictures (copied to the output buffer); when the ring of in-flight pictures is nearly full, wait for the oldest ones -
          * only as many as needed, the writers keep running */
@@ -2724,14 +2758,8 @@ static int lane_encode_frame(Enc *e, QY265Nal **pNals, int *iNalCount, QY265Pict
         }
         r = take_output(e, in_flight, 1 << 30, pNals, iNalCount, out, NULL);
         e->st.output_ms += now_ms() - t0;
-        if (e->pending_up) {                                           /* the caller's buffer is its own again when the call returns: the upload out of it has finished */
-            const double tw = now_ms();
-            const int ru = ks265_event_wait(e->ctx_up, e->pending_up->ev_up);
-            e->pending_up = NULL;
-            e->st.in_copy_ms += now_ms() - tw;
-            if (ru && !r) r = hip_rc(ru);
-        }
-        return r ? r : e->sched_err;
+        const int ru = finish_upload(e);
+        return r ? r : ru ? ru : e->sched_err;
     }
     /* flush: then every picture in flight is collected */
     const double t0 = now_ms();
@@ -2849,7 +2877,7 @@ static int lane_has_slot(Enc *e, const uint8_t *data)
 {
     int ok = 0;
     pthread_mutex_lock(&e->mu);
-    for (int i = 0; i < e->nin && !ok; ++i) ok = !e->in[i].used || (e->in[i].used == 4 && e->in[i].i420 == data);
+    for (int i = 0; i < e->nin && !ok; ++i) ok = e->in[i].used == IN_FREE || (e->in[i].used == IN_ACQUIRED && e->in[i].i420 == data);
     pthread_mutex_unlock(&e->mu);
     return ok;
 }
@@ -3124,24 +3152,23 @@ int QY265EncoderDelayedFrames(void *h)
     return n;
 }
 
-/* one call of the API: a host picture (in), a device picture (dp) or, neither, the flush */
 /* the lane the NEXT picture goes to: a new GOP starts on the next lane (top_encode, ks265_enc_acquire_input, ks265_enc_encode_device_frame_scaled) */
 static int top_next_lane(const Top *t) { return t->nlanes == 1 ? 0 : (t->chunk_left <= 0 || t->key_request) ? (t->cur_lane + 1) % t->nlanes : t->cur_lane; }
 
-static int top_encode(Top *t, QY265Nal **pNals, int *iNalCount, QY265Picture *in, const ks265_dev_picture *dp, const struct ScalePlan *sc, QY265Picture *out)
+/* one call of the API: a picture (p) or, NULL, the flush */
+static int top_encode(Top *t, QY265Nal **pNals, int *iNalCount, PicIn *p, QY265Picture *out)
 {
     recon_release(t);                                                 /* `devrecon`: the previous call's reconstructions are the pool's again */
-    const ks265_roi *roi = (in || dp) && t->roi_set ? &t->roi : NULL;  /* `roi`: the pending map goes with this picture - whatever becomes of the call, nothing stays pending (a flush: it stays) */
-    if (in || dp) t->roi_set = 0;
+    if (p) { p->roi = t->roi_set ? &t->roi : NULL; t->roi_set = 0; }    /* `roi`: the pending map goes with this picture - whatever becomes of the call, nothing stays pending (a flush: it stays) */
     if (t->nlanes == 1) {
-        const int r1 = lane_encode_frame(t->lane[0], pNals, iNalCount, in, dp, sc, roi, out);
+        const int r1 = lane_encode_frame(t->lane[0], pNals, iNalCount, p, out);
         const int rr = t->lane[0]->pool_on ? recon_taken(t, t->lane[0], NULL, &t->handed) : QY_OK;
         return r1 ? r1 : rr;
     }
     *pNals = NULL; *iNalCount = 0;
     t->on = 0; t->opos = 0;
     int r = QY_OK;
-    if (in || dp) {
+    if (p) {
         int first = 0;
         const int next = top_next_lane(t);
         if (t->chunk_left <= 0 || t->key_request) {                     /* a new GOP: the next lane */
@@ -3158,24 +3185,18 @@ static int top_encode(Top *t, QY265Nal **pNals, int *iNalCount, QY265Picture *in
         }
         Enc *e = t->lane[t->cur_lane];
         const double t0 = now_ms();
-        while (!lane_has_slot(e, in && in->yuv ? in->yuv->pData[0] : NULL)) {                                     /* this lane is as far ahead as its buffers allow: finish older GOPs first */
+        while (!lane_has_slot(e, p->yuv ? p->yuv->pData[0] : NULL)) {                                     /* this lane is as far ahead as its buffers allow: finish older GOPs first */
             r = top_collect(t, 1, out);
             if (r) return r;
         }
         t->output_ms += now_ms() - t0;
-        r = in ? lane_put(e, in->yuv, NULL, NULL, roi, in->pts, first) : lane_put(e, NULL, dp, sc, roi, dp->pts, first);
+        r = lane_put(e, p, first);
         if (r) return r;
         ++t->ch[(t->ch_head + t->ch_n - 1) % MAX_CHUNKS].count; ++t->n_in; --t->chunk_left;
         const double t1 = now_ms();
         r = top_collect(t, 0, out);
         t->output_ms += now_ms() - t1;
-        if (e->pending_up) {                                            /* the caller's buffer is its own again when the call returns (lane_encode_frame) */
-            const double tw = now_ms();
-            const int ru = ks265_event_wait(e->ctx_up, e->pending_up->ev_up);
-            e->pending_up = NULL;
-            e->st.in_copy_ms += now_ms() - tw;
-            if (ru && !r) r = hip_rc(ru);
-        }
+        const int ru = finish_upload(e); if (!r) r = ru;
         if (!r) for (int i = 0; i < t->nlanes && !r; ++i) r = t->lane[i]->sched_err;
     } else {
         const double t0 = now_ms();
@@ -3198,7 +3219,8 @@ int QY265EncoderEncodeFrame(void *h, QY265Nal **pNals, int *iNalCount, QY265Pict
     (void)bForceLogo;
     Top *t = (Top *)h;
     if (!t || !pNals || !iNalCount) return QY_POINTER;
-    return top_encode(t, pNals, iNalCount, in, NULL, NULL, out);
+    PicIn p = {.how = PIC_HOST, .yuv = in ? in->yuv : NULL, .pts = in ? in->pts : 0};
+    return top_encode(t, pNals, iNalCount, in ? &p : NULL, out);
 }
 
 int ks265_enc_get_stats(void *h, ks265_enc_stats *out)
@@ -3282,25 +3304,6 @@ int ks265_enc_enable_device_input(void *h)
     return QY_OK;
 }
 
-int ks265_enc_encode_device_frame(void *h, QY265Nal **pNals, int *iNalCount, const ks265_dev_picture *pic, QY265Picture *out)
-{
-    Top *t = (Top *)h;
-    if (!t || !pNals || !iNalCount || !pic) return QY_POINTER;
-    *iNalCount = 0;
-    Enc *e0 = t->lane[0];
-    if (!e0->dev_in_on || !ks265_input_validate) return QY_NOTSUPPORTED;
-    if (pic->device != e0->dev_id) return QY_NOTSUPPORTED;
-    /* the whole picture is checked before anything of it is enqueued or counted: a refused picture leaves the handle as it was */
-    const double t0 = now_ms();
-    ks265_in_desc d;
-    dev_desc(e0, pic, &d);
-    if (e0->ragged && d.format != KS265_IN_I420 && d.format != KS265_IN_NV12) return QY_NOTSUPPORTED;   /* a ragged handle pads 8-bit I420 and NV12 only (ks265_enc.h) */
-    const int rv = e0->ragged ? ks265_input_pad_validate(main_ctx(e0), &d, e0->W, e0->H) : ks265_input_validate(main_ctx(e0), &d);
-    e0->st.in_copy_ms += now_ms() - t0;
-    if (rv) return hip_rc(rv);
-    return top_encode(t, pNals, iNalCount, NULL, pic, NULL, out);
-}
-
 /* the lane's plan for (source size, filter) into *out: the cached one, or a new one in the place of the least recently used - created here, on the caller's thread; the one that
  * goes may still be read by a picture in flight on ctx_up, which is waited for first.  More than SCALE_PLANS sizes in turn pay that wait and the tables with every picture */
 static int lane_scale_plan(Enc *e, int sw, int sh, int filter, const struct ScalePlan **out)
@@ -3343,29 +3346,36 @@ int ks265_enc_enable_device_scale(void *h, int max_src_width, int max_src_height
     return QY_OK;
 }
 
-int ks265_enc_encode_device_frame_scaled(void *h, QY265Nal **pNals, int *iNalCount, const ks265_dev_picture *pic, int src_width, int src_height, int filter, QY265Picture *out)
+/* a device picture resolved into *p: the operation that makes the slot's twin of it - scaled (from sw x sh, a size that is not the lane's), padded on a ragged handle, else converted - its view of the picture,
+ * validated, and for scaling the plan.  All of it before anything is enqueued or counted: a refused picture leaves the handle as it was (a pending ROI map too) */
+static int resolve_device(Top *t, const ks265_dev_picture *pic, int scaled, int sw, int sh, int filter, PicIn *p)
+{
+    Enc *e0 = t->lane[0];
+    *p = (PicIn){.how = scaled ? PIC_SCALE : e0->ragged ? PIC_PAD : PIC_CONVERT, .dp = pic, .pts = pic->pts};
+    if ((p->how == PIC_SCALE ? !e0->sc_on : !e0->dev_in_on || !ks265_input_validate) || pic->device != e0->dev_id) return QY_NOTSUPPORTED;
+    if (p->how == PIC_SCALE && (!ks265_scale_size_ok(sw, sh, e0->W, e0->H) || sw > e0->sc_max_w || sh > e0->sc_max_h || (filter != KS_SCALE_TRIANGLE && filter != KS_SCALE_CATMULL_ROM))) return QY_NOTSUPPORTED;
+    const double t0 = now_ms();
+    dev_desc(e0, pic, &p->d);
+    if (p->how == PIC_SCALE) { p->d.width = sw; p->d.height = sh; }
+    if (p->how == PIC_PAD && p->d.format != KS265_IN_I420 && p->d.format != KS265_IN_NV12) return QY_NOTSUPPORTED;   /* a ragged handle pads 8-bit I420 and NV12 only (ks265_enc.h) */
+    int rv = p->how == PIC_PAD ? ks265_input_pad_validate(main_ctx(e0), &p->d, e0->W, e0->H) : ks265_input_validate(main_ctx(e0), &p->d);
+    if (!rv && p->how == PIC_SCALE) rv = lane_scale_plan(t->lane[top_next_lane(t)], sw, sh, filter, &p->sc);
+    e0->st.in_copy_ms += now_ms() - t0;
+    return hip_rc(rv);
+}
+static int encode_device(void *h, QY265Nal **pNals, int *iNalCount, const ks265_dev_picture *pic, int scaled, int sw, int sh, int filter, QY265Picture *out)
 {
     Top *t = (Top *)h;
     if (!t || !pNals || !iNalCount || !pic) return QY_POINTER;
-    Enc *e0 = t->lane[0];
-    if (e0->ragged) { *iNalCount = 0; return QY_NOTSUPPORTED; }         /* the scaler writes coded sizes only (ks265_enc.h) */
-    if (src_width == e0->W && src_height == e0->H) return ks265_enc_encode_device_frame(h, pNals, iNalCount, pic, out);
     *iNalCount = 0;
-    if (!e0->sc_on || pic->device != e0->dev_id) return QY_NOTSUPPORTED;
-    if (!ks265_scale_size_ok(src_width, src_height, e0->W, e0->H) || src_width > e0->sc_max_w || src_height > e0->sc_max_h) return QY_NOTSUPPORTED;
-    if (filter != KS_SCALE_TRIANGLE && filter != KS_SCALE_CATMULL_ROM) return QY_NOTSUPPORTED;
-    /* the whole source is checked, and its plan is there, before anything is enqueued or counted: a refused picture leaves the handle as it was (a pending ROI map too) */
-    const double t0 = now_ms();
-    ks265_in_desc d;
-    dev_desc(e0, pic, &d);
-    d.width = src_width; d.height = src_height;
-    int rv = ks265_input_validate(main_ctx(e0), &d);
-    const struct ScalePlan *sc = NULL;                                  /* kept by the lane this picture goes to; any context of the device may run it */
-    if (!rv) rv = lane_scale_plan(t->lane[top_next_lane(t)], src_width, src_height, filter, &sc);
-    e0->st.in_copy_ms += now_ms() - t0;
-    if (rv) return hip_rc(rv);
-    return top_encode(t, pNals, iNalCount, NULL, pic, sc, out);
+    if (scaled && t->lane[0]->ragged) return QY_NOTSUPPORTED;               /* the scaler writes coded sizes only (ks265_enc.h) */
+    if (sw == t->lane[0]->W && sh == t->lane[0]->H) scaled = 0;           /* a source of the encoder's own size IS ks265_enc_encode_device_frame */
+    PicIn p;
+    const int r = resolve_device(t, pic, scaled, sw, sh, filter, &p);
+    return r ? r : top_encode(t, pNals, iNalCount, &p, out);
 }
+int ks265_enc_encode_device_frame(void *h, QY265Nal **pNals, int *iNalCount, const ks265_dev_picture *pic, QY265Picture *out) { return encode_device(h, pNals, iNalCount, pic, 0, 0, 0, 0, out); }
+int ks265_enc_encode_device_frame_scaled(void *h, QY265Nal **pNals, int *iNalCount, const ks265_dev_picture *pic, int src_width, int src_height, int filter, QY265Picture *out) { return encode_device(h, pNals, iNalCount, pic, 1, src_width, src_height, filter, out); }
 
 int ks265_enc_set_next_roi(void *h, const ks265_roi *roi)
 {

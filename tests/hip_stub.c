@@ -29,13 +29,18 @@ struct ks265_frame {
 /* KS265_STUB_CALL_LOG = file: one line per call that enqueues work, records an event, waits for one or changes a frame object's state - the entry's name, the context (c), the
  * frame object (f) and the events (e) it was given as the ordinals of their creation in this process (never addresses), a small integer argument where the entry has one, and
  * in front of them an ordinal of the calling thread (t, in order of first appearance) - so that a host test can pin the order in which one thread issues its calls.  Not logged:
- * allocation, creation and destruction, and ks265_event_query (a poll: how often it runs is the caller's timing) */
-static void call_log(const char *name, const ks265_ctx *c, const ks265_frame *f, const void *ev, int arg)
+ * allocation, creation and destruction, and ks265_event_query (a poll: how often it runs is the caller's timing).
+ * Every such call is also counted per thread, log file or none: after ks265_stub_fail_call(k) the k-th one of the thread that armed it returns KS265_FAIL instead of doing
+ * its work, once (tests/lane_put_main.c; 0 disarms; the entries a thread that hands pictures in reaches honour it: `if (LOGC(c)) return KS265_FAIL`);
+ * ks265_stub_thread_calls: this thread's calls since it armed or disarmed; ks265_stub_mark: a `mark` line, by which a test finds the thread that wrote it */
+static __thread long t_calls, t_fail_at;
+static int call_log(const char *name, const ks265_ctx *c, const ks265_frame *f, const void *ev, int arg)
 {
     static pthread_mutex_t mu = PTHREAD_MUTEX_INITIALIZER;
     static FILE *fp; static int tried, nthreads;
     static __thread int tid;
-    if (tried && !fp) return;
+    const int fail = ++t_calls == t_fail_at;
+    if (tried && !fp) return fail;
     pthread_mutex_lock(&mu);
     if (!tried) { const char *p = getenv("KS265_STUB_CALL_LOG"); tried = 1; if (p) fp = fopen(p, "a"); }
     if (fp) {
@@ -48,10 +53,14 @@ static void call_log(const char *name, const ks265_ctx *c, const ks265_frame *f,
         fflush(fp);
     }
     pthread_mutex_unlock(&mu);
+    return fail;
 }
 #define LOGC(c) call_log(__func__, c, NULL, NULL, 0)
 #define LOGE(c, ev) call_log(__func__, c, NULL, ev, 0)
 #define LOGF(c, f, arg) call_log(__func__, c, f, NULL, arg)
+void ks265_stub_fail_call(long k) { t_calls = 0; t_fail_at = k; }
+long ks265_stub_thread_calls(void) { return t_calls; }
+void ks265_stub_mark(void) { (void)call_log("mark", NULL, NULL, NULL, 0); }
 
 const char *ks265_version(void) { return "ks265hip CPU stub (tests only)"; }
 const char *ks265_last_error(ks265_ctx *c) { (void)c; return "stub"; }
@@ -110,10 +119,10 @@ int ks265_dev_free(ks265_ctx *c, void *p) { (void)c; if (p) live(LIVE_DEV, -1); 
 int ks265_host_malloc(ks265_ctx *c, void **p, size_t n) { return stub_malloc(c, p, n, "host_malloc", LIVE_PINNED); }
 int ks265_host_register(ks265_ctx *c, void *p, size_t n) { (void)c; (void)p; (void)n; return getenv("KS265_STUB_NO_REGISTER") ? KS265_FAIL : KS265_OK; }   /* (every byte of the stand-in's host is "DMA-able") */
 int ks265_host_unregister(ks265_ctx *c, void *p) { (void)c; (void)p; return KS265_OK; }
-int ks265_memcpy_h2d_sync(ks265_ctx *c, void *d, const void *s, size_t n) { LOGC(c); memcpy(d, s, n); return KS265_OK; }
+int ks265_memcpy_h2d_sync(ks265_ctx *c, void *d, const void *s, size_t n) { if (LOGC(c)) return KS265_FAIL; memcpy(d, s, n); return KS265_OK; }
 int ks265_host_free(ks265_ctx *c, void *p) { (void)c; if (p) live(LIVE_PINNED, -1); free(p); return KS265_OK; }
 static int stub_fast(void);
-int ks265_memcpy_h2d_async(ks265_ctx *c, void *d, const void *s, size_t n) { LOGC(c); if (n > (1u << 20) && stub_fast()) return KS265_OK;   /* (KS265_STUB_FAST: a picture's upload is the copy engine's time, not the caller's) */
+int ks265_memcpy_h2d_async(ks265_ctx *c, void *d, const void *s, size_t n) { if (LOGC(c)) return KS265_FAIL; if (n > (1u << 20) && stub_fast()) return KS265_OK;   /* (KS265_STUB_FAST: a picture's upload is the copy engine's time, not the caller's) */
     memcpy(d, s, n); return KS265_OK; }
 int ks265_memcpy_d2d_async(ks265_ctx *c, void *d, const void *s, size_t n) { LOGC(c); memcpy(d, s, n); return KS265_OK; }
 int ks265_memcpy_d2h_async(ks265_ctx *c, void *d, const void *s, size_t n) { LOGC(c); memcpy(d, s, n); return KS265_OK; }
@@ -125,8 +134,8 @@ int ks265_event_create(ks265_ctx *c, void **ev)                        /* an eve
     if (*ev) { ((int *)*ev)[1] = __atomic_add_fetch(&ids, 1, __ATOMIC_RELAXED); live(LIVE_EVENT, 1); }
     return *ev ? KS265_OK : KS265_OUTOFMEMORY;
 }
-int ks265_event_record(ks265_ctx *c, void *ev) { LOGE(c, ev); *(int *)ev = 0; return KS265_OK; }
-int ks265_event_wait(ks265_ctx *c, void *ev) { LOGE(c, ev); return KS265_OK; }
+int ks265_event_record(ks265_ctx *c, void *ev) { if (LOGE(c, ev)) return KS265_FAIL; *(int *)ev = 0; return KS265_OK; }
+int ks265_event_wait(ks265_ctx *c, void *ev) { return LOGE(c, ev) ? KS265_FAIL : KS265_OK; }
 /* KS265_STUB_EVENT_LAG = n: an event is reported done only at the n-th query after its record (the device stand-in runs everything at once: this is how the host's
  * "not ready yet" paths get exercised) */
 int ks265_event_query(ks265_ctx *c, void *ev, int *done)
@@ -146,7 +155,7 @@ int ks265_event_query(ks265_ctx *c, void *ev, int *done)
     ++*n;
     return KS265_OK;
 }
-int ks265_stream_wait_event(ks265_ctx *c, void *ev) { LOGE(c, ev); return KS265_OK; }
+int ks265_stream_wait_event(ks265_ctx *c, void *ev) { return LOGE(c, ev) ? KS265_FAIL : KS265_OK; }
 int ks265_event_destroy(ks265_ctx *c, void *ev) { (void)c; if (ev) live(LIVE_EVENT, -1); free(ev); return KS265_OK; }
 
 int ks265_frame_geometry(const ks265_frame_cfg *cfg, ks265_frame_geom *geom)

@@ -150,7 +150,7 @@ int ks265_input_convert(ks265_ctx *c, const ks265_in_desc *d, uint8_t *dst)
 {
     if (!c || !d || !dst) return KS265_POINTER;
     if (!f_elem_size(d->format)) return ks265_u8_input_convert(c, d, dst);
-    LOGC(c);
+    if (LOGC(c)) return KS265_FAIL;
     const int r = stub_float_in_check(d);
     if (r) return r;
     const uint8_t *ch[3] = {(const uint8_t *)d->plane[0], (const uint8_t *)d->plane[1], (const uint8_t *)d->plane[2]};

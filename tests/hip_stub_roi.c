@@ -6,8 +6,8 @@
 #include <math.h>
 #include "../ks265codec_amd/host/ks265_roi.h"
 
-int ks265_wait_external(ks265_ctx *c, void *s) { LOGC(c); (void)s; return c ? KS265_OK : KS265_POINTER; }
-int ks265_external_wait_event(ks265_ctx *c, void *s, void *ev) { LOGE(c, ev); (void)s; return c && ev ? KS265_OK : KS265_POINTER; }
+int ks265_wait_external(ks265_ctx *c, void *s) { if (LOGC(c)) return KS265_FAIL; (void)s; return c ? KS265_OK : KS265_POINTER; }
+int ks265_external_wait_event(ks265_ctx *c, void *s, void *ev) { if (LOGE(c, ev)) return KS265_FAIL; (void)s; return c && ev ? KS265_OK : KS265_POINTER; }
 
 /* the stand-in knows no allocations: NULL is a KS265_POINTER, what the description itself shows wrong a KS265_NOTSUPPORTED, as on the device */
 int ks265_roi_validate(ks265_ctx *c, const ks265_roi_desc *d)
@@ -21,7 +21,7 @@ int ks265_roi_validate(ks265_ctx *c, const ks265_roi_desc *d)
 
 int ks265_roi_reduce(ks265_ctx *c, const ks265_roi_desc *d, int width, int height, int32_t *rec)
 {
-    LOGC(c);
+    if (LOGC(c)) return KS265_FAIL;
     if (!rec) return KS265_POINTER;
     const int r = ks265_roi_validate(c, d);
     if (r) return r;

@@ -28,7 +28,7 @@ static uint8_t clip255(int v) { return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
 
 int ks265_input_convert(ks265_ctx *c, const ks265_in_desc *d, uint8_t *dst)
 {
-    LOGC(c);
+    if (LOGC(c)) return KS265_FAIL;
     if (!c || !d || !dst) return KS265_POINTER;
     const int r = stub_in_check(d);
     if (r) return r;
@@ -120,7 +120,7 @@ int ks265_input_scale(ks265_ctx *c, const ks265_scale_plan *p, const ks265_in_de
         src[0] = scratch; src[1] = scratch + sn; src[2] = scratch + sn + sn / 4;
         pitch[0] = p->sw; pitch[1] = pitch[2] = p->sw / 2;
     } else if (s->format == KS265_IN_NV12) { src[2] = src[1] + 1; pitch[2] = pitch[1]; step[1] = step[2] = 2; }
-    LOGC(c);
+    if (LOGC(c)) return KS265_FAIL;
     int16_t *tmp = (int16_t *)malloc((size_t)p->sh * p->dw * sizeof(int16_t));
     if (!tmp) return KS265_OUTOFMEMORY;
     for (int k = 0; k < 3; ++k) {

@@ -48,7 +48,7 @@ int ks265_input_pad(ks265_ctx *c, const ks265_in_desc *d, int cw, int ch, uint8_
     const int r = ks265_input_pad_validate(c, d, cw, ch);
     if (r) return r;
     if (!dst) return KS265_POINTER;
-    call_log(__func__, c, NULL, NULL, d->format);
+    if (call_log(__func__, c, NULL, NULL, d->format)) return KS265_FAIL;
     pthread_mutex_lock(&g_pad_mu);
     if (g_npad < 4096) g_pad[g_npad] = (StubPadCall){d->format, d->width, d->height, cw, ch, {d->pitch[0], d->pitch[1], d->pitch[2]}};
     ++g_npad;

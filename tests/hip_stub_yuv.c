@@ -124,7 +124,7 @@ int ks265_y_input_convert(ks265_ctx *c, const ks265_in_desc *d, uint8_t *dst)
     if (!c || !d || !dst) return KS265_POINTER;
     ks265_in_desc loc; int f[4], r;
     if (!y_route(&d, &loc, f, &r)) return ks265_f_input_convert(c, d, dst);
-    call_log("ks265_input_convert", c, NULL, NULL, 0);                  /* (LOGC would write this function's identifier) */
+    if (call_log("ks265_input_convert", c, NULL, NULL, 0)) return KS265_FAIL;                /* (LOGC would write this function's identifier) */
     if (r) return r;
     y_convert(d, f, dst);
     return KS265_OK;
