@@ -667,7 +667,9 @@ int ks265_ref_pick(ks265_frame *f, int nref, const ks265_pu *const *dev_pu, ks26
  * (a key picture: intra_candidates = the mode pre-selection, intra_pass = the wavefront reconstruction) */
 int ks265_frame_set_profiling(ks265_frame *f, int enable);
 int ks265_frame_stage_ms(ks265_frame *f, float ms[8]);
-/* duration of the last me_int_kernel launch alone (the SAD kernel: stage me_integer also holds the pre-search and the propagation round); -1 = none */
+/* duration of the last me_int_kernel launch alone (the SAD kernel: stage me_integer also holds the pre-search and the propagation round); -1 = none.  A picture with
+ * several searches (B, multi-reference) runs them all in one launch: the figure is that launch's duration divided by the searches it carried - a per-search figure, as
+ * when every search had a launch of its own */
 int ks265_frame_me_int_ms(ks265_frame *f, float *ms);
 /* accessors to the frame object's internal workspace (device pointers) */
 int16_t *ks265_frame_levels(ks265_frame *f, int comp);

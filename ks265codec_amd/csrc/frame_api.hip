@@ -38,14 +38,8 @@ int ks265_frame_create(ks265_ctx *ctx, const ks265_frame_cfg *cfg, ks265_frame *
     const size_t npx = (size_t)g.W * g.H;
     r = KS265_OK;
     for (int i = 0; i < 2 && !r; ++i) r = dev_alloc(ctx, (void **)&f->pu[i], (size_t)geom.bytes_pu, true);
-    if (!r && cfg->propagate) r = dev_alloc(ctx, (void **)&f->pu_s, (size_t)geom.bytes_pu, true);
     if (!r && cfg->bframes > 0) {
         r = dev_alloc(ctx, (void **)&f->pu1, (size_t)geom.bytes_pu, true);
-        if (!r && cfg->propagate) r = dev_alloc(ctx, (void **)&f->pu_s2, (size_t)geom.bytes_pu, true);
-        if (!r) r = ks265_hip(ctx, hipStreamCreateWithFlags(&f->side, hipStreamNonBlocking));
-        if (!r) r = ks265_hip(ctx, hipEventCreateWithFlags(&f->ev_fork, hipEventDisableTiming));
-        if (!r) r = ks265_hip(ctx, hipEventCreateWithFlags(&f->ev_join, hipEventDisableTiming));
-        f->b_parallel = getenv("KS265_B_SERIAL") ? 0 : 1;
         if (!r) r = dev_alloc(ctx, (void **)&f->pub, (size_t)geom.ctu_cols * geom.ctu_rows * 85 * sizeof(ks265_pu_b), true);
     }
     for (int x = 0; x + 1 < cfg->refs && !r; ++x) {              /* list-0 pictures 1..refs-1 of multi-reference P pictures */
@@ -88,16 +82,16 @@ void ks265_frame_destroy(ks265_frame *f)
     if (f->ctx) { (void)hipSetDevice(f->ctx->device); (void)hipStreamSynchronize(f->ctx->stream); }
     for (int i = 0; i <= KS_NSTAGE; ++i)
         if (f->ev[i]) (void)hipEventDestroy(f->ev[i]);
-    if (f->side) { (void)hipStreamSynchronize(f->side); (void)hipStreamDestroy(f->side); }
-    for (int i = 0; i < 2; ++i) { if (f->me_work_all[i]) (void)hipFree(f->me_work_all[i]); if (f->me_order_all[i]) (void)hipFree(f->me_order_all[i]); }
-    if (f->ev_fork) (void)hipEventDestroy(f->ev_fork);
-    if (f->ev_join) (void)hipEventDestroy(f->ev_join);
-    for (int i = 0; i < 10; ++i)
-        if (f->pyr2[i] && f->pyr2[i] != f->pyr[i]) (void)hipFree(f->pyr2[i]);
-    void *ptrs[] = {f->rq_coef, f->rq_pack_lvl, f->rq_pack_coef, f->rq_tus, f->rq_pos, f->rq_ctr, f->rq_out, f->rq_tab, f->rq_lam, f->rq_sigmask, f->rq_hidden, f->ic_work, f->pu1_x[0], f->pu1_x[1], f->pu1_x[2], f->ridx[0], f->ridx[1], f->pu_s2, f->pu1, f->pu_s, f->pub, f->pu[0], f->pu[1], f->cu8, f->sao, f->sao_ws, f->lvl[0], f->lvl[1], f->lvl[2], f->deb[0], f->deb[1], f->deb[2], f->sse, f->sse_acc, f->ssim_acc, f->hash_acc, f->cu8_tmp, f->progress, f->mats, f->icost, f->rect, f->pu_x[0], f->pu_x[1], f->pu_x[2]};
+    for (int k = KS_BATCH_MAX - 1; k >= 0; --k) {                    /* the search workspace sets (ks_search_ws); the source pyramid is set 0's */
+        KsSearchWs &w = f->ws[k];
+        for (int i = 0; i < 10; ++i)
+            if (w.pyr[i] && (k == 0 || w.pyr[i] != f->ws[0].pyr[i])) (void)hipFree(w.pyr[i]);
+        if (w.pu_s) (void)hipFree(w.pu_s);
+        if (w.work) (void)hipFree(w.work);
+        if (w.order) (void)hipFree(w.order);
+    }
+    void *ptrs[] = {f->rq_coef, f->rq_pack_lvl, f->rq_pack_coef, f->rq_tus, f->rq_pos, f->rq_ctr, f->rq_out, f->rq_tab, f->rq_lam, f->rq_sigmask, f->rq_hidden, f->ic_work, f->pu1_x[0], f->pu1_x[1], f->pu1_x[2], f->ridx[0], f->ridx[1], f->pu1, f->pub, f->pu[0], f->pu[1], f->cu8, f->sao, f->sao_ws, f->lvl[0], f->lvl[1], f->lvl[2], f->deb[0], f->deb[1], f->deb[2], f->sse, f->sse_acc, f->ssim_acc, f->hash_acc, f->cu8_tmp, f->progress, f->mats, f->icost, f->rect, f->pu_x[0], f->pu_x[1], f->pu_x[2]};
     for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    for (uint8_t *p : f->pyr)
         if (p) (void)hipFree(p);
     if (f->qp_eff) (void)hipFree(f->qp_eff);
     delete f;
@@ -139,19 +133,6 @@ int ks265_frame_set_picture_skip(ks265_frame *f, int skip_rd)
     return KS265_OK;
 }
 
-/* stage A (+ A2): the integer search of src in one reference picture, then cfg.propagate rounds of vector propagation; the records end up in pu */
-static int me_search(ks265_frame *f, ks265_pic src, ks265_pic ref, const ks265_pu *prev, ks265_pu *pu)
-{
-    const int n = f->cfg.propagate;
-    ks265_pu *a = (n & 1) ? f->pu_s : pu, *b = (n & 1) ? pu : f->pu_s;      /* n rounds swap sides n times */
-    int r = ks265_me_integer(f, src, ref, prev, a);
-    for (int i = 0; i < n && !r; ++i) {
-        r = ks265_me_propagate(f, src, ref, a, b);
-        ks265_pu *t = a; a = b; b = t;
-    }
-    return r;
-}
-
 /* the records of the previous picture (CU map, levels, SAO parameters) may still be read on another stream (ks265_frame_pack_compact_on): the host names the event that
  * ends that, and the picture waits for it right before its first kernel that writes a record - its search runs beside the previous picture's drain */
 int ks265_frame_set_records_fence(ks265_frame *f, void *ev)
@@ -167,42 +148,7 @@ static int records_fence(ks265_frame *f)
     f->rec_fence = nullptr;
     return ks265_hip(f->ctx, hipStreamWaitEvent(f->ctx->stream, (hipEvent_t)ev, 0));
 }
-}  // extern "C": the sequencer and its helpers (the chains of a fork are callables)
-
-/* The searches of one picture as two independent chains (pre-search, integer search, propagation, sub-pel refinement: ~ 0.4 ms each at 2160p, each kernel with a long tail
- * of half-empty CUs - an anchor with three pictures takes two chains' time instead of three).  Where the frame can fork, side_chain is enqueued on the side stream with its own
- * workspace and runs beside main_chain; both have finished, for the context's stream, when this returns.  Otherwise main_chain, then side_chain, on the one stream.  A chain
- * is a callable that enqueues on the stream the context holds at the moment.  (A picture being captured as a graph stays on the one stream: the fork's host-side workspace
- * swaps are not part of a graph.)  caller_can: the term of the condition that only one caller has */
-template <typename Side, typename Main>
-static int search_forked(ks265_frame *f, ks265_pic src, bool caller_can, Side side_chain, Main main_chain)
-{
-    int r;
-    if (!(caller_can && f->b_parallel && !f->ctx->capturing && f->side && f->cfg.pre_search && (!f->cfg.propagate || f->pu_s2))) {
-        if ((r = main_chain())) return r;
-        return side_chain();
-    }
-    if ((r = ks265_presearch_source(f, src))) return r;                        /* the source pyramid both use, once, before the fork */
-    if ((r = ks265_hip(f->ctx, hipEventRecord(f->ev_fork, f->ctx->stream)))) return r;
-    if ((r = ks265_hip(f->ctx, hipStreamWaitEvent(f->side, f->ev_fork, 0)))) return r;
-    hipStream_t mainst = f->ctx->stream;
-    auto swap_ws = [&]() {
-        for (int i = 0; i < 10; ++i) { uint8_t *t = f->pyr[i]; f->pyr[i] = f->pyr2[i]; f->pyr2[i] = t; }
-        ks265_pu *t = f->pu_s; f->pu_s = f->pu_s2; f->pu_s2 = t;
-        if (f->me_work) { const bool side = f->me_work == f->me_work_all[0]; f->me_work = f->me_work_all[side]; f->me_order = f->me_order_all[side]; }
-    };
-    f->src_pyr_ready = true;
-    f->ctx->stream = f->side; swap_ws();
-    r = side_chain();
-    /* the join is recorded and waited for whatever happened after the fork: what the side stream has been handed keeps reading src / refs and writing this frame's
-     * workspace, and the host recycles those on its error path */
-    const int rj = ks265_hip(f->ctx, hipEventRecord(f->ev_join, f->side));
-    f->ctx->stream = mainst; swap_ws();
-    if (!r) r = main_chain();
-    f->src_pyr_ready = false;
-    const int rw = rj ? ks265_hip(f->ctx, hipStreamSynchronize(f->side)) : ks265_hip(f->ctx, hipStreamWaitEvent(f->ctx->stream, f->ev_join, 0));
-    return r ? r : rw;
-}
+}  // extern "C": the sequencer and its helpers
 
 /* The stage marks of the in-situ timing (ks265_frame_stage_ms): mark(n) records event n, which closes stage n - 1.  Only ks265_encode_picture's two kinds of picture (key,
  * one-reference P) are timed: every other kind marks nothing */
@@ -217,6 +163,33 @@ struct KsStageMarks {
         evi = stage_done + 1;
     }
 };
+
+/* The searches of one picture, all of the same source: n reference pictures, per search the temporal predictors (or null) and the records it fills.  Every stage of the chain
+ * (reference pyramids, pre-search, CTU order, integer search, propagation rounds, sub-pel refinement) is ONE launch for up to KS_BATCH_MAX searches, on the context's stream:
+ * each kernel of the chain ends in a tail of half-empty CUs, and inside one grid the tails of the searches overlap - the sub-pel stage (a work-group owns a CU), the
+ * propagation and the order kernels take less GPU time than with a launch per search, and the host makes nine launches per picture whatever the number of searches, no fork
+ * and no join (DESIGN.md 5 has the measurements, also what one in-order chain loses on an otherwise idle GPU).  More searches than KS_BATCH_MAX (a B picture with up to
+ * 4 + 4 pictures) go in chunks, which reuse the workspace sets.  One search (one-reference P pictures) is a batch of one through the same launches */
+static int search_chain(ks265_frame *f, ks265_pic src, int n, const ks265_pic *refs, const ks265_pu *const *prevs, ks265_pu *const *pus, KsStageMarks &mark)
+{
+    int r;
+    const bool pre = f->cfg.pre_search != 0;
+    const int rounds = f->cfg.propagate;
+    if (pre && (r = ks_presearch_source(f, src))) return r;        /* the source pyramid all searches use, once */
+    for (int first = 0; first < n; first += KS_BATCH_MAX) {
+        KsSearchBatch B{};
+        B.n = n - first < KS_BATCH_MAX ? n - first : KS_BATCH_MAX;
+        if ((r = ks_search_ws(f, B.n, pre))) return r;
+        for (int i = 0; i < B.n; ++i) B.s[i] = ks_search_entry(f, i, refs[first + i], prevs[first + i], pus[first + i]);
+        if (pre && (r = ks_presearch_batch(f, B))) return r;
+        if ((r = ks_me_integer_batch(f, src, B))) return r;
+        for (int i = 0; i < rounds; ++i)
+            if ((r = ks_me_propagate_batch(f, src, B, i))) return r;
+        mark(1);
+        if (f->cfg.subme && (r = ks_me_subpel_batch(f, src, B, rounds & 1))) return r;
+    }
+    return KS265_OK;
+}
 
 /* The back end of every picture.  in_place: the picture is coded without SAO and reconstructed and deblocked where it is handed over - no SAO launch, no copy */
 static int loop_filters(ks265_frame *f, ks265_pic src, bool in_place, ks265_pic recon_out, KsStageMarks &mark)
@@ -244,7 +217,7 @@ static int inter_back_end(ks265_frame *f, ks265_pic src, const KsPicLists &lists
 }
 
 /* Every inter picture: the searches, the PU records, the CU tree, the merge pass, the common back end.  The kinds:
- *   KS_P1  one list-0 picture; one-list records (ks265_pu), one search on the context's stream; the only kind with stage marks and with -part 1 among the P kinds
+ *   KS_P1  one list-0 picture; one-list records (ks265_pu), a batch of one search; the only kind with stage marks and with -part 1 among the P kinds
  *   KS_PN  several list-0 pictures: one search per picture, the per-PU choice (ks265_ref_decide) into two-list records whose list 1 does not exist (lists.pslice: in the
  *          records it is the nearest picture).  Its workspace may be missing on a frame object made for fewer tools: those stages are then left out (icost, cu8_tmp)
  *   KS_B   list 0 = pictures before this one in display order, list 1 = after it, each nearest first; ks265_ref_pick keeps per PU and list the cheapest picture, the
@@ -254,32 +227,24 @@ enum KsInterKind { KS_P1, KS_PN, KS_B };
 static int encode_inter(ks265_frame *f, KsInterKind kind, ks265_pic src, const KsPicLists &lists, ks265_pic recon_out)
 {
     const bool p1 = kind == KS_P1, b = kind == KS_B;
-    const int n0 = lists.n[0], n1 = lists.n[1];
+    const int n0 = lists.n[0];
     int r;
     KsStageMarks mark{f, p1 && f->profiling};
     ks265_pu *pu0 = f->pu[f->cur_pu];                          /* (a B picture: scratch - the next P picture overwrites it) */
     auto records = [&](int l, int i) { return i == 0 ? (l ? f->pu1 : pu0) : (l ? f->pu1_x[i - 1] : f->pu_x[i - 1]); };
-    /* the chain of pictures first .. last - 1 of list l: each searched and refined on its own (pre-search, integer search, propagation, sub-pel refinement; the temporal
-     * predictor belongs to a P picture's nearest picture only), then, for a whole list of several pictures, the per-PU choice */
-    auto chain = [&](int l, int first, int last) -> int {
-        const ks265_pu *pus[4];
-        int rr = 0;
-        for (int i = first; i < last && !rr; ++i) {
-            ks265_pu *pu = records(l, i);
-            pus[i] = pu;
-            rr = me_search(f, src, lists.pic[l][i], !b && i == 0 && f->have_prev ? f->pu[f->cur_pu ^ 1] : nullptr, pu);
-            if (!rr) mark(1);
-            if (!rr && f->cfg.subme) rr = ks265_me_subpel(f, src, lists.pic[l][i], pu);
+    /* every picture of both lists is searched and refined on its own (the temporal predictor belongs to a P picture's nearest picture only), all of them in the same
+     * launches; then, for a B picture's list of several pictures, the per-PU choice */
+    ks265_pic refv[8]; const ks265_pu *prevs[8]; ks265_pu *pus_all[8];
+    int ns = 0;
+    for (int l = 0; l < (b ? 2 : 1); ++l)
+        for (int i = 0; i < lists.n[l]; ++i, ++ns) {
+            refv[ns] = lists.pic[l][i];
+            prevs[ns] = !b && i == 0 && f->have_prev ? f->pu[f->cur_pu ^ 1] : nullptr;
+            pus_all[ns] = records(l, i);
         }
-        if (!rr && b && lists.multi) rr = ks265_ref_pick(f, last, pus, records(l, 0), f->ridx[l]);
-        return rr;
-    };
     mark(0);
-    /* B: list 1's chain on the side stream beside list 0's.  Several list-0 pictures: the farther pictures' chains beside the nearest picture's - unlike a B picture, this
-     * kind forks only once the side workspace exists (f->pyr2[0]: the first pre-search of the frame object allocates it).  The join is in front of the records' kernel */
-    if (p1) r = chain(0, 0, 1);
-    else if (b) r = search_forked(f, src, true, [&] { return chain(1, 0, n1); }, [&] { return chain(0, 0, n0); });
-    else r = search_forked(f, src, f->pyr2[0] != nullptr, [&] { return chain(0, 1, n0); }, [&] { return chain(0, 0, 1); });
+    r = search_chain(f, src, ns, refv, prevs, pus_all, mark);
+    for (int l = 0; l < 2 && !r && b && lists.multi; ++l) r = ks265_ref_pick(f, lists.n[l], pus_all + (l ? n0 : 0), records(l, 0), f->ridx[l]);
     if (r) return r;
     mark(2);
     const ks265_pu *pus[4] = {pu0, f->pu_x[0], f->pu_x[1], f->pu_x[2]};
@@ -396,7 +361,8 @@ int ks265_frame_set_profiling(ks265_frame *f, int enable)
     return KS265_OK;
 }
 
-/* the duration of the last me_int_kernel launch alone (HIP events on the frame's stream around that one launch; -1 = none since profiling was switched on): the SAD kernel
+/* the duration of the last me_int_kernel launch alone, per search it carried (HIP events on the frame's stream around that one launch, divided by the number of searches of
+ * the picture that shared it; -1 = none since profiling was switched on): the SAD kernel
  * of bench.py's roofline figure - stage 0 of ks265_frame_stage_ms also holds the pyramid pre-search and the propagation round */
 int ks265_frame_me_int_ms(ks265_frame *f, float *ms)
 {
@@ -407,6 +373,7 @@ int ks265_frame_me_int_ms(ks265_frame *f, float *ms)
     if (r) return r;
     *ms = -1.0f;
     if (f->ev_k_valid && hipEventElapsedTime(ms, f->ev_k[0], f->ev_k[1]) != hipSuccess) *ms = -1.0f;
+    else if (f->ev_k_valid && f->ev_k_n > 1) *ms /= (float)f->ev_k_n;
     return KS265_OK;
 }
 

@@ -29,6 +29,35 @@ struct KsGeom {
     long org_y, org_c;        // byte offset of sample (0,0) inside a padded plane
 };
 
+// The searches of one picture that share their launches.  Every stage of the search chain - reference pyramid, pre-search, CTU order, integer search, propagation,
+// sub-pel refinement - takes up to KS_BATCH_MAX searches of the same source picture in one grid: a work-group does for its search what it did when every search had launches
+// of its own, the tails of the searches overlap inside the grid instead of following each other.  One entry = one search's operands; passed to the kernels by value.
+#define KS_BATCH_MAX 4
+#define KS_ME_ORDER_MAX 16384           // CTUs of a picture whose integer search is dispatched heavy-first (me_order_kernel keeps a score per CTU in LDS)
+struct KsSearch {
+    const uint8_t *ref;                 // the reference picture's luma plane (padded)
+    uint8_t *r1, *r2, *r3;              // pre-search: its pyramid ...
+    short2 *cand, *mv1, *ctu_off;       // ... the CTUs' votes, the L1 vectors (null: no pre-search), the CTUs' window offsets (null: zero)
+    const ks265_pu *prev;               // temporal predictors (the nearest picture of a P picture; else null)
+    ks265_pu *a, *b;                    // the integer search writes a; propagation round i reads a and writes b (i even) or the reverse; KsSearchBatch::final names the last one written
+    const int *order; unsigned *work;   // heavy-first dispatch: this search's CTU order (null: the usual one) and the rounds it leaves behind (null: none)
+};
+struct KsSearchBatch { int n; KsSearch s[KS_BATCH_MAX]; };
+// entry i with selects (i is uniform: scalar selects) - an indexed load from the by-value array would lose the pointers' global address space
+__device__ __forceinline__ KsSearch ks_search_pick(const KsSearchBatch &B, int i)
+{
+    KsSearch s = B.s[0];
+#pragma unroll
+    for (int k = 1; k < KS_BATCH_MAX; ++k) {
+        const bool t = i == k;
+        s.ref = t ? B.s[k].ref : s.ref; s.r1 = t ? B.s[k].r1 : s.r1; s.r2 = t ? B.s[k].r2 : s.r2; s.r3 = t ? B.s[k].r3 : s.r3;
+        s.cand = t ? B.s[k].cand : s.cand; s.mv1 = t ? B.s[k].mv1 : s.mv1; s.ctu_off = t ? B.s[k].ctu_off : s.ctu_off; s.prev = t ? B.s[k].prev : s.prev;
+        s.a = t ? B.s[k].a : s.a; s.b = t ? B.s[k].b : s.b; s.order = t ? B.s[k].order : s.order; s.work = t ? B.s[k].work : s.work;
+    }
+    return s;
+}
+struct KsSearchWs { uint8_t *pyr[10]; ks265_pu *pu_s; unsigned *work; int *order; };
+
 struct ks265_frame {
     ks265_ctx *ctx = nullptr;
     ks265_frame_cfg cfg{};
@@ -39,7 +68,6 @@ struct ks265_frame {
     // (no fractional planes: every consumer interpolates from the reference picture itself, interp_dev.h)
     ks265_pu *pu_x[3] = {nullptr, nullptr, nullptr};
     ks265_pu *pu1 = nullptr;
-    ks265_pu *pu_s = nullptr;            // cfg.propagate: the other side of the propagation rounds
     ks265_pu_b *pub = nullptr;
     ks265_pu *pu[2] = {nullptr, nullptr};
     int cur_pu = 0;
@@ -62,16 +90,12 @@ struct ks265_frame {
     void *rect = nullptr;                                  // cfg.part: the 2NxN / Nx2N records of the P picture being coded (KsRect, 21 per CTU)
     int *ic_work = nullptr;                                // ... the CTUs that passed the candidates' gate: [0] = count, [4 ..] = CTU indices (round 5)
     uint32_t *icost = nullptr;                             // cfg.intra_inter: intra candidates of the P / B picture being coded (85 per CTU: cost << 6 | mode)
-    uint8_t *pyr[10] = {};              // pre-search (cfg.pre_search): L1 / L2 of the source, L1 / L2 of the reference, L2 / L1 vectors, the 16x16 field, L3 of both, CTU window offsets
-    // round 5: the two uni-directional searches of a B picture are independent chains of latency-bound kernels - list 1's runs on a side stream beside list 0's
-    // (ks265_encode_picture_b).  Its own pre-search workspace (the source pyramid [0] [1] [7] is shared and built once, before the fork), propagation scratch, stream, fork / join events
-    uint8_t *pyr2[10] = {};
-    ks265_pu *pu_s2 = nullptr;
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    // heavy-first dispatch of the integer search (frame_me_int.hip me_order_kernel): rounds per CTU wave of the previous search, the order built from them; [1] = the side stream's
-    unsigned *me_work = nullptr, *me_work_all[2] = {nullptr, nullptr};
-    int *me_order = nullptr, *me_order_all[2] = {nullptr, nullptr};
+    // One workspace set per search of a picture that runs in the same launches (KsSearchBatch above): pyr = the pre-search's planes (cfg.pre_search): L1 / L2 of the source,
+    // L1 / L2 of the reference, the CTUs' votes, L1 vectors, the 16x16 field, L3 of both, CTU window offsets - the source's [0] [1] [7] belong to set 0 and are shared by all;
+    // pu_s = the other side of the propagation rounds (cfg.propagate); work / order = the heavy-first dispatch of the integer search (frame_me_int.hip me_order_kernel):
+    // rounds per CTU wave of the set's previous search, the order built from them.  Set 0, and set 1 of a frame object made for B pictures, are allocated with the first
+    // search; sets 2 and 3 when a picture first searches that many pictures at once (ks_search_ws)
+    KsSearchWs ws[KS_BATCH_MAX] = {};
     int me_order_off = 0;               // KS265_ME_ORDER_OFF: experiments
     // cfg.rdoq (round 6; -rdoq 1 = the SDK's rdoq field, qy265enc.h:129): the luma transform blocks of inter CUs go through the reference's rdoQuant (rdoq_ops.hip) - front half of
     // ks265_reconstruct* (coefficients + levels rounded at 1 / 2 to planes), rdoq_prep_kernel (the blocks listed, packed, their significance masks and last positions), rdoq_kernel,
@@ -86,12 +110,11 @@ struct ks265_frame {
     bool rq_ready = false;
     uint8_t *ridx[2] = {nullptr, nullptr};              // multi-reference B pictures: per list the index of every PU's picture (ks265_ref_pick) ...
     ks265_pu *pu1_x[3] = {nullptr, nullptr, nullptr};   // ... and the records of list 1's pictures 1 .. refs - 1
-    bool src_pyr_ready = false;         // ks265_presearch: the source picture's pyramid is in place (skip its pyr_down launch)
-    int b_parallel = 1;                 // 0: the two searches one after the other on the context's stream (graph capture, experiments: KS265_B_SERIAL)
     // optional in-situ stage timing (HIP events on the context's stream, between the stages of ks265_encode_picture)
     bool profiling = false;
     hipEvent_t ev[KS_NSTAGE + 1] = {};
     hipEvent_t ev_k[2] = {}; bool ev_k_valid = false;      // profiling: around the me_int_kernel launch alone (the SAD kernel of the roofline figure: stage me_integer also holds pre-search + propagation)
+    int ev_k_n = 1;                                        // ... and the searches that launch carried (ks265_frame_me_int_ms reports the duration per search)
     bool ev_valid[KS_NSTAGE + 1] = {};
 };
 
@@ -157,7 +180,14 @@ __device__ __forceinline__ void ctu_mv_limits(const KsGeom &g, int range, int cx
 }
 
 int ks265_frame_build_matrices(ks265_frame *f);      // frame_recon.hip
-int ks265_presearch_source(ks265_frame *f, ks265_pic src);   // frame_presearch.hip
+// the search chain on batches (frame_presearch.hip, frame_me_int.hip, frame_me.hip; no argument checks: the sequencer and the exported one-search functions made them)
+int ks_search_ws(ks265_frame *f, int nsets, bool pyr);                          // workspace sets 0 .. nsets - 1 exist (allocated on first use; pyr: with the pre-search's planes)
+KsSearch ks_search_entry(const ks265_frame *f, int set, ks265_pic ref, const ks265_pu *prev, ks265_pu *pu);   // one search on workspace set `set`, its records ending up in pu
+int ks_presearch_source(ks265_frame *f, ks265_pic src);                         // the source picture's pyramid (once per picture)
+int ks_presearch_batch(ks265_frame *f, const KsSearchBatch &B);                 // reference pyramids, L3 votes, window offsets, L2 / L1 vectors
+int ks_me_integer_batch(ks265_frame *f, ks265_pic src, const KsSearchBatch &B); // CTU orders + the integer search
+int ks_me_propagate_batch(ks265_frame *f, ks265_pic src, const KsSearchBatch &B, int round);
+int ks_me_subpel_batch(ks265_frame *f, ks265_pic src, const KsSearchBatch &B, int final_b);   // final_b: the records are the entries' b (else a)
 int ks265_sao_off(ks265_frame *f, ks265_sao_param *sao, ks265_pic dst);   // frame_loop.hip: the tail of a picture coded without SAO, in place
 // the stages that read reference pictures, on explicit lists (the exported ks265_* functions of the same names wrap them; same argument checks)
 int ks_bi_decide(ks265_frame *f, ks265_pic src, const KsPicLists &lists, const ks265_pu *pu0, const ks265_pu *pu1, ks265_pu_b *pub);                                         // frame_me.hip

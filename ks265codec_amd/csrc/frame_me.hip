@@ -75,18 +75,26 @@ struct KsGroupPerLane {
 #endif
 struct KsSubme { int subme, satd, thr, flat, cap, cap_step, diag_fast; };
 template <int NC, bool SATD>
-__global__ __launch_bounds__(NC * 64, KS_SUBPEL_OCC) void me_subpel_kernel(KsGeom g, int lam, KsSubme K, const uint8_t *src, const uint8_t *ref, ks265_pu *pus)
+__global__ __launch_bounds__(NC * 64, KS_SUBPEL_OCC) void me_subpel_kernel(KsGeom g, int lam, KsSubme K, const uint8_t *src, KsSearchBatch B, int final_b)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nctu = g.ctu_cols * g.ctu_rows;
-    const int grp = ks_xcd_swizzle(blockIdx.x, (nctu + NC - 1) / NC);
+    const int nctu = g.ctu_cols * g.ctu_rows, ngrp = (nctu + NC - 1) / NC;
+    // a batch of S searches: 8 x S x ceil(groups / 8) work-groups; block 8 (j S + s) + x is what block 8 j + x of search s is when the search has a launch of its own - the same
+    // group on the same XCD, the searches interleaved; the blocks past the end of a search's groups leave at once (in front of every barrier)
+    const unsigned bk = blockIdx.x >> 3, bj = bk / (unsigned)B.n;
+    const int bi = 8 * (int)bj + (int)(blockIdx.x & 7u);
+    if (bi >= ngrp) return;
+    const KsSearch sb = ks_search_pick(B, (int)(bk - bj * (unsigned)B.n));
+    const uint8_t *ref = sb.ref;
+    ks265_pu *pus = final_b ? sb.b : sb.a;
+    const int grp = ks_xcd_swizzle(bi, ngrp);
     // this wave keeps the books of one CTU, all four levels.  The group's CTUs are SPREAD over the picture (wave w takes CTU w x groups + g), not neighbours: at 2160p the kernel is
     // one round of 255 work-groups on 256 compute units, so it lasts as long as its busiest work-group, and a work-group's work is the number of distinct (tile, centre) items of
     // its eight CTUs - busy CTUs are neighbours (a moving edge), spread they even out: 0.182 -> 0.157 ms (round 5; KS_SUBPEL_ADJACENT restores the old grouping)
 #ifdef KS_SUBPEL_ADJACENT
     const int ctu = grp * NC + wave;
 #else
-    const int ctu = wave * ((nctu + NC - 1) / NC) + grp;
+    const int ctu = wave * ngrp + grp;
 #endif
     const bool have = ctu < nctu;
     ks265_pu *cp = pus + (long)(have ? ctu : 0) * 85;
@@ -582,16 +590,24 @@ __global__ __launch_bounds__(NC * 64, KS_SUBPEL_OCC) void me_subpel_kernel(KsGeo
     }
 }
 
+int ks_me_subpel_batch(ks265_frame *f, ks265_pic src, const KsSearchBatch &B, int final_b)
+{
+    const ks265_frame_cfg &c = f->cfg;
+    const KsSubme K = {c.subme, c.sub_satd, c.sub_thr, c.sub_flat, c.sub_cap, c.sub_cap_step, c.sub_diag_fast};
+    const int ngrp = (f->g.ctu_cols * f->g.ctu_rows + KS_SUBPEL_NC - 1) / KS_SUBPEL_NC;
+    const dim3 grid(8u * (unsigned)B.n * (unsigned)((ngrp + 7) / 8)), block(KS_SUBPEL_NC * 64);
+    if (c.sub_satd) hipLaunchKernelGGL((me_subpel_kernel<KS_SUBPEL_NC, true>), grid, block, 0, f->ctx->stream, f->g, f->cfg.lambda_q4, K, src.y, B, final_b);
+    else hipLaunchKernelGGL((me_subpel_kernel<KS_SUBPEL_NC, false>), grid, block, 0, f->ctx->stream, f->g, f->cfg.lambda_q4, K, src.y, B, final_b);
+    return ks265_check_launch(f->ctx);
+}
+
 extern "C" int ks265_me_subpel(ks265_frame *f, ks265_pic src, ks265_pic ref, ks265_pu *pu)
 {
     KS_FRAME_CHECK(f);
     if (!src.y || !ref.y || !pu) return KS265_POINTER;
-    const ks265_frame_cfg &c = f->cfg;
-    const KsSubme K = {c.subme, c.sub_satd, c.sub_thr, c.sub_flat, c.sub_cap, c.sub_cap_step, c.sub_diag_fast};
-    const dim3 grid((f->g.ctu_cols * f->g.ctu_rows + KS_SUBPEL_NC - 1) / KS_SUBPEL_NC), block(KS_SUBPEL_NC * 64);
-    if (c.sub_satd) hipLaunchKernelGGL((me_subpel_kernel<KS_SUBPEL_NC, true>), grid, block, 0, f->ctx->stream, f->g, f->cfg.lambda_q4, K, src.y, ref.y, pu);
-    else hipLaunchKernelGGL((me_subpel_kernel<KS_SUBPEL_NC, false>), grid, block, 0, f->ctx->stream, f->g, f->cfg.lambda_q4, K, src.y, ref.y, pu);
-    return ks265_check_launch(f->ctx);
+    KsSearchBatch B{};
+    B.n = 1; B.s[0].ref = ref.y; B.s[0].a = pu;
+    return ks_me_subpel_batch(f, src, B, 0);
 }
 
 

@@ -403,9 +403,15 @@ __device__ __forceinline__ int me_group(const KsGeom &g, int cx, int cy, int ran
 // The order: block index b runs on XCD b % 8, and ks_xcd_swizzle gives every XCD a contiguous raster range of CTUs (neighbours share window halos in one L2).  Each XCD's range
 // keeps its XCD: within it the heavy CTUs (the heaviest scores that together hold at most a tenth of the picture's CTUs) come first, the others follow in their usual order;
 // the k-th CTU of XCD x's list is dispatched as block 8 k + x.  One wave per XCD, ranks by ballots.
-#define ME_ORDER_MAX 16384
-__global__ __launch_bounds__(512) void me_order_kernel(int n, int cols, const unsigned *work, int *order)
+// A batch of searches: one work-group per search (blockIdx.x), each from its own counters to its own order.  me_int_kernel then takes the k-th CTU of XCD x's list of
+// search s of S as block 8 (k S + s) + x: a CTU of any search runs on the XCD it runs on alone, the searches interleave, and the heavy CTUs of all of them come before
+// the light ones (a search with fewer heavy CTUs on an XCD starts its light ones a few blocks early).
+#define ME_ORDER_MAX KS_ME_ORDER_MAX
+__global__ __launch_bounds__(512) void me_order_kernel(int n, int cols, KsSearchBatch B)
 {
+    const KsSearch sb = ks_search_pick(B, (int)blockIdx.x);
+    const unsigned *work = sb.work;
+    int *order = const_cast<int *>(sb.order);
     __shared__ unsigned char sc[ME_ORDER_MAX];
     __shared__ int part[2][8];
     const int tid = threadIdx.x, lane = tid & 63, x = tid >> 6;
@@ -453,16 +459,27 @@ __global__ __launch_bounds__(512) void me_order_kernel(int n, int cols, const un
     }
 }
 
-__global__ __launch_bounds__(256, 3) void me_int_kernel(KsGeom g, int range, int lam, int method, int hex_thr, const uint8_t *src, const uint8_t *ref,
-                                                        const ks265_pu *prev, ks265_pu *out, const short2 *field, int nb0x, int nb0y, const short2 *ctu_off,
-                                                        const int *order, unsigned *work)
+// The grid is 8 x S x ceil(nctu / 8) work-groups for the S searches of the batch: block b = 8 K + x runs on XCD x and takes the k-th CTU of XCD x's list of search
+// s = K % S, k = K / S (me_order_kernel; without an order: ks_xcd_swizzle's list).  The up to 7 S blocks past the end of a list (nctu no multiple of 8) leave at once.
+__global__ __launch_bounds__(256, 3) void me_int_kernel(KsGeom g, int range, int lam, int method, int hex_thr, const uint8_t *src, int nb0x, int nb0y, KsSearchBatch B)
 {
     __shared__ __attribute__((aligned(16))) MeLds L;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nctu = g.ctu_cols * g.ctu_rows, xcd = (int)(blockIdx.x & 7u);
+    const unsigned kk = blockIdx.x >> 3, ki = kk / (unsigned)B.n;
+    if ((int)ki >= (nctu >> 3) + (xcd < (nctu & 7) ? 1 : 0)) return;                   // (the whole work-group, in front of every barrier)
+    const KsSearch sb = ks_search_pick(B, (int)(kk - ki * (unsigned)B.n));
+    const uint8_t *ref = sb.ref;
+    const ks265_pu *prev = sb.prev;
+    ks265_pu *out = sb.a;
+    const short2 *field = sb.mv1, *ctu_off = sb.ctu_off;
+    const int *order = sb.order;
+    unsigned *work = sb.work;
+    const int bi = 8 * (int)ki + xcd;                                                   // the block this CTU is when its search has a launch of its own
 #ifdef KS_EXP_ME_CLOCK
     const long long tk0 = ME_NOW();
 #endif
-    const int ctu = order ? order[blockIdx.x] : ks_xcd_swizzle(blockIdx.x, g.ctu_cols * g.ctu_rows), cx = ctu % g.ctu_cols, cy = ctu / g.ctu_cols;
+    const int ctu = order ? order[bi] : ks_xcd_swizzle(bi, nctu), cx = ctu % g.ctu_cols, cy = ctu / g.ctu_cols;
 #ifdef KS_EXP_ME_TRACE
     if (tid == 0 && ctu < 4096) { unsigned hw; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw)); ks_me_trace[ctu * 8] = wall_clock64(); ks_me_trace[ctu * 8 + 7] = ((unsigned long long)blockIdx.x << 32) | hw; }
 #endif
@@ -596,11 +613,15 @@ __global__ __launch_bounds__(256, 3) void me_int_kernel(KsGeom g, int range, int
 // in `in` (across CTU borders), inside the CTU's limits, not its own, no repeats.  Step 2, per level: thread = (direction k, 8x8 block of the CTU) computes the SAD
 // of its block under candidate k of the PU the block belongs to (source: 8 aligned bytes per row, kept in registers for the four levels; reference: three aligned
 // dwords + v_alignbyte - the candidates are neighbours' vectors, their samples sit in L2); one thread per PU sums its blocks and takes the candidates in order,
-// strict '<' against the running best.  All 85 records go to `out`.
+// strict '<' against the running best.  All 85 records go to `out`.  blockIdx.y = search of the batch; flip: the round reads the entries' b and writes their a.
 #define PROP_NONE ((int)0x80000000)
-__global__ __launch_bounds__(256) void me_propagate_kernel(KsGeom g, int range, int lam, const uint8_t *src, const uint8_t *ref, const ks265_pu *in, ks265_pu *out,
-                                                           const short2 *ctu_off)
+__global__ __launch_bounds__(256) void me_propagate_kernel(KsGeom g, int range, int lam, const uint8_t *src, KsSearchBatch B, int flip)
 {
+    const KsSearch sb = ks_search_pick(B, (int)blockIdx.y);
+    const uint8_t *ref = sb.ref;
+    const ks265_pu *in = flip ? sb.b : sb.a;
+    ks265_pu *out = flip ? sb.a : sb.b;
+    const short2 *ctu_off = sb.ctu_off;
     __shared__ int cand[85][4];                // x & 0xFFFF | y << 16, PROP_NONE = no candidate
     __shared__ unsigned sad8[4][64];           // per direction and 8x8 block: the level in flight
     const int tid = threadIdx.x;
@@ -683,14 +704,35 @@ __global__ __launch_bounds__(256) void me_propagate_kernel(KsGeom g, int range, 
     }
 }
 
+int ks_me_propagate_batch(ks265_frame *f, ks265_pic src, const KsSearchBatch &B, int round)
+{
+    const dim3 grid(f->g.ctu_cols * f->g.ctu_rows, B.n), block(256);
+    hipLaunchKernelGGL(me_propagate_kernel, grid, block, 0, f->ctx->stream, f->g, f->cfg.me_range, f->cfg.lambda_q4, src.y, B, round & 1);
+    return ks265_check_launch(f->ctx);
+}
+
 extern "C" int ks265_me_propagate(ks265_frame *f, ks265_pic src, ks265_pic ref, const ks265_pu *in, ks265_pu *out)
 {
     KS_FRAME_CHECK(f);
     if (!src.y || !ref.y || !in || !out) return KS265_POINTER;
     if (in == out) return KS265_NOTSUPPORTED;
-    const dim3 grid(f->g.ctu_cols * f->g.ctu_rows), block(256);
-    hipLaunchKernelGGL(me_propagate_kernel, grid, block, 0, f->ctx->stream, f->g, f->cfg.me_range, f->cfg.lambda_q4, src.y, ref.y, in, out,
-                       f->cfg.pre_search ? (const short2 *)f->pyr[9] : nullptr);
+    KsSearchBatch B{};
+    B.n = 1; B.s[0].ref = ref.y; B.s[0].a = const_cast<ks265_pu *>(in); B.s[0].b = out;
+    B.s[0].ctu_off = f->cfg.pre_search ? (short2 *)f->ws[0].pyr[9] : nullptr;
+    return ks_me_propagate_batch(f, src, B, 0);
+}
+
+/* the CTU orders of the batch's searches (one work-group each), then their integer searches in one grid.  The pre-search fields of the entries are in place */
+int ks_me_integer_batch(ks265_frame *f, ks265_pic src, const KsSearchBatch &B)
+{
+    const int nctu = f->g.ctu_cols * f->g.ctu_rows;
+    const dim3 grid(8u * (unsigned)B.n * (unsigned)((nctu + 7) / 8)), block(256);
+    if (B.s[0].work) hipLaunchKernelGGL(me_order_kernel, dim3(B.n), dim3(512), 0, f->ctx->stream, nctu, f->g.ctu_cols, B);
+    const bool timed = f->profiling && f->ev_k[0];
+    if (timed) (void)hipEventRecord(f->ev_k[0], f->ctx->stream);
+    hipLaunchKernelGGL(me_int_kernel, grid, block, 0, f->ctx->stream, f->g, f->cfg.me_range, f->cfg.lambda_q4, f->cfg.me_method, f->cfg.me_hex_thr, src.y,
+                       (f->g.W + 15) / 16, (f->g.H + 15) / 16, B);
+    if (timed && f->ev_k[1]) { (void)hipEventRecord(f->ev_k[1], f->ctx->stream); f->ev_k_valid = true; f->ev_k_n = B.n; }
     return ks265_check_launch(f->ctx);
 }
 
@@ -699,29 +741,14 @@ extern "C" int ks265_me_integer(ks265_frame *f, ks265_pic src, ks265_pic ref, co
     KS_FRAME_CHECK(f);
     if (!src.y || !ref.y || !pu) return KS265_POINTER;
     if (f->cfg.me_method < 0 || f->cfg.me_method > 2) return KS265_NOTSUPPORTED;
-    const short2 *field = nullptr;
+    int r = ks_search_ws(f, 1, f->cfg.pre_search != 0);
+    if (r) return r;
+    KsSearchBatch B{};
+    B.n = 1; B.s[0] = ks_search_entry(f, 0, ref, prev_pu, pu);
+    B.s[0].a = pu;                                                           // (the stage alone: no propagation round follows in this call)
     if (f->cfg.pre_search) {                                                 // stage A0 first: the pre-search field of this (source, reference) pair
-        const int r = ks265_presearch(f, src, ref, nullptr, nullptr);
-        if (r) return r;
-        field = (const short2 *)f->pyr[5];                                   // the L1 vectors: the kernel does the full-resolution step itself
+        if ((r = ks_presearch_source(f, src))) return r;
+        if ((r = ks_presearch_batch(f, B))) return r;
     }
-    const int nctu = f->g.ctu_cols * f->g.ctu_rows;
-    const dim3 grid(nctu), block(256);
-    if (!f->me_work && !f->me_order_off && nctu <= ME_ORDER_MAX) {                                   // (first search of this frame object: the counters start at zero = the usual order)
-        for (int i = 0; i < 2; ++i) {
-            if (hipMalloc((void **)&f->me_work_all[i], (size_t)nctu * 16) != hipSuccess || hipMalloc((void **)&f->me_order_all[i], (size_t)nctu * 5 + 16) != hipSuccess) return KS265_OUTOFMEMORY;
-            (void)hipMemsetAsync(f->me_work_all[i], 0, (size_t)nctu * 16, f->ctx->stream);
-        }
-        if (hipStreamSynchronize(f->ctx->stream) != hipSuccess) return KS265_FAIL;      // (once per frame object: the side stream's first search reads its counters too)
-        f->me_work = f->me_work_all[0]; f->me_order = f->me_order_all[0];
-    }
-    if (f->me_work) {
-        hipLaunchKernelGGL(me_order_kernel, dim3(1), dim3(512), 0, f->ctx->stream, nctu, f->g.ctu_cols, (const unsigned *)f->me_work, f->me_order);
-    }
-    const bool timed = f->profiling && f->ev_k[0] && !(f->side && f->ctx->stream == f->side);      // the main chain's launch alone (a B picture's list-1 search runs on the side stream: its marks would pair with list 0's)
-    if (timed) (void)hipEventRecord(f->ev_k[0], f->ctx->stream);
-    hipLaunchKernelGGL(me_int_kernel, grid, block, 0, f->ctx->stream, f->g, f->cfg.me_range, f->cfg.lambda_q4, f->cfg.me_method, f->cfg.me_hex_thr, src.y, ref.y, prev_pu, pu,
-                       field, (f->g.W + 15) / 16, (f->g.H + 15) / 16, field ? (const short2 *)f->pyr[9] : nullptr, (const int *)f->me_order, f->me_work);
-    if (timed && f->ev_k[1]) { (void)hipEventRecord(f->ev_k[1], f->ctx->stream); f->ev_k_valid = true; }
-    return ks265_check_launch(f->ctx);
+    return ks_me_integer_batch(f, src, B);
 }

@@ -20,7 +20,7 @@ __device__ __forceinline__ unsigned avg_u8x4(unsigned a, unsigned b)        // p
 {
     return (a | b) - (((a ^ b) >> 1) & 0x7F7F7F7Fu);
 }
-__global__ __launch_bounds__(256) void pyr_down_kernel(KsGeom g, const uint8_t *plane, uint8_t *l1, uint8_t *l2, uint8_t *l3)
+__device__ __forceinline__ void pyr_down(const KsGeom &g, const uint8_t *plane, uint8_t *l1, uint8_t *l2, uint8_t *l3)
 {
     // one thread = 8x8 samples -> 4x4 of L1 -> 2x2 of L2 -> 1 of L3 (every level = downsample_c of the one above)
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
@@ -47,6 +47,13 @@ __global__ __launch_bounds__(256) void pyr_down_kernel(KsGeom g, const uint8_t *
     const unsigned v3 = avg_u8x4(o2[0], o2[1]), h3 = avg_u8x4(v3, v3 >> 8);
     l3[(long)(y0 >> 3) * W3 + (x0 >> 3)] = (uint8_t)(h3 & 0xFFu);
 }
+__global__ __launch_bounds__(256) void pyr_down_kernel(KsGeom g, const uint8_t *plane, uint8_t *l1, uint8_t *l2, uint8_t *l3) { pyr_down(g, plane, l1, l2, l3); }
+// the reference pictures of a batch of searches: blockIdx.z = search
+__global__ __launch_bounds__(256) void pyr_down_refs_kernel(KsGeom g, KsSearchBatch B)
+{
+    const KsSearch s = ks_search_pick(B, (int)blockIdx.z);
+    pyr_down(g, s.ref, s.r1, s.r2, s.r3);
+}
 
 // SAD of a bw x bh block of packed low-resolution planes, reference reads clamped to the picture (generic: any bw, bh <= 8)
 __device__ __forceinline__ unsigned sad_clamped_any(const uint8_t *cur, const uint8_t *ref, int W, int H, int x0, int y0, int bw, int bh, int mx, int my)
@@ -64,9 +71,12 @@ __device__ __forceinline__ unsigned sad_clamped_any(const uint8_t *cur, const ui
 // ------------------------------------------------------------------ L3 (1/8 resolution): one 8x8 block = one CTU, every vector of +-range/4.  A CTU VOTES for its
 // best vector when that vector lies where the zero-centred window does not reach and matches at least a quarter better than the best vector the window
 // covers; a vector with the votes of at least half of the CTUs becomes the picture's WINDOW OFFSET for stage A (x 8, clipped per CTU to the planes' margin).
-// One wave per CTU, lane = candidates; then one work-group counts the votes.
-__global__ __launch_bounds__(256) void presearch_l3_kernel(KsGeom g, int range, int R3, const uint8_t *c3, const uint8_t *r3, short2 *cand)
+// One wave per CTU, lane = candidates; then one work-group counts the votes.  blockIdx.y = search of the batch (presearch_vote_kernel: blockIdx.x).
+__global__ __launch_bounds__(256) void presearch_l3_kernel(KsGeom g, int range, int R3, const uint8_t *c3, KsSearchBatch B)
 {
+    const KsSearch sb = ks_search_pick(B, (int)blockIdx.y);
+    const uint8_t *r3 = sb.r3;
+    short2 *cand = sb.cand;
     // per wave: the CTU's 8x8 block (two dwords per row, masked to the picture) and its (8 + 2 R3) x (8 + 2 R3) window, clamped, in LDS
     extern __shared__ unsigned char lds3[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, ctu = blockIdx.x * 4 + wave;
@@ -117,8 +127,11 @@ __global__ __launch_bounds__(256) void presearch_l3_kernel(KsGeom g, int range, 
         cand[ctu] = make_short2((short)mx, (short)my);
     }
 }
-__global__ __launch_bounds__(256) void presearch_vote_kernel(KsGeom g, int R3, const short2 *cand, short2 *ctu_off)
+__global__ __launch_bounds__(256) void presearch_vote_kernel(KsGeom g, int R3, KsSearchBatch B)
 {
+    const KsSearch sb = ks_search_pick(B, (int)blockIdx.x);
+    const short2 *cand = sb.cand;
+    short2 *ctu_off = sb.ctu_off;
     extern __shared__ unsigned votes[];                                     // side x side counters, then the winner
     const int side = 2 * R3 + 1, n = side * side, nctu = g.ctu_cols * g.ctu_rows, t = threadIdx.x;
     __shared__ unsigned long long top;
@@ -181,11 +194,15 @@ __device__ __forceinline__ unsigned l2_column(const uint8_t *p, int ws, unsigned
 
 // Work-group = the 2 x 2 blocks of 8x8 L2 samples of ONE CTU, searched +-R around the CTU's window offset / 4.  LB lanes per block (LB = 32 when
 // 2R + 1 <= 32: two blocks per wave; else 64), lane = one horizontal displacement; 4 LB threads.  Then every block's four L1 children (+-2 around twice
-// its vector) by the same lanes.  dynamic LDS: window (8 + nrow) rows x ws bytes, then the 16 x 32 source tile.
+// its vector) by the same lanes.  dynamic LDS: window (8 + nrow) rows x ws bytes, then the 16 x 32 source tile.  blockIdx.z = search of the batch.
 template <int LB>
-__global__ __launch_bounds__(4 * LB) void presearch_l2l1_kernel(int W2, int H2, int R, const uint8_t *c2, const uint8_t *r2, int nbx, int nby,
-                                                                int W1, int H1, const uint8_t *c1, const uint8_t *r1, short2 *mv1, int nb1x, int nb1y, const short2 *ctu_off)
+__global__ __launch_bounds__(4 * LB) void presearch_l2l1_kernel(int W2, int H2, int R, const uint8_t *c2, int nbx, int nby,
+                                                                int W1, int H1, const uint8_t *c1, int nb1x, int nb1y, KsSearchBatch B)
 {
+    const KsSearch sb = ks_search_pick(B, (int)blockIdx.z);
+    const uint8_t *r2 = sb.r2, *r1 = sb.r1;
+    short2 *mv1 = sb.mv1;
+    const short2 *ctu_off = sb.ctu_off;
     extern __shared__ unsigned char lds[];
     constexpr int BX = 2, NT = 4 * LB;
     const int side = 2 * R + 1, nrow = (8 + 2 * R + 7) & ~7, wd = BX * 8 + 2 * R, wrows = 8 + nrow;
@@ -317,40 +334,85 @@ __global__ __launch_bounds__(256) void presearch_l0_kernel(KsGeom g, int range, 
     if (k == (int)(b & 15u) && key == b) field[blk] = make_short2((short)mx, (short)my);
 }
 
-static int presearch_alloc(ks265_frame *f)
+/* Workspace sets 0 .. nsets - 1 (frame_common.h KsSearchWs), each part where the frame object's tools need it.  A frame object made for B pictures gets two sets at once (its
+ * first B picture may be part of a captured graph: no allocation there); set 0's source pyramid is every set's */
+int ks_search_ws(ks265_frame *f, int nsets, bool pyr)
 {
-    if (f->pyr[0]) return KS265_OK;
-    const int W = f->g.W, H = f->g.H;
+    if (nsets < 2 && f->pu1) nsets = 2;
+    const int W = f->g.W, H = f->g.H, nctu = f->g.ctu_cols * f->g.ctu_rows;
     const size_t n1 = (size_t)(W / 2) * (H / 2), n2 = (size_t)(W / 4) * (H / 4), n3 = (size_t)(W / 8) * (H / 8);
     const size_t nb2 = (size_t)((W / 4 + 7) / 8) * ((H / 4 + 7) / 8), nb1 = (size_t)((W / 2 + 7) / 8) * ((H / 2 + 7) / 8), nb0 = (size_t)((W + 15) / 16) * ((H + 15) / 16);
-    const size_t nctu4 = (size_t)f->g.ctu_cols * f->g.ctu_rows * 4;
+    const size_t nctu4 = (size_t)nctu * 4;
     const size_t sz[10] = {n1 + 16, n2 + 16, n1 + 16, n2 + 16, (nb2 * 4 > nctu4 ? nb2 * 4 : nctu4) + 16 /* the CTUs' votes */, nb1 * 4, nb0 * 4, n3 + 16, n3 + 16, nctu4 + 16};
-    for (int i = 0; i < 10; ++i) {
-        void *p = nullptr;
-        const int r = ks265_hip(f->ctx, hipMalloc(&p, sz[i]));
-        if (r) return r;
-        f->pyr[i] = (uint8_t *)p;
-    }
-    if (f->pu1)                                                      /* B pictures: list 1's own reference pyramid, vector fields and window offsets (the source pyramid is shared) */
-        for (int i = 0; i < 10; ++i) {
-            if (i == 0 || i == 1 || i == 7) { f->pyr2[i] = f->pyr[i]; continue; }
-            void *p = nullptr;
-            const int r = ks265_hip(f->ctx, hipMalloc(&p, sz[i]));
+    for (int k = 0; k < nsets && k < KS_BATCH_MAX; ++k) {
+        KsSearchWs &w = f->ws[k];
+        if (pyr && !w.pyr[9])
+            for (int i = 0; i < 10; ++i) {
+                if (k && (i == 0 || i == 1 || i == 7)) { w.pyr[i] = f->ws[0].pyr[i]; continue; }
+                void *p = nullptr;
+                const int r = ks265_hip(f->ctx, hipMalloc(&p, sz[i]));
+                if (r) return r;
+                w.pyr[i] = (uint8_t *)p;
+            }
+        if (f->cfg.propagate && !w.pu_s) {
+            const int r = ks265_hip(f->ctx, hipMalloc((void **)&w.pu_s, (size_t)f->geom.bytes_pu));
             if (r) return r;
-            f->pyr2[i] = (uint8_t *)p;
+            if (hipMemsetAsync(w.pu_s, 0, (size_t)f->geom.bytes_pu, f->ctx->stream) != hipSuccess) return KS265_FAIL;
         }
+        if (!w.work && !f->me_order_off && nctu <= KS_ME_ORDER_MAX) {                 // (the counters start at zero = the usual order)
+            if (hipMalloc((void **)&w.work, (size_t)nctu * 16) != hipSuccess || hipMalloc((void **)&w.order, (size_t)nctu * 5 + 16) != hipSuccess) return KS265_OUTOFMEMORY;
+            if (hipMemsetAsync(w.work, 0, (size_t)nctu * 16, f->ctx->stream) != hipSuccess) return KS265_FAIL;
+        }
+    }
     return KS265_OK;
 }
 
-/* the source picture's pyramid alone (a B picture builds it once for its two searches) */
-int ks265_presearch_source(ks265_frame *f, ks265_pic src)
+KsSearch ks_search_entry(const ks265_frame *f, int set, ks265_pic ref, const ks265_pu *prev, ks265_pu *pu)
 {
-    KS_FRAME_CHECK(f);
-    int r = presearch_alloc(f);
+    const KsSearchWs &w = f->ws[set];
+    const bool odd = (f->cfg.propagate & 1) != 0;                    /* n rounds swap sides n times: the last one written is pu */
+    KsSearch s;
+    s.ref = ref.y; s.r1 = w.pyr[2]; s.r2 = w.pyr[3]; s.r3 = w.pyr[8];
+    s.cand = (short2 *)w.pyr[4]; s.mv1 = f->cfg.pre_search ? (short2 *)w.pyr[5] : nullptr; s.ctu_off = f->cfg.pre_search ? (short2 *)w.pyr[9] : nullptr;
+    s.prev = prev;
+    s.a = f->cfg.propagate && odd ? w.pu_s : pu; s.b = f->cfg.propagate && odd ? pu : w.pu_s;
+    s.order = w.work ? w.order : nullptr; s.work = w.work;
+    return s;
+}
+
+/* the source picture's pyramid (once per picture, whatever the number of its searches) */
+int ks_presearch_source(ks265_frame *f, ks265_pic src)
+{
+    int r = ks_search_ws(f, 1, true);
     if (r) return r;
     const KsGeom &g = f->g;
     const dim3 gd((unsigned)((g.W + 127) / 128), (unsigned)((g.H + 127) / 128));
-    hipLaunchKernelGGL(pyr_down_kernel, gd, dim3(256), 0, f->ctx->stream, g, src.y, f->pyr[0], f->pyr[1], f->pyr[7]);
+    hipLaunchKernelGGL(pyr_down_kernel, gd, dim3(256), 0, f->ctx->stream, g, src.y, f->ws[0].pyr[0], f->ws[0].pyr[1], f->ws[0].pyr[7]);
+    return ks265_check_launch(f->ctx);
+}
+
+/* stage A0 of a batch of searches of one source picture, whose pyramid is in place: per search the reference pyramid, the CTUs' votes, the window offsets, the L2 / L1 vectors */
+int ks_presearch_batch(ks265_frame *f, const KsSearchBatch &B)
+{
+    const KsGeom &g = f->g;
+    const int W1 = g.W / 2, H1 = g.H / 2, W2 = g.W / 4, H2 = g.H / 4;
+    const int nb2x = (W2 + 7) / 8, nb2y = (H2 + 7) / 8, nb1x = (W1 + 7) / 8, nb1y = (H1 + 7) / 8;
+    const uint8_t *c1 = f->ws[0].pyr[0], *c2 = f->ws[0].pyr[1], *c3 = f->ws[0].pyr[7];
+    hipStream_t st = f->ctx->stream;
+    const unsigned n = (unsigned)B.n;
+    const int R = max((f->cfg.me_range >> 2) - 1, 1), R3 = max(f->cfg.me_range >> 2, 1), wrows = 8 + ((8 + 2 * R + 7) & ~7);
+    if (2 * R + 1 > 64 || (2 * R3 + 1) * (2 * R3 + 1) > 65535) return KS265_NOTSUPPORTED;   // one lane per horizontal displacement (me_range <= 128)
+    hipLaunchKernelGGL(pyr_down_refs_kernel, dim3((unsigned)((g.W + 127) / 128), (unsigned)((g.H + 127) / 128), n), dim3(256), 0, st, g, B);
+    const int nctu = g.ctu_cols * g.ctu_rows;
+    const int wd3 = 8 + 2 * R3, ws3 = (((wd3 + 8 + 3) >> 2) | 1) << 2;
+    hipLaunchKernelGGL(presearch_l3_kernel, dim3((unsigned)((nctu + 3) / 4), n), dim3(256), (size_t)4 * (wd3 * ws3 + 64), st, g, f->cfg.me_range, R3, c3, B);
+    hipLaunchKernelGGL(presearch_vote_kernel, dim3(n), dim3(256), (size_t)(2 * R3 + 1) * (2 * R3 + 1) * 4, st, g, R3, B);
+    const int wd = 16 + 2 * R, ws = (((wd + 8 + 3) >> 2) | 1) << 2;
+    const dim3 gc((unsigned)g.ctu_cols, (unsigned)g.ctu_rows, n);
+    if (2 * R + 1 <= 32)
+        hipLaunchKernelGGL(presearch_l2l1_kernel<32>, gc, dim3(128), (size_t)(wrows * ws + 512), st, W2, H2, R, c2, nb2x, nb2y, W1, H1, c1, nb1x, nb1y, B);
+    else
+        hipLaunchKernelGGL(presearch_l2l1_kernel<64>, gc, dim3(256), (size_t)(wrows * ws + 512), st, W2, H2, R, c2, nb2x, nb2y, W1, H1, c1, nb1x, nb1y, B);
     return ks265_check_launch(f->ctx);
 }
 
@@ -359,31 +421,18 @@ extern "C" int ks265_presearch(ks265_frame *f, ks265_pic src, ks265_pic ref, int
     KS_FRAME_CHECK(f);
     if (!src.y || !ref.y) return KS265_POINTER;
     (void)hipSetDevice(f->ctx->device);
-    int r = presearch_alloc(f);
+    int r = ks_presearch_source(f, src);
     if (r) return r;
-    const KsGeom &g = f->g;
-    const int W1 = g.W / 2, H1 = g.H / 2, W2 = g.W / 4, H2 = g.H / 4;
-    const int nb2x = (W2 + 7) / 8, nb2y = (H2 + 7) / 8, nb1x = (W1 + 7) / 8, nb1y = (H1 + 7) / 8, nb0x = (g.W + 15) / 16, nb0y = (g.H + 15) / 16;
-    uint8_t *c1 = f->pyr[0], *c2 = f->pyr[1], *r1 = f->pyr[2], *r2 = f->pyr[3], *c3 = f->pyr[7], *r3 = f->pyr[8];
-    short2 *mv1 = (short2 *)f->pyr[5], *field = (short2 *)dev_field;      // dev_field = NULL: no stand-alone full-resolution step (ks265_me_integer does it itself)
-    short2 *ctu_off = dev_ctu_off ? (short2 *)dev_ctu_off : (short2 *)f->pyr[9];
-    hipStream_t st = f->ctx->stream;
-    const dim3 gd((unsigned)((g.W + 127) / 128), (unsigned)((g.H + 127) / 128));
-    if (!f->src_pyr_ready) hipLaunchKernelGGL(pyr_down_kernel, gd, dim3(256), 0, st, g, src.y, c1, c2, c3);
-    hipLaunchKernelGGL(pyr_down_kernel, gd, dim3(256), 0, st, g, ref.y, r1, r2, r3);
-    const int R = max((f->cfg.me_range >> 2) - 1, 1), R3 = max(f->cfg.me_range >> 2, 1), wrows = 8 + ((8 + 2 * R + 7) & ~7);
-    if (2 * R + 1 > 64 || (2 * R3 + 1) * (2 * R3 + 1) > 65535) return KS265_NOTSUPPORTED;   // one lane per horizontal displacement (me_range <= 128)
-    const int nctu = g.ctu_cols * g.ctu_rows;
-    const int wd3 = 8 + 2 * R3, ws3 = (((wd3 + 8 + 3) >> 2) | 1) << 2;
-    hipLaunchKernelGGL(presearch_l3_kernel, dim3((unsigned)((nctu + 3) / 4)), dim3(256), (size_t)4 * (wd3 * ws3 + 64), st, g, f->cfg.me_range, R3, c3, r3, (short2 *)f->pyr[4]);
-    hipLaunchKernelGGL(presearch_vote_kernel, dim3(1), dim3(256), (size_t)(2 * R3 + 1) * (2 * R3 + 1) * 4, st, g, R3, (const short2 *)f->pyr[4], ctu_off);
-    const int wd = 16 + 2 * R, ws = (((wd + 8 + 3) >> 2) | 1) << 2;
-    const dim3 gc((unsigned)g.ctu_cols, (unsigned)g.ctu_rows);
-    if (2 * R + 1 <= 32)
-        hipLaunchKernelGGL(presearch_l2l1_kernel<32>, gc, dim3(128), (size_t)(wrows * ws + 512), st, W2, H2, R, c2, r2, nb2x, nb2y, W1, H1, c1, r1, mv1, nb1x, nb1y, ctu_off);
-    else
-        hipLaunchKernelGGL(presearch_l2l1_kernel<64>, gc, dim3(256), (size_t)(wrows * ws + 512), st, W2, H2, R, c2, r2, nb2x, nb2y, W1, H1, c1, r1, mv1, nb1x, nb1y, ctu_off);
+    KsSearchBatch B{};
+    B.n = 1; B.s[0] = ks_search_entry(f, 0, ref, nullptr, nullptr);
+    B.s[0].mv1 = (short2 *)f->ws[0].pyr[5];                              // (whatever cfg.pre_search says: the stage API runs the stage)
+    B.s[0].ctu_off = dev_ctu_off ? (short2 *)dev_ctu_off : (short2 *)f->ws[0].pyr[9];
+    if ((r = ks_presearch_batch(f, B))) return r;
     // the full-resolution step: stage A does it itself from its LDS window (frame_me_int.hip); the stand-alone kernel serves the stage API
-    if (field) hipLaunchKernelGGL(presearch_l0_kernel, dim3((unsigned)((nb0x * nb0y + 15) / 16)), dim3(256), 0, st, g, f->cfg.me_range, src.y, ref.y, mv1, field, nb0x, nb0y, ctu_off);
+    if (dev_field) {
+        const KsGeom &g = f->g;
+        const int nb0x = (g.W + 15) / 16, nb0y = (g.H + 15) / 16;
+        hipLaunchKernelGGL(presearch_l0_kernel, dim3((unsigned)((nb0x * nb0y + 15) / 16)), dim3(256), 0, f->ctx->stream, g, f->cfg.me_range, src.y, ref.y, B.s[0].mv1, (short2 *)dev_field, nb0x, nb0y, B.s[0].ctu_off);
+    }
     return ks265_check_launch(f->ctx);
 }
