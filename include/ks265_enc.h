@@ -31,7 +31,19 @@
  *   - calcSsim (-ssim 1 | 2): the reference's ` ssim:` line behind `bitrate, psnr:` (8x8 windows), computed on the device in the same pass as the SSE; 2 adds one
  *     `ks265enc: poc N ssim Y U V` line per picture (the reference prints nothing per picture); totals and the last picture's values: ks265_enc_get_quality;
  *   - hash (not in the SDK; ks265_enc_set_default "hash" = `-hash N`, below): a decoded picture hash SEI message behind every picture, CRC or checksum, computed on the device;
- *   - transskip, tuIntra, vpp_*, 2-pass, long-term references, VBV / CVQ: accepted, ignored;
+ *   - vpp_denoise (0 off, 1 gentle, 2 medium, 3 aggressive; QY265ConfigParse "denoise" = `-denoise N`) and vpp_recur_filter (0 .. 30; "recur" = `-recur V`): a motion-compensated
+ *     temporal filter on the GPU, the last step a picture takes on its way in - behind the upload, the conversion, the scaler or the padding, in the caller's stream order, for
+ *     host pictures, acquired slots and device pictures alike (tests/denoise_ref.py is the specification of every byte).  Per 16x16 luma block of the coded
+ *     picture an exhaustive integer search (+-8) in the previous FILTERED picture; a block that matches (SAD below thr per sample) is blended towards its prediction, sample by
+ *     sample, by a weight that falls from weight / 32 to 0 as the difference grows to thr; one that does not stays as it is.  Levels 1 / 2 / 3 = (thr, weight) (6, 16) /
+ *     (10, 20) / (16, 24); vpp_recur_filter v > 0 replaces the weight by round(v), at least 1, and alone runs at thr 10.  These values are this build's choice (the reference's
+ *     Linux binaries have no VPP code); they were tried on synthetic noise only.  Everything downstream - the lookahead, the search, `analysis`, `devrecon`, -o - sees the
+ *     filtered picture, and -psnr / -ssim are measured AGAINST THE FILTERED PICTURE, as they are against the scaled one.  History: a lane's first picture has none, and neither
+ *     has the first picture of a GOP chunk dealt to a lane; a one-lane handle never restarts, the recursion runs across its periodic key pictures.  With several GOP lanes every
+ *     chunk therefore starts unfiltered and the stream differs between lane counts: the known limit - history is not carried between lanes or GPUs.  QY265EncoderReconfig
+ *     leaves the filter as opened.  Values outside the ranges, or a device library without ks265_input_denoise: QY265EncoderOpen fails with QY_NOTSUPPORTED.  Both 0 (the
+ *     default): no call, no allocation, no byte of the stream changes;
+ *   - transskip, tuIntra, the other vpp_* fields, 2-pass, long-term references, VBV / CVQ: accepted, ignored;
  *   - input pictures: the caller's planes are pinned in place and uploaded from where they lie inside QY265EncoderEncodeFrame; the caller may reuse its buffers when the call returns
  *     (the SDK requires them to stay valid until the frame is done);
  *   - analysis out (not in the SDK; ks265_enc_set_default "analysis", ks265_enc_get_device_analysis below): motion, modes, QP and block error of every picture as device arrays;

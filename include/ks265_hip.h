@@ -205,6 +205,24 @@ int ks265_output_convert(ks265_ctx *, const uint8_t *dev_i420, const ks265_in_de
 int ks265_input_pad_validate(ks265_ctx *, const ks265_in_desc *src, int coded_w, int coded_h);
 int ks265_input_pad(ks265_ctx *, const ks265_in_desc *src, int coded_w, int coded_h, uint8_t *dev_i420);
 int ks265_output_crop(ks265_ctx *, const uint8_t *dev_i420_coded, int coded_w, int coded_h, int w, int h, uint8_t *dev_i420);
+/* The temporal denoiser on the way in (input_denoise.hip; tests/denoise_ref.py is the specification of every byte).  One launch on the context's stream filters
+ * the packed I420 picture of width x height (positive multiples of 8, at most 8192: the coded size, so it runs behind ks265_input_pad) IN PLACE against the previous filtered
+ * picture: per 16x16 luma block (edge blocks the 8-wide / 8-tall remainder) an exhaustive integer search over |dx|, |dy| <= 8 among the vectors whose block lies inside the
+ * picture (cost = SAD + 16 (|dx| + |dy|), ties to the smaller |dx| + |dy|, then dy, then dx), the block left as it is when the winner's SAD >= thr x samples, else every sample
+ * blended with its prediction by a weight that falls from `weight` / 32 to 0 as |c - p| grows to thr (chroma: the rounded 2x2 mean at half the vector, threshold (thr + 1) >> 1).
+ *   cfg            thr 1 .. 64, weight 1 .. 30; anything else, or a size outside the rule: KS265_NOTSUPPORTED
+ *   dev_i420       the picture, in and out; dev_hist_in: the previous call's dev_hist_out, or NULL = no history (the picture stays as it is); dev_hist_out: receives the bytes
+ *                  dev_i420 ends up with - the next picture's history.  Nothing outside the picture is read (the search window's loads are clamped into it; candidates that
+ *                  leave it are masked) and nothing outside the three pictures' extents is written.
+ *   dev_blocks     optional (NULL in the product path): two words per 16x16 block in raster order, ceil(width / 16) x ceil(height / 16) of them - dx + 8 | (dy + 8) << 8 |
+ *                  gated << 16, then the winner's plain SAD; without a history (0, 0), gated, 0.  So that a test can tell a wrong vector from a wrong blend.
+ * Pointers are judged as ks265_input_validate judges a plane - KS265_POINTER unless the whole extent lies inside ONE device allocation on the context's device - and must be
+ * 4-byte aligned (KS265_NOTSUPPORTED); the three pictures may not overlap each other (the history is read at displaced positions across blocks): KS265_POINTER.
+ * ks265_input_denoise_validate enqueues nothing and judges cfg and size alone. */
+typedef struct ks265_denoise_cfg { int32_t thr, weight; } ks265_denoise_cfg;
+int ks265_input_denoise_validate(ks265_ctx *, const ks265_denoise_cfg *, int width, int height);
+int ks265_input_denoise(ks265_ctx *, const ks265_denoise_cfg *, int width, int height, uint8_t *dev_i420 /* in and out */, const uint8_t *dev_hist_in /* NULL: none */,
+                        uint8_t *dev_hist_out, int32_t *dev_blocks /* optional */);
 /* Launch sequences as graphs: between ks265_capture_begin and ks265_capture_end everything enqueued on this context's stream by THIS thread (kernel launches,
  * async memsets of the stage functions) is recorded instead of run (hipStreamBeginCapture, relaxed mode: other threads may go on using the runtime);
  * ks265_capture_end returns an executable graph, ks265_graph_launch enqueues all of it with one runtime call.  A host whose pictures repeat the same

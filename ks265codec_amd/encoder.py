@@ -45,7 +45,12 @@ unused or intra), cu uint8 (5, H/8, W/8) kind / log2 size / partition / cbf / in
 Any EVEN width and height opens (Encoder(854, 480), Encoder(960, 540)): a size that is no multiple of 8 is coded at the next multiple of 8 with a conformance window, the
 picture padded on the GPU by replicating its last column and row (tests/picture_window_ref.py is the specification).  On such a handle encode() takes uint8 "i420" and "nv12"
 tensors of the SOURCE shape only (every other format, and scale=, raises ValueError); recon() returns W x H pictures in every format and dtype; quality() counts the window;
-a roi= map describes the source picture; analysis() describes the CODED picture - ceil(H / 8) x ceil(W / 8) blocks, block errors with the padding in them."""
+a roi= map describes the source picture; analysis() describes the CODED picture - ceil(H / 8) x ceil(W / 8) blocks, block errors with the padding in them.
+
+denoise=1|2|3 (gentle, medium, aggressive) and recur=V (the blend weight in 1/32, 0 .. 30) switch on the temporal denoiser of THIS handle (`vpp_denoise` / `vpp_recur_filter`,
+include/ks265_enc.h; tests/denoise_ref.py is the specification): every picture, whatever its format, is filtered on the GPU against the previous filtered picture - motion
+compensated, per 16x16 block - as the last step on its way in, in the order of torch's current stream.  The encoder, recon(), analysis() and quality() see the filtered
+picture: PSNR is against it, not against the tensor handed in."""
 from __future__ import annotations
 
 import ctypes as C

@@ -70,6 +70,10 @@
 #pragma weak ks265_input_pad
 #pragma weak ks265_output_crop
 #pragma weak ks265_sse_window
+/* `vpp_denoise` / `vpp_recur_filter` (ks265_enc.h): the temporal filter behind whatever made the input slot's twin.  A handle that asks for it on a device library without the
+ * two entries is refused at open (QY_NOTSUPPORTED, one log line) */
+#pragma weak ks265_input_denoise_validate
+#pragma weak ks265_input_denoise
 
 const char strLibQy265Version[] = "ks265enc 0.2 (MI355X pixel path + host CABAC; API of libqycodec V2.6.1.3)";
 
@@ -221,10 +225,12 @@ int QY265ConfigParse(QY265EncConfig *c, const char *name, const char *value)
     if (!strcmp(name, "sao-ref")) { if (!num_ok || dv != iv || iv < 0 || iv > 2) return QY265_PARAM_BAD_VALUE; if (iv) c->sao = 4 + iv; return 0; }
     INTP("wpp", enWavefront, 0, 1) INTP("fpp", enFrameParallel, 0, 1) INTP("vbv-maxrate", vbv_max_rate, 0, 10000000)
     INTP("aq", iAqMode, 0, 3)                                  /* the reference's hidden -aq (iAqMode, qy265enc.h:145) */
+    INTP("denoise", vpp_denoise, 0, 3)                           /* the temporal filter on the way in (vpp_denoise / vpp_recur_filter, ks265_enc.h) */
     INTP("vbv-bufsize", vbv_buffer_size, 0, 10000000) INTP("pass", iPass, 0, 2) INTP("tlayer", temporalLayer, 0, 1) INTP("frameskip", enFrameSkip, 0, 1)
 #undef INTP
     if (!strcmp(name, "fr")) { if (!num_ok || dv <= 0 || dv > 1000) return QY265_PARAM_BAD_VALUE; c->frameRate = dv; return 0; }
     if (!strcmp(name, "aqs")) { if (!num_ok || dv < 0 || dv > 3.0) return QY265_PARAM_BAD_VALUE; c->fAqStrength = dv; return 0; }   /* -aqs (fAqStrength, qy265enc.h:146) */
+    if (!strcmp(name, "recur")) { if (!num_ok || !(dv >= 0) || dv > 30) return QY265_PARAM_BAD_VALUE; c->vpp_recur_filter = dv; return 0; }
     if (!strcmp(name, "ratetol")) { if (!num_ok || dv < 0) return QY265_PARAM_BAD_VALUE; c->fRateTolerance = dv; return 0; }
     if (!strcmp(name, "preset") || !strcmp(name, "latency") || !strcmp(name, "tune")) {
         const int k = find_name(name[0] == 'p' ? kPresetNames : name[0] == 'l' ? kLatencyNames : kTuneNames, value);
@@ -518,6 +524,9 @@ typedef struct Enc {
 #define SCALE_PLANS 4
     int sc_on, sc_max_w, sc_max_h; uint8_t *sc_scratch; long sc_tick;
     struct ScalePlan { ks265_scale_plan *plan; int sw, sh, filter; long used; } sc_plan[SCALE_PLANS];
+    /* `vpp_denoise` / `vpp_recur_filter` (lane_resolve: dn_on, dn_cfg): two history pictures of the coded size on the lane's device, used ping-pong by stage_denoise -
+     * dn_hist[dn_at] holds the last filtered picture once dn_has is set.  Off: no field is touched, nothing is allocated */
+    int dn_on, dn_at, dn_has; ks265_denoise_cfg dn_cfg; uint8_t *dn_hist[2];
 } Enc;
 
 static ks265_ctx *main_ctx(const Enc *e) { return e->path[PATH_MAIN].ctx; }
@@ -1779,6 +1788,16 @@ static void lane_resolve(Enc *e, const QY265EncConfig *cfg, int device, int mult
               !an_lib ? "the device library has no ks265_analysis_pack" : multi == 2 ? "the handle's GOP lanes run on several GPUs" : "the KS265_GRAPH experiment replays captured pictures");
     e->pool_on = e->devrecon || e->analysis;
 
+    /* the temporal filter on the way in: vpp_denoise 1 / 2 / 3 = (thr, weight) (6, 16) / (10, 20) / (16, 24); vpp_recur_filter v > 0 replaces the weight by round(v) in 1 .. 30
+     * and, alone, runs at thr 10 (lane_open has judged both fields) */
+    e->dn_on = cfg->vpp_denoise > 0 || cfg->vpp_recur_filter > 0;
+    if (e->dn_on) {
+        static const int kDnThr[4] = {10, 6, 10, 16}, kDnWeight[4] = {20, 16, 20, 24};
+        const int lv = cfg->vpp_denoise & 3, v = (int)(cfg->vpp_recur_filter + 0.5);
+        e->dn_cfg.thr = kDnThr[lv];
+        e->dn_cfg.weight = cfg->vpp_recur_filter > 0 ? (v < 1 ? 1 : v > 30 ? 30 : v) : kDnWeight[lv];
+    }
+
     /* the lookahead and the two optional streams */
     /* no -lookahead on the command line and the SDK's default GOP (hierarchical B, 8): the slice-type decision runs by itself (round 4: it costs a search of the half-size
      * picture every fourth picture, and the caller does not wait for it) - the reference's adaptive BiPredFrames is on by default as well.  -lookahead 0 switches it off. */
@@ -2121,7 +2140,7 @@ static int open_inputs(Enc *e)
      * analysis would see the picture 10 ms and more late); without it the picture is uploaded when it is scheduled, on the copy-in stream, as before.  One stream for both,
      * not a sixth: a stream more is a hardware queue shared with somebody (lane_open) */
     open_upl_stream(e, 2);
-    if ((e->la_on && e->ctx_la) || e->direct_in || e->ragged) {        /* (ragged: the padded picture exists on the device only - every consumer reads the twin) */
+    if ((e->la_on && e->ctx_la) || e->direct_in || e->ragged || e->dn_on) {   /* (ragged, the denoiser: the padded / filtered picture exists on the device only - every consumer reads the twin) */
         e->ctx_up = e->direct_in == 1 && e->ctx_upl ? e->ctx_upl : e->ctx_la ? e->ctx_la : main_ctx(e);
         reg_handle(main_ctx(e), 1);
         for (int i = 0; i < e->nin && !r; ++i) { r = ks265_dev_malloc(main_ctx(e), (void **)&e->in[i].dev, fsz); if (!r) r = ks265_event_create(e->ctx_up, &e->in[i].ev_up); }
@@ -2129,6 +2148,8 @@ static int open_inputs(Enc *e)
     }
     if (e->ragged)                                                      /* every slot: the staging area of the picture as it came */
         for (int i = 0; i < e->nin && !r; ++i) r = ks265_dev_malloc(main_ctx(e), (void **)&e->in[i].raw, (size_t)e->srcW * e->srcH * 3 / 2);
+    if (e->dn_on)                                                       /* the two history pictures */
+        for (int k = 0; k < 2 && !r; ++k) r = ks265_dev_malloc(main_ctx(e), (void **)&e->dn_hist[k], fsz);
     if (e->roi_on) {                                                    /* every slot: the picture's record on the device, its pinned twin, the event behind its filling - on the upload stream there is, no stream more */
         const size_t nb = (size_t)e->geom.ctu_cols * e->geom.ctu_rows * sizeof(int32_t);
         if (!e->ctx_up) { e->ctx_up = e->ctx_la ? e->ctx_la : main_ctx(e); reg_handle(main_ctx(e), 1); }
@@ -2142,6 +2163,7 @@ static int open_inputs(Enc *e)
 }
 static void close_inputs(Enc *e)                                       /* (also what lane_enable_device_input added: twins, their events, the handle's count) */
 {
+    for (int k = 0; k < 2; ++k) if (e->dn_hist[k]) ks265_dev_free(main_ctx(e), e->dn_hist[k]);
     for (int i = 0; i < MAX_INPUT; ++i) { ks265_host_free(main_ctx(e), e->in[i].i420); ks265_dev_free(main_ctx(e), e->in[i].dev); ev_free(e->ctx_up, &e->in[i].ev_up);
                                           if (e->in[i].raw) ks265_dev_free(main_ctx(e), e->in[i].raw);
                                           ks265_dev_free(main_ctx(e), e->in[i].roi_rec); ks265_host_free(main_ctx(e), e->in[i].roi_host); ev_free(e->ctx_up, &e->in[i].ev_roi); }
@@ -2291,6 +2313,13 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
             *err = QY_NOTSUPPORTED; return NULL;
         }
     }
+    if (cfg->vpp_denoise || cfg->vpp_recur_filter != 0) {               /* the temporal filter: both fields inside their ranges, and the device library has the two entries */
+        if (cfg->vpp_denoise < 0 || cfg->vpp_denoise > 3 || !(cfg->vpp_recur_filter >= 0) || cfg->vpp_recur_filter > 30) { *err = QY_NOTSUPPORTED; return NULL; }
+        if (!ks265_input_denoise || !ks265_input_denoise_validate) {
+            logf_(2, cfg->logLevel, "ks265enc: vpp_denoise %d / vpp_recur_filter %g asked for and the device library has no ks265_input_denoise\n", cfg->vpp_denoise, cfg->vpp_recur_filter);
+            *err = QY_NOTSUPPORTED; return NULL;
+        }
+    }
     if (cfg->picWidth <= 0 || cfg->picHeight <= 0 || (cfg->picWidth & 1) || (cfg->picHeight & 1) || cfg->frameRate <= 0 || cfg->rc < 0 || cfg->rc > 5 || cfg->bframes > GOP_MAX_B) { *err = QY_NOTSUPPORTED; return NULL; }
     Enc *e = (Enc *)calloc(1, sizeof *e);
     if (e) { e->recon_fd = -1; e->qmap_fd = -1; }
@@ -2321,7 +2350,9 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
     if (!r) r = open_md5(e);
     if (!r) r = open_devrecon(e);
     if (!r) r = open_threads(e);
+    if (!r && e->dn_on) r = ks265_input_denoise_validate(main_ctx(e), &e->dn_cfg, e->W, e->H);
     if (r) { *err = hip_rc(r); lane_close(e, 0); return NULL; }
+    if (e->dn_on) logf_(0, e->log_level, "ks265enc: temporal denoiser on the way in: level %d, thr %d, weight %d/32 (motion-compensated, +-8, 16x16 blocks; the history restarts with every GOP chunk a lane is dealt)\n", cfg->vpp_denoise, e->dn_cfg.thr, e->dn_cfg.weight);
     logf_(0, e->log_level, "ks265enc: GPU %d: %dx%d %.2f fps, qp %d, -me %d (hex below %d), subme %d, refs %d, %s, sao %d (%s), key period %d, %d slice writer threads, %s\n", device, e->W, e->H,
           cfg->frameRate, e->base_qp, e->me_method, e->hex_thr, e->subme, e->refs, e->hier ? (e->gop_b == 3 ? "hierarchical-B GOP 4" : "hierarchical-B GOP 8") : e->gop_b ? "P + non-reference B" : "IPPP", e->use_sao,
           e->fcfg.sao == 3 ? "the reference's decision with merge candidates" : e->fcfg.sao == 2 ? "the reference's decision" : e->fcfg.sao ? "the build's rule" : "off", e->iper,
@@ -2669,6 +2700,17 @@ static int stage_host_copy(Enc *e, Input *slot, const QY265YUV *yuv, int own)
     const int r = ks265_memcpy_h2d_async(e->ctx_up, upload_dst(e, slot), slot->i420, (size_t)sw * sh * 3 / 2);
     return r ? r : e->ragged ? lane_pad_slot(e, slot) : ks265_event_record(e->ctx_up, slot->ev_up);
 }
+/* `vpp_denoise`: the slot's twin, whichever way it was made, is filtered in place on ctx_up against the lane's last filtered picture, and ev_up is recorded again behind that:
+ * a host-synchronous upload has finished by now, but its readers must wait for the filter (up_sync off).  key: a GOP chunk starts on this lane - no history, like the lane's
+ * first picture (one lane: key is never set here, the recursion runs across the periodic key pictures) */
+static int stage_denoise(Enc *e, Input *slot, int key)
+{
+    const int to = e->dn_has ? e->dn_at ^ 1 : 0;
+    int r = ks265_input_denoise(e->ctx_up, &e->dn_cfg, e->W, e->H, slot->dev, e->dn_has && !key ? e->dn_hist[e->dn_at] : NULL, e->dn_hist[to], NULL);
+    if (!r) r = ks265_event_record(e->ctx_up, slot->ev_up);
+    slot->up_sync = 0; e->dn_at = to; e->dn_has = 1;
+    return r;
+}
 /* the picture's own fields travel with it from now, and it goes on to the scheduler thread - at once, or with the lookahead when its results are there (la_drain).  A QY code */
 static int publish_input(Enc *e, Input *slot, long long pts, int key)
 {
@@ -2702,6 +2744,7 @@ static int lane_put(Enc *e, const PicIn *p, int key)
     if (!r && p->how != PIC_HOST) r = stage_device(e, slot, p);
     if (!r && p->how == PIC_HOST && e->direct_in && !own && slot->dev && packed_strides(e, yuv)) r = stage_host_direct(e, slot, yuv, &direct);
     if (!r && p->how == PIC_HOST && !direct) r = stage_host_copy(e, slot, yuv, own);
+    if (!r && e->dn_on) r = stage_denoise(e, slot, key);
     if (r) { e->pending_up = NULL; r = hip_rc(r); }                    /* (nothing of a failed picture is waited for) */
     else r = publish_input(e, slot, p->pts, key);
     if (r) return input_fail(e, slot, r);

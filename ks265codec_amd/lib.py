@@ -71,6 +71,10 @@ class InDesc(C.Structure):                    # ks265_in_desc
                 ("pixel_step", C.c_int32), ("matrix", C.c_int32), ("full_range", C.c_int32)]
 
 
+class DenoiseCfg(C.Structure):                # ks265_denoise_cfg
+    _fields_ = [("thr", C.c_int32), ("weight", C.c_int32)]
+
+
 IN_I420, IN_NV12, IN_RGB = 0, 1, 2
 IN_RGB_F16, IN_RGB_BF16, IN_RGB_F32 = 16, 17, 18          # RGB as float samples in [0, 1]: plane, pixel_step and pitch stay in bytes
 RGB_ELEM_SIZE = {IN_RGB: 1, IN_RGB_F16: 2, IN_RGB_BF16: 2, IN_RGB_F32: 4}
@@ -119,6 +123,7 @@ EXPORTS = [
     "ks265_scale_plan_create", "ks265_scale_plan_destroy", "ks265_input_scale_validate", "ks265_input_scale",
     "ks265_analysis_layout", "ks265_analysis_bytes", "ks265_analysis_pack", "ks265_analysis_pack_on", "ks265_analysis_validate", "ks265_analysis_export",
     "ks265_input_pad_validate", "ks265_input_pad", "ks265_output_crop", "ks265_sse_window",
+    "ks265_input_denoise_validate", "ks265_input_denoise",
 ]
 
 
@@ -458,6 +463,20 @@ class KsContext:
     def input_scale(self, plan: C.c_void_p, desc, dst, scratch=None) -> None:
         """desc: a ks265_in_desc (ctypes structure) of the source at the plan's source size; dst: uint8 device tensor of dst_w * dst_h * 3 / 2 bytes; scratch: for RGB and KS265_IN_YUV sources"""
         self._chk(self.lib.ks265_input_scale(self.h, plan, C.byref(desc), _p(scratch), _p(dst)))
+
+    # ---- the temporal denoiser on the way in (include/ks265_hip.h ks265_input_denoise; tests/denoise_ref.py is its specification)
+    def input_denoise_validate(self, thr: int, weight: int, width: int, height: int) -> int:
+        """the library's return code (0, KS265_POINTER -3, KS265_NOTSUPPORTED -4): nothing is enqueued"""
+        return int(self.lib.ks265_input_denoise_validate(self.h, C.byref(DenoiseCfg(thr, weight)), C.c_int(width), C.c_int(height)))
+
+    def input_denoise_rc(self, thr: int, weight: int, width: int, height: int, pic, hist_in, hist_out, blocks=None) -> int:
+        """one launch on the context's stream: `pic` (uint8 device tensor, packed I420 of width x height) filtered in place against hist_in (None: no history), the same
+        bytes into hist_out; blocks: an int32 device tensor of 2 * ceil(width / 16) * ceil(height / 16) words or None.  The library's return code"""
+        ptr = lambda x: C.c_void_p(x) if isinstance(x, int) else _p(x)
+        return int(self.lib.ks265_input_denoise(self.h, C.byref(DenoiseCfg(thr, weight)), C.c_int(width), C.c_int(height), ptr(pic), ptr(hist_in), ptr(hist_out), ptr(blocks)))
+
+    def input_denoise(self, thr: int, weight: int, width: int, height: int, pic, hist_in, hist_out, blocks=None) -> None:
+        self._chk(self.input_denoise_rc(thr, weight, width, height, pic, hist_in, hist_out, blocks))
 
     def intra_pred(self, ref, dst, blks: np.ndarray):
         """g_IntraPredFunction: predict every described block from dev `ref` into dev `dst` (in place)"""
