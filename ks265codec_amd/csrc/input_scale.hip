@@ -3,7 +3,7 @@
 // One launch makes all three planes.  A work-group owns a tile of 64 destination columns x up to 16 destination rows of one plane: it reads the tile's coefficients once into
 // LDS, brings the tile's span of source rows in chunk by chunk (whole 16-byte words along the row where the row's own extent allows, narrower at its ends), filters every
 // source row of the span horizontally into an int16 picture in LDS, then filters that vertically and stores one aligned word per thread.  No scratch memory, no atomics.
-#include "ks265_internal.h"
+#include "convert_dev.h"
 #include "../host/ks265_scale.h"
 #include <algorithm>
 #include <cstring>
@@ -37,12 +37,6 @@ struct ScaleArgs {
     int Tx[2], Ty[2], nbx[2], nby[2];
     int tile_rows, chunk_rows, lstr, span_rows, tx_max, ty_max;
 };
-
-__device__ inline uint32_t shr_clip255(int v, int sh)          // (input_convert.hip: the clamp before a logical shift)
-{
-    const int hi = (256 << sh) - 1;
-    return (uint32_t)(v < 0 ? 0 : v > hi ? hi : v) >> sh;
-}
 
 // the 16 bytes at the 16-byte aligned address a, of which only those inside [lo, hi) are read (the others count 0): one 16-byte load, else 8-byte, 4-byte, single bytes
 __device__ inline uint4 load16_inside(uintptr_t a, uintptr_t lo, uintptr_t hi)
@@ -152,7 +146,7 @@ __global__ __launch_bounds__(NT) void scale_i420_kernel(ScaleArgs a)
     }
     uint32_t w = 0;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) w |= shr_clip255(v[e] + (1 << 19), 20) << 8 * e;
+    for (int e = 0; e < 4; ++e) w |= shr_clip255(v[e] + (1 << 19), 20) << 8 * e;   // (convert_dev.h: the clamp in front of the shift)
     *(uint32_t *)(P.dst + (size_t)y * P.dw + x) = w;
 }
 
@@ -256,16 +250,14 @@ int ks265_input_scale(ks265_ctx *c, const ks265_scale_plan *p, const ks265_in_de
     if (r) return r;
     if (p->identity) return ks265_input_convert(c, s, dst);
     const long long sn = (long long)p->sw * p->sh, dn = (long long)p->dw * p->dh;
-    if ((uintptr_t)dst & 15) { c->last_error = "scale: destination not 16-byte aligned"; return KS265_NOTSUPPORTED; }
-    if ((r = ks265_check_extent(c, dst, dn * 3 / 2, 1, dn * 3 / 2, "destination"))) return r;
+    if ((r = ks_check_slot(c, dst, dn * 3 / 2, "scale", "destination"))) return r;
     ScaleArgs a = {};
     ks265_yuv_fmt yf;
     const int fam = ks265_yuv_decode(s->format, &yf);                  // (validated above: a valid code of the YUV family, or none of it)
     const bool nv12 = s->format == KS265_IN_NV12 || (fam > 0 && yf.alias && yf.layout == 1);
     if (ks265_rgb_elem_size(s->format) || (fam > 0 && !yf.alias)) {    // RGB of any sample type, YUV of more bits or more chroma: converted at the source's size first
         if (!scratch) { c->last_error = "scale: an RGB or KS265_IN_YUV source needs the scratch picture"; return KS265_POINTER; }
-        if ((uintptr_t)scratch & 15) { c->last_error = "scale: scratch not 16-byte aligned"; return KS265_NOTSUPPORTED; }
-        if ((r = ks265_check_extent(c, scratch, sn * 3 / 2, 1, sn * 3 / 2, "scratch"))) return r;
+        if ((r = ks_check_slot(c, scratch, sn * 3 / 2, "scale", "scratch"))) return r;
         if ((r = ks265_input_convert(c, s, scratch))) return r;        // the conversion at the source's size, then the scaler on the same stream
         a.pl[0] = {scratch, p->sw, 0, 1, p->sw, 0, 0, 0, 0, nullptr};
         a.pl[1] = {scratch + sn, p->sw / 2, 0, 1, p->sw / 2, 0, 0, 0, 0, nullptr};

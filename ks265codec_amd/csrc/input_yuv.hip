@@ -1,11 +1,10 @@
 // input_yuv.hip — the YUV family of the device input (include/ks265_hip.h KS265_IN_YUV(layout, sub, depth, msb)): 8- to 16-bit 4:2:0 / 4:2:2 / 4:4:4 pictures, planar,
 // semi-planar or packed, reduced to the packed 8-bit I420 of the encoder's input slots.  tests/yuv_hibit_ref.py is the specification: luma rounded to 8 bits, chroma summed at
 // full depth - 4:2:2 by (1, 1) vertically, 4:4:4 by (1, 2, 1) x (1, 1) with the left edge clamped - and rounded ONCE with the depth reduction, ties up, clipped to 255; no
-// dither, no range or matrix conversion.  The shape of input_convert.hip's kernels: memory-bound, one thread owns 8 luma columns across the two rows of one chroma row, every
-// chroma sample is made from registers (no LDS, no scratch: every register array is indexed by unrolled constants).  A run is loaded as exactly its own bytes - 16, 8 or 4 at a
-// time where the address allows, element by element otherwise - so no load leaves [row start, row start + row bytes); the stores are aligned words (width a multiple of 8, the
-// destination on 16 bytes).  Templates: (layout shape, subsampling, element size); depth, alignment and the packed byte order are arguments.
-#include "ks265_internal.h"
+// dither, no range or matrix conversion.  Memory-bound, on convert_dev.h's cell: one thread owns 8 luma columns across the two rows of one chroma row, every chroma sample is
+// made from registers (no LDS, no scratch: every register array is indexed by unrolled constants).  A run is loaded as exactly its own bytes (convert_dev.h load_run), so no load
+// leaves [row start, row start + row bytes); the stores are aligned words (width a multiple of 8, the destination on 16 bytes).  Templates: (layout shape, subsampling, element size); depth, alignment and the packed byte order are arguments.
+#include "convert_dev.h"
 
 namespace {
 
@@ -21,46 +20,16 @@ struct YuvArgs {
 
 enum { SH_PLANAR = 0, SH_SEMI = 1, SH_PACKED = 2 };
 
-// NB bytes at p (for ES 2 an even address) into words, little-endian
-template <int NB, int ES> __device__ inline void load_run(const uint8_t *p, uint32_t (&w)[NB / 4])
-{
-    const uintptr_t a = (uintptr_t)p;
-    if (NB % 16 == 0 && !(a & 15)) {
-#pragma unroll
-        for (int k = 0; k < NB / 16; ++k) { const uint4 v = ((const uint4 *)p)[k]; w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w; }
-    } else if (NB % 8 == 0 && !(a & 7)) {
-#pragma unroll
-        for (int k = 0; k < NB / 8; ++k) { const uint2 v = ((const uint2 *)p)[k]; w[2 * k] = v.x; w[2 * k + 1] = v.y; }
-    } else if (!(a & 3)) {
-#pragma unroll
-        for (int k = 0; k < NB / 4; ++k) w[k] = ((const uint32_t *)p)[k];
-    } else if (ES == 2) {
-#pragma unroll
-        for (int k = 0; k < NB / 4; ++k) w[k] = (uint32_t)((const uint16_t *)p)[2 * k] | (uint32_t)((const uint16_t *)p)[2 * k + 1] << 16;
-    } else {
-#pragma unroll
-        for (int k = 0; k < NB / 4; ++k) w[k] = (uint32_t)p[4 * k] | (uint32_t)p[4 * k + 1] << 8 | (uint32_t)p[4 * k + 2] << 16 | (uint32_t)p[4 * k + 3] << 24;
-    }
-}
-// stored element k (a constant after unrolling) of a run
-template <int ES> __device__ inline uint32_t run_elem(const uint32_t *w, int k) { return ES == 2 ? w[k >> 1] >> 16 * (k & 1) & 0xffffu : w[k >> 2] >> 8 * (k & 3) & 0xffu; }
 template <int ES> __device__ inline uint32_t one_elem(const uint8_t *p) { return ES == 2 ? (uint32_t)*(const uint16_t *)p : (uint32_t)*p; }
 // the sample of a stored element
 template <int ES> __device__ inline uint32_t norm(const YuvArgs &a, uint32_t w) { return ES == 1 ? w : (w >> a.nsh) & (uint32_t)a.mask; }
-// min(255, v >> sh) as a clamp in front of a logical shift (the note at input_convert.hip's shr_clip255: hipcc for gfx950 must not see a clip of a shifted pair)
-__device__ inline uint32_t shr_min255(uint32_t v, int sh)
-{
-    const uint32_t hi = (256u << sh) - 1u;
-    return (v > hi ? hi : v) >> sh;
-}
 
 // SHAPE x SUB x ES: 8 luma columns x the two rows of chroma row i -> 16 Y, 4 Cb, 4 Cr
 template <int SHAPE, int SUB, int ES> __global__ __launch_bounds__(256) void yuvx_to_i420_kernel(YuvArgs a)
 {
-    const int x0 = (blockIdx.x * 64 + threadIdx.x) * 8, i = blockIdx.y * 4 + threadIdx.y;
-    if (x0 >= a.W || 2 * i >= a.H) return;
+    int x0, i;
+    if (!ks_cell<8>(a.W, a.H, x0, i)) return;
     constexpr int T = SUB == 0 ? 0 : SUB == 1 ? 1 : 3;                 // log2 of the chroma filter's weight
-    const size_t W = (size_t)a.W, npx = W * a.H;
     uint32_t su[4] = {0, 0, 0, 0}, sv[4] = {0, 0, 0, 0};
 #pragma unroll
     for (int dy = 0; dy < 2; ++dy) {
@@ -74,7 +43,7 @@ template <int SHAPE, int SUB, int ES> __global__ __launch_bounds__(256) void yuv
                 for (int k = 0; k < 4 * ES; ++k) w[k] = ES == 2 ? (w[k] << 16 | w[k] >> 16) : ((w[k] & 0x00ff00ffu) << 8 | (w[k] >> 8 & 0x00ff00ffu));
             }
 #pragma unroll
-            for (int k = 0; k < 8; ++k) yw[k >> 2] |= shr_min255(norm<ES>(a, run_elem<ES>(w, 2 * k)) + a.rl, a.s) << 8 * (k & 3);
+            for (int k = 0; k < 8; ++k) yw[k >> 2] |= shr_clip255<uint32_t>(norm<ES>(a, run_elem<ES>(w, 2 * k)) + a.rl, a.s) << 8 * (k & 3);
 #pragma unroll
             for (int k = 0; k < 4; ++k) { su[k] += norm<ES>(a, run_elem<ES>(w, 4 * k + 1)); sv[k] += norm<ES>(a, run_elem<ES>(w, 4 * k + 3)); }
         } else {
@@ -83,7 +52,7 @@ template <int SHAPE, int SUB, int ES> __global__ __launch_bounds__(256) void yuv
             if constexpr (ES == 1) { yw[0] = w[0]; yw[1] = w[1]; }
             else {
 #pragma unroll
-                for (int k = 0; k < 8; ++k) yw[k >> 2] |= shr_min255(norm<ES>(a, run_elem<ES>(w, k)) + a.rl, a.s) << 8 * (k & 3);
+                for (int k = 0; k < 8; ++k) yw[k >> 2] |= shr_clip255<uint32_t>(norm<ES>(a, run_elem<ES>(w, k)) + a.rl, a.s) << 8 * (k & 3);
             }
             if (SUB != 0 || dy == 0) {                                  // 4:2:0: the one chroma row i
                 const long long cy = SUB == 0 ? i : y;
@@ -122,23 +91,22 @@ template <int SHAPE, int SUB, int ES> __global__ __launch_bounds__(256) void yuv
                 }
             }
         }
-        *(uint2 *)(a.dst + (size_t)y * W + x0) = make_uint2(yw[0], yw[1]);
+        store_words<8>(a.dst + (size_t)y * a.W + x0, yw);
     }
-    uint32_t u = 0, v = 0;
+    uint32_t u[1] = {0}, v[1] = {0};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        u |= shr_min255(su[k] + a.rc, a.s + T) << 8 * k;
-        v |= shr_min255(sv[k] + a.rc, a.s + T) << 8 * k;
+        u[0] |= shr_clip255<uint32_t>(su[k] + a.rc, a.s + T) << 8 * k;
+        v[0] |= shr_clip255<uint32_t>(sv[k] + a.rc, a.s + T) << 8 * k;
     }
-    uint8_t *dc = a.dst + npx + (size_t)i * (W / 2) + x0 / 2;
-    *(uint32_t *)dc = u;
-    *(uint32_t *)(dc + npx / 4) = v;
+    store_chroma(a.dst, a.W, a.H, i, x0, u, v);
 }
 
-template <int SHAPE, int SUB> void launch_es(hipStream_t st, dim3 grid, dim3 blk, int es, const YuvArgs &a)
+template <int SHAPE, int SUB> void launch_es(hipStream_t st, int es, const YuvArgs &a)
 {
-    if (es == 2) hipLaunchKernelGGL((yuvx_to_i420_kernel<SHAPE, SUB, 2>), grid, blk, 0, st, a);
-    else hipLaunchKernelGGL((yuvx_to_i420_kernel<SHAPE, SUB, 1>), grid, blk, 0, st, a);
+    const KsCellLaunch l = ks_cell_launch(a.W, a.H, 8);
+    if (es == 2) hipLaunchKernelGGL((yuvx_to_i420_kernel<SHAPE, SUB, 2>), l.grid, l.blk, 0, st, a);
+    else hipLaunchKernelGGL((yuvx_to_i420_kernel<SHAPE, SUB, 1>), l.grid, l.blk, 0, st, a);
 }
 
 }  // namespace
@@ -171,16 +139,15 @@ int ks265_yuv_launch(ks265_ctx *c, const ks265_in_desc *d, const ks265_yuv_fmt &
     a.nsh = f.msb ? 16 - f.depth : 0; a.mask = (1 << f.depth) - 1;
     a.rl = a.s ? 1 << (a.s - 1) : 0; a.rc = a.s + t ? 1 << (a.s + t - 1) : 0;
     a.uyvy = f.layout == 3;
-    const dim3 blk(64, 4), grid((unsigned)((d->width / 8 + 63) / 64), (unsigned)((d->height / 2 + 3) / 4));
-    if (f.layout >= 2) launch_es<SH_PACKED, 1>(c->stream, grid, blk, f.es, a);
+    if (f.layout >= 2) launch_es<SH_PACKED, 1>(c->stream, f.es, a);
     else if (f.layout == 1) {
-        if (f.sub == 0) launch_es<SH_SEMI, 0>(c->stream, grid, blk, f.es, a);
-        else if (f.sub == 1) launch_es<SH_SEMI, 1>(c->stream, grid, blk, f.es, a);
-        else launch_es<SH_SEMI, 2>(c->stream, grid, blk, f.es, a);
+        if (f.sub == 0) launch_es<SH_SEMI, 0>(c->stream, f.es, a);
+        else if (f.sub == 1) launch_es<SH_SEMI, 1>(c->stream, f.es, a);
+        else launch_es<SH_SEMI, 2>(c->stream, f.es, a);
     } else {
-        if (f.sub == 0) launch_es<SH_PLANAR, 0>(c->stream, grid, blk, f.es, a);
-        else if (f.sub == 1) launch_es<SH_PLANAR, 1>(c->stream, grid, blk, f.es, a);
-        else launch_es<SH_PLANAR, 2>(c->stream, grid, blk, f.es, a);
+        if (f.sub == 0) launch_es<SH_PLANAR, 0>(c->stream, f.es, a);
+        else if (f.sub == 1) launch_es<SH_PLANAR, 1>(c->stream, f.es, a);
+        else launch_es<SH_PLANAR, 2>(c->stream, f.es, a);
     }
     return ks265_check_launch(c);
 }

@@ -3,11 +3,12 @@
 //   ks265_input_pad    8-bit I420 / NV12 of W x H with its own pitches -> the packed I420 of cW x cH of an input slot, last column and last row replicated (np.pad mode="edge")
 //   ks265_output_crop  packed I420 of cW x cH -> packed I420 of W x H (the top-left corner)
 //   ks265_sse_window   takes the padding strips' squared error out of the three plane sums of ks265_sse_picture / ks265_ssim_picture
-// Pad and crop are memory-bound and shaped like input_convert.hip's repack: one thread owns 8 luma columns across the two rows of one chroma row, no LDS.  A source row of 854
+// Pad and crop are memory-bound and run on convert_dev.h's cell: one thread owns 8 luma columns across the two rows of one chroma row, no LDS.  A source row of 854
 // bytes starts at any address, so a run is copied out of the row as exactly its own bytes (memcpy of 8 or 4: the hardware takes a dword load at any byte address) and a run
 // that crosses the row's end is read byte by byte with the column clamped; nothing outside [row start, row start + row bytes) is read.  The coded rows are multiples of 8 / 4
 // bytes and the slot is 16-byte aligned, so the pad's stores are aligned words.  The thread of the LAST source row pair also writes the rows below it: the source is read once.
 #include "frame_common.h"
+#include "convert_dev.h"
 
 namespace {
 
@@ -57,31 +58,25 @@ __device__ inline void ld4_pairs_edge(const uint8_t *row, int x0, int w, uint32_
 // a thread: luma columns x0 .. x0 + 7 of source rows 2 i and 2 i + 1, chroma columns x0 / 2 .. + 3 of chroma row i; for the last source row pair also every row below
 template <bool NV12> __global__ __launch_bounds__(256) void input_pad_kernel(PadArgs a)
 {
-    const int x0 = (blockIdx.x * 64 + threadIdx.x) * 8, i = blockIdx.y * 4 + threadIdx.y;
-    if (x0 >= a.cW || 2 * i >= a.H) return;
-    const size_t cW = (size_t)a.cW, npx = cW * a.cH;
+    int x0, i;
+    if (!ks_cell<8>(a.cW, a.H, x0, i)) return;
+    const size_t cW = (size_t)a.cW;
     // x0 < W: cW - 8 < W, so every run holds at least one source column
     const uint2 y0 = ld8_edge(a.p[0] + (long long)(2 * i) * a.pitch[0], x0, a.W);
     const uint2 y1 = ld8_edge(a.p[0] + (long long)(2 * i + 1) * a.pitch[0], x0, a.W);
-    uint32_t u, v;
-    if (NV12) ld4_pairs_edge(a.p[1] + (long long)i * a.pitch[1], x0 / 2, a.W / 2, u, v);
+    uint32_t u[1], v[1];
+    if (NV12) ld4_pairs_edge(a.p[1] + (long long)i * a.pitch[1], x0 / 2, a.W / 2, u[0], v[0]);
     else {
-        u = ld4_edge(a.p[1] + (long long)i * a.pitch[1], x0 / 2, a.W / 2);
-        v = ld4_edge(a.p[2] + (long long)i * a.pitch[2], x0 / 2, a.W / 2);
+        u[0] = ld4_edge(a.p[1] + (long long)i * a.pitch[1], x0 / 2, a.W / 2);
+        v[0] = ld4_edge(a.p[2] + (long long)i * a.pitch[2], x0 / 2, a.W / 2);
     }
     uint8_t *dy = a.dst + (size_t)(2 * i) * cW + x0;
     *(uint2 *)dy = y0;
     *(uint2 *)(dy + cW) = y1;
-    uint8_t *dc = a.dst + npx + (size_t)i * (cW / 2) + x0 / 2;
-    *(uint32_t *)dc = u;
-    *(uint32_t *)(dc + npx / 4) = v;
+    store_chroma(a.dst, cW, a.cH, i, x0, u, v);
     if (2 * i + 2 == a.H) {                                                // at most 6 luma and 3 chroma rows
         for (int y = a.H; y < a.cH; ++y) *(uint2 *)(a.dst + (size_t)y * cW + x0) = y1;
-        for (int y = a.H / 2; y < a.cH / 2; ++y) {
-            uint8_t *d = a.dst + npx + (size_t)y * (cW / 2) + x0 / 2;
-            *(uint32_t *)d = u;
-            *(uint32_t *)(d + npx / 4) = v;
-        }
+        for (int y = a.H / 2; y < a.cH / 2; ++y) store_chroma(a.dst, cW, a.cH, y, x0, u, v);
     }
 }
 
@@ -102,8 +97,8 @@ __device__ inline void st_run4(uint8_t *row, int x0, int w, uint32_t v)
 }
 __global__ __launch_bounds__(256) void output_crop_kernel(const uint8_t *src, int cW, int cH, int w, int h, uint8_t *dst)
 {
-    const int x0 = (blockIdx.x * 64 + threadIdx.x) * 8, i = blockIdx.y * 4 + threadIdx.y;
-    if (x0 >= w || 2 * i >= h) return;
+    int x0, i;
+    if (!ks_cell<8>(w, h, x0, i)) return;
     const size_t sW = (size_t)cW, snpx = sW * cH, dW = (size_t)w, dnpx = dW * h;
     const uint8_t *sy = src + (size_t)(2 * i) * sW + x0, *sc = src + snpx + (size_t)i * (sW / 2) + x0 / 2;
     const uint2 y0 = *(const uint2 *)sy, y1 = *(const uint2 *)(sy + sW);
@@ -150,12 +145,9 @@ int pad_check(ks265_ctx *c, const ks265_in_desc *d, int cw, int ch)
     if (W <= 0 || H <= 0 || (W & 1) || (H & 1) || (cw & 7) || (ch & 7) || cw < W || cw >= W + 8 || ch < H || ch >= H + 8) {
         c->last_error = "pad: width and height even, the coded size theirs rounded up to a multiple of 8"; return KS265_NOTSUPPORTED;
     }
-    const int nv12 = d->format == KS265_IN_NV12;
+    const bool nv12 = d->format == KS265_IN_NV12;
     if (d->pitch[0] < W || d->pitch[1] < (nv12 ? W : W / 2) || (!nv12 && d->pitch[2] < W / 2)) { c->last_error = "pad: pitch below the row's bytes"; return KS265_NOTSUPPORTED; }
-    int r = ks265_check_extent(c, d->plane[0], d->pitch[0], (int)H, W, "Y");
-    if (!r && nv12) r = ks265_check_extent(c, d->plane[1], d->pitch[1], (int)(H / 2), W, "UV");
-    for (int k = 1; k < 3 && !r && !nv12; ++k) r = ks265_check_extent(c, d->plane[k], d->pitch[k], (int)(H / 2), W / 2, k == 1 ? "U" : "V");
-    return r;
+    return ks_check_planes_420(c, d, nv12);
 }
 
 }  // namespace
@@ -175,15 +167,13 @@ int ks265_input_pad(ks265_ctx *c, const ks265_in_desc *d, int coded_w, int coded
     ks_use_device(c);
     int r = pad_check(c, d, coded_w, coded_h);
     if (r) return r;
-    const long long bytes = (long long)coded_w * coded_h * 3 / 2;
-    if ((uintptr_t)dst & 15) { c->last_error = "pad: destination not 16-byte aligned"; return KS265_NOTSUPPORTED; }
-    if ((r = ks265_check_extent(c, dst, bytes, 1, bytes, "destination"))) return r;
+    if ((r = ks_check_slot(c, dst, (long long)coded_w * coded_h * 3 / 2, "pad", "destination"))) return r;
     PadArgs a = {};
     for (int k = 0; k < 3; ++k) { a.p[k] = (const uint8_t *)d->plane[k]; a.pitch[k] = d->pitch[k]; }
     a.W = d->width; a.H = d->height; a.cW = coded_w; a.cH = coded_h; a.dst = dst;
-    const dim3 blk(64, 4), grid((unsigned)((coded_w / 8 + 63) / 64), (unsigned)((d->height / 2 + 3) / 4));
-    if (d->format == KS265_IN_NV12) hipLaunchKernelGGL(input_pad_kernel<true>, grid, blk, 0, c->stream, a);
-    else hipLaunchKernelGGL(input_pad_kernel<false>, grid, blk, 0, c->stream, a);
+    const KsCellLaunch l = ks_cell_launch(coded_w, d->height, 8);
+    if (d->format == KS265_IN_NV12) hipLaunchKernelGGL(input_pad_kernel<true>, l.grid, l.blk, 0, c->stream, a);
+    else hipLaunchKernelGGL(input_pad_kernel<false>, l.grid, l.blk, 0, c->stream, a);
     return ks265_check_launch(c);
 }
 
@@ -199,8 +189,8 @@ int ks265_output_crop(ks265_ctx *c, const uint8_t *src, int coded_w, int coded_h
     int r = ks265_check_extent(c, src, sb, 1, sb, "source");
     if (!r) r = ks265_check_extent(c, dst, db, 1, db, "destination");
     if (r) return r;
-    const dim3 blk(64, 4), grid((unsigned)(((w + 7) / 8 + 63) / 64), (unsigned)((h / 2 + 3) / 4));
-    hipLaunchKernelGGL(output_crop_kernel, grid, blk, 0, c->stream, src, coded_w, coded_h, w, h, dst);
+    const KsCellLaunch l = ks_cell_launch(w, h, 8);
+    hipLaunchKernelGGL(output_crop_kernel, l.grid, l.blk, 0, c->stream, src, coded_w, coded_h, w, h, dst);
     return ks265_check_launch(c);
 }
 
