@@ -43,7 +43,19 @@
  *     chunk therefore starts unfiltered and the stream differs between lane counts: the known limit - history is not carried between lanes or GPUs.  QY265EncoderReconfig
  *     leaves the filter as opened.  Values outside the ranges, or a device library without ks265_input_denoise: QY265EncoderOpen fails with QY_NOTSUPPORTED.  Both 0 (the
  *     default): no call, no allocation, no byte of the stream changes;
- *   - transskip, tuIntra, the other vpp_* fields, 2-pass, long-term references, VBV / CVQ: accepted, ignored;
+ *   - vpp_edge and vpp_color (each 0 off, 1 gentle, 2 medium, 3 aggressive; QY265ConfigParse "edge" = `-edge N`, "color" = `-color N`): edge and colour enhancement on the GPU,
+ *     one stateless step behind the denoiser and in front of the encoder, for every way in (tests/enhance_ref.py is the specification of every byte).  Luma: an
+ *     unsharp mask - the detail against the exact 5x5 binomial blur, cored (a soft threshold), amplified, limited, added, and the result held inside the sample's 3x3
+ *     neighbourhood's minimum / maximum widened by `over` (halo control); picture edges replicate.  Levels 1 / 2 / 3 = (gain in 1/16, core, limit, over) (8, 2, 8, 2) /
+ *     (16, 2, 16, 4) / (24, 3, 24, 8).  Chroma: every (u, v) pair is pushed away from grey by a gain that falls linearly from 1 + g / 64 at grey to 1 at full saturation
+ *     (g = 8 / 16 / 32); grey stays grey, nothing clips.  These values are this build's choice (the reference's Linux binaries have no VPP code) and NOBODY HAS TRIED THEM ON
+ *     REAL FOOTAGE.  The range that goes in is not protected: a limited-range picture may leave 16 .. 235 by `over`.  With the denoiser on, its history stays unsharpened: the
+ *     recursion never sees enhanced samples.  The filter has no state, so any number of GOP lanes gives the one-lane stream.  Everything downstream - the lookahead, -aq, the
+ *     search, `analysis`, `devrecon`, -o - sees the enhanced picture, and -psnr / -ssim are measured AGAINST THE ENHANCED PICTURE.  QY265EncoderReconfig leaves the filter as
+ *     opened.  Values outside 0 .. 3, or a device library without ks265_input_enhance: QY265EncoderOpen fails with QY_NOTSUPPORTED.  Both 0 (the default): no call, no
+ *     allocation, no byte of the stream changes;
+ *   - vpp_hdr* (out of scope so far): accepted, ignored;
+ *   - transskip, tuIntra, 2-pass, long-term references, VBV / CVQ: accepted, ignored;
  *   - input pictures: the caller's planes are pinned in place and uploaded from where they lie inside QY265EncoderEncodeFrame; the caller may reuse its buffers when the call returns
  *     (the SDK requires them to stay valid until the frame is done);
  *   - analysis out (not in the SDK; ks265_enc_set_default "analysis", ks265_enc_get_device_analysis below): motion, modes, QP and block error of every picture as device arrays;

@@ -223,6 +223,25 @@ typedef struct ks265_denoise_cfg { int32_t thr, weight; } ks265_denoise_cfg;
 int ks265_input_denoise_validate(ks265_ctx *, const ks265_denoise_cfg *, int width, int height);
 int ks265_input_denoise(ks265_ctx *, const ks265_denoise_cfg *, int width, int height, uint8_t *dev_i420 /* in and out */, const uint8_t *dev_hist_in /* NULL: none */,
                         uint8_t *dev_hist_out, int32_t *dev_blocks /* optional */);
+/* Edge and colour enhancement on the way in (input_enhance.hip; tests/enhance_ref.py is the specification of every byte).  One launch on the context's stream,
+ * no state, on the packed I420 picture of width x height (positive multiples of 8, at most 8192: the coded size, so it runs behind ks265_input_pad, whose replicated padding
+ * is what the edge rule below would have read anyway).
+ *   luma (edge_gain > 0)    an unsharp mask: the 5x5 binomial blur ((1 4 6 4 1) both ways, exact, in 1/256 of a code; coordinates outside the plane clamped into it), the
+ *                  detail 256 S - blur cored by 256 edge_core (a soft threshold), times edge_gain / 16, rounded, at most edge_limit codes, added to S; the result clipped to
+ *                  [min - edge_over, max + edge_over] of the sample's 3x3 neighbourhood, and to 0 .. 255.  The stencil reads neighbours across work-groups, so the luma is read
+ *                  from dev_luma_src - a copy of the plane, width x height at pitch width, that does not overlap the picture (KS265_POINTER if it does) - and written to dev_i420.
+ *   chroma (color_gain > 0) pointwise and IN PLACE, per co-located (u, v): K = 8192 + color_gain (128 - max(|u - 128|, |v - 128|)), each component 128 + sgn(c) ((|c| K + 4096)
+ *                  >> 13): the gain falls to 1 as the pair approaches full saturation, grey stays grey, no component shrinks and none clips.
+ *   cfg            edge_gain 0 .. 64 (1/16), edge_core 0 .. 16, edge_limit 1 .. 64 when edge_gain > 0, edge_over 0 .. 32, color_gain 0 .. 32; anything else, both gains 0, or a
+ *                  size outside the rule: KS265_NOTSUPPORTED.  A gain of 0 leaves its planes untouched (edge_gain == 0: dev_luma_src is not looked at, NULL is fine).
+ * The range that goes in is not protected: a limited-range picture may leave 16 .. 235 by edge_over.  Pointers are judged as ks265_input_denoise judges them - the whole extent
+ * inside ONE allocation on the context's device (KS265_POINTER), 4-byte aligned (KS265_NOTSUPPORTED); a refused call enqueues nothing.  Nothing outside the two extents is read
+ * or written.  ks265_input_enhance_validate enqueues nothing and judges cfg and size alone. */
+typedef struct ks265_enhance_cfg { int32_t edge_gain, edge_core, edge_limit, edge_over, color_gain; } ks265_enhance_cfg;
+int ks265_input_enhance_validate(ks265_ctx *, const ks265_enhance_cfg *, int width, int height);
+int ks265_input_enhance(ks265_ctx *, const ks265_enhance_cfg *, int width, int height,
+                        const uint8_t *dev_luma_src /* W x H, pitch W; NULL only when edge_gain == 0 */,
+                        uint8_t *dev_i420 /* the picture: luma written from dev_luma_src, chroma in place */);
 /* Launch sequences as graphs: between ks265_capture_begin and ks265_capture_end everything enqueued on this context's stream by THIS thread (kernel launches,
  * async memsets of the stage functions) is recorded instead of run (hipStreamBeginCapture, relaxed mode: other threads may go on using the runtime);
  * ks265_capture_end returns an executable graph, ks265_graph_launch enqueues all of it with one runtime call.  A host whose pictures repeat the same

@@ -50,7 +50,12 @@ a roi= map describes the source picture; analysis() describes the CODED picture 
 denoise=1|2|3 (gentle, medium, aggressive) and recur=V (the blend weight in 1/32, 0 .. 30) switch on the temporal denoiser of THIS handle (`vpp_denoise` / `vpp_recur_filter`,
 include/ks265_enc.h; tests/denoise_ref.py is the specification): every picture, whatever its format, is filtered on the GPU against the previous filtered picture - motion
 compensated, per 16x16 block - as the last step on its way in, in the order of torch's current stream.  The encoder, recon(), analysis() and quality() see the filtered
-picture: PSNR is against it, not against the tensor handed in."""
+picture: PSNR is against it, not against the tensor handed in.
+
+edge=1|2|3 and color=1|2|3 (gentle, medium, aggressive) switch on the enhancement of THIS handle (`vpp_edge` / `vpp_color`, include/ks265_enc.h; tests/enhance_ref.py is the
+specification): an unsharp mask with coring and halo control on the luma and a saturation boost on the chroma, one stateless GPU step behind the denoiser and in front of the
+encoder, for every format and for scale= (Encoder(w, h, edge=1) behind a shrinking scale= is the ladder's mild sharpening).  The levels are untuned choices; the encoder,
+recon(), analysis() and quality() see the enhanced picture, so PSNR is against it."""
 from __future__ import annotations
 
 import ctypes as C

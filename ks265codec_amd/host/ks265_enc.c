@@ -74,6 +74,9 @@
  * two entries is refused at open (QY_NOTSUPPORTED, one log line) */
 #pragma weak ks265_input_denoise_validate
 #pragma weak ks265_input_denoise
+/* `vpp_edge` / `vpp_color` (ks265_enc.h): the stateless enhancement behind the denoiser, the last step in front of the encoder.  Refused at open in the same way */
+#pragma weak ks265_input_enhance_validate
+#pragma weak ks265_input_enhance
 
 const char strLibQy265Version[] = "ks265enc 0.2 (MI355X pixel path + host CABAC; API of libqycodec V2.6.1.3)";
 
@@ -226,6 +229,7 @@ int QY265ConfigParse(QY265EncConfig *c, const char *name, const char *value)
     INTP("wpp", enWavefront, 0, 1) INTP("fpp", enFrameParallel, 0, 1) INTP("vbv-maxrate", vbv_max_rate, 0, 10000000)
     INTP("aq", iAqMode, 0, 3)                                  /* the reference's hidden -aq (iAqMode, qy265enc.h:145) */
     INTP("denoise", vpp_denoise, 0, 3)                           /* the temporal filter on the way in (vpp_denoise / vpp_recur_filter, ks265_enc.h) */
+    INTP("edge", vpp_edge, 0, 3) INTP("color", vpp_color, 0, 3)   /* edge / colour enhancement on the way in (vpp_edge / vpp_color, ks265_enc.h) */
     INTP("vbv-bufsize", vbv_buffer_size, 0, 10000000) INTP("pass", iPass, 0, 2) INTP("tlayer", temporalLayer, 0, 1) INTP("frameskip", enFrameSkip, 0, 1)
 #undef INTP
     if (!strcmp(name, "fr")) { if (!num_ok || dv <= 0 || dv > 1000) return QY265_PARAM_BAD_VALUE; c->frameRate = dv; return 0; }
@@ -527,6 +531,9 @@ typedef struct Enc {
     /* `vpp_denoise` / `vpp_recur_filter` (lane_resolve: dn_on, dn_cfg): two history pictures of the coded size on the lane's device, used ping-pong by stage_denoise -
      * dn_hist[dn_at] holds the last filtered picture once dn_has is set.  Off: no field is touched, nothing is allocated */
     int dn_on, dn_at, dn_has; ks265_denoise_cfg dn_cfg; uint8_t *dn_hist[2];
+    /* `vpp_edge` / `vpp_color` (lane_resolve: en_on, en_cfg; stage_enhance).  en_luma: the W x H copy of the luma that the stencil reads, owned by a lane with vpp_edge on and
+     * the denoiser off (with it on, the history picture it just wrote is that copy).  Off: no field is touched, nothing is allocated */
+    int en_on; ks265_enhance_cfg en_cfg; uint8_t *en_luma;
 } Enc;
 
 static ks265_ctx *main_ctx(const Enc *e) { return e->path[PATH_MAIN].ctx; }
@@ -1798,6 +1805,16 @@ static void lane_resolve(Enc *e, const QY265EncConfig *cfg, int device, int mult
         e->dn_cfg.weight = cfg->vpp_recur_filter > 0 ? (v < 1 ? 1 : v > 30 ? 30 : v) : kDnWeight[lv];
     }
 
+    /* edge / colour enhancement on the way in: vpp_edge 1 / 2 / 3 = (gain in 1/16, core, limit, over) (8, 2, 8, 2) / (16, 2, 16, 4) / (24, 3, 24, 8); vpp_color 1 / 2 / 3 =
+     * colour gain 8 / 16 / 32 (lane_open has judged both fields) */
+    e->en_on = cfg->vpp_edge > 0 || cfg->vpp_color > 0;
+    if (e->en_on) {
+        static const ks265_enhance_cfg kEdge[4] = {{0, 0, 0, 0, 0}, {8, 2, 8, 2, 0}, {16, 2, 16, 4, 0}, {24, 3, 24, 8, 0}};
+        static const int kColor[4] = {0, 8, 16, 32};
+        e->en_cfg = kEdge[cfg->vpp_edge & 3];
+        e->en_cfg.color_gain = kColor[cfg->vpp_color & 3];
+    }
+
     /* the lookahead and the two optional streams */
     /* no -lookahead on the command line and the SDK's default GOP (hierarchical B, 8): the slice-type decision runs by itself (round 4: it costs a search of the half-size
      * picture every fourth picture, and the caller does not wait for it) - the reference's adaptive BiPredFrames is on by default as well.  -lookahead 0 switches it off. */
@@ -2140,7 +2157,7 @@ static int open_inputs(Enc *e)
      * analysis would see the picture 10 ms and more late); without it the picture is uploaded when it is scheduled, on the copy-in stream, as before.  One stream for both,
      * not a sixth: a stream more is a hardware queue shared with somebody (lane_open) */
     open_upl_stream(e, 2);
-    if ((e->la_on && e->ctx_la) || e->direct_in || e->ragged || e->dn_on) {   /* (ragged, the denoiser: the padded / filtered picture exists on the device only - every consumer reads the twin) */
+    if ((e->la_on && e->ctx_la) || e->direct_in || e->ragged || e->dn_on || e->en_on) {   /* (ragged, the denoiser, the enhancement: the padded / filtered picture exists on the device only - every consumer reads the twin) */
         e->ctx_up = e->direct_in == 1 && e->ctx_upl ? e->ctx_upl : e->ctx_la ? e->ctx_la : main_ctx(e);
         reg_handle(main_ctx(e), 1);
         for (int i = 0; i < e->nin && !r; ++i) { r = ks265_dev_malloc(main_ctx(e), (void **)&e->in[i].dev, fsz); if (!r) r = ks265_event_create(e->ctx_up, &e->in[i].ev_up); }
@@ -2150,6 +2167,8 @@ static int open_inputs(Enc *e)
         for (int i = 0; i < e->nin && !r; ++i) r = ks265_dev_malloc(main_ctx(e), (void **)&e->in[i].raw, (size_t)e->srcW * e->srcH * 3 / 2);
     if (e->dn_on)                                                       /* the two history pictures */
         for (int k = 0; k < 2 && !r; ++k) r = ks265_dev_malloc(main_ctx(e), (void **)&e->dn_hist[k], fsz);
+    if (e->en_on && e->en_cfg.edge_gain && !e->dn_on && !r)             /* the luma copy that the stencil reads (with the denoiser: its history picture) */
+        r = ks265_dev_malloc(main_ctx(e), (void **)&e->en_luma, (size_t)e->W * e->H);
     if (e->roi_on) {                                                    /* every slot: the picture's record on the device, its pinned twin, the event behind its filling - on the upload stream there is, no stream more */
         const size_t nb = (size_t)e->geom.ctu_cols * e->geom.ctu_rows * sizeof(int32_t);
         if (!e->ctx_up) { e->ctx_up = e->ctx_la ? e->ctx_la : main_ctx(e); reg_handle(main_ctx(e), 1); }
@@ -2164,6 +2183,7 @@ static int open_inputs(Enc *e)
 static void close_inputs(Enc *e)                                       /* (also what lane_enable_device_input added: twins, their events, the handle's count) */
 {
     for (int k = 0; k < 2; ++k) if (e->dn_hist[k]) ks265_dev_free(main_ctx(e), e->dn_hist[k]);
+    if (e->en_luma) ks265_dev_free(main_ctx(e), e->en_luma);
     for (int i = 0; i < MAX_INPUT; ++i) { ks265_host_free(main_ctx(e), e->in[i].i420); ks265_dev_free(main_ctx(e), e->in[i].dev); ev_free(e->ctx_up, &e->in[i].ev_up);
                                           if (e->in[i].raw) ks265_dev_free(main_ctx(e), e->in[i].raw);
                                           ks265_dev_free(main_ctx(e), e->in[i].roi_rec); ks265_host_free(main_ctx(e), e->in[i].roi_host); ev_free(e->ctx_up, &e->in[i].ev_roi); }
@@ -2320,6 +2340,13 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
             *err = QY_NOTSUPPORTED; return NULL;
         }
     }
+    if (cfg->vpp_edge || cfg->vpp_color) {                              /* the enhancement: both fields 0 .. 3, and the device library has the two entries */
+        if (cfg->vpp_edge < 0 || cfg->vpp_edge > 3 || cfg->vpp_color < 0 || cfg->vpp_color > 3) { *err = QY_NOTSUPPORTED; return NULL; }
+        if (!ks265_input_enhance || !ks265_input_enhance_validate) {
+            logf_(2, cfg->logLevel, "ks265enc: vpp_edge %d / vpp_color %d asked for and the device library has no ks265_input_enhance\n", cfg->vpp_edge, cfg->vpp_color);
+            *err = QY_NOTSUPPORTED; return NULL;
+        }
+    }
     if (cfg->picWidth <= 0 || cfg->picHeight <= 0 || (cfg->picWidth & 1) || (cfg->picHeight & 1) || cfg->frameRate <= 0 || cfg->rc < 0 || cfg->rc > 5 || cfg->bframes > GOP_MAX_B) { *err = QY_NOTSUPPORTED; return NULL; }
     Enc *e = (Enc *)calloc(1, sizeof *e);
     if (e) { e->recon_fd = -1; e->qmap_fd = -1; }
@@ -2351,7 +2378,10 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
     if (!r) r = open_devrecon(e);
     if (!r) r = open_threads(e);
     if (!r && e->dn_on) r = ks265_input_denoise_validate(main_ctx(e), &e->dn_cfg, e->W, e->H);
+    if (!r && e->en_on) r = ks265_input_enhance_validate(main_ctx(e), &e->en_cfg, e->W, e->H);
     if (r) { *err = hip_rc(r); lane_close(e, 0); return NULL; }
+    if (e->en_on) logf_(0, e->log_level, "ks265enc: enhancement on the way in: edge level %d (gain %d/16, core %d, limit %d, over %d), colour level %d (gain %d)\n", cfg->vpp_edge, e->en_cfg.edge_gain,
+                        e->en_cfg.edge_core, e->en_cfg.edge_limit, e->en_cfg.edge_over, cfg->vpp_color, e->en_cfg.color_gain);
     if (e->dn_on) logf_(0, e->log_level, "ks265enc: temporal denoiser on the way in: level %d, thr %d, weight %d/32 (motion-compensated, +-8, 16x16 blocks; the history restarts with every GOP chunk a lane is dealt)\n", cfg->vpp_denoise, e->dn_cfg.thr, e->dn_cfg.weight);
     logf_(0, e->log_level, "ks265enc: GPU %d: %dx%d %.2f fps, qp %d, -me %d (hex below %d), subme %d, refs %d, %s, sao %d (%s), key period %d, %d slice writer threads, %s\n", device, e->W, e->H,
           cfg->frameRate, e->base_qp, e->me_method, e->hex_thr, e->subme, e->refs, e->hier ? (e->gop_b == 3 ? "hierarchical-B GOP 4" : "hierarchical-B GOP 8") : e->gop_b ? "P + non-reference B" : "IPPP", e->use_sao,
@@ -2711,6 +2741,22 @@ static int stage_denoise(Enc *e, Input *slot, int key)
     slot->up_sync = 0; e->dn_at = to; e->dn_has = 1;
     return r;
 }
+/* `vpp_edge` / `vpp_color`: the slot's twin is enhanced on ctx_up, the last step in front of the encoder, and ev_up is recorded again behind it (up_sync off, as behind the
+ * denoiser).  The luma stencil reads a copy: the history picture the denoiser has just written (dn_hist[dn_at] - the twin's bytes; it stays unsharpened, the recursion never
+ * sees enhanced samples), else the lane's own plane, copied in front of the launch.  vpp_color alone needs none */
+static int stage_enhance(Enc *e, Input *slot)
+{
+    const uint8_t *luma = NULL;
+    int r = KS265_OK;
+    if (e->en_cfg.edge_gain) {
+        if (e->dn_on) luma = e->dn_hist[e->dn_at];
+        else { r = ks265_memcpy_d2d_async(e->ctx_up, e->en_luma, slot->dev, (size_t)e->W * e->H); luma = e->en_luma; }
+    }
+    if (!r) r = ks265_input_enhance(e->ctx_up, &e->en_cfg, e->W, e->H, luma, slot->dev);
+    if (!r) r = ks265_event_record(e->ctx_up, slot->ev_up);
+    slot->up_sync = 0;
+    return r;
+}
 /* the picture's own fields travel with it from now, and it goes on to the scheduler thread - at once, or with the lookahead when its results are there (la_drain).  A QY code */
 static int publish_input(Enc *e, Input *slot, long long pts, int key)
 {
@@ -2745,6 +2791,7 @@ static int lane_put(Enc *e, const PicIn *p, int key)
     if (!r && p->how == PIC_HOST && e->direct_in && !own && slot->dev && packed_strides(e, yuv)) r = stage_host_direct(e, slot, yuv, &direct);
     if (!r && p->how == PIC_HOST && !direct) r = stage_host_copy(e, slot, yuv, own);
     if (!r && e->dn_on) r = stage_denoise(e, slot, key);
+    if (!r && e->en_on) r = stage_enhance(e, slot);
     if (r) { e->pending_up = NULL; r = hip_rc(r); }                    /* (nothing of a failed picture is waited for) */
     else r = publish_input(e, slot, p->pts, key);
     if (r) return input_fail(e, slot, r);

@@ -75,6 +75,10 @@ class DenoiseCfg(C.Structure):                # ks265_denoise_cfg
     _fields_ = [("thr", C.c_int32), ("weight", C.c_int32)]
 
 
+class EnhanceCfg(C.Structure):                # ks265_enhance_cfg
+    _fields_ = [("edge_gain", C.c_int32), ("edge_core", C.c_int32), ("edge_limit", C.c_int32), ("edge_over", C.c_int32), ("color_gain", C.c_int32)]
+
+
 IN_I420, IN_NV12, IN_RGB = 0, 1, 2
 IN_RGB_F16, IN_RGB_BF16, IN_RGB_F32 = 16, 17, 18          # RGB as float samples in [0, 1]: plane, pixel_step and pitch stay in bytes
 RGB_ELEM_SIZE = {IN_RGB: 1, IN_RGB_F16: 2, IN_RGB_BF16: 2, IN_RGB_F32: 4}
@@ -124,6 +128,7 @@ EXPORTS = [
     "ks265_analysis_layout", "ks265_analysis_bytes", "ks265_analysis_pack", "ks265_analysis_pack_on", "ks265_analysis_validate", "ks265_analysis_export",
     "ks265_input_pad_validate", "ks265_input_pad", "ks265_output_crop", "ks265_sse_window",
     "ks265_input_denoise_validate", "ks265_input_denoise",
+    "ks265_input_enhance_validate", "ks265_input_enhance",
 ]
 
 
@@ -477,6 +482,20 @@ class KsContext:
 
     def input_denoise(self, thr: int, weight: int, width: int, height: int, pic, hist_in, hist_out, blocks=None) -> None:
         self._chk(self.input_denoise_rc(thr, weight, width, height, pic, hist_in, hist_out, blocks))
+
+    # ---- edge and colour enhancement on the way in (include/ks265_hip.h ks265_input_enhance; tests/enhance_ref.py is its specification)
+    def input_enhance_validate(self, cfg, width: int, height: int) -> int:
+        """cfg: (edge_gain, edge_core, edge_limit, edge_over, color_gain).  The library's return code (0, KS265_POINTER -3, KS265_NOTSUPPORTED -4): nothing is enqueued"""
+        return int(self.lib.ks265_input_enhance_validate(self.h, C.byref(EnhanceCfg(*cfg)), C.c_int(width), C.c_int(height)))
+
+    def input_enhance_rc(self, cfg, width: int, height: int, luma_src, pic) -> int:
+        """one launch on the context's stream: the luma of `pic` (uint8 device tensor, packed I420 of width x height) written from luma_src (a copy of the plane that does not
+        overlap pic; None when edge_gain is 0), its chroma mapped in place.  The library's return code"""
+        ptr = lambda x: C.c_void_p(x) if isinstance(x, int) else _p(x)
+        return int(self.lib.ks265_input_enhance(self.h, C.byref(EnhanceCfg(*cfg)), C.c_int(width), C.c_int(height), ptr(luma_src), ptr(pic)))
+
+    def input_enhance(self, cfg, width: int, height: int, luma_src, pic) -> None:
+        self._chk(self.input_enhance_rc(cfg, width, height, luma_src, pic))
 
     def intra_pred(self, ref, dst, blks: np.ndarray):
         """g_IntraPredFunction: predict every described block from dev `ref` into dev `dst` (in place)"""
