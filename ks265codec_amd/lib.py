@@ -655,6 +655,47 @@ class KsFrame:
     def cu_decide_b(self, pub, cu8):
         self.ks._chk(self.lib.ks265_cu_decide_b(self.h, _p(pub), _p(cu8)))
 
+    # ---- the decision stages of the encoder's tool set, one call each (stage tests; ks265_encode_picture* runs them itself)
+    def intra_candidates(self, src: DevPic, records, best):
+        """records: the picture's ks265_pu or ks265_pu_b records (the gate reads their costs); best: nctu x 85 uint32, cost << 6 | mode, all ones = no candidate"""
+        self.ks._chk(self.lib.ks265_intra_candidates(self.h, src.c(), _p(records), _p(best)))
+
+    def cu_decide_ii(self, pu, ibest, cu8):
+        self.ks._chk(self.lib.ks265_cu_decide_ii(self.h, _p(pu), _p(ibest), _p(cu8)))
+
+    def cu_decide_b_ii(self, pub, ibest, cu8):
+        self.ks._chk(self.lib.ks265_cu_decide_b_ii(self.h, _p(pub), _p(ibest), _p(cu8)))
+
+    def cu_decide_part(self, src: DevPic, ref: DevPic, pu, ibest, cu8):
+        """needs KsFrame(part=1)"""
+        self.ks._chk(self.lib.ks265_cu_decide_part(self.h, src.c(), ref.c(), _p(pu), _p(ibest), _p(cu8)))
+
+    def cu_decide_part_b(self, src: DevPic, ref0: DevPic, ref1: DevPic, pu0, pu1, pub, ibest, cu8):
+        self.ks._chk(self.lib.ks265_cu_decide_part_b(self.h, src.c(), ref0.c(), ref1.c(), _p(pu0), _p(pu1), _p(pub), _p(ibest), _p(cu8)))
+
+    def merge_pass(self, src: DevPic, ref0: DevPic, ref1: "DevPic | None", pu, pub, cu_in, cu_out):
+        """stage C2: pu for a P picture (ref1 None), pub for a B picture (the other None); cu_in and cu_out differ"""
+        self.ks._chk(self.lib.ks265_merge_pass(self.h, src.c(), ref0.c(), ref1.c() if ref1 is not None else Pic(None, None, None), _p(pu), _p(pub), _p(cu_in), _p(cu_out)))
+
+    def intra_inter_reconstruct(self, src: DevPic, cu8, lvl, recon: DevPic):
+        """the intra CUs of a P / B picture, after reconstruct[_b / _mref] (and the skip pass): cu8 / lvl / recon updated in place"""
+        self.ks._chk(self.lib.ks265_intra_inter_reconstruct(self.h, src.c(), _p(cu8), _p(lvl[0]), _p(lvl[1]), _p(lvl[2]), recon.c()))
+
+    def ref_pick(self, pus: list, out, idx):
+        """one list's per-PU choice: out (may be pus[0]) = the winner's record with the index bits in its cost, idx = its picture, one byte per record"""
+        arr = (C.c_void_p * len(pus))(*[p.data_ptr() for p in pus])
+        self.ks._chk(self.lib.ks265_ref_pick(self.h, C.c_int(len(pus)), arr, _p(out), _p(idx)))
+
+    def intra_decide_ex(self, src: DevPic, cu8, cost):
+        """ks265_intra_decide with the pre-selection costs (nctu x 85 uint32, PU indexing; None = not wanted)"""
+        self.ks._chk(self.lib.ks265_intra_decide_ex(self.h, src.c(), _p(cu8), _p(cost)))
+
+    def lookahead_reduce(self, intra_cost, pu) -> np.ndarray:
+        """[sum intra, sum inter, sum min, blocks | intra-cheaper << 32] over the 8x8 blocks (intra_cost None: the search's sums alone)"""
+        out = self.ks.zeros(32)
+        self.ks._chk(self.lib.ks265_lookahead_reduce(self.h, _p(intra_cost), _p(pu), _p(out)))
+        return self.ks.host(out, np.uint64)
+
     def encode_picture_mref(self, src: DevPic, refs: list, out: DevPic):
         """P picture searching len(refs) list-0 pictures (nearest first); needs KsFrame(refs >= len(refs))"""
         arr = (Pic * len(refs))(*[r.c() for r in refs])

@@ -106,6 +106,14 @@ class OraclePipeline:
         self.src, self.rec, self.deb = HostPic(g), HostPic(g), HostPic(g)
         self.ref = HostPic(g)
 
+    # ---- what each stage wrote (tests/decision_stage_cases.py): copies taken between the stages of encode / encode_mref / encode_b_mref, none of them read back by the pipeline
+    def _keep(self, name, a) -> None:
+        self.snap[name] = [x.copy() for x in a] if isinstance(a, (list, tuple)) else a.copy()
+
+    def _keep_state(self, tag: str) -> None:
+        """the CU map, the level planes and the reconstruction's samples as they stand"""
+        self._keep("cu_" + tag, self.cu8); self._keep("lvl_" + tag, self.lvl); self._keep("rec_" + tag, [self.rec.y, self.rec.u, self.rec.v])
+
     def set_picture_tools(self, intra_inter: int = -1, bi_refine: int = -1, sao: int = -1, me_method: int = -1) -> None:
         """ks265_frame_set_picture_tools: the tools of the pictures coded from here on (-1 = as created)"""
         if not hasattr(self, "_tools0"):
@@ -180,6 +188,7 @@ class OraclePipeline:
         """one picture through all stages; kind 'I' (flat key picture), 'P' (ref0) or 'B' (ref0 = L0 past, ref1 = L1 future);
         returns the reconstructed padded picture.  Intermediate results stay in self.* for stage-by-stage comparison."""
         o, cfg = self.o, C.byref(self.cfg)
+        self.snap = {}
         self.load(self.src, i420)
         null = OPic(None, None, None)
         r0 = ref0.c() if ref0 is not None else null
@@ -200,8 +209,10 @@ class OraclePipeline:
             ii = self.cfg.intra_inter
             if ii and not hasattr(self, "icost"):
                 self.icost, self.imode = np.zeros(self.nctu * 85, np.uint32), np.zeros(self.nctu * 85, np.uint8)
+            self._keep("pu0", self.pu)
             if ii and kind == "P":                       # intra candidates of this picture: cost + mode of every block from source neighbours, gated by the inter costs
                 o.kso_intra_candidates(cfg, self.src.c(), ptr(self.pu), ptr(self.icost), ptr(self.imode))
+                self._keep("icost", self.icost); self._keep("imode", self.imode)
             if kind == "P":
                 if self.cfg.part:                        # -part 1: the CU decision also prices the 2NxN / Nx2N halves (needs the pixels)
                     o.kso_cu_decide_part(cfg, self.src.c(), ptr(self.planes), ptr(self.pu), ptr(self.icost) if ii else None, ptr(self.imode) if ii else None, ptr(self.cu8))
@@ -209,9 +220,11 @@ class OraclePipeline:
                     o.kso_cu_decide_ii(cfg, ptr(self.pu), ptr(self.icost), ptr(self.imode), ptr(self.cu8))
                 else:
                     o.kso_cu_decide(cfg, ptr(self.pu), ptr(self.cu8))
+                self._keep("cu_decide", self.cu8)
                 if self.cfg.merge:
                     tmp = self.cu8.copy()
                     o.kso_merge_pass(cfg, self.src.c(), ptr(self.planes), None, ptr(self.pu), None, ptr(tmp), ptr(self.cu8))
+                    self._keep("cu_merge", self.cu8)
             else:
                 if not hasattr(self, "planes1"):
                     self.planes1 = np.zeros(16 * self.geom.bytes_y, np.uint8)
@@ -223,8 +236,10 @@ class OraclePipeline:
                 if self.cfg.subme:
                     o.kso_me_subpel(cfg, self.src.c(), ptr(self.planes1), ptr(self.pu1))
                 o.kso_bi_decide(cfg, self.src.c(), ptr(self.planes), ptr(self.planes1), ptr(self.pu), ptr(self.pu1), ptr(self.pub))
+                self._keep("pu1", self.pu1); self._keep("pub_decide", self.pub)
                 if ii:
                     o.kso_intra_candidates(cfg, self.src.c(), ptr(self.pub), ptr(self.icost), ptr(self.imode))
+                    self._keep("icost", self.icost); self._keep("imode", self.imode)
                 if self.cfg.part:                        # -part 1 in B pictures: the halves take the motions of the CU and of its quarters
                     o.kso_cu_decide_part_b(cfg, self.src.c(), ptr(self.planes), ptr(self.planes1), ptr(self.pu), ptr(self.pu1), ptr(self.pub),
                                            ptr(self.icost) if ii else None, ptr(self.imode) if ii else None, ptr(self.cu8))
@@ -232,22 +247,29 @@ class OraclePipeline:
                     o.kso_cu_decide_b_ii(cfg, ptr(self.pub), ptr(self.icost), ptr(self.imode), ptr(self.cu8))
                 else:
                     o.kso_cu_decide_b(cfg, ptr(self.pub), ptr(self.cu8))
+                self._keep("cu_decide", self.cu8)
                 if self.cfg.bi_refine == 2:              # the joint refinement for the CUs the decision chose (round 5)
                     o.kso_bi_refine_chosen(cfg, self.src.c(), ptr(self.planes), ptr(self.planes1), ptr(self.pu), ptr(self.pu1), ptr(self.pub), ptr(self.cu8))
+                    self._keep("pub_refine", self.pub); self._keep("cu_refine", self.cu8)
                 if self.cfg.merge:
                     for _ in range(int(os.environ.get("RD_MERGE_ROUNDS", "1"))):     # (experiment hook of tools/rd_eval.py; the pipeline runs one round)
                         tmp = self.cu8.copy()
                         o.kso_merge_pass(cfg, self.src.c(), ptr(self.planes), ptr(self.planes1), None, ptr(self.pub), ptr(tmp), ptr(self.cu8))
+                    self._keep("cu_merge", self.cu8)
                 p1 = ptr(self.planes1)
         if kind == "I" and self.intra:
             o.kso_intra_reconstruct(cfg, self.src.c(), ptr(self.cu8), ptr(self.lvl[0]), ptr(self.lvl[1]), ptr(self.lvl[2]), self.rec.c())
         else:
+            self._keep_state("recon_in")
             o.kso_reconstruct(cfg, self.src.c(), r0, ptr(self.planes), r1, p1, ptr(self.cu8), ptr(self.lvl[0]), ptr(self.lvl[1]), ptr(self.lvl[2]),
                               self.rec.c())
+            self._keep_state("recon")
             if (self.skip_rd and kind == "B") or (self.skip_rd >= 2 and kind == "P"):     # 1: B pictures only (where the pass pays: P pictures gain nothing measurable), 2: P pictures too
                 self.skip_pass(r0, r1)
             if self.cfg.intra_inter:
+                self._keep_state("pre_ii")
                 o.kso_intra_inter_reconstruct(cfg, self.src.c(), ptr(self.cu8), ptr(self.lvl[0]), ptr(self.lvl[1]), ptr(self.lvl[2]), self.rec.c())
+                self._keep_state("post_ii")
         self.rec_pre = [self.rec.y.copy(), self.rec.u.copy(), self.rec.v.copy()]
         if self.cfg.deblock:
             o.kso_deblock(cfg, ptr(self.cu8), self.rec.c())
@@ -264,6 +286,7 @@ class OraclePipeline:
         o, cfg = self.o, C.byref(self.cfg)
         if len(refs0) == 1 and len(refs1) == 1:
             return self.encode(i420, "B", refs0[0], refs1[0])
+        self.snap = {}
         self.load(self.src, i420)
         lists = (refs0, refs1)
         if not hasattr(self, "mr_planes"):
@@ -284,7 +307,9 @@ class OraclePipeline:
                     o.kso_me_subpel(cfg, self.src.c(), ptr(self.mr_planes[L][i]), ptr(self.mr_pu[L][i]))
             n = len(lists[L])
             arr = (C.c_void_p * n)(*[p.ctypes.data for p in self.mr_pu[L][:n]])
+            self._keep(f"pick_in{L}", self.mr_pu[L][:n])
             o.kso_ref_pick(cfg, C.c_int(n), arr, ptr(best[L]), ptr(self.mr_idx[L]))
+            self._keep(f"pick_out{L}", best[L]); self._keep(f"pick_idx{L}", self.mr_idx[L])
         mr = OMref()
         mr.n0, mr.n1 = len(refs0), len(refs1)
         for i in range(4):
@@ -295,29 +320,38 @@ class OraclePipeline:
         try:
             pl0, pl1 = ptr(self.mr_planes[0][0]), ptr(self.mr_planes[1][0])
             o.kso_bi_decide(cfg, self.src.c(), pl0, pl1, ptr(self.pu), ptr(self.pu1), ptr(self.pub))
+            self._keep("pu0", self.pu); self._keep("pu1", self.pu1); self._keep("pub_decide", self.pub)
             ii = self.cfg.intra_inter
             if ii and not hasattr(self, "icost"):
                 self.icost, self.imode = np.zeros(self.nctu * 85, np.uint32), np.zeros(self.nctu * 85, np.uint8)
             if ii:
                 o.kso_intra_candidates(cfg, self.src.c(), ptr(self.pub), ptr(self.icost), ptr(self.imode))
+                self._keep("icost", self.icost); self._keep("imode", self.imode)
             if self.cfg.part:
                 o.kso_cu_decide_part_b(cfg, self.src.c(), pl0, pl1, ptr(self.pu), ptr(self.pu1), ptr(self.pub), ptr(self.icost) if ii else None, ptr(self.imode) if ii else None, ptr(self.cu8))
             elif ii:
                 o.kso_cu_decide_b_ii(cfg, ptr(self.pub), ptr(self.icost), ptr(self.imode), ptr(self.cu8))
             else:
                 o.kso_cu_decide_b(cfg, ptr(self.pub), ptr(self.cu8))
+            self._keep("cu_decide", self.cu8)
             if self.cfg.bi_refine == 2:
                 o.kso_bi_refine_chosen(cfg, self.src.c(), pl0, pl1, ptr(self.pu), ptr(self.pu1), ptr(self.pub), ptr(self.cu8))
+                self._keep("pub_refine", self.pub); self._keep("cu_refine", self.cu8)
             if self.cfg.merge:
                 tmp = self.cu8.copy()
                 o.kso_merge_pass(cfg, self.src.c(), pl0, pl1, None, ptr(self.pub), ptr(tmp), ptr(self.cu8))
+                self._keep("cu_merge", self.cu8)
             ref_arr = (OPic * mr.n0)(*[r.c() for r in refs0])
             pl_arr = (C.c_void_p * mr.n0)(*[p.ctypes.data for p in self.mr_planes[0][:mr.n0]])
+            self._keep_state("recon_in")
             o.kso_reconstruct_mref(cfg, self.src.c(), C.c_int(mr.n0), ref_arr, pl_arr, ptr(self.cu8), ptr(self.lvl[0]), ptr(self.lvl[1]), ptr(self.lvl[2]), self.rec.c())
+            self._keep_state("recon")
             if self.skip_rd:
                 self.skip_pass(refs0[0].c(), refs1[0].c())
             if self.cfg.intra_inter:
+                self._keep_state("pre_ii")
                 o.kso_intra_inter_reconstruct(cfg, self.src.c(), ptr(self.cu8), ptr(self.lvl[0]), ptr(self.lvl[1]), ptr(self.lvl[2]), self.rec.c())
+                self._keep_state("post_ii")
         finally:
             o.kso_set_mref(None)
         self.rec_pre = [self.rec.y.copy(), self.rec.u.copy(), self.rec.v.copy()]
@@ -332,6 +366,7 @@ class OraclePipeline:
         o, cfg = self.o, C.byref(self.cfg)
         if len(refs) == 1:
             return self.encode(i420, "P", refs[0])
+        self.snap = {}
         self.load(self.src, i420)
         n = len(refs)
         if not hasattr(self, "planes_x"):
@@ -347,7 +382,9 @@ class OraclePipeline:
             if self.cfg.subme:
                 o.kso_me_subpel(cfg, self.src.c(), ptr(planes[i]), ptr(pus[i]))
         pu_arr = (C.c_void_p * n)(*[p.ctypes.data for p in pus])
+        self._keep("decide_in", pus)
         o.kso_ref_decide(cfg, C.c_int(n), pu_arr, ptr(self.pub))
+        self._keep("pub_decide", self.pub)
         # round 6 (-ref0: the anchors of the pyramid GOPs search several past anchors): the two-list records go through the stages a one-reference P picture has - intra
         # candidates against them (cfg.intra_inter), the CU tree, the merge pass on the records' pictures (cfg.merge; a context without list-1 pictures), the intra CUs' pass
         ii = self.cfg.intra_inter
@@ -355,9 +392,11 @@ class OraclePipeline:
             self.icost, self.imode = np.zeros(self.nctu * 85, np.uint32), np.zeros(self.nctu * 85, np.uint8)
         if ii:
             o.kso_intra_candidates(cfg, self.src.c(), ptr(self.pub), ptr(self.icost), ptr(self.imode))
+            self._keep("icost", self.icost); self._keep("imode", self.imode)
             o.kso_cu_decide_b_ii(cfg, ptr(self.pub), ptr(self.icost), ptr(self.imode), ptr(self.cu8))
         else:
             o.kso_cu_decide_b(cfg, ptr(self.pub), ptr(self.cu8))
+        self._keep("cu_decide", self.cu8)
         if self.cfg.merge:
             mr = OMref()
             mr.n0, mr.n1 = n, 0
@@ -370,9 +409,12 @@ class OraclePipeline:
                 o.kso_merge_pass(cfg, self.src.c(), ptr(planes[0]), None, None, ptr(self.pub), ptr(tmp), ptr(self.cu8))
             finally:
                 o.kso_set_mref(None)
+            self._keep("cu_merge", self.cu8)
         ref_arr = (OPic * n)(*[r.c() for r in refs])
         pl_arr = (C.c_void_p * n)(*[p.ctypes.data for p in planes])
+        self._keep_state("recon_in")
         o.kso_reconstruct_mref(cfg, self.src.c(), C.c_int(n), ref_arr, pl_arr, ptr(self.cu8), ptr(self.lvl[0]), ptr(self.lvl[1]), ptr(self.lvl[2]), self.rec.c())
+        self._keep_state("recon")
         if self.skip_rd >= 2:
             mr = OMref()
             mr.n0, mr.n1 = n, 0
@@ -385,7 +427,9 @@ class OraclePipeline:
             finally:
                 o.kso_set_mref(None)
         if ii:
+            self._keep_state("pre_ii")
             o.kso_intra_inter_reconstruct(cfg, self.src.c(), ptr(self.cu8), ptr(self.lvl[0]), ptr(self.lvl[1]), ptr(self.lvl[2]), self.rec.c())
+            self._keep_state("post_ii")
         self.rec_pre = [self.rec.y.copy(), self.rec.u.copy(), self.rec.v.copy()]
         if self.cfg.deblock:
             o.kso_deblock(cfg, ptr(self.cu8), self.rec.c())
