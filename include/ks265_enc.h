@@ -54,7 +54,18 @@
  *     search, `analysis`, `devrecon`, -o - sees the enhanced picture, and -psnr / -ssim are measured AGAINST THE ENHANCED PICTURE.  QY265EncoderReconfig leaves the filter as
  *     opened.  Values outside 0 .. 3, or a device library without ks265_input_enhance: QY265EncoderOpen fails with QY_NOTSUPPORTED.  Both 0 (the default): no call, no
  *     allocation, no byte of the stream changes;
- *   - vpp_hdr* (out of scope so far): accepted, ignored;
+ *   - vpp_hdr (0 / 1; QY265ConfigParse "hdr" = `-hdr 0|1`) with vpp_hdr_strength (0 .. 5; "hdr-strength"), vpp_hdr_iter (2 or 3; "hdr-iter"), vpp_hdr_sigma_s and vpp_hdr_sigma_r
+ *     (each 0 .. 100; "hdr-sigma-s", "hdr-sigma-r"; sigma_r a percentage of the 8-bit range): local contrast on the GPU, one stateless step between the denoiser and the
+ *     enhancement, for every way in (tests/hdr_ref.py is the specification of every byte).  Luma only: the base layer is vpp_hdr_iter iterations of the domain
+ *     transform in its normalised-convolution form - rows, then columns, the radius halved each iteration, guided by the luma that came in, exact in integers - and the
+ *     result is Y + strength (Y - base), rounded and clipped: contrast at large scale, no halo at a strong edge.  No tone curve on the base; chroma is not touched.  A field
+ *     left at 0 takes this build's default - strength 1.0, iter 3, sigma_s 20, sigma_r 15 = (gain 16/16, slope 8, radii 484 / 242 / 121 in 1/16 sample).  These values are
+ *     this build's choice (the reference's Linux binaries have no VPP code) and NOBODY HAS TRIED THEM ON REAL FOOTAGE.  The range that goes in is not protected.  The
+ *     denoiser's history never sees boosted samples; with vpp_edge on, the enhancement then reads a luma copy of its own.  The filter has no state, so any number of GOP
+ *     lanes gives the one-lane stream.  Everything downstream - the lookahead, -aq, the search, `analysis`, `devrecon`, -o - sees the filtered picture, and -psnr / -ssim are
+ *     measured AGAINST THE FILTERED PICTURE.  QY265EncoderReconfig leaves the filter as opened.  vpp_hdr other than 0 / 1, a field outside its range, or a device library
+ *     without ks265_input_hdr: QY265EncoderOpen fails with QY_NOTSUPPORTED.  vpp_hdr 0 (the default): the other four fields are not looked at; no call, no allocation, no
+ *     byte of the stream changes;
  *   - transskip, tuIntra, 2-pass, long-term references, VBV / CVQ: accepted, ignored;
  *   - input pictures: the caller's planes are pinned in place and uploaded from where they lie inside QY265EncoderEncodeFrame; the caller may reuse its buffers when the call returns
  *     (the SDK requires them to stay valid until the frame is done);

@@ -242,6 +242,24 @@ int ks265_input_enhance_validate(ks265_ctx *, const ks265_enhance_cfg *, int wid
 int ks265_input_enhance(ks265_ctx *, const ks265_enhance_cfg *, int width, int height,
                         const uint8_t *dev_luma_src /* W x H, pitch W; NULL only when edge_gain == 0 */,
                         uint8_t *dev_i420 /* the picture: luma written from dev_luma_src, chroma in place */);
+/* Local contrast on the way in (input_hdr.hip; tests/hdr_ref.py is the specification of every byte).  No state, on the packed I420 picture of width x height
+ * (positive multiples of 8, at most 8192: the coded size, so it runs behind ks265_input_pad).  LUMA ONLY AND IN PLACE: chroma is neither read nor written.
+ *   base           the domain transform in its normalised-convolution form, in integers: along a line d[x] = 16 + slope |Y[x] - Y[x - 1]| (1/16 sample; Y = the luma that came
+ *                  in, fixed over all iterations), ct = its running sum; a 1-D pass of radius r over a plane J of 12-bit values (1/16 code, J starts as 16 Y) replaces every
+ *                  sample by the rounded mean (2 S + n) / (2 n) of J over the samples j of its line with |ct[j] - ct[x]| <= r; the picture's ends cut the window.  Iteration
+ *                  i = 1 .. iters: a pass along the rows, then one along the columns, both with radius[i - 1].
+ *   output         D = 16 Y - base, out = clip(Y + sgn(gain D) ((|gain D| + 128) >> 8), 0, 255), gain in 1/16.  No tone curve on the base.
+ *   cfg            gain 1 .. 80, iters 2 or 3, slope 0 .. 4096, every radius in use 16 .. 2480 (a halo of at most 155 samples); anything else, or a size outside the rule:
+ *                  KS265_NOTSUPPORTED.
+ *   dev_work       ks265_input_hdr_work_bytes(width, height) bytes of device memory (0 for a size outside the rule) that the caller owns and the call may use as it likes;
+ *                  nothing is kept in it between calls.  Smaller than that (work_bytes), or overlapping the picture: KS265_POINTER.
+ * 2 x iters launches, all on the context's stream.  The range that goes in is not protected.  Pointers are judged as ks265_input_enhance judges them - the whole extent inside
+ * ONE allocation on the context's device (ks265_check_extent: KS265_POINTER), 4-byte aligned (KS265_NOTSUPPORTED); a refused call enqueues nothing.  Nothing outside the luma
+ * plane and the work buffer is read or written.  ks265_input_hdr_validate enqueues nothing and judges cfg and size alone. */
+typedef struct ks265_hdr_cfg { int32_t gain, iters, slope, radius[3]; } ks265_hdr_cfg;
+int ks265_input_hdr_validate(ks265_ctx *, const ks265_hdr_cfg *, int width, int height);
+size_t ks265_input_hdr_work_bytes(int width, int height);
+int ks265_input_hdr(ks265_ctx *, const ks265_hdr_cfg *, int width, int height, uint8_t *dev_i420 /* luma in and out */, void *dev_work, size_t work_bytes);
 /* Launch sequences as graphs: between ks265_capture_begin and ks265_capture_end everything enqueued on this context's stream by THIS thread (kernel launches,
  * async memsets of the stage functions) is recorded instead of run (hipStreamBeginCapture, relaxed mode: other threads may go on using the runtime);
  * ks265_capture_end returns an executable graph, ks265_graph_launch enqueues all of it with one runtime call.  A host whose pictures repeat the same

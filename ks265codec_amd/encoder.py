@@ -55,7 +55,13 @@ picture: PSNR is against it, not against the tensor handed in.
 edge=1|2|3 and color=1|2|3 (gentle, medium, aggressive) switch on the enhancement of THIS handle (`vpp_edge` / `vpp_color`, include/ks265_enc.h; tests/enhance_ref.py is the
 specification): an unsharp mask with coring and halo control on the luma and a saturation boost on the chroma, one stateless GPU step behind the denoiser and in front of the
 encoder, for every format and for scale= (Encoder(w, h, edge=1) behind a shrinking scale= is the ladder's mild sharpening).  The levels are untuned choices; the encoder,
-recon(), analysis() and quality() see the enhanced picture, so PSNR is against it."""
+recon(), analysis() and quality() see the enhanced picture, so PSNR is against it.
+
+hdr=True switches on the local-contrast filter of THIS handle (`vpp_hdr`, include/ks265_enc.h; tests/hdr_ref.py is the specification): the luma's base layer from 2 or 3
+iterations of an edge-preserving smoother (the domain transform, exact in integers) and the detail above it amplified - contrast at large scale without halos at strong
+edges - as a stateless GPU step between the denoiser and the enhancement, for every format and for scale=.  hdr_strength=S (0 .. 5: the detail's gain), hdr_iter=2|3,
+hdr_sigma_s=V (0 .. 100: the spatial scale in samples), hdr_sigma_r=V (0 .. 100: the range scale in per cent of the 8-bit range); one left out or 0 takes the default 1.0 / 3 /
+20 / 15.  The defaults are untuned choices; chroma is not touched; PSNR is against the filtered picture."""
 from __future__ import annotations
 
 import ctypes as C
@@ -314,7 +320,7 @@ class Encoder:
         if self._ragged and self._scale is not None:
             raise ValueError(f"scale=: the scaler writes sizes that are multiples of 8, not {width}x{height}")
         for k, v in (("wdt", width), ("hgt", height), *params.items()):
-            rc = self.lib.QY265ConfigParse(self._cfg, str(k).replace("_", "-").encode(), str(v).encode())   # keyword form of the names with a dash: sao_ref=2 -> "sao-ref"
+            rc = self.lib.QY265ConfigParse(self._cfg, str(k).replace("_", "-").encode(), str(int(v) if isinstance(v, bool) else v).encode())   # keyword form of the names with a dash: sao_ref=2 -> "sao-ref"; hdr=True -> "1"
             if rc != 0:
                 raise ValueError(f"parameter {k}={v!r}: {'unknown name' if rc == -1 else 'bad value'}")
         err = C.c_int(0)

@@ -59,7 +59,7 @@ static void usage(void)
 {
     puts("usage: ks265enc -i in.yuv -wdt W -hgt H [-fr FPS] [-preset ultrafast..placebo] [-latency zerolatency|lowdelay|livestreaming|default] [-tune T]\n"
          "                [-rc 0..5] [-qp Q] [-crf C] [-br KBPS] [-iper N] [-bframes N] [-frms N] [-threads N] [-psnr 0|1|2] [-ssim 0|1|2] [-b out.265] [-o recon.yuv]\n"
-         "                [-me 0|1|2] [-subme 0|1|2] [-merange R] [-ref N] [-sao 0..4] [-sao-ref 0|1|2 (the reference's SAO decision: 1 = as -sao 3, 2 = with its left / up merge candidates)] [-df 0|1] [-fixqp 0|1] [-md5 0|1] [-scenecut N (with -lookahead: the reference's scene-cut rule at threshold N)] [-cutree 0|1 (-rc 3: the reference's macroblock tree over the lookahead, a QP per CTU; default 1)] [-gpb 0|1 (anchors of the B-picture GOPs that search two or more past anchors go out as B slices over them; default 0)] [-hash 0|2|3 (a decoded picture hash SEI message behind every picture: 2 = CRC, 3 = checksum; default 0)] [-aq 0|1 -aqs S (adaptive quantisation: a QP per CTU from the reference's block-variance rule)] [-roi x:y:w:h:dqp (up to 8 times: dqp is added to the QP of the CTUs under the rectangle, in luma samples, for the whole stream; later rectangles win)] [-denoise 0..3 (a motion-compensated temporal filter on the GPU in front of the encoder: 1 gentle, 2 medium, 3 aggressive; default 0) -recur V (its blend weight in 1/32, 0 .. 30; alone: at the medium threshold)] [-edge 0..3 -color 0..3 (edge / colour enhancement on the GPU in front of the encoder, behind the denoiser: 1 gentle, 2 medium, 3 aggressive; default 0)] [-c config_file] [-gpus N] [-v]\n"
+         "                [-me 0|1|2] [-subme 0|1|2] [-merange R] [-ref N] [-sao 0..4] [-sao-ref 0|1|2 (the reference's SAO decision: 1 = as -sao 3, 2 = with its left / up merge candidates)] [-df 0|1] [-fixqp 0|1] [-md5 0|1] [-scenecut N (with -lookahead: the reference's scene-cut rule at threshold N)] [-cutree 0|1 (-rc 3: the reference's macroblock tree over the lookahead, a QP per CTU; default 1)] [-gpb 0|1 (anchors of the B-picture GOPs that search two or more past anchors go out as B slices over them; default 0)] [-hash 0|2|3 (a decoded picture hash SEI message behind every picture: 2 = CRC, 3 = checksum; default 0)] [-aq 0|1 -aqs S (adaptive quantisation: a QP per CTU from the reference's block-variance rule)] [-roi x:y:w:h:dqp (up to 8 times: dqp is added to the QP of the CTUs under the rectangle, in luma samples, for the whole stream; later rectangles win)] [-denoise 0..3 (a motion-compensated temporal filter on the GPU in front of the encoder: 1 gentle, 2 medium, 3 aggressive; default 0) -recur V (its blend weight in 1/32, 0 .. 30; alone: at the medium threshold)] [-edge 0..3 -color 0..3 (edge / colour enhancement on the GPU in front of the encoder, behind the denoiser: 1 gentle, 2 medium, 3 aggressive; default 0)] [-hdr 0|1 -hdr-strength S -hdr-iter N -hdr-sigma-s V -hdr-sigma-r V (local contrast on the GPU in front of the encoder, between the denoiser and the enhancement: the luma's detail above an edge-preserving base times S (0 .. 5), N = 2 or 3 iterations, spatial sigma in samples and range sigma in per cent of the 8-bit range (each 0 .. 100); a value left out or 0: 1.0 / 3 / 20 / 15; default off)] [-c config_file] [-gpus N] [-v]\n"
          "  I420 8-bit input of W x H; width and height even (a size that is no multiple of 8 is coded at the next one, with a conformance window;\n"
          "  -o then writes W x H pictures).  Needs one MI355X (gfx950): there is no CPU fallback.");
 }

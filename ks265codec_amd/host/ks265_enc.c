@@ -77,6 +77,10 @@
 /* `vpp_edge` / `vpp_color` (ks265_enc.h): the stateless enhancement behind the denoiser, the last step in front of the encoder.  Refused at open in the same way */
 #pragma weak ks265_input_enhance_validate
 #pragma weak ks265_input_enhance
+/* `vpp_hdr` (ks265_enc.h): the local-contrast filter between the denoiser and the enhancement.  Refused at open in the same way */
+#pragma weak ks265_input_hdr_validate
+#pragma weak ks265_input_hdr_work_bytes
+#pragma weak ks265_input_hdr
 
 const char strLibQy265Version[] = "ks265enc 0.2 (MI355X pixel path + host CABAC; API of libqycodec V2.6.1.3)";
 
@@ -230,11 +234,16 @@ int QY265ConfigParse(QY265EncConfig *c, const char *name, const char *value)
     INTP("aq", iAqMode, 0, 3)                                  /* the reference's hidden -aq (iAqMode, qy265enc.h:145) */
     INTP("denoise", vpp_denoise, 0, 3)                           /* the temporal filter on the way in (vpp_denoise / vpp_recur_filter, ks265_enc.h) */
     INTP("edge", vpp_edge, 0, 3) INTP("color", vpp_color, 0, 3)   /* edge / colour enhancement on the way in (vpp_edge / vpp_color, ks265_enc.h) */
+    INTP("hdr", vpp_hdr, 0, 1)                                   /* local contrast on the way in (vpp_hdr*, ks265_enc.h); the four values below: 0 = this build's default */
+    if (!strcmp(name, "hdr-iter")) { if (!num_ok || dv != iv || (iv != 0 && iv != 2 && iv != 3)) return QY265_PARAM_BAD_VALUE; c->vpp_hdr_iter = iv; return 0; }
     INTP("vbv-bufsize", vbv_buffer_size, 0, 10000000) INTP("pass", iPass, 0, 2) INTP("tlayer", temporalLayer, 0, 1) INTP("frameskip", enFrameSkip, 0, 1)
 #undef INTP
     if (!strcmp(name, "fr")) { if (!num_ok || dv <= 0 || dv > 1000) return QY265_PARAM_BAD_VALUE; c->frameRate = dv; return 0; }
     if (!strcmp(name, "aqs")) { if (!num_ok || dv < 0 || dv > 3.0) return QY265_PARAM_BAD_VALUE; c->fAqStrength = dv; return 0; }   /* -aqs (fAqStrength, qy265enc.h:146) */
     if (!strcmp(name, "recur")) { if (!num_ok || !(dv >= 0) || dv > 30) return QY265_PARAM_BAD_VALUE; c->vpp_recur_filter = dv; return 0; }
+    if (!strcmp(name, "hdr-strength")) { if (!num_ok || !(dv >= 0) || dv > 5) return QY265_PARAM_BAD_VALUE; c->vpp_hdr_strength = dv; return 0; }
+    if (!strcmp(name, "hdr-sigma-s")) { if (!num_ok || !(dv >= 0) || dv > 100) return QY265_PARAM_BAD_VALUE; c->vpp_hdr_sigma_s = dv; return 0; }
+    if (!strcmp(name, "hdr-sigma-r")) { if (!num_ok || !(dv >= 0) || dv > 100) return QY265_PARAM_BAD_VALUE; c->vpp_hdr_sigma_r = dv; return 0; }
     if (!strcmp(name, "ratetol")) { if (!num_ok || dv < 0) return QY265_PARAM_BAD_VALUE; c->fRateTolerance = dv; return 0; }
     if (!strcmp(name, "preset") || !strcmp(name, "latency") || !strcmp(name, "tune")) {
         const int k = find_name(name[0] == 'p' ? kPresetNames : name[0] == 'l' ? kLatencyNames : kTuneNames, value);
@@ -532,8 +541,12 @@ typedef struct Enc {
      * dn_hist[dn_at] holds the last filtered picture once dn_has is set.  Off: no field is touched, nothing is allocated */
     int dn_on, dn_at, dn_has; ks265_denoise_cfg dn_cfg; uint8_t *dn_hist[2];
     /* `vpp_edge` / `vpp_color` (lane_resolve: en_on, en_cfg; stage_enhance).  en_luma: the W x H copy of the luma that the stencil reads, owned by a lane with vpp_edge on and
-     * the denoiser off (with it on, the history picture it just wrote is that copy).  Off: no field is touched, nothing is allocated */
+     * the denoiser off or vpp_hdr on (with the denoiser alone, the history picture it just wrote is that copy).  Off: no field is touched, nothing is allocated */
     int en_on; ks265_enhance_cfg en_cfg; uint8_t *en_luma;
+    /* `vpp_hdr` (lane_resolve: hdr_on, hdr_cfg; stage_hdr).  hdr_work: the filter's work buffer, ks265_input_hdr_work_bytes (hdr_bytes) of the coded size, one per lane.  With
+     * it on, stage_enhance reads en_luma whether the denoiser runs or not (the history picture is no longer the luma in front of the enhancement).  Off: no field is touched,
+     * nothing is allocated */
+    int hdr_on; ks265_hdr_cfg hdr_cfg; size_t hdr_bytes; void *hdr_work;
 } Enc;
 
 static ks265_ctx *main_ctx(const Enc *e) { return e->path[PATH_MAIN].ctx; }
@@ -1815,6 +1828,24 @@ static void lane_resolve(Enc *e, const QY265EncConfig *cfg, int device, int mult
         e->en_cfg.color_gain = kColor[cfg->vpp_color & 3];
     }
 
+    /* local contrast on the way in (tests/hdr_ref.py params(), restated with its expression order; lane_open has judged the fields).  A field left at 0 takes this build's
+     * default - strength 1.0, iter 3, sigma_s 20, sigma_r 15 (a percentage of the 8-bit range): untuned choices */
+    e->hdr_on = cfg->vpp_hdr == 1;
+    if (e->hdr_on) {
+        const double strength = cfg->vpp_hdr_strength != 0 ? cfg->vpp_hdr_strength : 1.0, sigma_s = cfg->vpp_hdr_sigma_s != 0 ? cfg->vpp_hdr_sigma_s : 20.0,
+                     sigma_r = cfg->vpp_hdr_sigma_r != 0 ? cfg->vpp_hdr_sigma_r : 15.0;
+        const int n = cfg->vpp_hdr_iter ? cfg->vpp_hdr_iter : 3;
+        const double sl = floor(1600 * sigma_s / (255 * sigma_r) + 0.5);
+        memset(&e->hdr_cfg, 0, sizeof e->hdr_cfg);
+        e->hdr_cfg.gain = (int)floor(16 * strength + 0.5);
+        e->hdr_cfg.iters = n;
+        e->hdr_cfg.slope = sl > 4096 ? 4096 : (int)sl;
+        for (int i = 1; i <= n; ++i) {
+            const int rad = (int)floor(16 * (3 * sigma_s * pow(2.0, n - i) / sqrt(pow(4.0, n) - 1)) + 0.5);
+            e->hdr_cfg.radius[i - 1] = rad < 16 ? 16 : rad;
+        }
+    }
+
     /* the lookahead and the two optional streams */
     /* no -lookahead on the command line and the SDK's default GOP (hierarchical B, 8): the slice-type decision runs by itself (round 4: it costs a search of the half-size
      * picture every fourth picture, and the caller does not wait for it) - the reference's adaptive BiPredFrames is on by default as well.  -lookahead 0 switches it off. */
@@ -2157,7 +2188,7 @@ static int open_inputs(Enc *e)
      * analysis would see the picture 10 ms and more late); without it the picture is uploaded when it is scheduled, on the copy-in stream, as before.  One stream for both,
      * not a sixth: a stream more is a hardware queue shared with somebody (lane_open) */
     open_upl_stream(e, 2);
-    if ((e->la_on && e->ctx_la) || e->direct_in || e->ragged || e->dn_on || e->en_on) {   /* (ragged, the denoiser, the enhancement: the padded / filtered picture exists on the device only - every consumer reads the twin) */
+    if ((e->la_on && e->ctx_la) || e->direct_in || e->ragged || e->dn_on || e->en_on || e->hdr_on) {   /* (ragged, the denoiser, local contrast, the enhancement: the padded / filtered picture exists on the device only - every consumer reads the twin) */
         e->ctx_up = e->direct_in == 1 && e->ctx_upl ? e->ctx_upl : e->ctx_la ? e->ctx_la : main_ctx(e);
         reg_handle(main_ctx(e), 1);
         for (int i = 0; i < e->nin && !r; ++i) { r = ks265_dev_malloc(main_ctx(e), (void **)&e->in[i].dev, fsz); if (!r) r = ks265_event_create(e->ctx_up, &e->in[i].ev_up); }
@@ -2167,8 +2198,12 @@ static int open_inputs(Enc *e)
         for (int i = 0; i < e->nin && !r; ++i) r = ks265_dev_malloc(main_ctx(e), (void **)&e->in[i].raw, (size_t)e->srcW * e->srcH * 3 / 2);
     if (e->dn_on)                                                       /* the two history pictures */
         for (int k = 0; k < 2 && !r; ++k) r = ks265_dev_malloc(main_ctx(e), (void **)&e->dn_hist[k], fsz);
-    if (e->en_on && e->en_cfg.edge_gain && !e->dn_on && !r)             /* the luma copy that the stencil reads (with the denoiser: its history picture) */
+    if (e->en_on && e->en_cfg.edge_gain && (!e->dn_on || e->hdr_on) && !r)   /* the luma copy that the stencil reads (with the denoiser and without vpp_hdr: its history picture) */
         r = ks265_dev_malloc(main_ctx(e), (void **)&e->en_luma, (size_t)e->W * e->H);
+    if (e->hdr_on && !r) {                                              /* the local-contrast filter's work buffer: what the device library asks for */
+        e->hdr_bytes = ks265_input_hdr_work_bytes(e->W, e->H);
+        r = e->hdr_bytes ? ks265_dev_malloc(main_ctx(e), &e->hdr_work, e->hdr_bytes) : KS265_NOTSUPPORTED;
+    }
     if (e->roi_on) {                                                    /* every slot: the picture's record on the device, its pinned twin, the event behind its filling - on the upload stream there is, no stream more */
         const size_t nb = (size_t)e->geom.ctu_cols * e->geom.ctu_rows * sizeof(int32_t);
         if (!e->ctx_up) { e->ctx_up = e->ctx_la ? e->ctx_la : main_ctx(e); reg_handle(main_ctx(e), 1); }
@@ -2184,6 +2219,7 @@ static void close_inputs(Enc *e)                                       /* (also 
 {
     for (int k = 0; k < 2; ++k) if (e->dn_hist[k]) ks265_dev_free(main_ctx(e), e->dn_hist[k]);
     if (e->en_luma) ks265_dev_free(main_ctx(e), e->en_luma);
+    if (e->hdr_work) ks265_dev_free(main_ctx(e), e->hdr_work);
     for (int i = 0; i < MAX_INPUT; ++i) { ks265_host_free(main_ctx(e), e->in[i].i420); ks265_dev_free(main_ctx(e), e->in[i].dev); ev_free(e->ctx_up, &e->in[i].ev_up);
                                           if (e->in[i].raw) ks265_dev_free(main_ctx(e), e->in[i].raw);
                                           ks265_dev_free(main_ctx(e), e->in[i].roi_rec); ks265_host_free(main_ctx(e), e->in[i].roi_host); ev_free(e->ctx_up, &e->in[i].ev_roi); }
@@ -2340,6 +2376,14 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
             *err = QY_NOTSUPPORTED; return NULL;
         }
     }
+    if (cfg->vpp_hdr) {                                                 /* local contrast: 0 / 1, the four values 0 (this build's default) or inside their ranges, and the device library has the entries */
+        if (cfg->vpp_hdr != 1 || !(cfg->vpp_hdr_strength >= 0) || cfg->vpp_hdr_strength > 5 || (cfg->vpp_hdr_iter != 0 && cfg->vpp_hdr_iter != 2 && cfg->vpp_hdr_iter != 3) ||
+            !(cfg->vpp_hdr_sigma_s >= 0) || cfg->vpp_hdr_sigma_s > 100 || !(cfg->vpp_hdr_sigma_r >= 0) || cfg->vpp_hdr_sigma_r > 100) { *err = QY_NOTSUPPORTED; return NULL; }
+        if (!ks265_input_hdr || !ks265_input_hdr_validate || !ks265_input_hdr_work_bytes) {
+            logf_(2, cfg->logLevel, "ks265enc: vpp_hdr asked for and the device library has no ks265_input_hdr\n");
+            *err = QY_NOTSUPPORTED; return NULL;
+        }
+    }
     if (cfg->vpp_edge || cfg->vpp_color) {                              /* the enhancement: both fields 0 .. 3, and the device library has the two entries */
         if (cfg->vpp_edge < 0 || cfg->vpp_edge > 3 || cfg->vpp_color < 0 || cfg->vpp_color > 3) { *err = QY_NOTSUPPORTED; return NULL; }
         if (!ks265_input_enhance || !ks265_input_enhance_validate) {
@@ -2379,9 +2423,12 @@ static Enc *lane_open(QY265EncConfig *cfg, int device, int multi, int *err)
     if (!r) r = open_threads(e);
     if (!r && e->dn_on) r = ks265_input_denoise_validate(main_ctx(e), &e->dn_cfg, e->W, e->H);
     if (!r && e->en_on) r = ks265_input_enhance_validate(main_ctx(e), &e->en_cfg, e->W, e->H);
+    if (!r && e->hdr_on) r = ks265_input_hdr_validate(main_ctx(e), &e->hdr_cfg, e->W, e->H);
     if (r) { *err = hip_rc(r); lane_close(e, 0); return NULL; }
     if (e->en_on) logf_(0, e->log_level, "ks265enc: enhancement on the way in: edge level %d (gain %d/16, core %d, limit %d, over %d), colour level %d (gain %d)\n", cfg->vpp_edge, e->en_cfg.edge_gain,
                         e->en_cfg.edge_core, e->en_cfg.edge_limit, e->en_cfg.edge_over, cfg->vpp_color, e->en_cfg.color_gain);
+    if (e->hdr_on) logf_(0, e->log_level, "ks265enc: local contrast on the way in: gain %d/16, %d iterations, slope %d, radii %d / %d / %d (1/16 sample), work buffer %zu bytes\n", e->hdr_cfg.gain,
+                         e->hdr_cfg.iters, e->hdr_cfg.slope, e->hdr_cfg.radius[0], e->hdr_cfg.radius[1], e->hdr_cfg.radius[2], e->hdr_bytes);
     if (e->dn_on) logf_(0, e->log_level, "ks265enc: temporal denoiser on the way in: level %d, thr %d, weight %d/32 (motion-compensated, +-8, 16x16 blocks; the history restarts with every GOP chunk a lane is dealt)\n", cfg->vpp_denoise, e->dn_cfg.thr, e->dn_cfg.weight);
     logf_(0, e->log_level, "ks265enc: GPU %d: %dx%d %.2f fps, qp %d, -me %d (hex below %d), subme %d, refs %d, %s, sao %d (%s), key period %d, %d slice writer threads, %s\n", device, e->W, e->H,
           cfg->frameRate, e->base_qp, e->me_method, e->hex_thr, e->subme, e->refs, e->hier ? (e->gop_b == 3 ? "hierarchical-B GOP 4" : "hierarchical-B GOP 8") : e->gop_b ? "P + non-reference B" : "IPPP", e->use_sao,
@@ -2741,15 +2788,24 @@ static int stage_denoise(Enc *e, Input *slot, int key)
     slot->up_sync = 0; e->dn_at = to; e->dn_has = 1;
     return r;
 }
+/* `vpp_hdr`: the luma of the slot's twin gets its local contrast raised in place on ctx_up, behind the denoiser - whose history pictures stay as they are: the recursion never
+ * sees boosted samples - and in front of the enhancement (sharpening comes last); ev_up is recorded again behind it (up_sync off, as behind its neighbours) */
+static int stage_hdr(Enc *e, Input *slot)
+{
+    int r = ks265_input_hdr(e->ctx_up, &e->hdr_cfg, e->W, e->H, slot->dev, e->hdr_work, e->hdr_bytes);
+    if (!r) r = ks265_event_record(e->ctx_up, slot->ev_up);
+    slot->up_sync = 0;
+    return r;
+}
 /* `vpp_edge` / `vpp_color`: the slot's twin is enhanced on ctx_up, the last step in front of the encoder, and ev_up is recorded again behind it (up_sync off, as behind the
  * denoiser).  The luma stencil reads a copy: the history picture the denoiser has just written (dn_hist[dn_at] - the twin's bytes; it stays unsharpened, the recursion never
- * sees enhanced samples), else the lane's own plane, copied in front of the launch.  vpp_color alone needs none */
+ * sees enhanced samples), else - without the denoiser, or with `vpp_hdr` between the two - the lane's own plane, copied in front of the launch.  vpp_color alone needs none */
 static int stage_enhance(Enc *e, Input *slot)
 {
     const uint8_t *luma = NULL;
     int r = KS265_OK;
     if (e->en_cfg.edge_gain) {
-        if (e->dn_on) luma = e->dn_hist[e->dn_at];
+        if (e->dn_on && !e->hdr_on) luma = e->dn_hist[e->dn_at];
         else { r = ks265_memcpy_d2d_async(e->ctx_up, e->en_luma, slot->dev, (size_t)e->W * e->H); luma = e->en_luma; }
     }
     if (!r) r = ks265_input_enhance(e->ctx_up, &e->en_cfg, e->W, e->H, luma, slot->dev);
@@ -2791,6 +2847,7 @@ static int lane_put(Enc *e, const PicIn *p, int key)
     if (!r && p->how == PIC_HOST && e->direct_in && !own && slot->dev && packed_strides(e, yuv)) r = stage_host_direct(e, slot, yuv, &direct);
     if (!r && p->how == PIC_HOST && !direct) r = stage_host_copy(e, slot, yuv, own);
     if (!r && e->dn_on) r = stage_denoise(e, slot, key);
+    if (!r && e->hdr_on) r = stage_hdr(e, slot);
     if (!r && e->en_on) r = stage_enhance(e, slot);
     if (r) { e->pending_up = NULL; r = hip_rc(r); }                    /* (nothing of a failed picture is waited for) */
     else r = publish_input(e, slot, p->pts, key);

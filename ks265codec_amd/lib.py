@@ -79,6 +79,16 @@ class EnhanceCfg(C.Structure):                # ks265_enhance_cfg
     _fields_ = [("edge_gain", C.c_int32), ("edge_core", C.c_int32), ("edge_limit", C.c_int32), ("edge_over", C.c_int32), ("color_gain", C.c_int32)]
 
 
+class HdrCfg(C.Structure):                    # ks265_hdr_cfg
+    _fields_ = [("gain", C.c_int32), ("iters", C.c_int32), ("slope", C.c_int32), ("radius", C.c_int32 * 3)]
+
+    @classmethod
+    def of(cls, cfg):
+        """cfg: (gain, iters, slope, (radius ...)) as tests/hdr_ref.py params() gives it"""
+        gain, iters, slope, radius = cfg
+        return cls(int(gain), int(iters), int(slope), (C.c_int32 * 3)(*[int(r) for r in tuple(radius)[:3]]))
+
+
 IN_I420, IN_NV12, IN_RGB = 0, 1, 2
 IN_RGB_F16, IN_RGB_BF16, IN_RGB_F32 = 16, 17, 18          # RGB as float samples in [0, 1]: plane, pixel_step and pitch stay in bytes
 RGB_ELEM_SIZE = {IN_RGB: 1, IN_RGB_F16: 2, IN_RGB_BF16: 2, IN_RGB_F32: 4}
@@ -129,6 +139,7 @@ EXPORTS = [
     "ks265_input_pad_validate", "ks265_input_pad", "ks265_output_crop", "ks265_sse_window",
     "ks265_input_denoise_validate", "ks265_input_denoise",
     "ks265_input_enhance_validate", "ks265_input_enhance",
+    "ks265_input_hdr_validate", "ks265_input_hdr_work_bytes", "ks265_input_hdr",
 ]
 
 
@@ -496,6 +507,26 @@ class KsContext:
 
     def input_enhance(self, cfg, width: int, height: int, luma_src, pic) -> None:
         self._chk(self.input_enhance_rc(cfg, width, height, luma_src, pic))
+
+    # ---- local contrast on the way in (include/ks265_hip.h ks265_input_hdr; tests/hdr_ref.py is its specification)
+    def input_hdr_validate(self, cfg, width: int, height: int) -> int:
+        """cfg: (gain, iters, slope, (radius ...)).  The library's return code (0, KS265_POINTER -3, KS265_NOTSUPPORTED -4): nothing is enqueued"""
+        return int(self.lib.ks265_input_hdr_validate(self.h, C.byref(HdrCfg.of(cfg)), C.c_int(width), C.c_int(height)))
+
+    def input_hdr_work_bytes(self, width: int, height: int) -> int:
+        self.lib.ks265_input_hdr_work_bytes.restype = C.c_size_t
+        return int(self.lib.ks265_input_hdr_work_bytes(C.c_int(width), C.c_int(height)))
+
+    def input_hdr_rc(self, cfg, width: int, height: int, pic, work, work_bytes=None) -> int:
+        """2 x iters launches on the context's stream: the luma of `pic` (uint8 device tensor, packed I420 of width x height) filtered in place, `work` (a device tensor of
+        input_hdr_work_bytes bytes, or an address) as the passes' buffer.  The library's return code"""
+        ptr = lambda x: C.c_void_p(x) if isinstance(x, int) else _p(x)
+        if work_bytes is None:
+            work_bytes = work.numel() * work.element_size()
+        return int(self.lib.ks265_input_hdr(self.h, C.byref(HdrCfg.of(cfg)), C.c_int(width), C.c_int(height), ptr(pic), ptr(work), C.c_size_t(work_bytes)))
+
+    def input_hdr(self, cfg, width: int, height: int, pic, work) -> None:
+        self._chk(self.input_hdr_rc(cfg, width, height, pic, work))
 
     def intra_pred(self, ref, dst, blks: np.ndarray):
         """g_IntraPredFunction: predict every described block from dev `ref` into dev `dst` (in place)"""
