@@ -4,7 +4,6 @@ python tests/golden/gen_gpb_off_golden.py [directory with ks265_enc.c, ks265_cli
 import hashlib
 import json
 import os
-import subprocess
 import sys
 import tempfile
 
@@ -16,15 +15,12 @@ ROOT = os.path.dirname(TESTS)
 sys.path.insert(0, TESTS)
 sys.path.insert(0, ROOT)
 import test_gpb_host_cpu as T  # noqa: E402
+from host_harness import build_host_cli  # noqa: E402
 
 CASES = {"pyramid4": ["-bframes", "3", "-ref0", "3", "-iper", "16", "-frms", "33"], "ippp": ["-bframes", "0", "-iper", "16", "-frms", "20"]}
 host = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "ks265codec_amd", "host")
 with tempfile.TemporaryDirectory() as d:
-    from oracle_lib import build_oracle
-    build_oracle()
-    exe = os.path.join(d, "ks265enc_stub")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-I", os.path.join(ROOT, "include"), "-o", exe, *[os.path.join(host, f) for f in ("ks265_cli.c", "ks265_enc.c", "ks265_stream.c")],
-                           os.path.join(TESTS, "hip_stub.c"), "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
+    exe = build_host_cli(host_dir=host)
     yuv = os.path.join(d, "in.yuv")
     np.random.default_rng(5).integers(0, 256, 70 * T.W * T.H * 3 // 2, dtype=np.uint8).tofile(yuv)
     doc = {"cases": {}}

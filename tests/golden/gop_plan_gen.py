@@ -16,6 +16,7 @@ ROOT = os.path.dirname(TESTS)
 sys.path.insert(0, TESTS)
 sys.path.insert(0, ROOT)
 import test_gop_plan_cpu as T  # noqa: E402
+from host_harness import build_host_lib  # noqa: E402
 
 
 def case(n, iper, bframes, size=(128, 72), **env):
@@ -95,7 +96,7 @@ def host_sources(arg, d):
 
 with tempfile.TemporaryDirectory() as d:
     host, origin = host_sources(sys.argv[1] if len(sys.argv) > 1 else "HEAD^", d)
-    so = T.build_stub(d, host)
+    so = build_host_lib("hip_stub.c", host_dir=host)
     doc = {"generated_from": origin, "fields": list(T.FIELDS), "cases": {}}
     for name, c in sorted(CASES.items()):
         c["rules"] = T.lane_rules(c)

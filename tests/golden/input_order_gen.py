@@ -83,7 +83,7 @@ if __name__ == "__main__":
         os.mkdir(host)
         for f in subprocess.check_output(["git", "-C", T.ROOT, "ls-tree", "--name-only", commit, "ks265codec_amd/host/"], text=True).split():
             open(os.path.join(host, os.path.basename(f)), "wb").write(subprocess.check_output(["git", "-C", T.ROOT, "show", f"{commit}:{f}"]))
-        exe = T.build_program(d, host=host)
+        exe = T.build_program(host=host)
         for name, c in sorted(CASES.items()):
             for entries in NARROWER:
                 c["entries"] = entries

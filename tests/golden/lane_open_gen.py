@@ -4,24 +4,22 @@ python tests/golden/lane_open_gen.py"""
 import json
 import os
 import sys
-import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 import test_lane_open_cpu as T  # noqa: E402
 
 doc = json.load(open(T.GOLDEN))
-with tempfile.TemporaryDirectory() as d:
-    exe = T.build_program(d)
-    for name, case in sorted(doc["cases"].items()):
-        if "error" in case:
-            continue
-        runs = [T.open_trace(exe, case)[0] for _ in range(3)]
-        missing = [m for m in case["must"] if not any(m in ln for ln in runs[0])]
-        if runs[0] != runs[1] or runs[0] != runs[2] or missing:
-            print(f"{name}: NOT STORED - " + (f"never shows {missing}" if missing else "the three outputs differ"))
-            continue
-        case["lines"], case["sha256"] = len(runs[0]), T.digest(runs[0])
-        print(f"{name}: {case['lines']} lines {case['sha256'][:16]}")
+exe = T.build_program()
+for name, case in sorted(doc["cases"].items()):
+    if "error" in case:
+        continue
+    runs = [T.open_trace(exe, case)[0] for _ in range(3)]
+    missing = [m for m in case["must"] if not any(m in ln for ln in runs[0])]
+    if runs[0] != runs[1] or runs[0] != runs[2] or missing:
+        print(f"{name}: NOT STORED - " + (f"never shows {missing}" if missing else "the three outputs differ"))
+        continue
+    case["lines"], case["sha256"] = len(runs[0]), T.digest(runs[0])
+    print(f"{name}: {case['lines']} lines {case['sha256'][:16]}")
 json.dump(doc, open(T.GOLDEN, "w"), indent=1, sort_keys=True)
 open(T.GOLDEN, "a").write("\n")

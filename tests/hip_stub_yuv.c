@@ -26,16 +26,6 @@ int ks265_y_input_scale(ks265_ctx *, const ks265_scale_plan *, const ks265_in_de
 #include "ks265_hip.h"
 #endif
 
-/* the fields of a code: 1 valid, 0 no code of the family (below 0x1000), -1 refused */
-static int y_decode(int format, int *layout, int *sub, int *depth, int *msb)
-{
-    if (!(format & ~0xFFF)) return 0;
-    if ((format & ~0x3FF) != 0x1000) return -1;
-    *layout = format >> 8 & 3; *sub = format >> 6 & 3; *msb = format >> 5 & 1; *depth = format & 31;
-    if (*depth < 8 || *depth > 16 || *sub > 2 || (*depth == 8 && *msb) || (*layout >= 2 && *sub != 1)) return -1;
-    return 1;
-}
-
 /* the sample of the element at p */
 static int y_sample(const uint8_t *p, int depth, int msb)
 {
@@ -80,6 +70,16 @@ static void stub_yuv_to_i420(int layout, int sub, int depth, int msb, const uint
 }
 
 #ifndef KS265_STUB_YUV_ROUTINES_ONLY
+/* the fields of a code: 1 valid, 0 no code of the family (below 0x1000), -1 refused */
+static int y_decode(int format, int *layout, int *sub, int *depth, int *msb)
+{
+    if (!(format & ~0xFFF)) return 0;
+    if ((format & ~0x3FF) != 0x1000) return -1;
+    *layout = format >> 8 & 3; *sub = format >> 6 & 3; *msb = format >> 5 & 1; *depth = format & 31;
+    if (*depth < 8 || *depth > 16 || *sub > 2 || (*depth == 8 && *msb) || (*layout >= 2 && *sub != 1)) return -1;
+    return 1;
+}
+
 /* the stand-in knows no allocations: NULL and a pitch below the row are a KS265_POINTER, what the description itself shows wrong a KS265_NOTSUPPORTED, as on the device */
 static int stub_yuv_in_check(const ks265_in_desc *d, int layout, int sub, int depth)
 {

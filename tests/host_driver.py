@@ -5,11 +5,9 @@ import ctypes as C, hashlib, json, os, sys
 ROOT, N, iper, bframes, W, H = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5]), int(sys.argv[6])
 out_path = sys.argv[7] if len(sys.argv) > 7 else None
 import numpy as np
-LAY = json.load(open(os.path.join(ROOT, "tests", "golden", "qy265_layout.json")))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from host_harness import LAY, YUV, Nal, Picture
 lib = C.CDLL(os.environ["KS265_STUB_LIB"]); lib.QY265EncoderOpen.restype = C.c_void_p
-class YUV(C.Structure): _fields_ = [("iWidth", C.c_int), ("iHeight", C.c_int), ("pData", C.POINTER(C.c_ubyte) * 3), ("iStride", C.c_int * 3)]
-class Picture(C.Structure): _fields_ = [("iSliceType", C.c_int), ("poc", C.c_int), ("pts", C.c_longlong), ("dts", C.c_longlong), ("yuv", C.POINTER(YUV))]
-class Nal(C.Structure): _fields_ = [("naltype", C.c_int), ("tid", C.c_int), ("iSize", C.c_int), ("pts", C.c_longlong), ("pPayload", C.POINTER(C.c_ubyte))]
 rng = np.random.default_rng(3)
 clip = rng.integers(0, 256, (11, W * H * 3 // 2), dtype=np.uint8)
 cfg = (C.c_uint8 * LAY["sizeof_config"])()

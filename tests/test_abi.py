@@ -83,9 +83,10 @@ def test_product_does_not_touch_the_oracle():
 def test_header_is_plain_c(tmp_path):
     """the drop-in boundary is a C ABI: include/ks265_hip.h must compile as C99 (-pedantic) with the documented struct sizes"""
     import subprocess
+    from host_harness import cc
     src = tmp_path / "h.c"
     src.write_text('#include "ks265_hip.h"\nint main(void) { ks265_frame_cfg c = {0}; (void)c;\n'
                    '  return sizeof(ks265_intra_blk) == 16 && sizeof(ks265_cu8) == 12 && sizeof(ks265_pu) == 16 && sizeof(ks265_frame_cfg) == 124 ? 0 : 1; }\n')
     exe = tmp_path / "h"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    cc("-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), src, "-o", exe)
     assert subprocess.call([str(exe)]) == 0

@@ -10,18 +10,18 @@
 from __future__ import annotations
 
 import ctypes as C
-import os
 import re
 import subprocess
 
 import numpy as np
 import pytest
 
-import test_device_recon_host_cpu as dr
-from test_device_recon_host_cpu import CLIP, FSZ, H, LAY, LOG_CB, QY_FAIL, QY_NOTSUPPORTED, QY_OK, QY_POINTER, W, DevPicture, Nal, Picture, YUV
+import host_harness
+from host_harness import (CLIP, LOG_CB, QY_FAIL, QY_NOTSUPPORTED, QY_OK, QY_POINTER, DevPicture, Nal, Picture, YUV, build_host_lib, build_host_program, digest, load_host_lib,
+                          open_handle, scheduler_trace, submit_order_cases)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+W, H = 128, 72
+FSZ = W * H * 3 // 2
 W8, H8, CC, CR = W // 8, H // 8, (W + 63) // 64, (H + 63) // 64
 MAGIC = 0x414E4C59
 
@@ -35,18 +35,13 @@ class DevAnalysis(C.Structure):
 
 
 @pytest.fixture(scope="module")
-def an_lib(tmp_path_factory):
-    lib = C.CDLL(dr._build(tmp_path_factory.mktemp("stuban"), "hip_stub_analysis.c"))
-    lib.QY265EncoderOpen.restype = C.c_void_p
-    lib.ks265_stub_live.restype = C.c_long
-    return lib
+def an_lib():
+    return load_host_lib(build_host_lib("hip_stub_analysis.c"))
 
 
 @pytest.fixture(scope="module")
-def plain_lib(tmp_path_factory):
-    lib = C.CDLL(dr._build(tmp_path_factory.mktemp("stubplain_an"), "hip_stub.c"))
-    lib.QY265EncoderOpen.restype = C.c_void_p
-    return lib
+def plain_lib():
+    return load_host_lib(build_host_lib("hip_stub.c"))
 
 
 class Arrays:
@@ -87,27 +82,7 @@ def run(lib, n, params=(), latency=b"default", env=None, analysis=None, devrecon
     lines = []
     cb = LOG_CB(lambda m: lines.append(m.decode()))
     lib.QY265SetLogPrintf(cb)
-    old = {k: os.environ.get(k) for k in (env or {})}
-    os.environ.update({k: str(v) for k, v in (env or {}).items()})
-    try:
-        cfg = (C.c_uint8 * LAY["sizeof_config"])()
-        assert lib.QY265ConfigDefaultPreset(cfg, b"medium", None, latency) == 0
-        for k, v in (("wdt", W), ("hgt", H), ("fr", 50), ("rc", 0), ("qp", 34), ("threads", 4), ("log", 1), *params):
-            assert lib.QY265ConfigParse(cfg, k.encode(), str(v).encode()) == 0, k
-        for name, v in (("analysis", analysis), ("devrecon", devrecon)):
-            if v is not None:
-                assert lib.ks265_enc_set_default(name.encode(), C.c_int(v)) == 0
-        err = C.c_int(0)
-        h = C.c_void_p(lib.QY265EncoderOpen(cfg, C.byref(err)))
-        for name, v in (("analysis", analysis), ("devrecon", devrecon)):
-            if v is not None:
-                assert lib.ks265_enc_set_default(name.encode(), C.c_int(0)) == 0      # read at open: the handle keeps it
-        assert h.value, hex(err.value & 0xFFFFFFFF)
-    finally:
-        for k, v in old.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
+    h = open_handle(lib, W, H, params=params, latency=latency, env=env, defaults=[name for name, v in (("analysis", analysis), ("devrecon", devrecon)) if v])
     live_dev = lib.ks265_stub_live(3) if hasattr(lib, "ks265_stub_live") else -1
     nal, nn, pic, outp, yuv, info = C.POINTER(Nal)(), C.c_int(0), Picture(), Picture(), YUV(), Picture()
     yuv.iWidth, yuv.iHeight = W, H
@@ -182,7 +157,7 @@ def run(lib, n, params=(), latency=b"default", env=None, analysis=None, devrecon
     return bytes(bs), "".join(lines), calls, pend, lanes, live_dev
 
 
-SESSIONS = dict(dr.SESSIONS, bframes3=dict(n=40, params=(("iper", 32), ("bframes", 3))))
+SESSIONS = dict(host_harness.SESSIONS, bframes3=dict(n=40, params=(("iper", 32), ("bframes", 3))))
 
 
 def check_plan(name, st, qp, has_map, deltas):
@@ -306,15 +281,7 @@ def test_device_library_without_the_entries(plain_lib):
         assert bs == plain and len(plain) > 100 and all(p[0] == 0 for p in pend)
         assert log.count("ks265enc: analysis is unavailable: ") == 1 and "unavailable" not in log0
     lib = plain_lib
-    cfg = (C.c_uint8 * LAY["sizeof_config"])()
-    assert lib.QY265ConfigDefaultPreset(cfg, b"medium", None, b"default") == 0
-    for k, v in (("wdt", W), ("hgt", H), ("log", 3)):
-        assert lib.QY265ConfigParse(cfg, k.encode(), str(v).encode()) == 0
-    assert lib.ks265_enc_set_default(b"analysis", C.c_int(1)) == 0
-    err = C.c_int(0)
-    h = C.c_void_p(lib.QY265EncoderOpen(cfg, C.byref(err)))
-    assert lib.ks265_enc_set_default(b"analysis", C.c_int(0)) == 0
-    assert h.value
+    h = open_handle(lib, W, H, params=(("log", 3),), defaults=("analysis",))
     assert lib.ks265_enc_get_device_analysis(h, C.byref(Arrays().desc()), C.byref(Picture())) == QY_NOTSUPPORTED
     assert lib.ks265_enc_device_analysis_pending(h) == 0
     lib.QY265EncoderClose(h)
@@ -324,24 +291,21 @@ def test_device_library_without_the_entries(plain_lib):
 def test_switch_off_the_scheduler_threads_calls_are_the_pinned_ones(tmp_path, case):
     """the stand-in WITH the entries, the switch off: the scheduler thread's calls to the device library are those tests/golden/submit_order.json pins - not one call added;
     with it on: one pack per picture, and one record of the slot's ev_packed behind it"""
-    import test_submit_order_cpu as so
-    lib = dr._build(tmp_path, "hip_stub_analysis.c", extra=("-DKS265_STUB_SSIM",))
-    c = so.CASES[case]
-    lines = so.scheduler_trace(lib, c, str(tmp_path / "calls.log"))
-    assert len(lines) == c["lines"] and so.digest(lines) == c["sha256"]
-    on = so.scheduler_trace(lib, dict(c, env=dict(c["env"], KS265_ANALYSIS=1)), str(tmp_path / "calls_on.log"))
+    lib = build_host_lib("hip_stub_analysis.c", ("KS265_STUB_SSIM",))
+    c = submit_order_cases()[case]
+    lines = scheduler_trace(lib, c, str(tmp_path / "calls.log"))
+    assert len(lines) == c["lines"] and digest(lines) == c["sha256"]
+    on = scheduler_trace(lib, dict(c, env=dict(c["env"], KS265_ANALYSIS=1)), str(tmp_path / "calls_on.log"))
     packs = [i for i, ln in enumerate(on) if ln.startswith("ks265_analysis_pack_on ")]
     assert len(packs) == c["n"] and len(on) == c["lines"] + 2 * c["n"], "one pack and one event record per picture, nothing else"
     assert all(on[i + 1].startswith("ks265_event_record ") for i in packs)
-    both = so.scheduler_trace(lib, dict(c, env=dict(c["env"], KS265_ANALYSIS=1, KS265_DEVRECON=1)), str(tmp_path / "calls_both.log"))
+    both = scheduler_trace(lib, dict(c, env=dict(c["env"], KS265_ANALYSIS=1, KS265_DEVRECON=1)), str(tmp_path / "calls_both.log"))
     assert len(both) == c["lines"] + 3 * c["n"], "both switches: two packs, ONE record of ev_packed"
 
 
-def test_bookkeeping_with_two_cursors_under_the_sanitizers(tmp_path):
+def test_bookkeeping_with_two_cursors_under_the_sanitizers():
     """ks265_recon.h with both fetch cursors driven alone by a stand-alone program built with -fsanitize=address,undefined, as a child process"""
-    exe = str(tmp_path / "analysis_list")
-    subprocess.check_call(["gcc", "-O1", "-g", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan",
-                           "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "ks265codec_amd", "host"), "-o", exe, os.path.join(HERE, "analysis_list_main.c")])
+    exe = build_host_program("analysis_list_main.c")
     for seed in (1, 2, 3):
         r = subprocess.run([exe, str(seed), "60000"], capture_output=True, text=True, timeout=120)
         assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout[-400:] + r.stderr[-2000:]

@@ -8,17 +8,12 @@ import subprocess
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+from host_harness import HOST, build_host_program
 
 
 @pytest.fixture(scope="module")
-def cli(tmp_path_factory):
-    d = tmp_path_factory.mktemp("cli")
-    exe = str(d / "cli_stub")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "ks265codec_amd", "host", "ks265_cli.c"),
-                           os.path.join(HERE, "cli_stub_encoder.c"), "-o", exe, "-lpthread"])
-    return exe
+def cli():
+    return build_host_program(os.path.join(HOST, "ks265_cli.c"), sanitize=False, extra_sources=("cli_stub_encoder.c",))
 
 
 def _clip(path, W, H, n, tail=b""):

@@ -4,16 +4,12 @@ tests/test_gpu_compact_records.py holds the kernels to."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import compact_records_ref as R
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+from host_harness import build_host_lib, load_host_lib
 
 
 def chunk_orders(nchunk: int):
@@ -83,17 +79,9 @@ def test_check_block_sees_what_is_wrong():
 
 
 @pytest.fixture(scope="module")
-def stub(tmp_path_factory):
-    """the stand-in built as tests/test_host_pipeline_cpu.py builds it"""
-    from oracle_lib import build_oracle
-    build_oracle()
-    d = tmp_path_factory.mktemp("stubpack")
-    so = str(d / "libks265enc_stub.so")
-    host = os.path.join(ROOT, "ks265codec_amd", "host")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-fPIC", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"), "-shared", "-o", so,
-                           os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"), os.path.join(HERE, "hip_stub.c"),
-                           "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
-    lib = C.CDLL(so)
+def stub():
+    """the stand-in as tests/test_host_pipeline_cpu.py has it"""
+    lib = load_host_lib(build_host_lib("hip_stub.c"))
     lib.ks265_frame_levels.restype = C.c_void_p
     ctx = C.c_void_p()
     assert lib.ks265_create(C.byref(ctx), 0) == 0

@@ -9,12 +9,10 @@
   * against the plain stand-in (tests/hip_stub.c) a handle with either field set is refused with QY_NOTSUPPORTED; `recur=30` alone works (thr 10, weight 30); `denoise=4` and
     `recur=31` are QY265_PARAM_BAD_VALUE; values outside the ranges written into the structure are refused at open;
   * a handle with both fields 0 makes no denoise call;
-  * tests/denoise_main.c, the host and the stand-in under -fsanitize=address,undefined as a program of its own: 5 pictures at 202x134 with denoise=3, both latencies."""
+  * tests/input_filter_main.c, the host and the stand-in under -fsanitize=address,undefined as a program of its own: 5 pictures at 202x134 with denoise=3, both latencies."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -23,10 +21,9 @@ import denoise_ref as dr
 import picture_window_ref as pw
 import window_sps as ws
 import yuv_scale_ref as ys
-from test_window_host_cpu import LAY, QY_NOTSUPPORTED, QY_OK, DevPicture, Nal, Picture, _build, clip, nals, open_handle, session, try_open
+from host_harness import (LAY, QY_NOTSUPPORTED, QY_OK, build_host_lib, build_host_program, clip, drive, filter_program, host_picture, i420_picture, load_host_lib, nals,
+                          open_handle, preceded, session, try_open)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 W, H, N = 208, 136, 17
 BAD_VALUE = -2
 T2 = dr.level_params(2)
@@ -38,28 +35,12 @@ class DnCall(C.Structure):
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp("stubdn")
-    so, log = _build(d, "hip_stub_denoise.c"), str(d / "calls.log")
-    old = os.environ.get("KS265_STUB_CALL_LOG")
-    os.environ["KS265_STUB_CALL_LOG"] = log                              # read once, at the library's first logged call
-    try:
-        lib = C.CDLL(so)
-        lib.QY265EncoderOpen.restype = C.c_void_p
-        lib.ks265_stub_live.restype = C.c_long
-        lib.QY265EncoderClose(open_handle(lib, 128, 72))                # (the first logged call)
-    finally:
-        os.environ.pop("KS265_STUB_CALL_LOG", None)
-        if old is not None:
-            os.environ["KS265_STUB_CALL_LOG"] = old
-    lib.call_log_path = log
-    return lib
+    return load_host_lib(build_host_lib("hip_stub_denoise.c"), call_log=str(tmp_path_factory.mktemp("stubdn") / "calls.log"))
 
 
 @pytest.fixture(scope="module")
-def plain(tmp_path_factory):
-    lib = C.CDLL(_build(tmp_path_factory.mktemp("stubplaindn"), "hip_stub.c"))
-    lib.QY265EncoderOpen.restype = C.c_void_p
-    return lib
+def plain():
+    return load_host_lib(build_host_lib("hip_stub.c"))
 
 
 def dn_calls(lib):
@@ -69,7 +50,7 @@ def dn_calls(lib):
 
 
 def noisy_clip(w, h, n, seed):
-    """test_window_host_cpu's moving clip with noise in all three planes"""
+    """the harness's moving clip with noise in all three planes"""
     rng = np.random.default_rng(seed)
     return [np.clip(p.astype(np.int32) + np.rint(rng.normal(0, 3, p.shape)).astype(np.int32), 0, 255).astype(np.uint8) for p in clip(w, h, n, seed)]
 
@@ -151,28 +132,9 @@ def test_every_way_in_gives_the_plain_handle_s_stream_of_filtered_pictures(lib, 
 
 def scaled_session(lib, pictures, sw, sh, params=()):
     """a W x H handle fed sources of sw x sh through the scaled entry (filter 1); its stream"""
-    hd = open_handle(lib, W, H, params=params)
+    hd = open_handle(lib, W, H, lanes=1, params=params)
     assert lib.ks265_enc_enable_device_input(hd) == QY_OK and lib.ks265_enc_enable_device_scale(hd, sw, sh) == QY_OK
-    nal, nn, outp, bs = C.POINTER(Nal)(), C.c_int(0), Picture(), bytearray()
-
-    def collect():
-        bs.extend(b"".join(C.string_at(nal[i].pPayload, nal[i].iSize) for i in range(nn.value) if nal[i].iSize > 0))
-
-    for t, a in enumerate(pictures):
-        a = np.ascontiguousarray(a).copy()
-        d = DevPicture()
-        d.format, d.device, d.stream, d.pts = 0, 0, None, t
-        d.plane[0], d.plane[1], d.plane[2] = a.ctypes.data, a.ctypes.data + sw * sh, a.ctypes.data + sw * sh * 5 // 4
-        d.pitch[0], d.pitch[1], d.pitch[2] = sw, sw // 2, sw // 2
-        assert lib.ks265_enc_encode_device_frame_scaled(hd, C.byref(nal), C.byref(nn), C.byref(d), sw, sh, 1, C.byref(outp)) == QY_OK
-        collect()
-        a[:] = 0x5A
-    while lib.QY265EncoderDelayedFrames(hd) > 0:
-        assert lib.QY265EncoderEncodeFrame(hd, C.byref(nal), C.byref(nn), None, C.byref(outp), 0) == QY_OK
-        collect()
-    lib.QY265EncoderClose(hd)
-    assert [lib.ks265_stub_live(k) for k in range(5)] == [0] * 5
-    return bytes(bs)
+    return drive(lib, hd, (i420_picture(lib, hd, a, sw, sh, t, scaled=(sw, sh, 1)) for t, a in enumerate(pictures)))
 
 
 def test_scaled_way_in(lib):
@@ -227,9 +189,9 @@ def test_ragged_size_is_filtered_behind_the_pad(lib):
 
 def test_open_and_configuration(lib, plain):
     for params in ((("denoise", 1),), (("recur", 12),), (("denoise", 3), ("recur", 2.5))):
-        hd, err = try_open(plain, W, H, params=params)
+        hd, err = try_open(plain, W, H, lanes=1, params=params)
         assert not hd.value and err == QY_NOTSUPPORTED, params
-    hd, err = try_open(plain, W, H)
+    hd, err = try_open(plain, W, H, lanes=1)
     assert hd.value
     plain.QY265EncoderClose(hd)
     cfg = (C.c_uint8 * LAY["sizeof_config"])()
@@ -261,26 +223,16 @@ def test_open_and_configuration(lib, plain):
 
 def test_reconfig_leaves_the_filter_as_opened(lib):
     src = noisy_clip(W, H, 4, 181)
-    hd = open_handle(lib, W, H, latency=b"zerolatency", params=(("denoise", 2),))
+    hd = open_handle(lib, W, H, lanes=1, latency=b"zerolatency", params=(("denoise", 2),))
     cfg = (C.c_uint8 * LAY["sizeof_config"])()
     assert lib.QY265ConfigDefaultPreset(cfg, b"medium", None, b"zerolatency") == 0
     for k, v in (("wdt", W), ("hgt", H), ("fr", 50), ("rc", 0), ("qp", 34), ("denoise", 0)):
         assert lib.QY265ConfigParse(cfg, k.encode(), str(v).encode()) == 0
-    from test_window_host_cpu import YUV
-    nal, nn, pic, outp, yuv = C.POINTER(Nal)(), C.c_int(0), Picture(), Picture(), YUV()
-    yuv.iWidth, yuv.iHeight = W, H
-    yuv.iStride[0], yuv.iStride[1], yuv.iStride[2] = W, W // 2, W // 2
-    pic.yuv = C.pointer(yuv)
+    lib.QY265EncoderReconfig.restype = None
     lib.ks265_stub_denoise_reset()
-    for t, p in enumerate(src):
-        if t == 2:
-            lib.QY265EncoderReconfig.restype = None
-            lib.QY265EncoderReconfig(hd, cfg)
-        for k, off in enumerate((0, W * H, W * H * 5 // 4)):
-            yuv.pData[k] = C.cast(p.ctypes.data + off, C.POINTER(C.c_ubyte))
-        pic.pts = t
-        assert lib.QY265EncoderEncodeFrame(hd, C.byref(nal), C.byref(nn), C.byref(pic), C.byref(outp), 0) == QY_OK
-    lib.QY265EncoderClose(hd)
+    puts = [host_picture(lib, hd, p, W, H, t) for t, p in enumerate(src)]
+    puts[2] = preceded(lambda: lib.QY265EncoderReconfig(hd, cfg), puts[2])
+    drive(lib, hd, puts)
     assert [c[2:5] for c in dn_calls(lib)] == [(*T2, int(t > 0)) for t in range(4)]
 
 
@@ -299,24 +251,16 @@ def test_off_makes_no_call(lib):
 
 
 @pytest.fixture(scope="module")
-def sanitized(tmp_path_factory):
-    """tests/denoise_main.c + the host + the stand-in, built once with -fsanitize=address,undefined"""
-    from oracle_lib import build_oracle
-    build_oracle()
-    host = os.path.join(ROOT, "ks265codec_amd", "host")
-    exe = str(tmp_path_factory.mktemp("dnsan") / "denoise_main")
-    subprocess.check_call(["gcc", "-O1", "-g", "-std=gnu11", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "include"),
-                           "-o", exe, os.path.join(HERE, "denoise_main.c"), os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"),
-                           os.path.join(HERE, "hip_stub_denoise.c"), "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
-    return exe
+def sanitized():
+    """tests/input_filter_main.c + the host + the stand-in, built once with -fsanitize=address,undefined"""
+    return build_host_program("input_filter_main.c", stub="hip_stub_denoise.c")
 
 
 @pytest.mark.parametrize("latency", ["default", "zerolatency"])
 def test_host_and_stand_in_under_the_sanitizers(sanitized, tmp_path, latency):
     out = str(tmp_path / "out.265")
-    r = subprocess.run([sanitized, "202", "134", "5", out] + (["zerolatency"] if latency == "zerolatency" else []), capture_output=True, text=True,
-                       env={**os.environ, "KS265_GOP_LANES": "1", "ASAN_OPTIONS": "detect_leaks=1"})
-    assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
-    assert "denoise calls 5" in r.stdout
+    recs = filter_program(sanitized, 202, 134, 5, out, latency, "denoise=3")
+    assert recs["denoise"] == [dict(w=208, h=136, thr=16, weight=24, has_hist=int(t > 0), hist_in=(t - 1) & 1 if t else -1, hist_out=t & 1) for t in range(5)]
+    assert len(recs["pad"]) == 5 and not recs["enhance"] + recs["hdr"]
     sps = ws.stream_sps(open(out, "rb").read())
     assert ws.output_size(sps) == (202, 134) and (sps["width"], sps["height"]) == (208, 136)

@@ -9,19 +9,16 @@ import sys
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+from host_harness import ROOT, build_host_lib
 
 _DRIVER = r"""
 import ctypes as C, hashlib, json, os, sys
 import numpy as np
 ROOT, probe = sys.argv[1], int(sys.argv[2])
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 from ks265codec_amd.encoder import DevPicture, Nal, QY_NOTSUPPORTED
-LAY = json.load(open(os.path.join(ROOT, "tests", "golden", "qy265_layout.json")))
+from host_harness import LAY, YUV, Picture
 lib = C.CDLL(os.environ["KS265_STUB_LIB"], mode=os.RTLD_NOW); lib.QY265EncoderOpen.restype = C.c_void_p
-class YUV(C.Structure): _fields_ = [("iWidth", C.c_int), ("iHeight", C.c_int), ("pData", C.POINTER(C.c_ubyte) * 3), ("iStride", C.c_int * 3)]
-class Picture(C.Structure): _fields_ = [("iSliceType", C.c_int), ("poc", C.c_int), ("pts", C.c_longlong), ("dts", C.c_longlong), ("yuv", C.POINTER(YUV))]
 W, H, N = 128, 72, 9
 clip = np.random.default_rng(5).integers(0, 256, (N, W * H * 3 // 2), dtype=np.uint8)
 cfg = (C.c_uint8 * LAY["sizeof_config"])()
@@ -57,23 +54,12 @@ print(json.dumps({"md5": md.hexdigest(), "codes": codes, "notsupported": QY_NOTS
 
 
 @pytest.fixture(scope="module")
-def stub_lib(tmp_path_factory):
-    from oracle_lib import build_oracle
-    build_oracle()
-    d = tmp_path_factory.mktemp("stubdev")
-    so = str(d / "libks265enc_stub.so")
-    host = os.path.join(ROOT, "ks265codec_amd", "host")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-fPIC", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"), "-shared", "-o", so,
-                           os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"), os.path.join(HERE, "hip_stub.c"),
-                           "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
-    return so
+def stub_lib():
+    return build_host_lib("hip_stub.c")
 
 
 def _run(stub_lib, probe):
-    script = os.path.join(os.path.dirname(stub_lib), "drive.py")
-    with open(script, "w") as f:
-        f.write(_DRIVER)
-    r = subprocess.run([sys.executable, script, ROOT, str(probe)], capture_output=True, text=True, timeout=120, env=dict(os.environ, KS265_STUB_LIB=stub_lib))
+    r = subprocess.run([sys.executable, "-c", _DRIVER, ROOT, str(probe)], capture_output=True, text=True, timeout=120, env=dict(os.environ, KS265_STUB_LIB=stub_lib))
     assert r.returncode == 0, r.stdout[-600:] + r.stderr[-1200:]
     return json.loads(r.stdout.strip().splitlines()[-1])
 

@@ -8,66 +8,26 @@
 from __future__ import annotations
 
 import ctypes as C
-import json
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+from host_harness import (CLIP, LOG_CB, SESSIONS, QY_FAIL, QY_NOTSUPPORTED, QY_OK, QY_POINTER, DevPicture, Nal, Picture, YUV, build_host_lib, build_host_program, digest, load_host_lib, open_handle,
+                          scheduler_trace, submit_order_cases)
+
 W, H = 128, 72
 FSZ = W * H * 3 // 2
-QY_OK, QY_FAIL, QY_POINTER, QY_NOTSUPPORTED = 0, -0x7FFFFFFF, -0x7FFFFFFD, -0x7FFFFFFC
-LAY = json.load(open(os.path.join(HERE, "golden", "qy265_layout.json")))
-
-
-class YUV(C.Structure):
-    _fields_ = [("iWidth", C.c_int), ("iHeight", C.c_int), ("pData", C.POINTER(C.c_ubyte) * 3), ("iStride", C.c_int * 3)]
-
-
-class Picture(C.Structure):
-    _fields_ = [("iSliceType", C.c_int), ("poc", C.c_int), ("pts", C.c_longlong), ("dts", C.c_longlong), ("yuv", C.POINTER(YUV))]
-
-
-class Nal(C.Structure):
-    _fields_ = [("naltype", C.c_int), ("tid", C.c_int), ("iSize", C.c_int), ("pts", C.c_longlong), ("pPayload", C.POINTER(C.c_ubyte))]
-
-
-class DevPicture(C.Structure):
-    _fields_ = [("format", C.c_int), ("device", C.c_int), ("plane", C.c_void_p * 3), ("pitch", C.c_int * 3), ("pixel_step", C.c_int),
-                ("matrix", C.c_int), ("full_range", C.c_int), ("stream", C.c_void_p), ("pts", C.c_longlong)]
-
-
-def _build(d, stub, extra=()):
-    from oracle_lib import build_oracle
-    build_oracle()
-    so = str(d / "libks265enc_stub.so")
-    host = os.path.join(ROOT, "ks265codec_amd", "host")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-fPIC", "-Wall", "-Wextra", *extra, "-I", os.path.join(ROOT, "include"), "-shared", "-o", so,
-                           os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"), os.path.join(HERE, stub),
-                           "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
-    return so
 
 
 @pytest.fixture(scope="module")
-def recon_lib(tmp_path_factory):
-    lib = C.CDLL(_build(tmp_path_factory.mktemp("stubrecon"), "hip_stub_recon.c"))
-    lib.QY265EncoderOpen.restype = C.c_void_p
-    lib.ks265_stub_live.restype = C.c_long
-    return lib
+def recon_lib():
+    return load_host_lib(build_host_lib("hip_stub_recon.c"))
 
 
 @pytest.fixture(scope="module")
-def plain_lib(tmp_path_factory):
-    lib = C.CDLL(_build(tmp_path_factory.mktemp("stubplain"), "hip_stub.c"))
-    lib.QY265EncoderOpen.restype = C.c_void_p
-    return lib
-
-
-CLIP = np.random.default_rng(17).integers(0, 256, (13, FSZ), dtype=np.uint8)
-LOG_CB = C.CFUNCTYPE(None, C.c_char_p)
+def plain_lib():
+    return load_host_lib(build_host_lib("hip_stub.c"))
 
 
 def run(lib, n, params=(), latency=b"default", env=None, devrecon=None, dump=None, fetch=lambda k, t: True, close_early=False, bad_first=False):
@@ -76,25 +36,7 @@ def run(lib, n, params=(), latency=b"default", env=None, devrecon=None, dump=Non
     lines = []
     cb = LOG_CB(lambda m: lines.append(m.decode()))
     lib.QY265SetLogPrintf(cb)
-    old = {k: os.environ.get(k) for k in (env or {})}
-    os.environ.update({k: str(v) for k, v in (env or {}).items()})
-    try:
-        cfg = (C.c_uint8 * LAY["sizeof_config"])()
-        assert lib.QY265ConfigDefaultPreset(cfg, b"medium", None, latency) == 0
-        for k, v in (("wdt", W), ("hgt", H), ("fr", 50), ("rc", 0), ("qp", 34), ("threads", 4), ("log", 1), *params):
-            assert lib.QY265ConfigParse(cfg, k.encode(), str(v).encode()) == 0, k
-        if devrecon is not None:
-            assert lib.ks265_enc_set_default(b"devrecon", C.c_int(devrecon)) == 0
-        err = C.c_int(0)
-        h = C.c_void_p(lib.QY265EncoderOpen(cfg, C.byref(err)))
-        if devrecon is not None:
-            assert lib.ks265_enc_set_default(b"devrecon", C.c_int(0)) == 0      # read at open: the handle keeps it
-        assert h.value, hex(err.value & 0xFFFFFFFF)
-    finally:
-        for k, v in old.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
+    h = open_handle(lib, W, H, params=params, latency=latency, env=env, defaults=("devrecon",) if devrecon else ())
     if dump:
         assert lib.ks265_enc_set_recon_file(h, str(dump).encode()) == 0
     nal, nn, pic, outp, yuv, info = C.POINTER(Nal)(), C.c_int(0), Picture(), Picture(), YUV(), Picture()
@@ -147,14 +89,6 @@ def run(lib, n, params=(), latency=b"default", env=None, devrecon=None, dump=Non
     lib.QY265EncoderClose(h)
     lib.QY265SetLogPrintf(None)
     return bytes(bs), "".join(lines), calls, pend, lanes
-
-
-SESSIONS = {
-    "ippp": dict(n=40, params=(("iper", 32), ("bframes", 0))),
-    "default_gop": dict(n=40, params=(("iper", 32),)),
-    "two_lanes": dict(n=100, params=(("iper", 32), ("bframes", 0)), env={"KS265_GOP_LANES": "2"}),
-    "zerolatency": dict(n=20, params=(("iper", 32), ("bframes", 0)), latency=b"zerolatency"),
-}
 
 
 @pytest.mark.parametrize("name", list(SESSIONS))
@@ -242,15 +176,7 @@ def test_device_library_without_the_way_back(plain_lib):
         assert log.count("ks265enc: device reconstruction is unavailable: ") == 1 and "unavailable" not in log0
     # ks265_enc_get_device_recon on such a handle
     lib = plain_lib
-    cfg = (C.c_uint8 * LAY["sizeof_config"])()
-    assert lib.QY265ConfigDefaultPreset(cfg, b"medium", None, b"default") == 0
-    for k, v in (("wdt", W), ("hgt", H), ("log", 3)):
-        assert lib.QY265ConfigParse(cfg, k.encode(), str(v).encode()) == 0
-    assert lib.ks265_enc_set_default(b"devrecon", C.c_int(1)) == 0
-    err = C.c_int(0)
-    h = C.c_void_p(lib.QY265EncoderOpen(cfg, C.byref(err)))
-    assert lib.ks265_enc_set_default(b"devrecon", C.c_int(0)) == 0
-    assert h.value
+    h = open_handle(lib, W, H, params=(("log", 3),), defaults=("devrecon",))
     d, info = DevPicture(), Picture()
     assert lib.ks265_enc_get_device_recon(h, C.byref(d), C.byref(info)) == QY_NOTSUPPORTED
     assert lib.ks265_enc_device_recon_pending(h) == 0
@@ -260,20 +186,17 @@ def test_device_library_without_the_way_back(plain_lib):
 @pytest.mark.parametrize("case", ["plain_ippp", "plain_hier8", "no_split_hier8"])
 def test_switch_off_the_scheduler_threads_calls_are_the_pinned_ones(tmp_path, case):
     """the stand-in WITH the way back, the switch off: the scheduler thread's calls to the device library are those tests/golden/submit_order.json pins - not one call added"""
-    import test_submit_order_cpu as so
-    lib = _build(tmp_path, "hip_stub_recon.c", extra=("-DKS265_STUB_SSIM",))
-    c = so.CASES[case]
-    lines = so.scheduler_trace(lib, c, str(tmp_path / "calls.log"))
-    assert len(lines) == c["lines"] and so.digest(lines) == c["sha256"]
-    on = so.scheduler_trace(lib, dict(c, env=dict(c["env"], KS265_DEVRECON=1)), str(tmp_path / "calls_on.log"))
+    lib = build_host_lib("hip_stub_recon.c", ("KS265_STUB_SSIM",))
+    c = submit_order_cases()[case]
+    lines = scheduler_trace(lib, c, str(tmp_path / "calls.log"))
+    assert len(lines) == c["lines"] and digest(lines) == c["sha256"]
+    on = scheduler_trace(lib, dict(c, env=dict(c["env"], KS265_DEVRECON=1)), str(tmp_path / "calls_on.log"))
     assert len(on) > c["lines"] and sum(ln.startswith("ks265_store_i420 ") for ln in on) == c["n"], "and with it on: one pack per picture"
 
 
-def test_bookkeeping_unit_under_the_sanitizers(tmp_path):
+def test_bookkeeping_unit_under_the_sanitizers():
     """ks265_recon.h driven alone by a stand-alone program built with -fsanitize=address,undefined, as a child process"""
-    exe = str(tmp_path / "recon_pool")
-    subprocess.check_call(["gcc", "-O1", "-g", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan",
-                           "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "ks265codec_amd", "host"), "-o", exe, os.path.join(HERE, "recon_pool_main.c")])
+    exe = build_host_program("recon_pool_main.c")
     for seed in (1, 2, 3):
         r = subprocess.run([exe, str(seed), "60000"], capture_output=True, text=True, timeout=120)
         assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout[-400:] + r.stderr[-2000:]

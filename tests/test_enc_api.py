@@ -9,6 +9,8 @@ import subprocess
 
 import pytest
 
+from host_harness import LAY, cc
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SDK = "/root/reference/Android_demo/prebuilt/include"
@@ -16,14 +18,14 @@ SDK = "/root/reference/Android_demo/prebuilt/include"
 
 def _layout(tmp_path, hdr, inc):
     exe = tmp_path / "off"
-    subprocess.check_call(["gcc", f'-DHDR="{hdr}"', "-I", inc, os.path.join(HERE, "golden", "qy265_layout_probe.c"), "-o", str(exe)])
+    cc(f'-DHDR="{hdr}"', "-I", inc, os.path.join(HERE, "golden", "qy265_layout_probe.c"), "-o", exe)
     return json.loads(subprocess.check_output([str(exe)]))
 
 
 def test_struct_layout_is_the_sdks(tmp_path):
     """offsets of every field group of QY265EncConfig / QY265YUV / QY265Picture / QY265Nal equal those computed from the SDK's own header
     (tests/golden/qy265_layout.json, written in the builder container from /root/reference/.../qy265enc.h)"""
-    gold = json.load(open(os.path.join(HERE, "golden", "qy265_layout.json")))
+    gold = LAY
     assert _layout(tmp_path, "ks265_enc.h", os.path.join(ROOT, "include")) == gold
     if os.path.exists(os.path.join(SDK, "qy265enc.h")):
         assert _layout(tmp_path, "qy265enc.h", SDK) == gold
@@ -43,7 +45,7 @@ def _lib():
 
 def test_config_functions_and_error_codes():
     lib = _lib()
-    gold = json.load(open(os.path.join(HERE, "golden", "qy265_layout.json")))
+    gold = LAY
     buf = (C.c_uint8 * gold["sizeof_config"])()
 
     def i32(name): return C.c_int32.from_buffer(buf, gold[name]).value

@@ -11,13 +11,11 @@
   * values outside 0 .. 3 are QY265_PARAM_BAD_VALUE in QY265ConfigParse and QY_NOTSUPPORTED at open when written into the structure; a handle with either field set on a
     stand-in without the entries (tests/hip_stub_denoise.c) is QY_NOTSUPPORTED; QY265EncoderReconfig leaves the filter as opened;
   * with both fields 0 the call log of an encode is line for line that of the same encode on the stand-in WITHOUT the entries (what the parent saw), thread numbers aside;
-  * tests/enhance_main.c, the host and the stand-in under -fsanitize=address,undefined as a program of its own: 5 pictures at 202x134, both latencies, with and without
+  * tests/input_filter_main.c, the host and the stand-in under -fsanitize=address,undefined as a program of its own: 5 pictures at 202x134, both latencies, with and without
     the denoiser."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -27,67 +25,24 @@ import enhance_ref as er
 import picture_window_ref as pw
 import window_sps as ws
 from enhance_cases import CFGS, SIZES, contents
-from test_window_host_cpu import LAY, QY_NOTSUPPORTED, QY_OK, YUV, Nal, Picture, _build, clip, nals, open_handle, session, try_open
+from host_harness import (LAY, QY_NOTSUPPORTED, build_host_lib, build_host_program, drive, edgy_clip, en_calls, filter_program, host_picture, load_host_lib, logged, nals, open_handle,
+                          preceded, same_calls, session, try_open)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 W, H, N = 208, 136, 9
 BAD_VALUE = -2
 OFF_EDGE, OFF_COLOR = LAY["vpp_denoise"] + 4, LAY["vpp_denoise"] + 8     # int vpp_denoise, vpp_edge, vpp_color (include/ks265_enc.h)
 E22 = er.level_params(2, 2)
 
 
-class EnCall(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("w", "h", "edge_gain", "edge_core", "edge_limit", "edge_over", "color_gain", "has_src", "src_is_hist")]
-
-
-def _logged(tmp_path_factory, name, stub):
-    d = tmp_path_factory.mktemp(name)
-    so, log = _build(d, stub), str(d / "calls.log")
-    old = os.environ.get("KS265_STUB_CALL_LOG")
-    os.environ["KS265_STUB_CALL_LOG"] = log                              # read once, at the library's first logged call
-    try:
-        lib = C.CDLL(so)
-        lib.QY265EncoderOpen.restype = C.c_void_p
-        lib.ks265_stub_live.restype = C.c_long
-        lib.QY265EncoderClose(open_handle(lib, 128, 72))                # (the first logged call)
-    finally:
-        os.environ.pop("KS265_STUB_CALL_LOG", None)
-        if old is not None:
-            os.environ["KS265_STUB_CALL_LOG"] = old
-    lib.call_log_path = log
-    return lib
-
-
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    return _logged(tmp_path_factory, "stuben", "hip_stub_enhance.c")
+    return load_host_lib(build_host_lib("hip_stub_enhance.c"), call_log=str(tmp_path_factory.mktemp("stuben") / "calls.log"))
 
 
 @pytest.fixture(scope="module")
 def without(tmp_path_factory):
     """the stand-in without the two entries: the device library of the parent"""
-    return _logged(tmp_path_factory, "stubnoen", "hip_stub_denoise.c")
-
-
-def en_calls(lib):
-    buf = (EnCall * 4096)()
-    n = lib.ks265_stub_enhance_calls(buf, 4096)
-    return [(c.w, c.h, (c.edge_gain, c.edge_core, c.edge_limit, c.edge_over, c.color_gain), c.has_src, c.src_is_hist) for c in buf[:n]]
-
-
-def logged(lib, fn):
-    """(fn's result, the call log's lines it added: `thread name context frame event arg`)"""
-    before = sum(1 for _ in open(lib.call_log_path))
-    out = fn()
-    return out, [ln for ln in open(lib.call_log_path).read().split("\n")[before:] if ln]
-
-
-def same_calls(log):
-    """the lines without their thread numbers, sorted; contexts, frames and events - numbered by the stand-in from its first call on - counted from the section's first"""
-    rows = [ln.split(" ")[1:] for ln in log]
-    base = {k: min((int(r[i][1:]) for r in rows if r[i] != "-"), default=0) for i, k in ((1, "c"), (2, "f"), (3, "e"))}
-    return sorted(" ".join([r[0]] + [x if x == "-" else "%s%d" % (x[0], int(x[1:]) - base[x[0]]) for x in r[1:4]] + r[4:]) for r in rows)
+    return load_host_lib(build_host_lib("hip_stub_denoise.c"), call_log=str(tmp_path_factory.mktemp("stubnoen") / "calls.log"))
 
 
 def around_enhance(log):
@@ -98,18 +53,6 @@ def around_enhance(log):
         if f[1] == "ks265_input_enhance":
             mine = lambda rng: [log[k].split(" ") for k in rng if log[k].split(" ")[0] == f[0]]
             out.append((f, mine(range(i))[-2:], mine(range(i + 1, len(log)))[0]))
-    return out
-
-
-def edgy_clip(w, h, n, seed):
-    """test_window_host_cpu's moving clip with a hard-edged box moving over it and saturated chroma corners"""
-    out = []
-    for t, p in enumerate(clip(w, h, n, seed)):
-        y, u, v = [q.copy() for q in pw.planes(p, w, h)]
-        y[20 + t:60 + t, 30 + 3 * t:90 + 3 * t] = 200
-        y[70:74, :] = 30
-        u[:8, :8], v[:8, -8:], u[-8:, -8:], v[-8:, :8] = 0, 255, 255, 3
-        out.append(pw.pack([y, u, v]))
     return out
 
 
@@ -244,9 +187,9 @@ def test_two_lanes_give_the_one_lane_bytes(lib):
 
 def test_open_and_configuration(lib, without):
     for params in ((("edge", 1),), (("color", 3),), (("edge", 2), ("color", 2)), (("denoise", 2), ("edge", 1))):
-        hd, err = try_open(without, W, H, params=params)
+        hd, err = try_open(without, W, H, lanes=1, params=params)
         assert not hd.value and err == QY_NOTSUPPORTED, params
-    hd, err = try_open(without, W, H, params=(("denoise", 2),))
+    hd, err = try_open(without, W, H, lanes=1, params=(("denoise", 2),))
     assert hd.value
     without.QY265EncoderClose(hd)
     cfg = (C.c_uint8 * LAY["sizeof_config"])()
@@ -269,36 +212,27 @@ def test_open_and_configuration(lib, without):
 
 def test_open_names_the_resolved_parameters(lib, without, capfd):
     capfd.readouterr()
-    lib.QY265EncoderClose(open_handle(lib, W, H, params=(("log", 0), ("edge", 3), ("color", 1))))
+    lib.QY265EncoderClose(open_handle(lib, W, H, lanes=1, params=(("log", 0), ("edge", 3), ("color", 1))))
     out = capfd.readouterr().out
     assert out.count("enhancement on the way in") == 1 and "edge level 3 (gain 24/16, core 3, limit 24, over 8), colour level 1 (gain 8)" in out
-    lib.QY265EncoderClose(open_handle(lib, W, H, params=(("log", 0),)))
+    lib.QY265EncoderClose(open_handle(lib, W, H, lanes=1, params=(("log", 0),)))
     assert "enhancement" not in capfd.readouterr().out, "off: no log line"
-    hd, err = try_open(without, W, H, params=(("log", 0), ("color", 2)))
+    hd, err = try_open(without, W, H, lanes=1, params=(("log", 0), ("color", 2)))
     assert not hd.value and capfd.readouterr().out.count("has no ks265_input_enhance") == 1
 
 
 def test_reconfig_leaves_the_filter_as_opened(lib):
     src = source()[:4]
-    hd = open_handle(lib, W, H, latency=b"zerolatency", params=(("edge", 2), ("color", 2)))
+    hd = open_handle(lib, W, H, lanes=1, latency=b"zerolatency", params=(("edge", 2), ("color", 2)))
     cfg = (C.c_uint8 * LAY["sizeof_config"])()
     assert lib.QY265ConfigDefaultPreset(cfg, b"medium", None, b"zerolatency") == 0
     for k, v in (("wdt", W), ("hgt", H), ("fr", 50), ("rc", 0), ("qp", 34), ("edge", 0), ("color", 3)):
         assert lib.QY265ConfigParse(cfg, k.encode(), str(v).encode()) == 0
-    nal, nn, pic, outp, yuv = C.POINTER(Nal)(), C.c_int(0), Picture(), Picture(), YUV()
-    yuv.iWidth, yuv.iHeight = W, H
-    yuv.iStride[0], yuv.iStride[1], yuv.iStride[2] = W, W // 2, W // 2
-    pic.yuv = C.pointer(yuv)
+    lib.QY265EncoderReconfig.restype = None
     lib.ks265_stub_enhance_reset()
-    for t, p in enumerate(src):
-        if t == 2:
-            lib.QY265EncoderReconfig.restype = None
-            lib.QY265EncoderReconfig(hd, cfg)
-        for k, off in enumerate((0, W * H, W * H * 5 // 4)):
-            yuv.pData[k] = C.cast(p.ctypes.data + off, C.POINTER(C.c_ubyte))
-        pic.pts = t
-        assert lib.QY265EncoderEncodeFrame(hd, C.byref(nal), C.byref(nn), C.byref(pic), C.byref(outp), 0) == QY_OK
-    lib.QY265EncoderClose(hd)
+    puts = [host_picture(lib, hd, p, W, H, t) for t, p in enumerate(src)]
+    puts[2] = preceded(lambda: lib.QY265EncoderReconfig(hd, cfg), puts[2])
+    drive(lib, hd, puts)
     assert en_calls(lib) == [(W, H, E22, 1, 0)] * 4
 
 
@@ -316,25 +250,17 @@ def test_off_is_the_parent_s_call_log(lib, without):
 
 
 @pytest.fixture(scope="module")
-def sanitized(tmp_path_factory):
-    """tests/enhance_main.c + the host + the stand-in, built once with -fsanitize=address,undefined"""
-    from oracle_lib import build_oracle
-    build_oracle()
-    host = os.path.join(ROOT, "ks265codec_amd", "host")
-    exe = str(tmp_path_factory.mktemp("ensan") / "enhance_main")
-    subprocess.check_call(["gcc", "-O1", "-g", "-std=gnu11", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "include"),
-                           "-o", exe, os.path.join(HERE, "enhance_main.c"), os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"),
-                           os.path.join(HERE, "hip_stub_enhance.c"), "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
-    return exe
+def sanitized():
+    """tests/input_filter_main.c + the host + the stand-in, built once with -fsanitize=address,undefined"""
+    return build_host_program("input_filter_main.c", stub="hip_stub_enhance.c")
 
 
 @pytest.mark.parametrize("denoise", [0, 1], ids=["alone", "behind_the_denoiser"])
 @pytest.mark.parametrize("latency", ["default", "zerolatency"])
 def test_host_and_stand_in_under_the_sanitizers(sanitized, tmp_path, latency, denoise):
     out = str(tmp_path / "out.265")
-    r = subprocess.run([sanitized, "202", "134", "5", out, latency] + (["denoise"] if denoise else []), capture_output=True, text=True,
-                       env={**os.environ, "KS265_GOP_LANES": "1", "ASAN_OPTIONS": "detect_leaks=1"})
-    assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
-    assert "enhance calls 5" in r.stdout
+    recs = filter_program(sanitized, 202, 134, 5, out, latency, "edge=2", "color=3", *(["denoise=2"] if denoise else []))
+    assert recs["enhance"] == [dict(w=208, h=136, edge_gain=16, edge_core=2, edge_limit=16, edge_over=4, color_gain=32, has_src=1, src_is_hist=denoise)] * 5
+    assert len(recs["denoise"]) == 5 * denoise and not recs["hdr"]
     sps = ws.stream_sps(open(out, "rb").read())
     assert ws.output_size(sps) == (202, 134) and (sps["width"], sps["height"]) == (208, 136)

@@ -12,26 +12,14 @@ import sys
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+from host_harness import HERE, ROOT, build_host_lib, build_host_program
+
 GOLDEN = os.path.join(HERE, "golden", "gop_plan.json")
 DOC = json.load(open(GOLDEN)) if os.path.exists(GOLDEN) else {"cases": {}}
 CASES = DOC["cases"]
 FIELDS = ("poc", "slice_type", "nal_type", "l0", "l1", "rps", "qp")
 BASE_QP = 34                                                  # tests/host_driver.py: -qp 34
 KEYREQ_AFTER = (17, 18, 40)                                   # tests/host_driver.py, KS_TEST_KEYREQ: the picture behind each of these is asked to be a key picture
-
-
-def build_stub(d, host: str | None = None) -> str:
-    """the host (of this tree, or the sources in `host`) + the stand-in of the device library"""
-    from oracle_lib import build_oracle
-    build_oracle()
-    so = os.path.join(str(d), "libks265enc_stub.so")
-    host = host or os.path.join(ROOT, "ks265codec_amd", "host")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-fPIC", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"), "-shared", "-o", so,
-                           os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"), os.path.join(HERE, "hip_stub.c"),
-                           "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
-    return so
 
 
 def host_records(so: str, case: dict, out: str) -> tuple[list[list], int]:
@@ -164,17 +152,14 @@ def first_difference(got: list[list], want: list[list], skip_qp: bool = False) -
 
 
 @pytest.fixture(scope="module")
-def stub_lib(tmp_path_factory):
-    return build_stub(tmp_path_factory.mktemp("gopplan"))
+def stub_lib():
+    return build_host_lib("hip_stub.c")
 
 
 @pytest.fixture(scope="module")
-def planner(tmp_path_factory):
+def planner():
     """tests/gop_plan_main.c: the planner's header and nothing else of the host (the sanitizers' runtimes inside the program)"""
-    exe = str(tmp_path_factory.mktemp("gopplanmain") / "gop_plan_main")
-    subprocess.check_call(["gcc", "-O1", "-std=gnu11", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-fno-omit-frame-pointer", "-g",
-                           "-I", os.path.join(ROOT, "ks265codec_amd", "host"), "-o", exe, os.path.join(HERE, "gop_plan_main.c")])
-    return exe
+    return build_host_program("gop_plan_main.c")
 
 
 def test_the_fixture_covers_the_planner():

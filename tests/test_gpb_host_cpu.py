@@ -13,42 +13,20 @@ import sys
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+from host_harness import HERE, ROOT, build_host_cli, build_host_lib
+from host_harness import cli_encode as encode
+
 REF_DEC = os.path.join(ROOT, "oracle", "_ref", "appdecoder")
 GOLD = os.path.join(HERE, "golden", "gpb_off_stream_md5.json")
 W, H = 200, 136                                             # no multiple of the CTU in either direction, more than one CTU row and column
 
 
-def build_stub_cli(d) -> tuple[str, str]:
-    """the CLI and the library of the host, both on the stand-in"""
-    from oracle_lib import build_oracle
-    build_oracle()
-    host = os.path.join(ROOT, "ks265codec_amd", "host")
-    src = [os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"), os.path.join(HERE, "hip_stub.c")]
-    tail = ["-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"]
-    exe, so = os.path.join(str(d), "ks265enc_stub"), os.path.join(str(d), "libks265enc_stub.so")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"), "-o", exe, os.path.join(host, "ks265_cli.c"), *src, *tail])
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-fPIC", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"), "-shared", "-o", so, *src, *tail])
-    return exe, so
-
-
 @pytest.fixture(scope="module")
 def stub(tmp_path_factory):
+    """the CLI and the library of the host, both on the stand-in, and a clip"""
     d = tmp_path_factory.mktemp("stubgpb")
-    exe, so = build_stub_cli(d)
     np.random.default_rng(5).integers(0, 256, 70 * W * H * 3 // 2, dtype=np.uint8).tofile(d / "in.yuv")
-    return {"exe": exe, "so": so, "yuv": str(d / "in.yuv")}
-
-
-def encode(stub, out, opts, env=None, size=(W, H)) -> bytes:
-    """one run of the CLI at constant QP; KS265_GPB reaches it only through `env`"""
-    e = {k: v for k, v in os.environ.items() if k not in ("KS265_GPB", "KS265_GOP_LANES")}
-    e.update({k: str(v) for k, v in (env or {}).items()})
-    r = subprocess.run([stub["exe"], "-i", stub["yuv"], "-wdt", str(size[0]), "-hgt", str(size[1]), "-fr", "50", "-preset", "slow", "-rc", "0", "-qp", "30", "-threads", "3",
-                        "-b", str(out), *opts], capture_output=True, text=True, timeout=120, env=e)
-    assert r.returncode == 0 and "H265 encoder passed!!!" in r.stdout, r.stdout[-800:] + r.stderr[-800:]
-    return open(out, "rb").read()
+    return {"exe": build_host_cli(), "so": build_host_lib("hip_stub.c"), "yuv": str(d / "in.yuv")}
 
 
 def decodes(tmp_path, name, n, size=(W, H)):

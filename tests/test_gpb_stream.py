@@ -85,17 +85,17 @@ def test_host_mirror_follows_the_switch(tmp_path, monkeypatch):
     import rd_eval as R
     from ks265codec_amd.synth import ENCODER_TOOLS, make_clip
     from slice_headers import pictures
-    import test_gpb_host_cpu as T
+    from host_harness import build_host_cli, cli_encode
     W, H, N = 64, 64, 17
     clip = make_clip(W, H, N, seed=3, abc=(17, 23, 9), pan=(1, 1))
     clip.tofile(tmp_path / "in.yuv")
-    exe, _ = T.build_stub_cli(tmp_path)
+    exe = build_host_cli()
     monkeypatch.setenv("RD_G", "4")
     for g in ("1", "0"):
         monkeypatch.setenv("KS265_GPB", g)
         seq, _ = R.adaptive_seq(clip, W, H, 30, decide=False)
         bs, _, _ = R.encode_ours(clip, W, H, 30, "hier", dict(ENCODER_TOOLS), layer_qp=[0, 1, 2], lam_scale=-1.0, seq=seq)
-        host = T.encode({"exe": exe, "yuv": str(tmp_path / "in.yuv")}, tmp_path / "h.265", ["-bframes", "3", "-ref0", "3", "-iper", "128", "-gpb", g], size=(W, H))
+        host = cli_encode({"exe": exe, "yuv": str(tmp_path / "in.yuv")}, tmp_path / "h.265", ["-bframes", "3", "-ref0", "3", "-iper", "128", "-gpb", g], size=(W, H))
         keys = ("poc", "nal_type", "slice_type", "rps", "l0", "l1", "qp", "list_mod", "sao")
         assert [[p[k] for k in keys] for p in pictures(bs)] == [[p[k] for k in keys] for p in pictures(host)], g
         nh = [i for i in range(len(host) - 3) if host[i:i + 3] == b"\x00\x00\x01"][3]          # the first slice's start code: VPS, SPS and PPS lie in front of it

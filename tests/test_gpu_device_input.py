@@ -18,19 +18,13 @@ import torch  # noqa: E402  (torch's HIP runtime first, as in the other GPU modu
 torch.cuda.is_available()
 
 import yuv_convert_ref as ref  # noqa: E402
+from host_harness import YUV  # noqa: E402  (YUV, HostPicture: the GPU modules that share this one's sessions import them from here too)
+from host_harness import Picture as HostPicture  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 REF_DEC = os.path.join(ROOT, "oracle", "_ref", "appdecoder")
 QY_OK, QY_POINTER, QY_NOTSUPPORTED = 0, -0x7FFFFFFD, -0x7FFFFFFC
-
-
-class YUV(C.Structure):
-    _fields_ = [("iWidth", C.c_int), ("iHeight", C.c_int), ("pData", C.POINTER(C.c_ubyte) * 3), ("iStride", C.c_int * 3)]
-
-
-class HostPicture(C.Structure):
-    _fields_ = [("iSliceType", C.c_int), ("poc", C.c_int), ("pts", C.c_longlong), ("dts", C.c_longlong), ("yuv", C.POINTER(YUV))]
 
 
 class InDesc(C.Structure):

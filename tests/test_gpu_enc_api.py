@@ -15,6 +15,7 @@ import sys
 import numpy as np
 import pytest
 
+from host_harness import LAY, YUV, Nal, Picture
 from stream_cases import CASES
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +26,6 @@ torch.cuda.is_available()
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 GOLD = json.load(open(os.path.join(HERE, "golden", "stream_md5.json")))
-LAY = json.load(open(os.path.join(HERE, "golden", "qy265_layout.json")))
 OUT = os.path.join(ROOT, "gpurun_out")
 
 
@@ -220,18 +220,6 @@ def test_anchor_lane_writes_the_same_stream(bframes, iper, n):
         assert r.returncode == 0, r.stdout[-800:] + r.stderr[-800:]
         md5[tag] = json.loads(r.stdout.strip().splitlines()[-1])["md5"]
     assert md5["lane"] == md5["main"], md5
-
-
-class YUV(C.Structure):
-    _fields_ = [("iWidth", C.c_int), ("iHeight", C.c_int), ("pData", C.POINTER(C.c_ubyte) * 3), ("iStride", C.c_int * 3)]
-
-
-class Picture(C.Structure):
-    _fields_ = [("iSliceType", C.c_int), ("poc", C.c_int), ("pts", C.c_longlong), ("dts", C.c_longlong), ("yuv", C.POINTER(YUV))]
-
-
-class Nal(C.Structure):
-    _fields_ = [("naltype", C.c_int), ("tid", C.c_int), ("iSize", C.c_int), ("pts", C.c_longlong), ("pPayload", C.POINTER(C.c_ubyte))]
 
 
 @pytest.mark.parametrize("bframes,tag", [(-1, "hier8"), (3, "b3"), (0, "ippp_ref3")])

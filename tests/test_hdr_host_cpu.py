@@ -11,13 +11,11 @@
     QY265EncoderReconfig leaves the filter as opened; one log line at open names the integers and the work buffer's bytes;
   * `vpp_hdr = 0` with junk in the other four fields: the call log is that of the same encode on the stand-in WITHOUT the entries, lines sorted, thread numbers aside;
   * the host's derived integers, read back through ks265_stub_hdr_calls, equal hdr_ref.params over a grid;
-  * tests/hdr_main.c, the host and the stand-in under -fsanitize=address,undefined as a program of its own: 5 pictures at 202x134, both latencies, alone and between the
+  * tests/input_filter_main.c, the host and the stand-in under -fsanitize=address,undefined as a program of its own: 5 pictures at 202x134, both latencies, alone and between the
     denoiser and the enhancement."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -28,11 +26,9 @@ import hdr_ref as hr
 import picture_window_ref as pw
 import window_sps as ws
 from hdr_cases import CFGS, SIZES, contents
-from test_enhance_host_cpu import _logged, edgy_clip, en_calls, logged, same_calls
-from test_window_host_cpu import LAY, QY_NOTSUPPORTED, QY_OK, YUV, Nal, Picture, nals, open_handle, session, try_open
+from host_harness import (LAY, QY_NOTSUPPORTED, build_host_lib, build_host_program, drive, edgy_clip, en_calls, filter_program, host_picture, load_host_lib, logged, nals, open_handle,
+                          preceded, same_calls, session, try_open)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 W, H, N = 208, 136, 9
 BAD_VALUE = -2
 OFF_HDR, OFF_STRENGTH = LAY["vpp_denoise"] + 12, LAY["vpp_hdr_strength"]     # int vpp_denoise, vpp_edge, vpp_color, vpp_hdr; double vpp_hdr_strength; int vpp_hdr_iter;
@@ -47,7 +43,7 @@ class HdrCall(C.Structure):
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    lb = _logged(tmp_path_factory, "stubhdr", "hip_stub_hdr.c")
+    lb = load_host_lib(build_host_lib("hip_stub_hdr.c"), call_log=str(tmp_path_factory.mktemp("stubhdr") / "calls.log"))
     lb.ks265_input_hdr_work_bytes.restype = C.c_size_t
     return lb
 
@@ -55,7 +51,7 @@ def lib(tmp_path_factory):
 @pytest.fixture(scope="module")
 def without(tmp_path_factory):
     """the stand-in without the three entries: the device library of the parent"""
-    return _logged(tmp_path_factory, "stubnohdr", "hip_stub_enhance.c")
+    return load_host_lib(build_host_lib("hip_stub_enhance.c"), call_log=str(tmp_path_factory.mktemp("stubnohdr") / "calls.log"))
 
 
 def hdr_calls(lib):
@@ -225,9 +221,9 @@ def _fresh_cfg(lib):
 
 def test_open_and_configuration(lib, without):
     for params in (ON, ON + (("hdr-iter", 2),), (("denoise", 2), ("hdr", 1)), (("hdr", 1), ("edge", 1))):
-        hd, err = try_open(without, W, H, params=params)
+        hd, err = try_open(without, W, H, lanes=1, params=params)
         assert not hd.value and err == QY_NOTSUPPORTED, params
-    hd, err = try_open(without, W, H, params=(("edge", 2), ("hdr-strength", 3)))
+    hd, err = try_open(without, W, H, lanes=1, params=(("edge", 2), ("hdr-strength", 3)))
     assert hd.value, "vpp_hdr 0: the other fields are not looked at"
     without.QY265EncoderClose(hd)
     cfg = _fresh_cfg(lib)
@@ -251,37 +247,28 @@ def test_open_and_configuration(lib, without):
 
 def test_open_names_the_resolved_parameters(lib, without, capfd):
     capfd.readouterr()
-    lib.QY265EncoderClose(open_handle(lib, W, H, params=(("log", 0), ("hdr", 1), ("hdr-iter", 2), ("hdr-sigma-s", 100), ("hdr-sigma-r", 100), ("hdr-strength", 5))))
+    lib.QY265EncoderClose(open_handle(lib, W, H, lanes=1, params=(("log", 0), ("hdr", 1), ("hdr-iter", 2), ("hdr-sigma-s", 100), ("hdr-sigma-r", 100), ("hdr-strength", 5))))
     out = capfd.readouterr().out
     assert out.count("local contrast on the way in") == 1
     assert "gain 80/16, 2 iterations, slope 6, radii 2479 / 1239 / 0 (1/16 sample), work buffer %d bytes" % hr.work_bytes(W, H) in out
-    lib.QY265EncoderClose(open_handle(lib, W, H, params=(("log", 0),)))
+    lib.QY265EncoderClose(open_handle(lib, W, H, lanes=1, params=(("log", 0),)))
     assert "local contrast" not in capfd.readouterr().out, "off: no log line"
-    hd, err = try_open(without, W, H, params=(("log", 0), ("hdr", 1)))
+    hd, err = try_open(without, W, H, lanes=1, params=(("log", 0), ("hdr", 1)))
     assert not hd.value and capfd.readouterr().out.count("has no ks265_input_hdr") == 1
 
 
 def test_reconfig_leaves_the_filter_as_opened(lib):
     src = source()[:4]
-    hd = open_handle(lib, W, H, latency=b"zerolatency", params=ON)
+    hd = open_handle(lib, W, H, lanes=1, latency=b"zerolatency", params=ON)
     cfg = (C.c_uint8 * LAY["sizeof_config"])()
     assert lib.QY265ConfigDefaultPreset(cfg, b"medium", None, b"zerolatency") == 0
     for k, v in (("wdt", W), ("hgt", H), ("fr", 50), ("rc", 0), ("qp", 34), ("hdr", 0), ("hdr-strength", 4)):
         assert lib.QY265ConfigParse(cfg, k.encode(), str(v).encode()) == 0
-    nal, nn, pic, outp, yuv = C.POINTER(Nal)(), C.c_int(0), Picture(), Picture(), YUV()
-    yuv.iWidth, yuv.iHeight = W, H
-    yuv.iStride[0], yuv.iStride[1], yuv.iStride[2] = W, W // 2, W // 2
-    pic.yuv = C.pointer(yuv)
+    lib.QY265EncoderReconfig.restype = None
     lib.ks265_stub_hdr_reset()
-    for t, p in enumerate(src):
-        if t == 2:
-            lib.QY265EncoderReconfig.restype = None
-            lib.QY265EncoderReconfig(hd, cfg)
-        for k, off in enumerate((0, W * H, W * H * 5 // 4)):
-            yuv.pData[k] = C.cast(p.ctypes.data + off, C.POINTER(C.c_ubyte))
-        pic.pts = t
-        assert lib.QY265EncoderEncodeFrame(hd, C.byref(nal), C.byref(nn), C.byref(pic), C.byref(outp), 0) == QY_OK
-    lib.QY265EncoderClose(hd)
+    puts = [host_picture(lib, hd, p, W, H, t) for t, p in enumerate(src)]
+    puts[2] = preceded(lambda: lib.QY265EncoderReconfig(hd, cfg), puts[2])
+    drive(lib, hd, puts)
     assert hdr_calls(lib) == [(W, H, DEF, 0, 1)] * 4
 
 
@@ -315,25 +302,21 @@ def test_the_host_derives_the_reference_s_integers(lib):
 
 
 @pytest.fixture(scope="module")
-def sanitized(tmp_path_factory):
-    """tests/hdr_main.c + the host + the stand-in, built once with -fsanitize=address,undefined"""
-    from oracle_lib import build_oracle
-    build_oracle()
-    host = os.path.join(ROOT, "ks265codec_amd", "host")
-    exe = str(tmp_path_factory.mktemp("hdrsan") / "hdr_main")
-    subprocess.check_call(["gcc", "-O1", "-g", "-std=gnu11", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "include"),
-                           "-o", exe, os.path.join(HERE, "hdr_main.c"), os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"),
-                           os.path.join(HERE, "hip_stub_hdr.c"), "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
-    return exe
+def sanitized():
+    """tests/input_filter_main.c + the host + the stand-in, built once with -fsanitize=address,undefined"""
+    return build_host_program("input_filter_main.c", stub="hip_stub_hdr.c")
 
 
 @pytest.mark.parametrize("around", [0, 1], ids=["alone", "between_denoiser_and_enhancement"])
 @pytest.mark.parametrize("latency", ["default", "zerolatency"])
 def test_host_and_stand_in_under_the_sanitizers(sanitized, tmp_path, latency, around):
+    """strength 2, 2 iterations, sigma_s 30, sigma_r at its default: the derived integers (32, 2, 13, 744 / 372), always the same work buffer of exactly
+    ks265_input_hdr_work_bytes"""
     out = str(tmp_path / "out.265")
-    r = subprocess.run([sanitized, "202", "134", "5", out, latency] + (["all"] if around else []), capture_output=True, text=True,
-                       env={**os.environ, "KS265_GOP_LANES": "1", "ASAN_OPTIONS": "detect_leaks=1"})
-    assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
-    assert "hdr calls 5" in r.stdout
+    recs = filter_program(sanitized, 202, 134, 5, out, latency, "hdr=1", "hdr-strength=2", "hdr-iter=2", "hdr-sigma-s=30", *(["denoise=2", "edge=2"] if around else []))
+    assert len(recs["hdr"]) == 5
+    for c in recs["hdr"]:
+        assert (c["w"], c["h"], c["gain"], c["iters"], c["slope"], c["radius0"], c["radius1"], c["work_no"]) == (208, 136, 32, 2, 13, 744, 372, 0) and c["work_ok"], c
+    assert len(recs["denoise"]) == len(recs["enhance"]) == 5 * around
     sps = ws.stream_sps(open(out, "rb").read())
     assert ws.output_size(sps) == (202, 134) and (sps["width"], sps["height"]) == (208, 136)

@@ -11,22 +11,14 @@ import sys
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+from host_harness import HERE, ROOT, build_host_cli, build_host_lib
+
 REF_DEC = os.path.join(ROOT, "oracle", "_ref", "appdecoder")
 
 
 @pytest.fixture(scope="module")
-def stub_lib(tmp_path_factory):
-    from oracle_lib import build_oracle
-    build_oracle()
-    d = tmp_path_factory.mktemp("stubenc")
-    so = str(d / "libks265enc_stub.so")
-    host = os.path.join(ROOT, "ks265codec_amd", "host")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-fPIC", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"), "-shared", "-o", so,
-                           os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"), os.path.join(HERE, "hip_stub.c"),
-                           "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
-    return so
+def stub_lib():
+    return build_host_lib("hip_stub.c")
 
 
 def run(stub_lib, n, iper, bframes, W=128, H=72, out=None, timeout=120, **env):
@@ -327,11 +319,7 @@ def test_cli_prints_the_reference_per_picture_and_md5_lines(stub_lib, tmp_path):
     `POC n MD5 y,u,v` in display order, the two `Total Frames:` lines and `bitrate, psnr:` (the line encoderwrapper.c:249-277 parses)"""
     import re
     import numpy as np
-    host = os.path.join(ROOT, "ks265codec_amd", "host")
-    exe = str(tmp_path / "ks265enc_stub")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"), "-o", exe, os.path.join(host, "ks265_cli.c"),
-                           os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"), os.path.join(HERE, "hip_stub.c"),
-                           "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
+    exe = build_host_cli()
     W, H, N = 128, 72, 12
     np.random.default_rng(5).integers(0, 256, N * W * H * 3 // 2, dtype=np.uint8).tofile(tmp_path / "in.yuv")
     (tmp_path / "enc.cfg").write_text("# options of the run\nqp 30\n-iper = 64\nbframes : 3\n")
@@ -360,11 +348,7 @@ def test_qp_ladders_of_the_host(stub_lib, tmp_path):
     import re
     import numpy as np
     from stream_cases import HOST_IPPP_CASCADE
-    host = os.path.join(ROOT, "ks265codec_amd", "host")
-    exe = str(tmp_path / "ks265enc_stub")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"), "-o", exe, os.path.join(host, "ks265_cli.c"),
-                           os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"), os.path.join(HERE, "hip_stub.c"),
-                           "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
+    exe = build_host_cli()
     W, H, N = 128, 72, 21
     np.random.default_rng(5).integers(0, 256, N * W * H * 3 // 2, dtype=np.uint8).tofile(tmp_path / "in.yuv")
 
@@ -400,11 +384,7 @@ def test_gop_structure_and_qp_ladders_are_the_reference_s(tmp_path):
     import re
     import numpy as np
     ref = json.load(open(os.path.join(HERE, "golden", "ref_gop_structure.json")))
-    host = os.path.join(ROOT, "ks265codec_amd", "host")
-    exe = str(tmp_path / "ks265enc_stub")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-I", os.path.join(ROOT, "include"), "-o", exe, os.path.join(host, "ks265_cli.c"),
-                           os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"), os.path.join(HERE, "hip_stub.c"),
-                           "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
+    exe = build_host_cli()
     W, H, N = 128, 72, ref["clip"]["pictures"]
     np.random.default_rng(5).integers(0, 256, N * W * H * 3 // 2, dtype=np.uint8).tofile(tmp_path / "in.yuv")
 
@@ -595,11 +575,7 @@ def test_crf_runs_the_cutree_pass_of_the_lookahead(tmp_path, opts, n, W, H):
     import numpy as np
     from ks265codec_amd.synth import make_clip
     from cutree_mirror import CuTree, read_qpmap_dump
-    host = os.path.join(ROOT, "ks265codec_amd", "host")
-    exe = str(tmp_path / "ks265enc_stub")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"), "-o", exe, os.path.join(host, "ks265_cli.c"),
-                           os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"), os.path.join(HERE, "hip_stub.c"),
-                           "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
+    exe = build_host_cli()
     clip = make_clip(W, H, n, seed=11, abc=(17, 23, 9), pan=(3, 2))
     clip.tofile(tmp_path / "in.yuv")
     dump = tmp_path / "maps.bin"

@@ -15,34 +15,17 @@ import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+from host_harness import HERE, ROOT, build_host_program, digest  # noqa: F401  (ROOT: tests/golden/input_order_gen.py's)
+from host_harness import lane_put_env as case_env
+
 GOLDEN = os.path.join(HERE, "golden", "input_order.json")
 DOC = json.load(open(GOLDEN))
 CASES = DOC["cases"]
 
 
-def build_program(d, host: str | None = None, sanitize: bool = False) -> str:
+def build_program(host: str | None = None) -> str:
     """tests/lane_put_main.c with the host (of `host`, else the tree's) and the stand-in that has every way in"""
-    from oracle_lib import build_oracle
-    build_oracle()
-    exe = os.path.join(str(d), "lane_put_asan" if sanitize else "lane_put")
-    host = host or os.path.join(ROOT, "ks265codec_amd", "host")
-    # (the sanitizers' runtimes inside the program: it starts whatever else the environment preloads into every process)
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-fno-omit-frame-pointer", "-g"] if sanitize else []
-    subprocess.check_call(["gcc", "-O1" if sanitize else "-O2", "-std=gnu11", "-Wall", "-Wextra", *san, "-I", os.path.join(ROOT, "include"), "-o", exe,
-                           os.path.join(HERE, "lane_put_main.c"), os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"), os.path.join(HERE, "hip_stub_window.c"),
-                           "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
-    return exe
-
-
-def case_env(case: dict, **more) -> dict:
-    """the case's variables; nothing else of KS265_* comes in from outside.  One lane and no lookahead unless the case says otherwise"""
-    env = {k: v for k, v in os.environ.items() if not k.startswith("KS265_")}
-    env.update({"KS265_GOP_LANES": "1", "KS265_NO_AUTO_LOOKAHEAD": "1"})
-    env.update({k: str(v) for k, v in case.get("env", {}).items()})
-    env.update(more)
-    return {k: v for k, v in env.items() if v != ""}
+    return build_host_program("lane_put_main.c", stub="hip_stub_window.c", sanitize=False, host_dir=host)
 
 
 def run_case(exe: str, case: dict, d) -> dict:
@@ -62,13 +45,9 @@ def run_case(exe: str, case: dict, d) -> dict:
     return {"lines": mine, "md5": hashlib.md5(open(out, "rb").read()).hexdigest(), "rc": rcs}
 
 
-def digest(lines: list[str]) -> str:
-    return hashlib.sha256("\n".join(lines).encode()).hexdigest()
-
-
 @pytest.fixture(scope="module")
-def program(tmp_path_factory):
-    return build_program(tmp_path_factory.mktemp("laneput"))
+def program():
+    return build_program()
 
 
 @pytest.mark.parametrize("name", sorted(CASES))

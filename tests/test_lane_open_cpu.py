@@ -6,32 +6,22 @@ tests/lane_open_main.c opens a lane and prints those lines, then the host's log 
 takes one of its designed fall-backs, and after the close nothing of the stand-in's is alive."""
 from __future__ import annotations
 
-import hashlib
 import json
 import os
 import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+from host_harness import HERE, build_host_program, digest
+
 GOLDEN = os.path.join(HERE, "golden", "lane_open.json")
 DOC = json.load(open(GOLDEN))
 CASES = DOC["cases"]
 
 
-def build_program(d, sanitize: bool = False, stub: str = "hip_stub_hash.c") -> str:
+def build_program(sanitize: bool = False) -> str:
     """tests/lane_open_main.c with the host and the stand-in (with its -ssim and `hash` entries, so that those switches allocate what they allocate on the device library)"""
-    from oracle_lib import build_oracle
-    build_oracle()
-    exe = os.path.join(str(d), "lane_open_asan" if sanitize else "lane_open")
-    host = os.path.join(ROOT, "ks265codec_amd", "host")
-    # (the sanitizers' runtimes inside the program: it starts whatever else the environment preloads into every process)
-    san = ["-fsanitize=address,undefined", "-static-libasan", "-static-libubsan", "-fno-omit-frame-pointer", "-g"] if sanitize else []
-    subprocess.check_call(["gcc", "-O1" if sanitize else "-O2", "-std=gnu11", "-Wall", "-Wextra", "-DKS265_STUB_SSIM", *san, "-I", os.path.join(ROOT, "include"), "-o", exe,
-                           os.path.join(HERE, "lane_open_main.c"), os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"), os.path.join(HERE, stub),
-                           "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
-    return exe
+    return build_host_program("lane_open_main.c", stub="hip_stub_hash.c", sanitize=sanitize, defines=("KS265_STUB_SSIM",))
 
 
 def case_env(case: dict) -> dict:
@@ -55,18 +45,14 @@ def open_trace(exe: str, case: dict) -> tuple[list[str], str]:
     return lines[:-1], lines[-1]
 
 
-def digest(lines: list[str]) -> str:
-    return hashlib.sha256("\n".join(lines).encode()).hexdigest()
+@pytest.fixture(scope="module")
+def program():
+    return build_program()
 
 
 @pytest.fixture(scope="module")
-def program(tmp_path_factory):
-    return build_program(tmp_path_factory.mktemp("laneopen"))
-
-
-@pytest.fixture(scope="module")
-def program_asan(tmp_path_factory):
-    return build_program(tmp_path_factory.mktemp("laneopenasan"), sanitize=True)
+def program_asan():
+    return build_program(sanitize=True)
 
 
 @pytest.mark.parametrize("name", sorted(CASES))

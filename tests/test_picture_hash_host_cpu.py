@@ -9,7 +9,6 @@ entries (tests/hip_stub_hash.c), 128x72.
 from __future__ import annotations
 
 import ctypes as C
-import json
 import os
 import subprocess
 
@@ -17,39 +16,29 @@ import numpy as np
 import pytest
 
 import picture_hash_ref as ph
+from host_harness import ROOT, Nal, Picture, build_host_cli, build_host_lib, load_host_lib, open_handle, packed_yuv
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 REF_DEC = os.path.join(ROOT, "oracle", "_ref", "appdecoder")
 W, H, N = 128, 72, 17
 FSZ = W * H * 3 // 2
 GOPS = {"ippp": ("-bframes", "0"), "pyramid": (), "gpb": ("-gpb", "1"), "zerolatency": ("-latency", "zerolatency")}
 
 
-def _build(d, stub):
-    so, exe = str(d / "libks265enc.so"), str(d / "ks265enc")
-    host, inc = os.path.join(ROOT, "ks265codec_amd", "host"), os.path.join(ROOT, "include")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-fPIC", "-Wall", "-Wextra", "-I", inc, "-shared", "-o", so,
-                           os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"), os.path.join(HERE, stub),
-                           "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-Wextra", "-I", inc, "-o", exe, os.path.join(host, "ks265_cli.c"), "-L", str(d), "-lks265enc",
-                           "-Wl,-rpath," + str(d), "-Wl,-rpath-link," + os.path.join(ROOT, "oracle"), "-lpthread"])
+def _cli(d, stub):
+    """a directory with the command line on the stand-in (as ks265enc) and a clip"""
+    os.symlink(build_host_cli(stub), d / "ks265enc")
     np.random.default_rng(11).integers(0, 256, (64, FSZ), dtype=np.uint8).tofile(str(d / "in.yuv"))
     return d
 
 
 @pytest.fixture(scope="module")
 def stub_cli(tmp_path_factory):
-    from oracle_lib import build_oracle
-    build_oracle()
-    return _build(tmp_path_factory.mktemp("stubhash"), "hip_stub_hash.c")
+    return _cli(tmp_path_factory.mktemp("stubhash"), "hip_stub_hash.c")
 
 
 @pytest.fixture(scope="module")
 def plain_cli(tmp_path_factory):
-    from oracle_lib import build_oracle
-    build_oracle()
-    return _build(tmp_path_factory.mktemp("stubnohash"), "hip_stub.c")
+    return _cli(tmp_path_factory.mktemp("stubnohash"), "hip_stub.c")
 
 
 _runs = {}
@@ -145,8 +134,8 @@ def test_other_values_are_rejected(stub_cli, value):
     assert rc == 2 and "bad value for -hash" in out and bs == b""
 
 
-def test_set_default_values(stub_cli):
-    lib = C.CDLL(str(stub_cli / "libks265enc.so"), mode=os.RTLD_NOW)
+def test_set_default_values():
+    lib = load_host_lib(build_host_lib("hip_stub_hash.c"), mode=os.RTLD_NOW)
     assert hasattr(lib, "ks265_picture_hash") and hasattr(lib, "ks265_write_picture_hash_sei")
     for v, rc in ((0, 0), (2, 0), (3, 0), (1, -2), (4, -2), (-1, -2), (0, 0)):                       # QY265_PARAM_BAD_VALUE = -2; MD5 (1) stays with -md5
         assert lib.ks265_enc_set_default(b"hash", C.c_int(v)) == rc, v
@@ -161,7 +150,7 @@ def test_environment_overrides_the_default(stub_cli):
 
 
 def test_device_library_without_the_entry(plain_cli):
-    lib = C.CDLL(str(plain_cli / "libks265enc.so"), mode=os.RTLD_NOW)
+    lib = load_host_lib(build_host_lib("hip_stub.c"), mode=os.RTLD_NOW)
     assert hasattr(lib, "ks265_enc_set_default") and not hasattr(lib, "ks265_picture_hash")
     for gop in ((), ("-bframes", "0")):                                  # (the default GOP runs two lanes: one line per handle all the same)
         out0, plain, _, _ = _run(plain_cli, "-rc", "0", *gop, "-hash", "0", n=64, env={"KS265_GOP_LANES": "2"} if not gop else None)
@@ -171,49 +160,23 @@ def test_device_library_without_the_entry(plain_cli):
 
 
 # ---------------------------------------------------------------- the API: one more QY265Nal per picture
-class _YUV(C.Structure):
-    _fields_ = [("iWidth", C.c_int), ("iHeight", C.c_int), ("pData", C.POINTER(C.c_ubyte) * 3), ("iStride", C.c_int * 3)]
-
-
-class _Picture(C.Structure):
-    _fields_ = [("iSliceType", C.c_int), ("poc", C.c_int), ("pts", C.c_longlong), ("dts", C.c_longlong), ("yuv", C.POINTER(_YUV))]
-
-
-class _Nal(C.Structure):
-    _fields_ = [("naltype", C.c_int), ("tid", C.c_int), ("iSize", C.c_int), ("pts", C.c_longlong), ("pPayload", C.POINTER(C.c_ubyte))]
-
-
 class _Stats(C.Structure):
     _fields_ = [("frames", C.c_long), ("bytes", C.c_longlong), ("rest", C.c_uint8 * 1024)]
 
 
 def test_api_hands_the_message_out_as_a_nal_of_its_own(stub_cli):
-    lay = json.load(open(os.path.join(HERE, "golden", "qy265_layout.json")))
-    lib = C.CDLL(str(stub_cli / "libks265enc.so"))
-    lib.QY265EncoderOpen.restype = C.c_void_p
+    lib = load_host_lib(build_host_lib("hip_stub_hash.c"))
     clip = np.fromfile(str(stub_cli / "in.yuv"), np.uint8).reshape(-1, FSZ)[:N].copy()
-    cfg = (C.c_uint8 * lay["sizeof_config"])()
-    assert lib.QY265ConfigDefaultPreset(cfg, b"medium", None, b"default") == 0
-    for k, v in (("wdt", W), ("hgt", H), ("rc", 0), ("qp", 34), ("threads", 3), ("log", 3)):
-        assert lib.QY265ConfigParse(cfg, k.encode(), str(v).encode()) == 0
-    assert lib.ks265_enc_set_default(b"hash", C.c_int(2)) == 0
-    err = C.c_int(0)
-    h = C.c_void_p(lib.QY265EncoderOpen(cfg, C.byref(err)))
-    assert lib.ks265_enc_set_default(b"hash", C.c_int(0)) == 0             # read at open: the handle keeps it
-    assert h.value, hex(err.value & 0xFFFFFFFF)
-    nal, nn, pic, outp, yuv = C.POINTER(_Nal)(), C.c_int(0), _Picture(), _Picture(), _YUV()
-    yuv.iWidth, yuv.iHeight = W, H
-    yuv.iStride[0], yuv.iStride[1], yuv.iStride[2] = W, W // 2, W // 2
-    pic.yuv = C.pointer(yuv)
+    h = open_handle(lib, W, H, params=(("threads", 3), ("log", 3)), defaults={"hash": 2})
+    nal, nn, pic, outp = C.POINTER(Nal)(), C.c_int(0), Picture(), Picture()
     got = []                                                             # (naltype, pts, bytes) in output order
 
     def take():
         got.extend((nal[i].naltype, nal[i].pts, C.string_at(nal[i].pPayload, nal[i].iSize)) for i in range(nn.value) if nal[i].iSize > 0)
 
     for t in range(N):
-        for k, off in enumerate((0, W * H, W * H * 5 // 4)):
-            yuv.pData[k] = C.cast(clip[t].ctypes.data + off, C.POINTER(C.c_ubyte))
-        pic.pts = 1000 + t
+        yuv = packed_yuv(clip[t], W, H)
+        pic.yuv, pic.pts = C.pointer(yuv), 1000 + t
         assert lib.QY265EncoderEncodeFrame(h, C.byref(nal), C.byref(nn), C.byref(pic), C.byref(outp), 0) == 0
         take()
     while lib.QY265EncoderDelayedFrames(h) > 0:

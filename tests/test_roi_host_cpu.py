@@ -3,7 +3,6 @@ tests/roi_reduce_main.c is a stand-alone program built with -fsanitize=address,u
 so a read past the map is a sanitizer report."""
 from __future__ import annotations
 
-import os
 import subprocess
 
 import numpy as np
@@ -12,16 +11,12 @@ import pytest
 import roi_cases
 import roi_map_ref as R
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+from host_harness import build_host_program
 
 
 @pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("roi") / "roi_reduce_main")
-    subprocess.check_call(["gcc", "-O1", "-g", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan",
-                           "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "ks265codec_amd", "host"), "-o", out, os.path.join(HERE, "roi_reduce_main.c")])
-    return out
+def exe():
+    return build_host_program("roi_reduce_main.c")
 
 
 def _reduce(exe, tmp_path, m, lb, w, h, pad_elems, offset):

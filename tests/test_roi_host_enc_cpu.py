@@ -9,7 +9,6 @@ WITH the ROI entries (tests/hip_stub_roi.c), 128x72 and 200x136, a different map
 from __future__ import annotations
 
 import ctypes as C
-import json
 import os
 import subprocess
 
@@ -18,57 +17,23 @@ import pytest
 
 import roi_map_ref as R
 from cutree_mirror import read_qpmap_dump
+from host_harness import (LOG_CB, QY_NOTSUPPORTED, QY_OK, QY_POINTER, ROOT, Nal, Picture, Roi, YUV, build_host_lib, digest, load_host_lib, open_handle, scheduler_trace,
+                          submit_order_cases)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 REF_DEC = os.path.join(ROOT, "oracle", "_ref", "appdecoder")
-QY_OK, QY_FAIL, QY_POINTER, QY_NOTSUPPORTED = 0, -0x7FFFFFFF, -0x7FFFFFFD, -0x7FFFFFFC
-LAY = json.load(open(os.path.join(HERE, "golden", "qy265_layout.json")))
 SIZES = [(128, 72), (200, 136)]
 
 
-class YUV(C.Structure):
-    _fields_ = [("iWidth", C.c_int), ("iHeight", C.c_int), ("pData", C.POINTER(C.c_ubyte) * 3), ("iStride", C.c_int * 3)]
-
-
-class Picture(C.Structure):
-    _fields_ = [("iSliceType", C.c_int), ("poc", C.c_int), ("pts", C.c_longlong), ("dts", C.c_longlong), ("yuv", C.POINTER(YUV))]
-
-
-class Nal(C.Structure):
-    _fields_ = [("naltype", C.c_int), ("tid", C.c_int), ("iSize", C.c_int), ("pts", C.c_longlong), ("pPayload", C.POINTER(C.c_ubyte))]
-
-
-class Roi(C.Structure):
-    _fields_ = [("type", C.c_int), ("log2_block", C.c_int), ("device", C.c_int), ("data", C.c_void_p), ("pitch", C.c_int), ("stream", C.c_void_p)]
-
-
-def _build(d, stub, extra=()):
-    from oracle_lib import build_oracle
-    build_oracle()
-    so = str(d / "libks265enc_stub.so")
-    host = os.path.join(ROOT, "ks265codec_amd", "host")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-fPIC", "-Wall", "-Wextra", *extra, "-I", os.path.join(ROOT, "include"), "-shared", "-o", so,
-                           os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"), os.path.join(HERE, stub),
-                           "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
-    return so
+@pytest.fixture(scope="module")
+def roi_lib():
+    return load_host_lib(build_host_lib("hip_stub_roi.c"))
 
 
 @pytest.fixture(scope="module")
-def roi_lib(tmp_path_factory):
-    lib = C.CDLL(_build(tmp_path_factory.mktemp("stubroi"), "hip_stub_roi.c"))
-    lib.QY265EncoderOpen.restype = C.c_void_p
-    return lib
+def plain_lib():
+    return load_host_lib(build_host_lib("hip_stub.c"))
 
 
-@pytest.fixture(scope="module")
-def plain_lib(tmp_path_factory):
-    lib = C.CDLL(_build(tmp_path_factory.mktemp("stubplain"), "hip_stub.c"))
-    lib.QY265EncoderOpen.restype = C.c_void_p
-    return lib
-
-
-LOG_CB = C.CFUNCTYPE(None, C.c_char_p)
 _CLIPS = {}
 
 
@@ -112,25 +77,7 @@ def run(lib, W, H, n, params=(), latency=b"default", env=None, roi=None, maps=ma
         if os.path.exists(dump):
             os.remove(dump)
         env["KS265_DUMP_QPMAP"] = str(dump)
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update({k: str(v) for k, v in env.items()})
-    try:
-        cfg = (C.c_uint8 * LAY["sizeof_config"])()
-        assert lib.QY265ConfigDefaultPreset(cfg, b"medium", None, latency) == 0
-        for k, v in (("wdt", W), ("hgt", H), ("fr", 50), ("rc", rc), ("qp", 34), ("threads", 4), ("log", 1), *params):
-            assert lib.QY265ConfigParse(cfg, k.encode(), str(v).encode()) == 0, k
-        if roi is not None:
-            assert lib.ks265_enc_set_default(b"roi", C.c_int(roi)) == 0
-        err = C.c_int(0)
-        h = C.c_void_p(lib.QY265EncoderOpen(cfg, C.byref(err)))
-        if roi is not None:
-            assert lib.ks265_enc_set_default(b"roi", C.c_int(0)) == 0           # read at open: the handle keeps it
-        assert h.value, hex(err.value & 0xFFFFFFFF)
-    finally:
-        for k, v in old.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
+    h = open_handle(lib, W, H, params=(("rc", rc), *params), latency=latency, env=env, roi=bool(roi))
     nal, nn, pic, outp, yuv = C.POINTER(Nal)(), C.c_int(0), Picture(), Picture(), YUV()
     yuv.iWidth, yuv.iHeight = W, H
     yuv.iStride[0], yuv.iStride[1], yuv.iStride[2] = W, W // 2, W // 2
@@ -315,19 +262,7 @@ def test_refusals_leave_nothing_pending(roi_lib, tmp_path):
 
     lib = roi_lib
     # one handle, driven by hand: every refusal, then a picture - it must be coded without a map
-    os.environ["KS265_DUMP_QPMAP"] = str(dump)
-    try:
-        cfg = (C.c_uint8 * LAY["sizeof_config"])()
-        assert lib.QY265ConfigDefaultPreset(cfg, b"medium", None, b"zerolatency") == 0
-        for k, v in (("wdt", W), ("hgt", H), ("rc", 0), ("qp", 34), ("threads", 2), ("log", 3), ("bframes", 0)):
-            assert lib.QY265ConfigParse(cfg, k.encode(), str(v).encode()) == 0
-        assert lib.ks265_enc_set_default(b"roi", C.c_int(1)) == 0
-        err = C.c_int(0)
-        h = C.c_void_p(lib.QY265EncoderOpen(cfg, C.byref(err)))
-        assert lib.ks265_enc_set_default(b"roi", C.c_int(0)) == 0
-        assert h.value
-    finally:
-        os.environ.pop("KS265_DUMP_QPMAP")
+    h = open_handle(lib, W, H, params=(("threads", 2), ("log", 3), ("bframes", 0)), latency=b"zerolatency", env={"KS265_DUMP_QPMAP": dump}, roi=True)
     nal, nn, pic, outp, yuv = C.POINTER(Nal)(), C.c_int(0), Picture(), Picture(), YUV()
     yuv.iWidth, yuv.iHeight = W, H
     yuv.iStride[0], yuv.iStride[1], yuv.iStride[2] = W, W // 2, W // 2
@@ -377,12 +312,11 @@ def test_switch_values_and_environment(roi_lib, tmp_path):
 @pytest.mark.parametrize("case", ["plain_ippp", "plain_hier8", "no_split_hier8"])
 def test_switch_off_the_scheduler_threads_calls_are_the_pinned_ones(tmp_path, case):
     """the stand-in WITH the ROI entries, the switch off: the scheduler thread's calls to the device library are those tests/golden/submit_order.json pins - not one call added"""
-    import test_submit_order_cpu as so
-    lib = _build(tmp_path, "hip_stub_roi.c", extra=("-DKS265_STUB_SSIM",))
-    c = so.CASES[case]
-    lines = so.scheduler_trace(lib, c, str(tmp_path / "calls.log"))
-    assert len(lines) == c["lines"] and so.digest(lines) == c["sha256"]
-    on = so.scheduler_trace(lib, dict(c, env=dict(c["env"], KS265_ROI=1)), str(tmp_path / "calls_on.log"))
+    lib = build_host_lib("hip_stub_roi.c", ("KS265_STUB_SSIM",))
+    c = submit_order_cases()[case]
+    lines = scheduler_trace(lib, c, str(tmp_path / "calls.log"))
+    assert len(lines) == c["lines"] and digest(lines) == c["sha256"]
+    on = scheduler_trace(lib, dict(c, env=dict(c["env"], KS265_ROI=1)), str(tmp_path / "calls_on.log"))
     assert sum(ln.startswith("ks265_roi_ctu_map ") for ln in on) == c["n"], "and with it on: one map per picture"
     assert not any(ln.startswith(("ks265_aq_ctu_map ", "ks265_qoff_ctu_map ")) for ln in on)
 
@@ -396,15 +330,7 @@ def test_device_library_without_the_entries(plain_lib):
         assert bs == plain and len(plain) > 100
         assert log.count("ks265enc: ROI maps are unavailable: ") == 1 and "unavailable" not in log0
     lib = plain_lib
-    cfg = (C.c_uint8 * LAY["sizeof_config"])()
-    assert lib.QY265ConfigDefaultPreset(cfg, b"medium", None, b"default") == 0
-    for k, v in (("wdt", W), ("hgt", H), ("log", 3)):
-        assert lib.QY265ConfigParse(cfg, k.encode(), str(v).encode()) == 0
-    assert lib.ks265_enc_set_default(b"roi", C.c_int(1)) == 0
-    err = C.c_int(0)
-    h = C.c_void_p(lib.QY265EncoderOpen(cfg, C.byref(err)))
-    assert lib.ks265_enc_set_default(b"roi", C.c_int(0)) == 0
-    assert h.value
+    h = open_handle(lib, W, H, params=(("log", 3),), roi=True)
     m = map_of(0, W, H)
     assert lib.ks265_enc_set_next_roi(h, C.byref(describe(*m))) == QY_NOTSUPPORTED
     assert lib.ks265_enc_set_next_roi(h, None) == QY_OK

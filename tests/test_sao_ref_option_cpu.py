@@ -10,18 +10,15 @@ import sys
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+from host_harness import LAY, ROOT, build_host_lib, load_host_lib
 
 _DRIVER = r"""
 import ctypes as C, json, os, sys
 import numpy as np
 ROOT = sys.argv[1]
-LAY = json.load(open(os.path.join(ROOT, "tests", "golden", "qy265_layout.json")))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from host_harness import LAY, YUV, Nal, Picture
 lib = C.CDLL(os.environ["KS265_STUB_LIB"]); lib.QY265EncoderOpen.restype = C.c_void_p
-class YUV(C.Structure): _fields_ = [("iWidth", C.c_int), ("iHeight", C.c_int), ("pData", C.POINTER(C.c_ubyte) * 3), ("iStride", C.c_int * 3)]
-class Picture(C.Structure): _fields_ = [("iSliceType", C.c_int), ("poc", C.c_int), ("pts", C.c_longlong), ("dts", C.c_longlong), ("yuv", C.POINTER(YUV))]
-class Nal(C.Structure): _fields_ = [("naltype", C.c_int), ("tid", C.c_int), ("iSize", C.c_int), ("pts", C.c_longlong), ("pPayload", C.POINTER(C.c_ubyte))]
 W, H, N = 128, 72, 6
 clip = np.random.default_rng(5).integers(0, 256, (N, W * H * 3 // 2), dtype=np.uint8)
 cfg = (C.c_uint8 * LAY["sizeof_config"])()
@@ -52,21 +49,13 @@ print(json.dumps({"vcl": vcl}))
 
 
 @pytest.fixture(scope="module")
-def stub_lib(tmp_path_factory):
-    from oracle_lib import build_oracle
-    build_oracle()
-    d = tmp_path_factory.mktemp("stubenc_sao_ref")
-    so = str(d / "libks265enc_stub.so")
-    host = os.path.join(ROOT, "ks265codec_amd", "host")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-fPIC", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"), "-shared", "-o", so,
-                           os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"), os.path.join(HERE, "hip_stub.c"),
-                           "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
-    return so
+def stub_lib():
+    return build_host_lib("hip_stub.c")
 
 
 def test_sao_ref_is_parsed_and_sao_is_parsed_as_before(stub_lib):
-    lib = C.CDLL(stub_lib)
-    gold = json.load(open(os.path.join(HERE, "golden", "qy265_layout.json")))
+    lib = load_host_lib(stub_lib)
+    gold = LAY
     buf = (C.c_uint8 * gold["sizeof_config"])()
 
     def sao(): return C.c_int32.from_buffer(buf, gold["sao"]).value

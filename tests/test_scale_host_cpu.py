@@ -7,67 +7,21 @@ input and the scaler (tests/hip_stub_scale.c):
 from __future__ import annotations
 
 import ctypes as C
-import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import yuv_convert_ref as cref
 import yuv_scale_ref as ys
+from host_harness import IN_I420, IN_RGB, LOG_CB, QY_NOTSUPPORTED, QY_OK, QY_POINTER, Nal, Picture, Roi, build_host_lib, calls, dev_pic, device_picture, drive, load_host_lib, preceded
+from host_harness import open_handle as open_at
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-QY_OK, QY_FAIL, QY_POINTER, QY_NOTSUPPORTED = 0, -0x7FFFFFFF, -0x7FFFFFFD, -0x7FFFFFFC
-LAY = json.load(open(os.path.join(HERE, "golden", "qy265_layout.json")))
 W, H, SW, SH, N = 64, 48, 128, 96, 17
 
 
-class Picture(C.Structure):
-    _fields_ = [("iSliceType", C.c_int), ("poc", C.c_int), ("pts", C.c_longlong), ("dts", C.c_longlong), ("yuv", C.c_void_p)]
-
-
-class Nal(C.Structure):
-    _fields_ = [("naltype", C.c_int), ("tid", C.c_int), ("iSize", C.c_int), ("pts", C.c_longlong), ("pPayload", C.POINTER(C.c_ubyte))]
-
-
-class DevPicture(C.Structure):
-    _fields_ = [("format", C.c_int), ("device", C.c_int), ("plane", C.c_void_p * 3), ("pitch", C.c_int * 3), ("pixel_step", C.c_int),
-                ("matrix", C.c_int), ("full_range", C.c_int), ("stream", C.c_void_p), ("pts", C.c_longlong)]
-
-
-class Roi(C.Structure):
-    _fields_ = [("type", C.c_int), ("log2_block", C.c_int), ("device", C.c_int), ("data", C.c_void_p), ("pitch", C.c_int), ("stream", C.c_void_p)]
-
-
-def _build(d, extra=()):
-    from oracle_lib import build_oracle
-    build_oracle()
-    so = str(d / "libks265enc_stub.so")
-    host = os.path.join(ROOT, "ks265codec_amd", "host")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-fPIC", "-Wall", "-Wextra", *extra, "-I", os.path.join(ROOT, "include"), "-shared", "-o", so,
-                           os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"), os.path.join(HERE, "hip_stub_scale.c"),
-                           "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
-    return so
-
-
-def _load(d, extra=()):
-    log = str(d / "calls.log")
-    old = os.environ.get("KS265_STUB_CALL_LOG")
-    os.environ["KS265_STUB_CALL_LOG"] = log                              # read once, at the library's first logged call
-    try:
-        lib = C.CDLL(_build(d, extra))
-        lib.QY265EncoderOpen.restype = C.c_void_p
-        lib.ks265_stub_live.restype = C.c_long
-        lib.ks265_stub_creating_calls.restype = C.c_long
-        h = open_handle(lib)                                            # (the first logged call)
-        lib.QY265EncoderClose(h)
-    finally:
-        os.environ.pop("KS265_STUB_CALL_LOG", None)
-        if old is not None:
-            os.environ["KS265_STUB_CALL_LOG"] = old
-    lib.call_log_path = log
+def _load(d, defines=()):
+    lib = load_host_lib(build_host_lib("hip_stub_scale.c", defines), call_log=str(d / "calls.log"))
+    lib.ks265_stub_creating_calls.restype = C.c_long
     return lib
 
 
@@ -78,55 +32,19 @@ def lib(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def lib_without(tmp_path_factory):
-    return _load(tmp_path_factory.mktemp("stubnoscale"), ("-DKS265_STUB_NO_SCALE",))
+    return _load(tmp_path_factory.mktemp("stubnoscale"), ("KS265_STUB_NO_SCALE",))
 
 
-LOG_CB = C.CFUNCTYPE(None, C.c_char_p)
+def open_handle(lib, w=W, h=H, **kw):
+    return open_at(lib, w, h, **kw)
 
 
-def open_handle(lib, w=W, h=H, params=(), env=None, roi=False, lines=None):
-    env = dict(env or {})
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        cfg = (C.c_uint8 * LAY["sizeof_config"])()
-        assert lib.QY265ConfigDefaultPreset(cfg, b"medium", None, b"default") == 0
-        for k, v in (("wdt", w), ("hgt", h), ("fr", 50), ("rc", 0), ("qp", 34), ("threads", 4), ("log", 1), *params):
-            assert lib.QY265ConfigParse(cfg, k.encode(), str(v).encode()) == 0, k
-        if roi:
-            assert lib.ks265_enc_set_default(b"roi", C.c_int(1)) == 0
-        err = C.c_int(0)
-        hd = C.c_void_p(lib.QY265EncoderOpen(cfg, C.byref(err)))
-        if roi:
-            assert lib.ks265_enc_set_default(b"roi", C.c_int(0)) == 0
-        assert hd.value, hex(err.value & 0xFFFFFFFF)
-    finally:
-        for k, v in old.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-    return hd
+def i420_args(w, h):
+    return (0, w * h, w * h * 5 // 4), (w, w // 2, w // 2), IN_I420
 
 
-def calls(lib) -> int:
-    return sum(1 for _ in open(lib.call_log_path))
-
-
-def i420_pic(a: np.ndarray, w: int, h: int, pts=0) -> DevPicture:
-    p = DevPicture()
-    p.format, p.device, p.stream, p.pts = 0, 0, None, pts
-    p.plane[0], p.plane[1], p.plane[2] = a.ctypes.data, a.ctypes.data + w * h, a.ctypes.data + w * h * 5 // 4
-    p.pitch[0], p.pitch[1], p.pitch[2] = w, w // 2, w // 2
-    return p
-
-
-def rgba_pic(a: np.ndarray, w: int, pts=0) -> DevPicture:
-    p = DevPicture()
-    p.format, p.device, p.stream, p.pts, p.pixel_step, p.matrix, p.full_range = 2, 0, None, pts, 4, 0, 0
-    for k in range(3):
-        p.plane[k] = a.ctypes.data + k
-    p.pitch[0] = w * 4
-    return p
+def i420_pic(a: np.ndarray, w: int, h: int, pts=0):
+    return dev_pic([a], *i420_args(w, h), pts)
 
 
 def roi_of(t):
@@ -141,36 +59,25 @@ def session(lib, pictures, scaled, filt=1, rgba=False, lanes=1, roi=False, param
     lines = []
     cb = LOG_CB(lambda m: lines.append(m.decode()))
     lib.QY265SetLogPrintf(cb)
-    h = open_handle(lib, params=params, env={"KS265_GOP_LANES": str(lanes)}, roi=roi)
+    h = open_handle(lib, params=params, lanes=lanes, roi=roi)
     assert lib.ks265_enc_enable_device_input(h) == QY_OK
     if scaled:
         assert lib.ks265_enc_enable_device_scale(h, SW, SH) == QY_OK
-    nal, nn, outp, bs = C.POINTER(Nal)(), C.c_int(0), Picture(), bytearray()
 
-    def collect():
-        bs.extend(b"".join(C.string_at(nal[i].pPayload, nal[i].iSize) for i in range(nn.value) if nal[i].iSize > 0))
-
-    for t, a in enumerate(pictures):
-        a = np.ascontiguousarray(a).copy()
-        if roi and t % 3 != 2:
-            keep, r = roi_of(t)
-            assert lib.ks265_enc_set_next_roi(h, C.byref(r)) == QY_OK
-        if scaled:
-            pic = rgba_pic(a, SW, t) if rgba else i420_pic(a, SW, SH, t)
-            rc = lib.ks265_enc_encode_device_frame_scaled(h, C.byref(nal), C.byref(nn), C.byref(pic), SW, SH, filt, C.byref(outp))
+    def picture(t, a):
+        if scaled and rgba:
+            put = device_picture(lib, h, [a], (0, 1, 2), (SW * 4,), IN_RGB, t, step=4, scaled=(SW, SH, filt))
         else:
-            pic = i420_pic(a, W, H, t)
-            rc = lib.ks265_enc_encode_device_frame(h, C.byref(nal), C.byref(nn), C.byref(pic), C.byref(outp))
-        assert rc == QY_OK, hex(rc & 0xFFFFFFFF)
-        collect()
-        a[:] = 0x5A                                                     # the picture is the caller's again once the call has returned (the stand-in runs everything inside the call)
-    while lib.QY265EncoderDelayedFrames(h) > 0:
-        assert lib.QY265EncoderEncodeFrame(h, C.byref(nal), C.byref(nn), None, C.byref(outp), 0) == QY_OK
-        collect()
-    lib.QY265EncoderClose(h)
+            put = device_picture(lib, h, [a], *i420_args(*((SW, SH) if scaled else (W, H))), t, scaled=(SW, SH, filt) if scaled else None)
+        return preceded(lambda: set_map(t), put) if roi and t % 3 != 2 else put
+
+    def set_map(t, keep=[]):
+        keep[:] = roi_of(t)                                             # (the map stays the caller's until the picture is taken)
+        assert lib.ks265_enc_set_next_roi(h, C.byref(keep[1])) == QY_OK
+
+    bs = drive(lib, h, (picture(t, a) for t, a in enumerate(pictures)))
     lib.QY265SetLogPrintf(None)
-    assert [lib.ks265_stub_live(k) for k in range(5)] == [0] * 5, "contexts, frame objects, events, device and pinned blocks"
-    return bytes(bs), "".join(lines)
+    return bs, "".join(lines)
 
 
 _SRC = {}
@@ -205,18 +112,9 @@ def test_scaled_entry_equals_prescaled_pictures(lib, filt, rgba, lanes, roi):
 def test_own_size_is_the_plain_entry(lib):
     pics = prescaled(False, 1)
     exp, _ = session(lib, pics, False)
-    h = open_handle(lib, env={"KS265_GOP_LANES": "1"})
+    h = open_handle(lib, lanes=1)
     assert lib.ks265_enc_enable_device_input(h) == QY_OK               # (the switch is not even on)
-    nal, nn, outp, bs = C.POINTER(Nal)(), C.c_int(0), Picture(), bytearray()
-    for t, a in enumerate(pics):
-        pic = i420_pic(a, W, H, t)
-        assert lib.ks265_enc_encode_device_frame_scaled(h, C.byref(nal), C.byref(nn), C.byref(pic), W, H, 1, C.byref(outp)) == QY_OK
-        bs.extend(b"".join(C.string_at(nal[i].pPayload, nal[i].iSize) for i in range(nn.value) if nal[i].iSize > 0))
-    while lib.QY265EncoderDelayedFrames(h) > 0:
-        assert lib.QY265EncoderEncodeFrame(h, C.byref(nal), C.byref(nn), None, C.byref(outp), 0) == QY_OK
-        bs.extend(b"".join(C.string_at(nal[i].pPayload, nal[i].iSize) for i in range(nn.value) if nal[i].iSize > 0))
-    lib.QY265EncoderClose(h)
-    assert bytes(bs) == exp
+    assert drive(lib, h, (device_picture(lib, h, [a], *i420_args(W, H), t, scaled=(W, H, 1)) for t, a in enumerate(pics))) == exp
 
 
 def test_enable_refusals(lib, lib_without):
@@ -254,7 +152,7 @@ def test_enable_refusals(lib, lib_without):
 
 
 def test_picture_refusals_enqueue_nothing_and_keep_the_map(lib):
-    h = open_handle(lib, roi=True, env={"KS265_GOP_LANES": "1"})
+    h = open_handle(lib, roi=True, lanes=1)
     assert lib.ks265_enc_enable_device_input(h) == QY_OK
     nal, nn, outp = C.POINTER(Nal)(), C.c_int(0), Picture()
     src = sources(False)[0].copy()
@@ -293,7 +191,7 @@ def test_picture_refusals_enqueue_nothing_and_keep_the_map(lib):
 
 
 def test_plan_cache_keeps_four_and_leaks_nothing(lib):
-    h = open_handle(lib, env={"KS265_GOP_LANES": "1"}, params=(("bframes", 0),))
+    h = open_handle(lib, lanes=1, params=(("bframes", 0),))
     assert lib.ks265_enc_enable_device_input(h) == QY_OK
     assert lib.ks265_enc_enable_device_scale(h, 256, 192) == QY_OK
     nal, nn, outp = C.POINTER(Nal)(), C.c_int(0), Picture()

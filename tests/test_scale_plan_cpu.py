@@ -2,7 +2,6 @@
 a stand-alone program built with -fsanitize=address,undefined and run as a child process: every table sits in a heap block of exactly its extent."""
 from __future__ import annotations
 
-import os
 import subprocess
 
 import numpy as np
@@ -10,16 +9,12 @@ import pytest
 
 import yuv_scale_ref as ys
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+from host_harness import build_host_program
 
 
 @pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("scale") / "scale_plan_main")
-    subprocess.check_call(["gcc", "-O1", "-g", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan",
-                           "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "ks265codec_amd", "host"), "-o", out, os.path.join(HERE, "scale_plan_main.c")])
-    return out
+def exe():
+    return build_host_program("scale_plan_main.c")
 
 
 @pytest.mark.parametrize("filt", [ys.TRIANGLE, ys.CATMULL_ROM])

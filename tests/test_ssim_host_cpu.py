@@ -3,30 +3,22 @@ SSIM pass as a weak symbol, so the library still loads (RTLD_NOW), the encoder w
 `bitrate, psnr:` but no ` ssim:` line.  (The guard of the weak-symbol path: the GPU side of -ssim is tests/test_gpu_ssim.py.)"""
 from __future__ import annotations
 
-import ctypes as C
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+from host_harness import build_host_cli, build_host_lib, load_host_lib
+
 W, H, N = 128, 72, 9
 
 
 @pytest.fixture(scope="module")
 def stub_cli(tmp_path_factory):
-    from oracle_lib import build_oracle
-    build_oracle()
+    """a directory with the command line on the stand-in (as ks265enc) and a clip"""
     d = tmp_path_factory.mktemp("stubssim")
-    so, exe = str(d / "libks265enc.so"), str(d / "ks265enc")
-    host, inc = os.path.join(ROOT, "ks265codec_amd", "host"), os.path.join(ROOT, "include")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-fPIC", "-Wall", "-Wextra", "-I", inc, "-shared", "-o", so,
-                           os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"), os.path.join(HERE, "hip_stub.c"),
-                           "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-Wall", "-Wextra", "-I", inc, "-o", exe, os.path.join(host, "ks265_cli.c"), "-L", str(d), "-lks265enc",
-                           "-Wl,-rpath," + str(d), "-Wl,-rpath-link," + os.path.join(ROOT, "oracle"), "-lpthread"])
+    os.symlink(build_host_cli(), d / "ks265enc")
     np.random.default_rng(11).integers(0, 256, (N, W * H * 3 // 2), dtype=np.uint8).tofile(str(d / "in.yuv"))
     return d
 
@@ -38,8 +30,8 @@ def _run(d, name, *extra):
     return r, open(out, "rb").read() if os.path.exists(out) else b""
 
 
-def test_host_library_loads_now(stub_cli):
-    lib = C.CDLL(str(stub_cli / "libks265enc.so"), mode=os.RTLD_NOW)
+def test_host_library_loads_now():
+    lib = load_host_lib(build_host_lib("hip_stub.c"), mode=os.RTLD_NOW)
     assert hasattr(lib, "ks265_enc_get_quality") and not hasattr(lib, "ks265_ssim_picture")
 
 

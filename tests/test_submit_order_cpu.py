@@ -5,54 +5,20 @@ place in a picture's sequence is a race on the GPU that no stream comparison sho
 tests/golden/submit_order.json holds for every case (tests/golden/submit_order_gen.py writes them)."""
 from __future__ import annotations
 
-import hashlib
-import json
 import os
-import subprocess
-import sys
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+from host_harness import HERE, build_host_lib, digest, scheduler_trace, submit_order_cases
+
 GOLDEN = os.path.join(HERE, "golden", "submit_order.json")
-CASES = json.load(open(GOLDEN))["cases"]
-
-
-def build_stub(d) -> str:
-    """the host + the stand-in, the stand-in with its two -ssim entries (-DKS265_STUB_SSIM) so that the `-ssim` case runs the fused pass"""
-    from oracle_lib import build_oracle
-    build_oracle()
-    so = os.path.join(str(d), "libks265enc_stub.so")
-    host = os.path.join(ROOT, "ks265codec_amd", "host")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-fPIC", "-Wall", "-Wextra", "-DKS265_STUB_SSIM", "-I", os.path.join(ROOT, "include"), "-shared", "-o", so,
-                           os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"), os.path.join(HERE, "hip_stub.c"),
-                           "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
-    return so
-
-
-def scheduler_trace(so: str, case: dict, log: str) -> list[str]:
-    """one run of tests/host_driver.py (128x72, one lane); the lines of the thread that issued the ks265_encode_picture* calls, without the thread column"""
-    if os.path.exists(log):
-        os.remove(log)
-    env = dict(os.environ, KS265_STUB_LIB=so, KS265_STUB_CALL_LOG=log, KS265_GOP_LANES="1", **{k: str(v) for k, v in case["env"].items()})
-    args = [sys.executable, os.path.join(HERE, "host_driver.py"), ROOT, str(case["n"]), str(case["iper"]), str(case["bframes"]), "128", "72"]
-    r = subprocess.run(args, capture_output=True, text=True, timeout=120, env=env)
-    assert r.returncode == 0, r.stdout[-600:] + r.stderr[-1200:]
-    assert json.loads(r.stdout.strip().splitlines()[-1])["vcl"] == case["n"]
-    lines = [ln.split(" ", 1) for ln in open(log).read().splitlines()]
-    threads = sorted({t for t, rest in lines if rest.startswith("ks265_encode_picture")})
-    assert len(threads) == 1, threads
-    return [rest for t, rest in lines if t == threads[0]]
-
-
-def digest(lines: list[str]) -> str:
-    return hashlib.sha256("\n".join(lines).encode()).hexdigest()
+CASES = submit_order_cases()
+STUB = ("hip_stub.c", ("KS265_STUB_SSIM",))                      # the stand-in with its two -ssim entries, so that the `-ssim` case runs the fused pass
 
 
 @pytest.fixture(scope="module")
-def stub_lib(tmp_path_factory):
-    return build_stub(tmp_path_factory.mktemp("stuborder"))
+def stub_lib():
+    return build_host_lib(*STUB)
 
 
 @pytest.mark.parametrize("name", sorted(CASES))

@@ -12,119 +12,35 @@ at 202x134 (coded 208x136) and 128x72:
     behind the previous call's conversion (the calls may name different streams and share the lane's scratch picture);
   * a `roi` map of the SOURCE picture's ceil(W / b) x ceil(H / b) elements is taken, from "device" and from host memory;
   * a 128x72 handle makes none of the new calls;
-  * tests/window_main.c, the host and the stand-in under -fsanitize=address,undefined as a program of its own: 5 pictures at 202x134, both latencies."""
+  * tests/input_filter_main.c, the host and the stand-in under -fsanitize=address,undefined as a program of its own: 5 pictures at 202x134, both latencies."""
 from __future__ import annotations
 
 import ctypes as C
-import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import picture_window_ref as pw
 import window_sps as ws
+from host_harness import (IN_I420, IN_NV12, IN_RGB, LAY, QY_NOTSUPPORTED, QY_OK, DevPicture, Nal, Picture, Roi, YUV, build_host_lib, build_host_program, clip,
+                          filter_program, load_host_lib, nals, open_handle, session, try_open)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-QY_OK, QY_FAIL, QY_POINTER, QY_NOTSUPPORTED = 0, -0x7FFFFFFF, -0x7FFFFFFD, -0x7FFFFFFC
-LAY = json.load(open(os.path.join(HERE, "golden", "qy265_layout.json")))
 W, H, CW, CH, N = 202, 134, 208, 136, 17
-IN_I420, IN_NV12, IN_RGB = 0, 1, 2
-
-
-class YUV(C.Structure):
-    _fields_ = [("iWidth", C.c_int), ("iHeight", C.c_int), ("pData", C.POINTER(C.c_ubyte) * 3), ("iStride", C.c_int * 3)]
-
-
-class Picture(C.Structure):
-    _fields_ = [("iSliceType", C.c_int), ("poc", C.c_int), ("pts", C.c_longlong), ("dts", C.c_longlong), ("yuv", C.POINTER(YUV))]
-
-
-class Nal(C.Structure):
-    _fields_ = [("naltype", C.c_int), ("tid", C.c_int), ("iSize", C.c_int), ("pts", C.c_longlong), ("pPayload", C.POINTER(C.c_ubyte))]
-
-
-class DevPicture(C.Structure):
-    _fields_ = [("format", C.c_int), ("device", C.c_int), ("plane", C.c_void_p * 3), ("pitch", C.c_int * 3), ("pixel_step", C.c_int),
-                ("matrix", C.c_int), ("full_range", C.c_int), ("stream", C.c_void_p), ("pts", C.c_longlong)]
 
 
 class PadCall(C.Structure):
     _fields_ = [("format", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("cw", C.c_int32), ("ch", C.c_int32), ("pitch", C.c_int32 * 3)]
 
 
-def _build(d, stub):
-    from oracle_lib import build_oracle
-    build_oracle()
-    so = str(d / "libks265enc_stub.so")
-    host = os.path.join(ROOT, "ks265codec_amd", "host")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-fPIC", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"), "-shared", "-o", so,
-                           os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"), os.path.join(HERE, stub),
-                           "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
-    return so
-
-
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp("stubwin")
-    so, log = _build(d, "hip_stub_window.c"), str(d / "calls.log")
-    old = os.environ.get("KS265_STUB_CALL_LOG")
-    os.environ["KS265_STUB_CALL_LOG"] = log                              # read once, at the library's first logged call
-    try:
-        lib = C.CDLL(so)
-        lib.QY265EncoderOpen.restype = C.c_void_p
-        lib.ks265_stub_live.restype = C.c_long
-        lib.QY265EncoderClose(open_handle(lib, 128, 72))                # (the first logged call)
-    finally:
-        os.environ.pop("KS265_STUB_CALL_LOG", None)
-        if old is not None:
-            os.environ["KS265_STUB_CALL_LOG"] = old
-    lib.call_log_path = log
-    return lib
+    return load_host_lib(build_host_lib("hip_stub_window.c"), call_log=str(tmp_path_factory.mktemp("stubwin") / "calls.log"))
 
 
 @pytest.fixture(scope="module")
-def plain(tmp_path_factory):
-    lib = C.CDLL(_build(tmp_path_factory.mktemp("stubplain"), "hip_stub.c"))
-    lib.QY265EncoderOpen.restype = C.c_void_p
-    return lib
-
-
-def try_open(lib, w, h, params=(), lanes=1, latency=b"default"):
-    old = os.environ.get("KS265_GOP_LANES")
-    os.environ["KS265_GOP_LANES"] = str(lanes)
-    try:
-        cfg = (C.c_uint8 * LAY["sizeof_config"])()
-        assert lib.QY265ConfigDefaultPreset(cfg, b"medium", None, latency) == 0
-        for k, v in (("wdt", w), ("hgt", h), ("fr", 50), ("rc", 0), ("qp", 34), ("threads", 4), ("log", 1), *params):
-            assert lib.QY265ConfigParse(cfg, k.encode(), str(v).encode()) == 0, k
-        err = C.c_int(0)
-        return C.c_void_p(lib.QY265EncoderOpen(cfg, C.byref(err))), err.value
-    finally:
-        os.environ.pop("KS265_GOP_LANES", None)
-        if old is not None:
-            os.environ["KS265_GOP_LANES"] = old
-
-
-def open_handle(lib, w, h, **kw):
-    hd, err = try_open(lib, w, h, **kw)
-    assert hd.value, hex(err & 0xFFFFFFFF)
-    return hd
-
-
-def clip(w, h, n, seed):
-    """n moving packed I420 pictures"""
-    rng = np.random.default_rng(seed)
-    yy, xx = np.mgrid[0:h, 0:w]
-    out = []
-    for t in range(n):
-        y = np.clip(128 + 90 * np.sin(0.11 * (xx + 2 * t)) * np.cos(0.07 * (yy + 3 * t)) + rng.integers(0, 6, (h, w)), 0, 255).astype(np.uint8)
-        u = np.clip(128 + 50 * np.sin(0.05 * (xx[::2, ::2] + t)), 0, 255).astype(np.uint8)
-        v = np.clip(128 + 50 * np.cos(0.09 * (yy[::2, ::2] + t)), 0, 255).astype(np.uint8)
-        out.append(pw.pack([y, u, v]))
-    return out
+def plain():
+    return load_host_lib(build_host_lib("hip_stub.c"))
 
 
 def pad_calls(lib):
@@ -133,75 +49,10 @@ def pad_calls(lib):
     return [(c.format, c.w, c.h, c.cw, c.ch, tuple(c.pitch)) for c in buf[:n]]
 
 
-def session(lib, w, h, pictures, ways="c", lanes=1, latency=b"default", params=(), recon=None):
-    """one w x h handle fed packed I420 `pictures`, picture t by way ways[t % len(ways)]: c contiguous, s strided, a an acquired slot, d / n a device I420 / NV12 picture with
-    pitches of its own.  The stream."""
-    hd = open_handle(lib, w, h, lanes=lanes, latency=latency, params=params)
-    if recon:
-        assert lib.ks265_enc_set_recon_file(hd, recon.encode()) == QY_OK
-    if set(ways) & set("dn"):
-        assert lib.ks265_enc_enable_device_input(hd) == QY_OK
-    nal, nn, pic, outp, bs = C.POINTER(Nal)(), C.c_int(0), Picture(), Picture(), bytearray()
-
-    def collect():
-        bs.extend(b"".join(C.string_at(nal[i].pPayload, nal[i].iSize) for i in range(nn.value) if nal[i].iSize > 0))
-
-    for t, p in enumerate(pictures):
-        way = ways[t % len(ways)]
-        pl = pw.planes(p, w, h)
-        yuv = YUV()
-        keep = []
-        if way in "dn":
-            extra = 5
-            if way == "n":
-                uv = np.empty((h // 2, w), np.uint8)
-                uv[:, 0::2], uv[:, 1::2] = pl[1], pl[2]
-                pl = [pl[0], uv]
-            d = DevPicture()
-            d.format, d.device, d.stream, d.pts = (IN_NV12 if way == "n" else IN_I420), 0, None, t
-            for k, q in enumerate(pl):
-                b = np.full((q.shape[0], q.shape[1] + extra), 0xA5, np.uint8)
-                b[:, :q.shape[1]] = q
-                keep.append(b)
-                d.plane[k], d.pitch[k] = b.ctypes.data, b.strides[0]
-            rc = lib.ks265_enc_encode_device_frame(hd, C.byref(nal), C.byref(nn), C.byref(d), C.byref(outp))
-            for b in keep:
-                b[:] = 0x5A                                             # the caller's again once the call has returned (the stand-in runs everything inside it)
-        else:
-            if way == "a" and lib.ks265_enc_acquire_input(hd, C.byref(yuv)) == QY_OK:
-                assert (yuv.iWidth, yuv.iHeight, tuple(yuv.iStride)) == (w, h, (w, w // 2, w // 2))
-                for k, q in enumerate(pl):
-                    C.memmove(yuv.pData[k], np.ascontiguousarray(q).ctypes.data, q.size)
-            else:
-                extra = 9 if way == "s" else 0
-                yuv.iWidth, yuv.iHeight = w, h
-                for k, q in enumerate(pl):
-                    b = np.full((q.shape[0], q.shape[1] + extra), 0xA5, np.uint8)
-                    b[:, :q.shape[1]] = q
-                    keep.append(b)
-                    yuv.pData[k], yuv.iStride[k] = C.cast(b.ctypes.data, C.POINTER(C.c_ubyte)), b.strides[0]
-            pic.yuv, pic.pts = C.pointer(yuv), t
-            rc = lib.QY265EncoderEncodeFrame(hd, C.byref(nal), C.byref(nn), C.byref(pic), C.byref(outp), 0)
-        assert rc == QY_OK, (way, hex(rc & 0xFFFFFFFF))
-        collect()
-    while lib.QY265EncoderDelayedFrames(hd) > 0:
-        assert lib.QY265EncoderEncodeFrame(hd, C.byref(nal), C.byref(nn), None, C.byref(outp), 0) == QY_OK
-        collect()
-    lib.QY265EncoderClose(hd)
-    assert [lib.ks265_stub_live(k) for k in range(5)] == [0] * 5, "contexts, frame objects, events, device and pinned blocks"
-    return bytes(bs)
-
-
-def nals(stream: bytes) -> list[tuple[int, bytes]]:
-    """(type, bytes) of every NAL unit, start codes dropped"""
-    parts = stream.split(b"\x00\x00\x01")[1:]
-    return [((p[0] >> 1) & 63, p.rstrip(b"\x00") if i + 1 < len(parts) else p) for i, p in enumerate(parts)]
-
-
 def test_plain_stand_in_refuses_a_ragged_size(plain):
-    hd, err = try_open(plain, W, H)
+    hd, err = try_open(plain, W, H, lanes=1)
     assert not hd.value and err == QY_NOTSUPPORTED
-    hd, err = try_open(plain, 128, 72)
+    hd, err = try_open(plain, 128, 72, lanes=1)
     assert hd.value
     plain.QY265EncoderClose(hd)
 
@@ -271,7 +122,7 @@ def test_odd_sizes_are_refused(lib):
 
 
 def test_refusals_on_a_ragged_handle_leave_it_usable(lib):
-    hd = open_handle(lib, W, H, latency=b"zerolatency")
+    hd = open_handle(lib, W, H, lanes=1, latency=b"zerolatency")
     assert lib.ks265_enc_enable_device_input(hd) == QY_OK
     assert lib.ks265_enc_enable_device_scale(hd, 512, 512) == QY_NOTSUPPORTED
     nal, nn, outp = C.POINTER(Nal)(), C.c_int(0), Picture()
@@ -330,11 +181,7 @@ def test_upload_out_of_the_callers_memory_is_padded_too(lib, upl):
 def _fetch_all(lib, w, h, pictures):
     """a zero-latency handle with `devrecon`: every picture's reconstruction fetched as packed I420 right behind its call, each fetch naming another stream; (pictures, the
     call log's lines of every fetch)"""
-    assert lib.ks265_enc_set_default(b"devrecon", C.c_int(1)) == 0
-    try:
-        hd = open_handle(lib, w, h, latency=b"zerolatency")
-    finally:
-        assert lib.ks265_enc_set_default(b"devrecon", C.c_int(0)) == 0
+    hd = open_handle(lib, w, h, lanes=1, latency=b"zerolatency", defaults=("devrecon",))
     nal, nn, pic, outp, yuv = C.POINTER(Nal)(), C.c_int(0), Picture(), Picture(), YUV()
     yuv.iWidth, yuv.iHeight = w, h
     yuv.iStride[0], yuv.iStride[1], yuv.iStride[2] = w, w // 2, w // 2
@@ -384,16 +231,8 @@ def test_device_recon_is_the_window_and_its_scratch_picture_is_guarded(lib):
         assert len(rest) - len(names(logs_c[t])) == (1 if t == 0 else 2), (rest, names(logs_c[t]))
 
 
-class Roi(C.Structure):
-    _fields_ = [("type", C.c_int), ("log2_block", C.c_int), ("device", C.c_int), ("data", C.c_void_p), ("pitch", C.c_int), ("stream", C.c_void_p)]
-
-
 def test_roi_maps_describe_the_source_picture(lib):
-    assert lib.ks265_enc_set_default(b"roi", C.c_int(1)) == 0
-    try:
-        hd = open_handle(lib, W, H, latency=b"zerolatency")
-    finally:
-        assert lib.ks265_enc_set_default(b"roi", C.c_int(0)) == 0
+    hd = open_handle(lib, W, H, lanes=1, latency=b"zerolatency", roi=True)
     assert lib.ks265_enc_enable_device_input(hd) == QY_OK
     nal, nn, outp = C.POINTER(Nal)(), C.c_int(0), Picture()
     pl = [np.ascontiguousarray(q) for q in pw.planes(clip(W, H, 1, 79)[0], W, H)]
@@ -426,19 +265,17 @@ def test_a_multiple_of_8_makes_no_new_call(lib):
     assert pad_calls(lib) == []
 
 
+@pytest.fixture(scope="module")
+def sanitized():
+    """tests/input_filter_main.c + the host + the stand-in (which has none of the filters' entries), built with -fsanitize=address,undefined"""
+    return build_host_program("input_filter_main.c", stub="hip_stub_window.c")
+
+
 @pytest.mark.parametrize("latency", ["default", "zerolatency"])
-def test_host_and_stand_in_under_the_sanitizers(tmp_path_factory, tmp_path, latency):
-    from oracle_lib import build_oracle
-    build_oracle()
-    host = os.path.join(ROOT, "ks265codec_amd", "host")
-    exe = str(tmp_path / "window_main")
-    subprocess.check_call(["gcc", "-O1", "-g", "-std=gnu11", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "include"),
-                           "-o", exe, os.path.join(HERE, "window_main.c"), os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"),
-                           os.path.join(HERE, "hip_stub_window.c"), "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
+def test_host_and_stand_in_under_the_sanitizers(sanitized, tmp_path, latency):
     rec, out = str(tmp_path / "rec.yuv"), str(tmp_path / "out.265")
-    r = subprocess.run([exe, str(W), str(H), "5", rec, out] + (["zerolatency"] if latency == "zerolatency" else []), capture_output=True, text=True,
-                       env={**os.environ, "KS265_GOP_LANES": "1", "ASAN_OPTIONS": "detect_leaks=1"})
-    assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
+    recs = filter_program(sanitized, W, H, 5, out, latency, "recon=" + rec)
+    assert recs["pad"] == [dict(format=IN_I420, w=W, h=H, cw=CW, ch=CH, pitch0=W, pitch1=W // 2, pitch2=W // 2)] * 5 and not recs["denoise"] + recs["enhance"] + recs["hdr"]
     sps = ws.stream_sps(open(out, "rb").read())
     assert ws.output_size(sps) == (W, H) and (sps["width"], sps["height"]) == (CW, CH)
     assert os.path.getsize(rec) == 5 * W * H * 3 // 2

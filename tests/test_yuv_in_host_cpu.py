@@ -12,8 +12,6 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
-import json
-import os
 import subprocess
 
 import numpy as np
@@ -21,90 +19,25 @@ import pytest
 
 import yuv_hibit_ref as yh
 import yuv_scale_ref as ys
+from host_harness import QY_NOTSUPPORTED, QY_OK, QY_POINTER, Nal, Picture, Roi, build_host_lib, build_host_program, dev_pic, device_picture, drive, host_picture, load_host_lib
+from host_harness import open_handle as open_at
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-QY_OK, QY_FAIL, QY_POINTER, QY_NOTSUPPORTED = 0, -0x7FFFFFFF, -0x7FFFFFFD, -0x7FFFFFFC
-LAY = json.load(open(os.path.join(HERE, "golden", "qy265_layout.json")))
 W, H, SW, SH, N = 128, 72, 256, 144, 17
 P010, I210, YUYV8, NV12 = (yh.SEMI, yh.S420, 10, 1), (yh.PLANAR, yh.S422, 10, 0), (yh.YUYV, yh.S422, 8, 0), (yh.SEMI, yh.S420, 8, 0)
-
-
-class YUV(C.Structure):
-    _fields_ = [("iWidth", C.c_int), ("iHeight", C.c_int), ("pData", C.POINTER(C.c_ubyte) * 3), ("iStride", C.c_int * 3)]
-
-
-class Picture(C.Structure):
-    _fields_ = [("iSliceType", C.c_int), ("poc", C.c_int), ("pts", C.c_longlong), ("dts", C.c_longlong), ("yuv", C.POINTER(YUV))]
-
-
-class Nal(C.Structure):
-    _fields_ = [("naltype", C.c_int), ("tid", C.c_int), ("iSize", C.c_int), ("pts", C.c_longlong), ("pPayload", C.POINTER(C.c_ubyte))]
-
-
-class DevPicture(C.Structure):
-    _fields_ = [("format", C.c_int), ("device", C.c_int), ("plane", C.c_void_p * 3), ("pitch", C.c_int * 3), ("pixel_step", C.c_int),
-                ("matrix", C.c_int), ("full_range", C.c_int), ("stream", C.c_void_p), ("pts", C.c_longlong)]
-
-
-class Roi(C.Structure):
-    _fields_ = [("type", C.c_int), ("log2_block", C.c_int), ("device", C.c_int), ("data", C.c_void_p), ("pitch", C.c_int), ("stream", C.c_void_p)]
+JUNK = dict(step=77, matrix=9, full_range=5)                            # pixel_step, matrix, full_range: ignored by the family
 
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    from oracle_lib import build_oracle
-    build_oracle()
-    d = tmp_path_factory.mktemp("stubyuv")
-    so, log = str(d / "libks265enc_stub.so"), str(d / "calls.log")
-    host = os.path.join(ROOT, "ks265codec_amd", "host")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-fPIC", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"), "-shared", "-o", so,
-                           os.path.join(host, "ks265_enc.c"), os.path.join(host, "ks265_stream.c"), os.path.join(HERE, "hip_stub_yuv.c"),
-                           "-L", os.path.join(ROOT, "oracle"), "-lks265_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-lm"])
-    old = os.environ.get("KS265_STUB_CALL_LOG")
-    os.environ["KS265_STUB_CALL_LOG"] = log                              # read once, at the library's first logged call
-    try:
-        lib = C.CDLL(so)
-        lib.QY265EncoderOpen.restype = C.c_void_p
-        lib.ks265_stub_live.restype = C.c_long
-        lib.QY265EncoderClose(open_handle(lib))                         # (the first logged call)
-    finally:
-        os.environ.pop("KS265_STUB_CALL_LOG", None)
-        if old is not None:
-            os.environ["KS265_STUB_CALL_LOG"] = old
-    lib.call_log_path = log
-    return lib
+    return load_host_lib(build_host_lib("hip_stub_yuv.c"), call_log=str(tmp_path_factory.mktemp("stubyuv") / "calls.log"))
 
 
 def open_handle(lib, params=(), lanes=1, roi=False):
-    old = os.environ.get("KS265_GOP_LANES")
-    os.environ["KS265_GOP_LANES"] = str(lanes)
-    try:
-        cfg = (C.c_uint8 * LAY["sizeof_config"])()
-        assert lib.QY265ConfigDefaultPreset(cfg, b"medium", None, b"default") == 0
-        for k, v in (("wdt", W), ("hgt", H), ("fr", 50), ("rc", 0), ("qp", 34), ("threads", 4), ("log", 1), *params):
-            assert lib.QY265ConfigParse(cfg, k.encode(), str(v).encode()) == 0, k
-        if roi:
-            assert lib.ks265_enc_set_default(b"roi", C.c_int(1)) == 0
-        err = C.c_int(0)
-        h = C.c_void_p(lib.QY265EncoderOpen(cfg, C.byref(err)))
-        if roi:
-            assert lib.ks265_enc_set_default(b"roi", C.c_int(0)) == 0
-        assert h.value, hex(err.value & 0xFFFFFFFF)
-    finally:
-        os.environ.pop("KS265_GOP_LANES", None)
-        if old is not None:
-            os.environ["KS265_GOP_LANES"] = old
-    return h
+    return open_at(lib, W, H, params=params, lanes=lanes, roi=roi)
 
 
-def yuv_pic(bufs, offs, pitches, code, pts=0) -> DevPicture:
-    p = DevPicture()
-    p.format, p.device, p.stream, p.pts = code, 0, None, pts
-    p.pixel_step, p.matrix, p.full_range = 77, 9, 5                     # ignored by the family
-    for k, b in enumerate(bufs):
-        p.plane[k], p.pitch[k] = b.ctypes.data + offs[k], pitches[k]
-    return p
+def yuv_pic(bufs, offs, pitches, code, pts=0):
+    return dev_pic(bufs, offs, pitches, code, pts, **JUNK)
 
 
 def session(lib, pictures, lanes=1, scaled=None, params=()):
@@ -115,37 +48,7 @@ def session(lib, pictures, lanes=1, scaled=None, params=()):
         assert lib.ks265_enc_enable_device_input(h) == QY_OK
     if scaled:
         assert lib.ks265_enc_enable_device_scale(h, scaled[0], scaled[1]) == QY_OK
-    nal, nn, pic, outp, yuv, bs = C.POINTER(Nal)(), C.c_int(0), Picture(), Picture(), YUV(), bytearray()
-    yuv.iWidth, yuv.iHeight = W, H
-    yuv.iStride[0], yuv.iStride[1], yuv.iStride[2] = W, W // 2, W // 2
-    pic.yuv = C.pointer(yuv)
-
-    def collect():
-        bs.extend(b"".join(C.string_at(nal[i].pPayload, nal[i].iSize) for i in range(nn.value) if nal[i].iSize > 0))
-
-    for t, p in enumerate(pictures):
-        if isinstance(p, tuple):
-            bufs = [b.copy() for b in p[0]]
-            d = yuv_pic(bufs, *p[1:], pts=t)
-            if scaled:
-                rc = lib.ks265_enc_encode_device_frame_scaled(h, C.byref(nal), C.byref(nn), C.byref(d), scaled[0], scaled[1], scaled[2], C.byref(outp))
-            else:
-                rc = lib.ks265_enc_encode_device_frame(h, C.byref(nal), C.byref(nn), C.byref(d), C.byref(outp))
-            for b in bufs:
-                b[:] = 0x5A                                             # the picture is the caller's again once the call has returned (the stand-in runs everything inside it)
-        else:
-            for k, off in enumerate((0, W * H, W * H * 5 // 4)):
-                yuv.pData[k] = C.cast(p.ctypes.data + off, C.POINTER(C.c_ubyte))
-            pic.pts = t
-            rc = lib.QY265EncoderEncodeFrame(h, C.byref(nal), C.byref(nn), C.byref(pic), C.byref(outp), 0)
-        assert rc == QY_OK, hex(rc & 0xFFFFFFFF)
-        collect()
-    while lib.QY265EncoderDelayedFrames(h) > 0:
-        assert lib.QY265EncoderEncodeFrame(h, C.byref(nal), C.byref(nn), None, C.byref(outp), 0) == QY_OK
-        collect()
-    lib.QY265EncoderClose(h)
-    assert [lib.ks265_stub_live(k) for k in range(5)] == [0] * 5, "contexts, frame objects, events, device and pinned blocks"
-    return bytes(bs)
+    return drive(lib, h, (device_picture(lib, h, *p, pts=t, scaled=scaled, **JUNK) if isinstance(p, tuple) else host_picture(lib, h, p, W, H, t) for t, p in enumerate(pictures)))
 
 
 def yuv_clip(fmt, w, h, n, seed, front=1, behind=3):
@@ -273,11 +176,8 @@ def test_refusals_enqueue_nothing_and_keep_the_map(lib):
 
 
 @pytest.fixture(scope="module")
-def sanitized(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("yuvsan") / "yuv_stub_main")
-    subprocess.check_call(["gcc", "-O1", "-g", "-std=gnu11", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "include"),
-                           "-o", exe, os.path.join(HERE, "yuv_stub_main.c")])
-    return exe
+def sanitized():
+    return build_host_program("yuv_stub_main.c")
 
 
 @pytest.mark.parametrize("layout,sub", yh.SHAPES, ids=[f"{yh.LAYOUT_NAMES[l]}{yh.SUB_NAMES[s]}" for l, s in yh.SHAPES])
