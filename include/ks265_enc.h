@@ -373,6 +373,45 @@ typedef struct ks265_roi {
     const void *data; int pitch; void *stream;
 } ks265_roi;
 int ks265_enc_set_next_roi(void *pEncoder, const ks265_roi *roi);   /* NULL withdraws */
+/* extension: overlays - a station logo or watermark, burnt-in captions, a timestamp, a picture in picture - blended onto every picture on the GPU as the LAST step on its way
+ * in, in the encoder's own matrix-free terms: the overlay is RGB plus alpha with ITS matrix and range, the picture is the YCbCr the encoder codes (DESIGN.md 4u;
+ * tests/overlay_ref.py is the specification of every byte).  Eight slots, 0 .. 7, blended in ascending slot number where they overlap.  With no overlay set there is no call,
+ * no allocation, no log line and no changed stream byte.
+ *   rgb            the samples, as ks265_enc_encode_device_frame describes an RGB picture: format KS265_IN_RGB / _RGB_F16 / _RGB_BF16 / _RGB_F32, plane[0..2] = the R, G, B
+ *                  sample of pixel (0, 0), pitch[0], pixel_step, matrix, full_range; device = the handle's GPU (read on `stream`) or -1 = host memory; pts is ignored
+ *   width, height  even, 2 .. 8192
+ *   alpha          the alpha sample of pixel (0, 0): the same element type, pixel_step and pitch as the colours (RGBA: rgb.plane[0] + 3 elements' bytes); NULL = opaque
+ *   x, y           the top-left corner in the ENCODER's picture (behind the scaler; picWidth x picHeight): even, any sign, -16384 .. 16384; the part outside is clipped.  On a
+ *                  handle whose size is no multiple of 8 the rectangle is clipped to picWidth x picHeight: the padding keeps the bytes it had
+ *   opacity        0 .. 256 on top of the alpha samples (256 = as they are)
+ *   flags          KS265_OV_FORCED_ONLY: drawn only on pictures whose QY265EncoderEncodeFrame call passed bForceLogo != 0 - the SDK's slot for "this picture carries the
+ *                  logo" - and never for ks265_enc_encode_device_frame[_scaled].  With no such overlay set bForceLogo stays without effect
+ * Float samples count as the 8-bit code nearest to them ([0, 1] the full range, NaN = 0); an opaque overlay is byte for byte what the encoder's own RGB conversion makes of it;
+ * chroma is filtered from premultiplied samples, so the colour of transparent pixels never bleeds in.
+ *   ks265_enc_set_overlay  sets, replaces or (ov = NULL) clears a slot.  In force from the NEXT picture handed in, by either entry point, until replaced or cleared; pictures
+ *       handed in before keep what they had.  The set travels with the picture: one GOP lane and several give the same bytes.  Validated at once; on any refusal the slot keeps
+ *       what it had:  QY_POINTER - a NULL handle or channel, or a device overlay whose extent (every channel's, alpha's included: [p, p + pitch (height - 1) + row bytes)) does
+ *       not lie inside one device allocation of the handle's GPU;  QY_NOTSUPPORTED - slot, size, parity, position, opacity, flags, format, pixel step or matrix outside the
+ *       list, rgb.device neither -1 nor the handle's GPU, GOP lanes on several GPUs, the KS265_GRAPH experiment, a device library without ks265_input_overlay (one log line
+ *       `ks265enc: overlays are unavailable: ...`);  QY_OUTOFMEMORY.  With overlays in force every input slot needs a twin in device memory, as the vpp_* filters arrange at
+ *       open: a handle that has none yet (no lookahead, no filter, no device input) gets them inside the first ks265_enc_set_overlay call that sets an overlay, which therefore
+ *       wants no picture in flight - before the first picture, on a zero-latency handle, or after a flush; else QY_NOTSUPPORTED with a log line.
+ * CONTRACT: a DEVICE overlay is read in place inside every encode call, in the order of ov->rgb.stream, as ks265_dev_picture's planes are: the caller may rewrite it with work
+ * on that stream as soon as an encode call returns - that is how captions animate, with no host synchronisation - and it must stay allocated until the slot is cleared or
+ * replaced and the pictures handed in before that have been read (a flush, or a synchronisation of that stream after the next encode call).  A HOST overlay (device = -1) is
+ * copied inside the set call into device memory the handle owns - the buffer is the caller's again on return - shared read-only by the lanes and freed at clear, replace and
+ * close; its channels are those of ONE buffer (everything between the lowest and the highest of them is copied: at most four planes apart, else QY_NOTSUPPORTED).
+ * What sees the overlay: everything behind the input - lookahead, -aq, cuTree, -psnr / -ssim (against the overlaid picture), `analysis`, `devrecon`, the hash.  What does not:
+ * the vpp_* filters, which run in front of it, and the denoiser's history - a logo is never smeared into later pictures. */
+typedef struct ks265_overlay {
+    ks265_dev_picture rgb;                     /* device = -1: host memory; pts ignored */
+    int width, height;
+    const void *alpha;                         /* NULL = opaque */
+    int x, y, opacity /* 0 .. 256 */, flags;
+} ks265_overlay;
+#define KS265_OV_FORCED_ONLY 1
+#define KS265_OV_SLOTS 8
+int ks265_enc_set_overlay(void *pEncoder, int slot /* 0 .. 7 */, const ks265_overlay *ov /* NULL clears the slot */);
 /* extension: write the reconstruction (I420, display order) to `path` - the reference CLI's `-o`; call between Open and the first picture */
 int ks265_enc_set_recon_file(void *pEncoder, const char *path);
 

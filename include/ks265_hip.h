@@ -260,6 +260,28 @@ typedef struct ks265_hdr_cfg { int32_t gain, iters, slope, radius[3]; } ks265_hd
 int ks265_input_hdr_validate(ks265_ctx *, const ks265_hdr_cfg *, int width, int height);
 size_t ks265_input_hdr_work_bytes(int width, int height);
 int ks265_input_hdr(ks265_ctx *, const ks265_hdr_cfg *, int width, int height, uint8_t *dev_i420 /* luma in and out */, void *dev_work, size_t work_bytes);
+/* Overlays on the way in (input_overlay.hip; tests/overlay_ref.py is the specification of every byte): up to 8 pictures of RGB plus alpha - a logo, captions, a
+ * timestamp, a picture in picture - blended IN PLACE onto the packed I420 picture of coded_w x coded_h (positive multiples of 8, at most 8192) by ONE launch on the context's
+ * stream, however many there are; the descriptors travel by value as the kernel's argument (no upload, no allocation, no state).
+ *   rgb            the overlay's samples, described as ks265_input_convert's RGB sources are: format KS265_IN_RGB / _RGB_F16 / _RGB_BF16 / _RGB_F32, width and height (even,
+ *                  2 .. 8192), plane[0..2] = the R, G, B sample of pixel (0, 0), pitch[0], pixel_step, matrix, full_range - the overlay's own, whatever the picture came in as
+ *   alpha          the alpha sample of pixel (0, 0): the same element type, pixel_step and pitch[0] as the colours (RGBA: the fourth element); NULL = opaque
+ *   x, y           where the overlay's top-left corner lies in the picture: even, any sign, |x|, |y| <= 16384; what lies outside the window is clipped
+ *   opacity        0 .. 256, on top of the alpha samples: A = (a * opacity + 128) >> 8
+ *   win_w, win_h   the window the overlays are clipped to: even, 2 .. coded_w / coded_h.  On a picture whose size is no multiple of 8 this is picWidth x picHeight: the
+ *                  padding right of and below it keeps the bytes it had
+ * Float samples are reduced to 8-bit codes first, (q + 128) >> 8 of ks265_input_convert's q: a float32 overlay u8 / 255 gives byte for byte what the u8 overlay gives.  Luma is
+ * blended sample by sample, Y' = (Y (255 - A) + A Yov) / 255 rounded once in Q16; chroma from PREMULTIPLIED (1, 2, 1) x (1, 1) sums of A, A R, A G, A B at HEVC's default
+ * siting, taken over the overlay as a picture of its own (columns clamp to ITS edges; the sums never read the picture, so clipping changes no sample that remains, and the
+ * colour of a transparent pixel never bleeds in).  An opaque overlay gives exactly ks265_input_convert's bytes; alpha or opacity 0 changes nothing.  The overlays are blended in
+ * the order of the array where they overlap.  A thread outside every rectangle touches no memory; nothing outside the picture and the overlays' extents is read or written.
+ * Pointers are judged as ks265_input_validate judges a source - every channel's whole extent, alpha's included, inside ONE allocation on the context's device, the picture's
+ * coded_w x coded_h x 3 / 2 bytes likewise: KS265_POINTER; n outside 1 .. 8, sizes, parity, positions, opacity, formats, steps, a matrix outside the list, a picture that is not
+ * 16-byte aligned: KS265_NOTSUPPORTED.  A refused call enqueues nothing.  ks265_input_overlay_validate enqueues nothing and judges everything but the picture's pointer. */
+typedef struct ks265_overlay_desc { ks265_in_desc rgb; const void *alpha; int32_t x, y, opacity; } ks265_overlay_desc;
+#define KS265_OVERLAY_MAX 8
+int ks265_input_overlay_validate(ks265_ctx *, const ks265_overlay_desc *ov, int n, int coded_w, int coded_h, int win_w, int win_h);
+int ks265_input_overlay(ks265_ctx *, const ks265_overlay_desc *ov, int n /* 1 .. 8 */, int coded_w, int coded_h, int win_w, int win_h, uint8_t *dev_i420);
 /* Launch sequences as graphs: between ks265_capture_begin and ks265_capture_end everything enqueued on this context's stream by THIS thread (kernel launches,
  * async memsets of the stage functions) is recorded instead of run (hipStreamBeginCapture, relaxed mode: other threads may go on using the runtime);
  * ks265_capture_end returns an executable graph, ks265_graph_launch enqueues all of it with one runtime call.  A host whose pictures repeat the same

@@ -78,6 +78,14 @@ template <typename T> __device__ inline uint32_t shr_clip255(T v, int sh)
     if constexpr (std::is_signed<T>::value) v = v < 0 ? 0 : v;          // (two steps, the upper bound last: written as one nested conditional it compiles to compare + select + min)
     return (uint32_t)((typename std::make_unsigned<T>::type)(v > hi ? hi : v) >> sh);
 }
+// the same rule where a constant divides as well: clip255(floor(v / (DEN << sh))) of a 64-bit v - the clamp to [0, 256 DEN << sh) in front of the shift, and what remains
+// (below 256 DEN, 32 bits) divided by the constant.  floor(floor(v / 2^sh) / DEN) = floor(v / (DEN 2^sh)) for v >= 0; a negative v clips to 0 either way
+template <int DEN> __device__ inline uint32_t shr_div_clip255(long long v, int sh)
+{
+    const long long hi = ((long long)(256 * DEN) << sh) - 1;
+    v = v < 0 ? 0 : v;
+    return (uint32_t)((unsigned long long)(v > hi ? hi : v) >> sh) / (uint32_t)DEN;
+}
 
 // ---- float RGB samples (KS265_IN_RGB_F16 / _BF16 / _F32; tests/yuv_float_ref.py is the specification).  Nothing here may be built with fast-math
 template <int FMT> struct FElem { typedef uint16_t type; };

@@ -61,7 +61,13 @@ hdr=True switches on the local-contrast filter of THIS handle (`vpp_hdr`, includ
 iterations of an edge-preserving smoother (the domain transform, exact in integers) and the detail above it amplified - contrast at large scale without halos at strong
 edges - as a stateless GPU step between the denoiser and the enhancement, for every format and for scale=.  hdr_strength=S (0 .. 5: the detail's gain), hdr_iter=2|3,
 hdr_sigma_s=V (0 .. 100: the spatial scale in samples), hdr_sigma_r=V (0 .. 100: the range scale in per cent of the 8-bit range); one left out or 0 takes the default 1.0 / 3 /
-20 / 15.  The defaults are untuned choices; chroma is not touched; PSNR is against the filtered picture."""
+20 / 15.  The defaults are untuned choices; chroma is not touched; PSNR is against the filtered picture.
+
+enc.set_overlay(slot, tensor, x=0, y=0, opacity=1.0, format="rgba") blends a GPU tensor of RGB plus alpha onto every picture from the next encode() on (`ks265_enc_set_overlay`,
+include/ks265_enc.h; tests/overlay_ref.py is the specification): a logo, captions, a timestamp, a picture in picture.  Eight slots, later slots on top; x, y even, any sign, in the
+encoder's picture, the part outside is clipped.  The tensor is read in place inside every encode(), in the order of torch's stream current at the set call: rewrite it on that
+stream as soon as encode() returns and the next picture carries the new caption.  It is blended behind the filters above - they never see it - and in front of everything else:
+recon(), analysis() and quality() see the overlaid picture.  enc.set_overlay(slot, None) clears the slot."""
 from __future__ import annotations
 
 import ctypes as C
@@ -104,6 +110,17 @@ class DevAnalysis(C.Structure):
     _fields_ = [("device", C.c_int), ("stream", C.c_void_p), ("mv", AnField), ("ref", AnField), ("cu", AnField), ("qp", AnField), ("sse", AnField)]
 
 
+class Overlay(C.Structure):
+    """ks265_overlay of include/ks265_enc.h"""
+    _fields_ = [("rgb", DevPicture), ("width", C.c_int), ("height", C.c_int), ("alpha", C.c_void_p), ("x", C.c_int), ("y", C.c_int), ("opacity", C.c_int), ("flags", C.c_int)]
+
+
+OV_FORCED_ONLY, OV_SLOTS = 1, 8
+# overlay format name -> (planar, element of R, G, B, alpha or None)
+_OVERLAY_FORMATS = {"rgba": (False, 0, 1, 2, 3), "bgra": (False, 2, 1, 0, 3), "rgb": (False, 0, 1, 2, None), "bgr": (False, 2, 1, 0, None),
+                    "rgb_planar": (True, 0, 1, 2, None), "rgba_planar": (True, 0, 1, 2, 3)}
+
+
 class Roi(C.Structure):
     """ks265_roi of include/ks265_enc.h"""
     _fields_ = [("type", C.c_int), ("log2_block", C.c_int), ("device", C.c_int), ("data", C.c_void_p), ("pitch", C.c_int), ("stream", C.c_void_p)]
@@ -142,6 +159,7 @@ def library() -> C.CDLL:
         _lib.ks265_enc_device_recon_pending.argtypes = [C.c_void_p]
         _lib.ks265_enc_get_device_recon.argtypes = [C.c_void_p, C.POINTER(DevPicture), C.c_void_p]
         _lib.ks265_enc_set_next_roi.argtypes = [C.c_void_p, C.POINTER(Roi)]
+        _lib.ks265_enc_set_overlay.argtypes = [C.c_void_p, C.c_int, C.POINTER(Overlay)]
         _lib.ks265_enc_device_analysis_pending.argtypes = [C.c_void_p]
         _lib.ks265_enc_get_device_analysis.argtypes = [C.c_void_p, C.POINTER(DevAnalysis), C.c_void_p]
         _lib.ks265_enc_enable_device_scale.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -257,6 +275,41 @@ def describe(t, format: str, matrix: int = MATRIX_BT709, full_range: bool = Fals
     return p
 
 
+def describe_overlay(t, format: str = "rgba", x: int = 0, y: int = 0, opacity: float = 1.0, matrix: int = MATRIX_BT709, full_range: bool = False, forced_only: bool = False) -> Overlay:
+    """the ks265_overlay of a GPU tensor (no copy: its storage, its strides; read on torch's current stream): (H, W, 3 | 4) for "rgb" | "bgr" | "rgba" | "bgra" - in a
+    four-element pixel without alpha the fourth element is ignored - or (3 | 4, H, W) for "rgb_planar" | "rgba_planar"; uint8, or float16 / bfloat16 / float32 in [0, 1].  One
+    row stride and one column stride serve all channels, so a tensor's own strides always do.  opacity 0 .. 1 (in 1/256)"""
+    import torch
+    if format not in _OVERLAY_FORMATS:
+        raise ValueError(f"format: one of {sorted(_OVERLAY_FORMATS)}")
+    if not isinstance(t, torch.Tensor) or t.dtype not in (torch.uint8, torch.float16, torch.bfloat16, torch.float32) or t.device.type != "cuda" or t.dim() != 3:
+        raise ValueError("an overlay is a 3-D uint8, float16, bfloat16 or float32 tensor on the GPU")
+    planar, r, g, b, a = _OVERLAY_FORMATS[format]
+    need = 1 + max(r, g, b, a or 0)
+    if planar:
+        if t.shape[0] != need:
+            raise ValueError(f"{format}: a ({need}, H, W) tensor")
+        h, w, row, col, chan = t.shape[1], t.shape[2], t.stride(1), t.stride(2), t.stride(0)
+    else:
+        if t.shape[2] < need or t.shape[2] > 4:
+            raise ValueError(f"{format}: an (H, W, {need}{' | 4' if need == 3 else ''}) tensor")
+        h, w, row, col, chan = t.shape[0], t.shape[1], t.stride(0), t.stride(1), t.stride(2)
+    if min(row, col, chan) < 1 or row < w * col:
+        raise ValueError(f"{format}: positive strides, rows that do not overlap")
+    if not 0.0 <= float(opacity) <= 1.0:
+        raise ValueError("opacity: 0 .. 1")
+    es, base = t.element_size(), t.data_ptr()
+    o = Overlay()
+    o.rgb.format, o.rgb.device = _rgb_code(t.dtype), t.device.index if t.device.index is not None else torch.cuda.current_device()
+    for k, c in enumerate((r, g, b)):
+        o.rgb.plane[k] = base + c * chan * es
+    o.rgb.pitch[0], o.rgb.pixel_step, o.rgb.matrix, o.rgb.full_range = row * es, col * es, matrix, int(bool(full_range))
+    o.rgb.stream = torch.cuda.current_stream(t.device).cuda_stream
+    o.width, o.height, o.alpha = w, h, (base + a * chan * es if a is not None else None)
+    o.x, o.y, o.opacity, o.flags = int(x), int(y), int(round(float(opacity) * 256)), OV_FORCED_ONLY if forced_only else 0
+    return o
+
+
 def describe_roi(m, block: int = 16) -> Roi:
     """the ks265_roi of a 2-D int8 / float32 map with unit column stride: a GPU tensor (no copy; read on torch's current stream) or a NumPy array in host memory"""
     import numpy as np
@@ -356,6 +409,7 @@ class Encoder:
                 self.close()
                 raise EncoderError("recon=: device reconstruction is unavailable on this handle (see the log)", QY_NOTSUPPORTED)
         self._flushed_an = []                                   # analysis(): what flush() fetched call by call
+        self._overlays = {}                                     # set_overlay(): slot -> the tensor, kept alive while the encoder reads it
         if self._analysis:                                      # refused at open?  Nothing is pending: QY_FAIL if the switch is on
             probe = DevAnalysis()
             probe.device = int(os.environ.get("KS265_DEVICE", "0"))
@@ -399,6 +453,25 @@ class Encoder:
                 self.lib.ks265_enc_set_next_roi(self.h, None)       # a picture refused before it was handed in has not taken its map: withdrawn
             raise EncoderError(f"ks265_enc_encode_device_frame_scaled: picture {shape[1]}x{shape[0]}, encoder {self.width}x{self.height}" if scaled else "ks265_enc_encode_device_frame", rc)
         return self._take()
+
+    def set_overlay(self, slot: int, tensor, x: int = 0, y: int = 0, opacity: float = 1.0, format: str = "rgba", matrix: int = MATRIX_BT709, full_range: bool = False,
+                    forced_only: bool = False) -> None:
+        """slot 0 .. 7 blends `tensor` (describe_overlay) onto every picture from the next encode() on, its top-left corner at (x, y) of the encoder's picture; None clears
+        the slot.  The tensor is read in place inside every encode() in the order of torch's stream current NOW: rewrite it there as soon as an encode() has returned.
+        forced_only: KS265_OV_FORCED_ONLY - drawn for host pictures handed in with bForceLogo alone, so never for encode()'s tensors.  A refused overlay (ValueError for what
+        this module can see, EncoderError for the library's codes) leaves the slot as it was"""
+        if self.h is None:
+            raise RuntimeError("encoder closed")
+        if tensor is None:
+            rc = self.lib.ks265_enc_set_overlay(self.h, int(slot), None)
+        else:
+            rc = self.lib.ks265_enc_set_overlay(self.h, int(slot), C.byref(describe_overlay(tensor, format, x, y, opacity, matrix, full_range, forced_only)))
+        if rc != QY_OK:
+            raise EncoderError(f"ks265_enc_set_overlay(slot {slot})", rc)
+        # (the tensor it replaces may go: every read of it was enqueued inside an encode() that put the tensor's stream behind that read before it returned)
+        self._overlays.pop(int(slot), None)
+        if tensor is not None:
+            self._overlays[int(slot)] = tensor
 
     def flush(self) -> bytes:
         out = bytearray()

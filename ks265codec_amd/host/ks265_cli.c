@@ -13,6 +13,8 @@
 #include <pthread.h>
 /* -roi reaches the entry behind it as a weak symbol: an encoder library without it leaves it NULL, and the option is ignored with a line */
 #pragma weak ks265_enc_set_next_roi
+/* -logo likewise: without the entry the option is refused */
+#pragma weak ks265_enc_set_overlay
 
 static double now_ms(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec * 1e3 + t.tv_nsec * 1e-6; }
 
@@ -59,7 +61,7 @@ static void usage(void)
 {
     puts("usage: ks265enc -i in.yuv -wdt W -hgt H [-fr FPS] [-preset ultrafast..placebo] [-latency zerolatency|lowdelay|livestreaming|default] [-tune T]\n"
          "                [-rc 0..5] [-qp Q] [-crf C] [-br KBPS] [-iper N] [-bframes N] [-frms N] [-threads N] [-psnr 0|1|2] [-ssim 0|1|2] [-b out.265] [-o recon.yuv]\n"
-         "                [-me 0|1|2] [-subme 0|1|2] [-merange R] [-ref N] [-sao 0..4] [-sao-ref 0|1|2 (the reference's SAO decision: 1 = as -sao 3, 2 = with its left / up merge candidates)] [-df 0|1] [-fixqp 0|1] [-md5 0|1] [-scenecut N (with -lookahead: the reference's scene-cut rule at threshold N)] [-cutree 0|1 (-rc 3: the reference's macroblock tree over the lookahead, a QP per CTU; default 1)] [-gpb 0|1 (anchors of the B-picture GOPs that search two or more past anchors go out as B slices over them; default 0)] [-hash 0|2|3 (a decoded picture hash SEI message behind every picture: 2 = CRC, 3 = checksum; default 0)] [-aq 0|1 -aqs S (adaptive quantisation: a QP per CTU from the reference's block-variance rule)] [-roi x:y:w:h:dqp (up to 8 times: dqp is added to the QP of the CTUs under the rectangle, in luma samples, for the whole stream; later rectangles win)] [-denoise 0..3 (a motion-compensated temporal filter on the GPU in front of the encoder: 1 gentle, 2 medium, 3 aggressive; default 0) -recur V (its blend weight in 1/32, 0 .. 30; alone: at the medium threshold)] [-edge 0..3 -color 0..3 (edge / colour enhancement on the GPU in front of the encoder, behind the denoiser: 1 gentle, 2 medium, 3 aggressive; default 0)] [-hdr 0|1 -hdr-strength S -hdr-iter N -hdr-sigma-s V -hdr-sigma-r V (local contrast on the GPU in front of the encoder, between the denoiser and the enhancement: the luma's detail above an edge-preserving base times S (0 .. 5), N = 2 or 3 iterations, spatial sigma in samples and range sigma in per cent of the 8-bit range (each 0 .. 100); a value left out or 0: 1.0 / 3 / 20 / 15; default off)] [-c config_file] [-gpus N] [-v]\n"
+         "                [-me 0|1|2] [-subme 0|1|2] [-merange R] [-ref N] [-sao 0..4] [-sao-ref 0|1|2 (the reference's SAO decision: 1 = as -sao 3, 2 = with its left / up merge candidates)] [-df 0|1] [-fixqp 0|1] [-md5 0|1] [-scenecut N (with -lookahead: the reference's scene-cut rule at threshold N)] [-cutree 0|1 (-rc 3: the reference's macroblock tree over the lookahead, a QP per CTU; default 1)] [-gpb 0|1 (anchors of the B-picture GOPs that search two or more past anchors go out as B slices over them; default 0)] [-hash 0|2|3 (a decoded picture hash SEI message behind every picture: 2 = CRC, 3 = checksum; default 0)] [-aq 0|1 -aqs S (adaptive quantisation: a QP per CTU from the reference's block-variance rule)] [-roi x:y:w:h:dqp (up to 8 times: dqp is added to the QP of the CTUs under the rectangle, in luma samples, for the whole stream; later rectangles win)] [-denoise 0..3 (a motion-compensated temporal filter on the GPU in front of the encoder: 1 gentle, 2 medium, 3 aggressive; default 0) -recur V (its blend weight in 1/32, 0 .. 30; alone: at the medium threshold)] [-edge 0..3 -color 0..3 (edge / colour enhancement on the GPU in front of the encoder, behind the denoiser: 1 gentle, 2 medium, 3 aggressive; default 0)] [-hdr 0|1 -hdr-strength S -hdr-iter N -hdr-sigma-s V -hdr-sigma-r V (local contrast on the GPU in front of the encoder, between the denoiser and the enhancement: the luma's detail above an edge-preserving base times S (0 .. 5), N = 2 or 3 iterations, spatial sigma in samples and range sigma in per cent of the 8-bit range (each 0 .. 100); a value left out or 0: 1.0 / 3 / 20 / 15; default off)] [-logo file:w:h:x:y[:opacity] (a raw file of w x h pixels of R G B A bytes blended onto every picture on the GPU, its top-left corner at (x, y) - all four even, the part outside the picture is clipped - at opacity 0 .. 256, default 256)] [-c config_file] [-gpus N] [-v]\n"
          "  I420 8-bit input of W x H; width and height even (a size that is no multiple of 8 is coded at the next one, with a conformance window;\n"
          "  -o then writes W x H pictures).  Needs one MI355X (gfx950): there is no CPU fallback.");
 }
@@ -104,6 +106,7 @@ int main(int argc, char **argv)
     const char *rec_path = NULL;
     int frames = -1;
     ks265_roi_rect roi_rect[KS265_ROI_MAX_RECTS]; int nroi = 0;
+    const char *logo = NULL;
     /* two passes over the arguments: preset / latency / tune first (they reset every field), then the explicit settings */
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "-v")) { printf("%s\n", strLibQy265Version); return 0; }
@@ -137,6 +140,7 @@ int main(int argc, char **argv)
             ++nroi;
             if (ks265_enc_set_default("roi", 1) != QY_OK) return 2;
         }
+        else if (!strcmp(a, "-logo")) logo = v;                                              /* an overlay for the whole stream (ks265_enc.h ks265_enc_set_overlay), slot 0 */
         else if (!strcmp(a, "-gpus")) setenv("KS265_GPUS", v, 1);                            /* closed GOPs dealt to N GPUs behind this one handle (ks265_enc.h) */
         else {
             const int r = QY265ConfigParse(&cfg, a + 1, v);
@@ -156,6 +160,23 @@ int main(int argc, char **argv)
     void *h = QY265EncoderOpen(&cfg, &err);
     if (!h) { fprintf(stderr, "QY265EncoderOpen failed: 0x%08x\n", (unsigned)err); return 1; }
     if (rec_path && ks265_enc_set_recon_file(h, rec_path) != QY_OK) { fprintf(stderr, "cannot write the reconstruction to %s\n", rec_path); return 1; }
+    if (logo) {                                                         /* -logo file:w:h:x:y[:opacity]: read whole, handed over as a host overlay (copied inside the call) */
+        char path[1024], tail; int lw, lh, lx, ly, op = 256;
+        const int got = sscanf(logo, "%1023[^:]:%d:%d:%d:%d:%d%c", path, &lw, &lh, &lx, &ly, &op, &tail);
+        if ((got != 5 && got != 6) || lw < 2 || lh < 2 || lw > 8192 || lh > 8192) { fprintf(stderr, "bad value for -logo: %s (file:w:h:x:y[:opacity])\n", logo); return 2; }
+        const size_t lsz = (size_t)lw * lh * 4;
+        unsigned char *px = (unsigned char *)malloc(lsz);
+        FILE *fl = fopen(path, "rb");
+        if (!px || !fl || fread(px, 1, lsz, fl) != lsz) { fprintf(stderr, "-logo: cannot read %d x %d RGBA pixels from %s\n", lw, lh, path); return 1; }
+        fclose(fl);
+        ks265_overlay ov;
+        memset(&ov, 0, sizeof ov);
+        ov.rgb.format = KS265_IN_RGB; ov.rgb.device = -1; ov.rgb.plane[0] = px; ov.rgb.plane[1] = px + 1; ov.rgb.plane[2] = px + 2; ov.rgb.pitch[0] = 4 * lw; ov.rgb.pixel_step = 4;
+        ov.width = lw; ov.height = lh; ov.alpha = px + 3; ov.x = lx; ov.y = ly; ov.opacity = op;
+        err = ks265_enc_set_overlay ? ks265_enc_set_overlay(h, 0, &ov) : QY_NOTSUPPORTED;
+        free(px);
+        if (err) { fprintf(stderr, "-logo: the overlay was refused: 0x%08x\n", (unsigned)err); return 1; }
+    }
     const size_t luma = (size_t)cfg.picWidth * cfg.picHeight, fsz = luma * 3 / 2;
     /* -roi: the rectangles rasterised once at 16 x 16 into an int8 map in host memory, handed in with every picture */
     ks265_roi roi = {KS265_ROI_INT8, KS265_ROI_RECT_LOG2, -1, NULL, ks265_roi_map_cols(cfg.picWidth, KS265_ROI_RECT_LOG2), NULL};

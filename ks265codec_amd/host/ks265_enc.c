@@ -81,6 +81,10 @@
 #pragma weak ks265_input_hdr_validate
 #pragma weak ks265_input_hdr_work_bytes
 #pragma weak ks265_input_hdr
+/* overlays (ks265_enc_set_overlay, ks265_enc.h): the blend behind everything else on the way in.  Against a device library without the two entries the setter is
+ * QY_NOTSUPPORTED with one log line */
+#pragma weak ks265_input_overlay_validate
+#pragma weak ks265_input_overlay
 
 const char strLibQy265Version[] = "ks265enc 0.2 (MI355X pixel path + host CABAC; API of libqycodec V2.6.1.3)";
 
@@ -2690,7 +2694,11 @@ static int lane_pad_slot(Enc *e, Input *slot)
  * runs what `how` says and decides nothing again.  how: a host picture (yuv); a device picture (dp, validated; d: the operation's view of it) converted / padded (a ragged lane) /
  * scaled (d at the source's size; sc: kept by the lane this picture goes to, any context of the device may run it) into the slot's twin.  roi: the pending map or NULL */
 enum { PIC_HOST, PIC_CONVERT, PIC_PAD, PIC_SCALE };
-typedef struct PicIn { int how; long long pts; const QY265YUV *yuv; const ks265_dev_picture *dp; ks265_in_desc d; const struct ScalePlan *sc; const ks265_roi *roi; } PicIn;
+/* the overlays in force for one picture (top_encode: the handle's slots in ascending number, without the forced-only ones unless the call forced them), as the device
+ * library takes them, and the caller's streams the device overlays among them are read in the order of (each once; nst = 0: host overlays only) */
+typedef struct OvSet { int n, nst; ks265_overlay_desc d[KS265_OV_SLOTS]; void *stream[KS265_OV_SLOTS]; } OvSet;
+typedef struct PicIn { int how; long long pts; const QY265YUV *yuv; const ks265_dev_picture *dp; ks265_in_desc d; const struct ScalePlan *sc; const ks265_roi *roi;
+                       int force_logo; const OvSet *ovs; /* bForceLogo of the call; the overlays or NULL (top_encode) */ } PicIn;
 /* back-pressure on the input side (mu held): at most 16 pictures wait for the scheduler thread (it may itself be waiting for ring space, which only the caller's take_output
  * frees - then go on and collect).  GOP lanes (multi): the input slots are the limit (lane_has_slot) - a lane takes a whole GOP in while it is still coding the previous one, or
  * the caller would wait here while the other lanes run dry.  cuTree: the scheduler itself holds a mini-GOP back until its window has arrived - that many more may wait */
@@ -2813,6 +2821,19 @@ static int stage_enhance(Enc *e, Input *slot)
     slot->up_sync = 0;
     return r;
 }
+/* overlays (ks265_enc_set_overlay): the picture's set is blended onto the slot's twin by one launch on ctx_up, the last step in front of the encoder - behind the filters, so
+ * neither they nor the denoiser's history ever see it - inside the bracket of every caller's stream a device overlay is read in the order of, and ev_up is recorded again
+ * behind it (up_sync off, as behind its neighbours).  The window is the caller's picture: a ragged lane's padding keeps its bytes */
+static int stage_overlay(Enc *e, Input *slot, const OvSet *ovs)
+{
+    int r = KS265_OK;
+    for (int k = 0; k < ovs->nst && !r; ++k) r = caller_stream_in(e, ovs->stream[k]);
+    if (!r) r = ks265_input_overlay(e->ctx_up, ovs->d, ovs->n, e->W, e->H, e->srcW, e->srcH, slot->dev);
+    if (!r) r = ks265_event_record(e->ctx_up, slot->ev_up);
+    for (int k = 0; k < ovs->nst && !r; ++k) r = ks265_external_wait_event(e->ctx_up, ovs->stream[k], slot->ev_up);
+    slot->up_sync = 0;
+    return r;
+}
 /* the picture's own fields travel with it from now, and it goes on to the scheduler thread - at once, or with the lookahead when its results are there (la_drain).  A QY code */
 static int publish_input(Enc *e, Input *slot, long long pts, int key)
 {
@@ -2849,6 +2870,7 @@ static int lane_put(Enc *e, const PicIn *p, int key)
     if (!r && e->dn_on) r = stage_denoise(e, slot, key);
     if (!r && e->hdr_on) r = stage_hdr(e, slot);
     if (!r && e->en_on) r = stage_enhance(e, slot);
+    if (!r && p->ovs) r = stage_overlay(e, slot, p->ovs);
     if (r) { e->pending_up = NULL; r = hip_rc(r); }                    /* (nothing of a failed picture is waited for) */
     else r = publish_input(e, slot, p->pts, key);
     if (r) return input_fail(e, slot, r);
@@ -2976,6 +2998,10 @@ typedef struct Top {
     TopWake wake;
     ReconList handed;                                                /* `devrecon`: the reconstructions the last call handed out, in the order of its NAL units (ks265_recon.h) */
     ks265_roi roi; int roi_set;                                      /* `roi`: the map of the next picture handed in (ks265_enc_set_next_roi) */
+    /* overlays (ks265_enc_set_overlay): the slots - d: as the device library takes it (a host overlay: pointing into `own`, its copy in device memory on lane 0's GPU, which
+     * all lanes share read-only), stream: the caller's, for a device overlay - and the set built from them for the picture being handed in */
+    struct OvSlot { int on, dev, forced_only; ks265_overlay_desc d; void *stream; void *own; } ov[KS265_OV_SLOTS];
+    int ov_n, ov_warned; OvSet ovs;
 } Top;
 
 /* `devrecon`: what take_output just moved out of lane e's ring (Enc::taken) joins `dst` - the handle's list: the slots are handed out; a chunk's stash: they go on travelling.
@@ -3248,6 +3274,18 @@ void *QY265EncoderOpen(QY265EncConfig *cfg, int *err)
     return t;
 }
 
+/* a slot is emptied: what pictures in flight still read of a host overlay's copy is waited for (every lane's upload stream), then the copy goes */
+static void overlay_drop(Top *t, int k)
+{
+    struct OvSlot *o = &t->ov[k];
+    if (o->own) {
+        for (int i = 0; i < t->nlanes; ++i) if (t->lane[i]->ctx_up) (void)ks265_synchronize(t->lane[i]->ctx_up);
+        ks265_dev_free(main_ctx(t->lane[0]), o->own);
+    }
+    if (o->on) --t->ov_n;
+    memset(o, 0, sizeof *o);
+}
+
 void QY265EncoderClose(void *h)
 {
     Top *t = (Top *)h;
@@ -3261,6 +3299,7 @@ void QY265EncoderClose(void *h)
         run_summary(e0, st.frames, st.bytes, st.sse, hi, lo);
     }
     recon_release(t);
+    for (int k = 0; k < KS265_OV_SLOTS; ++k) overlay_drop(t, k);         /* (the host overlays' copies, behind the pictures that read them) */
     for (int i = 0; i < t->nlanes; ++i) lane_close(t->lane[i], t->nlanes == 1);
     recon_list_free(&t->handed);
     pthread_mutex_destroy(&t->wake.mu); pthread_cond_destroy(&t->wake.cv);
@@ -3302,11 +3341,28 @@ int QY265EncoderDelayedFrames(void *h)
 /* the lane the NEXT picture goes to: a new GOP starts on the next lane (top_encode, ks265_enc_acquire_input, ks265_enc_encode_device_frame_scaled) */
 static int top_next_lane(const Top *t) { return t->nlanes == 1 ? 0 : (t->chunk_left <= 0 || t->key_request) ? (t->cur_lane + 1) % t->nlanes : t->cur_lane; }
 
+/* the overlays of the picture being handed in: the slots that are set, ascending, a forced-only one if the call forced the logo; p->ovs stays NULL if that leaves none */
+static void top_overlay_set(Top *t, PicIn *p)
+{
+    OvSet *s = &t->ovs;
+    s->n = s->nst = 0;
+    for (int k = 0; k < KS265_OV_SLOTS; ++k) {
+        const struct OvSlot *o = &t->ov[k];
+        if (!o->on || (o->forced_only && !p->force_logo)) continue;
+        s->d[s->n++] = o->d;
+        int seen = !o->dev;
+        for (int j = 0; j < s->nst && !seen; ++j) seen = s->stream[j] == o->stream;
+        if (!seen) s->stream[s->nst++] = o->stream;
+    }
+    if (s->n) p->ovs = s;
+}
+
 /* one call of the API: a picture (p) or, NULL, the flush */
 static int top_encode(Top *t, QY265Nal **pNals, int *iNalCount, PicIn *p, QY265Picture *out)
 {
     recon_release(t);                                                 /* `devrecon`: the previous call's reconstructions are the pool's again */
     if (p) { p->roi = t->roi_set ? &t->roi : NULL; t->roi_set = 0; }    /* `roi`: the pending map goes with this picture - whatever becomes of the call, nothing stays pending (a flush: it stays) */
+    if (p && t->ov_n) top_overlay_set(t, p);                            /* overlays: the set in force goes with this picture, into whichever lane takes it */
     if (t->nlanes == 1) {
         const int r1 = lane_encode_frame(t->lane[0], pNals, iNalCount, p, out);
         const int rr = t->lane[0]->pool_on ? recon_taken(t, t->lane[0], NULL, &t->handed) : QY_OK;
@@ -3363,10 +3419,9 @@ static int top_encode(Top *t, QY265Nal **pNals, int *iNalCount, PicIn *p, QY265P
 
 int QY265EncoderEncodeFrame(void *h, QY265Nal **pNals, int *iNalCount, QY265Picture *in, QY265Picture *out, int bForceLogo)
 {
-    (void)bForceLogo;
     Top *t = (Top *)h;
     if (!t || !pNals || !iNalCount) return QY_POINTER;
-    PicIn p = {.how = PIC_HOST, .yuv = in ? in->yuv : NULL, .pts = in ? in->pts : 0};
+    PicIn p = {.how = PIC_HOST, .yuv = in ? in->yuv : NULL, .pts = in ? in->pts : 0, .force_logo = bForceLogo != 0};   /* (bForceLogo: KS265_OV_FORCED_ONLY overlays alone look at it) */
     return top_encode(t, pNals, iNalCount, in ? &p : NULL, out);
 }
 
@@ -3423,9 +3478,8 @@ int ks265_enc_acquire_input(void *h, QY265YUV *yuv)
 
 /* every input slot of the lane gets a device twin (and the event behind its filling) if it has none yet, and the lane a stream for filling them: the lookahead's when there is one
  * (its analysis reads the twin right after), else the pixel path's - no stream more (a stream more is a hardware queue shared with somebody, lane_open) */
-static int lane_enable_device_input(Enc *e)
+static int lane_make_twins(Enc *e)
 {
-    if (e->dev_in_on) return QY_OK;
     if (!e->ctx_up) { e->ctx_up = e->ctx_la ? e->ctx_la : main_ctx(e); reg_handle(main_ctx(e), 1); }     /* (lane_close lets go of the registrations of every lane with a ctx_up) */
     const size_t fsz = (size_t)e->W * e->H * 3 / 2;
     int r = KS265_OK;
@@ -3433,9 +3487,26 @@ static int lane_enable_device_input(Enc *e)
         if (!e->in[i].dev) r = ks265_dev_malloc(main_ctx(e), (void **)&e->in[i].dev, fsz);
         if (!r && !e->in[i].ev_up) r = ks265_event_create(e->ctx_up, &e->in[i].ev_up);
     }
-    if (r) return hip_rc(r);
+    return hip_rc(r);
+}
+static int lane_enable_device_input(Enc *e)
+{
+    if (e->dev_in_on) return QY_OK;
+    const int r = lane_make_twins(e);
+    if (r) return r;
     e->dev_in_on = 1;
     return QY_OK;
+}
+/* overlays need the twins too.  A lane that has them all is fine as it is; one that has none may get them only while no picture is in flight: the scheduler thread reads a
+ * slot's twin pointer when it takes the picture, and a picture handed in without a twin has its bytes in pinned memory alone */
+static int lane_twins_missing(const Enc *e) { for (int i = 0; i < e->nin; ++i) if (!e->in[i].dev || !e->in[i].ev_up) return 1; return 0; }
+static int lane_idle(Enc *e)
+{
+    pthread_mutex_lock(&e->mu);
+    int idle = 1;
+    for (int i = 0; i < e->nin; ++i) if (e->in[i].used != IN_FREE && e->in[i].used != IN_ACQUIRED) idle = 0;
+    pthread_mutex_unlock(&e->mu);
+    return idle;
 }
 
 int ks265_enc_enable_device_input(void *h)
@@ -3541,6 +3612,57 @@ int ks265_enc_set_next_roi(void *h, const ks265_roi *roi)
         if (rv) return hip_rc(rv);
     }
     t->roi = *roi; t->roi_set = 1;
+    return QY_OK;
+}
+
+int ks265_enc_set_overlay(void *h, int slot, const ks265_overlay *ov)
+{
+    Top *t = (Top *)h;
+    if (!t) return QY_POINTER;
+    Enc *e0 = t->lane[0];
+    if (!ks265_input_overlay || !ks265_input_overlay_validate) {
+        if (!t->ov_warned) logf_(2, e0->log_level, "ks265enc: overlays are unavailable: the device library has no ks265_input_overlay\n");
+        t->ov_warned = 1;
+        return QY_NOTSUPPORTED;
+    }
+    if (slot < 0 || slot >= KS265_OV_SLOTS) return QY_NOTSUPPORTED;
+    if (!ov) { overlay_drop(t, slot); return QY_OK; }
+    for (int i = 0; i < t->nlanes; ++i) if (t->lane[i]->dev_id != e0->dev_id || t->lane[i]->use_graph) return QY_NOTSUPPORTED;   /* lanes on several GPUs; the graph experiment (a fixed launch sequence) */
+    if ((ov->flags & ~KS265_OV_FORCED_ONLY) || (ov->rgb.device != -1 && ov->rgb.device != e0->dev_id)) return QY_NOTSUPPORTED;
+    if (!ov->rgb.plane[0] || !ov->rgb.plane[1] || !ov->rgb.plane[2]) return QY_POINTER;
+    struct OvSlot n = {.on = 1, .dev = ov->rgb.device >= 0, .forced_only = (ov->flags & KS265_OV_FORCED_ONLY) != 0, .stream = ov->rgb.stream};
+    n.d = (ks265_overlay_desc){.rgb = {.format = ov->rgb.format, .width = ov->width, .height = ov->height, .plane = {ov->rgb.plane[0], ov->rgb.plane[1], ov->rgb.plane[2]}, .pitch = {ov->rgb.pitch[0]},
+                                       .pixel_step = ov->rgb.pixel_step, .matrix = ov->rgb.matrix, .full_range = ov->rgb.full_range}, .alpha = ov->alpha, .x = ov->x, .y = ov->y, .opacity = ov->opacity};
+    if (!n.dev) {
+        /* host memory: the bytes between the lowest channel sample of pixel (0, 0) and the end of the highest one's last row go to the device as they lie, and the description
+         * moves with them.  What is needed to size the copy is judged here; everything else by the device library, on the copy */
+        const int es = ov->rgb.format == KS265_IN_RGB ? 1 : ov->rgb.format == KS265_IN_RGB_F32 ? 4 : ov->rgb.format == KS265_IN_RGB_F16 || ov->rgb.format == KS265_IN_RGB_BF16 ? 2 : 0;
+        if (!es || ov->width < 2 || ov->height < 2 || ov->width > 8192 || ov->height > 8192 || ov->rgb.pixel_step < es || ov->rgb.pixel_step > 64) return QY_NOTSUPPORTED;
+        if ((long long)ov->rgb.pitch[0] < (long long)ov->width * ov->rgb.pixel_step) return QY_POINTER;
+        uintptr_t lo = (uintptr_t)ov->rgb.plane[0], hi = lo;
+        const void *ch[4] = {ov->rgb.plane[0], ov->rgb.plane[1], ov->rgb.plane[2], ov->alpha};
+        for (int k = 1; k < 4; ++k) if (ch[k]) { const uintptr_t q = (uintptr_t)ch[k]; lo = q < lo ? q : lo; hi = q > hi ? q : hi; }
+        if (hi - lo > (uintptr_t)4 * (uintptr_t)ov->rgb.pitch[0] * (uintptr_t)ov->height) return QY_NOTSUPPORTED;   /* (the channels of ONE buffer: at most four planes apart - the copy takes everything between them) */
+        const size_t nb = (size_t)(hi - lo) + (size_t)ov->rgb.pitch[0] * (size_t)(ov->height - 1) + (size_t)(ov->width - 1) * (size_t)ov->rgb.pixel_step + (size_t)es;
+        const size_t skew = lo & 15;                                    /* the copy keeps the address modulo 16: element alignment and the kernel's choice of loads stay */
+        int r = ks265_dev_malloc(main_ctx(e0), &n.own, nb + skew);
+        if (!r) r = ks265_memcpy_h2d_sync(main_ctx(e0), (uint8_t *)n.own + skew, (const void *)lo, nb);
+        if (r) { if (n.own) ks265_dev_free(main_ctx(e0), n.own); return hip_rc(r); }
+        const uint8_t *base = (const uint8_t *)n.own + skew;
+        for (int k = 0; k < 3; ++k) n.d.rgb.plane[k] = base + ((uintptr_t)ch[k] - lo);
+        if (ov->alpha) n.d.alpha = base + ((uintptr_t)ov->alpha - lo);
+    }
+    int r = hip_rc(ks265_input_overlay_validate(main_ctx(e0), &n.d, 1, e0->W, e0->H, e0->srcW, e0->srcH));
+    /* every input slot of every lane needs its twin: made here if the lane has none and no picture is in flight */
+    for (int i = 0; i < t->nlanes && !r; ++i) {
+        Enc *e = t->lane[i];
+        if (!lane_twins_missing(e)) continue;
+        if (!lane_idle(e)) { logf_(2, e->log_level, "ks265enc: the handle's first overlay needs a device twin for every input slot, and pictures are in flight: set it before the first picture, on a zero-latency handle, or after a flush\n"); r = QY_NOTSUPPORTED; }
+        else r = lane_make_twins(e);
+    }
+    if (r) { if (n.own) ks265_dev_free(main_ctx(e0), n.own); return r; }
+    overlay_drop(t, slot);
+    t->ov[slot] = n; ++t->ov_n;
     return QY_OK;
 }
 

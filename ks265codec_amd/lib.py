@@ -89,6 +89,12 @@ class HdrCfg(C.Structure):                    # ks265_hdr_cfg
         return cls(int(gain), int(iters), int(slope), (C.c_int32 * 3)(*[int(r) for r in tuple(radius)[:3]]))
 
 
+class OverlayDesc(C.Structure):               # ks265_overlay_desc
+    _fields_ = [("rgb", InDesc), ("alpha", C.c_void_p), ("x", C.c_int32), ("y", C.c_int32), ("opacity", C.c_int32)]
+
+
+OVERLAY_MAX = 8
+
 IN_I420, IN_NV12, IN_RGB = 0, 1, 2
 IN_RGB_F16, IN_RGB_BF16, IN_RGB_F32 = 16, 17, 18          # RGB as float samples in [0, 1]: plane, pixel_step and pitch stay in bytes
 RGB_ELEM_SIZE = {IN_RGB: 1, IN_RGB_F16: 2, IN_RGB_BF16: 2, IN_RGB_F32: 4}
@@ -140,6 +146,7 @@ EXPORTS = [
     "ks265_input_denoise_validate", "ks265_input_denoise",
     "ks265_input_enhance_validate", "ks265_input_enhance",
     "ks265_input_hdr_validate", "ks265_input_hdr_work_bytes", "ks265_input_hdr",
+    "ks265_input_overlay_validate", "ks265_input_overlay",
 ]
 
 
@@ -527,6 +534,32 @@ class KsContext:
 
     def input_hdr(self, cfg, width: int, height: int, pic, work) -> None:
         self._chk(self.input_hdr_rc(cfg, width, height, pic, work))
+
+    # ---- overlays on the way in (include/ks265_hip.h ks265_input_overlay; tests/overlay_ref.py is its specification)
+    @staticmethod
+    def overlay_descs(overlays):
+        """overlays: a sequence of (fmt, w, h, (R, G, B addresses), alpha address or None, pitch, pixel_step, x, y, opacity, matrix, full_range), everything in bytes; the
+        array of ks265_overlay_desc"""
+        arr = (OverlayDesc * max(1, len(overlays)))()
+        for d, (fmt, w, h, planes, alpha, pitch, step, x, y, opacity, matrix, full_range) in zip(arr, overlays):
+            d.rgb = InDesc(int(fmt), int(w), int(h), (C.c_void_p * 3)(*[int(q) for q in planes]), (C.c_int32 * 3)(int(pitch), 0, 0), int(step), int(matrix), int(bool(full_range)))
+            d.alpha, d.x, d.y, d.opacity = (int(alpha) if alpha else None), int(x), int(y), int(opacity)
+        return arr
+
+    def input_overlay_validate(self, overlays, coded_w: int, coded_h: int, win_w=None, win_h=None, n=None) -> int:
+        """The library's return code (0, KS265_POINTER -3, KS265_NOTSUPPORTED -4): nothing is enqueued"""
+        return int(self.lib.ks265_input_overlay_validate(self.h, self.overlay_descs(overlays), C.c_int(len(overlays) if n is None else n), C.c_int(coded_w), C.c_int(coded_h),
+                                                         C.c_int(coded_w if win_w is None else win_w), C.c_int(coded_h if win_h is None else win_h)))
+
+    def input_overlay_rc(self, overlays, coded_w: int, coded_h: int, pic, win_w=None, win_h=None, n=None) -> int:
+        """one launch on the context's stream: the overlays blended in the order of the sequence onto `pic` (uint8 device tensor or an address, packed I420 of coded_w x
+        coded_h), clipped to the window.  The library's return code"""
+        ptr = lambda x: C.c_void_p(x) if isinstance(x, int) else _p(x)
+        return int(self.lib.ks265_input_overlay(self.h, self.overlay_descs(overlays), C.c_int(len(overlays) if n is None else n), C.c_int(coded_w), C.c_int(coded_h),
+                                                C.c_int(coded_w if win_w is None else win_w), C.c_int(coded_h if win_h is None else win_h), ptr(pic)))
+
+    def input_overlay(self, overlays, coded_w: int, coded_h: int, pic, win_w=None, win_h=None) -> None:
+        self._chk(self.input_overlay_rc(overlays, coded_w, coded_h, pic, win_w, win_h))
 
     def intra_pred(self, ref, dst, blks: np.ndarray):
         """g_IntraPredFunction: predict every described block from dev `ref` into dev `dst` (in place)"""
