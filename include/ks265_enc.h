@@ -412,6 +412,28 @@ typedef struct ks265_overlay {
 #define KS265_OV_FORCED_ONLY 1
 #define KS265_OV_SLOTS 8
 int ks265_enc_set_overlay(void *pEncoder, int slot /* 0 .. 7 */, const ks265_overlay *ov /* NULL clears the slot */);
+/* extension: tone mapping on the way in - HDR10 device pictures (SMPTE ST 2084 "PQ", BT.2020 primaries and matrix; P010, P012, P016, yuv420p10le ...) become the 8-bit SDR
+ * picture the encoder codes, BT.709 in limited range, inside the ONE kernel that reads the source (tests/tonemap_ref.py is the specification of every byte).
+ * Without it such a picture is only rounded to 8 bits, PQ codes and BT.2020 colours as they are.  Call after ks265_enc_enable_device_input and before the first picture.
+ *   transfer       16 = PQ (H.273's code).  Anything else is QY_NOTSUPPORTED: HLG is not built yet
+ *   curve          0 bt2390 (BT.2390's EETF in PQ space: identity below the knee, a Hermite roll-off to the peak), 1 reinhard, 2 clip.  The gain is taken on the largest
+ *                  of R, G and B, so hue is preserved
+ *   full_range     of the SOURCE (the result is always limited range)
+ *   peak_nits      the light that maps to SDR white's top; 0 = 1000; 100 .. 10000.  What the source holds above it is clipped to it
+ *   white_nits     the light that diffuse SDR white (1.0) stands for; 0 = 203 (BT.2408); 80 .. 1000 and at most the peak
+ * From then on ks265_enc_encode_device_frame[_scaled] sends every picture of format KS265_IN_YUV(0 or 1, 0, 10 .. 16, msb) - 4:2:0, planar or semi-planar - through the
+ * tone mapper where it would be converted; the scaled entry maps at the source's size and scales the SDR picture.  A YUV picture of more than 8 bits outside that list
+ * (9 bits, 4:2:2, 4:4:4, packed) is QY_NOTSUPPORTED - never passed through unmapped - and leaves the handle as it was.  8-bit YUV, RGB and host pictures go in as before.
+ * Everything behind the input sees the SDR picture: the vpp_* filters, overlays, lookahead, -psnr / -ssim, `analysis`, `devrecon`.  The filter has no state: any number of GOP
+ * lanes gives the one-lane stream.  The stream's VUI stays the caller's business, as for RGB input.  A handle that never calls this makes not one more call.
+ * QY_NOTSUPPORTED: a call in any other order or a second one, a field out of range, a handle whose size is no multiple of 8 (device input takes 8-bit I420 / NV12 only there),
+ * a device library without the entries (one log line `ks265enc: tone mapping is unavailable: ...`).  The command line has no switch for it: it reads 8-bit host files only. */
+typedef struct ks265_tonemap { int transfer;      /* 16 = PQ (H.273's code); anything else QY_NOTSUPPORTED - HLG is left for later */
+                               int curve;         /* 0 bt2390, 1 reinhard, 2 clip */
+                               int full_range;    /* of the SOURCE */
+                               double peak_nits;  /* 0 = 1000; 100 .. 10000 */
+                               double white_nits; /* 0 = 203 (BT.2408); 80 .. 1000, <= peak */ } ks265_tonemap;
+int ks265_enc_enable_tonemap(void *pEncoder, const ks265_tonemap *tm);
 /* extension: write the reconstruction (I420, display order) to `path` - the reference CLI's `-o`; call between Open and the first picture */
 int ks265_enc_set_recon_file(void *pEncoder, const char *path);
 

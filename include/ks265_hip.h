@@ -282,6 +282,27 @@ typedef struct ks265_overlay_desc { ks265_in_desc rgb; const void *alpha; int32_
 #define KS265_OVERLAY_MAX 8
 int ks265_input_overlay_validate(ks265_ctx *, const ks265_overlay_desc *ov, int n, int coded_w, int coded_h, int win_w, int win_h);
 int ks265_input_overlay(ks265_ctx *, const ks265_overlay_desc *ov, int n /* 1 .. 8 */, int coded_w, int coded_h, int win_w, int win_h, uint8_t *dev_i420);
+/* Tone mapping on the way in (input_tonemap.hip; tests/tonemap_ref.py is the specification of every byte): an HDR10 picture - SMPTE ST 2084 "PQ", BT.2020
+ * primaries and non-constant-luminance matrix - into the packed 8-bit I420 picture at dev_i420 (width x height x 3 / 2 bytes, 16-byte aligned) as BT.709 in limited range,
+ * where ks265_input_convert would only round the samples.  One launch on the context's stream reads the source once where it lies.
+ *   cfg            transfer 16 (H.273's code of PQ; HLG is not built), curve 0 bt2390 (BT.2390's EETF in PQ space) / 1 reinhard / 2 clip, full_range of the SOURCE,
+ *                  peak_nits 100 .. 10000 (what lies above is clipped to it), white_nits 80 .. 1000 and at most the peak (the light that becomes SDR white).  The gain is
+ *                  taken on the largest of R, G, B: hue is preserved.  Anything else: KS265_NOTSUPPORTED
+ *   plan           three tables (host/ks265_tonemap.h) built on the host and put into device memory by ks265_tonemap_plan_create, which returns when they are there; it
+ *                  belongs to the context's device, any context of that device may use it, and ks265_tonemap_plan_destroy wants every call that used it waited for
+ *   src            KS265_IN_YUV(0 or 1, 0, 10 .. 16, msb): planar or semi-planar 4:2:0 - P010, P012, P016, I010.  8 or 9 bits, 4:2:2, 4:4:4, packed, and every format
+ *                  outside the family: KS265_NOTSUPPORTED.  Otherwise judged as ks265_input_validate judges it: even addresses and pitches, width a multiple of 8 and
+ *                  height even (KS265_NOTSUPPORTED), every plane's whole extent inside ONE allocation of the context's device (KS265_POINTER)
+ * A refused call enqueues nothing.  No load leaves [row start, row start + row bytes) of a source row; nothing outside the destination picture is written.
+ * ks265_input_tonemap_validate enqueues nothing and judges plan and source.  ks265_tonemap_plan_tables is a measuring aid (tools/tonemap_bench.py): where the kernel reads
+ * its tables from now on, 0 global memory through the caches, 1 LDS (what a new plan does: the faster) - the bytes are the same. */
+typedef struct ks265_tonemap_cfg { int32_t transfer, curve, full_range; double peak_nits, white_nits; } ks265_tonemap_cfg;
+typedef struct ks265_tonemap_plan ks265_tonemap_plan;
+int ks265_tonemap_plan_create(ks265_ctx *, const ks265_tonemap_cfg *cfg, ks265_tonemap_plan **plan);
+int ks265_tonemap_plan_destroy(ks265_ctx *, ks265_tonemap_plan *plan);
+int ks265_tonemap_plan_tables(ks265_tonemap_plan *plan, int where);
+int ks265_input_tonemap_validate(ks265_ctx *, const ks265_tonemap_plan *plan, const ks265_in_desc *src);
+int ks265_input_tonemap(ks265_ctx *, const ks265_tonemap_plan *plan, const ks265_in_desc *src, uint8_t *dev_i420);
 /* Launch sequences as graphs: between ks265_capture_begin and ks265_capture_end everything enqueued on this context's stream by THIS thread (kernel launches,
  * async memsets of the stage functions) is recorded instead of run (hipStreamBeginCapture, relaxed mode: other threads may go on using the runtime);
  * ks265_capture_end returns an executable graph, ks265_graph_launch enqueues all of it with one runtime call.  A host whose pictures repeat the same

@@ -129,31 +129,7 @@ template <int FMT, int NPIX> __device__ inline void load_rgbf_row(const CvtArgs 
     }
 }
 
-// RGB -> YCbCr of one cell (8 luma columns x the two rows of chroma row i -> 16 Y, 4 Cb, 4 Cr) in three pieces.  c holds a row's samples of SH - 16 fraction bits, columns x0 - 1 .. x0 + 7;
-// the sums are of type A, the luma shifted by SH and the (1, 2, 1) x (1, 1) chroma sums (weight 8) by SH + 3
-template <typename A, int SH> __device__ inline void rgb_store_luma(const CvtArgs &a, int y, int x0, const int (&c)[3][9])
-{
-    const A yoff = ((A)a.oy << SH) + ((A)1 << (SH - 1));
-    uint32_t w[2] = {0, 0};
-#pragma unroll
-    for (int k = 0; k < 8; ++k) w[k >> 2] |= shr_clip255<A>((A)a.cy[0] * c[0][k + 1] + (A)a.cy[1] * c[1][k + 1] + (A)a.cy[2] * c[2][k + 1] + yoff, SH) << 8 * (k & 3);
-    store_words<8>(a.dst + y * (size_t)a.W + x0, w);
-}
-// chroma column x0 / 2 + k of one row and channel, weight 4: luma columns x0 + 2k - 1, x0 + 2k, x0 + 2k + 1 = entries 2k, 2k + 1, 2k + 2.  (Returned by value on purpose: the same sum
-// added inside a function that takes the 3 x 4 accumulator by reference costs the float kernels up to 10 VGPRs and a wave per SIMD)
-__device__ inline int rgb_sum121(const int (&c)[9], int k) { return c[2 * k] + 2 * c[2 * k + 1] + c[2 * k + 2]; }
-template <typename A, int SH> __device__ inline void rgb_store_chroma(const CvtArgs &a, int i, int x0, const int (&s)[3][4])
-{
-    const A rnd = ((A)128 << (SH + 3)) + ((A)1 << (SH + 2));
-    uint32_t u[1] = {0}, v[1] = {0};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        u[0] |= shr_clip255<A>((A)a.cb[0] * s[0][k] + (A)a.cb[1] * s[1][k] + (A)a.cb[2] * s[2][k] + rnd, SH + 3) << 8 * k;
-        v[0] |= shr_clip255<A>((A)a.cr[0] * s[0][k] + (A)a.cr[1] * s[1][k] + (A)a.cr[2] * s[2][k] + rnd, SH + 3) << 8 * k;
-    }
-    store_chroma(a.dst, a.W, a.H, i, x0, u, v);
-}
-
+// (the three pieces of RGB -> YCbCr of one cell - rgb_store_luma, rgb_sum121, rgb_store_chroma - are convert_dev.h's: input_tonemap.hip ends in them too)
 // bytes: 32-bit sums throughout; both rows are loaded before anything is stored
 __global__ __launch_bounds__(256) void rgb_to_i420_kernel(CvtArgs a)
 {

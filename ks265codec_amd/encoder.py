@@ -63,6 +63,13 @@ edges - as a stateless GPU step between the denoiser and the enhancement, for ev
 hdr_sigma_s=V (0 .. 100: the spatial scale in samples), hdr_sigma_r=V (0 .. 100: the range scale in per cent of the 8-bit range); one left out or 0 takes the default 1.0 / 3 /
 20 / 15.  The defaults are untuned choices; chroma is not touched; PSNR is against the filtered picture.
 
+tonemap="bt2390"|"reinhard"|"clip" makes THIS handle tone-map HDR10 planes (`ks265_enc_enable_tonemap`, include/ks265_enc.h; tests/tonemap_ref.py is the specification):
+enc.encode((y, uv), "nv12", depth=10) - a decoder's P010 surface in PQ and BT.2020 - and every other 4:2:0 picture of 10 to 16 bits, "i420" or "nv12", comes out as BT.709 SDR
+in limited range from the one kernel that reads it, where it would otherwise only be rounded to 8 bits.  tonemap_peak=1000.0 (100 .. 10000 nits: the light that still fits),
+tonemap_white=203.0 (80 .. 1000: the light of SDR white), tonemap_full_range=False (of the source).  The gain is taken on the largest of R, G, B, so hue is preserved; with
+scale= the picture is mapped at its own size and scaled as SDR.  Planes of more than 8 bits in 4:2:2 or 4:4:4 raise EncoderError on such a handle: nothing is passed through
+unmapped; uint8 planes and RGB tensors go in as before.  HLG is not built.
+
 enc.set_overlay(slot, tensor, x=0, y=0, opacity=1.0, format="rgba") blends a GPU tensor of RGB plus alpha onto every picture from the next encode() on (`ks265_enc_set_overlay`,
 include/ks265_enc.h; tests/overlay_ref.py is the specification): a logo, captions, a timestamp, a picture in picture.  Eight slots, later slots on top; x, y even, any sign, in the
 encoder's picture, the part outside is clipped.  The tensor is read in place inside every encode(), in the order of torch's stream current at the set call: rewrite it on that
@@ -121,6 +128,15 @@ _OVERLAY_FORMATS = {"rgba": (False, 0, 1, 2, 3), "bgra": (False, 2, 1, 0, 3), "r
                     "rgb_planar": (True, 0, 1, 2, None), "rgba_planar": (True, 0, 1, 2, 3)}
 
 
+class Tonemap(C.Structure):
+    """ks265_tonemap of include/ks265_enc.h"""
+    _fields_ = [("transfer", C.c_int), ("curve", C.c_int), ("full_range", C.c_int), ("peak_nits", C.c_double), ("white_nits", C.c_double)]
+
+
+_TONEMAP_CURVES = {"bt2390": 0, "reinhard": 1, "clip": 2}
+TONEMAP_PQ = 16                                                # H.273's transfer code of SMPTE ST 2084
+
+
 class Roi(C.Structure):
     """ks265_roi of include/ks265_enc.h"""
     _fields_ = [("type", C.c_int), ("log2_block", C.c_int), ("device", C.c_int), ("data", C.c_void_p), ("pitch", C.c_int), ("stream", C.c_void_p)]
@@ -163,6 +179,7 @@ def library() -> C.CDLL:
         _lib.ks265_enc_device_analysis_pending.argtypes = [C.c_void_p]
         _lib.ks265_enc_get_device_analysis.argtypes = [C.c_void_p, C.POINTER(DevAnalysis), C.c_void_p]
         _lib.ks265_enc_enable_device_scale.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        _lib.ks265_enc_enable_tonemap.argtypes = [C.c_void_p, C.POINTER(Tonemap)]
         _lib.ks265_enc_encode_device_frame_scaled.argtypes = [C.c_void_p, C.POINTER(C.POINTER(Nal)), C.POINTER(C.c_int), C.POINTER(DevPicture), C.c_int, C.c_int, C.c_int, C.c_void_p]
     return _lib
 
@@ -370,6 +387,16 @@ class Encoder:
         if scale_from is not None and self._scale is None:
             raise ValueError("scale_from: needs scale=")
         self._ragged = bool(width % 8 or height % 8)            # coded at the next multiple of 8 with a conformance window (ks265_enc.h)
+        tonemap = params.pop("tonemap", None)                   # ks265_enc_enable_tonemap for this handle: HDR10 planes of 10 to 16 bits come out as BT.709 SDR
+        tm_peak, tm_white, tm_full = params.pop("tonemap_peak", 1000.0), params.pop("tonemap_white", 203.0), params.pop("tonemap_full_range", False)
+        if tonemap is not None and tonemap not in _TONEMAP_CURVES:
+            raise ValueError(f"tonemap: one of {sorted(_TONEMAP_CURVES)}")
+        if tonemap is None and (tm_peak, tm_white, bool(tm_full)) != (1000.0, 203.0, False):
+            raise ValueError("tonemap_peak / tonemap_white / tonemap_full_range: need tonemap=")
+        if tonemap is not None and self._ragged:
+            raise ValueError(f"tonemap=: a {width}x{height} encoder (no multiple of 8) takes 8-bit i420 and nv12 pictures only")
+        if tonemap is not None and not (100.0 <= float(tm_peak) <= 10000.0 and 80.0 <= float(tm_white) <= 1000.0 and float(tm_white) <= float(tm_peak)):
+            raise ValueError("tonemap_peak: 100 .. 10000 nits; tonemap_white: 80 .. 1000 nits and at most the peak")
         if self._ragged and self._scale is not None:
             raise ValueError(f"scale=: the scaler writes sizes that are multiples of 8, not {width}x{height}")
         for k, v in (("wdt", width), ("hgt", height), *params.items()):
@@ -400,6 +427,12 @@ class Encoder:
                 self.lib.QY265EncoderClose(self.h)
                 self.h = None
                 raise EncoderError(f"ks265_enc_enable_device_scale({mw}, {mh})", rc)
+        if tonemap is not None:
+            rc = self.lib.ks265_enc_enable_tonemap(self.h, C.byref(Tonemap(TONEMAP_PQ, _TONEMAP_CURVES[tonemap], int(bool(tm_full)), float(tm_peak), float(tm_white))))
+            if rc != QY_OK:
+                self.lib.QY265EncoderClose(self.h)
+                self.h = None
+                raise EncoderError(f"ks265_enc_enable_tonemap({tonemap}, peak {tm_peak}, white {tm_white}): tone mapping is unavailable on this handle (see the log)", rc)
         self._nal, self._nn, self._out, self._pts = C.POINTER(Nal)(), C.c_int(0), Picture(), 0
         self._flushed, self._held, self._next_display = [], {}, 0  # recon(): what flush() fetched call by call; order="display": early pictures by poc, the next index to return
         if self._recon is not None:                             # refused at open (a device library without the way back, lanes on several GPUs, KS265_GRAPH)?  Nothing is pending: QY_FAIL if on

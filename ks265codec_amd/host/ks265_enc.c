@@ -18,6 +18,7 @@
 #include "ks265_recon.h"
 #include "ks265_roi.h"
 #include "ks265_scale.h"
+#include "ks265_tonemap.h"
 #include <dirent.h>
 #include <fcntl.h>
 #include <math.h>
@@ -85,6 +86,12 @@
  * QY_NOTSUPPORTED with one log line */
 #pragma weak ks265_input_overlay_validate
 #pragma weak ks265_input_overlay
+/* tone mapping on the way in (ks265_enc_enable_tonemap) reaches its plan and its kernel the same way: on a device library without them the encoder logs once that tone mapping
+ * is unavailable and the call is QY_NOTSUPPORTED */
+#pragma weak ks265_tonemap_plan_create
+#pragma weak ks265_tonemap_plan_destroy
+#pragma weak ks265_input_tonemap_validate
+#pragma weak ks265_input_tonemap
 
 const char strLibQy265Version[] = "ks265enc 0.2 (MI355X pixel path + host CABAC; API of libqycodec V2.6.1.3)";
 
@@ -551,6 +558,9 @@ typedef struct Enc {
      * it on, stage_enhance reads en_luma whether the denoiser runs or not (the history picture is no longer the luma in front of the enhancement).  Off: no field is touched,
      * nothing is allocated */
     int hdr_on; ks265_hdr_cfg hdr_cfg; size_t hdr_bytes; void *hdr_work;
+    /* ks265_enc_enable_tonemap: a device picture of 10 to 16 bits in 4:2:0 goes through ks265_input_tonemap where ks265_input_convert stands (stage_device), with the lane's
+     * own plan - the tables in device memory, made by the enabling call and destroyed at close.  The filter has no state.  Off: no field is touched, nothing is allocated */
+    int tm_on; ks265_tonemap_plan *tm_plan;
 } Enc;
 
 static ks265_ctx *main_ctx(const Enc *e) { return e->path[PATH_MAIN].ctx; }
@@ -2341,6 +2351,7 @@ static void lane_close(Enc *e, int report)
         if (report) run_summary(e, e->st.frames, e->st.bytes, e->st.sse, e->q_hi, e->q_lo);
         close_devrecon(e);
         if (e->sc_on) close_scale(e);
+        if (e->tm_plan) { (void)ks265_tonemap_plan_destroy(main_ctx(e), e->tm_plan); e->tm_plan = NULL; }
         close_jobs(e); close_inputs(e); close_dpb(e); close_key_path(e); close_anchor_path(e); close_pipeline(e);
         for (int i = 0; i < e->ngraph; ++i) ks265_graph_destroy(main_ctx(e), e->graph[i].exec);
         close_quality(e);
@@ -2698,6 +2709,7 @@ enum { PIC_HOST, PIC_CONVERT, PIC_PAD, PIC_SCALE };
  * library takes them, and the caller's streams the device overlays among them are read in the order of (each once; nst = 0: host overlays only) */
 typedef struct OvSet { int n, nst; ks265_overlay_desc d[KS265_OV_SLOTS]; void *stream[KS265_OV_SLOTS]; } OvSet;
 typedef struct PicIn { int how; long long pts; const QY265YUV *yuv; const ks265_dev_picture *dp; ks265_in_desc d; const struct ScalePlan *sc; const ks265_roi *roi;
+                       int tm;                            /* a device picture that is tone-mapped (ks265_enc_enable_tonemap) where it would be converted; scaled: in front of the scaler */
                        int force_logo; const OvSet *ovs; /* bForceLogo of the call; the overlays or NULL (top_encode) */ } PicIn;
 /* back-pressure on the input side (mu held): at most 16 pictures wait for the scheduler thread (it may itself be waiting for ring space, which only the caller's take_output
  * frees - then go on and collect).  GOP lanes (multi): the input slots are the limit (lane_has_slot) - a lane takes a whole GOP in while it is still coding the previous one, or
@@ -2742,6 +2754,13 @@ static int stage_roi(Enc *e, Input *slot, const ks265_roi *roi)
 static int stage_device(Enc *e, Input *slot, const PicIn *p)
 {
     int r = caller_stream_in(e, p->dp->stream);
+    if (!r && p->tm) {                                                 /* tone-mapped at its own size: into the twin, or into the scaler's way-station picture and scaled from there as I420 */
+        const size_t sn = (size_t)p->d.width * p->d.height;
+        const ks265_in_desc sdr = {.format = KS265_IN_I420, .width = p->d.width, .height = p->d.height, .plane = {e->sc_scratch, e->sc_scratch + sn, e->sc_scratch + sn + sn / 4}, .pitch = {p->d.width, p->d.width / 2, p->d.width / 2}};
+        r = ks265_input_tonemap(e->ctx_up, e->tm_plan, &p->d, p->how == PIC_SCALE ? e->sc_scratch : slot->dev);
+        if (!r && p->how == PIC_SCALE) r = ks265_input_scale(e->ctx_up, p->sc->plan, &sdr, NULL, slot->dev);
+        return r ? r : caller_stream_out(e, p->dp->stream, slot->ev_up);
+    }
     if (!r) r = p->how == PIC_SCALE ? ks265_input_scale(e->ctx_up, p->sc->plan, &p->d, e->sc_scratch, slot->dev)
               : p->how == PIC_PAD ? ks265_input_pad(e->ctx_up, &p->d, e->W, e->H, slot->dev) : ks265_input_convert(e->ctx_up, &p->d, slot->dev);
     return r ? r : caller_stream_out(e, p->dp->stream, slot->ev_up);
@@ -3002,6 +3021,7 @@ typedef struct Top {
      * all lanes share read-only), stream: the caller's, for a device overlay - and the set built from them for the picture being handed in */
     struct OvSlot { int on, dev, forced_only; ks265_overlay_desc d; void *stream; void *own; } ov[KS265_OV_SLOTS];
     int ov_n, ov_warned; OvSet ovs;
+    int tm_warned;                                        /* ks265_enc_enable_tonemap has logged that the device library lacks the entries */
 } Top;
 
 /* `devrecon`: what take_output just moved out of lane e's ring (Enc::taken) joins `dst` - the handle's list: the slots are handed out; a chunk's stash: they go on travelling.
@@ -3576,7 +3596,12 @@ static int resolve_device(Top *t, const ks265_dev_picture *pic, int scaled, int 
     dev_desc(e0, pic, &p->d);
     if (p->how == PIC_SCALE) { p->d.width = sw; p->d.height = sh; }
     if (p->how == PIC_PAD && p->d.format != KS265_IN_I420 && p->d.format != KS265_IN_NV12) return QY_NOTSUPPORTED;   /* a ragged handle pads 8-bit I420 and NV12 only (ks265_enc.h) */
-    int rv = p->how == PIC_PAD ? ks265_input_pad_validate(main_ctx(e0), &p->d, e0->W, e0->H) : ks265_input_validate(main_ctx(e0), &p->d);
+    /* a tone-mapping handle: YUV of more than 8 bits is mapped when it is 4:2:0, planar or semi-planar, of 10 to 16 bits - and refused otherwise, never passed through unmapped */
+    if (e0->tm_on && (p->d.format & ~0x3FF) == 0x1000 && (p->d.format & 31) > 8) {
+        if (!ks265_tm_format_ok(p->d.format >> 8 & 3, p->d.format >> 6 & 3, p->d.format & 31)) return QY_NOTSUPPORTED;
+        p->tm = 1;
+    }
+    int rv = p->tm ? ks265_input_tonemap_validate(main_ctx(e0), e0->tm_plan, &p->d) : p->how == PIC_PAD ? ks265_input_pad_validate(main_ctx(e0), &p->d, e0->W, e0->H) : ks265_input_validate(main_ctx(e0), &p->d);
     if (!rv && p->how == PIC_SCALE) rv = lane_scale_plan(t->lane[top_next_lane(t)], sw, sh, filter, &p->sc);
     e0->st.in_copy_ms += now_ms() - t0;
     return hip_rc(rv);
@@ -3594,6 +3619,29 @@ static int encode_device(void *h, QY265Nal **pNals, int *iNalCount, const ks265_
 }
 int ks265_enc_encode_device_frame(void *h, QY265Nal **pNals, int *iNalCount, const ks265_dev_picture *pic, QY265Picture *out) { return encode_device(h, pNals, iNalCount, pic, 0, 0, 0, 0, out); }
 int ks265_enc_encode_device_frame_scaled(void *h, QY265Nal **pNals, int *iNalCount, const ks265_dev_picture *pic, int src_width, int src_height, int filter, QY265Picture *out) { return encode_device(h, pNals, iNalCount, pic, 1, src_width, src_height, filter, out); }
+
+int ks265_enc_enable_tonemap(void *h, const ks265_tonemap *tm)
+{
+    Top *t = (Top *)h;
+    if (!t || !tm) return QY_POINTER;
+    Enc *e0 = t->lane[0];
+    if (!ks265_tonemap_plan_create || !ks265_tonemap_plan_destroy || !ks265_input_tonemap_validate || !ks265_input_tonemap) {
+        if (!t->tm_warned) logf_(2, e0->log_level, "ks265enc: tone mapping is unavailable: the device library has no ks265_input_tonemap\n");
+        t->tm_warned = 1;
+        return QY_NOTSUPPORTED;
+    }
+    if (!e0->dev_in_on || e0->tm_on) return QY_NOTSUPPORTED;             /* behind ks265_enc_enable_device_input, once */
+    for (int i = 0; i < t->nlanes; ++i) if (t->lane[i]->in_disp) return QY_NOTSUPPORTED;   /* after the first picture */
+    if ((e0->W & 7) || (e0->H & 7) || e0->ragged) return QY_NOTSUPPORTED;  /* a ragged handle takes 8-bit I420 and NV12 only */
+    const ks265_tonemap_cfg cfg = {tm->transfer, tm->curve, tm->full_range, tm->peak_nits == 0.0 ? 1000.0 : tm->peak_nits, tm->white_nits == 0.0 ? 203.0 : tm->white_nits};
+    if (!ks265_tm_cfg_ok(cfg.transfer, cfg.curve, cfg.peak_nits, cfg.white_nits) || (cfg.full_range != 0 && cfg.full_range != 1)) return QY_NOTSUPPORTED;
+    for (int i = 0; i < t->nlanes; ++i) {
+        const int r = ks265_tonemap_plan_create(main_ctx(t->lane[i]), &cfg, &t->lane[i]->tm_plan);
+        if (r) { for (int k = 0; k < i; ++k) { (void)ks265_tonemap_plan_destroy(main_ctx(t->lane[k]), t->lane[k]->tm_plan); t->lane[k]->tm_plan = NULL; } return hip_rc(r); }
+    }
+    for (int i = 0; i < t->nlanes; ++i) t->lane[i]->tm_on = 1;
+    return QY_OK;
+}
 
 int ks265_enc_set_next_roi(void *h, const ks265_roi *roi)
 {

@@ -95,6 +95,14 @@ class OverlayDesc(C.Structure):               # ks265_overlay_desc
 
 OVERLAY_MAX = 8
 
+
+class TonemapCfg(C.Structure):                # ks265_tonemap_cfg
+    _fields_ = [("transfer", C.c_int32), ("curve", C.c_int32), ("full_range", C.c_int32), ("peak_nits", C.c_double), ("white_nits", C.c_double)]
+
+
+TONEMAP_PQ = 16                                           # H.273's transfer code of SMPTE ST 2084
+TONEMAP_CURVES = {"bt2390": 0, "reinhard": 1, "clip": 2}
+
 IN_I420, IN_NV12, IN_RGB = 0, 1, 2
 IN_RGB_F16, IN_RGB_BF16, IN_RGB_F32 = 16, 17, 18          # RGB as float samples in [0, 1]: plane, pixel_step and pitch stay in bytes
 RGB_ELEM_SIZE = {IN_RGB: 1, IN_RGB_F16: 2, IN_RGB_BF16: 2, IN_RGB_F32: 4}
@@ -147,6 +155,7 @@ EXPORTS = [
     "ks265_input_enhance_validate", "ks265_input_enhance",
     "ks265_input_hdr_validate", "ks265_input_hdr_work_bytes", "ks265_input_hdr",
     "ks265_input_overlay_validate", "ks265_input_overlay",
+    "ks265_tonemap_plan_create", "ks265_tonemap_plan_destroy", "ks265_tonemap_plan_tables", "ks265_input_tonemap_validate", "ks265_input_tonemap",
 ]
 
 
@@ -560,6 +569,36 @@ class KsContext:
 
     def input_overlay(self, overlays, coded_w: int, coded_h: int, pic, win_w=None, win_h=None) -> None:
         self._chk(self.input_overlay_rc(overlays, coded_w, coded_h, pic, win_w, win_h))
+
+    # ---- tone mapping on the way in (include/ks265_hip.h ks265_input_tonemap; tests/tonemap_ref.py is its specification)
+    def tonemap_plan_create_rc(self, curve: int = 0, peak: float = 1000.0, white: float = 203.0, full_range: bool = False, transfer: int = TONEMAP_PQ):
+        """(the library's return code, the plan or None): the tables of one configuration in device memory"""
+        plan = C.c_void_p()
+        rc = int(self.lib.ks265_tonemap_plan_create(self.h, C.byref(TonemapCfg(int(transfer), int(curve), int(full_range), float(peak), float(white))), C.byref(plan)))
+        return rc, (plan if rc == 0 else None)
+
+    def tonemap_plan_create(self, curve: int = 0, peak: float = 1000.0, white: float = 203.0, full_range: bool = False):
+        rc, plan = self.tonemap_plan_create_rc(curve, peak, white, full_range)
+        self._chk(rc)
+        return plan
+
+    def tonemap_plan_destroy(self, plan) -> None:
+        self._chk(self.lib.ks265_tonemap_plan_destroy(self.h, plan))
+
+    def tonemap_plan_tables(self, plan, where: int) -> None:
+        """a measuring aid: the kernel gathers from global memory (0) or from LDS (1, what a new plan does); the bytes are the same"""
+        self._chk(self.lib.ks265_tonemap_plan_tables(plan, C.c_int(where)))
+
+    def input_tonemap_validate(self, plan, desc: InDesc) -> int:
+        """The library's return code (0, KS265_POINTER -3, KS265_NOTSUPPORTED -4): nothing is enqueued"""
+        return int(self.lib.ks265_input_tonemap_validate(self.h, plan, C.byref(desc)))
+
+    def input_tonemap_rc(self, plan, desc: InDesc, dst) -> int:
+        """one launch on the context's stream: the HDR10 picture `desc` describes into the packed I420 picture at `dst` (uint8 device tensor or an address)"""
+        return int(self.lib.ks265_input_tonemap(self.h, plan, C.byref(desc), C.c_void_p(dst) if isinstance(dst, int) else _p(dst)))
+
+    def input_tonemap(self, plan, desc: InDesc, dst) -> None:
+        self._chk(self.input_tonemap_rc(plan, desc, dst))
 
     def intra_pred(self, ref, dst, blks: np.ndarray):
         """g_IntraPredFunction: predict every described block from dev `ref` into dev `dst` (in place)"""
